@@ -28,10 +28,6 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
-# A process that drives several sessions (a batch's workers in threads, this file's two-session leg) has 6+ HIP streams; the runtime maps them onto 4 hardware queues by
-# default and streams that share one serialise.  Has to be in the environment before the HIP runtime starts: hence here, in front of torch.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 
 ROOT = Path(__file__).resolve().parent
@@ -248,6 +244,36 @@ def verify_stream(packets, headers, cfg, clip, stats, limit=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ output dump (--dump-outputs)
+DUMP_BUDGET = 64 << 20          # bytes of .npy data in all
+
+
+def dump_outputs(out_dir, packets, headers, stats, psnr):
+    """What one timed step hands its caller: the packets (bytes, pts, key flag), the parameter sets and the session's statistics, as .npy files:
+    float64 for the small arrays, float32 for the stream bytes, which are stored whole while they fit the budget, else a fixed sample (positions
+    drawn with seed 0, sorted)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    sizes = np.array([len(p[0]) for p in packets], dtype=np.float64)
+    arrays = {
+        "packet_sizes": sizes,
+        "packet_pts": np.array([p[1] for p in packets], dtype=np.float64),
+        "packet_keyframe": np.array([1.0 if p[2] else 0.0 for p in packets], dtype=np.float64),
+        "headers": np.frombuffer(headers, dtype=np.uint8).astype(np.float64),
+        "stats": np.array([stats.frames_in, stats.frames_out, stats.bytes_out, stats.sse_y, stats.sse_u, stats.sse_v, stats.last_qp, psnr], dtype=np.float64),
+    }
+    stream = np.frombuffer(b"".join(p[0] for p in packets), dtype=np.uint8)
+    room = (DUMP_BUDGET - sum(a.nbytes for a in arrays.values()) - (1 << 20)) // (4 + 8)     # float32 bytes + float64 positions, 1 MB for .npy headers
+    if stream.size <= room:
+        arrays["stream_bytes"] = stream.astype(np.float32)
+    else:
+        pos = np.sort(np.random.default_rng(0).choice(stream.size, size=room, replace=False))
+        arrays["stream_sample_positions"] = pos.astype(np.float64)
+        arrays["stream_sample_bytes"] = stream[pos].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(d / (name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ rank launcher
 def free_port():
     with socket.socket() as s:
@@ -344,10 +370,14 @@ def main():
     ap.add_argument("--host-threads", type=int, default=0, help="CABAC worker threads (0 = library default)")
     ap.add_argument("--qp", type=int, default=-1, help="experiments only: force the P-picture QP instead of deriving it from the CRF")
     ap.add_argument("--profile-stages", type=int, default=2, help="HIP events in the timed steps: 2 = around the dominant kernel (inter_ctu) only, 1 = every stage, 0 = none")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0) as DIR/<name>.npy, for output-for-output comparison of two builds")
     ap.add_argument("--stub", action="store_true", help="tests only: no GPU, no encoder — exercises the rank spawn / rendezvous / JSON path (tests/test_bench_ranks.py)")
     for name in ("intra-nxn", "intra-tiles", "pre-search", "rdo-zero", "intra-in-p", "chroma-modes", "gop-balance", "scenecut", "rdo-cg", "gops-in-flight"):
         ap.add_argument("--" + name, type=int, default=None, help="experiments only: override cfg." + name.replace("-", "_"))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)                        # never returns
@@ -501,6 +531,8 @@ def main():
     dt = max(dts)
     own = ranks.gather(own)
     st, nbytes, psnr, hdrs = last
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, kept, hdrs, st, psnr)
 
     # ---- untimed legs ----
     if rank == 0 and args.profile_stages != 1:       # one more step with every stage bracketed: the per-stage table (events cost ~5 % fps)

@@ -5,6 +5,7 @@ rank before any GPU call, the gloo rendezvous on 127.0.0.1 (no RCCL: nothing is 
 timing, rank 0 printing ONE JSON line with n_gpus = N and the per-rank rates — both when bench.py spawns the ranks itself and when
 the driver starts them with torch.distributed.run."""
 import json
+import os
 import socket
 import subprocess
 import sys
@@ -47,11 +48,19 @@ def test_bench_under_the_drivers_launcher():
     assert out["n_gpus"] == 2 and len(out["per_rank_fps"]) == 2
 
 
+def _bench_with_devices(visible, *args):
+    """bench.py in a child that sees `visible` devices: HIP_VISIBLE_DEVICES picks among the devices this process was given ("0" = the first
+    one, "-1" = none), whatever the host has"""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES=visible)
+    env.pop("MIHEVC_BENCH_SHARE_GPU", None)
+    return subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True, timeout=300, env=env)
+
+
 def test_bench_refuses_more_ranks_than_devices():
-    """no MI355X in this container: --gpus 2 must fail loudly before anything is spawned (and N = 1 must refuse to run without a GPU)"""
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=300)
+    """at most one MI355X visible: --gpus 2 must fail loudly before anything is spawned; none visible: N = 1 must refuse to run"""
+    p = _bench_with_devices("0", "--gpus", "2", "--steps", "1", "--warmup", "0")
     assert p.returncode != 0 and "MI355X visible" in p.stderr
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=300)
+    p = _bench_with_devices("-1", "--steps", "1", "--warmup", "0")
     assert p.returncode != 0 and "no CPU fallback" in p.stderr
 
 
