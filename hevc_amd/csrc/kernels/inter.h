@@ -52,7 +52,8 @@ DEVCONST int8_t kOff[9][2] = {{0, 0}, {-1, -1}, {0, -1}, {1, -1}, {-1, 0}, {1, 0
 DEVCONST int8_t kRingSlot[8] = {4, 5, 2, 7, 1, 3, 6, 8};
 
 // ------------------------------------------------------------------------------------------ search centres (pre-search)
-// 1/4-size 8-bit pictures (rounded mean of every 4x4 luma block, reduced to 8 bits) of the source and of the reference; every
+// 1/4-size 8-bit pictures (rounded mean of every 4x4 luma block, reduced to 8 bits; at 10 bit a mean of 1022 or more rounds to 256 and
+// saturates to 255) of the source and of the reference; every
 // CTU's 8x8 low-resolution block is searched over +-PRE_RANGE with clamped reads: cost = 4 * SAD + |dx| + |dy|, ties -> raster
 // order (oracle: orc_pre_search).  One lane = four horizontal positions (v_qsad_pk_u16_u8), 8 quads x 29 rows = 232 lanes.
 template <typename T> struct PreArgs {
@@ -77,7 +78,8 @@ template <typename T> DEV void lowres_sample(const PreArgs<T> &a, int i)
         } else
             s += (int)row[0] + (int)row[1] + (int)row[2] + (int)row[3];
     }
-    (i < n ? a.lsrc : a.lref)[k] = (uint8_t)(s >> (4 + sh));
+    s >>= 4 + sh;
+    (i < n ? a.lsrc : a.lref)[k] = (uint8_t)(s < 255 ? s : 255);
 }
 constexpr int PRE_SPAN = 2 * PRE_RANGE + 1;      // 29 positions per axis
 constexpr int PRE_WIN_W = 40;                    // columns a lane's 12-byte reads can touch: 8 quads x 4 + 8

@@ -654,7 +654,8 @@ static void node_geom(int node, int *x, int *y, int *log2n)
 /* ---- search centres from the 1/4-size pictures ------------------------------------------------------------------
  * The integer search covers +-me_range around a per-CTU centre.  With pre_search the centre comes from a full search of
  * +-ORC_PRE_RANGE low-resolution samples (+-56 luma samples) of the CTU's 8x8 low-resolution block: cost = 4 * SAD + |dx| + |dy|
- * (a slight pull towards zero), ties -> first position in raster order; samples outside the low-resolution picture clamp. */
+ * (a slight pull towards zero), ties -> first position in raster order; samples outside the low-resolution picture clamp.
+ * A low-resolution sample is the rounded mean of a 4x4 luma block in 8 bits (saturated: the device keeps these pictures as bytes). */
 #define ORC_PRE_RANGE 14
 void orc_lowres(const pix *src, int stride, int w, int h, int bit_depth, pix *dst)
 {
@@ -664,7 +665,8 @@ void orc_lowres(const pix *src, int stride, int w, int h, int bit_depth, pix *ds
             int s = 8 << sh;
             for (int j = 0; j < 4; j++)
                 for (int i = 0; i < 4; i++) s += src[(4 * y + j) * stride + 4 * x + i];
-            dst[y * lw + x] = (pix)(s >> (4 + sh));
+            s >>= 4 + sh;
+            dst[y * lw + x] = (pix)(s < 255 ? s : 255);      /* 8 bits: at 10 bit a mean of 1022 or more would round to 256 */
         }
 }
 void orc_pre_search(const pix *lsrc, const pix *lref, int lw, int lh, int16_t *centers) { orc_pre_search_cost(lsrc, lref, lw, lh, centers, NULL); }

@@ -1,5 +1,7 @@
 """Randomised end-to-end check on a GPU box: random geometry / bit depth / GOP structure / analysis knobs / rate control, every stream must
-decode (oracle decoder) to the encoder's own reconstruction.  Usage: python tests/fuzz_sessions.py [iterations] [seed]"""
+decode (oracle decoder) to the encoder's own reconstruction.  Usage: python tests/fuzz_sessions.py [iterations] [seed] [large] [envelope]
+"envelope" (opt in): fixed QPs drawn from 0..51 instead of 10..44, and content drawn from synth / full_range / rails (tests/util.envelope_frame).
+Without it the generator draws exactly as before, so earlier seeds reproduce."""
 import os
 import sys
 from pathlib import Path
@@ -18,13 +20,16 @@ try:                       # the device-frame cases hold their planes in torch t
 except Exception:          # noqa: BLE001
     torch = None
 LARGE = False     # third argument "large": pictures up to 2160p, longer clips (several chunks)
+ENVELOPE = False  # argument "envelope": the whole QP range and content at the ends of the sample range
 
 
-def run(iters, seed, verbose=True, large=None):
+def run(iters, seed, verbose=True, large=None, envelope=None):
     """returns the descriptions of the failing cases"""
-    global LARGE
+    global LARGE, ENVELOPE
     if large is not None:
         LARGE = large
+    if envelope is not None:
+        ENVELOPE = envelope
     rng = np.random.default_rng(seed)
     failed = []
     for it in range(iters):
@@ -60,18 +65,23 @@ def one_case(rng, it):
         cfg.bframes = int(rng.choice([0, 0, 1, -1]))          # round 3: B pictures (fixed / decided by the probe), P pictures as tiles (forced: at least 2 x 2 where the level allows)
         cfg.p_tiles = int(rng.choice([-1, 0, 1]))
         if rng.random() < 0.5:
-            cfg.qp = int(rng.integers(10, 45))
+            cfg.qp = int(rng.integers(0, 52)) if ENVELOPE else int(rng.integers(10, 45))
         else:
             cfg.crf, cfg.qp = int(rng.integers(14, 30)), -1
             cfg.vbv_maxrate_kbps = int(rng.integers(50, 4000)); cfg.vbv_bufsize_kbits = int(cfg.vbv_maxrate_kbps * 1.2)
         cw, ch = (w + 7) & ~7, (h + 7) & ~7
         detail = min(cw, ch) >= 64
+        content = str(rng.choice(["synth", *util.ENVELOPE_KINDS])) if ENVELOPE else "synth"        # (no draw without ENVELOPE)
         frames = []
         for i in range(n):
-            f = util.synth_frame(ch, cw, seed=int(rng.integers(0, 1000)) if rng.random() < 0.15 else 7, shift=(int(rng.integers(-3, 4)) * i, i), bit_depth=bd, detail=detail)
+            fseed, shift = int(rng.integers(0, 1000)) if rng.random() < 0.15 else 7, (int(rng.integers(-3, 4)) * i, i)
+            if content == "synth":
+                f = util.synth_frame(ch, cw, seed=fseed, shift=shift, bit_depth=bd, detail=detail)
+            else:
+                f = util.envelope_frame(content, ch, cw, bd, seed=fseed, shift=shift)
             frames.append((f.y[:h, :w].copy(), f.u[:h // 2, :w // 2].copy(), f.v[:h // 2, :w // 2].copy()))
         dev_path, extra_y, extra_c = bool(rng.random() < 0.3) and torch is not None, int(rng.integers(0, 9)), int(rng.integers(0, 5))
-        desc = f"#{it} {'dev ' if dev_path else ''}{w}x{h} bd{bd} keyint{keyint} lanes{lanes} n{n} qp{cfg.qp} crf{cfg.crf} vbv{cfg.vbv_maxrate_kbps} R{cfg.me_range} lvl{cfg.level_idc} " \
+        desc = f"#{it} {'dev ' if dev_path else ''}{'' if content == 'synth' else content + ' '}{w}x{h} bd{bd} keyint{keyint} lanes{lanes} n{n} qp{cfg.qp} crf{cfg.crf} vbv{cfg.vbv_maxrate_kbps} R{cfg.me_range} lvl{cfg.level_idc} " \
                f"nxn{cfg.intra_nxn} ip{cfg.intra_in_p} cm{cfg.chroma_modes} rz{cfg.rdo_zero} cg{cfg.rdo_cg} ps{cfg.pre_search} tiles{cfg.intra_tiles} sao{cfg.sao} aud{cfg.aud} hrd{cfg.hrd} b{cfg.bframes} pt{cfg.p_tiles}"
         only = os.environ.get("FUZZ_ONLY")               # "23,27": run just these cases (the generator still draws every case)
         if only and it not in [int(x) for x in only.split(",")]:
@@ -117,7 +127,8 @@ def one_case(rng, it):
 
 if __name__ == "__main__":
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    LARGE = len(sys.argv) > 3 and sys.argv[3] == "large"
+    LARGE = "large" in sys.argv[3:]
+    ENVELOPE = "envelope" in sys.argv[3:]
     bad = run(iters, int(sys.argv[2]) if len(sys.argv) > 2 else 1)
     print(f"{iters - len(bad)}/{iters} passed")
     sys.exit(1 if bad else 0)

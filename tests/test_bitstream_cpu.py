@@ -23,7 +23,7 @@ def encode_pictures(cfg, srcs, qp, bd, me_range=8, keyint=1000, nxn=0, intra_in_
     prm_i.intra_nxn = prm_p.intra_nxn = nxn
     prm_p.intra_in_p = intra_in_p
     prm_p.tile_cols, prm_p.tile_rows = _lib.p_tile_grid(cfg)   # P pictures: PPS 0's own grid (cfg.p_tiles), which the intra second pass must respect
-    cus = []
+    cus, analyses = [], []
     for i, src in enumerate(srcs):
         intra = i % keyint == 0
         prm = prm_i if intra else prm_p
@@ -35,6 +35,7 @@ def encode_pictures(cfg, srcs, qp, bd, me_range=8, keyint=1000, nxn=0, intra_in_
         assert n > 0, n
         packets.append((bytes(buf[:n]), i, intra))
         cus.append(a.cu)
+        analyses.append(a)
         pkt = packets[-1][0]
         if i == 0:          # parameter sets belong to the first access unit, after its AUD when there is one (7.4.2.4.4)
             cut = pkt.index(b"\0\0\0\1", 4) if cfg.aud else 0
@@ -42,6 +43,7 @@ def encode_pictures(cfg, srcs, qp, bd, me_range=8, keyint=1000, nxn=0, intra_in_
         stream += pkt
         recs.append(ref)
     encode_pictures.last_cus = cus
+    encode_pictures.last_analyses = analyses
     return headers, stream, recs, packets
 
 
@@ -53,16 +55,42 @@ def make_cfg(w, h, bd=8, **kw):
     return cfg
 
 
-@pytest.mark.parametrize("w,h,qp,bd,n,keyint", [(64, 64, 30, 8, 3, 100), (96, 80, 20, 8, 4, 2), (136, 72, 36, 8, 3, 100), (72, 104, 26, 10, 3, 100),
-                                                 (160, 96, 12, 8, 2, 100)])
-def test_stream_decodes_to_the_oracle_reconstruction(w, h, qp, bd, n, keyint):
+def flashing_clip(w, h, bd, n, seed=11):
+    """full-range pictures (util.envelope_frame) in which a flat 48x48 square at (24, 24) flips between 0 and 2^bd - 1 from picture to picture:
+    the inter residual there is +-(2^bd - 1) over a whole 32x32 CU, whose DC level at QP 0 is about 13000 (long coeff_abs_level_remaining escapes)
+    and whose scaled level at QP 51 meets the 16-bit clip"""
+    out = []
+    for i in range(n):
+        f = util.envelope_frame("full_range", h, w, bd, seed, shift=(3 * i, i))
+        f.y[24:72, 24:72] = ((1 << bd) - 1) * (i % 2)
+        out.append(f)
+    return out
+
+
+STREAM_CASES = [(64, 64, 30, 8, 3, 100), (96, 80, 20, 8, 4, 2), (136, 72, 36, 8, 3, 100), (72, 104, 26, 10, 3, 100), (160, 96, 12, 8, 2, 100)]
+ENVELOPE_STREAM_CASES = [(96, 80, 0, 8, 3, 100), (96, 80, 51, 8, 3, 100), (72, 104, 0, 10, 3, 100), (72, 104, 51, 10, 3, 100)]
+
+
+@pytest.mark.parametrize("w,h,qp,bd,n,keyint,content", [pytest.param(*c, "synth", id="-".join(map(str, c))) for c in STREAM_CASES] +
+                         [pytest.param(*c, "full_range", id="-".join(map(str, c + ("full_range",)))) for c in ENVELOPE_STREAM_CASES])
+def test_stream_decodes_to_the_oracle_reconstruction(w, h, qp, bd, n, keyint, content):
+    """full_range cases: QP 0 and 51 (the I picture at max(0, qp - 3)), samples at both ends in every source and reconstructed plane, levels
+    of at least 4000 at QP 0"""
     cfg = make_cfg(w, h, bd, aud=1)
-    srcs = [util.synth_frame(h, w, seed=11, shift=(3 * i, i), bit_depth=bd) for i in range(n)]
+    if content == "synth":
+        srcs = [util.synth_frame(h, w, seed=11, shift=(3 * i, i), bit_depth=bd) for i in range(n)]
+    else:
+        srcs = flashing_clip(w, h, bd, n)
     _, stream, recs, _ = encode_pictures(cfg, srcs, qp, bd, keyint=keyint)
     frames, info = O.decode(stream)
     assert len(frames) == n and info["count.aud"] == n and info["bit_depth"] == bd
     for i, (f, r) in enumerate(zip(frames, recs)):
         assert f.same(r), f"picture {i} differs after decode"
+    if content != "synth":
+        for i, (src, r) in enumerate(zip(srcs, recs)):
+            assert util.reaches_both_ends(src, bd, 0.01) and util.reaches_both_ends(r, bd), f"picture {i} misses an end of the range"
+        if qp == 0:
+            assert max(int(np.abs(a.coef_y).max()) for a in encode_pictures.last_analyses) >= 4000
 
 
 @pytest.mark.parametrize("w,h,level,grid,qp,bd", [(512, 128, 120, (2, 2), 30, 8), (544, 160, 120, (2, 2), 24, 8), (800, 224, 93, (3, 3), 34, 8),

@@ -287,3 +287,56 @@ def test_stress_clip_zoom_fades_flash_and_cut(lib):
     psnr = [util.psnr(r.y[:h, :w], s[0]) for r, s in zip(recs, src)]
     assert min(psnr[:n // 4] + psnr[n // 4 + 1:]) > 22.0 and np.mean(psnr) > 27.0, (min(psnr), float(np.mean(psnr)))      # 294 kb/s for zooming 640x352: sanity, not a quality claim (measured 25.9 / 29.5 dB)
     assert min(qps) >= crf - 1
+
+
+@pytest.mark.parametrize("w,h,bd,qp,bframes", [(96, 80, 8, 0, 0), (72, 104, 10, 0, 1), (96, 80, 8, 51, 1), (72, 104, 10, 51, 0)])
+def test_sessions_at_the_ends_of_the_qp_range_on_full_range_content(lib, w, h, bd, qp, bframes):
+    """cfg.qp 0 and 51 on full-range pictures (tests/test_bitstream_cpu.flashing_clip: samples at 0 and 2^bd - 1 in every plane, a 32x32 block
+    whose inter residual is +-(2^bd - 1)): the stream decodes to the session's reconstruction, and the oracle pipeline replayed with the session's
+    QPs gives the same pictures.  Keyint 3, seven pictures; B pictures in one case per QP."""
+    from hevc_amd import _lib
+    from tests.test_bitstream_cpu import flashing_clip
+    from tests.test_gpu_bframes import replay as replay_b, run_b_session
+    cfg = _lib.default_config()
+    cfg.width, cfg.height, cfg.bit_depth, cfg.keyint, cfg.min_keyint, cfg.me_range, cfg.gops_in_flight, cfg.qp = w, h, bd, 3, 2, 8, 2, qp
+    cfg.bframes, cfg.scenecut = bframes, 0
+    n = 7
+    frames = flashing_clip(w, h, bd, n)
+    pk, infos, recs, st = run_b_session(cfg, frames, bd)
+    assert st.frames_out == n
+    qps = [q for q, _, _ in infos]
+    assert (min(qps), max(qps)) == ((0, 2 if bframes else 0) if qp == 0 else (48, 51)), qps
+    assert any(t == 0 for _, t, _ in infos) == bool(bframes)
+    for i in range(n):
+        assert util.reaches_both_ends(frames[i], bd, 0.01) and util.reaches_both_ends(recs[i], bd), f"picture {i} misses an end of the range"
+    dec, _ = O.decode(b"".join(p[0] for p in pk))
+    assert len(dec) == n
+    for i in range(n):
+        assert dec[i].same(recs[i]), f"display picture {i}: decoded picture != encoder reconstruction"
+    if bframes:
+        replay_b(lib, cfg, frames, infos, recs)
+    else:
+        replay(lib, cfg, [(None, f) for f in frames], infos, recs, n)
+
+
+@pytest.mark.parametrize("w,h,bd", [(96, 80, 8), (72, 104, 10)])
+def test_rate_control_reaches_qp_51_under_a_tight_vbv_cap(lib, w, h, bd):
+    """a VBV cap far below what full-range content needs drives the rate control to QP 51 (csrc/session.cpp: the IDR search and decide_p
+    stop there); the stream still decodes to the session's reconstruction and the oracle pipeline with the session's QPs reproduces it"""
+    from hevc_amd import _lib
+    from tests.test_bitstream_cpu import flashing_clip
+    cfg = _lib.default_config()
+    cfg.width, cfg.height, cfg.bit_depth, cfg.keyint, cfg.min_keyint, cfg.me_range, cfg.gops_in_flight = w, h, bd, 5, 2, 8, 2
+    cfg.crf, cfg.qp, cfg.vbv_maxrate_kbps, cfg.vbv_bufsize_kbits, cfg.scenecut = 20, -1, 8, 10, 0
+    n = 10
+    clip = flashing_clip(w, h, bd, n)
+    frames = [(util.planes(f, bd), f) for f in clip]
+    stream, sizes, infos, recs, st = run_session(cfg, frames)
+    assert st.frames_out == n
+    assert max(q for q, _, _ in infos) == 51, [q for q, _, _ in infos]
+    dec, _ = O.decode(stream)
+    assert len(dec) == n
+    for i in range(n):
+        assert dec[i].same(recs[i]), f"picture {i}: decoded picture != encoder reconstruction"
+        assert util.reaches_both_ends(recs[i], bd), f"picture {i} misses an end of the range"
+    replay(lib, cfg, frames, infos, recs, n)

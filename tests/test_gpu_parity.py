@@ -31,8 +31,12 @@ def lib_params(lib, qp, bd, rng):
 
 
 @pytest.mark.parametrize("log2n,dst", [(2, 0), (2, 1), (3, 0), (4, 0), (5, 0)])
-@pytest.mark.parametrize("qp,bd,intra", [(22, 8, 1), (37, 8, 0), (27, 10, 1)])
+@pytest.mark.parametrize("qp,bd,intra", [(22, 8, 1), (37, 8, 0), (27, 10, 1), (32, 10, 0)])
 def test_k3_transform_quant_roundtrip(lib, log2n, dst, qp, bd, intra):
+    """random residuals at `qp` against the oracle; then, at every QP 0..51, the random and the adversarial residuals (+-amp DC, basis sign
+    patterns, checkerboards, corner impulses, random +-amp, dead-zone edges) against the numpy integer reference of test_transform_reference.py
+    (which the CPU suite checks against the oracle at every QP)"""
+    from tests.test_transform_reference import adversarial_residuals, dead_zone_residuals, reference
     n = 1 << log2n
     rng = np.random.default_rng(log2n * 100 + qp)
     nb = 70
@@ -51,6 +55,14 @@ def test_k3_transform_quant_roundtrip(lib, log2n, dst, qp, bd, intra):
         assert np.array_equal(lv[b], want_l), (b, log2n)
         assert np.array_equal(rc[b], want_r), (b, log2n)
     assert not lv[0].any() and not rc[0].any()
+    base = np.concatenate([res.astype(np.int64), adversarial_residuals(log2n, bd, bool(dst))])
+    for q in range(52):
+        blocks = np.ascontiguousarray(np.concatenate([base, dead_zone_residuals(log2n, q, bd, intra)]).astype(np.int16))
+        want_l, want_r = reference(blocks, log2n, q, bd, intra, bool(dst))
+        lv, rc = np.zeros_like(blocks), np.zeros_like(blocks)
+        assert lib.mihevc_k_transform(0, util.ptr(blocks), util.ptr(lv), util.ptr(rc), len(blocks), log2n, q, bd, intra, dst) == 0
+        assert np.array_equal(lv, want_l), f"levels at qp {q}: blocks {np.nonzero((lv != want_l).any(axis=(1, 2)))[0][:8]}"
+        assert np.array_equal(rc, want_r), f"reconstruction at qp {q}: blocks {np.nonzero((rc != want_r).any(axis=(1, 2)))[0][:8]}"
 
 
 CASES = [
@@ -63,16 +75,24 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("w,h,qp,bd,rng", CASES)
-def test_stage_parity_i_p_p(lib, api, w, h, qp, bd, rng):
-    """K2+K3 (intra), K1+K3 (inter), K4a (deblock), K4b (SAO) each against the oracle on the same inputs."""
-    prm_i, cp_i = lib_params(lib, max(0, qp - 3), bd, rng)
+# + the ends of the QP range on content at the ends of the sample range (util.ENVELOPE_STAGE_CASES); the synth cases keep their ids
+STAGE_CASES = [pytest.param(*c, "synth", id="-".join(map(str, c))) for c in CASES] + [pytest.param(*c, id="-".join(map(str, c))) for c in util.ENVELOPE_STAGE_CASES]
+
+
+@pytest.mark.parametrize("w,h,qp,bd,rng,content", STAGE_CASES)
+def test_stage_parity_i_p_p(lib, api, w, h, qp, bd, rng, content):
+    """K2+K3 (intra), K1+K3 (inter), K4a (deblock), K4b (SAO) each against the oracle on the same inputs.  Envelope content: the I picture at
+    the case's QP too."""
+    prm_i, cp_i = lib_params(lib, max(0, qp - 3) if content == "synth" else qp, bd, rng)
     prm_p, cp_p = lib_params(lib, qp, bd, rng)
     prm_p.rdo_zero = cp_p.rdo_zero = int(qp >= 24)       # RD zero-out of inter TUs on for the higher QPs, off for the rest
     prm_p.rdo_cg = cp_p.rdo_cg = 5 if 22 <= qp <= 30 else 0   # RD zero-out of 4x4 coefficient groups at the session's default strength / off
     prm_i.chroma_modes = cp_i.chroma_modes = int(qp < 35)  # chroma intra mode decision
-    srcs = [util.synth_frame(h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(3)]
+    prm_p.pre_search = cp_p.pre_search = int(content != "synth")   # envelope content: centres from the device's own 1/4-size pictures (8-bit samples at 10 bit)
+    srcs = [util.content_frame(content, h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(3)]
     want = util.run_pipeline(O, srcs, prm_i, prm_p, bd)
+    if content != "synth":
+        util.check_envelope_run(srcs, want, qp, bd)
     ref = None
     for i, (src, (a, d, f, sp)) in enumerate(zip(srcs, want)):
         cp = cp_i if i == 0 else cp_p
@@ -453,16 +473,24 @@ def test_concurrent_sessions_from_several_threads(lib):
     assert failed == []
 
 
-@pytest.mark.parametrize("w,h,qp,bd,rng,pre", [(96, 80, 26, 8, 8, 0), (136, 72, 32, 8, 12, 1), (200, 104, 24, 10, 15, 1), (544, 320, 22, 8, 15, 1)])
-def test_b_picture_stage_equals_oracle(api, w, h, qp, bd, rng, pre):
+B_CASES = [(96, 80, 26, 8, 8, 0), (136, 72, 32, 8, 12, 1), (200, 104, 24, 10, 15, 1), (544, 320, 22, 8, 15, 1)]
+B_STAGE_CASES = [pytest.param(*c, "synth", id="-".join(map(str, c))) for c in B_CASES] + \
+                [pytest.param(w, h, qp, bd, rng, int(qp % 2 == 0), kind, id="-".join(map(str, (w, h, qp, bd, rng, int(qp % 2 == 0), kind))))
+                 for w, h, qp, bd, rng, kind in util.ENVELOPE_STAGE_CASES]
+
+
+@pytest.mark.parametrize("w,h,qp,bd,rng,pre,content", B_STAGE_CASES)
+def test_b_picture_stage_equals_oracle(api, w, h, qp, bd, rng, pre, content):
     """cfg.bframes on the device (mihevc_k_b_frame: k_me_search against both anchors + k_inter_ctu_b) against orc_analyze_b_frame, bit for bit: both
     integer-search dumps, records incl. which lists and the list-1 vector, levels, reconstruction, estimate; then the deblocking kernel with the
-    two-list boundary strength."""
+    two-list boundary strength.  Envelope content: every picture at the case's QP, then SAO and the fused loop filter of the B picture too."""
     from hevc_amd import _lib
-    cp_i, cp_p, cp_b = _lib.cost_params(max(0, qp - 3), bd, rng), _lib.cost_params(qp, bd, rng), _lib.cost_params(qp + 2, bd, rng)
+    synth = content == "synth"
+    qi, qb = (max(0, qp - 3), qp + 2) if synth else (qp, qp)
+    cp_i, cp_p, cp_b = _lib.cost_params(qi, bd, rng), _lib.cost_params(qp, bd, rng), _lib.cost_params(qb, bd, rng)
     cp_p.rdo_zero = cp_b.rdo_zero = 1
     to_prm = lambda cp: O.Params(cp.qp, cp.qp_c, cp.bit_depth, cp.lambda_sad_q4, cp.lambda_q4, cp.me_range, 1, 1, 0, 0, 0, cp.rdo_zero, 0)      # noqa: E731
-    f = [util.synth_frame(h, w, seed=23, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(3)]
+    f = [util.content_frame(content, h, w, seed=23, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(3)]
     a0 = O.analyze_intra(f[0], to_prm(cp_i))
     r0, _ = O.sao(f[0], O.deblock(a0.rec, a0.cu, bd), to_prm(cp_i))
     a2 = O.analyze_inter(f[2], r0, to_prm(cp_p))
@@ -475,6 +503,14 @@ def test_b_picture_stage_equals_oracle(api, w, h, qp, bd, rng, pre):
     assert util.same_analysis(want, got), util.describe_diff(want, got)
     assert len({int(x) & 96 for x in np.unique(want.cu["flags"])}) >= 2
     assert api.deblock(want.rec, want.cu, bd).same(O.deblock(want.rec, want.cu, bd))
+    if not synth:
+        d = O.deblock(want.rec, want.cu, bd)
+        wf, wsp = O.sao(f[1], d, to_prm(cp_b))
+        util.check_envelope_run([f[1]], [(want, d, wf, wsp)], qp, bd)
+        gf, gsp = api.sao(f[1], d, cp_b)
+        assert np.array_equal(gsp, wsp) and gf.same(wf), "sao"
+        lf, lsp = api.loop_filter(f[1], want.rec, want.cu, cp_b)
+        assert np.array_equal(lsp, wsp) and lf.same(wf), "fused loop filter"
 
 
 @pytest.mark.parametrize("bd", [8, 10])

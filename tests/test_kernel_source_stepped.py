@@ -31,17 +31,22 @@ CASES = [
     (72, 104, 26, 10, 8),      # Main10
     (160, 96, 14, 8, 12),      # low QP: many coefficients, small CUs
 ]
+# + the ends of the QP range on content at the ends of the sample range (util.ENVELOPE_STAGE_CASES); the synth cases keep their ids
+STAGE_CASES = [pytest.param(*c, "synth", id="-".join(map(str, c))) for c in CASES] + [pytest.param(*c, id="-".join(map(str, c))) for c in util.ENVELOPE_STAGE_CASES]
 
 
-@pytest.mark.parametrize("w,h,qp,bd,rng", CASES)
-def test_stepped_kernels_equal_oracle(emu, w, h, qp, bd, rng):
-    prm_i = O.default_params(max(0, qp - 3), bit_depth=bd, me_range=rng)
+@pytest.mark.parametrize("w,h,qp,bd,rng,content", STAGE_CASES)
+def test_stepped_kernels_equal_oracle(emu, w, h, qp, bd, rng, content):
+    prm_i = O.default_params(max(0, qp - 3) if content == "synth" else qp, bit_depth=bd, me_range=rng)
     prm_p = O.default_params(qp, bit_depth=bd, me_range=rng)
     prm_p.rdo_zero = int(qp >= 26)               # RD zero-out of inter TUs on for the higher QPs (where it bites), off for the rest
     prm_p.rdo_cg = 5 if 22 <= qp <= 30 else 0    # RD zero-out of 4x4 coefficient groups: the session's default strength / off
     prm_i.chroma_modes = int(qp < 35)            # chroma intra mode decision on for most cases (4x4, 8x8 and 16x16 chroma blocks)
-    srcs = [util.synth_frame(h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(3)]
+    prm_p.pre_search = int(content != "synth")   # envelope content: the search centres from the kernels' own 1/4-size pictures (their 8-bit samples at 10 bit)
+    srcs = [util.content_frame(content, h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(3)]
     want = util.run_pipeline(O, srcs, prm_i, prm_p, bd)
+    if content != "synth":
+        util.check_envelope_run(srcs, want, qp, bd)
     ref = None
     for i, (src, (a, d, f, sp)) in enumerate(zip(srcs, want)):
         prm = prm_i if i == 0 else prm_p
@@ -53,6 +58,9 @@ def test_stepped_kernels_equal_oracle(emu, w, h, qp, bd, rng):
         assert gd.same(d), f"deblock picture {i}"
         gf, gsp = emu.sao(src, d, prm)
         assert np.array_equal(gsp, sp) and gf.same(f), f"sao picture {i}"
+        if content != "synth":
+            lf, lsp = emu.loop_filter(src, a.rec, a.cu, prm)          # both filters in one CTU program over the pre-deblock picture
+            assert np.array_equal(lsp, sp) and lf.same(f), f"fused loop filter picture {i}"
         ref = f
     # the content must exercise more than one CU size somewhere in the run
     sizes = np.unique(np.concatenate([x[0].cu["log2_size"].ravel() for x in want]))
@@ -170,14 +178,23 @@ def test_waves_as_threads_with_real_barriers(emu, monkeypatch):
     assert util.same_analysis(want, got), util.describe_diff(want, got)
 
 
-@pytest.mark.parametrize("w,h,qp,bd,rng,pre", [(96, 80, 26, 8, 8, 0), (136, 72, 32, 8, 12, 1), (72, 104, 24, 10, 8, 1), (160, 96, 20, 8, 12, 0)])
-def test_stepped_b_picture_kernels_equal_oracle(emu, w, h, qp, bd, rng, pre):
+B_CASES = [(96, 80, 26, 8, 8, 0), (136, 72, 32, 8, 12, 1), (72, 104, 24, 10, 8, 1), (160, 96, 20, 8, 12, 0)]
+B_STAGE_CASES = [pytest.param(*c, "synth", id="-".join(map(str, c))) for c in B_CASES] + \
+                [pytest.param(w, h, qp, bd, rng, int(qp % 2 == 0), kind, id="-".join(map(str, (w, h, qp, bd, rng, int(qp % 2 == 0), kind))))
+                 for w, h, qp, bd, rng, kind in util.ENVELOPE_STAGE_CASES]
+
+
+@pytest.mark.parametrize("w,h,qp,bd,rng,pre,content", B_STAGE_CASES)
+def test_stepped_b_picture_kernels_equal_oracle(emu, w, h, qp, bd, rng, pre, content):
     """cfg.bframes: the B form of the CTU program (list-0 tree + refinement, list-1 refinement from its own integer search, bi-prediction trial by the
     default weighted average of the 14-bit predictions, cheapest of three) against orc_analyze_b_frame: both integer-search dumps, records (incl. which
-    lists and the list-1 vector), levels, reconstruction, estimate; then deblocking with the two-list boundary strength and SAO."""
-    prm_i, prm_p, prm_b = O.default_params(max(0, qp - 3), bd, rng), O.default_params(qp, bd, rng), O.default_params(qp + 2, bd, rng)
+    lists and the list-1 vector), levels, reconstruction, estimate; then deblocking with the two-list boundary strength and SAO.  Envelope content:
+    every picture at the case's QP, the fused loop filter too."""
+    synth = content == "synth"
+    qi, qb = (max(0, qp - 3), qp + 2) if synth else (qp, qp)
+    prm_i, prm_p, prm_b = O.default_params(qi, bd, rng), O.default_params(qp, bd, rng), O.default_params(qb, bd, rng)
     prm_p.rdo_zero = prm_b.rdo_zero = 1
-    f = [util.synth_frame(h, w, seed=23, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(3)]
+    f = [util.content_frame(content, h, w, seed=23, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(3)]
     a0 = O.analyze_intra(f[0], prm_i)
     r0, _ = O.sao(f[0], O.deblock(a0.rec, a0.cu, bd), prm_i)
     a2 = O.analyze_inter(f[2], r0, prm_p)
@@ -195,6 +212,10 @@ def test_stepped_b_picture_kernels_equal_oracle(emu, w, h, qp, bd, rng, pre):
     gf, gsp = emu.sao(f[1], d, prm_b)
     wf, wsp = O.sao(f[1], d, prm_b)
     assert np.array_equal(gsp, wsp) and gf.same(wf)
+    if not synth:
+        util.check_envelope_run([f[1]], [(want, d, wf, wsp)], qp, bd)
+        lf, lsp = emu.loop_filter(f[1], want.rec, want.cu, prm_b)
+        assert np.array_equal(lsp, wsp) and lf.same(wf), "fused loop filter"
 
 
 @pytest.mark.parametrize("w,h,bd", [(136, 104, 8), (96, 72, 10)])

@@ -35,6 +35,93 @@ def synth_frame(h, w, seed=0, shift=(0, 0), bit_depth=8, detail=True) -> O.Frame
     return O.Frame((y * sc).astype(np.uint16), (u * sc).astype(np.uint16), (v * sc).astype(np.uint16))
 
 
+ENVELOPE_KINDS = ("full_range", "rails")
+
+
+def envelope_frame(kind, h, w, bit_depth=8, seed=0, shift=(0, 0)) -> O.Frame:
+    """Content at the ends of the sample range, where synth_frame never goes (it stays mostly inside 15..240, x4 at 10 bit).
+    'full_range': band-limited textures stretched past 0 and 2^bd - 1 and clipped, so that several per cent of every plane, chroma
+    included, sit at each end (at 10 bit 1021..1023 occur too).  'rails': a mid-grey texture under hard-edged blocks of 0 and 2^bd - 1
+    whose edges miss the 8x8 grid, plus black fields with single bright samples.  `shift` translates the content (P and B input) and
+    changes only the per-picture grain, which never touches a rail."""
+    assert kind in ENVELOPE_KINDS, kind
+    top = (1 << bit_depth) - 1
+    H, W = h + 384, w + 384                              # room for shifts up to +-190 samples, as synth_frame
+    rng = np.random.default_rng(seed)
+
+    def texture():
+        t = rng.normal(0, 1, (H, W))
+        for _ in range(3):
+            t = (t + np.roll(t, 1, 0) + np.roll(t, 1, 1) + np.roll(t, -1, 0) + np.roll(t, -1, 1)) / 5
+        return (t - t.min()) / (t.max() - t.min())
+    yy, xx = np.mgrid[0:H, 0:W]
+    fixed = np.zeros((3, H, W), bool)                    # samples the grain must leave at their rail
+    if kind == "full_range":
+        canvas = np.stack([((texture() - 0.5) * (3.2 if p == 0 else 4.0) + 0.5 + 0.12 * np.sin(xx / (6.0 + p) + yy / 11.0)) * top for p in range(3)])
+    else:
+        canvas = np.stack([(0.25 + 0.5 * texture()) * top for _ in range(3)])
+        r2 = np.random.default_rng(seed + 7)
+        for _ in range(H * W // 700):                    # blocks of 0 / top, odd sizes and positions: edges off the 8x8 (and 4x4) grid
+            bw, bh = int(r2.integers(3, 29)), int(r2.integers(3, 29))
+            bx, by = int(r2.integers(0, W - bw)), int(r2.integers(0, H - bh))
+            for p in range(3):
+                if p == 0 or r2.random() < 0.6:
+                    canvas[p, by:by + bh, bx:bx + bw] = top * int(r2.integers(0, 2))
+                    fixed[p, by:by + bh, bx:bx + bw] = True
+        for _ in range(H * W // 6000):                   # black fields with single bright samples
+            bw, bh = int(r2.integers(12, 40)), int(r2.integers(12, 40))
+            bx, by = int(r2.integers(0, W - bw)), int(r2.integers(0, H - bh))
+            dots = r2.random((bh, bw)) < 0.04
+            for p in range(3):
+                canvas[p, by:by + bh, bx:bx + bw] = np.where(dots, top, 0)
+                fixed[p, by:by + bh, bx:bx + bw] = True
+    oy, ox = 192 + shift[1], 192 + shift[0]
+    g = np.random.default_rng((seed * 1000 + shift[0] * 31 + shift[1] + 1) % (1 << 32))
+    out = []
+    for p in range(3):
+        c, f = canvas[p, oy:oy + h, ox:ox + w], fixed[p, oy:oy + h, ox:ox + w]
+        if p:
+            c, f = c[::2, ::2], f[::2, ::2]
+        c = np.where(f, c, c + g.normal(0, 0.004 * top, c.shape))
+        out.append(np.clip(np.rint(c), 0, top).astype(np.uint16))
+    return O.Frame(*out)
+
+
+def content_frame(content, h, w, bit_depth=8, seed=0, shift=(0, 0)) -> O.Frame:
+    """'synth' (synth_frame) or one of ENVELOPE_KINDS"""
+    if content == "synth":
+        return synth_frame(h, w, seed, shift=shift, bit_depth=bit_depth)
+    return envelope_frame(content, h, w, bit_depth, seed, shift)
+
+
+def end_fractions(plane, bit_depth):
+    """(share of samples at 0, share at 2^bd - 1)"""
+    p = np.asarray(plane)
+    return float(np.mean(p == 0)), float(np.mean(p == (1 << bit_depth) - 1))
+
+
+def reaches_both_ends(frame: O.Frame, bit_depth, share=0.0):
+    """every plane has more than `share` of its samples at exactly 0 and more than `share` at exactly 2^bd - 1"""
+    return all(min(end_fractions(p, bit_depth)) > share for p in (frame.y, frame.u, frame.v))
+
+
+# stage-parity cases at the ends of the QP range on envelope content, partial CTUs, both bit depths: (w, h, qp, bit depth, me range, kind).
+# Every picture of such a case, the I picture included, is coded at the case's QP.
+ENVELOPE_QPS = (0, 4, 45, 51)
+ENVELOPE_STAGE_CASES = [((136, 72) if (i + i // 4) % 2 == 0 else (72, 104)) + (qp, bd, 8, kind)                    # every QP at both sizes
+                        for i, (kind, bd, qp) in enumerate((k, b, q) for k in ENVELOPE_KINDS for b in (8, 10) for q in ENVELOPE_QPS)]
+
+
+def check_envelope_run(srcs, want, qp, bd):
+    """an envelope case must reach what it exists for: both ends of the range in every source plane and in every plane of the reconstruction
+    (a share of luma), deblocking that changes samples of the run at the high QPs.  want: run_pipeline's (analysis, deblocked, final, sao) per picture"""
+    for i, (src, (a, d, f, _)) in enumerate(zip(srcs, want)):
+        assert reaches_both_ends(src, bd, 0.01), f"source {i} misses an end of the range"
+        assert min(end_fractions(f.y, bd)) > 0.002 and reaches_both_ends(f, bd), f"reconstruction {i} misses an end of the range"
+    if qp >= 45:
+        assert any(not d.same(a.rec) for a, d, _, _ in want), "deblocking left every sample alone"
+
+
 def dtype_for(bit_depth):
     return np.uint8 if bit_depth == 8 else np.uint16
 
