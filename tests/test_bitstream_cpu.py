@@ -23,7 +23,7 @@ def encode_pictures(cfg, srcs, qp, bd, me_range=8, keyint=1000, nxn=0, intra_in_
     prm_i.intra_nxn = prm_p.intra_nxn = nxn
     prm_p.intra_in_p = intra_in_p
     prm_p.tile_cols, prm_p.tile_rows = _lib.p_tile_grid(cfg)   # P pictures: PPS 0's own grid (cfg.p_tiles), which the intra second pass must respect
-    cus, analyses = [], []
+    cus, analyses, saos, qps = [], [], [], []
     for i, src in enumerate(srcs):
         intra = i % keyint == 0
         prm = prm_i if intra else prm_p
@@ -36,6 +36,8 @@ def encode_pictures(cfg, srcs, qp, bd, me_range=8, keyint=1000, nxn=0, intra_in_
         packets.append((bytes(buf[:n]), i, intra))
         cus.append(a.cu)
         analyses.append(a)
+        saos.append(sao)
+        qps.append(prm.qp)
         pkt = packets[-1][0]
         if i == 0:          # parameter sets belong to the first access unit, after its AUD when there is one (7.4.2.4.4)
             cut = pkt.index(b"\0\0\0\1", 4) if cfg.aud else 0
@@ -44,6 +46,7 @@ def encode_pictures(cfg, srcs, qp, bd, me_range=8, keyint=1000, nxn=0, intra_in_
         recs.append(ref)
     encode_pictures.last_cus = cus
     encode_pictures.last_analyses = analyses
+    encode_pictures.last_saos, encode_pictures.last_qps = saos, qps          # the SAO parameters and QP each picture was coded with
     return headers, stream, recs, packets
 
 
@@ -380,6 +383,7 @@ def encode_gop_with_b(cfg, srcs, qp, bd, me_range=8):
     for prm in (prm_p, prm_b):
         prm.rdo_zero = 1
     recs, types, cus = {}, {}, {}
+    coded = []                  # (display position, slice type, analysis, SAO parameters, QP) in decoding order
     last_anchor = None
     for k, (pos, st) in enumerate(coding_order(len(srcs))):
         src = srcs[pos]
@@ -392,6 +396,7 @@ def encode_gop_with_b(cfg, srcs, qp, bd, me_range=8):
         dbk = O.deblock(a.rec, a.cu, bd)
         rec, sao = O.sao(src, dbk, prm) if cfg.sao else (dbk, None)
         recs[pos], types[pos], cus[pos] = rec, st, a.cu
+        coded.append((pos, st, a, sao, prm.qp))
         if st != 0:
             last_anchor = pos
         m = lib.mihevc_encode_picture_host(C.byref(cfg), st, pos, prm.qp, util.ptr(a.cu), util.ptr(a.coef_y), util.ptr(a.coef_u), util.ptr(a.coef_v),
@@ -402,6 +407,7 @@ def encode_gop_with_b(cfg, srcs, qp, bd, me_range=8):
             cut = pkt.index(b"\0\0\0\1", 4)
             pkt = pkt[:cut] + headers + pkt[cut:]
         stream += pkt
+    encode_gop_with_b.last_coded = coded
     return stream, [recs[i] for i in range(len(srcs))], [types[i] for i in range(len(srcs))], [cus[i] for i in range(len(srcs))]
 
 

@@ -43,8 +43,9 @@ def gops_of(infos):
     return [(a, b) for a, b in zip(idr, idr[1:] + [len(infos)])]
 
 
-def replay(lib, cfg, frames, infos, recs, with_b=True):
-    """the oracle pipeline in coding order with the session's per-picture QPs"""
+def replay(lib, cfg, frames, infos, recs, with_b=True, out=None):
+    """the oracle pipeline in coding order with the session's per-picture QPs; out: a list that receives (analysis, SAO parameters, QP, slice type,
+    display position) per picture in coding order"""
     bd = cfg.bit_depth
     for g0, g1 in gops_of(infos):
         rec, last = {}, None
@@ -60,7 +61,9 @@ def replay(lib, cfg, frames, infos, recs, with_b=True):
             else:
                 a = O.analyze_b(src, rec[pos - 1], rec[pos + 1], prm, O.search_centres(src, frames[i - 1], bd) if cfg.pre_search else None,
                                 O.search_centres(src, frames[i + 1], bd) if cfg.pre_search else None)
-            rec[pos], _ = O.sao(src, O.deblock(a.rec, a.cu, bd), prm)
+            rec[pos], sao = O.sao(src, O.deblock(a.rec, a.cu, bd), prm)
+            if out is not None:
+                out.append((a, sao, infos[i][0], st, i))
             if st != 0:
                 last = pos
             assert recs[i].same(rec[pos]), f"display picture {i} (slice type {st}, qp {infos[i][0]}): session reconstruction != oracle pipeline"

@@ -102,16 +102,19 @@ def run_session(cfg, frames):
     return stream, sizes, infos, recs, st
 
 
-def replay(lib, cfg, frames, infos, recs, upto):
-    """the oracle pipeline with the session's per-picture QPs must give the session's reconstruction"""
+def replay(lib, cfg, frames, infos, recs, upto, out=None):
+    """the oracle pipeline with the session's per-picture QPs must give the session's reconstruction; out: a list that receives
+    (analysis, SAO parameters, QP, slice type, display position) per picture"""
     ref = None
     for i in range(upto):
         qp, st, _ = infos[i]
         prm, _ = session_params(lib, cfg, qp, st == 2)
         src = frames[i][1]
         a = O.analyze_intra(src, prm) if st == 2 else O.analyze_inter(src, ref, prm, centers=O.search_centres(src, frames[i - 1][1], cfg.bit_depth) if cfg.pre_search else None)
-        ref, _ = O.sao(src, O.deblock(a.rec, a.cu, cfg.bit_depth), prm)
+        ref, sao = O.sao(src, O.deblock(a.rec, a.cu, cfg.bit_depth), prm)
         assert recs[i].same(ref), f"picture {i} (qp {qp}): session reconstruction != oracle pipeline"
+        if out is not None:
+            out.append((a, sao, qp, st, i))
 
 
 def test_config2_1080p_stage_parity_i_p_p(lib, api):
