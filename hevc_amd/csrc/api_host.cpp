@@ -6,6 +6,10 @@
 
 using namespace mihevc;
 
+// what the last host-only call of this thread refused (mihevc_last_error(NULL))
+static thread_local std::string g_host_error;
+const char *mihevc::host_last_error() { return g_host_error.empty() ? "null session" : g_host_error.c_str(); }
+
 extern "C" {
 
 int mihevc_abi_version(void) { return MIHEVC_ABI_VERSION; }
@@ -80,7 +84,7 @@ static int copy_out(const std::vector<uint8_t> &v, uint8_t *buf, size_t cap)
 static bool config_ok(const mihevc_config *c)
 {
     return c && c->width >= 16 && c->height >= 16 && c->width <= 8192 && c->height <= 4352 && !(c->width & 1) && !(c->height & 1) &&
-           (c->bit_depth == 8 || c->bit_depth == 10) && c->fps_num > 0 && c->fps_den > 0;
+           (c->bit_depth == 8 || c->bit_depth == 10) && c->fps_num > 0 && c->fps_den > 0 && (c->sign_hide == 0 || c->sign_hide == 1);
 }
 
 int mihevc_tile_grid(const mihevc_config *cfg, int *cols, int *rows)
@@ -115,7 +119,10 @@ int mihevc_encode_picture_host(const mihevc_config *cfg, int slice_type, int poc
     if (slice_type != 1 && slice_type != 2 && !(slice_type == 0 && cfg->bframes > 0)) return MIHEVC_EINVAL;
     PictureSyms p{slice_type, poc, qp, cu, {coef_y, coef_u, coef_v}, cfg->sao ? sao : nullptr, 0};
     std::vector<uint8_t> v;
-    encode_picture(*cfg, p, v);
+    std::string err;
+    g_host_error.clear();
+    encode_picture(*cfg, p, v, true, &err);
+    if (!err.empty()) { g_host_error = err; return MIHEVC_EINVAL; }
     return copy_out(v, buf, cap);
 }
 

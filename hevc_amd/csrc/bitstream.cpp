@@ -302,7 +302,7 @@ void write_pps(const mihevc_config &cfg, int pps_id, std::vector<uint8_t> &out)
     w.put1(0);            // dependent_slice_segments_enabled_flag
     w.put1(0);            // output_flag_present_flag
     w.put(0, 3);          // num_extra_slice_header_bits
-    w.put1(0);            // sign_data_hiding_enabled_flag
+    w.put1(cfg.sign_hide == 1);      // sign_data_hiding_enabled_flag
     w.put1(0);            // cabac_init_present_flag
     w.ue(0);              // num_ref_idx_l0_default_active_minus1
     w.ue(0);              // num_ref_idx_l1_default_active_minus1
@@ -658,6 +658,7 @@ public:
         grid_.wc = wc_; grid_.hc = hc_;
     }
     const TileGrid &grid() const { return grid_; }
+    const std::string &error() const { return err_; }
     // 7.3.8.1 slice_segment_data for tile (tx, ty) into `out`: one CABAC substream.  Every tile but the last ends with
     // end_of_subset_one_bit + byte_alignment(), the last with end_of_slice_segment_flag = 1 + trailing bits; both are the
     // same flush (the final written '1' is the alignment / stop bit).
@@ -1003,12 +1004,12 @@ private:
         int cbf_luma = nxn ? (r.cbf_y4 >> blk) & 1 : (r.flags & F_CBF_Y) != 0;
         if (intra || depth != 0 || cbf_cb || cbf_cr) cabac_.bin(kCbfLuma + (depth == 0 ? 1 : 0), cbf_luma);
         int lmode = intra ? r.intra_mode[nxn ? blk : 0] : 1;
-        if (cbf_luma) residual(pic_.coef[0] + (size_t)y0 * w_ + x0, w_, log2n, 0, intra ? scan_idx(log2n, 0, lmode) : 0);
+        if (cbf_luma) residual(pic_.coef[0] + (size_t)y0 * w_ + x0, w_, log2n, 0, intra ? scan_idx(log2n, 0, lmode) : 0, x0, y0);
         if (log2n > 2 || blk == 3) {
             int xc = (log2n > 2 ? x0 : xb) >> 1, yc = (log2n > 2 ? y0 : yb) >> 1, l2c = log2n > 2 ? log2n - 1 : 2;
             int sc = intra ? scan_idx(l2c, 1, r.chroma_mode) : 0;
-            if (cbf_cb) residual(pic_.coef[1] + (size_t)yc * (w_ >> 1) + xc, w_ >> 1, l2c, 1, sc);
-            if (cbf_cr) residual(pic_.coef[2] + (size_t)yc * (w_ >> 1) + xc, w_ >> 1, l2c, 2, sc);
+            if (cbf_cb) residual(pic_.coef[1] + (size_t)yc * (w_ >> 1) + xc, w_ >> 1, l2c, 1, sc, xc, yc);
+            if (cbf_cr) residual(pic_.coef[2] + (size_t)yc * (w_ >> 1) + xc, w_ >> 1, l2c, 2, sc, xc, yc);
         }
     }
     static int scan_idx(int log2n, int c_idx, int mode)   // 7.4.9.11
@@ -1020,9 +1021,13 @@ private:
         return 0;
     }
 
-    // 7.3.8.11 residual_coding (no transform skip, no sign hiding)
-    void residual(const int16_t *lv, int stride, int log2n, int c_idx, int scan)
+    // 7.3.8.11 residual_coding (no transform skip).  Sign data hiding (cfg.sign_hide): a sub-block whose first and last levels lie more than 3 scan
+    // positions apart leaves out the sign of its first level (the lowest scan position), which the decoder infers from the parity of the sub-block's
+    // absolute sum; the kernels made every such sum agree (residual_pipeline), and a sub-block that does not is refused here rather than coded into
+    // a stream that decodes to another picture.  (tu_x, tu_y): the TU's position in its plane, for the message.
+    void residual(const int16_t *lv, int stride, int log2n, int c_idx, int scan, int tu_x, int tu_y)
     {
+        const bool sdh = cfg_.sign_hide == 1;
         const int l2sb = log2n - 2, nsb = 1 << l2sb, n = 1 << log2n;
         const uint8_t(*sbscan)[2] = kScans.xy[scan][l2sb];
         const uint8_t(*pscan)[2] = kScans.xy[scan][2];
@@ -1068,9 +1073,19 @@ private:
                 cabac_.bin(kCsbf + ((right | below) ? 1 : 0) + (c_idx ? 2 : 0), 0);
                 continue;
             }
-            int lev[16], nsig = 0;
+            int lev[16], nsig = 0, first_sig = 16, last_sig = -1, abs_sum = 0;
             int start = i == last_sb ? last_pos : 15;
-            for (int k = 0; k < 16; k++) { lev[k] = k <= start ? b[pscan[k][1] * stride + pscan[k][0]] : 0; nsig += lev[k] != 0; }
+            for (int k = 0; k < 16; k++) {
+                lev[k] = k <= start ? b[pscan[k][1] * stride + pscan[k][0]] : 0;
+                if (lev[k]) { nsig++; first_sig = std::min(first_sig, k); last_sig = k; abs_sum += std::abs(lev[k]); }
+            }
+            const bool hidden = sdh && last_sig - first_sig > 3;
+            if (hidden && (abs_sum & 1) != (lev[first_sig] < 0) && err_.empty()) {
+                const int sh = c_idx ? 1 : 0;
+                err_ = "sign data hiding: CTU (" + std::to_string((tu_x << sh) >> kCtuLog2) + ", " + std::to_string((tu_y << sh) >> kCtuLog2) + ") plane " +
+                       std::to_string(c_idx) + ": the 4x4 group at (" + std::to_string(tu_x + 4 * xs) + ", " + std::to_string(tu_y + 4 * ys) +
+                       ") has an absolute sum whose parity does not match its first level's sign";
+            }
             bool infer_dc = false;
             if (i < last_sb && i > 0) {
                 csbf[ys][xs] = nsig != 0;
@@ -1112,6 +1127,7 @@ private:
             if (g2_pos >= 0) cabac_.bin(kG2 + ctx_set + (c_idx ? 4 : 0), std::abs(lev[g2_pos]) > 2);
             uint32_t signs = 0; int ns = 0;
             for (int k = 15; k >= 0; k--) if (lev[k]) { signs = (signs << 1) | (uint32_t)(lev[k] < 0); ns++; }
+            if (hidden) { signs >>= 1; ns--; }      // the first level's sign is the last one gathered
             cabac_.bypass_bits(signs, ns);
             int num = 0, rice = 0;
             for (int k = 15; k >= 0; k--) {
@@ -1150,6 +1166,7 @@ private:
     int w_, h_, w8_, wc_, hc_;
     TileGrid grid_;
     std::vector<uint8_t> skip_, depth_;
+    std::string err_;         // the first sub-block that broke the sign data hiding rule (cfg.sign_hide), empty when none
 };
 
 }  // namespace
@@ -1162,7 +1179,7 @@ int picture_tiles(const mihevc_config &cfg, const PictureSyms &pic)
     return g.cols * g.rows;
 }
 
-size_t encode_tiles(const mihevc_config &cfg, const PictureSyms &pic, int t0, int t1, std::vector<std::vector<uint8_t>> &sub)
+size_t encode_tiles(const mihevc_config &cfg, const PictureSyms &pic, int t0, int t1, std::vector<std::vector<uint8_t>> &sub, std::string *err)
 {
     SliceCoder coder(cfg, pic);          // its neighbourhood state (skip flags, depths) is only ever read inside the tile that wrote it
     const TileGrid &grid = coder.grid();
@@ -1172,6 +1189,7 @@ size_t encode_tiles(const mihevc_config &cfg, const PictureSyms &pic, int t0, in
         sub[(size_t)t].reserve(1 << 14);
         bins += coder.run_tile(t % grid.cols, t / grid.cols, sub[(size_t)t]);
     }
+    if (err && !coder.error().empty()) *err = coder.error();
     return bins;
 }
 
@@ -1249,11 +1267,11 @@ void assemble_picture(const mihevc_config &cfg, const PictureSyms &pic, const st
     append_nal(out, idr ? 19 : pic.slice_type == 0 ? 0 : 1, rbsp);      // IDR_W_RADL, TRAIL_N (a B picture is never a reference), TRAIL_R
 }
 
-size_t encode_picture(const mihevc_config &cfg, const PictureSyms &pic, std::vector<uint8_t> &out, bool with_aud)
+size_t encode_picture(const mihevc_config &cfg, const PictureSyms &pic, std::vector<uint8_t> &out, bool with_aud, std::string *err)
 {
     const int n_tiles = picture_tiles(cfg, pic);
     std::vector<std::vector<uint8_t>> sub((size_t)n_tiles);
-    const size_t bins = encode_tiles(cfg, pic, 0, n_tiles, sub);
+    const size_t bins = encode_tiles(cfg, pic, 0, n_tiles, sub, err);
     assemble_picture(cfg, pic, sub, out, with_aud);
     return bins;
 }

@@ -6,6 +6,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../include/mihevc.h"
@@ -103,12 +104,15 @@ struct PictureSyms {
 // CABAC-code the picture into one slice-segment NAL appended to out; returns the number of bins coded (stats).
 // with_aud: prepend the access unit delimiter when cfg.aud (callers that put parameter sets / SEI into the same access unit write
 // the AUD themselves, it must come first: 7.4.2.4.4)
-size_t encode_picture(const mihevc_config &cfg, const PictureSyms &pic, std::vector<uint8_t> &out, bool with_aud = true);
+// err: set when the levels break the sign data hiding rule (cfg.sign_hide); the stream is then unusable
+size_t encode_picture(const mihevc_config &cfg, const PictureSyms &pic, std::vector<uint8_t> &out, bool with_aud = true, std::string *err = nullptr);
 // The same in pieces, so that the tiles of one picture can be coded by several host threads: every tile is its own CABAC substream and looks at
 // nothing outside itself.  picture_tiles: substreams of this picture; encode_tiles: tiles [t0, t1) into sub[t] (any thread, any order, each range
 // once); assemble_picture: slice header + entry points + substreams -> one NAL.  encode_picture = all three in one thread.
 int picture_tiles(const mihevc_config &cfg, const PictureSyms &pic);
-size_t encode_tiles(const mihevc_config &cfg, const PictureSyms &pic, int t0, int t1, std::vector<std::vector<uint8_t>> &sub);
+size_t encode_tiles(const mihevc_config &cfg, const PictureSyms &pic, int t0, int t1, std::vector<std::vector<uint8_t>> &sub, std::string *err = nullptr);
+// mihevc_last_error(NULL): what the calling thread's last mihevc_encode_picture_host refused ("null session" when nothing)
+const char *host_last_error();
 void assemble_picture(const mihevc_config &cfg, const PictureSyms &pic, const std::vector<std::vector<uint8_t>> &sub, std::vector<uint8_t> &out, bool with_aud);
 
 }  // namespace mihevc

@@ -576,9 +576,10 @@ INSTANTIATE(uint8_t)
 INSTANTIATE(uint16_t)
 
 // ------------------------------------------------------------------------------------------ K3 alone (parity/bench entry)
-// One workgroup per batch of residual blocks laid out as a pseudo-CTU: the blocks of one launch share log2n.
+// One workgroup per batch of residual blocks laid out as a pseudo-CTU: the blocks of one launch share log2n.  sign_hide: with sign data
+// hiding, every block's groups in the 4x4 scan `scan` (residual_pipeline)
 __global__ __launch_bounds__(NT) void k_transform_blocks(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int log2n, int qp,
-                                                         int bit_depth, int intra)
+                                                         int bit_depth, int intra, int scan, int sign_hide)
 {
     __shared__ ResidualShared s;
     GpuExec ex;
@@ -599,9 +600,9 @@ __global__ __launch_bounds__(NT) void k_transform_blocks(const int16_t *res, int
             int x = i & 31, y = i >> 5, blk = first + (y >> log2n) * (32 >> log2n) + (x >> log2n);
             if (blk < n_blocks) s.res[i] = res[(size_t)blk * n * n + (y & (n - 1)) * n + (x & (n - 1))];
         }
-        for (int i = tid; i < 1536; i += NT) s.desc[i] = pack_loc(locate(s, i));
+        for (int i = tid; i < 1536; i += NT) { SampleLoc l = locate(s, i); l.scan = scan; s.desc[i] = pack_loc(l); }
     });
-    residual_pipeline(ex, s, qp, qp, bit_depth, whole_ctu());
+    residual_pipeline(ex, s, qp, qp, bit_depth, whole_ctu(), 0, sign_hide);
     ex.phase([&](int tid) {
         for (int i = tid; i < 1024; i += NT) {
             int x = i & 31, y = i >> 5, blk = first + (y >> log2n) * (32 >> log2n) + (x >> log2n);
@@ -614,8 +615,9 @@ __global__ __launch_bounds__(NT) void k_transform_blocks(const int16_t *res, int
 }
 
 // 4x4 TUs (DCT, or DST-VII for intra luma): 16 lanes per block, four blocks per wave, the same step sequence and arithmetic as the
-// NxN trial of k_intra_diag (kernels/intra.h code_blocks): rows, columns + quantisation, scaling + inverse columns, inverse rows.
-__global__ __launch_bounds__(NT) void k_transform4_blocks(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int qp, int bit_depth, int intra, int dst)
+// NxN trial of k_intra_diag (kernels/intra.h code_blocks): rows, columns + quantisation, (sign data hiding,) scaling + inverse columns, inverse rows.
+__global__ __launch_bounds__(NT) void k_transform4_blocks(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int qp, int bit_depth, int intra, int dst,
+                                                          int scan, int sign_hide)
 {
     __shared__ int16_t M[16], sres[NT], slvl[NT];
     __shared__ int tmp[NT];
@@ -641,8 +643,18 @@ __global__ __launch_bounds__(NT) void k_transform4_blocks(const int16_t *res, in
         long long a = ((long long)iabs(c) * g_tab.quant_scale[q % 6] + ((long long)(intra ? 171 : 85) << (qbits - 9))) >> qbits;
         if (a > 32767) a = 32767;
         l[i] = (int16_t)(c < 0 ? -(int)a : (int)a);
+        if (sign_hide) sres[tid] = (int16_t)c;      // the residual is spent: the coefficient for the sign hiding step
         if (a) atomicOr(&nz[g], 1u); }
     __syncthreads();
+    if (sign_hide) {
+        if (i == 0) {
+            int lv[16], c[16], nv = 0;
+            for (int j = 0; j < 16; j++) { lv[j] = l[j]; c[j] = r[j]; }
+            const int p = sdh_adjust_scan(scan, lv, c, g_tab.quant_scale[q % 6], qbits, nv);
+            if (p >= 0) l[p] = (int16_t)nv;
+        }
+        __syncthreads();
+    }
     {   const int x = i & 3, y = i >> 2;
         const long long scale = (long long)16 * g_tab.level_scale[q % 6] << (q / 6);
         int acc = 0;
@@ -940,10 +952,11 @@ int mihevc_device_numa_node(int device)
     return node;
 }
 
-int mihevc_k_transform(int device, const int16_t *residual, int16_t *levels, int16_t *recon_residual, int n_blocks, int log2n, int qp,
-                       int bit_depth, int intra, int dst4)
+int mihevc_k_transform_sdh(int device, const int16_t *residual, int16_t *levels, int16_t *recon_residual, int n_blocks, int log2n, int qp,
+                           int bit_depth, int intra, int dst4, int scan_idx, int sign_hide)
 {
     if (!residual || !levels || !recon_residual || n_blocks <= 0 || log2n < 2 || log2n > 5 || (dst4 && log2n != 2)) return MIHEVC_EINVAL;
+    if (scan_idx < 0 || scan_idx > 2 || (sign_hide != 0 && sign_hide != 1)) return MIHEVC_EINVAL;
     if (bit_depth != 8 && bit_depth != 10) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
     const size_t bytes = (size_t)n_blocks << (2 * log2n + 1);
@@ -952,7 +965,7 @@ int mihevc_k_transform(int device, const int16_t *residual, int16_t *levels, int
     CK(hipMemcpy(dres.p, residual, bytes, hipMemcpyHostToDevice));
     if (log2n == 2) {     // 4-point DCT, or DST-VII (intra luma 4x4)
         hipLaunchKernelGGL(k_transform4_blocks, dim3((unsigned)((n_blocks + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, 0, dres.as<int16_t>(), dlvl.as<int16_t>(),
-                           drec.as<int16_t>(), n_blocks, qp, bit_depth, intra, dst4);
+                           drec.as<int16_t>(), n_blocks, qp, bit_depth, intra, dst4, scan_idx, sign_hide);
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(levels, dlvl.p, bytes, hipMemcpyDeviceToHost));
@@ -961,12 +974,18 @@ int mihevc_k_transform(int device, const int16_t *residual, int16_t *levels, int
     }
     const int per = 1024 >> (2 * log2n);
     hipLaunchKernelGGL(k_transform_blocks, dim3((unsigned)((n_blocks + per - 1) / per)), dim3(NT), 0, 0, dres.as<int16_t>(), dlvl.as<int16_t>(),
-                       drec.as<int16_t>(), n_blocks, log2n, qp, bit_depth, intra);
+                       drec.as<int16_t>(), n_blocks, log2n, qp, bit_depth, intra, scan_idx, sign_hide);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(levels, dlvl.p, bytes, hipMemcpyDeviceToHost));
     CK(hipMemcpy(recon_residual, drec.p, bytes, hipMemcpyDeviceToHost));
     return MIHEVC_OK;
+}
+
+int mihevc_k_transform(int device, const int16_t *residual, int16_t *levels, int16_t *recon_residual, int n_blocks, int log2n, int qp,
+                       int bit_depth, int intra, int dst4)
+{
+    return mihevc_k_transform_sdh(device, residual, levels, recon_residual, n_blocks, log2n, qp, bit_depth, intra, dst4, 0, 0);
 }
 
 int mihevc_k_intra_frame(int device, const void *sy, const void *su, const void *sv, int w, int h, const mihevc_cost_params *prm, void *ry, void *ru,

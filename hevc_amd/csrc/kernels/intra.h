@@ -568,7 +568,7 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
                 s.rs.res[i] = (int16_t)((int)s.src[i] - v);
             }
         });
-        residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, whole_ctu());
+        residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, whole_ctu());      // no sign hiding: these levels are a cost estimate, intra_code_cu recodes every CU
         ex.phase([&](int tid) {
             const int maxv = (1 << bd) - 1;
             for (int i = 4 * tid; i < 1536; i += 4 * NT) {
@@ -696,9 +696,11 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
     ex.phase([&](int tid) {      // prediction with the planned modes, residual
         const int cang = s.tab_angle[cmode], cinv = s.tab_inv[cmode], ang = s.tab_angle[mode], inv = s.tab_inv[mode];
         const T *L = intra_filter_on(log2n, mode) ? s.filt : s.ref[0];
+        const int lscan = scan_idx_of(log2n, 0, mode), cscan = scan_idx_of(log2n - 1, 1, cmode);
         for (int k = tid; k < rcnt; k += NT) {
             const int i = rg.index(k);
             SampleLoc l = locate(s.rs, i);
+            l.scan = l.plane ? cscan : lscan;
             s.rs.desc[i] = pack_loc(l);
             if (!l.log2n) continue;
             int v;
@@ -708,7 +710,7 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
             s.rs.res[i] = (int16_t)((int)s.src[i] - v);
         }
     });
-    residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, rg);
+    residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, rg, 0, a.prm.sign_hide);
     ex.phase([&](int tid) {      // reconstruction into the LDS neighbourhood, distortion, rate estimate
         const int maxv = (1 << bd) - 1;
         unsigned sse = 0;
@@ -799,6 +801,7 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
         const int sh = luma ? 0 : 1, qp = luma ? a.prm.qp : a.prm.qp_c, q = qp + 6 * (bd - 8);
         const int qbits = 14 + q / 6 + (15 - bd - 2), qs = s.tab_qs[q % 6], ls = s.tab_ls[q % 6], bsh = bd + 2 - 5;
         const int16_t *M = s.nx_mat[luma ? 0 : 1];
+        const bool sdh = a.prm.sign_hide != 0;
         const int zc = zaddr(x0 + (bx << sh), y0 + (by << sh), a.ctus_w);
         ex.wave_step([&](int tid0) {
             const int tid = tid0 - wbase;
@@ -888,7 +891,20 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             long long l = ((long long)iabs(c) * qs + ((long long)171 << (qbits - 9))) >> qbits;
             if (l > 32767) l = 32767;
             w.lvl[g][i] = (int16_t)(c < 0 ? -(int)l : (int)l);
+            if (sdh) w.res[g][i] = (int16_t)c;          // (the residual is spent) the coefficient for the sign hiding step
             if (l) ex.atomic_or(&w.nz[g], 1u);
+        });
+        if (sdh) ex.wave_step([&](int tid0) {
+            const int tid = tid0 - wbase;
+            if (tid < 0 || tid >= 64) return;          // sign data hiding: one lane per block, a 4x4 TU is one coefficient group
+            const int g = tid >> 5, i = tid & 31;
+            if (g >= nb || i != 0) return;
+            const int mode = luma ? (int)(s.mode_key & 63) : (int)s.cu_acc[tile].intra_mode[0];
+            int lv[16], c[16], nv = 0;
+#pragma unroll
+            for (int j = 0; j < 16; j++) { lv[j] = w.lvl[g][j]; c[j] = w.res[g][j]; }
+            const int p = sdh_adjust_scan(scan_idx_of(2, luma ? 0 : 1, mode), lv, c, qs, qbits, nv);
+            if (p >= 0) w.lvl[g][p] = (int16_t)nv;
         });
         ex.wave_step([&](int tid0) {
             const int tid = tid0 - wbase;

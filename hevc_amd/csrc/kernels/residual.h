@@ -42,6 +42,7 @@ struct SampleLoc {
     int log2n, tx0, ty0;       // TU geometry in the same coordinates; log2n == 0: not covered
     int tile0;                 // 8x8 tile index of the TU origin (for the cbf word)
     int intra;
+    int scan;                  // scanIdx of the TU (7.4.9.11): 0 diagonal, 1 horizontal, 2 vertical; locate() leaves it 0, intra callers set it
     int stride, base;          // row stride and base offset of the plane inside the 1536-sample arrays
 };
 
@@ -79,6 +80,7 @@ DEV SampleLoc locate(const ResidualShared &s, int idx)
     int tile = (l.y >> sh) * 4 + (l.x >> sh);
     int lg = s.tu_log2[tile];
     l.intra = s.tu_intra[tile];
+    l.scan = 0;
     if (!lg) { l.log2n = 0; l.tx0 = l.ty0 = l.tile0 = 0; return l; }
     int lgp = l.plane ? lg - 1 : lg;
     l.log2n = lgp;
@@ -88,13 +90,13 @@ DEV SampleLoc locate(const ResidualShared &s, int idx)
     return l;
 }
 // packed form kept in LDS so the five transform phases do one read instead of re-deriving the geometry
-DEV uint32_t pack_loc(const SampleLoc &l) { return (uint32_t)l.log2n | (uint32_t)l.tx0 << 3 | (uint32_t)l.ty0 << 8 | (uint32_t)l.tile0 << 13 | (uint32_t)l.intra << 17; }
+DEV uint32_t pack_loc(const SampleLoc &l) { return (uint32_t)l.log2n | (uint32_t)l.tx0 << 3 | (uint32_t)l.ty0 << 8 | (uint32_t)l.tile0 << 13 | (uint32_t)l.intra << 17 | (uint32_t)l.scan << 18; }
 DEV SampleLoc unpack_loc(uint32_t d, int idx)
 {
     SampleLoc l;
     if (idx < 1024) { l.plane = 0; l.x = idx & 31; l.y = idx >> 5; l.stride = 32; l.base = 0; }
     else { int i = idx - 1024; l.plane = 1 + (i >> 8); i &= 255; l.x = i & 15; l.y = i >> 4; l.stride = 16; l.base = 1024 + (l.plane - 1) * 256; }
-    l.log2n = (int)(d & 7); l.tx0 = (int)(d >> 3) & 31; l.ty0 = (int)(d >> 8) & 31; l.tile0 = (int)(d >> 13) & 15; l.intra = (int)(d >> 17) & 1;
+    l.log2n = (int)(d & 7); l.tx0 = (int)(d >> 3) & 31; l.ty0 = (int)(d >> 8) & 31; l.tile0 = (int)(d >> 13) & 15; l.intra = (int)(d >> 17) & 1; l.scan = (int)(d >> 18) & 3;
     return l;
 }
 
@@ -103,6 +105,67 @@ DEV void load_x4(const void *p, uint32_t (&v)[4]) { __builtin_memcpy(v, __builti
 DEV void load_x2(const void *p, uint32_t (&v)[2]) { __builtin_memcpy(v, __builtin_assume_aligned(p, 8), 8); }
 DEV void store_x4(void *p, const uint32_t (&v)[4]) { __builtin_memcpy(__builtin_assume_aligned(p, 16), v, 16); }
 DEV void store_x2(void *p, const uint32_t (&v)[2]) { __builtin_memcpy(__builtin_assume_aligned(p, 8), v, 8); }
+
+// scanIdx of a TU (7.4.9.11): mode-dependent for intra 4x4 TUs and 8x8 luma TUs, diagonal otherwise
+DEV int scan_idx_of(int log2n, int c_idx, int mode)
+{
+    if (log2n == 2 || (log2n == 3 && c_idx == 0)) {
+        if (mode >= 6 && mode <= 14) return 2;
+        if (mode >= 22 && mode <= 30) return 1;
+    }
+    return 0;
+}
+// raster position (y * 4 + x) of scan position n inside a 4x4 group (6.5.3 up-right diagonal, 6.5.4 horizontal, 6.5.5 vertical)
+constexpr int scan4_pos(int scan, int n) { return scan == 1 ? n : scan == 2 ? ((n & 3) << 2) | (n >> 2) : (int)((0xFBE7AD369C258140ull >> (4 * n)) & 15); }
+
+// Sign data hiding, encoder side (7.3.8.11 signHidden: the decoder infers the sign of the group's first level from the parity of its
+// absolute sum when lastSigScanPos - firstSigScanPos > 3).  One 4x4 group after quantisation: lv[16] levels and c[16] forward coefficients
+// in raster order, qs / qbits the quantiser's.  When the parity disagrees with the first level's sign, the one +-1 change whose rounding
+// error costs least is made (cost of scan position n: -delta for +1, delta for -1, delta = (|c| qs - |L| << qbits) >> (qbits - 8); ties
+// to the highest n; the first level may not drop to 0; a new level before the first one must carry the first one's sign; never above the
+// last level, so which TUs and groups hold levels does not change).  Returns the raster position of the changed level and its new value in
+// `nv`, or -1 when nothing changes.  SCAN is a template argument so that every index is a constant: the arrays stay in registers.
+template <int SCAN> DEV int sdh_adjust(const int (&lv)[16], const int (&c)[16], int qs, int qbits, int &nv)
+{
+    int first = 16, last = -1, sum = 0;
+#pragma unroll
+    for (int n = 0; n < 16; n++) {
+        const int v = lv[scan4_pos(SCAN, n)];
+        if (v) { first = first < 16 ? first : n; last = n; sum += iabs(v); }
+    }
+    if (last - first <= 3) return -1;
+    int sf = 0;
+#pragma unroll
+    for (int n = 0; n < 16; n++) if (n == first) sf = lv[scan4_pos(SCAN, n)] < 0;
+    if ((sum & 1) == sf) return -1;
+    long long best = 0;
+    int bp = -1;
+#pragma unroll
+    for (int n = 15; n >= 0; n--) {
+        const int p = scan4_pos(SCAN, n), a = iabs(lv[p]);
+        if (n > last) continue;
+        const long long u = (long long)iabs(c[p]) * qs, delta = (u - ((long long)a << qbits)) >> (qbits - 8);
+        int chg;
+        long long cost;
+        if (a) {
+            if (delta > 0) { chg = 1; cost = -delta; }
+            else { if (n == first && a == 1) continue; chg = -1; cost = delta; }
+        } else {
+            if (n < first && (c[p] < 0) != (sf != 0)) continue;
+            chg = 1; cost = -delta;
+        }
+        if (bp < 0 || cost < best) {
+            best = cost; bp = p;
+            const int na = chg > 0 && a == 32767 ? a - 1 : a + chg;
+            nv = c[p] < 0 ? -na : na;
+        }
+    }
+    return bp;
+}
+DEV int sdh_adjust_scan(int scan, const int (&lv)[16], const int (&c)[16], int qs, int qbits, int &nv)
+{
+    return scan == 1 ? sdh_adjust<1>(lv, c, qs, qbits, nv) : scan == 2 ? sdh_adjust<2>(lv, c, qs, qbits, nv) : sdh_adjust<0>(lv, c, qs, qbits, nv);
+}
 
 // forward + quant + scaling + inverse for every TU of the region; s.desc must describe the region's samples
 // (callers fill it while they form the residual).  qp / qp_c are syntax QPs.
@@ -114,7 +177,9 @@ DEV void store_x2(void *p, const uint32_t (&v)[2]) { __builtin_memcpy(__builtin_
 // coefficient error (c coefficient, r its reconstruction) and saves its levels' bits + one sub-block; drop <=> 16 D < ((cg_lam_q4 * bits) >> 4) << 2 (15 - bitDepth - log2n).
 // A group is two vertically adjacent 2x4 blocks, i.e. two lanes: both leave their partial sums in LDS (`res` is free between the forward and the
 // inverse transform) and the next phase lets each decide for its own half.
-template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp, int qp_c, int bit_depth, Region rg, int cg_lam_q4 = 0)
+// sign_hide: after the group decisions, every 4x4 group is brought to the sign data hiding parity (sdh_adjust) by the lane of its upper
+// 2x4 block; the TU's scanIdx comes with s.desc.  Skipped by a uniform branch when off.
+template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp, int qp_c, int bit_depth, Region rg, int cg_lam_q4 = 0, int sign_hide = 0)
 {
     const int nblk = rg.count() >> 3;
     long long *cg_d = s.cg.d;
@@ -272,6 +337,34 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
                 store_rows(s.lvl, l, zero);
                 store_pairs(l, zero);
             } else ex.atomic_or(&s.cbf[l.plane], 1u << l.tile0);
+        }
+    });
+    if (sign_hide) ex.phase([&](int tid) {      // sign data hiding: the forward coefficients are still in `coef`, the scaled levels in `tmp`
+        for (int k = tid; k < nblk; k += NT) {
+            const int idx = rg.block_index(k);
+            SampleLoc l = unpack_loc(s.desc[idx], idx);
+            if (!l.log2n || (l.y & 3)) continue;
+            int lv[16], c[16];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                uint32_t l2[2], c2[2];
+                load_x2(s.lvl + l.base + (l.y + j) * l.stride + l.x, l2);
+                load_x2(s.coef + l.base + (l.y + j) * l.stride + l.x, c2);
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    lv[j * 4 + i] = (int)(int16_t)(l2[i >> 1] >> (16 * (i & 1)));
+                    c[j * 4 + i] = (int)(int16_t)(c2[i >> 1] >> (16 * (i & 1)));
+                }
+            }
+            const int q = (l.plane ? qp_c : qp) + 6 * (bit_depth - 8);
+            const int qbits = 14 + q / 6 + (15 - bit_depth - l.log2n), bd_shift = bit_depth + l.log2n - 5;
+            int nv = 0;
+            const int p = sdh_adjust_scan(l.scan, lv, c, s.quant_scale[q % 6], qbits, nv);
+            if (p < 0) continue;
+            const int y = l.y + (p >> 2), x = l.x + (p & 3);
+            const long long d = (nv * ((long long)16 * s.level_scale[q % 6] << (q / 6)) + ((long long)1 << (bd_shift - 1))) >> bd_shift;
+            s.lvl[l.base + y * l.stride + x] = (int16_t)nv;
+            s.tmp[l.base + (y & ~1) * l.stride + 2 * x + (y & 1)] = (int16_t)(d < -32768 ? -32768 : d > 32767 ? 32767 : d);
         }
     });
     ex.phase([&](int tid) {      // inverse stage 1: columns, shift 7, clip to 16 bit (8.6.4.2)

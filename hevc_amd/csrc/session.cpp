@@ -152,6 +152,7 @@ struct Packet {
     std::vector<uint8_t> data;
     int64_t pts = 0, dts = 0;
     bool key = false, ready = false;
+    std::string error;      // the host coder refused the picture's levels (sign data hiding parity): mihevc_receive_packet fails with MIHEVC_EINVAL here
 };
 
 // symbol block of one picture: [cu | coef Y | coef U | coef V | sao | sse[3] | rate estimate]; the device twin carries the per-CTU squared errors behind it
@@ -189,6 +190,7 @@ struct mihevc_session {
     TileGrid ptiles;                                           // P pictures (PPS 0, cfg.p_tiles); 1x1 when off
     int keyint = 90, lanes = 4, me_range = 16, qp_p = 22, qp_i = 19;
     bool is16 = false, keep_recon = false, flushed = false, failed = false, flushing = false;
+    int fail_code = MIHEVC_EDEVICE;      // what calls return once `failed` is set: MIHEVC_EINVAL when the host coder refused a picture
     std::string err;
     hipStream_t st_compute = nullptr, st_copy = nullptr, st_pre = nullptr;      // st_pre: the chunk's pre-search, beside the IDR step
     // uploads of host frames (mihevc_send_frame / _async) go through st_pre (idle outside a chunk's IDR step; a FOURTH stream per session made two of them share a
@@ -387,6 +389,8 @@ struct PictureJob {
     std::vector<std::vector<uint8_t>> sub;
     std::atomic<int> left;
     std::atomic<long long> ns{0};
+    std::mutex err_m;
+    std::string err;        // first refusal of any part (encode_tiles)
 };
 
 void picture_symbols(mihevc_session *s, int slot, int lane_i, PictureSyms &pic)
@@ -407,6 +411,7 @@ void publish_picture(PictureJob *j)
     const uint8_t *b = s->lane[j->lane_i].sym_host[j->slot];
     Packet pk;
     pk.pts = j->pts; pk.dts = j->dts; pk.key = j->slice_type == 2;
+    pk.error = j->err;      // (every part has finished: no lock needed)
     // a picture's later slices (sessions on other devices, cfg.slice_index > 0) contribute their slice NAL unit only: the access unit's
     // delimiter, parameter sets and SEI come with slice 0
     const bool au_head = s->cfg.slice_count <= 1 || s->cfg.slice_index == 0;
@@ -452,7 +457,9 @@ void entropy_part(PictureJob *j, int part)
 {
     auto t0 = std::chrono::steady_clock::now();
     const int t_a = (int)((long long)j->n_tiles * part / j->parts), t_b = (int)((long long)j->n_tiles * (part + 1) / j->parts);
-    encode_tiles(j->s->cfg, j->pic, t_a, t_b, j->sub);
+    std::string err;
+    encode_tiles(j->s->cfg, j->pic, t_a, t_b, j->sub, &err);
+    if (!err.empty()) { std::lock_guard<std::mutex> l(j->err_m); if (j->err.empty()) j->err = "picture " + std::to_string(j->index) + ": " + err; }
     j->ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
     if (j->left.fetch_sub(1) == 1) publish_picture(j);
 }
@@ -754,7 +761,7 @@ template <typename T> int encode_chunk(mihevc_session *s)
         mihevc_cost_params c;
         mihevc_cost_params_for_qp(qp, s->cfg.bit_depth, s->me_range, &c);
         return CostParams{c.qp, c.qp_c, c.bit_depth, c.lambda_sad_q4, c.lambda_q4, c.me_range, s->tiles.cols, s->tiles.rows, s->cfg.intra_nxn != 0, s->cfg.intra_in_p != 0, s->cfg.pre_search != 0, s->cfg.rdo_zero != 0, s->cfg.chroma_modes != 0,
-                          s->cfg.slice_count > 1 && !s->cfg.slice_halo && s->cfg.slice_index > 0, s->cfg.slice_count > 1 && !s->cfg.slice_halo && s->cfg.slice_index < s->cfg.slice_count - 1, std::max(0, s->cfg.rdo_cg)};
+                          s->cfg.slice_count > 1 && !s->cfg.slice_halo && s->cfg.slice_index > 0, s->cfg.slice_count > 1 && !s->cfg.slice_halo && s->cfg.slice_index < s->cfg.slice_count - 1, std::max(0, s->cfg.rdo_cg), s->cfg.sign_hide};
     };
     const int64_t first_index = s->frames_in - n;
     {
@@ -1376,6 +1383,7 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     *out = nullptr;
     if (cfg->width < 16 || cfg->height < 16 || (cfg->width & 1) || (cfg->height & 1) || cfg->width > 8192 || cfg->height > 4352) return MIHEVC_EINVAL;
     if (cfg->bit_depth != 8 && cfg->bit_depth != 10) return MIHEVC_EINVAL;
+    if (cfg->sign_hide != 0 && cfg->sign_hide != 1) return MIHEVC_EINVAL;
     if (cfg->fps_num <= 0 || cfg->fps_den <= 0 || cfg->keyint < 1 || cfg->keyint > 240) return MIHEVC_EINVAL;
     if (cfg->bframes < -1 || cfg->bframes > 1 || (cfg->bframes && cfg->slice_count > 1)) return MIHEVC_EINVAL;      // B pictures: whole pictures only (for now)
     if (cfg->slice_count > 1) {        // one slice of a picture: a band of whole CTU rows (the last band takes the picture's remainder)
@@ -1460,7 +1468,7 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
 static int ingest(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
 {
     if (!s || !y || !u || !v) return MIHEVC_EINVAL;
-    if (s->failed) return MIHEVC_EDEVICE;
+    if (s->failed) return s->fail_code;
     if (s->flushed) return MIHEVC_ESTATE;
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     mihevc_session::Src src;
@@ -1527,7 +1535,7 @@ int mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, co
 int mihevc_sync_uploads(mihevc_session *s)
 {
     if (!s) return MIHEVC_EINVAL;
-    if (s->failed) return MIHEVC_EDEVICE;
+    if (s->failed) return s->fail_code;
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     HIPCK(s, hipStreamSynchronize(s->st_pre));
     s->up_pending = false;
@@ -1537,7 +1545,7 @@ int mihevc_sync_uploads(mihevc_session *s)
 int mihevc_flush(mihevc_session *s)
 {
     if (!s) return MIHEVC_EINVAL;
-    if (s->failed) return MIHEVC_EDEVICE;
+    if (s->failed) return s->fail_code;
     if (s->flushed) return MIHEVC_OK;
     s->flushing = true;
     int e = run_chunk(s);
@@ -1560,6 +1568,7 @@ int mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
     std::lock_guard<std::mutex> l(s->m);
     auto it = s->packets.find(s->next_out);
     if (it == s->packets.end() || !it->second.ready) return (s->flushed && s->next_out >= s->frames_in) ? MIHEVC_EOF : MIHEVC_EAGAIN;
+    if (!it->second.error.empty()) { s->failed = true; s->fail_code = MIHEVC_EINVAL; s->err = it->second.error; return MIHEVC_EINVAL; }
     s->cur_packet = std::move(it->second.data);
     if (pts) *pts = it->second.pts;
     if (dts) *dts = it->second.dts;        // packets come in decoding order; dts < pts only with B pictures (cfg.bframes)
@@ -1627,7 +1636,7 @@ int mihevc_coded_size(const mihevc_session *s, int *w, int *h)
     return MIHEVC_OK;
 }
 
-const char *mihevc_last_error(const mihevc_session *s) { return s ? s->err.c_str() : "null session"; }
+const char *mihevc_last_error(const mihevc_session *s) { return s ? s->err.c_str() : host_last_error(); }
 
 void mihevc_close(mihevc_session *s)
 {

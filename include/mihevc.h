@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MIHEVC_ABI_VERSION 3
+#define MIHEVC_ABI_VERSION 4
 
 typedef enum {
     MIHEVC_OK = 0,
@@ -118,6 +118,12 @@ typedef struct mihevc_config {
                                        * Point-to-point pulls out of the neighbour's device memory (xGMI peer access), no collective.  0: nothing is exchanged — motion
                                        * constrained slices, filters stop at the seams, every slice its own rate controller (round 2: -1.5 dB at 4320p over 8) */
     int32_t slice_group;              /* slice_halo: any non-zero number shared by the sessions of one picture's slices and by nobody else in the process */
+    /* ---- ABI 4 ---- */
+    int32_t sign_hide;                /* 1: sign data hiding (sign_data_hiding_enabled_flag in both PPS, x265 signhide): in every 4x4 coefficient group whose first and last
+                                       * levels lie more than 3 scan positions apart, the first level's sign is not coded but carried by the parity of the group's
+                                       * absolute sum; the kernels adjust one level per group where the parity disagrees (the cheapest +-1 by rounding error).  Every
+                                       * path that produces coded levels does it.  The host coder checks the rule in every group it codes and fails the picture with
+                                       * MIHEVC_EINVAL when one breaks it.  0 (default): off.  Any other value: MIHEVC_EINVAL at open and in mihevc_write_parameter_sets */
 } mihevc_config;
 
 typedef struct mihevc_session mihevc_session;
@@ -188,6 +194,7 @@ int  mihevc_coded_size(const mihevc_session *s, int *w, int *h);
 /* QP, slice type (2 = IDR, 1 = P) and coded size in bits (-1 while CABAC is still running) of output picture `index` */
 int  mihevc_get_frame_info(mihevc_session *s, int64_t index, int *qp, int *slice_type, int64_t *bits);
 const char *mihevc_strerror(int err);
+/* s = NULL: what the calling thread's last mihevc_encode_picture_host refused ("null session" when nothing) */
 const char *mihevc_last_error(const mihevc_session *s);
 
 /* ---- integer cost parameters derived from a QP (shared by every stage; exported so tests can hand the same
@@ -239,6 +246,10 @@ typedef struct mihevc_sao_ctu {
  * DCT); dst4 = 1 with log2n = 2 selects the 4x4 DST-VII of intra luma TUs (8.6.4.2) */
 int mihevc_k_transform(int device, const int16_t *residual, int16_t *levels, int16_t *recon_residual,
                        int n_blocks, int log2n, int qp, int bit_depth, int intra, int dst4);
+/* the same with sign data hiding (mihevc_config.sign_hide): sign_hide = 1 brings every 4x4 group of every block to the parity rule, scan_idx (0 diagonal,
+ * 1 horizontal, 2 vertical: 7.4.9.11) being the block's scan order.  sign_hide = 0 and scan_idx = 0: exactly mihevc_k_transform */
+int mihevc_k_transform_sdh(int device, const int16_t *residual, int16_t *levels, int16_t *recon_residual,
+                           int n_blocks, int log2n, int qp, int bit_depth, int intra, int dst4, int scan_idx, int sign_hide);
 /* K2+K3: intra picture analysis -> pre-deblock reconstruction, CU records, levels */
 int mihevc_k_intra_frame(int device, const void *src_y, const void *src_u, const void *src_v, int width, int height,
                          const mihevc_cost_params *prm, void *rec_y, void *rec_u, void *rec_v,
