@@ -614,61 +614,13 @@ __global__ __launch_bounds__(NT) void k_transform_blocks(const int16_t *res, int
     });
 }
 
-// 4x4 TUs (DCT, or DST-VII for intra luma): 16 lanes per block, four blocks per wave, the same step sequence and arithmetic as the
-// NxN trial of k_intra_diag (kernels/intra.h code_blocks): rows, columns + quantisation, (sign data hiding,) scaling + inverse columns, inverse rows.
+// 4x4 TUs (DCT, or DST-VII for intra luma): 16 lanes per block, NT / 16 blocks per workgroup (transform4_program on the 4x4 core of residual.h)
 __global__ __launch_bounds__(NT) void k_transform4_blocks(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int qp, int bit_depth, int intra, int dst,
                                                           int scan, int sign_hide)
 {
-    __shared__ int16_t M[16], sres[NT], slvl[NT];
-    __shared__ int tmp[NT];
-    __shared__ unsigned nz[NT / 16];
-    const int tid = (int)threadIdx.x, g = tid >> 4, i = tid & 15, blk = (int)blockIdx.x * (NT / 16) + g;
-    if (tid < 16) M[tid] = dst ? g_tab.dst4[tid >> 2][tid & 3] : g_tab.mat[(tid >> 2) * 8][tid & 3];
-    if (i == 0) nz[g] = 0;
-    sres[tid] = blk < n_blocks ? res[(size_t)blk * 16 + i] : (int16_t)0;
-    __syncthreads();
-    const int bd = bit_depth, q = qp + 6 * (bd - 8), qbits = 14 + q / 6 + (15 - bd - 2), bsh = bd + 2 - 5, s1 = bd - 7, s3 = 20 - bd;
-    const int16_t *r = sres + g * 16;
-    int *t = tmp + g * 16;
-    int16_t *l = slvl + g * 16;
-    {   const int u = i & 3, y = i >> 2;
-        int acc = 0;
-        for (int x = 0; x < 4; x++) acc += M[u * 4 + x] * r[y * 4 + x];
-        t[i] = (acc + (1 << (s1 - 1))) >> s1; }
-    __syncthreads();
-    {   const int u = i & 3, v = i >> 2;
-        int acc = 0;
-        for (int y = 0; y < 4; y++) acc += M[v * 4 + y] * t[y * 4 + u];
-        const int c = clip3(-32768, 32767, (acc + 128) >> 8);
-        long long a = ((long long)iabs(c) * g_tab.quant_scale[q % 6] + ((long long)(intra ? 171 : 85) << (qbits - 9))) >> qbits;
-        if (a > 32767) a = 32767;
-        l[i] = (int16_t)(c < 0 ? -(int)a : (int)a);
-        if (sign_hide) sres[tid] = (int16_t)c;      // the residual is spent: the coefficient for the sign hiding step
-        if (a) atomicOr(&nz[g], 1u); }
-    __syncthreads();
-    if (sign_hide) {
-        if (i == 0) {
-            int lv[16], c[16], nv = 0;
-            for (int j = 0; j < 16; j++) { lv[j] = l[j]; c[j] = r[j]; }
-            const int p = sdh_adjust_scan(scan, lv, c, g_tab.quant_scale[q % 6], qbits, nv);
-            if (p >= 0) l[p] = (int16_t)nv;
-        }
-        __syncthreads();
-    }
-    {   const int x = i & 3, y = i >> 2;
-        const long long scale = (long long)16 * g_tab.level_scale[q % 6] << (q / 6);
-        int acc = 0;
-        for (int j = 0; j < 4; j++) acc += M[j * 4 + y] * clip3(-32768, 32767, (int)((l[j * 4 + x] * scale + ((long long)1 << (bsh - 1))) >> bsh));
-        __syncthreads();
-        t[i] = clip3(-32768, 32767, (acc + 64) >> 7); }
-    __syncthreads();
-    {   const int x = i & 3, y = i >> 2;
-        int acc = 0;
-        for (int j = 0; j < 4; j++) acc += M[j * 4 + x] * t[y * 4 + j];
-        if (blk < n_blocks) {
-            lvl[(size_t)blk * 16 + i] = l[i];
-            rec[(size_t)blk * 16 + i] = nz[g] ? (int16_t)((acc + (1 << (s3 - 1))) >> s3) : (int16_t)0;
-        } }
+    __shared__ Transform4Shared s;
+    GpuExec ex;
+    transform4_program(ex, s, res, lvl, rec, n_blocks, (int)blockIdx.x * (NT / 16), qp, bit_depth, intra, dst, scan, sign_hide);
 }
 
 }  // namespace mihevc

@@ -61,9 +61,9 @@ constexpr int RC_STRIDE = 36;    // chroma: rows -1..15, cols -1..31
 
 template <typename T> struct Nx4 {       // per block group g: 0 = luma PU or Cb, 1 = Cr
     T ref_raw[2][17], ref[2][17];
-    unsigned av[2], nz[2];
-    int16_t pred[2][16], res[2][16], lvl[2][16];
-    int tmp[2][16];
+    unsigned av[2];
+    int16_t pred[2][16];
+    Block4 blk[2];           // the 4x4 core's residual, levels, intermediates and nz flag
 };
 
 // what the plan stage hands to the code stage for one CTU: the quadtree's leaves and their modes (k_intra_plan -> k_intra_diag through
@@ -762,7 +762,7 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
 // PU 0's mode (DM), and keep NxN only if its cost is lower.  The 4x4 blocks depend on each other, so the whole trial runs
 // on wave 0 as wave-local steps (ex.wave_step: no workgroup barriers): 17 lanes build the reference samples, 35 lanes rank
 // the modes by 4x4-Hadamard SATD, 16 lanes (one per sample) predict, transform (DST-VII luma / DCT chroma), quantise and
-// reconstruct.  Arithmetic as residual_pipeline / oracle code_tu.
+// reconstruct on the 4x4 core of residual.h (oracle code_tu).
 template <typename T, class Ex>
 DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, int y0, int cx, int cy)
 {
@@ -792,22 +792,25 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             s.cu_acc[tile] = r;
             s.nx_sse = 0; s.nx_bits = 16 + 24; s.nx_cbf_c = 0;
             s.mode_key = ~0ull;
-            w.av[0] = w.av[1] = 0; w.nz[0] = w.nz[1] = 0;
+            w.av[0] = w.av[1] = 0; w.blk[0].nz = w.blk[1].nz = 0;
         }
     });
     // one pass codes `nb` 4x4 blocks of the same kind side by side (lane group g = lane / 32): a luma PU (nb = 1) or Cb + Cr (nb = 2)
     auto code_blocks = [&](int nb, int pl0, int bx, int by, int k) {
         const bool luma = pl0 == 0;
-        const int sh = luma ? 0 : 1, qp = luma ? a.prm.qp : a.prm.qp_c, q = qp + 6 * (bd - 8);
-        const int qbits = 14 + q / 6 + (15 - bd - 2), qs = s.tab_qs[q % 6], ls = s.tab_ls[q % 6], bsh = bd + 2 - 5;
+        const int sh = luma ? 0 : 1;
+        const Quantiser qz(luma ? a.prm.qp : a.prm.qp_c, bd, 2, 1, s.tab_qs, s.tab_ls);
         const int16_t *M = s.nx_mat[luma ? 0 : 1];
         const bool sdh = a.prm.sign_hide != 0;
         const int zc = zaddr(x0 + (bx << sh), y0 + (by << sh), a.ctus_w);
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // reference samples: availability (6.4.1 incl. tiles) + raw values
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 17) return;
+        // a wave step on the first `lanes` lanes of every block's lane group: f(g, i); with 16 lanes i is the block's sample (y * 4 + x)
+        auto block_step = [&](int lanes, auto &&f) {
+            ex.wave_step([&](int tid0) {
+                const int tid = tid0 - wbase, g = tid >> 5, i = tid & 31;
+                if (tid >= 0 && tid < 64 && g < nb && i < lanes) f(g, i);
+            });
+        };
+        block_step(17, [&](int g, int i) {          // reference samples: availability (6.4.1 incl. tiles) + raw values
             const int pl = pl0 + g;
             int xn, yn;
             if (i < 8) { xn = bx - 1; yn = by + 7 - i; } else if (i == 8) { xn = bx - 1; yn = by - 1; } else { xn = bx + i - 9; yn = by - 1; }
@@ -816,11 +819,7 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             w.ref_raw[g][i] = ok ? (pl ? s.rec_c[pl - 1][(yn + 1) * RC_STRIDE + xn + 1] : s.rec_y[(yn + 1) * RY_STRIDE + xn + 1]) : (T)0;
             if (ok) ex.atomic_or(&w.av[g], 1u << i);
         });
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // substitution 8.4.4.2.2: nearest available below, else the first available
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 17) return;
+        block_step(17, [&](int g, int i) {          // substitution 8.4.4.2.2: nearest available below, else the first available
             const unsigned av = w.av[g], below = av & ((2u << i) - 1);
             w.ref[g][i] = !av ? (T)(1 << (bd - 1)) : below ? w.ref_raw[g][31 - __builtin_clz(below)] : w.ref_raw[g][__builtin_ctz(av)];
         });
@@ -851,11 +850,7 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             const unsigned cost = ((unsigned)((sat + 1) >> 1) << 4) + (unsigned)(a.prm.lambda_sad_q4 * bits);
             ex.atomic_min(&s.mode_key, ((unsigned long long)cost << 6) | (unsigned)tid);
         });
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // prediction + residual, one lane per sample
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 16) return;
+        block_step(16, [&](int g, int i) {          // prediction + residual, one lane per sample
             const int pl = pl0 + g, mode = luma ? (int)(s.mode_key & 63) : (int)s.cu_acc[tile].intra_mode[0];
             const T *ref = w.ref[g];
             int sum = 4;
@@ -865,77 +860,24 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             const int v = intra_sample<T>(ref, 2, mode, s.tab_angle[mode], s.tab_inv[mode], x, y, pl, bd, sum >> 3);
             const int sidx = luma ? (by + y) * 32 + bx + x : 1024 + (pl - 1) * 256 + (by + y) * 16 + bx + x;
             w.pred[g][i] = (int16_t)v;
-            w.res[g][i] = (int16_t)((int)s.src[sidx] - v);
+            w.blk[g].res[i] = (int16_t)((int)s.src[sidx] - v);
         });
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // forward stage 1 (rows)
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 16) return;
-            const int u = i & 3, y = i >> 2, s1 = bd - 7;
-            int acc = 0;
-#pragma unroll
-            for (int x = 0; x < 4; x++) acc += M[u * 4 + x] * w.res[g][y * 4 + x];
-            w.tmp[g][i] = (acc + (1 << (s1 - 1))) >> s1;
-        });
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // forward stage 2 (columns) + quantisation (intra dead zone 171/512)
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 16) return;
-            const int u = i & 3, v = i >> 2;
-            int acc = 0;
-#pragma unroll
-            for (int y = 0; y < 4; y++) acc += M[v * 4 + y] * w.tmp[g][y * 4 + u];
-            const int c = clip3(-32768, 32767, (acc + 128) >> 8);
-            long long l = ((long long)iabs(c) * qs + ((long long)171 << (qbits - 9))) >> qbits;
-            if (l > 32767) l = 32767;
-            w.lvl[g][i] = (int16_t)(c < 0 ? -(int)l : (int)l);
-            if (sdh) w.res[g][i] = (int16_t)c;          // (the residual is spent) the coefficient for the sign hiding step
-            if (l) ex.atomic_or(&w.nz[g], 1u);
-        });
-        if (sdh) ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // sign data hiding: one lane per block, a 4x4 TU is one coefficient group
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i != 0) return;
+        block_step(16, [&](int g, int i) { core4_fwd_rows(M, w.blk[g], i, bd); });
+        block_step(16, [&](int g, int i) { core4_fwd_cols_quant(ex, M, w.blk[g], i, qz, sdh); });
+        if (sdh) block_step(16, [&](int g, int i) {          // sign data hiding: one lane per block
+            if (i) return;
             const int mode = luma ? (int)(s.mode_key & 63) : (int)s.cu_acc[tile].intra_mode[0];
-            int lv[16], c[16], nv = 0;
-#pragma unroll
-            for (int j = 0; j < 16; j++) { lv[j] = w.lvl[g][j]; c[j] = w.res[g][j]; }
-            const int p = sdh_adjust_scan(scan_idx_of(2, luma ? 0 : 1, mode), lv, c, qs, qbits, nv);
-            if (p >= 0) w.lvl[g][p] = (int16_t)nv;
+            core4_sign_hide(w.blk[g], scan_idx_of(2, luma ? 0 : 1, mode), qz);
         });
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // scaling + inverse stage 1 (columns, 16-bit clip)
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 16 || !w.nz[g]) return;
-            const int x = i & 3, y = i >> 2;
-            const long long scale = (long long)16 * ls << (q / 6);
-            int acc = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc += M[j * 4 + y] * clip3(-32768, 32767, (int)((w.lvl[g][j * 4 + x] * scale + ((long long)1 << (bsh - 1))) >> bsh));
-            w.tmp[g][i] = clip3(-32768, 32767, (acc + 64) >> 7);
-        });
-        ex.wave_step([&](int tid0) {
-            const int tid = tid0 - wbase;
-            if (tid < 0 || tid >= 64) return;          // inverse stage 2 (rows), reconstruction, distortion, rate, records
-            const int g = tid >> 5, i = tid & 31;
-            if (g >= nb || i >= 16) return;
-            const int pl = pl0 + g, x = i & 3, y = i >> 2, s3 = 20 - bd, nz = (int)w.nz[g];
-            int r = 0;
-            if (nz) {
-                int acc = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc += M[j * 4 + x] * w.tmp[g][y * 4 + j];
-                r = (int)(int16_t)((acc + (1 << (s3 - 1))) >> s3);
-            }
+        block_step(16, [&](int g, int i) { core4_inv_cols(M, w.blk[g], i, qz); });
+        block_step(16, [&](int g, int i) {          // inverse stage 2 (rows), reconstruction, distortion, rate, records
+            const int pl = pl0 + g, x = i & 3, y = i >> 2, nz = (int)w.blk[g].nz;
+            const int r = core4_inv_rows(M, w.blk[g], i, bd);
             const int v = clip3(0, maxv, (int)w.pred[g][i] + r);
             const int sidx = luma ? (by + y) * 32 + bx + x : 1024 + (pl - 1) * 256 + (by + y) * 16 + bx + x;
             if (luma) s.rec_y[(by + y + 1) * RY_STRIDE + bx + x + 1] = (T)v; else s.rec_c[pl - 1][(by + y + 1) * RC_STRIDE + bx + x + 1] = (T)v;
-            s.coef_acc[sidx] = w.lvl[g][i];
-            const int d = (int)s.src[sidx] - v, al = iabs((int)w.lvl[g][i]);
+            s.coef_acc[sidx] = w.blk[g].lvl[i];
+            const int d = (int)s.src[sidx] - v, al = iabs((int)w.blk[g].lvl[i]);
             int bits = al ? rate_level(al) : 0;
             if (i == 0) {
                 if (nz) bits += R_SB + R_TU;
@@ -957,7 +899,7 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
         ex.wave_step([&](int tid0) {
             const int tid = tid0 - wbase;
             if (tid < 0 || tid >= 64) return;          // reset the per-block scratch for the next block
-            if (tid == 0) { s.mode_key = ~0ull; w.av[0] = w.av[1] = 0; w.nz[0] = w.nz[1] = 0; }
+            if (tid == 0) { s.mode_key = ~0ull; w.av[0] = w.av[1] = 0; w.blk[0].nz = w.blk[1].nz = 0; }
         });
     };
     for (int k = 0; k < 4; k++) code_blocks(1, 0, cx + (k & 1) * 4, cy + (k >> 1) * 4, k);

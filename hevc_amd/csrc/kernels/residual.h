@@ -118,14 +118,40 @@ DEV int scan_idx_of(int log2n, int c_idx, int mode)
 // raster position (y * 4 + x) of scan position n inside a 4x4 group (6.5.3 up-right diagonal, 6.5.4 horizontal, 6.5.5 vertical)
 constexpr int scan4_pos(int scan, int n) { return scan == 1 ? n : scan == 2 ? ((n & 3) << 2) | (n >> 2) : (int)((0xFBE7AD369C258140ull >> (4 * n)) & 15); }
 
+// The encoder's quantiser for one TU (flat m = 16): dead-zone quantisation with rounding offset 171/512 (intra) or 85/512 (inter),
+// and scaling (8.6.4.1).  qp is the syntax QP; the two tables (quant_scale, level_scale) are the caller's LDS copies.
+struct Quantiser {
+    int qs, qbits, bd_shift;
+    long long add, scale;
+    template <typename TQ, typename TL>
+    DEV Quantiser(int qp, int bit_depth, int log2n, int intra, const TQ *qs_tab, const TL *ls_tab)
+    {
+        const int q = qp + 6 * (bit_depth - 8);
+        qs = qs_tab[q % 6];
+        qbits = 14 + q / 6 + (15 - bit_depth - log2n);
+        bd_shift = bit_depth + log2n - 5;
+        add = (long long)(intra ? 171 : 85) << (qbits - 9);
+        scale = (long long)16 * ls_tab[q % 6] << (q / 6);
+    }
+    DEV int level(int c) const        // signed level, |level| clipped to 32767
+    {
+        const long long a = ((long long)iabs(c) * qs + add) >> qbits, m = a > 32767 ? 32767 : a;
+        return (int)(c < 0 ? -m : m);
+    }
+    DEV int dequant(int lv) const     // scaled level, clipped to 16 bit (|lv| <= 32767 and QP <= 51 keep the shifted product below 2^28)
+    {
+        return clip3(-32768, 32767, (int)((lv * scale + ((long long)1 << (bd_shift - 1))) >> bd_shift));
+    }
+};
+
 // Sign data hiding, encoder side (7.3.8.11 signHidden: the decoder infers the sign of the group's first level from the parity of its
-// absolute sum when lastSigScanPos - firstSigScanPos > 3).  One 4x4 group after quantisation: lv[16] levels and c[16] forward coefficients
-// in raster order, qs / qbits the quantiser's.  When the parity disagrees with the first level's sign, the one +-1 change whose rounding
+// absolute sum when lastSigScanPos - firstSigScanPos > 3).  One 4x4 group after quantisation by qz: lv[16] levels and c[16] forward coefficients
+// in raster order.  When the parity disagrees with the first level's sign, the one +-1 change whose rounding
 // error costs least is made (cost of scan position n: -delta for +1, delta for -1, delta = (|c| qs - |L| << qbits) >> (qbits - 8); ties
 // to the highest n; the first level may not drop to 0; a new level before the first one must carry the first one's sign; never above the
 // last level, so which TUs and groups hold levels does not change).  Returns the raster position of the changed level and its new value in
 // `nv`, or -1 when nothing changes.  SCAN is a template argument so that every index is a constant: the arrays stay in registers.
-template <int SCAN> DEV int sdh_adjust(const int (&lv)[16], const int (&c)[16], int qs, int qbits, int &nv)
+template <int SCAN> DEV int sdh_adjust(const int (&lv)[16], const int (&c)[16], const Quantiser &qz, int &nv)
 {
     int first = 16, last = -1, sum = 0;
 #pragma unroll
@@ -144,7 +170,7 @@ template <int SCAN> DEV int sdh_adjust(const int (&lv)[16], const int (&c)[16], 
     for (int n = 15; n >= 0; n--) {
         const int p = scan4_pos(SCAN, n), a = iabs(lv[p]);
         if (n > last) continue;
-        const long long u = (long long)iabs(c[p]) * qs, delta = (u - ((long long)a << qbits)) >> (qbits - 8);
+        const long long u = (long long)iabs(c[p]) * qz.qs, delta = (u - ((long long)a << qz.qbits)) >> (qz.qbits - 8);
         int chg;
         long long cost;
         if (a) {
@@ -162,9 +188,65 @@ template <int SCAN> DEV int sdh_adjust(const int (&lv)[16], const int (&c)[16], 
     }
     return bp;
 }
-DEV int sdh_adjust_scan(int scan, const int (&lv)[16], const int (&c)[16], int qs, int qbits, int &nv)
+DEV int sdh_adjust_scan(int scan, const int (&lv)[16], const int (&c)[16], const Quantiser &qz, int &nv)
 {
-    return scan == 1 ? sdh_adjust<1>(lv, c, qs, qbits, nv) : scan == 2 ? sdh_adjust<2>(lv, c, qs, qbits, nv) : sdh_adjust<0>(lv, c, qs, qbits, nv);
+    return scan == 1 ? sdh_adjust<1>(lv, c, qz, nv) : scan == 2 ? sdh_adjust<2>(lv, c, qz, nv) : sdh_adjust<0>(lv, c, qz, nv);
+}
+
+// ------------------------------------------------------------------------------------------ 4x4 core
+// One 4x4 TU (4-point DCT, or DST-VII for intra luma) with one lane per sample: the per-lane steps of the NxN trial (intra.h intra_cu_nxn)
+// and of k_transform4_blocks (transform4_program).  M is the 4x4 matrix [k * 4 + n]; i the lane's sample (y * 4 + x).  Each caller runs the
+// steps in this order, every step in a wave step or phase of its own: fwd_rows, fwd_cols_quant, (sign_hide, one lane per block,) inv_cols, inv_rows.
+struct Block4 {
+    int16_t res[16];          // residual in; the forward coefficients after fwd_cols_quant when sign hiding wants them (the residual is spent)
+    int16_t lvl[16];          // levels
+    int tmp[16];              // stage intermediates
+    unsigned nz;              // 1: the block has a non-zero level (the caller zeroes it before fwd_cols_quant)
+};
+DEV void core4_fwd_rows(const int16_t *M, Block4 &b, int i, int bit_depth)
+{
+    const int u = i & 3, y = i >> 2, s1 = bit_depth - 7;
+    int acc = 0;
+#pragma unroll
+    for (int x = 0; x < 4; x++) acc += M[u * 4 + x] * b.res[y * 4 + x];
+    b.tmp[i] = (acc + (1 << (s1 - 1))) >> s1;
+}
+template <class Ex> DEV void core4_fwd_cols_quant(Ex &ex, const int16_t *M, Block4 &b, int i, const Quantiser &qz, bool keep_coef)
+{
+    const int u = i & 3, v = i >> 2;
+    int acc = 0;
+#pragma unroll
+    for (int y = 0; y < 4; y++) acc += M[v * 4 + y] * b.tmp[y * 4 + u];
+    const int c = clip3(-32768, 32767, (acc + 128) >> 8), lv = qz.level(c);
+    b.lvl[i] = (int16_t)lv;
+    if (keep_coef) b.res[i] = (int16_t)c;
+    if (lv) ex.atomic_or(&b.nz, 1u);
+}
+DEV void core4_sign_hide(Block4 &b, int scan, const Quantiser &qz)      // a 4x4 TU is one coefficient group
+{
+    int lv[16], c[16], nv = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) { lv[j] = b.lvl[j]; c[j] = b.res[j]; }
+    const int p = sdh_adjust_scan(scan, lv, c, qz, nv);
+    if (p >= 0) b.lvl[p] = (int16_t)nv;
+}
+DEV void core4_inv_cols(const int16_t *M, Block4 &b, int i, const Quantiser &qz)      // scaling + inverse stage 1, 16-bit clip
+{
+    if (!b.nz) return;
+    const int x = i & 3, y = i >> 2;
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc += M[j * 4 + y] * qz.dequant(b.lvl[j * 4 + x]);
+    b.tmp[i] = clip3(-32768, 32767, (acc + 64) >> 7);
+}
+DEV int core4_inv_rows(const int16_t *M, const Block4 &b, int i, int bit_depth)      // -> the lane's reconstructed residual
+{
+    if (!b.nz) return 0;
+    const int x = i & 3, y = i >> 2, s3 = 20 - bit_depth;
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc += M[j * 4 + x] * b.tmp[y * 4 + j];
+    return (int)(int16_t)((acc + (1 << (s3 - 1))) >> s3);
 }
 
 // forward + quant + scaling + inverse for every TU of the region; s.desc must describe the region's samples
@@ -292,11 +374,7 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
                 store_rows(s.lvl, l, lev);
                 continue;
             }
-            const int q = (l.plane ? qp_c : qp) + 6 * (bit_depth - 8);
-            const int qbits = 14 + q / 6 + (15 - bit_depth - l.log2n), bd_shift = bit_depth + l.log2n - 5;
-            const long long add = (long long)(l.intra ? 171 : 85) << (qbits - 9);
-            const long long scale = (long long)16 * s.level_scale[q % 6] << (q / 6);
-            const int qs = s.quant_scale[q % 6];
+            const Quantiser qz(l.plane ? qp_c : qp, bit_depth, l.log2n, l.intra, s.quant_scale, s.level_scale);
             const bool cg = cg_lam_q4 > 0 && !l.intra;
             int any = 0, bits = 0;
             long long dsum = 0;
@@ -307,14 +385,11 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const int c = (int)(int16_t)(c2[i >> 1] >> (16 * (i & 1)));
-                    long long a = ((long long)iabs(c) * qs + add) >> qbits;
-                    if (a > 32767) a = 32767;
-                    const int lv = (int)(c < 0 ? -a : a);
+                    const int lv = qz.level(c);
                     lev[j][i] = lv;
                     any |= lv;
-                    const long long d = (lv * scale + ((long long)1 << (bd_shift - 1))) >> bd_shift;
-                    deq[j][i] = (int)(d < -32768 ? -32768 : d > 32767 ? 32767 : d);
-                    if (cg && lv) { bits += rate_level((int)a); dsum += (long long)deq[j][i] * (2 * c - deq[j][i]); }
+                    deq[j][i] = qz.dequant(lv);
+                    if (cg && lv) { bits += rate_level(iabs(lv)); dsum += (long long)deq[j][i] * (2 * c - deq[j][i]); }
                 }
             }
             store_rows(s.lvl, l, lev);
@@ -356,15 +431,13 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
                     c[j * 4 + i] = (int)(int16_t)(c2[i >> 1] >> (16 * (i & 1)));
                 }
             }
-            const int q = (l.plane ? qp_c : qp) + 6 * (bit_depth - 8);
-            const int qbits = 14 + q / 6 + (15 - bit_depth - l.log2n), bd_shift = bit_depth + l.log2n - 5;
+            const Quantiser qz(l.plane ? qp_c : qp, bit_depth, l.log2n, l.intra, s.quant_scale, s.level_scale);
             int nv = 0;
-            const int p = sdh_adjust_scan(l.scan, lv, c, s.quant_scale[q % 6], qbits, nv);
+            const int p = sdh_adjust_scan(l.scan, lv, c, qz, nv);
             if (p < 0) continue;
             const int y = l.y + (p >> 2), x = l.x + (p & 3);
-            const long long d = (nv * ((long long)16 * s.level_scale[q % 6] << (q / 6)) + ((long long)1 << (bd_shift - 1))) >> bd_shift;
             s.lvl[l.base + y * l.stride + x] = (int16_t)nv;
-            s.tmp[l.base + (y & ~1) * l.stride + 2 * x + (y & 1)] = (int16_t)(d < -32768 ? -32768 : d > 32767 ? 32767 : d);
+            s.tmp[l.base + (y & ~1) * l.stride + 2 * x + (y & 1)] = (int16_t)qz.dequant(nv);
         }
     });
     ex.phase([&](int tid) {      // inverse stage 1: columns, shift 7, clip to 16 bit (8.6.4.2)
@@ -432,6 +505,36 @@ DEV void residual_init_lane(ResidualShared &s, int tid)
 template <class Ex> DEV void residual_init(Ex &ex, ResidualShared &s)
 {
     ex.phase([&](int tid) { residual_init_lane(s, tid); });
+}
+
+// K3 for 4x4 TUs alone (k_transform4_blocks, the mihevc_k_transform_sdh entry for log2n 2): NT / 16 blocks from `first` on, 16 lanes per block,
+// matrix M (DST-VII when dst, else DCT), every block's group in scan `scan` with sign data hiding when sign_hide
+struct Transform4Shared {
+    int16_t M[16];
+    Block4 blk[NT / 16];
+};
+template <class Ex>
+DEV void transform4_program(Ex &ex, Transform4Shared &s, const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int first, int qp, int bit_depth,
+                            int intra, int dst, int scan, int sign_hide)
+{
+    const Quantiser qz(qp, bit_depth, 2, intra, g_tab.quant_scale, g_tab.level_scale);
+    ex.phase([&](int tid) {
+        const int g = tid >> 4, i = tid & 15, blk = first + g;
+        if (tid < 16) s.M[tid] = dst ? g_tab.dst4[tid >> 2][tid & 3] : g_tab.mat[(tid >> 2) * 8][tid & 3];
+        if (i == 0) s.blk[g].nz = 0;
+        s.blk[g].res[i] = blk < n_blocks ? res[(size_t)blk * 16 + i] : (int16_t)0;
+    });
+    ex.phase([&](int tid) { core4_fwd_rows(s.M, s.blk[tid >> 4], tid & 15, bit_depth); });
+    ex.phase([&](int tid) { core4_fwd_cols_quant(ex, s.M, s.blk[tid >> 4], tid & 15, qz, sign_hide != 0); });
+    if (sign_hide) ex.phase([&](int tid) { if (!(tid & 15)) core4_sign_hide(s.blk[tid >> 4], scan, qz); });
+    ex.phase([&](int tid) { core4_inv_cols(s.M, s.blk[tid >> 4], tid & 15, qz); });
+    ex.phase([&](int tid) {
+        const int g = tid >> 4, i = tid & 15, blk = first + g;
+        const int r = core4_inv_rows(s.M, s.blk[g], i, bit_depth);
+        if (blk >= n_blocks) return;
+        lvl[(size_t)blk * 16 + i] = s.blk[g].lvl[i];
+        rec[(size_t)blk * 16 + i] = (int16_t)r;
+    });
 }
 
 // coefficient-rate estimate of one 4x4 sub-block of levels, in 1/16 bit (oracle/hevc_oracle.c code_tu)

@@ -2,7 +2,8 @@
 // and four-wave executors over the same kernel sources, with CostParams::sign_hide taken from emu_set_sign_hide() instead of its default 0.
 // emu.cpp builds its CostParams from the frozen 16-field mihevc_cost_params by aggregate initialisation; here that name is bound, for the text
 // of emu.cpp only, to a type whose 16-argument constructor fills the same fields and then the switch.  Plus emu_transform_sdh, the stepped twin
-// of mihevc_k_transform_sdh for 4x4 DCT and 8..32-point blocks (residual_pipeline on a pseudo-CTU).  hevc_amd/ never loads this library.
+// of mihevc_k_transform_sdh for 4x4 DCT and 8..32-point blocks (residual_pipeline on a pseudo-CTU), and emu_transform4_sdh, the stepped twin of its
+// 4x4 path (k_transform4_blocks: transform4_program, DCT or DST-VII).  hevc_amd/ never loads this library.
 #include "../../hevc_amd/csrc/kernels/common.h"
 #include "../../hevc_amd/csrc/kernels/inter.h"
 #include "../../hevc_amd/csrc/kernels/intra.h"
@@ -62,6 +63,19 @@ int emu_transform_sdh(const int16_t *res, int16_t *lvl, int16_t *rec, int n_bloc
                 rec[(size_t)(first + b) * n * n + k] = s->res[o + (k / n) * st + k % n];
             }
         }
+        free(s);
+    }
+    return 0;
+}
+
+// k_transform4_blocks on n_blocks 4x4 blocks (DST-VII when dst, else DCT), the same grid of NT / 16 blocks per workgroup
+int emu_transform4_sdh(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int qp, int bit_depth, int intra, int dst, int scan, int sign_hide)
+{
+    if (scan < 0 || scan > 2) return -3;
+    SeqExec ex;
+    for (int first = 0; first < n_blocks; first += NT / 16) {
+        Transform4Shared *s = fresh_shared<Transform4Shared>();
+        transform4_program(ex, *s, res, lvl, rec, n_blocks, first, qp, bit_depth, intra, dst, scan, sign_hide);
         free(s);
     }
     return 0;

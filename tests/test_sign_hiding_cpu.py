@@ -147,15 +147,23 @@ def emu():
 
 
 def test_rule_restated_in_numpy_equals_the_stepped_k3(emu):
-    """residual_pipeline's sign hiding phase (every TU size, 4x4 DCT in the chroma planes) == the numpy rule, bit for bit, levels and reconstruction"""
-    f = emu.lib.emu_transform_sdh
+    """residual_pipeline's sign hiding phase (every TU size, 4x4 DCT in the chroma planes) == the numpy rule, bit for bit, levels and reconstruction;
+    so does the 4x4 core (k_transform4_blocks' program) on DCT and DST-VII blocks"""
+    f, f4 = emu.lib.emu_transform_sdh, emu.lib.emu_transform4_sdh
 
     def call(res, lvl, rec, count, log2n, qp, bd, intra, dst, scan):
         assert f(util.ptr(res), util.ptr(lvl), util.ptr(rec), count, log2n, qp, bd, intra, scan, 1) == 0
-    changed = 0
+
+    def call4(res, lvl, rec, count, log2n, qp, bd, intra, dst, scan):
+        assert log2n == 2 and f4(util.ptr(res), util.ptr(lvl), util.ptr(rec), count, qp, bd, intra, int(dst), scan, 1) == 0
+    changed = changed4 = 0
     for i, (log2n, scan, bd, qp, kind) in enumerate(k3_grid()):
         changed += k3_run(call, log2n, scan, bd, qp, kind, intra=i % 2)
+        if log2n == 2:
+            changed4 += k3_run(call4, log2n, scan, bd, qp, kind, intra=i % 2)
+            changed4 += k3_run(call4, log2n, scan, bd, qp, kind, intra=1, dst=True)          # the NxN trial's DST-VII luma blocks
     assert changed > 500            # the rule does change levels on this grid
+    assert changed4 > 100
 
 
 def test_stepped_k3_without_sign_hiding_is_plain_k3(emu):
@@ -168,6 +176,17 @@ def test_stepped_k3_without_sign_hiding_is_plain_k3(emu):
             for b in range(len(res)):
                 c = O.fwd_transform(res[b], False, bd)
                 assert np.array_equal(lvl[b], O.quant(c, qp, bd, True))
+    f4 = emu.lib.emu_transform4_sdh
+    for dst in (False, True):
+        for bd, qp in ((8, 22), (10, 37), (8, 0), (10, 51)):
+            for intra in (0, 1):
+                res = residuals(2, bd, "random", 40, seed=bd + qp + 2 * dst + intra)
+                lvl, rec = np.zeros_like(res), np.zeros_like(res)
+                assert f4(util.ptr(res), util.ptr(lvl), util.ptr(rec), len(res), qp, bd, intra, int(dst), 0, 0) == 0
+                for b in range(len(res)):
+                    lv = O.quant(O.fwd_transform(res[b], dst, bd), qp, bd, bool(intra))
+                    assert np.array_equal(lvl[b], lv)
+                    assert np.array_equal(rec[b], O.inv_transform(O.dequant(lv, qp, bd), dst, bd) if lv.any() else np.zeros((4, 4), np.int16))
 
 
 def groups_breaking_the_rule(a, bd):
