@@ -136,7 +136,7 @@ typedef struct mihevc_stats {
     int32_t reserved[7];              /* [0..2]: cfg.bframes = -1, the last probe; [3..5]: host microseconds of the chunks in front of their first launch, behind their last
                                        * kernel (last symbol copies + the entropy coding still open), and in all: where wall time that is not device time goes */
     /* per-stage device time, filled when cfg.profile_stages: sum of HIP-event intervals and number of launches.
-     * index: 0 intra (plan + the dataflow launch of a step), 1 me_search, 2 inter_ctu, 3 deblock (V+H; only without SAO: with SAO the loop filter is one kernel, counted
+     * index: 0 intra (plan + the anti-diagonal chain of a step), 1 me_search, 2 inter_ctu, 3 deblock (V+H; only without SAO: with SAO the loop filter is one kernel, counted
      * under 4), 4 sao (the whole loop filter: deblock of the CTU's tile + decide + apply + squared error), 5 border pad, 6 unused since ABI 2 (the SSE fold runs on the copy
      * stream), 7 intra second pass of P pictures (two rounds).  One launch covers `pictures` pictures (the lock-step batch). */
     double  stage_ms[8];
