@@ -24,7 +24,7 @@ class Config(C.Structure):
         [("md_primaries", (C.c_uint16 * 2) * 3), ("md_white", C.c_uint16 * 2), ("md_max_lum", C.c_uint32), ("md_min_lum", C.c_uint32),
          ("max_cll", C.c_uint16), ("max_fall", C.c_uint16)] +
         [(n, C.c_int32) for n in ("me_range", "gops_in_flight", "host_threads", "sao", "profile_stages", "intra_tiles", "intra_nxn", "intra_in_p", "hrd", "pre_search", "rdo_zero", "chroma_modes", "pic_height", "slice_count", "slice_index")] +
-        [("slice_ctu_rows", C.c_int32 * 16), ("rate_share_q16", C.c_int32), ("scenecut", C.c_int32), ("gop_balance", C.c_int32), ("rdo_cg", C.c_int32), ("p_tiles", C.c_int32), ("bframes", C.c_int32), ("b_qp_offset", C.c_int32), ("slice_halo", C.c_int32), ("slice_group", C.c_int32), ("sign_hide", C.c_int32)])
+        [("slice_ctu_rows", C.c_int32 * 16), ("rate_share_q16", C.c_int32), ("scenecut", C.c_int32), ("gop_balance", C.c_int32), ("rdo_cg", C.c_int32), ("p_tiles", C.c_int32), ("bframes", C.c_int32), ("b_qp_offset", C.c_int32), ("slice_halo", C.c_int32), ("slice_group", C.c_int32), ("sign_hide", C.c_int32), ("pic_hash", C.c_int32)])
 
 
 class Stats(C.Structure):
@@ -46,7 +46,7 @@ EXPORTS = (
     "mihevc_receive_packet", "mihevc_flush", "mihevc_abort", "mihevc_close", "mihevc_get_stats", "mihevc_get_headers", "mihevc_set_keep_recon",
     "mihevc_get_recon", "mihevc_coded_size", "mihevc_get_frame_info", "mihevc_strerror", "mihevc_last_error", "mihevc_cost_params_for_qp", "mihevc_tile_grid", "mihevc_p_tile_grid", "mihevc_k_transform", "mihevc_k_transform_sdh",
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
-    "mihevc_encode_picture_host",
+    "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei",
 )
 
 _lib = None
@@ -106,6 +106,8 @@ def load() -> C.CDLL:
     lib.mihevc_k_loop_filter.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.POINTER(CostParams), vp, vp, vp, vp]
     lib.mihevc_write_parameter_sets.argtypes = [C.POINTER(Config), vp, C.c_size_t]
     lib.mihevc_encode_picture_host.argtypes = [C.POINTER(Config), i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t]
+    lib.mihevc_k_picture_hash.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.mihevc_write_picture_hash_sei.argtypes = [C.POINTER(Config), i32, vp, vp, C.c_size_t]
     _lib = lib
     return lib
 

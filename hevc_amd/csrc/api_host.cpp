@@ -84,7 +84,8 @@ static int copy_out(const std::vector<uint8_t> &v, uint8_t *buf, size_t cap)
 static bool config_ok(const mihevc_config *c)
 {
     return c && c->width >= 16 && c->height >= 16 && c->width <= 8192 && c->height <= 4352 && !(c->width & 1) && !(c->height & 1) &&
-           (c->bit_depth == 8 || c->bit_depth == 10) && c->fps_num > 0 && c->fps_den > 0 && (c->sign_hide == 0 || c->sign_hide == 1);
+           (c->bit_depth == 8 || c->bit_depth == 10) && c->fps_num > 0 && c->fps_den > 0 && (c->sign_hide == 0 || c->sign_hide == 1) &&
+           c->pic_hash >= 0 && c->pic_hash <= 3 && (c->pic_hash == 0 || c->slice_count <= 1);
 }
 
 int mihevc_tile_grid(const mihevc_config *cfg, int *cols, int *rows)
@@ -108,6 +109,16 @@ int mihevc_write_parameter_sets(const mihevc_config *cfg, uint8_t *buf, size_t c
     if (!config_ok(cfg) || !buf) return MIHEVC_EINVAL;
     std::vector<uint8_t> v;
     write_parameter_sets(*cfg, v);
+    return copy_out(v, buf, cap);
+}
+
+int mihevc_write_picture_hash_sei(const mihevc_config *cfg, int hash_type, const void *values, uint8_t *buf, size_t cap)
+{
+    if (!config_ok(cfg) || !values || !buf || hash_type < 0 || hash_type > 2) return MIHEVC_EINVAL;
+    if (hash_type == 1)
+        for (int c = 0; c < 3; c++) if (((const uint32_t *)values)[c] > 0xffffu) return MIHEVC_EINVAL;
+    std::vector<uint8_t> v;
+    write_sei_picture_hash(*cfg, hash_type, values, v);
     return copy_out(v, buf, cap);
 }
 

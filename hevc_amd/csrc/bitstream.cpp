@@ -387,7 +387,8 @@ HrdInfo hrd_info(const mihevc_config &c)
     return h;
 }
 
-static void append_sei(int payload_type, BitWriter &body, std::vector<uint8_t> &out)
+// one SEI message in its own NAL unit: prefix (39) or suffix (40) SEI
+static void append_sei(int payload_type, BitWriter &body, std::vector<uint8_t> &out, int nal_type = 39)
 {
     // sei_payload: data, then payload_bit_equal_to_one + zero bits when the data is not byte aligned (D.2.1)
     if (!body.aligned()) { body.put1(1); body.align_zero(); }
@@ -396,7 +397,7 @@ static void append_sei(int payload_type, BitWriter &body, std::vector<uint8_t> &
     w.put((uint32_t)body.bytes().size(), 8);
     w.append_bytes(body.bytes().data(), body.bytes().size());
     w.trailing();
-    append_nal(out, 39, w.bytes());
+    append_nal(out, nal_type, w.bytes());
 }
 
 void write_sei_buffering_period(const mihevc_config &c, std::vector<uint8_t> &out)
@@ -420,6 +421,22 @@ void write_sei_pic_timing(const mihevc_config &c, uint32_t au_cpb_removal_delay_
     b.put(au_cpb_removal_delay_minus1 & 0xffffffu, 24);
     b.put(pic_dpb_output_delay & 31u, 5);      // clock ticks between removal from the CPB and output: 0 without reordering
     append_sei(1, b, out);
+}
+
+// D.2.19 decoded_picture_hash, a suffix SEI behind the picture's slice: hash_type u(8), then per component picture_md5[16] u(8) / picture_crc u(16) /
+// picture_checksum u(32).  values: hash_type 0 three 16-byte digests, 1 / 2 three uint32 (a CRC in the low 16 bits)
+void write_sei_picture_hash(const mihevc_config &cfg, int hash_type, const void *values, std::vector<uint8_t> &out)
+{
+    (void)cfg;
+    BitWriter b;
+    b.put((uint32_t)hash_type, 8);
+    for (int c = 0; c < 3; c++) {
+        if (hash_type == 0)
+            for (int i = 0; i < 16; i++) b.put(((const uint8_t *)values)[16 * c + i], 8);
+        else
+            b.put(((const uint32_t *)values)[c], hash_type == 1 ? 16 : 32);
+    }
+    append_sei(132, b, out, 40);
 }
 
 void write_aud(int slice_type, std::vector<uint8_t> &out)

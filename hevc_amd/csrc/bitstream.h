@@ -78,6 +78,9 @@ int slice_tile_rows(const mihevc_config &cfg, int k);
 bool idr_tiles_on(const mihevc_config &cfg);          // does PPS 1 enable tiles for the picture (a slice of it may still be one tile)
 void write_sei_hdr10(const mihevc_config &cfg, std::vector<uint8_t> &out);
 void write_aud(int slice_type, std::vector<uint8_t> &out);
+// decoded picture hash SEI (cfg.pic_hash): one suffix SEI NAL unit (type 40), payloadType 132; hash_type 0 MD5, 1 CRC, 2 checksum (D.3.19);
+// values: three 16-byte MD5 digests, or three uint32 (CRC: the low 16 bits)
+void write_sei_picture_hash(const mihevc_config &cfg, int hash_type, const void *values, std::vector<uint8_t> &out);
 // HRD signalling (cfg.hrd with a VBV): E.2.2 hrd_parameters in the VUI; D.2.2 buffering period at IRAP pictures, D.2.3 picture timing
 struct HrdInfo {
     bool on;

@@ -9,6 +9,7 @@
 #include "kernels/inter.h"
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
+#include "kernels/pichash.h"
 
 namespace mihevc {
 
@@ -43,6 +44,10 @@ template <typename T> hipError_t launch_pad(hipStream_t st, const SaoArgs<T> *d_
 // per-picture sum of squared error into args.sse[0..2] (u64, accumulated with atomics: zero the targets first)
 template <typename T> hipError_t launch_frame_sse(hipStream_t st, const SaoArgs<T> *d_args, int batch);
 template <typename T> hipError_t launch_sse_fold(hipStream_t st, const SaoArgs<T> *d_args, int n_ctu, int batch);
+// decoded picture hash (kernels/pichash.h) of the final reconstructions SaoArgs::out, coded size, every picture of the batch: kind 1 CRC, 2 checksum.
+// The three 32-bit hash words go to (uint8_t *)args.sse + out_off; `part` is scratch of pic_hash_part_words(w, h, sizeof(T)) words per picture
+int pic_hash_part_words(int w, int h, int bps);
+template <typename T> hipError_t launch_pic_hash(hipStream_t st, const SaoArgs<T> *d_args, int w, int h, int batch, int kind, uint32_t *part, size_t out_off);
 constexpr int MAX_LANES = 16;
 struct StepParams { CostParams prm[MAX_LANES]; int p_tile_cols, p_tile_rows; };      // one P step's cost parameters per lane, passed by value; the P pictures' tile grid (intra second pass: availability)
 template <typename T> hipError_t launch_begin_p_step(hipStream_t st, IntraArgs<T> *ia, InterArgs<T> *ea, SaoArgs<T> *sa, const StepParams &p, int batch);

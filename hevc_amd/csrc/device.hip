@@ -1,5 +1,6 @@
 // hevc_amd/csrc/device.hip — __global__ entry points, launchers and the per-stage C-ABI functions (mihevc_k_*).
 #include "device.h"
+#include "md5.h"
 
 #include <cstdio>
 #include <cstring>
@@ -265,6 +266,46 @@ template <typename T> hipError_t launch_sse_fold(hipStream_t st, const SaoArgs<T
     return hipGetLastError();
 }
 
+// decoded picture hash: the final reconstruction of every picture of the batch as three byte streams (kernels/pichash.h).  Segment partials,
+// then one workgroup per (component, picture) folds them in stream order: two launches, no atomics, nothing to zero in front
+// component c of the picture (args in global memory: a run-time index costs a load, not a private copy)
+template <typename T> __device__ __forceinline__ HashPlane hash_plane_of(const SaoArgs<T> &a, int c)
+{
+    return HashPlane{(const uint8_t *)a.out[c].p, (long long)a.out[c].stride * (long long)sizeof(T), (c ? a.w >> 1 : a.w) * (int)sizeof(T) / 4, c ? a.h >> 1 : a.h};
+}
+template <typename T> __global__ __launch_bounds__(NT) void k_pic_hash(const SaoArgs<T> *args, uint32_t *part, int part_words, int kind)
+{
+    __shared__ PicHashShared s;
+    GpuExec ex;
+    const SaoArgs<T> &a = args[blockIdx.y];
+    int blk = (int)blockIdx.x;
+    const int c = hash_locate(hash_blocks(hash_plane_of(a, 0)), hash_blocks(hash_plane_of(a, 1)), blk);
+    if (c < 0) return;
+    pichash_block_program(ex, s, hash_plane_of(a, c), (int)sizeof(T), kind, blk, part + (size_t)blockIdx.y * part_words + blockIdx.x);
+}
+template <typename T> __global__ __launch_bounds__(NT) void k_pic_hash_fold(const SaoArgs<T> *args, const uint32_t *part, int part_words, int kind, size_t out_off)
+{
+    __shared__ PicHashShared s;
+    GpuExec ex;
+    const SaoArgs<T> &a = args[blockIdx.y];
+    const int c = (int)blockIdx.x, first = hash_first_block(hash_blocks(hash_plane_of(a, 0)), hash_blocks(hash_plane_of(a, 1)), c);
+    pichash_fold_program(ex, s, hash_plane_of(a, c), kind, part + (size_t)blockIdx.y * part_words + first, (uint32_t *)((uint8_t *)a.sse + out_off) + c);
+}
+int pic_hash_part_words(int w, int h, int bps)
+{
+    const HashPlane y{nullptr, 0, w * bps / 4, h}, c{nullptr, 0, (w >> 1) * bps / 4, h >> 1};
+    return hash_blocks(y) + 2 * hash_blocks(c);
+}
+template <typename T> hipError_t launch_pic_hash(hipStream_t st, const SaoArgs<T> *d_args, int w, int h, int batch, int kind, uint32_t *part, size_t out_off)
+{
+    if (kind != 1 && kind != 2) return hipErrorInvalidValue;
+    const int nb = pic_hash_part_words(w, h, (int)sizeof(T));
+    hipLaunchKernelGGL(k_pic_hash<T>, dim3((unsigned)nb, (unsigned)batch), dim3(NT), 0, st, d_args, part, nb, kind);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(k_pic_hash_fold<T>, dim3(3, (unsigned)batch), dim3(NT), 0, st, d_args, (const uint32_t *)part, nb, kind, out_off);
+    return hipGetLastError();
+}
+
 // Start of a P step, one tiny launch for every lane: the step's cost parameters (QP from the rate controller, by value in the kernel
 // arguments) go into the lane's argument blocks — the rest of the blocks was uploaded with the chunk — and the per-picture accumulators
 // (SSE per plane + the rate estimate behind them: four 64-bit words at SaoArgs::sse) are zeroed.
@@ -503,6 +544,7 @@ int gfx950_device_count()
     template hipError_t launch_pad<T>(hipStream_t, const SaoArgs<T> *, int, int, int);                                  \
     template hipError_t launch_frame_sse<T>(hipStream_t, const SaoArgs<T> *, int);                                       \
     template hipError_t launch_sse_fold<T>(hipStream_t, const SaoArgs<T> *, int, int);                                   \
+    template hipError_t launch_pic_hash<T>(hipStream_t, const SaoArgs<T> *, int, int, int, int, uint32_t *, size_t);           \
     template hipError_t launch_begin_p_step<T>(hipStream_t, IntraArgs<T> *, InterArgs<T> *, SaoArgs<T> *, const StepParams &, int); \
     template hipError_t launch_extend_margin<T>(hipStream_t, Plane<T>, int, int, int, int);                             \
     template hipError_t launch_scene_diff<T>(hipStream_t, const ScenePic<T> *, unsigned long long *, int, int, int);            \
@@ -800,6 +842,24 @@ int stage_sao(const void *sy, const void *su, const void *sv, const void *dy, co
     return MIHEVC_OK;
 }
 
+// the decoded picture hash kernels alone, on reference-layout planes (the border of a session's final reconstruction around them)
+template <typename T> int stage_picture_hash(const void *sy, const void *su, const void *sv, int w, int h, int kind, uint32_t *out)
+{
+    Planes3<T> pic;
+    if (pic.alloc(w, h, true)) return MIHEVC_ENOMEM;
+    if (int e = pic.upload(sy, su, sv)) return e;
+    DevBuf dargs, dpart, dout;
+    CK(dargs.alloc(sizeof(SaoArgs<T>))); CK(dpart.alloc((size_t)pic_hash_part_words(w, h, (int)sizeof(T)) * 4)); CK(dout.alloc(3 * sizeof(uint32_t)));
+    SaoArgs<T> a{};
+    for (int i = 0; i < 3; i++) a.out[i] = pic.p[i].pl;
+    a.w = w; a.h = h; a.sse = dout.as<unsigned long long>();
+    CK(hipMemcpy(dargs.p, &a, sizeof a, hipMemcpyHostToDevice));
+    CK(launch_pic_hash<T>(0, dargs.as<SaoArgs<T>>(), w, h, 1, kind, dpart.as<uint32_t>(), 0));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -925,6 +985,23 @@ int mihevc_k_loop_filter(int device, const void *sy, const void *su, const void 
     if (prm->bit_depth == 8) return stage_sao<uint8_t>(sy, su, sv, ry, ru, rv, w, h, prm, oy, ou, ov, sao, cu);
     if (prm->bit_depth == 10) return stage_sao<uint16_t>(sy, su, sv, ry, ru, rv, w, h, prm, oy, ou, ov, sao, cu);
     return MIHEVC_EINVAL;
+}
+
+int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *v, int w, int h, int bit_depth, int hash_type, void *out)
+{
+    if (!y || !u || !v || !out || !geometry_ok(w, h) || (bit_depth != 8 && bit_depth != 10) || hash_type < 0 || hash_type > 2) return MIHEVC_EINVAL;
+    const int bps = bit_depth > 8 ? 2 : 1;
+    if (hash_type == 0) {     // MD5: on the host, as a session computes it
+        const void *pl[3] = {y, u, v};
+        for (int c = 0; c < 3; c++) {
+            const size_t row = (size_t)(c ? w / 2 : w) * bps;
+            md5_plane((const uint8_t *)pl[c], row, row, c ? h / 2 : h, (uint8_t *)out + 16 * c);
+        }
+        return MIHEVC_OK;
+    }
+    if (int e = select_device(device)) return e;
+    if (bps == 1) return stage_picture_hash<uint8_t>(y, u, v, w, h, hash_type, (uint32_t *)out);
+    return stage_picture_hash<uint16_t>(y, u, v, w, h, hash_type, (uint32_t *)out);
 }
 
 #ifdef MIHEVC_PHASE_PROF

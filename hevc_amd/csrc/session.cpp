@@ -25,6 +25,7 @@
 
 #include "bitstream.h"
 #include "device.h"
+#include "md5.h"
 #include "ratectl.h"
 #include "slice_group.h"
 
@@ -147,10 +148,10 @@ struct Packet {
     std::string error;      // the host coder refused the picture's levels (sign data hiding parity): mihevc_receive_packet fails with MIHEVC_EINVAL here
 };
 
-// symbol block of one picture: [cu | coef Y | coef U | coef V | sao | sse[3] | rate estimate]; the device twin carries the per-CTU squared errors behind it
-// (SaoArgs::sse_ctu: never copied to the host, k_sse_fold turns them into sse[3])
+// symbol block of one picture: [cu | coef Y | coef U | coef V | sao | sse[3] | rate estimate | hash[3]]; the device twin carries the per-CTU squared errors
+// behind it (SaoArgs::sse_ctu: never copied to the host, k_sse_fold turns them into sse[3]).  hash: the CRC / checksum words of cfg.pic_hash 2 / 3 (k_pic_hash_fold)
 struct SymLayout {
-    size_t cu, cu_bytes, cy, cu_, cv, sao, sse, est, total, sse_ctu, dev_total;
+    size_t cu, cu_bytes, cy, cu_, cv, sao, sse, est, hash, total, sse_ctu, dev_total;
     SymLayout(int w, int h)
     {
         size_t n8 = (size_t)(w / 8) * (h / 8), ny = (size_t)w * h, nctu = (size_t)((w + 31) / 32) * ((h + 31) / 32);
@@ -164,7 +165,8 @@ struct SymLayout {
         sao = al(cv + ny / 2);
         sse = al(sao + nctu * sizeof(mihevc_sao_ctu));
         est = sse + 3 * sizeof(unsigned long long);
-        total = al(est + sizeof(unsigned long long));
+        hash = est + sizeof(unsigned long long);
+        total = al(hash + 3 * sizeof(uint32_t));
         sse_ctu = total;
         dev_total = al(sse_ctu + nctu * 3 * sizeof(uint32_t));
     }
@@ -211,6 +213,7 @@ struct mihevc_session {
         IpInfo *ip = nullptr;      // per CTU: inter pass -> intra second pass of P pictures
         IntraPlan *plan = nullptr; // per CTU: k_intra_plan -> k_intra_diag (IDR pictures)
         uint8_t *sym_dev[kRing] = {nullptr}, *sym_host[kRing] = {nullptr};
+        uint8_t *md5_host[kRing] = {nullptr};      // cfg.pic_hash 1: the final picture (coded size, Y U V without gaps), pinned, per ring slot
     };
     std::vector<Lane> lane;
     CachedBuf args;                   // argument blocks of a whole chunk (device + pinned staging)
@@ -250,6 +253,9 @@ struct mihevc_session {
     size_t x1_part_bytes = 0, x1_lane_bytes = 0, x1_bytes = 0;
     CachedBuf jobs;                           // row-copy job tables of a chunk (device + pinned staging)
     std::vector<int> peers_enabled;
+    // ---- decoded picture hash (cfg.pic_hash)
+    uint32_t *hash_part = nullptr;            // 2 / 3: segment partials of k_pic_hash, MAX_LANES pictures (device)
+    size_t hash_part_bytes = 0;
 };
 
 namespace {
@@ -270,6 +276,7 @@ int fail(mihevc_session *s, std::string msg)
     } while (0)
 
 size_t esize(const mihevc_session *s) { return s->is16 ? 2 : 1; }
+size_t md5_pic_bytes(const mihevc_session *s) { return (size_t)s->w * s->h * 3 / 2 * esize(s); }
 
 // padded 0: a plain picture; 1: a reference picture with its PAD border all round; 2: a work picture with kSeamRows rows above and below (the rows the
 // neighbour slices hand over for deblocking across seams; unused otherwise)
@@ -301,6 +308,7 @@ int ensure_lanes(mihevc_session *s, int n)
         for (int k = 0; k < s->ring; k++) {
             HIPCK(s, BufferCache::get().alloc(s->device, sl.dev_total, false, (void **)&L.sym_dev[k]));
             HIPCK(s, BufferCache::get().alloc(s->device, sl.total, true, (void **)&L.sym_host[k]));
+            if (s->cfg.pic_hash == 1) HIPCK(s, BufferCache::get().alloc(s->device, md5_pic_bytes(s), true, (void **)&L.md5_host[k]));
         }
         s->lane.push_back(L);
     }
@@ -361,6 +369,7 @@ struct PictureJob {
     std::atomic<long long> ns{0};
     std::mutex err_m;
     std::string err;        // first refusal of any part (encode_tiles)
+    uint8_t md5[3][16];     // cfg.pic_hash 1: written by the job's MD5 part
 };
 
 void picture_symbols(mihevc_session *s, int slot, int lane_i, PictureSyms &pic)
@@ -395,6 +404,8 @@ void publish_picture(PictureJob *j)
                              j->reorder ? (uint32_t)(j->poc + 1 - j->dec_pos) : 0u);
     }
     assemble_picture(s->cfg, j->pic, j->sub, pk.data, false);
+    // decoded picture hash: a suffix SEI behind the slice (cfg.pic_hash 1 MD5 from the job's MD5 part, 2 / 3 the device's words in the symbol block)
+    if (s->cfg.pic_hash) write_sei_picture_hash(s->cfg, s->cfg.pic_hash - 1, s->cfg.pic_hash == 1 ? (const void *)j->md5 : (const void *)(b + sl.hash), pk.data);
     const unsigned long long *sse = (const unsigned long long *)(b + sl.sse);
     pk.ready = true;
     auto t1 = std::chrono::steady_clock::now();
@@ -430,6 +441,23 @@ void entropy_part(PictureJob *j, int part)
     std::string err;
     encode_tiles(j->s->cfg, j->pic, t_a, t_b, j->sub, &err);
     if (!err.empty()) { std::lock_guard<std::mutex> l(j->err_m); if (j->err.empty()) j->err = "picture " + std::to_string(j->index) + ": " + err; }
+    j->ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (j->left.fetch_sub(1) == 1) publish_picture(j);
+}
+
+// cfg.pic_hash 1: MD5 of the picture's three components from the pinned copy of the final reconstruction, beside the CABAC parts of its job
+void md5_part(PictureJob *j)
+{
+    mihevc_session *s = j->s;
+    auto t0 = std::chrono::steady_clock::now();
+    const uint8_t *p = s->lane[j->lane_i].md5_host[j->slot];
+    const size_t es = esize(s);
+    for (int c = 0; c < 3; c++) {
+        const size_t row = (size_t)(c ? s->w / 2 : s->w) * es;
+        const int rows = c ? s->h / 2 : s->h;
+        md5_plane(p, row, row, rows, j->md5[c]);
+        p += row * rows;
+    }
     j->ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
     if (j->left.fetch_sub(1) == 1) publish_picture(j);
 }
@@ -1093,6 +1121,18 @@ template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, 
     // picture and 25 us per step beside the compute stream.)  Without SAO that pass still runs: k_sao_apply is a plain copy and has no source.
     if (s->cfg.sao) HIPCK(s, launch_sse_fold<T>(s->st_copy, dv.sao, s->n_ctu, B));
     else HIPCK(s, launch_frame_sse<T>(s->st_copy, dv.sao, B));
+    // decoded picture hash of the final pictures (coded area only: the border is the next step's pad), in front of the symbol copies that carry it.
+    // The compute stream reuses these picture buffers two steps later, behind ev_copy of this step (rate_feedback)
+    if (s->cfg.pic_hash >= 2) HIPCK(s, launch_pic_hash<T>(s->st_copy, dv.sao, s->w, s->h, B, s->cfg.pic_hash - 1, s->hash_part, sl.hash - sl.sse));
+    for (int g = 0; s->cfg.pic_hash == 1 && g < B; g++) {      // MD5: the picture to pinned memory for the CABAC job (no wait here)
+        uint8_t *dst = s->lane[g].md5_host[slot];
+        const size_t es = esize(s);
+        for (int i = 0; i < 3; i++) {
+            const int pw = i ? s->w / 2 : s->w, ph = i ? s->h / 2 : s->h;
+            HIPCK(s, hipMemcpy2DAsync(dst, pw * es, s->lane[g].rec_p[c.step(g, t).cur][i], s->lane[g].rec_stride[i] * es, pw * es, ph, hipMemcpyDeviceToHost, s->st_copy));
+            dst += (size_t)pw * ph * es;
+        }
+    }
     for (int g = 0; g < B; g++) {   // CU records, then SAO parameters + SSE + rate estimate (the level planes were written to the host block directly)
         uint8_t *hd = s->lane[g].sym_host[slot], *dd = s->lane[g].sym_dev[slot];
         HIPCK(s, hipMemcpyAsync(hd + sl.cu, dd + sl.cu, sl.cu_bytes, hipMemcpyDeviceToHost, s->st_copy));
@@ -1143,13 +1183,20 @@ template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, int t,
         j->n_tiles = picture_tiles(s->cfg, j->pic);
         j->parts = std::min(j->n_tiles, parts_wanted);
         j->sub.resize((size_t)j->n_tiles);
-        j->left.store(j->parts);
+        const bool md5 = s->cfg.pic_hash == 1;
+        j->left.store(j->parts + (md5 ? 1 : 0));
         hipEvent_t ev = s->ev_copy[j->slot];
         for (int part = 0; part < j->parts; part++)
             s->pool->submit([s, j, part, ev] {
                 (void)hipSetDevice(s->device);          // worker threads start on device 0: wait on the event in its own device's context
                 (void)hipEventSynchronize(ev);
                 entropy_part(j, part);
+            });
+        if (md5)
+            s->pool->submit([s, j, ev] {
+                (void)hipSetDevice(s->device);
+                (void)hipEventSynchronize(ev);
+                md5_part(j);
             });
     }
 }
@@ -1271,6 +1318,7 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     if (cfg->width < 16 || cfg->height < 16 || (cfg->width & 1) || (cfg->height & 1) || cfg->width > 8192 || cfg->height > 4352) return MIHEVC_EINVAL;
     if (cfg->bit_depth != 8 && cfg->bit_depth != 10) return MIHEVC_EINVAL;
     if (cfg->sign_hide != 0 && cfg->sign_hide != 1) return MIHEVC_EINVAL;
+    if (cfg->pic_hash < 0 || cfg->pic_hash > 3 || (cfg->pic_hash && cfg->slice_count > 1)) return MIHEVC_EINVAL;      // hashes of sliced pictures: not yet
     if (cfg->fps_num <= 0 || cfg->fps_den <= 0 || cfg->keyint < 1 || cfg->keyint > 240) return MIHEVC_EINVAL;
     if (cfg->bframes < -1 || cfg->bframes > 1 || (cfg->bframes && cfg->slice_count > 1)) return MIHEVC_EINVAL;      // B pictures: whole pictures only (for now)
     if (cfg->slice_count > 1) {        // one slice of a picture: a band of whole CTU rows (the last band takes the picture's remainder)
@@ -1315,6 +1363,10 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
              hipEventCreateWithFlags(&s->ev_copy[i], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&s->ev_pre, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s->ev_args, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming) == hipSuccess;
+    if (ok && cfg->pic_hash >= 2) {
+        s->hash_part_bytes = (size_t)MAX_LANES * pic_hash_part_words(s->w, s->h, (int)esize(s)) * sizeof(uint32_t);
+        ok = BufferCache::get().alloc(s->device, s->hash_part_bytes, false, (void **)&s->hash_part) == hipSuccess;
+    }
     if (!ok) { mihevc_close(s); return MIHEVC_EDEVICE; }      // gives back what was acquired (event handles of the slots never reached stay null)
     if (cfg->slice_count > 1 && cfg->slice_halo) {
         // one slice of a picture whose slices exchange rows: meet the others (csrc/slice_group.h), and get the buffers the neighbours read
@@ -1536,7 +1588,9 @@ void mihevc_close(mihevc_session *s)
         bc.release(s->device, (size_t)s->n_ctu * sizeof(IpInfo), false, L.ip);
         bc.release(s->device, (size_t)s->n_ctu * sizeof(IntraPlan), false, L.plan);
         for (int k = 0; k < s->ring; k++) { bc.release(s->device, sl.dev_total, false, L.sym_dev[k]); bc.release(s->device, sl.total, true, L.sym_host[k]); }
+        for (int k = 0; k < s->ring; k++) bc.release(s->device, md5_pic_bytes(s), true, L.md5_host[k]);
     }
+    bc.release(s->device, s->hash_part_bytes, false, s->hash_part);
     for (CachedBuf *b : {&s->args, &s->scene, &s->low, &s->jobs, &s->probe}) { bc.release(s->device, b->cap, false, b->d); bc.release(s->device, b->cap, true, b->h); }
     for (int i = 0; i < kRing; i++) { if (s->ev_compute[i]) (void)hipEventDestroy(s->ev_compute[i]); if (s->ev_copy[i]) (void)hipEventDestroy(s->ev_copy[i]); }
     for (auto e : s->ev_pool) (void)hipEventDestroy(e);

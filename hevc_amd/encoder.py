@@ -54,9 +54,10 @@ def lanes_for(total_frames: int, keyint: int) -> int:
 
 
 def config_for(info: VideoInfo, crf: int, vbv_maxrate: int, vbv_bufsize: int, gop: int, level: str, tier: str,
-               master_display: str = "", max_cll: str = "", sign_hide: int = 0) -> _lib.Config:
+               master_display: str = "", max_cll: str = "", sign_hide: int = 0, pic_hash: int = 0) -> _lib.Config:
     """Map the reference's libx265 operating point (build_ffmpeg_params CPU branch) onto a mihevc_config.  sign_hide=1: sign data
-    hiding (x265 signhide, on in its presets; off here by default until the measured gain decides)."""
+    hiding (x265 signhide, on in its presets; off here by default until the measured gain decides).  pic_hash: decoded picture hash
+    SEI in every access unit, x265 hash= numbering (0 off, 1 MD5, 2 CRC, 3 checksum)."""
     from .utils import parse_master_display, parse_max_cll
     cfg = _lib.default_config()
     cfg.width, cfg.height = int(info.width), int(info.height)
@@ -72,6 +73,7 @@ def config_for(info: VideoInfo, crf: int, vbv_maxrate: int, vbv_bufsize: int, go
     cfg.keyint, cfg.min_keyint = int(gop), max(2, int(gop) // 2)
     cfg.gops_in_flight = lanes_for(int(getattr(info, 'nb_frames', 0) or 0), int(gop))
     cfg.sign_hide = int(sign_hide)
+    cfg.pic_hash = int(pic_hash)
     if hdr:   # the HDR10 set of core/utils.py:58-69
         cfg.colour_primaries, cfg.transfer, cfg.matrix = 9, 16, 9
         cfg.chroma_loc, cfg.aud, cfg.repeat_headers, cfg.hdr10, cfg.hrd = 0, 1, 1, 1, 1       # ... hrd=1:aud=1:chromaloc=0:repeat-headers=1

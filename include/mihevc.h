@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MIHEVC_ABI_VERSION 4
+#define MIHEVC_ABI_VERSION 5
 
 typedef enum {
     MIHEVC_OK = 0,
@@ -124,6 +124,12 @@ typedef struct mihevc_config {
                                        * absolute sum; the kernels adjust one level per group where the parity disagrees (the cheapest +-1 by rounding error).  Every
                                        * path that produces coded levels does it.  The host coder checks the rule in every group it codes and fails the picture with
                                        * MIHEVC_EINVAL when one breaks it.  0 (default): off.  Any other value: MIHEVC_EINVAL at open and in mihevc_write_parameter_sets */
+    /* ---- ABI 5 ---- */
+    int32_t pic_hash;                 /* decoded picture hash SEI (x265 hash): every access unit carries, in a suffix SEI NAL unit (type 40, payloadType 132) behind its
+                                       * slice, a hash of each colour component of the encoder's final reconstruction over the CODED size, which any conforming decoder
+                                       * can check the picture it decodes against.  0 (default): off; 1 MD5 (the final picture is copied to pinned host memory and hashed by
+                                       * the CABAC job: a verification mode, host-bound); 2 CRC; 3 checksum (both on the device, on the copy stream beside the next step).
+                                       * Any other value, or a value != 0 with slice_count > 1: MIHEVC_EINVAL at open and in mihevc_write_parameter_sets */
 } mihevc_config;
 
 typedef struct mihevc_session mihevc_session;
@@ -280,9 +286,17 @@ int mihevc_k_loop_filter(int device, const void *src_y, const void *src_u, const
                          const void *rec_y, const void *rec_u, const void *rec_v, int width, int height, const mihevc_cu_rec *cu,
                          const mihevc_cost_params *prm, void *out_y, void *out_u, void *out_v, mihevc_sao_ctu *sao);
 
+/* Decoded picture hash (H.265 Annex D, SEI payloadType 132) of one picture, host planes as above (width x height luma, chroma 4:2:0; coded sizes:
+ * multiples of 8): hash_type 0 MD5 (on the host; no device needed), 1 CRC, 2 checksum (the session's kernels).  out: hash_type 0 three 16-byte digests
+ * (Y, Cb, Cr), else three uint32_t (a CRC in the low 16 bits) */
+int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *v, int width, int height, int bit_depth, int hash_type, void *out);
+
 /* ---- host-only stages (no device needed): bitstream ---- */
 /* VPS+SPS+PPS (+SEI when hdr10) as Annex-B into buf; returns size or negative error */
 int mihevc_write_parameter_sets(const mihevc_config *cfg, uint8_t *buf, size_t cap);
+/* The decoded picture hash suffix SEI NAL unit (Annex-B, type 40, payloadType 132) into buf: hash_type 0 MD5, 1 CRC, 2 checksum; values as the
+ * out of mihevc_k_picture_hash.  Returns size or negative error */
+int mihevc_write_picture_hash_sei(const mihevc_config *cfg, int hash_type, const void *values, uint8_t *buf, size_t cap);
 /* CABAC-code one picture from its symbols into one slice NAL (+AUD when cfg->aud); returns size or negative error.
  * slice_type 2 = I (IDR), 1 = P, 0 = B (cfg->bframes); poc = position inside the closed GOP in display order. */
 int mihevc_encode_picture_host(const mihevc_config *cfg, int slice_type, int poc, int qp,
