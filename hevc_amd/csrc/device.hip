@@ -33,24 +33,21 @@ template <typename T> __global__ __launch_bounds__(NT, 5) void k_me_search(const
     } else me_search_program<T>(ex, s, win, args[blockIdx.y], ctu);
 }
 
-// 4 workgroups per CU (97 / 116 VGPRs for 8 / 10 bit and no scratch since the fractional search runs two lanes per tile; LDS allows 4 at
-// 8 bit, 3 at 10 bit)
-template <typename T> __global__ __launch_bounds__(NT, 4) void k_inter_ctu(const InterArgs<T> *args, int n_ctu)
+// 5 workgroups per CU at 8 bit (89 VGPRs, no scratch; the windows overlay the residual area, inter_lds: 31,440 B of LDS at me_range 15), 3 at
+// 10 bit (LDS).  Y_IN: the luma window lies in rs.scratch (inter_lds); its offset is a compile-time constant either way.  From a runtime base the
+// compiler merges the window's 4-byte-aligned dword reads into ds_read_b128 / b96, mostly misaligned, and the LDS replays them
+// (SQ_LDS_UNALIGNED_STALL 2.8e7 -> 9.7e7 per launch against the ds_read2_b32 pairs of a constant base, DESIGN.md §6a')
+template <typename T, bool Y_IN> __global__ __launch_bounds__(NT, (sizeof(T) == 1 ? 5 : 4)) void k_inter_ctu(const InterArgs<T> *args, int n_ctu)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int ctu = xcd_remap(blockIdx.x, n_ctu);
     if (ctu >= n_ctu) return;
     const InterArgs<T> &a = args[blockIdx.y];
-    const int R = a.prm.me_range;
+    const InterLds l = inter_lds<T>(a.prm.me_range);
     InterShared<T> &s = *reinterpret_cast<InterShared<T> *>(smem);
-    size_t off = round16(sizeof(InterShared<T>));
-    T *wy = reinterpret_cast<T *>(smem + off);
-    off += round16(((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T));
-    T *wu = reinterpret_cast<T *>(smem + off);
-    off += round16(((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T));
-    T *wv = reinterpret_cast<T *>(smem + off);
+    T *wy = reinterpret_cast<T *>(smem + (Y_IN ? inter_win_in<T>() : inter_win_out<T>()));
     GpuExec ex;
-    inter_ctu_program<T>(ex, s, wy, wu, wv, a, ctu);
+    inter_ctu_program<T>(ex, s, wy, reinterpret_cast<T *>(smem + l.u), reinterpret_cast<T *>(smem + l.v), a, ctu);
 }
 
 // B pictures: the same CTU program with the list-1 refinement and the bi-prediction trial (BiShared sits behind the windows); 3 workgroups per CU
@@ -390,12 +387,12 @@ template <typename T> hipError_t launch_me_search(hipStream_t st, const InterArg
 
 template <typename T> hipError_t launch_inter_ctu(hipStream_t st, const InterArgs<T> *d_args, int n_ctu, int batch, int R)
 {
-    size_t smem = round16(sizeof(InterShared<T>)) + round16(((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T)) +
-                  2 * round16(((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T));
-    hipError_t e = ensure_smem(k_inter_ctu<T>, smem);
+    const InterLds l = inter_lds<T>(R);
+    auto kernel = l.y == inter_win_in<T>() ? k_inter_ctu<T, true> : k_inter_ctu<T, false>;
+    hipError_t e = ensure_smem(kernel, l.bytes);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((n_ctu + 7) >> 3) << 3), (unsigned)batch);
-    hipLaunchKernelGGL(k_inter_ctu<T>, grid, dim3(NT), smem, st, d_args, n_ctu);
+    hipLaunchKernelGGL(kernel, grid, dim3(NT), l.bytes, st, d_args, n_ctu);
     return hipGetLastError();
 }
 

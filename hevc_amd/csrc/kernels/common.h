@@ -348,6 +348,15 @@ DEV void load_ctu_source(T *dst, const Plane<const T> (&src)[3], int x0, int y0,
     }
 }
 
+// a value that is the same in every lane, held in a scalar register: a 16-bit global load (no scalar form on gfx950) leaves it and everything
+// derived from it in VGPRs for the whole program otherwise
+DEV int wave_uniform(int v)
+{
+#if MIHEVC_GPU
+    v = __builtin_amdgcn_readfirstlane(v);
+#endif
+    return v;
+}
 // returns 0 in a way the optimiser cannot see through: stops loop-invariant hoisting of whole LDS tiles into VGPRs
 DEV int opaque_zero()
 {
@@ -564,6 +573,10 @@ struct GpuExec {
     template <class F> DEV void wave_step(F &&f)
     {
         f(lane_id());
+        wave_sync();
+    }
+    static DEV void wave_sync()
+    {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -577,7 +590,24 @@ struct GpuExec {
     DEV unsigned long long peek(const unsigned long long *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
     DEV void atomic_add_global(unsigned long long *p, unsigned long long v) { atomicAdd(p, v); }
 };
+// wave_chain (below) on the device: one straight stretch of code, the lane's state stays in its registers
+template <class F, class... G> DEV void wave_chain(GpuExec &, F &&first, G &&...then)
+{
+    const int tid = GpuExec::lane_id();
+    auto st = first(tid);
+    GpuExec::wave_sync();
+    ((then(tid, st), GpuExec::wave_sync()), ...);
+}
 #endif
+// wave_chain(ex, first, then...): a sequence of wave-local steps (as wave_step) in which every step after the first continues with the lane's own
+// values: first(tid) returns the lane's state, each later step runs as step(tid, state).  A stepping executor runs every step over all its lanes
+// before the next one, so it keeps the lanes' states in an array.
+template <class Ex, class F, class... G> DEV void wave_chain(Ex &ex, F &&first, G &&...then)
+{
+    decltype(first(0)) st[NT];
+    ex.wave_step([&](int tid) { st[tid] = first(tid); });
+    (ex.wave_step([&](int tid) { then(tid, st[tid]); }), ...);
+}
 struct SeqExec {      // sequential stepping of a phase program (tests/emu)
     // order 0: threads 0..NT-1; 1: NT-1..0; 2: a fresh pseudo-random permutation per phase.  A program without races inside a phase
     // gives the same result in every order (tests/test_kernel_source_stepped.py).

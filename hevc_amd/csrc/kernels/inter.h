@@ -405,13 +405,38 @@ template <typename T> struct InterShared {
     unsigned ip_cost, ip_act, ip_tiles;   // intra second pass: chosen CUs' cost, source AC activity, tiles inside the picture
     unsigned long long ip_sse;
     unsigned tu_dc[3][16], tu_dz[3][16], tu_bits[3][16], tu_zero[3];   // RD zero-out: per TU (plane, first 8x8 tile) SSE coded / zeroed, level bits
-    // followed in LDS by: T winY[(40 + 2R)^2 (stride padded)], T winU[(24 + R)^2], T winV[...]
+    // the motion-compensation windows T winY[(40 + 2R)^2 (stride padded)], T winU[(24 + R)^2], T winV[...]: inside rs.scratch or behind this struct (inter_lds)
 };
+// the fractional search's share of rs.scratch (dwords): the pair exchange, 8 per lane, then one SATD share per lane
+constexpr int FRAC_PAIR_SUM = 8 * NT;
+constexpr int FRAC_SCRATCH = FRAC_PAIR_SUM + NT;
+static_assert(FRAC_SCRATCH <= (int)(sizeof(ResidualShared::scratch) / 4), "the fractional search's exchange must fit rs.scratch");
 // motion-compensation windows cover every vector the search can return: |mv| <= R + 3 (widened horizontal span)
 HDI int mc_win_y(int R) { return (32 + 2 * (R + 3) + 8 + 3) & ~3; }
 HDI int mc_win_y_stride(int R) { return mc_win_y(R) + 4; }
 HDI int mc_win_c(int R) { return (16 + (R + 3) + 8 + 3) & ~3; }
 HDI int mc_win_c_stride(int R) { return mc_win_c(R) + 4; }
+
+// Dynamic LDS of k_inter_ctu (P pictures): InterShared, and the luma, Cb and Cr windows, byte offsets from its start.  rs.scratch is idle from the
+// end of the fractional search until the residual is formed, and the windows are read only before that (motion compensation is their last reader,
+// and the barrier that ends its phase comes before the phase that writes rs.res / rs.desc): each window, in that order, goes into rs.scratch behind
+// the search's share if it still fits, otherwise behind InterShared (the luma window, placed first, is at inter_win_in or inter_win_out).
+// 8 bit at me_range 15: luma and Cb inside, Cr behind.
+struct InterLds { size_t y, u, v, bytes; };
+template <typename T> HDI constexpr size_t inter_win_in() { return offsetof(InterShared<T>, rs) + offsetof(ResidualShared, scratch) + 4 * (size_t)FRAC_SCRATCH; }
+template <typename T> HDI constexpr size_t inter_win_out() { return (sizeof(InterShared<T>) + 15) & ~(size_t)15; }
+template <typename T> HDI InterLds inter_lds(int R)
+{
+    const size_t n[3] = {((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T), ((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T),
+                         ((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T)};
+    const size_t hi = offsetof(InterShared<T>, rs) + offsetof(ResidualShared, scratch) + sizeof(ResidualShared::scratch);
+    size_t in = inter_win_in<T>(), out = inter_win_out<T>(), at[3];
+    for (int i = 0; i < 3; i++) {
+        const size_t r = (n[i] + 15) & ~(size_t)15;
+        if (in + r <= hi) { at[i] = in; in += r; } else { at[i] = out; out += r; }
+    }
+    return InterLds{at[0], at[1], at[2], out};
+}
 
 // quarter-sample luma prediction of one 8x8 tile from the LDS window (8.5.3.3.3.1; the general 2-D form with the
 // {0,0,0,64,0,0,0,0} tap set for a zero fraction is exact for every case).  p00 = window sample at the tile's
@@ -910,7 +935,7 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
     const int R0 = a.prm.me_range, R = R0 + 3, bd = a.prm.bit_depth, lam = a.prm.lambda_sad_q4;
     const int x0 = (ctu % a.ctus_w) * CTU, y0 = (ctu / a.ctus_w) * CTU;
     const int mct = a.prm.mc_top, mcb = a.prm.mc_bottom;
-    const int sx = a.centers ? a.centers[2 * ctu] : 0, sy0 = a.centers ? a.centers[2 * ctu + 1] : 0;
+    const int sx = wave_uniform(a.centers ? a.centers[2 * ctu] : 0), sy0 = wave_uniform(a.centers ? a.centers[2 * ctu + 1] : 0);
     const int sy = (mct || mcb) ? clamp_center_y(sy0, y0, R0, a.h, mct, mcb) : sy0;
     const int wy = mc_win_y(R0), wys = mc_win_y_stride(R0), wc = mc_win_c(R0), wcs = mc_win_c_stride(R0);
     const int oy_x = x0 + sx - R - 4, oy_y = y0 + sy - R - 4;                                  // luma window origin
@@ -991,10 +1016,13 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
     auto refine = [&](const int csx, const int csy, const int wox, const int woy) {
     for (int round = 0; round < 2; round++) {
         const int step = round == 0 ? 2 : 1;
-        // 16 tiles x 8 ring positions x 2 column halves = the whole workgroup.  Wave-local steps: both lanes of a pair sit in one wave.
-        ex.wave_step([&](int tid) {
+        // 16 tiles x 8 ring positions x 2 column halves = the whole workgroup.  Wave-local steps: both lanes of a pair sit in one wave.  A lane keeps the
+        // rows it finishes (4 half .. 4 half + 3) in registers and passes only the other four rows to its partner through rs.scratch
+        struct Kept { uint32_t v[2][4]; };
+        wave_chain(ex, [&](int tid) -> Kept {
             const int u = tid >> 1, half = tid & 1, k = kRingSlot[u >> 4], t = u & 15;
-            if (!s.rs.tu_log2[t]) return;
+            Kept kept{};
+            if (!s.rs.tu_log2[t]) return kept;
             const int txp = t & 3, typ = t >> 2, node = s.tile_node[t];
             const int mx = s.mvx[node] + kOff[k][0] * step, my = s.mvy[node] + kOff[k][1] * step;
             const int px = x0 + txp * 8 + 4 * half + (mx >> 2) - wox, py = y0 + typ * 8 + (my >> 2) - woy;
@@ -1016,31 +1044,41 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
                     const uint32_t a0 = pk_add16(P[0][c], P[1][c]), a1 = pk_sub16(P[0][c], P[1][c]), a2 = pk_add16(P[2][c], P[3][c]), a3 = pk_sub16(P[2][c], P[3][c]);
                     P[0][c] = pk_add16(a0, a2); P[1][c] = pk_add16(a1, a3); P[2][c] = pk_sub16(a0, a2); P[3][c] = pk_sub16(a1, a3);
                 }
-                uint32_t *x = s.rs.scratch + tid * 16;
-                const int sw = tid >> 2;
+                uint32_t o[4][4];      // chunk r2 = rows 2 r2, 2 r2 + 1 of the four columns
 #pragma unroll
                 for (int r2 = 0; r2 < 4; r2++) {
                     const uint32_t p0 = pk_add16(P[r2][0], P[r2][1]), p1 = pk_sub16(P[r2][0], P[r2][1]), p2 = pk_add16(P[r2][2], P[r2][3]), p3 = pk_sub16(P[r2][2], P[r2][3]);
-                    const uint32_t o[4] = {pk_add16(p0, p2), pk_add16(p1, p3), pk_sub16(p0, p2), pk_sub16(p1, p3)};
-                    store_x4(x + 4 * ((r2 + sw) & 3), o);        // chunk r2 = rows 2 r2, 2 r2 + 1 of the four columns; rotated as below
+                    o[r2][0] = pk_add16(p0, p2); o[r2][1] = pk_add16(p1, p3); o[r2][2] = pk_sub16(p0, p2); o[r2][3] = pk_sub16(p1, p3);
+                }
+                uint32_t *x = s.rs.scratch + tid * 8;
+                const int sw = ((tid >> 2) ^ (tid >> 3)) & 1;
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    uint32_t send[4];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) { kept.v[c][i] = half ? o[2 + c][i] : o[c][i]; send[i] = half ? o[c][i] : o[2 + c][i]; }
+                    store_x4(x + 4 * (c ^ sw), send);
                 }
             }
-        });
-        ex.wave_step([&](int tid) {      // the last butterfly stage across the halves: this lane takes rows 4 half .. 4 half + 3
-            const int u = tid >> 1, half = tid & 1, t = u & 15;
+            return kept;
+        }, [&](int tid, const Kept &kept) {      // the last butterfly stage across the halves: this lane takes rows 4 half .. 4 half + 3
+            const int u = tid >> 1, t = u & 15;
             if (!s.rs.tu_log2[t]) return;
-            const uint32_t *xa = s.rs.scratch + (tid & ~1) * 16, *xb = xa + 16;      // the pair's two blocks (both lanes of a pair share lane >> 2)
-            const int sw = tid >> 2;
+            // the partner's chunks of these rows.  Slot c of lane l sits at dword 8 l + 4 (c ^ sw), sw = bit 2 ^ bit 3 of l (the same for both lanes of a
+            // pair): the eight-lane groups of ds_write_b128 and the sixteen-lane groups of ds_read_b128 then touch every bank once
+            const uint32_t *xp = s.rs.scratch + (tid ^ 1) * 8;
+            const int sw = ((tid >> 2) ^ (tid >> 3)) & 1;
             unsigned sum = 0;
             {
                 // packed form: the stage across the halves on whole dwords, then 2 max(|lo|, |hi|) per dword for the stage inside it + the absolute sum.  At 8 bit |values| <= 255 x 32
-                // here, so eight maxima still fit the 16-bit lanes of an accumulator; at 10 bit (1023 x 32) every maximum is widened
+                // here, so eight maxima still fit the 16-bit lanes of an accumulator; at 10 bit (1023 x 32) every maximum is widened.  |a + b| and |a - b| do not
+                // depend on which half is a: the lane's own rows and its partner's enter in either order
                 uint32_t acc[2] = {0, 0};
 #pragma unroll
                 for (int c = 0; c < 2; c++) {
-                    uint32_t va[4], vb[4];
-                    const int at = 4 * ((2 * half + c + sw) & 3);
-                    load_x4(xa + at, va); load_x4(xb + at, vb);
+                    uint32_t vb[4];
+                    load_x4(xp + 4 * (c ^ sw), vb);
+                    const uint32_t (&va)[4] = kept.v[c];
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
 #pragma unroll
@@ -1053,14 +1091,14 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
                     }
                 }
                 if constexpr (sizeof(T) == 1) sum = (acc[0] & 0xffffu) + (acc[1] & 0xffffu);
-                s.rs.scratch[4096 + tid] = 2u * sum;
+                s.rs.scratch[FRAC_PAIR_SUM + tid] = 2u * sum;
             }
         });
         ex.phase([&](int tid) {
             const int u = tid >> 1, k = kRingSlot[u >> 4], t = u & 15;
             if (tid >= 1 && tid < 43 && (tid & 1)) s.rbest[tid >> 1] = (unsigned long long)s.cost[tid >> 1] << 4;      // the centre: candidate 0 of every node (odd lanes are free here)
             if ((tid & 1) || !s.rs.tu_log2[t]) return;
-            const unsigned satd = (s.rs.scratch[4096 + tid] + s.rs.scratch[4096 + tid + 1] + 2) >> 2;
+            const unsigned satd = (s.rs.scratch[FRAC_PAIR_SUM + tid] + s.rs.scratch[FRAC_PAIR_SUM + tid + 1] + 2) >> 2;
             ex.atomic_add(&s.fsum[k - 1][s.tile_node[t]], satd);      // the CU's candidate sum, one LDS atomic per tile
         });
         // one lane per (CU, ring position) prices its candidate and bids with an LDS minimum (cost, then position: the order a walk over the positions finds); 21 lanes
