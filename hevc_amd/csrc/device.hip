@@ -1,6 +1,7 @@
 // hevc_amd/csrc/device.hip — __global__ entry points, launchers and the per-stage C-ABI functions (mihevc_k_*).
 #include "device.h"
 #include "md5.h"
+#include "stage_args.h"
 
 #include <cstdio>
 #include <cstring>
@@ -617,24 +618,34 @@ struct DevBuf {      // RAII device allocation
         if (e_ != hipSuccess) return MIHEVC_EDEVICE; \
     } while (0)
 
+// n host blocks of A into a new device buffer
+template <typename A> int to_device(DevBuf &d, const A *h, size_t n = 1)
+{
+    CK(d.alloc(n * sizeof(A)));
+    CK(hipMemcpy(d.p, h, n * sizeof(A), hipMemcpyHostToDevice));
+    return 0;
+}
+
 template <typename T> struct Planes3 {
     DevPlane<T> p[3];
+    Plane<T> rw[3]{};            // views for the argument builders (stage_args.h)
+    Plane<const T> ro[3]{};
     int alloc(int w, int h, bool padded)
     {
-        for (int i = 0; i < 3; i++)
+        for (int i = 0; i < 3; i++) {
             if (alloc_plane<T>(p[i], i ? w / 2 : w, i ? h / 2 : h, padded ? (i ? PAD_C : PAD_Y) : 0) != hipSuccess) return MIHEVC_ENOMEM;
+            rw[i] = p[i].pl; ro[i] = {p[i].pl.p, p[i].pl.stride};
+        }
         return 0;
     }
-    int upload(const void *y, const void *u, const void *v)
+    int upload(const void *const *src)
     {
-        const void *src[3] = {y, u, v};
         for (int i = 0; i < 3; i++)
             CK(hipMemcpy2D(p[i].pl.p, p[i].pl.stride * sizeof(T), src[i], p[i].w * sizeof(T), p[i].w * sizeof(T), p[i].h, hipMemcpyHostToDevice));
         return 0;
     }
-    int download(void *y, void *u, void *v)
+    int download(void *const *dst)
     {
-        void *dst[3] = {y, u, v};
         for (int i = 0; i < 3; i++)
             CK(hipMemcpy2D(dst[i], p[i].w * sizeof(T), p[i].pl.p, p[i].pl.stride * sizeof(T), p[i].w * sizeof(T), p[i].h, hipMemcpyDeviceToHost));
         return 0;
@@ -642,215 +653,156 @@ template <typename T> struct Planes3 {
     ~Planes3() { for (auto &x : p) free_plane<T>(x); }
 };
 
-CostParams to_prm(const mihevc_cost_params *p) { return CostParams{p->qp, p->qp_c, p->bit_depth, p->lambda_sad_q4, p->lambda_q4, p->me_range, p->tile_cols, p->tile_rows, p->intra_nxn, p->intra_in_p, p->pre_search, p->rdo_zero, p->chroma_modes, p->mc_top, p->mc_bottom, p->rdo_cg}; }
+struct DevAnalysis {     // what an analysis stage writes: CU records (zeroed), levels, rate estimate (zeroed)
+    DevBuf cu, coef[3], est;
+    size_t n8 = 0, ny = 0;
+    int alloc(int w, int h)
+    {
+        n8 = (size_t)(w / 8) * (h / 8); ny = (size_t)w * h;
+        CK(cu.alloc(n8 * sizeof(mihevc_cu_rec))); CK(coef[0].alloc(ny * 2)); CK(coef[1].alloc(ny / 2)); CK(coef[2].alloc(ny / 2)); CK(est.alloc(8));
+        CK(hipMemset(cu.p, 0, n8 * sizeof(mihevc_cu_rec))); CK(hipMemset(est.p, 0, 8));
+        return 0;
+    }
+    AnalysisOut view() const { return AnalysisOut{cu.as<mihevc_cu_rec>(), {coef[0].as<int16_t>(), coef[1].as<int16_t>(), coef[2].as<int16_t>()}, est.as<unsigned long long>()}; }
+    int download(mihevc_cu_rec *hcu, int16_t *const *hcoef, uint64_t *hest) const
+    {
+        CK(hipMemcpy(hcu, cu.p, n8 * sizeof(mihevc_cu_rec), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 3; i++) CK(hipMemcpy(hcoef[i], coef[i].p, i ? ny / 2 : ny * 2, hipMemcpyDeviceToHost));
+        if (hest) CK(hipMemcpy(hest, est.p, 8, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
 
 bool geometry_ok(int w, int h) { return w >= 16 && h >= 16 && !(w & 7) && !(h & 7) && w <= 8192 && h <= 4352; }
 
+// s, r, coef: the three planes (Y, Cb, Cr) of the source, the reconstruction, the levels
 template <typename T>
-int stage_intra(const void *sy, const void *su, const void *sv, int w, int h, const mihevc_cost_params *prm, void *ry, void *ru, void *rv,
-                mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_, int16_t *cv, uint64_t *est)
+int stage_intra(const void *const *s, int w, int h, const mihevc_cost_params *prm, void *const *r, mihevc_cu_rec *cu, int16_t *const *coef, uint64_t *est)
 {
     Planes3<T> src, rec;
     if (src.alloc(w, h, false) || rec.alloc(w, h, false)) return MIHEVC_ENOMEM;
-    if (int e = src.upload(sy, su, sv)) return e;
-    const size_t n8 = (size_t)(w / 8) * (h / 8), ny = (size_t)w * h;
-    DevBuf dcu, dc0, dc1, dc2, dargs, dest, dplan;
-    CK(dcu.alloc(n8 * sizeof(mihevc_cu_rec))); CK(dc0.alloc(ny * 2)); CK(dc1.alloc(ny / 2)); CK(dc2.alloc(ny / 2)); CK(dargs.alloc(sizeof(IntraArgs<T>)));
-    CK(dplan.alloc((size_t)((w + CTU - 1) / CTU) * ((h + CTU - 1) / CTU) * sizeof(IntraPlan)));
-    CK(dest.alloc(8)); CK(hipMemset(dest.p, 0, 8));
-    CK(hipMemset(dcu.p, 0, n8 * sizeof(mihevc_cu_rec)));
-    IntraArgs<T> a;
-    for (int i = 0; i < 3; i++) { a.src[i] = {src.p[i].pl.p, src.p[i].pl.stride}; a.rec[i] = rec.p[i].pl; }
-    a.w = w; a.h = h; a.ctus_w = (w + CTU - 1) / CTU; a.ctus_h = (h + CTU - 1) / CTU; a.prm = to_prm(prm);
-    a.cu = dcu.as<mihevc_cu_rec>(); a.coef[0] = dc0.as<int16_t>(); a.coef[1] = dc1.as<int16_t>(); a.coef[2] = dc2.as<int16_t>(); a.diagonal = 0; a.est = dest.as<unsigned long long>(); a.sparse_coef = 0; a.ip = nullptr; a.plan = dplan.as<IntraPlan>();
-    CK(hipMemcpy(dargs.p, &a, sizeof a, hipMemcpyHostToDevice));
+    if (int e = src.upload(s)) return e;
+    DevAnalysis out;
+    DevBuf dplan, dargs;
+    if (int e = out.alloc(w, h)) return e;
+    CK(dplan.alloc((size_t)ctus_of(w) * ctus_of(h) * sizeof(IntraPlan)));
+    const IntraArgs<T> a = intra_args<T>(src.ro, rec.rw, w, h, cost_params_of(*prm), out.view(), dplan.as<IntraPlan>());
+    if (int e = to_device(dargs, &a)) return e;
     CK(launch_intra_picture<T>(0, dargs.as<IntraArgs<T>>(), a.ctus_w, a.ctus_h, 1, a.prm.tile_cols, a.prm.tile_rows, nullptr));
     CK(hipDeviceSynchronize());
-    if (int e = rec.download(ry, ru, rv)) return e;
-    CK(hipMemcpy(cu, dcu.p, n8 * sizeof(mihevc_cu_rec), hipMemcpyDeviceToHost));
-    CK(hipMemcpy(cy, dc0.p, ny * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(cu_, dc1.p, ny / 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(cv, dc2.p, ny / 2, hipMemcpyDeviceToHost));
-    if (est) CK(hipMemcpy(est, dest.p, 8, hipMemcpyDeviceToHost));
-    return MIHEVC_OK;
+    if (int e = rec.download(r)) return e;
+    return out.download(cu, coef, est);
 }
 
+// A P picture (f1 == nullptr) against the reference f0: border pad, search centres from the 1/4-size pictures (prm->pre_search without centres0),
+// the list-0 search, the P CTU program, the intra second pass (prm->intra_in_p).  A B picture between the anchors f0 (list 0) and f1 (list 1):
+// border pad of both, the list-0 and list-1 searches, the B CTU program.  centers*, me_dump*: per list, optional
 template <typename T>
-int stage_inter(const void *sy, const void *su, const void *sv, const void *fy, const void *fu, const void *fv, int w, int h,
-                const mihevc_cost_params *prm, const int16_t *centers, void *ry, void *ru, void *rv, mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_,
-                int16_t *cv, int32_t *me_dump, uint64_t *est)
+int stage_inter(const void *const *s, const void *const *f0, const void *const *f1, int w, int h, const mihevc_cost_params *prm, const int16_t *centers0,
+                const int16_t *centers1, void *const *r, mihevc_cu_rec *cu, int16_t *const *coef, int32_t *me_dump0, int32_t *me_dump1, uint64_t *est)
 {
-    Planes3<T> src, ref, rec;
-    if (src.alloc(w, h, false) || ref.alloc(w, h, true) || rec.alloc(w, h, false)) return MIHEVC_ENOMEM;
-    if (int e = src.upload(sy, su, sv)) return e;
-    if (int e = ref.upload(fy, fu, fv)) return e;
-    const int ctus_w = (w + CTU - 1) / CTU, n_ctu = ctus_w * ((h + CTU - 1) / CTU);
-    const size_t n8 = (size_t)(w / 8) * (h / 8), ny = (size_t)w * h;
-    DevBuf dcu, dc0, dc1, dc2, dargs, dme, dcen, dpad, dest;
-    CK(dest.alloc(8)); CK(hipMemset(dest.p, 0, 8));
-    CK(dcu.alloc(n8 * sizeof(mihevc_cu_rec))); CK(dc0.alloc(ny * 2)); CK(dc1.alloc(ny / 2)); CK(dc2.alloc(ny / 2));
-    CK(dargs.alloc(sizeof(InterArgs<T>))); CK(dme.alloc((size_t)n_ctu * 63 * 4)); CK(dcen.alloc((size_t)n_ctu * 4)); CK(dpad.alloc(sizeof(SaoArgs<T>)));
-    CK(hipMemset(dcu.p, 0, n8 * sizeof(mihevc_cu_rec)));
-    if (centers) CK(hipMemcpy(dcen.p, centers, (size_t)n_ctu * 4, hipMemcpyHostToDevice));
-    // border extension of the uploaded reference (the pad kernel works on the `out` planes of a SaoArgs block)
-    SaoArgs<T> pa;
-    memset(&pa, 0, sizeof pa);
-    for (int i = 0; i < 3; i++) pa.out[i] = ref.p[i].pl;
-    pa.w = w; pa.h = h;
-    CK(hipMemcpy(dpad.p, &pa, sizeof pa, hipMemcpyHostToDevice));
-    CK(launch_pad<T>(0, dpad.as<SaoArgs<T>>(), w, h, 1));
-    InterArgs<T> a;
-    for (int i = 0; i < 3; i++) { a.src[i] = {src.p[i].pl.p, src.p[i].pl.stride}; a.ref[i] = {ref.p[i].pl.p, ref.p[i].pl.stride}; a.rec[i] = rec.p[i].pl; }
-    a.w = w; a.h = h; a.ctus_w = ctus_w; a.prm = to_prm(prm); a.centers = centers ? dcen.as<int16_t>() : nullptr; a.me = dme.as<int32_t>();
-    a.cu = dcu.as<mihevc_cu_rec>(); a.coef[0] = dc0.as<int16_t>(); a.coef[1] = dc1.as<int16_t>(); a.coef[2] = dc2.as<int16_t>();
-    a.est = dest.as<unsigned long long>(); a.sparse_coef = 0;
-    for (int i = 0; i < 3; i++) a.ref1[i] = {nullptr, 0};
-    a.centers1 = nullptr; a.me1 = nullptr;
-    DevBuf dip, diargs;
-    a.ip = nullptr;
-    if (a.prm.intra_in_p) { CK(dip.alloc((size_t)n_ctu * sizeof(IpInfo))); CK(hipMemset(dip.p, 0, (size_t)n_ctu * sizeof(IpInfo))); a.ip = dip.as<IpInfo>(); }
-    DevBuf dls, dlr, dpre;
-    if (a.prm.pre_search && !centers) {       // search centres from the 1/4-size pictures
-        const size_t ln = (size_t)(w >> 2) * (h >> 2);
-        CK(dls.alloc(ln)); CK(dlr.alloc(ln)); CK(dpre.alloc(sizeof(PreArgs<T>)));
-        PreArgs<T> pa2;
-        pa2.src = a.src[0]; pa2.ref = a.ref[0]; pa2.lsrc = dls.as<uint8_t>(); pa2.lref = dlr.as<uint8_t>(); pa2.w = w; pa2.h = h; pa2.bit_depth = a.prm.bit_depth; pa2.centers = dcen.as<int16_t>(); pa2.cost = nullptr;
-        CK(hipMemcpy(dpre.p, &pa2, sizeof pa2, hipMemcpyHostToDevice));
-        CK(launch_pre_search<T>(0, dpre.as<PreArgs<T>>(), w, h, n_ctu, 1, true));
-        a.centers = dcen.as<int16_t>();
+    const bool b = f1 != nullptr;
+    const int nref = b ? 2 : 1;
+    Planes3<T> src, ref[2], rec;
+    if (src.alloc(w, h, false) || ref[0].alloc(w, h, true) || (b && ref[1].alloc(w, h, true)) || rec.alloc(w, h, false)) return MIHEVC_ENOMEM;
+    if (int e = src.upload(s)) return e;
+    const void *const *f[2] = {f0, f1};
+    const int16_t *centers[2] = {centers0, centers1};
+    int32_t *me_dump[2] = {me_dump0, me_dump1};
+    for (int l = 0; l < nref; l++)
+        if (int e = ref[l].upload(f[l])) return e;
+    const CostParams p = cost_params_of(*prm);
+    const int n_ctu = ctus_of(w) * ctus_of(h);
+    const size_t me_bytes = (size_t)n_ctu * 63 * 4;
+    const bool pre = !b && p.pre_search && !centers0;
+    DevAnalysis out;
+    DevBuf dme[2], dcen[2], dip, dpad, dls, dlr, dpre, dargs, diargs;
+    if (int e = out.alloc(w, h)) return e;
+    for (int l = 0; l < nref; l++) {
+        CK(dme[l].alloc(me_bytes)); CK(dcen[l].alloc((size_t)n_ctu * 4));
+        if (centers[l]) CK(hipMemcpy(dcen[l].p, centers[l], (size_t)n_ctu * 4, hipMemcpyHostToDevice));
     }
-    CK(hipMemcpy(dargs.p, &a, sizeof a, hipMemcpyHostToDevice));
-    CK(launch_me_search<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, a.prm.me_range, 0));
-    CK(launch_inter_ctu<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, a.prm.me_range));
-    if (a.prm.intra_in_p) {       // intra second pass on the same reconstruction / records / levels
-        IntraArgs<T> ia;
-        for (int i = 0; i < 3; i++) { ia.src[i] = a.src[i]; ia.rec[i] = a.rec[i]; ia.coef[i] = a.coef[i]; }
-        ia.w = w; ia.h = h; ia.ctus_w = ctus_w; ia.ctus_h = (h + CTU - 1) / CTU;
-        ia.prm = a.prm;        // tile_cols / tile_rows: the P pictures' own grid (1x1 unless the caller passes cfg.p_tiles' grid)
-        ia.cu = a.cu; ia.diagonal = 0; ia.est = a.est; ia.sparse_coef = 0; ia.ip = a.ip; ia.plan = nullptr;
-        CK(diargs.alloc(sizeof ia));
-        CK(hipMemcpy(diargs.p, &ia, sizeof ia, hipMemcpyHostToDevice));
+    // border extension of the uploaded references
+    const SaoArgs<T> pa[2] = {picture_args<T>(ref[0].rw, w, h), picture_args<T>(ref[1].rw, w, h)};
+    if (int e = to_device(dpad, pa, nref)) return e;
+    CK(launch_pad<T>(0, dpad.as<SaoArgs<T>>(), w, h, nref));
+    if (!b && p.intra_in_p) { CK(dip.alloc((size_t)n_ctu * sizeof(IpInfo))); CK(hipMemset(dip.p, 0, (size_t)n_ctu * sizeof(IpInfo))); }
+    const InterArgs<T> a = inter_args<T>(src.ro, ref[0].ro, b ? ref[1].ro : nullptr, rec.rw, w, h, p, out.view(), centers0 || pre ? dcen[0].as<int16_t>() : nullptr,
+                                         centers1 ? dcen[1].as<int16_t>() : nullptr, dme[0].as<int32_t>(), dme[1].as<int32_t>(), dip.as<IpInfo>());
+    if (pre) {       // search centres from the 1/4-size pictures
+        const size_t ln = (size_t)(w >> 2) * (h >> 2);
+        CK(dls.alloc(ln)); CK(dlr.alloc(ln));
+        const PreArgs<T> pre_a = pre_args<T>(a, dls.as<uint8_t>(), dlr.as<uint8_t>(), dcen[0].as<int16_t>());
+        if (int e = to_device(dpre, &pre_a)) return e;
+        CK(launch_pre_search<T>(0, dpre.as<PreArgs<T>>(), w, h, n_ctu, 1, true));
+    }
+    if (int e = to_device(dargs, &a)) return e;
+    CK(launch_me_search<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, p.me_range, 0));
+    if (b) {
+        CK(launch_me_search<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, p.me_range, 1));
+        CK(launch_inter_ctu_b<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, p.me_range));
+    } else
+        CK(launch_inter_ctu<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, p.me_range));
+    if (a.ip) {       // intra second pass on the same reconstruction / records / levels
+        const IntraArgs<T> ia = intra_in_p_args(a);
+        if (int e = to_device(diargs, &ia)) return e;
         CK(launch_intra_p<T>(0, diargs.as<IntraArgs<T>>(), n_ctu, 1));
     }
     CK(hipDeviceSynchronize());
-    if (int e = rec.download(ry, ru, rv)) return e;
-    CK(hipMemcpy(cu, dcu.p, n8 * sizeof(mihevc_cu_rec), hipMemcpyDeviceToHost));
-    CK(hipMemcpy(cy, dc0.p, ny * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(cu_, dc1.p, ny / 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(cv, dc2.p, ny / 2, hipMemcpyDeviceToHost));
-    if (me_dump) CK(hipMemcpy(me_dump, dme.p, (size_t)n_ctu * 63 * 4, hipMemcpyDeviceToHost));
-    if (est) CK(hipMemcpy(est, dest.p, 8, hipMemcpyDeviceToHost));
-    return MIHEVC_OK;
+    if (int e = rec.download(r)) return e;
+    for (int l = 0; l < nref; l++)
+        if (me_dump[l]) CK(hipMemcpy(me_dump[l], dme[l].p, me_bytes, hipMemcpyDeviceToHost));
+    return out.download(cu, coef, est);
 }
 
-// B picture between two anchors: both integer searches, then the B form of the CTU program
-template <typename T>
-int stage_b(const void *sy, const void *su, const void *sv, const void *f0y, const void *f0u, const void *f0v, const void *f1y, const void *f1u, const void *f1v, int w, int h,
-            const mihevc_cost_params *prm, const int16_t *centers0, const int16_t *centers1, void *ry, void *ru, void *rv, mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_,
-            int16_t *cv, int32_t *me_dump0, int32_t *me_dump1, uint64_t *est)
-{
-    Planes3<T> src, ref0, ref1, rec;
-    if (src.alloc(w, h, false) || ref0.alloc(w, h, true) || ref1.alloc(w, h, true) || rec.alloc(w, h, false)) return MIHEVC_ENOMEM;
-    if (int e = src.upload(sy, su, sv)) return e;
-    if (int e = ref0.upload(f0y, f0u, f0v)) return e;
-    if (int e = ref1.upload(f1y, f1u, f1v)) return e;
-    const int ctus_w = (w + CTU - 1) / CTU, n_ctu = ctus_w * ((h + CTU - 1) / CTU);
-    const size_t n8 = (size_t)(w / 8) * (h / 8), ny = (size_t)w * h;
-    DevBuf dcu, dc0, dc1, dc2, dargs, dme0, dme1, dcen0, dcen1, dpad, dest;
-    CK(dest.alloc(8)); CK(hipMemset(dest.p, 0, 8));
-    CK(dcu.alloc(n8 * sizeof(mihevc_cu_rec))); CK(dc0.alloc(ny * 2)); CK(dc1.alloc(ny / 2)); CK(dc2.alloc(ny / 2));
-    CK(dargs.alloc(sizeof(InterArgs<T>))); CK(dme0.alloc((size_t)n_ctu * 63 * 4)); CK(dme1.alloc((size_t)n_ctu * 63 * 4)); CK(dcen0.alloc((size_t)n_ctu * 4)); CK(dcen1.alloc((size_t)n_ctu * 4));
-    CK(dpad.alloc(2 * sizeof(SaoArgs<T>)));
-    CK(hipMemset(dcu.p, 0, n8 * sizeof(mihevc_cu_rec)));
-    if (centers0) CK(hipMemcpy(dcen0.p, centers0, (size_t)n_ctu * 4, hipMemcpyHostToDevice));
-    if (centers1) CK(hipMemcpy(dcen1.p, centers1, (size_t)n_ctu * 4, hipMemcpyHostToDevice));
-    SaoArgs<T> pa[2];
-    memset(pa, 0, sizeof pa);
-    for (int i = 0; i < 3; i++) { pa[0].out[i] = ref0.p[i].pl; pa[1].out[i] = ref1.p[i].pl; }
-    pa[0].w = pa[1].w = w; pa[0].h = pa[1].h = h;
-    CK(hipMemcpy(dpad.p, pa, sizeof pa, hipMemcpyHostToDevice));
-    CK(launch_pad<T>(0, dpad.as<SaoArgs<T>>(), w, h, 2));
-    InterArgs<T> a;
-    for (int i = 0; i < 3; i++) {
-        a.src[i] = {src.p[i].pl.p, src.p[i].pl.stride}; a.ref[i] = {ref0.p[i].pl.p, ref0.p[i].pl.stride}; a.ref1[i] = {ref1.p[i].pl.p, ref1.p[i].pl.stride}; a.rec[i] = rec.p[i].pl;
-    }
-    a.w = w; a.h = h; a.ctus_w = ctus_w; a.prm = to_prm(prm);
-    a.centers = centers0 ? dcen0.as<int16_t>() : nullptr; a.centers1 = centers1 ? dcen1.as<int16_t>() : nullptr;
-    a.me = dme0.as<int32_t>(); a.me1 = dme1.as<int32_t>();
-    a.cu = dcu.as<mihevc_cu_rec>(); a.coef[0] = dc0.as<int16_t>(); a.coef[1] = dc1.as<int16_t>(); a.coef[2] = dc2.as<int16_t>();
-    a.est = dest.as<unsigned long long>(); a.sparse_coef = 0; a.ip = nullptr;
-    CK(hipMemcpy(dargs.p, &a, sizeof a, hipMemcpyHostToDevice));
-    CK(launch_me_search<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, a.prm.me_range, 0));
-    CK(launch_me_search<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, a.prm.me_range, 1));
-    CK(launch_inter_ctu_b<T>(0, dargs.as<InterArgs<T>>(), n_ctu, 1, a.prm.me_range));
-    CK(hipDeviceSynchronize());
-    if (int e = rec.download(ry, ru, rv)) return e;
-    CK(hipMemcpy(cu, dcu.p, n8 * sizeof(mihevc_cu_rec), hipMemcpyDeviceToHost));
-    CK(hipMemcpy(cy, dc0.p, ny * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(cu_, dc1.p, ny / 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(cv, dc2.p, ny / 2, hipMemcpyDeviceToHost));
-    if (me_dump0) CK(hipMemcpy(me_dump0, dme0.p, (size_t)n_ctu * 63 * 4, hipMemcpyDeviceToHost));
-    if (me_dump1) CK(hipMemcpy(me_dump1, dme1.p, (size_t)n_ctu * 63 * 4, hipMemcpyDeviceToHost));
-    if (est) CK(hipMemcpy(est, dest.p, 8, hipMemcpyDeviceToHost));
-    return MIHEVC_OK;
-}
-
-template <typename T> int stage_deblock(void *ry, void *ru, void *rv, int w, int h, const mihevc_cu_rec *cu, int bit_depth)
+template <typename T> int stage_deblock(void *const *r, int w, int h, const mihevc_cu_rec *cu, int bit_depth)
 {
     Planes3<T> rec;
     if (rec.alloc(w, h, false)) return MIHEVC_ENOMEM;
-    if (int e = rec.upload(ry, ru, rv)) return e;
-    const size_t n8 = (size_t)(w / 8) * (h / 8);
+    if (int e = rec.upload(r)) return e;
     DevBuf dcu, dargs;
-    CK(dcu.alloc(n8 * sizeof(mihevc_cu_rec))); CK(dargs.alloc(2 * sizeof(DeblockArgs<T>)));
-    CK(hipMemcpy(dcu.p, cu, n8 * sizeof(mihevc_cu_rec), hipMemcpyHostToDevice));
-    DeblockArgs<T> a[2];
-    for (int d = 0; d < 2; d++) {
-        for (int i = 0; i < 3; i++) a[d].rec[i] = rec.p[i].pl;
-        a[d].w = w; a[d].h = h; a[d].cu = dcu.as<mihevc_cu_rec>(); a[d].bit_depth = bit_depth; a[d].dir = d; a[d].y_org = 0;
-    }
-    CK(hipMemcpy(dargs.p, a, sizeof a, hipMemcpyHostToDevice));
+    if (int e = to_device(dcu, cu, (size_t)(w / 8) * (h / 8))) return e;
+    const DeblockArgs<T> a[2] = {deblock_args<T>(rec.rw, w, h, dcu.as<mihevc_cu_rec>(), bit_depth, 0), deblock_args<T>(rec.rw, w, h, dcu.as<mihevc_cu_rec>(), bit_depth, 1)};
+    if (int e = to_device(dargs, a, 2)) return e;
     CK(launch_deblock<T>(0, dargs.as<DeblockArgs<T>>(), dargs.as<DeblockArgs<T>>() + 1, w, h, 1));
     CK(hipDeviceSynchronize());
-    return rec.download(ry, ru, rv);
+    return rec.download(r);
 }
 
+// cu: the fused loop filter, `d` is then the pre-deblock reconstruction
 template <typename T>
-int stage_sao(const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int h,
-              const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *sao, const mihevc_cu_rec *cu = nullptr)
+int stage_sao(const void *const *s, const void *const *d, int w, int h, const mihevc_cost_params *prm, void *const *o, mihevc_sao_ctu *sao, const mihevc_cu_rec *cu = nullptr)
 {
     Planes3<T> src, dbk, out;
     if (src.alloc(w, h, false) || dbk.alloc(w, h, false) || out.alloc(w, h, true)) return MIHEVC_ENOMEM;
-    if (int e = src.upload(sy, su, sv)) return e;
-    if (int e = dbk.upload(dy, du, dv)) return e;
-    const int ctus_w = (w + CTU - 1) / CTU, n_ctu = ctus_w * ((h + CTU - 1) / CTU);
+    if (int e = src.upload(s)) return e;
+    if (int e = dbk.upload(d)) return e;
+    const int n_ctu = ctus_of(w) * ctus_of(h);
     DevBuf dsao, dargs, dcu;
-    CK(dsao.alloc((size_t)n_ctu * sizeof(mihevc_sao_ctu))); CK(dargs.alloc(sizeof(SaoArgs<T>)));
-    SaoArgs<T> a;
-    for (int i = 0; i < 3; i++) { a.src[i] = {src.p[i].pl.p, src.p[i].pl.stride}; a.dbk[i] = {dbk.p[i].pl.p, dbk.p[i].pl.stride}; a.out[i] = out.p[i].pl; }
-    a.w = w; a.h = h; a.ctus_w = ctus_w; a.prm = to_prm(prm); a.sao = dsao.as<mihevc_sao_ctu>(); a.sse = nullptr; a.sse_ctu = nullptr; a.halo_top = a.halo_bottom = 0;
-    a.cu = nullptr;
-    if (cu) {      // the fused loop filter: `dbk` is the pre-deblock reconstruction
-        const size_t n8 = (size_t)(w / 8) * (h / 8);
-        CK(dcu.alloc(n8 * sizeof(mihevc_cu_rec)));
-        CK(hipMemcpy(dcu.p, cu, n8 * sizeof(mihevc_cu_rec), hipMemcpyHostToDevice));
-        a.cu = dcu.as<mihevc_cu_rec>();
+    CK(dsao.alloc((size_t)n_ctu * sizeof(mihevc_sao_ctu)));
+    if (cu) {
+        if (int e = to_device(dcu, cu, (size_t)(w / 8) * (h / 8))) return e;
     }
-    CK(hipMemcpy(dargs.p, &a, sizeof a, hipMemcpyHostToDevice));
+    const SaoArgs<T> a = sao_args<T>(src.ro, dbk.ro, out.rw, w, h, cost_params_of(*prm), dsao.as<mihevc_sao_ctu>(), dcu.as<mihevc_cu_rec>());
+    if (int e = to_device(dargs, &a)) return e;
     CK(launch_sao<T>(0, dargs.as<SaoArgs<T>>(), w, h, 1, true));
     CK(launch_pad<T>(0, dargs.as<SaoArgs<T>>(), w, h, 1));
     CK(hipDeviceSynchronize());
-    if (int e = out.download(oy, ou, ov)) return e;
+    if (int e = out.download(o)) return e;
     CK(hipMemcpy(sao, dsao.p, (size_t)n_ctu * sizeof(mihevc_sao_ctu), hipMemcpyDeviceToHost));
     return MIHEVC_OK;
 }
 
 // the decoded picture hash kernels alone, on reference-layout planes (the border of a session's final reconstruction around them)
-template <typename T> int stage_picture_hash(const void *sy, const void *su, const void *sv, int w, int h, int kind, uint32_t *out)
+template <typename T> int stage_picture_hash(const void *const *s, int w, int h, int kind, uint32_t *out)
 {
     Planes3<T> pic;
     if (pic.alloc(w, h, true)) return MIHEVC_ENOMEM;
-    if (int e = pic.upload(sy, su, sv)) return e;
+    if (int e = pic.upload(s)) return e;
     DevBuf dargs, dpart, dout;
-    CK(dargs.alloc(sizeof(SaoArgs<T>))); CK(dpart.alloc((size_t)pic_hash_part_words(w, h, (int)sizeof(T)) * 4)); CK(dout.alloc(3 * sizeof(uint32_t)));
-    SaoArgs<T> a{};
-    for (int i = 0; i < 3; i++) a.out[i] = pic.p[i].pl;
-    a.w = w; a.h = h; a.sse = dout.as<unsigned long long>();
-    CK(hipMemcpy(dargs.p, &a, sizeof a, hipMemcpyHostToDevice));
+    CK(dpart.alloc((size_t)pic_hash_part_words(w, h, (int)sizeof(T)) * 4)); CK(dout.alloc(3 * sizeof(uint32_t)));
+    const SaoArgs<T> a = picture_args<T>(pic.rw, w, h, dout.as<unsigned long long>());
+    if (int e = to_device(dargs, &a)) return e;
     CK(launch_pic_hash<T>(0, dargs.as<SaoArgs<T>>(), w, h, 1, kind, dpart.as<uint32_t>(), 0));
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(out, dout.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -926,9 +878,10 @@ int mihevc_k_intra_frame(int device, const void *sy, const void *su, const void 
 {
     if (!sy || !su || !sv || !prm || !ry || !ru || !rv || !cu || !cy || !cu_ || !cv || !geometry_ok(w, h)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
-    if (prm->bit_depth == 8) return stage_intra<uint8_t>(sy, su, sv, w, h, prm, ry, ru, rv, cu, cy, cu_, cv, est);
-    if (prm->bit_depth == 10) return stage_intra<uint16_t>(sy, su, sv, w, h, prm, ry, ru, rv, cu, cy, cu_, cv, est);
-    return MIHEVC_EINVAL;
+    const void *s[3] = {sy, su, sv};
+    void *r[3] = {ry, ru, rv};
+    int16_t *c[3] = {cy, cu_, cv};
+    return with_depth(prm->bit_depth, [&](auto t) { return stage_intra<decltype(t)>(s, w, h, prm, r, cu, c, est); });
 }
 
 int mihevc_k_inter_frame(int device, const void *sy, const void *su, const void *sv, const void *fy, const void *fu, const void *fv, int w, int h,
@@ -938,9 +891,10 @@ int mihevc_k_inter_frame(int device, const void *sy, const void *su, const void 
     if (!sy || !su || !sv || !fy || !fu || !fv || !prm || !ry || !ru || !rv || !cu || !cy || !cu_ || !cv || !geometry_ok(w, h)) return MIHEVC_EINVAL;
     if (prm->me_range < 1 || prm->me_range > MAX_RANGE) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
-    if (prm->bit_depth == 8) return stage_inter<uint8_t>(sy, su, sv, fy, fu, fv, w, h, prm, centers, ry, ru, rv, cu, cy, cu_, cv, me_dump, est);
-    if (prm->bit_depth == 10) return stage_inter<uint16_t>(sy, su, sv, fy, fu, fv, w, h, prm, centers, ry, ru, rv, cu, cy, cu_, cv, me_dump, est);
-    return MIHEVC_EINVAL;
+    const void *s[3] = {sy, su, sv}, *f[3] = {fy, fu, fv};
+    void *r[3] = {ry, ru, rv};
+    int16_t *c[3] = {cy, cu_, cv};
+    return with_depth(prm->bit_depth, [&](auto t) { return stage_inter<decltype(t)>(s, f, nullptr, w, h, prm, centers, nullptr, r, cu, c, me_dump, nullptr, est); });
 }
 
 int mihevc_k_b_frame(int device, const void *sy, const void *su, const void *sv, const void *f0y, const void *f0u, const void *f0v, const void *f1y, const void *f1u,
@@ -950,18 +904,18 @@ int mihevc_k_b_frame(int device, const void *sy, const void *su, const void *sv,
     if (!sy || !su || !sv || !f0y || !f0u || !f0v || !f1y || !f1u || !f1v || !prm || !ry || !ru || !rv || !cu || !cy || !cu_ || !cv || !geometry_ok(w, h)) return MIHEVC_EINVAL;
     if (prm->me_range < 1 || prm->me_range > MAX_RANGE) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
-    if (prm->bit_depth == 8) return stage_b<uint8_t>(sy, su, sv, f0y, f0u, f0v, f1y, f1u, f1v, w, h, prm, centers0, centers1, ry, ru, rv, cu, cy, cu_, cv, me_dump0, me_dump1, est);
-    if (prm->bit_depth == 10) return stage_b<uint16_t>(sy, su, sv, f0y, f0u, f0v, f1y, f1u, f1v, w, h, prm, centers0, centers1, ry, ru, rv, cu, cy, cu_, cv, me_dump0, me_dump1, est);
-    return MIHEVC_EINVAL;
+    const void *s[3] = {sy, su, sv}, *f0[3] = {f0y, f0u, f0v}, *f1[3] = {f1y, f1u, f1v};
+    void *r[3] = {ry, ru, rv};
+    int16_t *c[3] = {cy, cu_, cv};
+    return with_depth(prm->bit_depth, [&](auto t) { return stage_inter<decltype(t)>(s, f0, f1, w, h, prm, centers0, centers1, r, cu, c, me_dump0, me_dump1, est); });
 }
 
 int mihevc_k_deblock(int device, void *ry, void *ru, void *rv, int w, int h, const mihevc_cu_rec *cu, int bit_depth)
 {
     if (!ry || !ru || !rv || !cu || !geometry_ok(w, h)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
-    if (bit_depth == 8) return stage_deblock<uint8_t>(ry, ru, rv, w, h, cu, bit_depth);
-    if (bit_depth == 10) return stage_deblock<uint16_t>(ry, ru, rv, w, h, cu, bit_depth);
-    return MIHEVC_EINVAL;
+    void *r[3] = {ry, ru, rv};
+    return with_depth(bit_depth, [&](auto t) { return stage_deblock<decltype(t)>(r, w, h, cu, bit_depth); });
 }
 
 int mihevc_k_sao(int device, const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int h,
@@ -969,9 +923,9 @@ int mihevc_k_sao(int device, const void *sy, const void *su, const void *sv, con
 {
     if (!sy || !su || !sv || !dy || !du || !dv || !prm || !oy || !ou || !ov || !sao || !geometry_ok(w, h)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
-    if (prm->bit_depth == 8) return stage_sao<uint8_t>(sy, su, sv, dy, du, dv, w, h, prm, oy, ou, ov, sao);
-    if (prm->bit_depth == 10) return stage_sao<uint16_t>(sy, su, sv, dy, du, dv, w, h, prm, oy, ou, ov, sao);
-    return MIHEVC_EINVAL;
+    const void *s[3] = {sy, su, sv}, *d[3] = {dy, du, dv};
+    void *o[3] = {oy, ou, ov};
+    return with_depth(prm->bit_depth, [&](auto t) { return stage_sao<decltype(t)>(s, d, w, h, prm, o, sao); });
 }
 
 int mihevc_k_loop_filter(int device, const void *sy, const void *su, const void *sv, const void *ry, const void *ru, const void *rv, int w, int h,
@@ -979,17 +933,17 @@ int mihevc_k_loop_filter(int device, const void *sy, const void *su, const void 
 {
     if (!sy || !su || !sv || !ry || !ru || !rv || !cu || !prm || !oy || !ou || !ov || !sao || !geometry_ok(w, h)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
-    if (prm->bit_depth == 8) return stage_sao<uint8_t>(sy, su, sv, ry, ru, rv, w, h, prm, oy, ou, ov, sao, cu);
-    if (prm->bit_depth == 10) return stage_sao<uint16_t>(sy, su, sv, ry, ru, rv, w, h, prm, oy, ou, ov, sao, cu);
-    return MIHEVC_EINVAL;
+    const void *s[3] = {sy, su, sv}, *r[3] = {ry, ru, rv};
+    void *o[3] = {oy, ou, ov};
+    return with_depth(prm->bit_depth, [&](auto t) { return stage_sao<decltype(t)>(s, r, w, h, prm, o, sao, cu); });
 }
 
 int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *v, int w, int h, int bit_depth, int hash_type, void *out)
 {
     if (!y || !u || !v || !out || !geometry_ok(w, h) || (bit_depth != 8 && bit_depth != 10) || hash_type < 0 || hash_type > 2) return MIHEVC_EINVAL;
-    const int bps = bit_depth > 8 ? 2 : 1;
+    const void *pl[3] = {y, u, v};
     if (hash_type == 0) {     // MD5: on the host, as a session computes it
-        const void *pl[3] = {y, u, v};
+        const int bps = bit_depth > 8 ? 2 : 1;
         for (int c = 0; c < 3; c++) {
             const size_t row = (size_t)(c ? w / 2 : w) * bps;
             md5_plane((const uint8_t *)pl[c], row, row, c ? h / 2 : h, (uint8_t *)out + 16 * c);
@@ -997,8 +951,7 @@ int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *
         return MIHEVC_OK;
     }
     if (int e = select_device(device)) return e;
-    if (bps == 1) return stage_picture_hash<uint8_t>(y, u, v, w, h, hash_type, (uint32_t *)out);
-    return stage_picture_hash<uint16_t>(y, u, v, w, h, hash_type, (uint32_t *)out);
+    return with_depth(bit_depth, [&](auto t) { return stage_picture_hash<decltype(t)>(pl, w, h, hash_type, (uint32_t *)out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

@@ -2,61 +2,63 @@
 // CPU with the sequential executor (one "thread" at a time, barrier = end of loop), so the kernel SOURCE can be
 // checked against the oracle on machines without a GPU.  It proves the kernels' logic, not the GPU execution:
 // the -m gpu tests run the real gfx950 binaries through the C ABI.  hevc_amd/ never loads this library.
+// The emu_* stage entries are the twins of the mihevc_k_* entries (device.hip) and build the same argument blocks (csrc/stage_args.h); those
+// that take a mihevc_cost_params take a last argument sign_hide as well (CostParams::sign_hide).  emu_transform_sdh / emu_transform4_sdh are
+// the twins of mihevc_k_transform_sdh; the picture hash twin is in pichash.cpp.
 #include <chrono>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
-#include "../../hevc_amd/csrc/kernels/common.h"
-#include "../../hevc_amd/csrc/kernels/inter.h"
-#include "../../hevc_amd/csrc/kernels/intra.h"
-#include "../../hevc_amd/csrc/kernels/loopfilter.h"
+#include "../../hevc_amd/csrc/stage_args.h"
 
 using namespace mihevc;
 
 // LDS is not zeroed on the device: with EMU_SHARED_FILL=<seed> the shared state of every workgroup starts as pseudo-random bytes, so a
 // read of a field the program never initialised shows up as a mismatch against the oracle (default: zeros)
 static int emu_order() { const char *e = getenv("EMU_ORDER"); return e ? atoi(e) : 0; }
-template <class S> static S *fresh_shared()
+template <class S> using Shared = std::unique_ptr<S, void (*)(void *)>;
+template <class S> static Shared<S> fresh_shared()
 {
     S *p = (S *)malloc(sizeof(S));
     const char *e = getenv("EMU_SHARED_FILL");
-    if (!e) { memset((void *)p, 0, sizeof(S)); return p; }
+    if (!e) { memset((void *)p, 0, sizeof(S)); return Shared<S>(p, free); }
     static unsigned long long x = 0;
     if (!x) x = 0x9E3779B97F4A7C15ull ^ (unsigned long long)atoll(e);
     unsigned char *b = (unsigned char *)p;
     for (size_t i = 0; i < sizeof(S); i++) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; b[i] = (unsigned char)(x >> 32); }
-    return p;
+    return Shared<S>(p, free);
 }
 
-template <typename T> struct Padded {
-    std::vector<T> buf;
-    int stride, pad;
-    Plane<T> plane;
-    Padded(int w, int h, int pad_) : pad(pad_)
+// views of the three caller planes (Y, Cb, Cr) of a picture w samples wide, unpadded, from row y0 on (chroma: row y0 / 2)
+template <typename T> struct Views {
+    Plane<T> p[3];
+    template <class V> Views(V *const *pl, int w, int y0 = 0)
     {
-        stride = w + 2 * pad;
-        buf.assign((size_t)stride * (h + 2 * pad), 0);
-        plane.p = buf.data() + (size_t)pad * stride + pad;
-        plane.stride = stride;
-    }
-    void load(const T *src, int w, int h)
-    {
-        for (int y = 0; y < h; y++) memcpy(plane.p + (ptrdiff_t)y * stride, src + (size_t)y * w, w * sizeof(T));
-        for (int i = 0; i < pad_border_count(w, h, pad); i++) pad_border_sample<T>(plane, w, h, pad, i);
-    }
-    void store(T *dst, int w, int h) const
-    {
-        for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * w, plane.p + (ptrdiff_t)y * stride, w * sizeof(T));
+        for (int i = 0; i < 3; i++) { const int s = i ? w / 2 : w; p[i] = {(T *)pl[i] + (ptrdiff_t)(i ? y0 / 2 : y0) * s, s}; }
     }
 };
 
-static CostParams to_prm(const mihevc_cost_params *p)
-{
-    return CostParams{p->qp, p->qp_c, p->bit_depth, p->lambda_sad_q4, p->lambda_q4, p->me_range, p->tile_cols, p->tile_rows, p->intra_nxn, p->intra_in_p, p->pre_search, p->rdo_zero, p->chroma_modes, p->mc_top, p->mc_bottom, p->rdo_cg};
-}
+// a reference picture copied into planes with the device's borders (PAD_Y / PAD_C), border extended
+template <typename T> struct PaddedPicture {
+    std::vector<T> buf[3];
+    Plane<const T> p[3];
+    PaddedPicture(const void *const *src, int w, int h)
+    {
+        for (int i = 0; i < 3; i++) {
+            const int pw = i ? w / 2 : w, ph = i ? h / 2 : h, pad = i ? PAD_C : PAD_Y, stride = pw + 2 * pad;
+            buf[i].assign((size_t)stride * (ph + 2 * pad), 0);
+            const Plane<T> pl{buf[i].data() + (size_t)pad * stride + pad, stride};
+            for (int y = 0; y < ph; y++) memcpy(pl.p + (ptrdiff_t)y * stride, (const T *)src[i] + (size_t)y * pw, pw * sizeof(T));
+            for (int k = 0; k < pad_border_count(pw, ph, pad); k++) pad_border_sample<T>(pl, pw, ph, pad, k);
+            p[i] = {pl.p, stride};
+        }
+    }
+};
 
 // ---- EMU_WAVES=<seed>: the four waves of a workgroup as four host threads -------------------------------------------------------------
 // The sequential executor runs the code BETWEEN two phases once, so it cannot see a wave that reads shared state for a uniform branch
@@ -126,143 +128,90 @@ template <class Program> static bool run_waves(unsigned long long seed, Program 
     return !bar.broken.load();
 }
 
+
+// Runs one workgroup program, program(ex), per call: on the sequential executor (EMU_ORDER: its thread order; one executor for every workgroup of
+// the picture), or with EMU_WAVES=<seed> on four wave threads seeded with seed + salt.  false: a barrier broke, and the frame call reports -2
+struct Stepper {
+    SeqExec seq;
+    const char *waves = getenv("EMU_WAVES");
+    Stepper() { seq.order = emu_order(); }
+    template <class Program> bool operator()(unsigned salt, Program &&program)
+    {
+        if (waves) return run_waves((unsigned long long)atoll(waves) + salt, program);
+        program(seq);
+        return true;
+    }
+};
+
+// A P picture (f1 == nullptr) against the reference f0, or a B picture between the anchors f0 (list 0) and f1 (list 1), in the order of the
+// device's launches (device.hip stage_inter): P: search centres (prm.pre_search without centres0), list-0 search, P CTU program, intra second pass
+// (prm.intra_in_p); B: list-0 and list-1 searches, B CTU program
 template <typename T>
-static int inter_frame(const T *sy, const T *su, const T *sv, const T *ry, const T *ru, const T *rv, int w, int h,
-                       const mihevc_cost_params *prm, const int16_t *centers, T *oy, T *ou, T *ov, mihevc_cu_rec *cu,
-                       int16_t *cy, int16_t *cu_, int16_t *cv, int32_t *me_dump, unsigned long long *est)
+static int inter_frame(const void *const *s, const void *const *f0, const void *const *f1, int w, int h, const CostParams &prm, const int16_t *centers0,
+                       const int16_t *centers1, void *const *o, mihevc_cu_rec *cu, int16_t *const *coef, int32_t *me_dump0, int32_t *me_dump1, unsigned long long *est)
 {
-    Padded<T> ref0(w, h, PAD_Y), ref1(w / 2, h / 2, PAD_C), ref2(w / 2, h / 2, PAD_C);
-    ref0.load(ry, w, h); ref1.load(ru, w / 2, h / 2); ref2.load(rv, w / 2, h / 2);
-    InterArgs<T> a;
-    a.src[0] = {sy, w}; a.src[1] = {su, w / 2}; a.src[2] = {sv, w / 2};
-    a.ref[0] = {ref0.plane.p, ref0.stride}; a.ref[1] = {ref1.plane.p, ref1.stride}; a.ref[2] = {ref2.plane.p, ref2.stride};
-    a.rec[0] = {oy, w}; a.rec[1] = {ou, w / 2}; a.rec[2] = {ov, w / 2};
-    a.w = w; a.h = h; a.ctus_w = (w + CTU - 1) / CTU;
-    a.prm = to_prm(prm); a.centers = centers; a.cu = cu; a.coef[0] = cy; a.coef[1] = cu_; a.coef[2] = cv; a.est = est; a.sparse_coef = 0;
-    for (int i = 0; i < 3; i++) a.ref1[i] = {nullptr, 0};
-    a.centers1 = nullptr; a.me1 = nullptr;
+    const bool b = f1 != nullptr;
+    const int nref = b ? 2 : 1, n_ctu = ctus_of(w) * ctus_of(h), R = prm.me_range;
+    const bool pre = !b && prm.pre_search && !centers0;
+    PaddedPicture<T> ref0(f0, w, h);
+    std::unique_ptr<PaddedPicture<T>> ref1(b ? new PaddedPicture<T>(f1, w, h) : nullptr);
+    std::vector<int32_t> me[2];
+    for (int l = 0; l < nref; l++) me[l].resize((size_t)n_ctu * 63);
+    std::vector<int16_t> cen(pre ? (size_t)n_ctu * 2 : 0, 0);
+    std::vector<IpInfo> ipv(!b && prm.intra_in_p ? (size_t)n_ctu : 0, IpInfo{0, 0, 0});
     if (est) *est = 0;
-    std::vector<IpInfo> ipv;
-    a.ip = nullptr;
-    int n_ctu = a.ctus_w * ((h + CTU - 1) / CTU), R = a.prm.me_range;
-    std::vector<int32_t> me((size_t)n_ctu * 63);
-    a.me = me.data();
-    if (a.prm.intra_in_p) { ipv.assign((size_t)n_ctu, IpInfo{0, 0, 0}); a.ip = ipv.data(); }
-    SeqExec ex; ex.order = emu_order();
-    std::vector<uint8_t> ls, lr;
-    std::vector<int16_t> cen;
-    if (a.prm.pre_search && !centers) {
-        PreArgs<T> pa;
-        ls.assign((size_t)(w / 4) * (h / 4), 0); lr = ls; cen.assign((size_t)n_ctu * 2, 0);
-        pa.src = a.src[0]; pa.ref = a.ref[0]; pa.lsrc = ls.data(); pa.lref = lr.data(); pa.w = w; pa.h = h; pa.bit_depth = a.prm.bit_depth; pa.centers = cen.data(); pa.cost = nullptr;
+    const InterArgs<T> a = inter_args<T>(Views<const T>(s, w).p, ref0.p, b ? ref1->p : nullptr, Views<T>(o, w).p, w, h, prm, AnalysisOut{cu, {coef[0], coef[1], coef[2]}, est},
+                                         pre ? cen.data() : centers0, centers1, me[0].data(), me[1].data(), ipv.empty() ? nullptr : ipv.data());
+    Stepper step;
+    if (pre) {
+        std::vector<uint8_t> ls((size_t)(w / 4) * (h / 4), 0), lr = ls;
+        const PreArgs<T> pa = pre_args<T>(a, ls.data(), lr.data(), cen.data());
         for (int i = 0; i < 2 * (w / 4) * (h / 4); i++) lowres_sample<T>(pa, i);
         for (int c = 0; c < n_ctu; c++) {
             PreShared ps;
-            if (const char *e = getenv("EMU_WAVES")) { if (!run_waves((unsigned long long)atoll(e) + 31u * (unsigned)c, [&](WaveExec &wx) { pre_search_program<T>(wx, ps, pa, c); })) return -2; }
-            else pre_search_program<T>(ex, ps, pa, c);
+            if (!step(31u * (unsigned)c, [&](auto &ex) { pre_search_program<T>(ex, ps, pa, c); })) return -2;
         }
-        a.centers = cen.data();
     }
-    const char *waves = getenv("EMU_WAVES");
     std::vector<uint8_t> win((size_t)me_win_elems(R) + 8);
     std::vector<T> wy((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16), wu((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16), wv(wu.size());
-    for (int c = 0; c < n_ctu; c++) {
-        MeShared<T> *ms = fresh_shared<MeShared<T>>();
-        bool ok = true;
-        if (waves) ok = run_waves((unsigned long long)atoll(waves) + (unsigned)c, [&](WaveExec &wx) { me_search_program<T>(wx, *ms, win.data(), a, c); });
-        else me_search_program<T>(ex, *ms, win.data(), a, c);
-        free(ms);
-        if (!ok) return -2;
+    for (int list = 0; list < nref; list++) {
+        const InterArgs<T> al = list ? list1_view(a) : a;
+        for (int c = 0; c < n_ctu; c++) {
+            Shared<MeShared<T>> ms = fresh_shared<MeShared<T>>();
+            if (!step((unsigned)c + 1000u * list, [&](auto &ex) { me_search_program<T>(ex, *ms, win.data(), al, c); })) return -2;
+        }
     }
-    if (me_dump) memcpy(me_dump, me.data(), me.size() * sizeof(int32_t));
+    int32_t *me_dump[2] = {me_dump0, me_dump1};
+    for (int l = 0; l < nref; l++)
+        if (me_dump[l]) memcpy(me_dump[l], me[l].data(), me[l].size() * sizeof(int32_t));
     for (int c = 0; c < n_ctu; c++) {
-        InterShared<T> *is = fresh_shared<InterShared<T>>();
-        bool ok = true;
-        if (waves) ok = run_waves((unsigned long long)atoll(waves) + 7919u * (unsigned)c, [&](WaveExec &wx) { inter_ctu_program<T>(wx, *is, wy.data(), wu.data(), wv.data(), a, c); });
-        else inter_ctu_program<T>(ex, *is, wy.data(), wu.data(), wv.data(), a, c);
-        free(is);
-        if (!ok) return -2;
+        Shared<InterShared<T>> is = fresh_shared<InterShared<T>>();
+        Shared<BiShared> bs = b ? fresh_shared<BiShared>() : Shared<BiShared>(nullptr, free);
+        if (!step(7919u * (unsigned)c, [&](auto &ex) {
+                using Ex = std::remove_reference_t<decltype(ex)>;
+                if (b) inter_ctu_program<T, Ex, true>(ex, *is, wy.data(), wu.data(), wv.data(), a, c, bs.get());
+                else inter_ctu_program<T>(ex, *is, wy.data(), wu.data(), wv.data(), a, c);
+            }))
+            return -2;
     }
     if (a.ip) {       // intra second pass, two rounds like the device's two launches
-        IntraArgs<T> ia;
-        for (int i = 0; i < 3; i++) { ia.src[i] = a.src[i]; ia.rec[i] = a.rec[i]; ia.coef[i] = a.coef[i]; }
-        ia.w = w; ia.h = h; ia.ctus_w = a.ctus_w; ia.ctus_h = (h + CTU - 1) / CTU;
-        ia.prm = a.prm;        // tile_cols / tile_rows: the P pictures' own grid
-        ia.cu = cu; ia.diagonal = 0; ia.est = est; ia.sparse_coef = 0; ia.ip = a.ip; ia.plan = nullptr;
+        const IntraArgs<T> ia = intra_in_p_args(a);
         for (int round = 0; round < 2; round++)
             for (int c = 0; c < n_ctu; c++) {
                 if (!ip_eligible(ia.ip, ia.ctus_w, ia.ctus_h, c % ia.ctus_w, c / ia.ctus_w, round)) continue;
-                IntraShared<T> *is = fresh_shared<IntraShared<T>>();
-                bool ok = true;
-                if (waves) ok = run_waves((unsigned long long)atoll(waves) + 104729u * (unsigned)c, [&](WaveExec &wx) { intra_ctu_program<T>(wx, *is, ia, c % ia.ctus_w, c / ia.ctus_w); });
-                else intra_ctu_program<T>(ex, *is, ia, c % ia.ctus_w, c / ia.ctus_w);
-                free(is);
-                if (!ok) return -2;
+                Shared<IntraShared<T>> is = fresh_shared<IntraShared<T>>();
+                if (!step(104729u * (unsigned)c, [&](auto &ex) { intra_ctu_program<T>(ex, *is, ia, c % ia.ctus_w, c / ia.ctus_w); })) return -2;
             }
     }
     return 0;
 }
 
-// B picture between two anchors: integer search against both (list 0: r0*, list 1: r1*), then the B form of the CTU program
 template <typename T>
-static int b_frame(const T *sy, const T *su, const T *sv, const T *r0y, const T *r0u, const T *r0v, const T *r1y, const T *r1u, const T *r1v, int w, int h,
-                   const mihevc_cost_params *prm, const int16_t *centers0, const int16_t *centers1, T *oy, T *ou, T *ov, mihevc_cu_rec *cu,
-                   int16_t *cy, int16_t *cu_, int16_t *cv, int32_t *me_dump0, int32_t *me_dump1, unsigned long long *est)
+static int intra_frame(const void *const *s, int w, int h, const CostParams &prm, void *const *o, mihevc_cu_rec *cu, int16_t *const *coef, unsigned long long *est)
 {
-    Padded<T> p00(w, h, PAD_Y), p01(w / 2, h / 2, PAD_C), p02(w / 2, h / 2, PAD_C), p10(w, h, PAD_Y), p11(w / 2, h / 2, PAD_C), p12(w / 2, h / 2, PAD_C);
-    p00.load(r0y, w, h); p01.load(r0u, w / 2, h / 2); p02.load(r0v, w / 2, h / 2);
-    p10.load(r1y, w, h); p11.load(r1u, w / 2, h / 2); p12.load(r1v, w / 2, h / 2);
-    InterArgs<T> a;
-    a.src[0] = {sy, w}; a.src[1] = {su, w / 2}; a.src[2] = {sv, w / 2};
-    a.ref[0] = {p00.plane.p, p00.stride}; a.ref[1] = {p01.plane.p, p01.stride}; a.ref[2] = {p02.plane.p, p02.stride};
-    a.ref1[0] = {p10.plane.p, p10.stride}; a.ref1[1] = {p11.plane.p, p11.stride}; a.ref1[2] = {p12.plane.p, p12.stride};
-    a.rec[0] = {oy, w}; a.rec[1] = {ou, w / 2}; a.rec[2] = {ov, w / 2};
-    a.w = w; a.h = h; a.ctus_w = (w + CTU - 1) / CTU;
-    a.prm = to_prm(prm); a.centers = centers0; a.centers1 = centers1; a.cu = cu; a.coef[0] = cy; a.coef[1] = cu_; a.coef[2] = cv; a.est = est; a.sparse_coef = 0; a.ip = nullptr;
+    IntraArgs<T> a = intra_args<T>(Views<const T>(s, w).p, Views<T>(o, w).p, w, h, prm, AnalysisOut{cu, {coef[0], coef[1], coef[2]}, est});
     if (est) *est = 0;
-    const int n_ctu = a.ctus_w * ((h + CTU - 1) / CTU), R = a.prm.me_range;
-    std::vector<int32_t> me0((size_t)n_ctu * 63), me1((size_t)n_ctu * 63);
-    a.me = me0.data(); a.me1 = me1.data();
-    SeqExec ex; ex.order = emu_order();
-    const char *waves = getenv("EMU_WAVES");
-    std::vector<uint8_t> win((size_t)me_win_elems(R) + 8);
-    std::vector<T> wy((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16), wu((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16), wv(wu.size());
-    for (int list = 0; list < 2; list++) {
-        const InterArgs<T> al = list ? list1_view(a) : a;
-        for (int c = 0; c < n_ctu; c++) {
-            MeShared<T> *ms = fresh_shared<MeShared<T>>();
-            bool ok = true;
-            if (waves) ok = run_waves((unsigned long long)atoll(waves) + (unsigned)c + 1000u * list, [&](WaveExec &wx) { me_search_program<T>(wx, *ms, win.data(), al, c); });
-            else me_search_program<T>(ex, *ms, win.data(), al, c);
-            free(ms);
-            if (!ok) return -2;
-        }
-    }
-    if (me_dump0) memcpy(me_dump0, me0.data(), me0.size() * sizeof(int32_t));
-    if (me_dump1) memcpy(me_dump1, me1.data(), me1.size() * sizeof(int32_t));
-    for (int c = 0; c < n_ctu; c++) {
-        InterShared<T> *is = fresh_shared<InterShared<T>>();
-        BiShared *bs = fresh_shared<BiShared>();
-        bool ok = true;
-        if (waves) ok = run_waves((unsigned long long)atoll(waves) + 7919u * (unsigned)c, [&](WaveExec &wx) { inter_ctu_program<T, WaveExec, true>(wx, *is, wy.data(), wu.data(), wv.data(), a, c, bs); });
-        else inter_ctu_program<T, SeqExec, true>(ex, *is, wy.data(), wu.data(), wv.data(), a, c, bs);
-        free(is); free(bs);
-        if (!ok) return -2;
-    }
-    return 0;
-}
-
-template <typename T>
-static int intra_frame(const T *sy, const T *su, const T *sv, int w, int h, const mihevc_cost_params *prm, T *oy, T *ou, T *ov,
-                       mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_, int16_t *cv, unsigned long long *est)
-{
-    IntraArgs<T> a;
-    a.src[0] = {sy, w}; a.src[1] = {su, w / 2}; a.src[2] = {sv, w / 2};
-    a.rec[0] = {oy, w}; a.rec[1] = {ou, w / 2}; a.rec[2] = {ov, w / 2};
-    a.w = w; a.h = h; a.ctus_w = (w + CTU - 1) / CTU; a.ctus_h = (h + CTU - 1) / CTU;
-    a.prm = to_prm(prm); a.cu = cu; a.coef[0] = cy; a.coef[1] = cu_; a.coef[2] = cv; a.est = est; a.sparse_coef = 0; a.ip = nullptr; a.plan = nullptr;
-    if (est) *est = 0;
-    SeqExec ex; ex.order = emu_order();
+    Stepper step;
     // same launch order as the device: per tile, one anti-diagonal (cx + 2 cy inside the tile) at a time
     const int tcn = a.prm.tile_cols > 1 ? a.prm.tile_cols : 1, trn = a.prm.tile_rows > 1 ? a.prm.tile_rows : 1;
     const int colw = (a.ctus_w + tcn - 1) / tcn, rowh = (a.ctus_h + trn - 1) / trn;
@@ -273,12 +222,8 @@ static int intra_frame(const T *sy, const T *su, const T *sv, int w, int h, cons
             const int cx0 = tile_bd(tx, tcn, a.ctus_w), cx1 = tile_bd(tx + 1, tcn, a.ctus_w), cy0 = tile_bd(ty, trn, a.ctus_h), cy1 = tile_bd(ty + 1, trn, a.ctus_h);
             const int cyi = cy0 + r, cxi = cx0 + d - 2 * r;
             if (cyi >= cy1 || cxi < cx0 || cxi >= cx1) continue;
-            IntraShared<T> *is = fresh_shared<IntraShared<T>>();
-            bool ok = true;
-            if (const char *e = getenv("EMU_WAVES")) ok = run_waves((unsigned long long)atoll(e) + (unsigned)(cyi * 4096 + cxi), [&](WaveExec &wx) { intra_ctu_program<T>(wx, *is, a, cxi, cyi); });
-            else intra_ctu_program<T>(ex, *is, a, cxi, cyi);
-            free(is);
-            if (!ok) return -2;
+            Shared<IntraShared<T>> is = fresh_shared<IntraShared<T>>();
+            if (!step((unsigned)(cyi * 4096 + cxi), [&](auto &ex) { intra_ctu_program<T>(ex, *is, a, cxi, cyi); })) return -2;
         }
     }
     return 0;
@@ -286,13 +231,10 @@ static int intra_frame(const T *sy, const T *su, const T *sv, int w, int h, cons
 
 // row0 / y_org: deblock rows [row0, row0 + h) of a whole picture's planes as a picture of its own whose first y_org rows belong to the slice above
 // (DeblockArgs::y_org; the band extended by the rows its neighbours hand over, csrc/slice_group.h)
-template <typename T> static int deblock(T *y, T *u, T *v, int w, int h, const mihevc_cu_rec *cu, int bit_depth, int row0 = 0, int y_org = 0)
+template <typename T> static int deblock(void *const *r, int w, int h, const mihevc_cu_rec *cu, int bit_depth, int row0 = 0, int y_org = 0)
 {
-    DeblockArgs<T> a;
-    a.rec[0] = {y + (ptrdiff_t)row0 * w, w}; a.rec[1] = {u + (ptrdiff_t)(row0 / 2) * (w / 2), w / 2}; a.rec[2] = {v + (ptrdiff_t)(row0 / 2) * (w / 2), w / 2};
-    a.w = w; a.h = h; a.cu = cu + (ptrdiff_t)(row0 / 8) * (w / 8); a.bit_depth = bit_depth; a.y_org = y_org;
     for (int dir = 0; dir < 2; dir++) {
-        a.dir = dir;
+        const DeblockArgs<T> a = deblock_args<T>(Views<T>(r, w, row0).p, w, h, cu + (ptrdiff_t)(row0 / 8) * (w / 8), bit_depth, dir, y_org);
         for (int i = 0; i < (w / 8) * (h / 8) * 2; i++) deblock_segment<T>(a, i);
     }
     return 0;
@@ -301,100 +243,142 @@ template <typename T> static int deblock(T *y, T *u, T *v, int w, int h, const m
 // y0 / halo: the planes are those of a whole picture of which rows [y0, y0 + h) are coded here as one slice whose filters run across the seams
 // (SaoArgs::halo; csrc/slice_group.h): the kernel then sees its band as the picture and finds the neighbour rows where the exchange puts them
 template <typename T>
-static int sao(const T *sy, const T *su, const T *sv, const T *dy, const T *du, const T *dv, int w, int h, const mihevc_cost_params *prm,
-               T *oy, T *ou, T *ov, mihevc_sao_ctu *out, int y0 = 0, int halo = 0, uint32_t *sse_ctu = nullptr, const mihevc_cu_rec *cu = nullptr)
+static int sao(const void *const *s, const void *const *d, int w, int h, const CostParams &prm, void *const *o, mihevc_sao_ctu *out, int y0 = 0, int halo = 0,
+               uint32_t *sse_ctu = nullptr, const mihevc_cu_rec *cu = nullptr)
 {
-    SaoArgs<T> a;
-    const ptrdiff_t oy_ = (ptrdiff_t)y0 * w, oc_ = (ptrdiff_t)(y0 / 2) * (w / 2);
-    a.src[0] = {sy + oy_, w}; a.src[1] = {su + oc_, w / 2}; a.src[2] = {sv + oc_, w / 2};
-    a.dbk[0] = {dy + oy_, w}; a.dbk[1] = {du + oc_, w / 2}; a.dbk[2] = {dv + oc_, w / 2};
-    a.out[0] = {oy + oy_, w}; a.out[1] = {ou + oc_, w / 2}; a.out[2] = {ov + oc_, w / 2};
-    a.w = w; a.h = h; a.ctus_w = (w + CTU - 1) / CTU; a.prm = to_prm(prm); a.sao = out; a.sse = nullptr; a.sse_ctu = sse_ctu; a.cu = cu ? cu + (size_t)(y0 / 8) * (w / 8) : nullptr; a.halo_top = (halo & 1) ? 1 : 0; a.halo_bottom = (halo & 2) ? 1 : 0;
-    SeqExec ex; ex.order = emu_order();
-    int n_ctu = a.ctus_w * ((h + CTU - 1) / CTU);
-    for (int c = 0; c < n_ctu; c++) {
-        SaoShared<T> s;
-        if (const char *e = getenv("EMU_WAVES")) { if (!run_waves((unsigned long long)atoll(e) + 131u * (unsigned)c, [&](WaveExec &wx) { sao_ctu_program<T>(wx, s, a, c); })) return -2; }
-        else sao_ctu_program<T>(ex, s, a, c);
+    const SaoArgs<T> a = sao_args<T>(Views<const T>(s, w, y0).p, Views<const T>(d, w, y0).p, Views<T>(o, w, y0).p, w, h, prm, out,
+                                     cu ? cu + (size_t)(y0 / 8) * (w / 8) : nullptr, halo, sse_ctu);
+    Stepper step;
+    for (int c = 0; c < ctus_of(w) * ctus_of(h); c++) {
+        SaoShared<T> ss;
+        if (!step(131u * (unsigned)c, [&](auto &ex) { sao_ctu_program<T>(ex, ss, a, c); })) return -2;
     }
     return 0;          // the CTU programs applied the offsets themselves (as k_sao_decide does)
 }
 
 extern "C" {
-int emu_inter_frame(const void *sy, const void *su, const void *sv, const void *ry, const void *ru, const void *rv, int w, int h,
-                    const mihevc_cost_params *prm, const int16_t *centers, void *oy, void *ou, void *ov, mihevc_cu_rec *cu,
-                    int16_t *cy, int16_t *cu_, int16_t *cv, int32_t *me_dump, unsigned long long *est)
+int emu_inter_frame(const void *sy, const void *su, const void *sv, const void *ry, const void *ru, const void *rv, int w, int h, const mihevc_cost_params *prm,
+                    const int16_t *centers, void *oy, void *ou, void *ov, mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_, int16_t *cv, int32_t *me_dump,
+                    unsigned long long *est, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return inter_frame<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, (const uint8_t *)ry, (const uint8_t *)ru,
-                                    (const uint8_t *)rv, w, h, prm, centers, (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov, cu, cy, cu_, cv, me_dump, est);
-    return inter_frame<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, (const uint16_t *)ry, (const uint16_t *)ru,
-                                 (const uint16_t *)rv, w, h, prm, centers, (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov, cu, cy, cu_, cv, me_dump, est);
+    const void *s[3] = {sy, su, sv}, *f[3] = {ry, ru, rv};
+    void *o[3] = {oy, ou, ov};
+    int16_t *c[3] = {cy, cu_, cv};
+    return with_depth(prm->bit_depth, [&](auto t) {
+        return inter_frame<decltype(t)>(s, f, nullptr, w, h, cost_params_of(*prm, sign_hide), centers, nullptr, o, cu, c, me_dump, nullptr, est);
+    });
 }
 int emu_b_frame(const void *sy, const void *su, const void *sv, const void *r0y, const void *r0u, const void *r0v, const void *r1y, const void *r1u, const void *r1v,
                 int w, int h, const mihevc_cost_params *prm, const int16_t *centers0, const int16_t *centers1, void *oy, void *ou, void *ov, mihevc_cu_rec *cu,
-                int16_t *cy, int16_t *cu_, int16_t *cv, int32_t *me_dump0, int32_t *me_dump1, unsigned long long *est)
+                int16_t *cy, int16_t *cu_, int16_t *cv, int32_t *me_dump0, int32_t *me_dump1, unsigned long long *est, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return b_frame<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, (const uint8_t *)r0y, (const uint8_t *)r0u, (const uint8_t *)r0v,
-                                (const uint8_t *)r1y, (const uint8_t *)r1u, (const uint8_t *)r1v, w, h, prm, centers0, centers1, (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov,
-                                cu, cy, cu_, cv, me_dump0, me_dump1, est);
-    return b_frame<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, (const uint16_t *)r0y, (const uint16_t *)r0u, (const uint16_t *)r0v,
-                             (const uint16_t *)r1y, (const uint16_t *)r1u, (const uint16_t *)r1v, w, h, prm, centers0, centers1, (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov,
-                             cu, cy, cu_, cv, me_dump0, me_dump1, est);
+    const void *s[3] = {sy, su, sv}, *f0[3] = {r0y, r0u, r0v}, *f1[3] = {r1y, r1u, r1v};
+    void *o[3] = {oy, ou, ov};
+    int16_t *c[3] = {cy, cu_, cv};
+    return with_depth(prm->bit_depth, [&](auto t) {
+        return inter_frame<decltype(t)>(s, f0, f1, w, h, cost_params_of(*prm, sign_hide), centers0, centers1, o, cu, c, me_dump0, me_dump1, est);
+    });
 }
 int emu_intra_frame(const void *sy, const void *su, const void *sv, int w, int h, const mihevc_cost_params *prm, void *oy, void *ou, void *ov,
-                    mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_, int16_t *cv, unsigned long long *est)
+                    mihevc_cu_rec *cu, int16_t *cy, int16_t *cu_, int16_t *cv, unsigned long long *est, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return intra_frame<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, w, h, prm, (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov, cu, cy, cu_, cv, est);
-    return intra_frame<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, w, h, prm, (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov, cu, cy, cu_, cv, est);
+    const void *s[3] = {sy, su, sv};
+    void *o[3] = {oy, ou, ov};
+    int16_t *c[3] = {cy, cu_, cv};
+    return with_depth(prm->bit_depth, [&](auto t) { return intra_frame<decltype(t)>(s, w, h, cost_params_of(*prm, sign_hide), o, cu, c, est); });
 }
 int emu_deblock(void *y, void *u, void *v, int w, int h, const mihevc_cu_rec *cu, int bit_depth)
 {
-    if (bit_depth == 8) return deblock<uint8_t>((uint8_t *)y, (uint8_t *)u, (uint8_t *)v, w, h, cu, bit_depth);
-    return deblock<uint16_t>((uint16_t *)y, (uint16_t *)u, (uint16_t *)v, w, h, cu, bit_depth);
+    void *r[3] = {y, u, v};
+    return with_depth(bit_depth, [&](auto t) { return deblock<decltype(t)>(r, w, h, cu, bit_depth); });
 }
 int emu_deblock_band(void *y, void *u, void *v, int w, int row0, int h, int y_org, const mihevc_cu_rec *cu, int bit_depth)
 {
-    if (bit_depth == 8) return deblock<uint8_t>((uint8_t *)y, (uint8_t *)u, (uint8_t *)v, w, h, cu, bit_depth, row0, y_org);
-    return deblock<uint16_t>((uint16_t *)y, (uint16_t *)u, (uint16_t *)v, w, h, cu, bit_depth, row0, y_org);
+    void *r[3] = {y, u, v};
+    return with_depth(bit_depth, [&](auto t) { return deblock<decltype(t)>(r, w, h, cu, bit_depth, row0, y_org); });
+}
+int emu_sao(const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int h, const mihevc_cost_params *prm,
+            void *oy, void *ou, void *ov, mihevc_sao_ctu *out, int sign_hide)
+{
+    const void *s[3] = {sy, su, sv}, *d[3] = {dy, du, dv};
+    void *o[3] = {oy, ou, ov};
+    return with_depth(prm->bit_depth, [&](auto t) { return sao<decltype(t)>(s, d, w, h, cost_params_of(*prm, sign_hide), o, out); });
 }
 int emu_sao_band(const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int y0, int h, int halo,
-                 const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *out)
+                 const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *out, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return sao<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, (const uint8_t *)dy, (const uint8_t *)du, (const uint8_t *)dv, w, h, prm,
-                            (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov, out, y0, halo);
-    return sao<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, (const uint16_t *)dy, (const uint16_t *)du, (const uint16_t *)dv, w, h, prm,
-                         (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov, out, y0, halo);
+    const void *s[3] = {sy, su, sv}, *d[3] = {dy, du, dv};
+    void *o[3] = {oy, ou, ov};
+    return with_depth(prm->bit_depth, [&](auto t) { return sao<decltype(t)>(s, d, w, h, cost_params_of(*prm, sign_hide), o, out, y0, halo); });
 }
 // the fused loop filter (SaoArgs::cu): r* = the PRE-deblock reconstruction; y0 / h / halo as emu_sao_band (cu: the whole picture's records)
 int emu_loop_filter(const void *sy, const void *su, const void *sv, const void *ry, const void *ru, const void *rv, int w, int y0, int h, int halo, const mihevc_cu_rec *cu,
-                    const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *out)
+                    const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *out, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return sao<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, (const uint8_t *)ry, (const uint8_t *)ru, (const uint8_t *)rv, w, h, prm,
-                            (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov, out, y0, halo, nullptr, cu);
-    return sao<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, (const uint16_t *)ry, (const uint16_t *)ru, (const uint16_t *)rv, w, h, prm,
-                         (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov, out, y0, halo, nullptr, cu);
+    const void *s[3] = {sy, su, sv}, *r[3] = {ry, ru, rv};
+    void *o[3] = {oy, ou, ov};
+    return with_depth(prm->bit_depth, [&](auto t) { return sao<decltype(t)>(s, r, w, h, cost_params_of(*prm, sign_hide), o, out, y0, halo, nullptr, cu); });
 }
-int emu_sao_sse(const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int h,
-                const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *out, uint32_t *sse_ctu)
+int emu_sao_sse(const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int h, const mihevc_cost_params *prm,
+                void *oy, void *ou, void *ov, mihevc_sao_ctu *out, uint32_t *sse_ctu, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return sao<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, (const uint8_t *)dy, (const uint8_t *)du, (const uint8_t *)dv, w, h, prm,
-                            (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov, out, 0, 0, sse_ctu);
-    return sao<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, (const uint16_t *)dy, (const uint16_t *)du, (const uint16_t *)dv, w, h, prm,
-                         (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov, out, 0, 0, sse_ctu);
+    const void *s[3] = {sy, su, sv}, *d[3] = {dy, du, dv};
+    void *o[3] = {oy, ou, ov};
+    return with_depth(prm->bit_depth, [&](auto t) { return sao<decltype(t)>(s, d, w, h, cost_params_of(*prm, sign_hide), o, out, 0, 0, sse_ctu); });
 }
-int emu_sao(const void *sy, const void *su, const void *sv, const void *dy, const void *du, const void *dv, int w, int h,
-            const mihevc_cost_params *prm, void *oy, void *ou, void *ov, mihevc_sao_ctu *out)
+
+// K3 on n_blocks blocks of 2^log2n (log2n 3..5: luma TUs of a pseudo-CTU, log2n 2: 4x4 DCT blocks in its chroma planes), every block in scan
+// `scan`, with sign data hiding when sign_hide
+int emu_transform_sdh(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int log2n, int qp, int bit_depth, int intra, int scan, int sign_hide)
 {
-    if (prm->bit_depth == 8)
-        return sao<uint8_t>((const uint8_t *)sy, (const uint8_t *)su, (const uint8_t *)sv, (const uint8_t *)dy, (const uint8_t *)du, (const uint8_t *)dv, w, h, prm,
-                            (uint8_t *)oy, (uint8_t *)ou, (uint8_t *)ov, out);
-    return sao<uint16_t>((const uint16_t *)sy, (const uint16_t *)su, (const uint16_t *)sv, (const uint16_t *)dy, (const uint16_t *)du, (const uint16_t *)dv, w, h, prm,
-                         (uint16_t *)oy, (uint16_t *)ou, (uint16_t *)ov, out);
+    if (log2n < 2 || log2n > 5 || scan < 0 || scan > 2) return -3;
+    const int n = 1 << log2n, lt = log2n < 3 ? 3 : log2n, per = log2n == 2 ? 32 : 1024 >> (2 * log2n);       // blocks per pseudo-CTU
+    // block b of a pseudo-CTU -> index of its top-left sample in the 1536-sample arrays
+    auto origin = [&](int b) {
+        if (log2n > 2) return (b / (32 >> log2n)) * n * 32 + (b % (32 >> log2n)) * n;
+        return 1024 + (b >> 4) * 256 + ((b & 15) >> 2) * 4 * 16 + (b & 3) * 4;
+    };
+    SeqExec ex;
+    for (int first = 0; first < n_blocks; first += per) {
+        Shared<ResidualShared> s = fresh_shared<ResidualShared>();
+        residual_init(ex, *s);
+        ex.phase([&](int tid) {
+            if (tid < 16) {
+                const int blk = log2n > 2 ? first + ((tid >> 2) * 8 >> lt) * (32 >> lt) + ((tid & 3) * 8 >> lt) : first + tid;
+                s->tu_log2[tid] = blk < n_blocks ? (uint8_t)lt : 0;
+                s->tu_intra[tid] = (uint8_t)intra;
+            }
+            for (int i = tid; i < 1536; i += NT) s->res[i] = 0;
+        });
+        ex.phase([&](int tid) {
+            for (int b = tid; b < per; b += NT) {
+                if (first + b >= n_blocks) continue;
+                const int o = origin(b), st = o < 1024 ? 32 : 16;
+                for (int k = 0; k < n * n; k++) s->res[o + (k / n) * st + k % n] = res[(size_t)(first + b) * n * n + k];
+            }
+        });
+        ex.phase([&](int tid) { for (int i = tid; i < 1536; i += NT) { SampleLoc l = locate(*s, i); l.scan = scan; s->desc[i] = pack_loc(l); } });
+        residual_pipeline(ex, *s, qp, qp, bit_depth, whole_ctu(), 0, sign_hide);
+        for (int b = 0; b < per && first + b < n_blocks; b++) {
+            const int o = origin(b), st = o < 1024 ? 32 : 16;
+            for (int k = 0; k < n * n; k++) {
+                lvl[(size_t)(first + b) * n * n + k] = s->lvl[o + (k / n) * st + k % n];
+                rec[(size_t)(first + b) * n * n + k] = s->res[o + (k / n) * st + k % n];
+            }
+        }
+    }
+    return 0;
+}
+
+// k_transform4_blocks on n_blocks 4x4 blocks (DST-VII when dst, else DCT), the same grid of NT / 16 blocks per workgroup
+int emu_transform4_sdh(const int16_t *res, int16_t *lvl, int16_t *rec, int n_blocks, int qp, int bit_depth, int intra, int dst, int scan, int sign_hide)
+{
+    if (scan < 0 || scan > 2) return -3;
+    SeqExec ex;
+    for (int first = 0; first < n_blocks; first += NT / 16) {
+        Shared<Transform4Shared> s = fresh_shared<Transform4Shared>();
+        transform4_program(ex, *s, res, lvl, rec, n_blocks, first, qp, bit_depth, intra, dst, scan, sign_hide);
+    }
+    return 0;
 }
 }

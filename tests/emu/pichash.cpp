@@ -1,4 +1,4 @@
-// tests/emu_hash/emu_hash.cpp — TEST HARNESS, NOT PRODUCT.  The decoded picture hash programs of hevc_amd/csrc/kernels/pichash.h (k_pic_hash, then
+// tests/emu/pichash.cpp — TEST HARNESS, NOT PRODUCT (part of tests/emu/libkernel_emu.so).  The decoded picture hash programs of hevc_amd/csrc/kernels/pichash.h (k_pic_hash, then
 // k_pic_hash_fold) stepped on the CPU with the sequential executor, over host planes laid out as mihevc_k_picture_hash takes them; the planes sit in a
 // border as a session's final reconstruction does, so rows are hashed through a pitch.  hevc_amd/ never loads this library.
 #include <cstdlib>

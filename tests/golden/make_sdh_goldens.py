@@ -2,7 +2,7 @@
 """Golden coded pictures with sign data hiding (cfg.sign_hide = 1): `python tests/golden/make_sdh_goldens.py` rewrites tests/golden/streams_sdh.json.
 
 The cases of make_stream_goldens.py with sign_hide = 1, plus one with B pictures.  The oracle has no sign data hiding, so here the KERNEL SOURCES
-stepped on the CPU with the switch on (tests/emu_sdh) analyse every picture, in the order and with the parameters a session uses, the product's
+stepped on the CPU with the switch on (tests/emu) analyse every picture, in the order and with the parameters a session uses, the product's
 host coder turns the symbols into slice NAL units, and the SHA-256 of every coded picture (decoding order) and of every reconstruction (display
 order) goes into the fixture.  tests/test_sign_hiding_cpu.py recomputes them and decodes them with the repository's decoder (whose sign inference
 was written apart from the encoder); tests/test_gpu_sign_hiding.py checks that an MI355X session produces the same bytes."""
@@ -10,7 +10,6 @@ import ctypes as C
 import hashlib
 import importlib.util
 import json
-import subprocess
 import sys
 from pathlib import Path
 
@@ -26,25 +25,9 @@ _spec = importlib.util.spec_from_file_location("make_stream_goldens", Path(__fil
 G = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(G)
 
-EMU_DIR = ROOT / "tests" / "emu_sdh"
 CASES = dict(G.CASES)
 CASES["b96x80_bframes"] = (96, 80, 8, 7, 7, 1, 28, 8, 93, {"bframes": 1, "rdo_cg": 5})
 sha, frame_hash = G.sha, G.frame_hash
-
-
-def emu_lib():
-    """tests/emu_sdh/libkernel_emu_sdh.so, rebuilt when a kernel header or the harness is newer"""
-    so = EMU_DIR / "libkernel_emu_sdh.so"
-    srcs = [EMU_DIR / "emu_sdh.cpp", ROOT / "tests" / "emu" / "emu.cpp", ROOT / "include" / "mihevc.h"] + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h"))
-    if not so.exists() or any(s.stat().st_mtime > so.stat().st_mtime for s in srcs):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-w", "-pthread", "-o", str(so), str(EMU_DIR / "emu_sdh.cpp")], check=True)
-    return C.CDLL(str(so))
-
-
-def stepped_api(sign_hide=1):
-    lib = emu_lib()
-    lib.emu_set_sign_hide(sign_hide)
-    return util.StageApi(lib, "emu_")
 
 
 def config(name):
@@ -77,7 +60,7 @@ def coding_order(n, with_b):
 
 
 def params(cfg, qp, idr):
-    """the cost parameters a session hands its kernels for one picture (mihevc_cost_params; sign_hide comes from the harness switch)"""
+    """the cost parameters a session hands its kernels for one picture (mihevc_cost_params; the stepped entries take sign_hide beside it)"""
     cp = _lib.cost_params(qp, cfg.bit_depth, cfg.me_range if cfg.me_range > 0 else 15)
     cp.tile_cols, cp.tile_rows = _lib.tile_grid(cfg) if idr else _lib.p_tile_grid(cfg)
     cp.intra_nxn, cp.intra_in_p, cp.pre_search, cp.rdo_zero, cp.chroma_modes = cfg.intra_nxn, cfg.intra_in_p, cfg.pre_search, cfg.rdo_zero, cfg.chroma_modes
@@ -119,7 +102,7 @@ def stepped_pictures(api, cfg, srcs, idr, qp):
 
 def case_pictures(name, api=None):
     w, h, bd, n, keyint, lanes, qp = CASES[name][:7]
-    return stepped_pictures(api or stepped_api(1), config(name), frames(name), util.idr_positions(n, keyint, lanes), qp)
+    return stepped_pictures(api or util.StageApi(util.stepped_library(), "emu_", sign_hide=1), config(name), frames(name), util.idr_positions(n, keyint, lanes), qp)
 
 
 def summary(pics):
@@ -128,7 +111,7 @@ def summary(pics):
 
 
 if __name__ == "__main__":
-    api = stepped_api(1)
+    api = util.StageApi(util.stepped_library(), "emu_", sign_hide=1)
     out = {name: summary(case_pictures(name, api)) for name in CASES}
     (Path(__file__).parent / "streams_sdh.json").write_text(json.dumps(out, indent=1) + "\n")
     for k, v in out.items():

@@ -10,8 +10,9 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import numpy as np                      # noqa: E402
 from oracle import oracle as O          # noqa: E402
 from tests import util                  # noqa: E402
+from tests.test_bitstream_cpu import occluded_clip      # noqa: E402
 
-emu = util.StageApi(C.CDLL(os.environ["EMU_LIB"]), "emu_")
+emu = util.StageApi(C.CDLL(os.environ["EMU_LIB"]), "emu_", sign_hide=0)
 cases = [(96, 96, 24, 8, 8), (72, 104, 26, 10, 8)] + ([] if os.environ.get("EMU_WAVES") else [(384, 320, 30, 8, 15)])
 for (w, h, qp, bd, rng) in cases:
     prm_i = O.default_params(max(0, qp - 3), bit_depth=bd, me_range=rng)
@@ -43,3 +44,21 @@ for (w, h, qp, bd, rng) in cases:
     gb = emu.b(srcs[1], recs[0], recs[2], prm_b)
     assert util.same_analysis(wb, gb), (w, h, "B")
     print("ok", w, h, bd, flush=True)
+
+# the intra second pass of P pictures (prm.intra_in_p), on pictures with a pasted patch the reference cannot predict: CTUs of every P picture
+# take the pass, which the check against the same P picture without it shows
+for (w, h, qp, bd) in [(128, 96, 28, 8), (72, 72, 26, 10)]:
+    prm = O.default_params(qp, bit_depth=bd, me_range=8)
+    prm.intra_nxn, prm.chroma_modes, prm.rdo_zero, prm.pre_search = 1, 1, 1, 1
+    srcs = occluded_clip(w, h, bd)
+    a = O.analyze_intra(srcs[0], prm)
+    ref, _ = O.sao(srcs[0], O.deblock(a.rec, a.cu, bd), prm)
+    for i in (1, 2):
+        prm.intra_in_p = 0
+        plain = O.analyze_inter(srcs[i], ref, prm, dump_me=True)
+        prm.intra_in_p = 1
+        want, got = O.analyze_inter(srcs[i], ref, prm, dump_me=True), emu.inter(srcs[i], ref, prm)
+        assert not util.same_analysis(plain, want), (w, h, i, "no CTU took the intra second pass")
+        assert util.same_analysis(want, got), (w, h, i, util.describe_diff(want, got))
+        ref, _ = O.sao(srcs[i], O.deblock(want.rec, want.cu, bd), prm)
+    print("ok intra second pass", w, h, bd, flush=True)

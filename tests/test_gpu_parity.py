@@ -489,15 +489,15 @@ def test_b_picture_stage_equals_oracle(api, w, h, qp, bd, rng, pre, content):
     qi, qb = (max(0, qp - 3), qp + 2) if synth else (qp, qp)
     cp_i, cp_p, cp_b = _lib.cost_params(qi, bd, rng), _lib.cost_params(qp, bd, rng), _lib.cost_params(qb, bd, rng)
     cp_p.rdo_zero = cp_b.rdo_zero = 1
-    to_prm = lambda cp: O.Params(cp.qp, cp.qp_c, cp.bit_depth, cp.lambda_sad_q4, cp.lambda_q4, cp.me_range, 1, 1, 0, 0, 0, cp.rdo_zero, 0)      # noqa: E731
+    oracle_prm = lambda cp: O.Params(cp.qp, cp.qp_c, cp.bit_depth, cp.lambda_sad_q4, cp.lambda_q4, cp.me_range, 1, 1, 0, 0, 0, cp.rdo_zero, 0)      # noqa: E731
     f = [util.content_frame(content, h, w, seed=23, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(3)]
-    a0 = O.analyze_intra(f[0], to_prm(cp_i))
-    r0, _ = O.sao(f[0], O.deblock(a0.rec, a0.cu, bd), to_prm(cp_i))
-    a2 = O.analyze_inter(f[2], r0, to_prm(cp_p))
-    r2, _ = O.sao(f[2], O.deblock(a2.rec, a2.cu, bd), to_prm(cp_p))
+    a0 = O.analyze_intra(f[0], oracle_prm(cp_i))
+    r0, _ = O.sao(f[0], O.deblock(a0.rec, a0.cu, bd), oracle_prm(cp_i))
+    a2 = O.analyze_inter(f[2], r0, oracle_prm(cp_p))
+    r2, _ = O.sao(f[2], O.deblock(a2.rec, a2.cu, bd), oracle_prm(cp_p))
     c0 = O.search_centres(f[1], f[0], bd) if pre else None
     c1 = O.search_centres(f[1], f[2], bd) if pre else None
-    want = O.analyze_b(f[1], r0, r2, to_prm(cp_b), c0, c1, dump_me=True)
+    want = O.analyze_b(f[1], r0, r2, oracle_prm(cp_b), c0, c1, dump_me=True)
     got = api.b(f[1], r0, r2, cp_b, c0, c1)
     assert np.array_equal(want.me[0], got.me[0]) and np.array_equal(want.me[1], got.me[1]), "integer searches differ"
     assert util.same_analysis(want, got), util.describe_diff(want, got)
@@ -505,7 +505,7 @@ def test_b_picture_stage_equals_oracle(api, w, h, qp, bd, rng, pre, content):
     assert api.deblock(want.rec, want.cu, bd).same(O.deblock(want.rec, want.cu, bd))
     if not synth:
         d = O.deblock(want.rec, want.cu, bd)
-        wf, wsp = O.sao(f[1], d, to_prm(cp_b))
+        wf, wsp = O.sao(f[1], d, oracle_prm(cp_b))
         util.check_envelope_run([f[1]], [(want, d, wf, wsp)], qp, bd)
         gf, gsp = api.sao(f[1], d, cp_b)
         assert np.array_equal(gsp, wsp) and gf.same(wf), "sao"

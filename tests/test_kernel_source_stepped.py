@@ -1,26 +1,15 @@
 """CPU: the HIP kernel SOURCES (hevc_amd/csrc/kernels/*.h) stepped with the sequential executor must reproduce the
 oracle bit for bit.  This checks the kernels' logic without a GPU; the -m gpu tests check the gfx950 binaries.
 tests/emu/libkernel_emu.so is a test harness only — hevc_amd/ never loads it (tests/test_layout.py)."""
-import ctypes as C
-import subprocess
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
 from tests import util
 
-EMU_DIR = Path(__file__).resolve().parent / "emu"
-
-
 @pytest.fixture(scope="module")
 def emu():
-    so = EMU_DIR / "libkernel_emu.so"
-    srcs = [EMU_DIR / "emu.cpp"] + list((EMU_DIR.parents[1] / "hevc_amd" / "csrc" / "kernels").glob("*.h"))
-    if not so.exists() or any(s.stat().st_mtime > so.stat().st_mtime for s in srcs):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-w", "-pthread", "-o", str(so), str(EMU_DIR / "emu.cpp")], check=True)
-    return util.StageApi(C.CDLL(str(so)), "emu_")
+    return util.StageApi(util.stepped_library(), "emu_", sign_hide=0)
 
 
 CASES = [

@@ -1,28 +1,21 @@
 """CPU: the decoded picture hash (mihevc_config.pic_hash, H.265 Annex D payloadType 132).  The numpy reference of tests/pichash_ref.py against its
-own definitions (known answers, the literal CRC bit loop); the kernel programs of hevc_amd/csrc/kernels/pichash.h stepped on the CPU (tests/emu_hash)
+own definitions (known answers, the literal CRC bit loop); the kernel programs of hevc_amd/csrc/kernels/pichash.h stepped on the CPU (tests/emu)
 against that reference; the host MD5 of mihevc_k_picture_hash against hashlib; the suffix SEI NAL unit mihevc_write_picture_hash_sei writes, read back;
 configuration checks."""
 import ctypes as C
 import hashlib
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from hevc_amd import _lib
 from tests import pichash_ref as R
-
-EMU_DIR = Path(__file__).resolve().parent / "emu_hash"
+from tests import util
 
 
 @pytest.fixture(scope="module")
 def emu():
-    so = EMU_DIR / "libemu_hash.so"
-    srcs = [EMU_DIR / "emu_hash.cpp"] + list((EMU_DIR.parents[1] / "hevc_amd" / "csrc" / "kernels").glob("*.h"))
-    if not so.exists() or any(s.stat().st_mtime > so.stat().st_mtime for s in srcs):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-w", "-o", str(so), str(EMU_DIR / "emu_hash.cpp")], check=True)
-    lib = C.CDLL(str(so))
+    lib = util.stepped_library()
     lib.emu_picture_hash.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]
     return lib
 

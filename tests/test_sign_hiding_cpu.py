@@ -1,5 +1,5 @@
 """CPU: sign data hiding (mihevc_config.sign_hide).  The rule the kernels apply, restated here in numpy on the oracle's transform and quantiser,
-against the kernel sources stepped with the switch on (tests/emu_sdh); whole pictures stepped with the switch on obey the parity rule in every coded
+against the kernel sources stepped with the switch on (tests/emu); whole pictures stepped with the switch on obey the parity rule in every coded
 4x4 group, and their symbols, coded by the product's host coder, decode with the repository's decoder (oracle/hevc_dec.c infers the hidden signs)
 to the stepped reconstruction; the host coder refuses a group that breaks the rule; the golden SDH streams (tests/golden/streams_sdh.json)."""
 import ctypes as C
@@ -143,7 +143,7 @@ def k3_run(call, log2n, scan, bd, qp, kind, intra, dst=False):
 
 @pytest.fixture(scope="module")
 def emu():
-    return S.stepped_api(1)
+    return util.StageApi(util.stepped_library(), "emu_", sign_hide=1)
 
 
 def test_rule_restated_in_numpy_equals_the_stepped_k3(emu):
@@ -277,25 +277,22 @@ def test_decoder_sees_the_pps_flag():
 
 
 def test_harness_without_sign_hiding_equals_the_oracle():
-    """the harness steps the same kernels as tests/emu: switched off, its pictures are the oracle's"""
-    api = S.stepped_api(0)
-    try:
-        for w, h, qp, bd in ((96, 80, 22, 8), (72, 104, 26, 10)):
-            prm_i, prm_p = O.default_params(qp - 3, bd, 8), O.default_params(qp, bd, 8)
-            prm_i.intra_nxn = 1
-            prm_p.rdo_cg, prm_p.intra_in_p, prm_p.rdo_zero = 5, 1, 1
-            srcs = [util.synth_frame(h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(3)]
-            want = util.run_pipeline(O, srcs, prm_i, prm_p, bd)
-            ref = None
-            for i, (src, (a, d, f, sp)) in enumerate(zip(srcs, want)):
-                got = api.intra(src, prm_i) if i == 0 else api.inter(src, ref, prm_p)
-                assert util.same_analysis(a, got), f"picture {i}: " + util.describe_diff(a, got)
-                ref = f
-            b = api.b(srcs[1], want[0][2], want[2][2], O.default_params(qp + 2, bd, 8))
-            ob = O.analyze_b(srcs[1], want[0][2], want[2][2], O.default_params(qp + 2, bd, 8))
-            assert util.same_analysis(ob, b)
-    finally:
-        api.lib.emu_set_sign_hide(1)
+    """the harness steps the same kernels as tests/test_kernel_source_stepped.py: switched off, its pictures are the oracle's"""
+    api = util.StageApi(util.stepped_library(), "emu_", sign_hide=0)
+    for w, h, qp, bd in ((96, 80, 22, 8), (72, 104, 26, 10)):
+        prm_i, prm_p = O.default_params(qp - 3, bd, 8), O.default_params(qp, bd, 8)
+        prm_i.intra_nxn = 1
+        prm_p.rdo_cg, prm_p.intra_in_p, prm_p.rdo_zero = 5, 1, 1
+        srcs = [util.synth_frame(h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(3)]
+        want = util.run_pipeline(O, srcs, prm_i, prm_p, bd)
+        ref = None
+        for i, (src, (a, d, f, sp)) in enumerate(zip(srcs, want)):
+            got = api.intra(src, prm_i) if i == 0 else api.inter(src, ref, prm_p)
+            assert util.same_analysis(a, got), f"picture {i}: " + util.describe_diff(a, got)
+            ref = f
+        b = api.b(srcs[1], want[0][2], want[2][2], O.default_params(qp + 2, bd, 8))
+        ob = O.analyze_b(srcs[1], want[0][2], want[2][2], O.default_params(qp + 2, bd, 8))
+        assert util.same_analysis(ob, b)
 
 
 def test_host_coder_refuses_a_group_that_breaks_the_rule(emu):

@@ -158,7 +158,7 @@ def test_sao_of_a_band_with_halo_rows_equals_the_whole_picture(emu, w, h, bd, ro
         halo = (1 if k > 0 else 0) | (2 if k < len(rows) - 1 else 0)
         sp = np.zeros(wc * r, O.SAO_DTYPE)
         rc = emu.lib.emu_sao_band(util.ptr(s[0]), util.ptr(s[1]), util.ptr(s[2]), util.ptr(d[0]), util.ptr(d[1]), util.ptr(d[2]), w, y0, bh, halo, C.byref(prm),
-                                  util.ptr(out[0]), util.ptr(out[1]), util.ptr(out[2]), util.ptr(sp))
+                                  util.ptr(out[0]), util.ptr(out[1]), util.ptr(out[2]), util.ptr(sp), emu.sign_hide)
         assert rc == 0
         got_sp[wc * r0:wc * (r0 + r)] = sp
         r0 += r

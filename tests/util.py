@@ -1,10 +1,16 @@
 """Shared helpers of the test-suite: deterministic synthetic pictures and array plumbing between the oracle
 (uint16 containers) and the product C ABI (uint8 planes at 8 bit, uint16 at 10 bit)."""
 import ctypes as C
+import os
+import subprocess
+from pathlib import Path
 
 import numpy as np
 
 from oracle import oracle as O
+
+ROOT = Path(__file__).resolve().parents[1]
+EMU_DIR = ROOT / "tests" / "emu"
 
 
 def synth_frame(h, w, seed=0, shift=(0, 0), bit_depth=8, detail=True) -> O.Frame:
@@ -148,15 +154,35 @@ def psnr(a, b, peak=255.0):
     return 99.0 if mse == 0 else 10 * np.log10(peak * peak / mse)
 
 
+def stepped_library():
+    """tests/emu/libkernel_emu.so: the kernel sources stepped on the CPU (a test harness: hevc_amd/ never loads it).  Rebuilt when a harness
+    source, a kernel header, the stage argument builders or the ABI header is newer than the library"""
+    so = EMU_DIR / "libkernel_emu.so"
+    sources = sorted(EMU_DIR.glob("*.cpp"))
+    deps = sources + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "include" / "mihevc.h"]
+    if not so.exists() or any(d.stat().st_mtime > so.stat().st_mtime for d in deps):
+        tmp = so.with_name(f"libkernel_emu.{os.getpid()}.so")                  # renamed into place: a process that has the old one loaded keeps it
+        try:
+            subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-w", "-pthread", "-o", str(tmp)] + [str(x) for x in sources], check=True)
+            os.replace(tmp, so)
+        finally:
+            tmp.unlink(missing_ok=True)
+    return C.CDLL(str(so))
+
+
 class StageApi:
-    """Thin wrapper over the per-stage C-ABI entry points (mihevc_k_* or the emu_* twins with the same shape)."""
+    """Thin wrapper over the per-stage C-ABI entry points: prefix "mihevc_k_" (the device entries; device: its index) or "emu_" (their stepped twins,
+    which take sign_hide after the arguments of every entry that takes cost parameters)."""
 
-    def __init__(self, lib, prefix, device=None):
-        self.lib, self.prefix, self.device = lib, prefix, device
+    def __init__(self, lib, prefix, device=None, sign_hide=0):
+        assert prefix == "emu_" or not sign_hide, "the device entries take sign data hiding from the session configuration only"
+        self.lib, self.prefix, self.device, self.sign_hide = lib, prefix, device, sign_hide
 
-    def _call(self, name, *args):
+    def _call(self, name, *args, cost=True):
+        """cost: the entry takes a mihevc_cost_params"""
         f = getattr(self.lib, self.prefix + name)
-        rc = f(*(([self.device] if self.device is not None else []) + list(args)))
+        tail = [self.sign_hide] if cost and self.prefix == "emu_" else []
+        rc = f(*(([self.device] if self.device is not None else []) + list(args) + tail))
         assert rc == 0, f"{self.prefix}{name} -> {rc}"
 
     def intra(self, src: O.Frame, prm):
@@ -172,39 +198,31 @@ class StageApi:
         return a
 
     def inter(self, src: O.Frame, ref: O.Frame, prm, centers=None):
-        bd = prm.bit_depth
-        h, w = src.shape
-        s, r = planes(src, bd), planes(ref, bd)
-        o = [np.zeros_like(p) for p in s]
-        a = O.Analysis(h, w)
-        me = np.zeros((n_ctus(w, h), 21, 3), np.int32)
-        est = C.c_uint64(0)
-        cen = np.ascontiguousarray(centers, dtype=np.int16) if centers is not None else None
-        self._call("inter_frame", ptr(s[0]), ptr(s[1]), ptr(s[2]), ptr(r[0]), ptr(r[1]), ptr(r[2]), w, h, C.byref(prm),
-                   ptr(cen) if cen is not None else None, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(a.cu), ptr(a.coef_y), ptr(a.coef_u), ptr(a.coef_v), ptr(me), C.byref(est))
-        a.rec, a.me, a.est = to_frame(o), me, est.value
-        return a
+        return self._inter(src, [ref], prm, [centers])
 
     def b(self, src: O.Frame, ref0: O.Frame, ref1: O.Frame, prm, centers0=None, centers1=None):
         """B picture between two anchors (mihevc_k_b_frame / emu_b_frame): a.me = (list-0 dump, list-1 dump)"""
+        return self._inter(src, [ref0, ref1], prm, [centers0, centers1])
+
+    def _inter(self, src, refs, prm, centers):
+        """P (one reference: inter_frame) or B (two: b_frame); centers: one entry per reference, None or per CTU (sx, sy)"""
         bd = prm.bit_depth
         h, w = src.shape
-        s, r0, r1 = planes(src, bd), planes(ref0, bd), planes(ref1, bd)
+        s, r = planes(src, bd), [p for ref in refs for p in planes(ref, bd)]
         o = [np.zeros_like(p) for p in s]
         a = O.Analysis(h, w)
-        me = [np.zeros((n_ctus(w, h), 21, 3), np.int32) for _ in range(2)]
+        me = [np.zeros((n_ctus(w, h), 21, 3), np.int32) for _ in refs]
         est = C.c_uint64(0)
-        cen = [np.ascontiguousarray(c, dtype=np.int16) if c is not None else None for c in (centers0, centers1)]
-        self._call("b_frame", ptr(s[0]), ptr(s[1]), ptr(s[2]), ptr(r0[0]), ptr(r0[1]), ptr(r0[2]), ptr(r1[0]), ptr(r1[1]), ptr(r1[2]), w, h, C.byref(prm),
-                   ptr(cen[0]) if cen[0] is not None else None, ptr(cen[1]) if cen[1] is not None else None, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(a.cu), ptr(a.coef_y),
-                   ptr(a.coef_u), ptr(a.coef_v), ptr(me[0]), ptr(me[1]), C.byref(est))
-        a.rec, a.me, a.est = to_frame(o), tuple(me), est.value
+        cen = [np.ascontiguousarray(c, dtype=np.int16) if c is not None else None for c in centers]
+        self._call("inter_frame" if len(refs) == 1 else "b_frame", *map(ptr, s), *map(ptr, r), w, h, C.byref(prm), *[ptr(c) if c is not None else None for c in cen],
+                   *map(ptr, o), ptr(a.cu), ptr(a.coef_y), ptr(a.coef_u), ptr(a.coef_v), *map(ptr, me), C.byref(est))
+        a.rec, a.me, a.est = to_frame(o), me[0] if len(refs) == 1 else tuple(me), est.value
         return a
 
     def deblock(self, rec: O.Frame, cu, bd):
         r = planes(rec, bd)
         h, w = rec.shape
-        self._call("deblock", ptr(r[0]), ptr(r[1]), ptr(r[2]), w, h, ptr(np.ascontiguousarray(cu)), bd)
+        self._call("deblock", ptr(r[0]), ptr(r[1]), ptr(r[2]), w, h, ptr(np.ascontiguousarray(cu)), bd, cost=False)
         return to_frame(r)
 
     def sao(self, src: O.Frame, dbk: O.Frame, prm):
