@@ -10,10 +10,14 @@ RANK / LOCAL_RANK / WORLD_SIZE in the environment) or `python bench.py --gpus N`
 Every rank binds device LOCAL_RANK and encodes its own clip; barrier and MAX-over-ranks time go over gloo (host TCP on 127.0.0.1) —
 nothing is exchanged between GPUs, so there is no RCCL anywhere (north_star).  Scaling is weak.
 
-Outside the timed region rank 0 adds: `stream_ok` (the last step's stream decoded by the oracle decoder: picture count and per-plane SSE
-against the source must equal the encoder's own statistics), `value_pcie_inclusive` (the same clip handed over as host buffers), a
-`configs` block with the 2160p30 Main10 HDR10 run (BASELINE configs[2]), `cpu_baseline` (the oracle on one host core) and `libx265`
-(the reference's own ffmpeg command when ffmpeg + libx265 exist on the host; probed, never assumed).
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes `--dump-outputs` and prints the line
+(`value`, `ms_per_step`, the workload, per-rank rates, the last step's PSNR / bitrate and host phases).
+
+With `--full`, rank 0 adds outside the timed region: `stages_ms_per_picture`, `roofline` and `pipeline` (from one more step with every stage
+bracketed), `stream_ok` (the last step's stream decoded by the oracle decoder: picture count and per-plane SSE against the source must equal
+the encoder's own statistics), `value_pcie_inclusive` (the same clip handed over as host buffers) and the two-session rates, a `configs`
+block with the 2160p30 Main10 HDR10 run (BASELINE configs[2]), `cpu_baseline` (the oracle on the host cores) and `libx265` (the reference's
+own ffmpeg command when ffmpeg + libx265 exist on the host; probed, never assumed).
 """
 import argparse
 import glob
@@ -365,8 +369,11 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--me-range", type=int, default=15)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed legs (stream check, PCIe-inclusive run, 2160p config, libx265 probe run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed legs: per-stage profile step and roofline, stream check, PCIe-inclusive and "
+                         "two-session runs, 2160p config, libx265, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the stream check, PCIe-inclusive and two-session runs, 2160p config and libx265")
     ap.add_argument("--host-threads", type=int, default=0, help="CABAC worker threads (0 = library default)")
     ap.add_argument("--qp", type=int, default=-1, help="experiments only: force the P-picture QP instead of deriving it from the CRF")
     ap.add_argument("--profile-stages", type=int, default=2, help="HIP events in the timed steps: 2 = around the dominant kernel (inter_ctu) only, 1 = every stage, 0 = none")
@@ -534,7 +541,32 @@ def main():
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, kept, hdrs, st, psnr)
 
-    # ---- untimed legs ----
+    if rank == 0:
+        fps = world * args.steps * N / dt
+        out = {
+            "metric": METRIC,
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u8", "data": "synthetic",
+            "config": {"workload": f"{W}x{H}@30 SDR 8-bit Main, crf {crf} capped by VBV maxrate {maxrate} kbps / bufsize {bufsize} kbit "
+                                   f"(the reference's libx265 operating point), {N}-frame synthetic 'motion' clip per GPU, "
+                                   f"keyint {gop} ({(N + gop - 1) // gop} closed GOPs" + (" of equal length" if cfg.gop_balance else "") + f"), IPPP, full-search +-{args.me_range}, one clip per GPU, input resident in HBM"},
+            "per_rank_fps": [round(args.steps * N / d, 2) for d in own], **({"shared_gpu_rehearsal": True} if SHARE_GPU else {}),
+            "stream_ok": None,
+            "quality": {"psnr_y_db": round(psnr, 3), "bitrate_kbps": round(nbytes * 8 / (N / 30.0) / 1e3, 1), "vbv_maxrate_kbps": maxrate},
+            "host": {"entropy_ms_per_frame_sum_over_threads": round(st.entropy_ms / max(1, st.frames_out), 4), "cpus": os.cpu_count(), "numa_node": numa_node, "cpus_bound": len(os.sched_getaffinity(0)),
+                     "step_phases_ms": dict(zip(("open", "send", "flush_drain", "close"), [round(x / args.steps * 1e3, 2) for x in phase_s])),
+                     "device_ms_per_step": round(st.device_ms, 2),
+                     "chunk_host_ms": {"before_first_launch": round(st.reserved[3] / 1e3, 2), "after_last_kernel": round(st.reserved[4] / 1e3, 2), "chunk_wall": round(st.reserved[5] / 1e3, 2)}},
+        }
+    if not args.full:
+        if rank == 0:
+            emit(out)
+        ranks.barrier()
+        ranks.close()
+        return
+
+    # ---- untimed legs (--full) ----
     if rank == 0 and args.profile_stages != 1:       # one more step with every stage bracketed: the per-stage table (events cost ~5 % fps)
         cfg.profile_stages = 1
         stp = step()[0]
@@ -546,7 +578,6 @@ def main():
     oks = ranks.gather(1.0 if check.get("stream_ok") else 0.0)
 
     if rank == 0:
-        fps = world * args.steps * N / dt
         # roofline of the dominant kernel: algorithmic bytes per launch / mean launch time (HIP events on the session's
         # compute stream).  Per picture: inter_ctu reads source + reference and writes the reconstruction = 3*S;
         # me_search reads source + reference luma = 2*W*H; intra = S read + S write; loop filters: see DESIGN.md.
@@ -565,33 +596,18 @@ def main():
         traffic, traffic_src, traffic_all = measured_traffic(kname, (W, H, N, args.me_range))
         valu = measured_valu(kname)
         ok265, why265 = libx265_probe()
-        out = {
-            "metric": METRIC,
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
-            "config": {"workload": f"{W}x{H}@30 SDR 8-bit Main, crf {crf} capped by VBV maxrate {maxrate} kbps / bufsize {bufsize} kbit "
-                                   f"(the reference's libx265 operating point), {N}-frame synthetic 'motion' clip per GPU, "
-                                   f"keyint {gop} ({(N + gop - 1) // gop} closed GOPs" + (" of equal length" if cfg.gop_balance else "") + f"), IPPP, full-search +-{args.me_range}, one clip per GPU, input resident in HBM"},
-            "per_rank_fps": [round(args.steps * N / d, 2) for d in own], **({"shared_gpu_rehearsal": True} if SHARE_GPU else {}),
-            "stream_ok": bool(all(o == 1.0 for o in oks)) if not args.no_extras else None,
-            "stream_check": check,
-            "quality": {"psnr_y_db": round(psnr, 3), "bitrate_kbps": round(nbytes * 8 / (N / 30.0) / 1e3, 1), "vbv_maxrate_kbps": maxrate,
-                        "libx265_parity": "see `libx265`" if ok265 else why265},
-            "stages_ms_per_picture": {_lib.STAGE_NAMES[i]: round(stage_ms[i] / max(1.0, stage_pics[i]), 4) for i in range(8)},
-            "host": {"entropy_ms_per_frame_sum_over_threads": round(st.entropy_ms / max(1, st.frames_out), 4), "cpus": os.cpu_count(), "numa_node": numa_node, "cpus_bound": len(os.sched_getaffinity(0)),
-                     "step_phases_ms": dict(zip(("open", "send", "flush_drain", "close"), [round(x / args.steps * 1e3, 2) for x in phase_s])),
-                     "device_ms_per_step": round(st.device_ms, 2),
-                     "chunk_host_ms": {"before_first_launch": round(st.reserved[3] / 1e3, 2), "after_last_kernel": round(st.reserved[4] / 1e3, 2), "chunk_wall": round(st.reserved[5] / 1e3, 2)}},
-            "roofline": {"bound": "hbm", "kernel": _lib.STAGE_NAMES[dom], "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                         "avg_launch_ms": round(avg_ms, 4), "pictures_per_launch": round(bytes_per_launch / per_pic[dom], 2),
-                         "dominant_by_full_profile": _lib.STAGE_NAMES[int(np.argmax(stage_ms[:7]))],
-                         "valu_issue_frac": valu["valu_issue_frac"] if valu else None, "valu": valu,
-                         "note": "integer-VALU/LDS bound path: the HBM fraction is small by construction (SURVEY.md §0.5); valu_issue_frac is the "
-                                 "share of SIMD issue slots the kernel fills, from the committed SQ counter pass"},
-        }
+        out["stream_ok"] = bool(all(o == 1.0 for o in oks)) if not args.no_extras else None
+        out["stream_check"] = check
+        out["quality"]["libx265_parity"] = "see `libx265`" if ok265 else why265
+        out["stages_ms_per_picture"] = {_lib.STAGE_NAMES[i]: round(stage_ms[i] / max(1.0, stage_pics[i]), 4) for i in range(8)}
+        out["roofline"] = {"bound": "hbm", "kernel": _lib.STAGE_NAMES[dom], "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
+                           "algorithmic_bytes_per_launch": int(bytes_per_launch),
+                           "avg_launch_ms": round(avg_ms, 4), "pictures_per_launch": round(bytes_per_launch / per_pic[dom], 2),
+                           "dominant_by_full_profile": _lib.STAGE_NAMES[int(np.argmax(stage_ms[:7]))],
+                           "valu_issue_frac": valu["valu_issue_frac"] if valu else None, "valu": valu,
+                           "note": "integer-VALU/LDS bound path: the HBM fraction is small by construction (SURVEY.md §0.5); valu_issue_frac is the "
+                                   "share of SIMD issue slots the kernel fills, from the committed SQ counter pass"}
         # the whole pipeline beside its dominant kernel: algorithmic bytes of a picture over ALL stages (an IDR picture reads its source and writes its
         # reconstruction, a P picture also reads its reference once: SURVEY.md §8d) x pictures / step time, and the HBM bytes the counters saw for all kernels
         n_idr = (N + gop - 1) // gop

@@ -99,7 +99,7 @@ def test_config5_4320p_unsliced_stage_parity_i_p(lib, api, frames_4320p):
 def test_config4_bench_two_ranks_share_device_0():
     """the real bench.py at world size 2 with real encoders: each rank its own clip (seed = rank), gloo barrier, MAX over ranks, one JSON line"""
     env = dict(os.environ, MIHEVC_BENCH_SHARE_GPU="1")
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

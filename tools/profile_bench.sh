@@ -8,7 +8,7 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py --steps 5 > $out/bench.json
+python3 bench.py --steps 5 --full > $out/bench.json
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $out/bench_under_rocprof.json
 rocprofv3 --pmc FETCH_SIZE -d $out/fetch -o f --output-format csv -- python3 $root/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras --profile-stages 1 > /dev/null
