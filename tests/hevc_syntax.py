@@ -6,13 +6,15 @@ tables are its own transcription of the standard.  tests/test_syntax_independent
 library and numpy.
 
 It parses the subset the encoder emits: Main and Main 10, 4:2:0, CTB 32, minimum CB 8, TU 4..32, tiles, several slices per picture, SAO,
-intra NxN, 2Nx2N inter, P and B slices with one picture per list.  Anything outside that subset -- including any tool flag the encoder never
-sets (TMVP, sign hiding, transform skip, cu_qp_delta, AMP, PCM, WPP, dependent slices, weighted prediction, scaling lists, long-term pictures,
-list modification, more than one reference per list) being 1 -- raises Unsupported instead of being guessed.
+intra NxN, 2Nx2N inter, P and B slices with one picture per list, sign data hiding, and the SEI messages buffering period, picture timing,
+mastering display colour volume, content light level and (in suffix SEI NAL units) decoded picture hash.  Anything outside that subset --
+including any tool flag the encoder never sets (TMVP, transform skip, cu_qp_delta, AMP, PCM, WPP, dependent slices, weighted prediction,
+scaling lists, long-term pictures, list modification, more than one reference per list) being 1 -- raises Unsupported instead of being guessed.
 
 parse_stream(bytes) -> Stream with the parameter sets, the SEI and AUD payloads and one Picture per coded picture in decoding order: NAL type,
-POC, slice types and QPs, a per-8x8 record of every coding-unit decision, the coefficient levels in picture raster, the SAO parameters per CTB
-and the number of times each (syntax element, ctxInc, initType) was decoded.
+POC, slice types and QPs, a per-8x8 record of every coding-unit decision, the coefficient levels in picture raster, the SAO parameters per CTB,
+the decoded picture hash that follows it and the number of times each (syntax element, ctxInc, initType) was decoded.  tests/hevc_recon.py
+reconstructs the samples from it.
 """
 from __future__ import annotations
 
@@ -354,7 +356,7 @@ def parse_pps(r: Bits):
     subset(r.u1() == 0, "dependent_slice_segments_enabled_flag")
     subset(r.u1() == 0, "output_flag_present_flag")
     p["num_extra_slice_header_bits"] = r.u(3)
-    subset(r.u1() == 0, "sign_data_hiding_enabled_flag")
+    p["sign_data_hiding_enabled_flag"] = r.u1()
     p["cabac_init_present_flag"] = r.u1()
     p["num_ref_idx_default"] = (r.ue() + 1, r.ue() + 1)
     p["init_qp"] = 26 + r.se()
@@ -444,6 +446,17 @@ def parse_sei(r: Bits, sps, nal_type):
             m["max_luminance"], m["min_luminance"] = r.u(32), r.u(32)
         elif ptype == 144:                                      # D.2.35 content_light_level_info
             m["max_content_light_level"], m["max_pic_average_light_level"] = r.u(16), r.u(16)
+        elif ptype == 132:                                      # D.2.19 decoded_picture_hash (suffix SEI only)
+            subset(nal_type == 40, "decoded picture hash in a prefix SEI NAL unit")
+            m["hash_type"] = r.u(8)
+            subset(m["hash_type"] <= 2, "hash_type %d" % m["hash_type"])
+            vals = []
+            for _ in range(3):                                  # cIdx 0..2 (chroma_format_idc 1)
+                if m["hash_type"] == 0:
+                    vals.append(bytes(r.u(8) for _ in range(16)))      # picture_md5[cIdx][i]
+                else:
+                    vals.append(r.u(16) if m["hash_type"] == 1 else r.u(32))   # picture_crc / picture_checksum
+            m["hash"] = vals
         else:
             raise Unsupported("SEI payload type %d" % ptype)
         need(r.pos - start <= 8 * size, "SEI payload %d reads past its size" % ptype)
@@ -760,13 +773,16 @@ class Picture:
         self.ctb_slice = [-1] * nctb
         self.decoded = 0
         self.merge_lists = {}                                   # (x, y) -> the derived merge candidate list of an inter CU
+        self.hash = None                                        # (hash_type, [3 values]) of the decoded picture hash SEI that follows it
 
 
 class SliceDecoder:
     """7.3.8 slice_segment_data and everything it calls, for one slice segment"""
+    sign_hiding = 0                                             # sign_data_hiding_enabled_flag of the PPS
 
     def __init__(self, pic: Picture, sps, pps, lay: Layout, hdr, rbsp, nal_pos, data_start, ref_pocs, hits):
         self.pic, self.sps, self.pps, self.lay, self.hdr = pic, sps, pps, lay, hdr
+        self.sign_hiding = pps.get("sign_data_hiding_enabled_flag", 0)
         self.rbsp, self.nal_pos, self.data_start = rbsp, nal_pos, data_start
         self.ref_pocs = ref_pocs                                # POC of RefPicList0[0], RefPicList1[0] (None: list not in use)
         self.hits = hits
@@ -1378,8 +1394,12 @@ class SliceDecoder:
             g2 = {}
             if last_g1_pos >= 0:
                 g2[last_g1_pos] = dec("coeff_abs_level_greater2_flag", ctx_set + (4 if c else 0))
-            signs = {nn: byp() for nn in sig_pos}               # no sign data hiding in the subset
+            # 7.3.8.11: signHidden when lastSigScanPos - firstSigScanPos > 3 (no cu_transquant_bypass_flag in the subset); the sign of the
+            # coefficient at firstSigScanPos is then not coded but inferred from the parity of sumAbsLevel (7.4.9.11)
+            hidden = self.sign_hiding and sig_pos[0] - sig_pos[-1] > 3
+            signs = {nn: (0 if hidden and nn == sig_pos[-1] else byp()) for nn in sig_pos}
             nsig = 0
+            sum_abs = 0
             rice, last_abs, first_rem = 0, 0, True
             for nn in sig_pos:
                 base = 1 + g1.get(nn, 0) + g2.get(nn, 0)
@@ -1392,8 +1412,12 @@ class SliceDecoder:
                     level = base + rem
                 else:
                     level = base
+                sum_abs += level
+                neg = signs[nn]
+                if hidden and nn == sig_pos[-1] and sum_abs % 2 == 1:
+                    neg = 1
                 xp, yp = pos_scan[nn]
-                out[(ys << 2) + yp, (xs << 2) + xp] = -level if signs[nn] else level
+                out[(ys << 2) + yp, (xs << 2) + xp] = -level if neg else level
                 nsig += 1
         return out
 
@@ -1552,7 +1576,12 @@ def parse_stream(stream: bytes) -> Stream:
             r.rbsp_trailing_bits()
         elif nal_type in (39, 40):
             sps = next(iter(out.sps.values())) if out.sps else None
-            out.sei.append((nal_type, parse_sei(r, sps, nal_type)))
+            msgs = parse_sei(r, sps, nal_type)
+            out.sei.append((nal_type, msgs))
+            for m in msgs:
+                if m["type"] == 132:                            # D.3.19: the hash of the picture whose slices precede this suffix SEI
+                    need(pic is not None and pic.hash is None, "decoded picture hash without a picture, or twice for one")
+                    pic.hash = (m["hash_type"], m["hash"])
         elif nal_type in (0, 1, 19, 20):
             h, sps, pps = slice_header(r, nal_type, out.sps, out.pps)
             key = (id(sps), id(pps))

@@ -1,10 +1,12 @@
 """GPU (-m gpu): the streams of small sessions read back by the independent syntax reader (tests/hevc_syntax.py).  What it reads -- quadtree,
 modes, motion, cbfs, levels, SAO, slice QP, NAL type and POC -- must equal, picture by picture, the analyses of the oracle pipeline replayed with the
-session's QPs (the replay also asserts that the session's reconstruction equals the oracle's)."""
+session's QPs (the replay also asserts that the session's reconstruction equals the oracle's), and the samples tests/hevc_recon.py rebuilds from
+what it reads must equal the session's reconstruction."""
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import hevc_recon as R
 from tests import hevc_syntax as S
 from tests import util
 from tests.test_syntax_independent import check_parameter_sets, check_picture
@@ -27,6 +29,24 @@ def small_cfg(w, h, bd, **kw):
     for k, v in kw.items():
         setattr(cfg, k, v)
     return cfg
+
+
+def check_recon(st, recs):
+    """the independent reconstruction of every picture equals the session's (recs by display position, at the coded size) and its hash SEI, if
+    any; -> the reconstruction's coverage counter"""
+    stats = {}
+    out = R.reconstruct(st, stats)
+    base = 0
+    for k, (pic, (poc, y, u, v)) in enumerate(zip(st.pictures, out)):
+        if pic.nal_type in (19, 20):
+            base = k                                            # closed GOPs: an IDR's display position is its decoding position
+        r = recs[base + poc]
+        for c, (a, b) in enumerate(((y, r.y), (u, r.u), (v, r.v))):
+            assert a.shape == b.shape and np.array_equal(a, b), \
+                "display picture %d plane %d: %d samples of the session's reconstruction differ from the independent one" % (base + poc, c, int((a != b).sum()))
+    for k, hh in enumerate(stats["hash"]):
+        assert hh is None or hh[1] == hh[2], "picture %d: hash SEI %s, independent reconstruction %s" % (k, hh[1], hh[2])
+    return stats["cov"]
 
 
 def check_session(st, replayed, infos):
@@ -53,6 +73,7 @@ def test_session_streams_read_independently_equal_the_replayed_analyses(lib, w, 
     st = S.parse_stream(stream)
     check_session(st, out, infos)
     check_parameter_sets(st, cfg, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)))
+    check_recon(st, recs)
 
 
 def test_session_with_p_tiles_read_independently(lib):
@@ -70,6 +91,7 @@ def test_session_with_p_tiles_read_independently(lib):
     check_session(st, out, infos)
     check_parameter_sets(st, cfg, ((2, 1), (2, 1)))
     assert all(len(p.slices[0]["header"]["entry_point_offsets"]) == 1 for p in st.pictures)
+    check_recon(st, recs)
 
 
 def test_b_session_read_independently(lib):
@@ -84,6 +106,7 @@ def test_b_session_read_independently(lib):
     st = S.parse_stream(b"".join(p[0] for p in pk))
     check_session(st, out, infos)
     check_parameter_sets(st, cfg, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)))
+    assert check_recon(st, recs)["inter", "bi"] > 0
     kinds = set()
     for pic in st.pictures:
         if pic.slices[0]["slice_type"] == 0:
@@ -126,3 +149,4 @@ def test_sliced_encoder_stream_read_independently(lib):
         check_picture(pic, a, sao, infos[i][0], 2 if intra else 1, 19 if intra else 1, i - g0)
     check_parameter_sets(st, cfgs[0], (_lib.tile_grid(cfgs[0]), _lib.p_tile_grid(cfgs[0])))
     assert np.all([len(p.slices) == len(rows) for p in st.pictures])
+    check_recon(st, recs)

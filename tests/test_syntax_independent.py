@@ -21,20 +21,29 @@ HERE = Path(__file__).resolve().parent
 
 
 # ================================================================ the reader is independent
+# the independent modules and what each may import besides the standard library and numpy
+INDEPENDENT = {"hevc_syntax.py": set(), "hevc_recon.py": {"tests.hevc_syntax", "tests.pichash_ref"}, "pichash_ref.py": set()}
+
+
 def test_the_reader_imports_only_the_standard_library_and_numpy():
-    tree = ast.parse((HERE / "hevc_syntax.py").read_text())
-    names = set()
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Import):
-            names |= {a.name.split(".")[0] for a in node.names}
-        elif isinstance(node, ast.ImportFrom):
-            assert node.level == 0, "relative import in the reader"
-            names.add(node.module.split(".")[0])
-        elif isinstance(node, ast.Call) and getattr(node.func, "id", getattr(node.func, "attr", "")) in ("__import__", "import_module", "open", "read_text"):
-            pytest.fail("the reader loads code or files at run time (%s)" % ast.dump(node.func))
-    names.discard("__future__")
-    assert names, names
-    assert all(n == "numpy" or n in sys.stdlib_module_names for n in names), names
+    """tests/hevc_syntax.py and tests/hevc_recon.py (with the stdlib-and-numpy tests/pichash_ref.py it uses) load nothing of hevc_amd/ or oracle/"""
+    for module, allowed in INDEPENDENT.items():
+        tree = ast.parse((HERE / module).read_text())
+        names = set()
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Import):
+                names |= {a.name.split(".")[0] for a in node.names}
+            elif isinstance(node, ast.ImportFrom):
+                assert node.level == 0, "relative import in %s" % module
+                if node.module == "tests":
+                    names |= {"tests." + a.name for a in node.names}
+                else:
+                    names.add(node.module.split(".")[0])
+            elif isinstance(node, ast.Call) and getattr(node.func, "id", getattr(node.func, "attr", "")) in ("__import__", "import_module", "open", "read_text"):
+                pytest.fail("%s loads code or files at run time (%s)" % (module, ast.dump(node.func)))
+        names.discard("__future__")
+        assert names, (module, names)
+        assert all(n == "numpy" or n in sys.stdlib_module_names or n in allowed for n in names), (module, names)
 
 
 # ================================================================ known answers, worked by hand
@@ -166,6 +175,32 @@ def test_residual_coding_4x4_with_an_escape_and_a_rising_rice_parameter():
     ctx = [e for e in cab.log if e != "bypass"]
     assert ctx[:4] == [("last_sig_coeff_x_prefix", 15), ("last_sig_coeff_x_prefix", 16), ("last_sig_coeff_x_prefix", 17), ("last_sig_coeff_y_prefix", 15)]
     assert [i for _, i in ctx[4:9]] == [30, 33, 28, 29, 27] and [i for _, i in ctx[9:14]] == [17, 16, 16, 16, 16] and ctx[14][1] == 4
+
+
+def test_residual_coding_4x4_with_a_hidden_sign():
+    """sign data hiding on, inter luma 4x4 (diagonal scan) with levels at scan positions 9, 4 and 0: (x 3, y 0) = 2, (1, 1) = -1 and (0, 0) = ?.
+    lastSigScanPos 9 - firstSigScanPos 0 = 9 > 3: signHidden, so coeff_sign_flag is coded for n = 9 and 4 only and the sign at n = 0 is inferred
+    from sumAbsLevel (7.4.9.11).  last x prefix 3 = '111' (cMax 3), last y prefix 0 = '0'; sig_coeff_flag n = 8..0; greater1 on n = 9, 4, 0 (flags 1, 0,
+    0), greater2 on n = 9 (0): |levels| 2, 1, 1, no coeff_abs_level_remaining.  sumAbsLevel 4 is even: the level at n = 0 stays +1.  With a third
+    level of 1 at n = 0 replaced by a remaining escape of 1 (|level| 2 there, sum 5, odd) it becomes -2."""
+    lead = [1, 1, 1, 0]                                             # last_sig_coeff_x_prefix '111', last_sig_coeff_y_prefix '0'
+    sig = [0, 0, 0, 0, 1, 0, 0, 0, 1]                               # sig_coeff_flag n = 8 .. 0
+    for g1_0, rem, want0 in ((0, [], 1), (1, [0], -2)):
+        bins = lead + sig + [1, 0, g1_0] + [0] + [0, 1]              # greater1 n = 9, 4, 0; greater2 n = 9; signs n = 9 (+), 4 (-)
+        bins += rem                                                  # n = 0 with greater1: baseLevel 2 = 1 + 1 + 0 (not first greater1): TR '0' -> 0
+        cab = ScriptedBins(bins)
+        dec = S.SliceDecoder.__new__(S.SliceDecoder)
+        dec.cab, dec.sign_hiding = cab, 1
+        out = dec.residual_block(2, 0, None)
+        assert not cab.bins, cab.bins
+        want = np.zeros((4, 4), np.int32)
+        want[0, 3], want[1, 1], want[0, 0] = 2, -1, want0
+        assert np.array_equal(out, want), out
+    # the same bins without sign data hiding leave one bin unread (the coded sign of n = 0) and then run out
+    dec = S.SliceDecoder.__new__(S.SliceDecoder)
+    dec.cab = ScriptedBins(lead + sig + [1, 0, 0] + [0] + [0, 1] + [1])
+    out = dec.residual_block(2, 0, None)
+    assert out[0, 0] == -1 and not dec.cab.bins
 
 
 def neighbourhood(poc, ref_pocs, motions, slice_type=0, max_merge=5):
@@ -366,12 +401,12 @@ def pictures_case(name, w, h, qp, bd, n, keyint, content="synth", nxn=0, intra_i
         hh = (h + 7) & ~7
         ww = (w + 7) & ~7
         srcs = [util.synth_frame(hh, ww, seed=6, shift=(2 * i, i), bit_depth=bd) for i in range(n)]
-    _, stream, _, packets = encode_pictures(cfg, srcs, qp, bd, keyint=keyint, nxn=nxn, intra_in_p=intra_in_p)
+    _, stream, recs, packets = encode_pictures(cfg, srcs, qp, bd, keyint=keyint, nxn=nxn, intra_in_p=intra_in_p)
     coded = []
     for i, (a, sao, q) in enumerate(zip(encode_pictures.last_analyses, encode_pictures.last_saos, encode_pictures.last_qps)):
         intra = i % keyint == 0
         coded.append((a, sao, q, 2 if intra else 1, 19 if intra else 1, i % keyint))
-    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg))
+    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)), recs
 
 
 def b_case(name, w, h, qp, bd, n, aud, content="synth"):
@@ -383,9 +418,9 @@ def b_case(name, w, h, qp, bd, n, aud, content="synth"):
         srcs = [util.synth_frame(h, w, seed=17, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(n)]
     else:
         srcs = flashing_clip(w, h, bd, n)
-    stream, _, types, _ = encode_gop_with_b(cfg, srcs, qp, bd)
+    stream, recs, types, _ = encode_gop_with_b(cfg, srcs, qp, bd)
     coded = [(a, sao, q, st, {2: 19, 1: 1, 0: 0}[st], pos) for pos, st, a, sao, q in encode_gop_with_b.last_coded]
-    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg))
+    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)), [recs[pos] for pos, _, _, _, _ in encode_gop_with_b.last_coded]
 
 
 def sliced_case(name, w, h, bd, rows, level, keyint, n=3):
@@ -401,7 +436,7 @@ def sliced_case(name, w, h, bd, rows, level, keyint, n=3):
     m = lib.mihevc_write_parameter_sets(C.byref(cfgs[0]), buf, len(buf))
     heads = bytes(buf[:m])
     prm_i, prm_p = O.default_params(24, bd, 12), O.default_params(27, bd, 12)
-    refs, stream, coded = [None] * len(rows), b"", []
+    refs, stream, coded, recs = [None] * len(rows), b"", [], []
     for i in range(n):
         intra = i % keyint == 0
         per = []
@@ -424,8 +459,106 @@ def sliced_case(name, w, h, bd, rows, level, keyint, n=3):
             stream += pkt
             per.append((a, sao, prm.qp))
         coded.append((per, 2 if intra else 1, 19 if intra else 1, i % keyint))
+        recs.append(O.Frame(*(np.vstack([getattr(r, c) for r in refs]) for c in "yuv")))
     full = sliced_cfg(w, h, bd, rows, 0, level, aud=1)
-    return full, stream, coded, (_lib.tile_grid(cfgs[0]), _lib.p_tile_grid(cfgs[0]))
+    return full, stream, coded, (_lib.tile_grid(cfgs[0]), _lib.p_tile_grid(cfgs[0])), recs
+
+
+def hash_case(name, w, h, qp, bd, n, pic_hash, **kw):
+    """pictures_case with a decoded picture hash SEI (hash_type pic_hash - 1, written by the product's SEI writer) behind every picture, of the
+    oracle pipeline's reconstruction.  No AUDs: the repository's decoder reads a suffix SEI behind the slices only without them (as in
+    tests/test_gpu_pichash.py)"""
+    from hevc_amd import _lib
+    from tests import pichash_ref as R
+    from tests import util
+    from tests.test_bitstream_cpu import encode_pictures, make_cfg
+    cfg = make_cfg(w, h, bd, aud=0, pic_hash=pic_hash, **kw)
+    srcs = [util.synth_frame(h, w, seed=13, shift=(3 * i, 2 * i), bit_depth=bd) for i in range(n)]
+    headers, _, recs, packets = encode_pictures(cfg, srcs, qp, bd, keyint=1000, nxn=1, intra_in_p=1)
+    lib, buf = _lib.load(), (C.c_uint8 * 256)()
+    stream, coded = b"", []
+    for i, ((pkt, _, intra), a, sao, q) in enumerate(zip(packets, encode_pictures.last_analyses, encode_pictures.last_saos, encode_pictures.last_qps)):
+        if i == 0:
+            pkt = headers + pkt
+        vals = R.picture_hash([recs[i].y, recs[i].u, recs[i].v], bd, pic_hash - 1)
+        raw = (C.c_uint8 * 48)(*b"".join(vals)) if pic_hash == 1 else (C.c_uint32 * 3)(*vals)
+        m = lib.mihevc_write_picture_hash_sei(C.byref(cfg), pic_hash - 1, raw, buf, len(buf))
+        assert m > 0, m
+        stream += pkt + bytes(buf[:m])
+        coded.append((a, sao, q, 2 if intra else 1, 19 if intra else 1, i))
+    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)), recs
+
+
+def sdh_case(name, w, h, qp, bd, n=3, content="synth"):
+    """test_sign_hiding_cpu's pictures: the kernel sources stepped on the CPU with sign_hide = 1 (I, P with NxN, the intra second pass and
+    rdo_cg, then a B picture), coded by the product's host coder"""
+    from hevc_amd import _lib
+    from oracle import oracle as O
+    from tests import util
+    from tests.test_sign_hiding_cpu import S as SDH
+    cfg = _lib.default_config()
+    cfg.width, cfg.height, cfg.bit_depth, cfg.me_range, cfg.qp, cfg.keyint, cfg.bframes = w, h, bd, 8, qp, 5, 1
+    cfg.intra_nxn, cfg.intra_in_p, cfg.rdo_cg, cfg.pre_search, cfg.sign_hide, cfg.level_idc = 1, 1, 5, 0, 1, 93
+    srcs = [util.content_frame(content, h, w, seed=3, shift=(2 * i, i), bit_depth=bd) for i in range(n)]
+    pics = SDH.stepped_pictures(util.StageApi(util.stepped_library(), "emu_", sign_hide=1), cfg, srcs, [0], qp)
+    buf = (C.c_uint8 * (1 << 16))()
+    m = _lib.load().mihevc_write_parameter_sets(C.byref(cfg), buf, len(buf))
+    stream, coded, recs = bytes(buf[:m]), [], []
+    for i, st, pkt, a, rec in pics:
+        q = max(0, qp - 3) if st == 2 else qp + 2 if st == 0 else qp
+        _, sao = O.sao(srcs[i], O.deblock(a.rec, a.cu, bd), SDH.params(cfg, q, st == 2))
+        stream += pkt
+        coded.append((a, sao, q, st, {2: 19, 1: 1, 0: 0}[st], i))
+        recs.append(rec)
+    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)), recs
+
+
+def drawn_intra_case(name, w, h, qp, bd):
+    """CU records drawn by hand and given straight to the host coder: two IDR pictures of 32x32 and then 16x16 intra CUs whose luma modes run
+    through 0..34 in raster order (chroma in DM, so its 16x16 and 8x8 TBs see every mode too), random low-frequency levels in every TB, and SAO
+    band offset in every CTB with sao_band_position 29, 30 and 31, where the four bands wrap round to 0.  The encoder's own search does not reach
+    every mode at every size.  No oracle pipeline made these pictures: the reconstruction to compare with is the repository decoder's."""
+    from hevc_amd import _lib
+    from oracle import oracle as O
+    from tests import util
+    from tests.test_bitstream_cpu import make_cfg
+    cfg = make_cfg(w, h, bd, aud=1)
+    lib = _lib.load()
+    buf = (C.c_uint8 * (4 << 20))()
+    m = lib.mihevc_write_parameter_sets(C.byref(cfg), buf, len(buf))
+    headers = bytes(buf[:m])
+    rng = np.random.default_rng(7)
+    cmax = (1 << (min(bd, 10) - 5)) - 1
+    stream, coded = b"", []
+    for i, log2 in enumerate((5, 4)):
+        a = O.Analysis(h, w)
+        n = 1 << log2
+        for k, (y0, x0) in enumerate((y, x) for y in range(0, h, n) for x in range(0, w, n)):
+            mode = k % 35
+            flags = 0
+            for c, (plane, tb) in enumerate(((a.coef_y, n), (a.coef_u, n // 2), (a.coef_v, n // 2))):
+                yc, xc = (y0, x0) if c == 0 else (y0 // 2, x0 // 2)
+                lv = rng.integers(-4, 5, (4, 4)) * (rng.random((4, 4)) < 0.5)
+                plane[yc:yc + 4, xc:xc + 4] = lv
+                flags |= int(lv.any()) << (c + 1)
+            r = a.cu[y0 // 8:(y0 + n) // 8, x0 // 8:(x0 + n) // 8]
+            r["log2_size"], r["flags"], r["qp"], r["intra_mode"], r["chroma_mode"] = log2, flags, qp, mode, mode
+        nctb = ((w + 31) // 32) * ((h + 31) // 32)
+        sao = np.zeros(nctb, O.SAO_DTYPE)
+        for rs in range(nctb):
+            sao[rs]["type"] = (1, 1)
+            sao[rs]["band_pos"] = (29 + rs % 3, 29 + (rs + 1) % 3, 29 + (rs + 2) % 3)
+            sao[rs]["offset"] = rng.integers(-cmax, cmax + 1, (3, 4))
+        m = lib.mihevc_encode_picture_host(C.byref(cfg), 2, 0, qp, util.ptr(a.cu), util.ptr(a.coef_y), util.ptr(a.coef_u), util.ptr(a.coef_v),
+                                           util.ptr(sao), buf, len(buf))
+        assert m > 0, m
+        pkt = bytes(buf[:m])
+        if i == 0:
+            cut = pkt.index(b"\0\0\0\1", 4)
+            pkt = pkt[:cut] + headers + pkt[cut:]
+        stream += pkt
+        coded.append((a, sao, qp, 2, 19, 0))
+    return cfg, stream, coded, (_lib.tile_grid(cfg), _lib.p_tile_grid(cfg)), None
 
 
 from tests.test_bitstream_cpu import ENVELOPE_STREAM_CASES, STREAM_CASES  # noqa: E402
@@ -456,13 +589,25 @@ CASES.update({
     "b-96x80-qp0-full_range": (b_case, dict(w=96, h=80, qp=0, bd=8, n=5, aud=1, content="full_range")),
     "sliced-160x96": (sliced_case, dict(w=160, h=96, bd=8, rows=(2, 1), level=63, keyint=3)),
     "sliced-96x160-10bit": (sliced_case, dict(w=96, h=160, bd=10, rows=(1, 2, 2), level=63, keyint=2)),
+    "sdh-64x64": (sdh_case, dict(w=64, h=64, qp=30, bd=8)),
+    "sdh-72x104-10bit": (sdh_case, dict(w=72, h=104, qp=26, bd=10)),
+    "drawn-intra-224x160": (drawn_intra_case, dict(w=224, h=160, qp=30, bd=8)),
+    "hash-md5-96x80": (hash_case, dict(w=96, h=80, qp=27, bd=8, n=3, pic_hash=1)),
+    "hash-crc-72x104-10bit": (hash_case, dict(w=72, h=104, qp=25, bd=10, n=3, pic_hash=2)),
+    "hash-checksum-136x72": (hash_case, dict(w=136, h=72, qp=32, bd=8, n=3, pic_hash=3)),
 })
 
 
 @functools.lru_cache(maxsize=None)
-def parsed(name):
+def encoded(name):
+    """(configuration, stream, per picture what was coded, tile grids, the oracle pipeline's reconstructions in decoding order)"""
     fn, kw = CASES[name]
-    cfg, stream, coded, grids = fn(name, **kw)
+    return fn(name, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def parsed(name):
+    cfg, stream, coded, grids, _ = encoded(name)
     return cfg, S.parse_stream(stream), coded, grids
 
 
@@ -502,6 +647,14 @@ def test_parsed_stream_equals_the_encoder_decisions(name):
         assert st.sps[0]["vui"]["chroma_sample_loc_type_top_field"] == 0
     if name == "sao-off-still":
         assert all(p.cu["skip"].all() for p in st.pictures[1:])
+    pps_flags = {st.pps[s["pps_id"]]["sign_data_hiding_enabled_flag"] for p in st.pictures for s in p.slices}
+    assert pps_flags == {int(name.startswith("sdh-"))}
+    if name.startswith("hash-"):
+        kind = CASES[name][1]["pic_hash"] - 1
+        assert all(p.hash is not None and p.hash[0] == kind for p in st.pictures)
+        assert all(m["type"] == 132 for t, msgs in st.sei if t == 40 for m in msgs)
+    else:
+        assert all(p.hash is None for p in st.pictures)
 
 
 # Contexts the emitted subset can never reach, with the reason.  Every other (syntax element, ctxInc, initType) of the reader's tables must be decoded
