@@ -24,13 +24,14 @@ class Config(C.Structure):
         [("md_primaries", (C.c_uint16 * 2) * 3), ("md_white", C.c_uint16 * 2), ("md_max_lum", C.c_uint32), ("md_min_lum", C.c_uint32),
          ("max_cll", C.c_uint16), ("max_fall", C.c_uint16)] +
         [(n, C.c_int32) for n in ("me_range", "gops_in_flight", "host_threads", "sao", "profile_stages", "intra_tiles", "intra_nxn", "intra_in_p", "hrd", "pre_search", "rdo_zero", "chroma_modes", "pic_height", "slice_count", "slice_index")] +
-        [("slice_ctu_rows", C.c_int32 * 16), ("rate_share_q16", C.c_int32), ("scenecut", C.c_int32), ("gop_balance", C.c_int32), ("rdo_cg", C.c_int32), ("p_tiles", C.c_int32), ("bframes", C.c_int32), ("b_qp_offset", C.c_int32), ("slice_halo", C.c_int32), ("slice_group", C.c_int32), ("sign_hide", C.c_int32), ("pic_hash", C.c_int32)])
+        [("slice_ctu_rows", C.c_int32 * 16), ("rate_share_q16", C.c_int32), ("scenecut", C.c_int32), ("gop_balance", C.c_int32), ("rdo_cg", C.c_int32), ("p_tiles", C.c_int32), ("bframes", C.c_int32), ("b_qp_offset", C.c_int32), ("slice_halo", C.c_int32), ("slice_group", C.c_int32), ("sign_hide", C.c_int32), ("pic_hash", C.c_int32), ("ssim", C.c_int32)])
 
 
 class Stats(C.Structure):
     _fields_ = [("frames_in", C.c_int64), ("frames_out", C.c_int64), ("bytes_out", C.c_int64), ("sse_y", C.c_double), ("sse_u", C.c_double),
                 ("sse_v", C.c_double), ("device_ms", C.c_double), ("entropy_ms", C.c_double), ("last_qp", C.c_int32), ("reserved", C.c_int32 * 7),
-                ("stage_ms", C.c_double * 8), ("stage_launches", C.c_int64 * 8), ("stage_pictures", C.c_int64 * 8)]
+                ("stage_ms", C.c_double * 8), ("stage_launches", C.c_int64 * 8), ("stage_pictures", C.c_int64 * 8),
+                ("ssim_y", C.c_double), ("ssim_u", C.c_double), ("ssim_v", C.c_double)]
 
 
 STAGE_NAMES = ("intra", "me_search", "inter_ctu", "deblock", "sao", "pad", "sse", "intra_p")
@@ -46,7 +47,7 @@ EXPORTS = (
     "mihevc_receive_packet", "mihevc_flush", "mihevc_abort", "mihevc_close", "mihevc_get_stats", "mihevc_get_headers", "mihevc_set_keep_recon",
     "mihevc_get_recon", "mihevc_coded_size", "mihevc_get_frame_info", "mihevc_strerror", "mihevc_last_error", "mihevc_cost_params_for_qp", "mihevc_tile_grid", "mihevc_p_tile_grid", "mihevc_k_transform", "mihevc_k_transform_sdh",
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
-    "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei",
+    "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
 )
 
 _lib = None
@@ -108,6 +109,8 @@ def load() -> C.CDLL:
     lib.mihevc_encode_picture_host.argtypes = [C.POINTER(Config), i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t]
     lib.mihevc_k_picture_hash.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.mihevc_write_picture_hash_sei.argtypes = [C.POINTER(Config), i32, vp, vp, C.c_size_t]
+    lib.mihevc_get_frame_quality.argtypes = [vp, i64, vp, vp, vp]
+    lib.mihevc_k_ssim.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     _lib = lib
     return lib
 

@@ -85,7 +85,7 @@ static bool config_ok(const mihevc_config *c)
 {
     return c && c->width >= 16 && c->height >= 16 && c->width <= 8192 && c->height <= 4352 && !(c->width & 1) && !(c->height & 1) &&
            (c->bit_depth == 8 || c->bit_depth == 10) && c->fps_num > 0 && c->fps_den > 0 && (c->sign_hide == 0 || c->sign_hide == 1) &&
-           c->pic_hash >= 0 && c->pic_hash <= 3 && (c->pic_hash == 0 || c->slice_count <= 1);
+           c->pic_hash >= 0 && c->pic_hash <= 3 && (c->pic_hash == 0 || c->slice_count <= 1) && (c->ssim == 0 || (c->ssim == 1 && c->slice_count <= 1));
 }
 
 int mihevc_tile_grid(const mihevc_config *cfg, int *cols, int *rows)

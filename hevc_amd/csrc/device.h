@@ -10,6 +10,7 @@
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
 #include "kernels/pichash.h"
+#include "kernels/ssim.h"
 
 namespace mihevc {
 
@@ -48,6 +49,10 @@ template <typename T> hipError_t launch_sse_fold(hipStream_t st, const SaoArgs<T
 // The three 32-bit hash words go to (uint8_t *)args.sse + out_off; `part` is scratch of pic_hash_part_words(w, h, sizeof(T)) words per picture
 int pic_hash_part_words(int w, int h, int bps);
 template <typename T> hipError_t launch_pic_hash(hipStream_t st, const SaoArgs<T> *d_args, int w, int h, int batch, int kind, uint32_t *part, size_t out_off);
+// SSIM (kernels/ssim.h) of the sources SaoArgs::src against the final reconstructions SaoArgs::out, coded size, every picture of the batch: the three int64
+// sums of Q go to (uint8_t *)args.sse + out_off (8-byte aligned); `part` is scratch of ssim_part_words(w, h) int64 per picture
+int ssim_part_words(int w, int h);
+template <typename T> hipError_t launch_ssim(hipStream_t st, const SaoArgs<T> *d_args, int w, int h, int batch, long long *part, size_t out_off);
 constexpr int MAX_LANES = 16;
 struct StepParams { CostParams prm[MAX_LANES]; int p_tile_cols, p_tile_rows; };      // one P step's cost parameters per lane, passed by value; the P pictures' tile grid (intra second pass: availability)
 template <typename T> hipError_t launch_begin_p_step(hipStream_t st, IntraArgs<T> *ia, InterArgs<T> *ea, SaoArgs<T> *sa, const StepParams &p, int batch);

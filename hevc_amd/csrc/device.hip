@@ -304,6 +304,41 @@ template <typename T> hipError_t launch_pic_hash(hipStream_t st, const SaoArgs<T
     return hipGetLastError();
 }
 
+// SSIM of every picture of the batch, source against final reconstruction (kernels/ssim.h): region partials, then one workgroup per (component, picture)
+// adds them up: two launches, no atomics, nothing to zero in front
+template <typename T> __device__ __forceinline__ SsimPlane<T> ssim_plane_of(const SaoArgs<T> &a, int c)
+{
+    return SsimPlane<T>{a.src[c].p, a.out[c].p, a.src[c].stride, a.out[c].stride, c ? a.w >> 1 : a.w, c ? a.h >> 1 : a.h};
+}
+template <typename T> __global__ __launch_bounds__(NT) void k_ssim(const SaoArgs<T> *args, long long *part, int part_words)
+{
+    __shared__ SsimShared s;
+    GpuExec ex;
+    const SaoArgs<T> &a = args[blockIdx.y];
+    int reg = (int)blockIdx.x;
+    const int c = ssim_locate(ssim_regions(a.w, a.h), ssim_regions(a.w >> 1, a.h >> 1), reg);
+    if (c < 0) return;
+    ssim_region_program<T>(ex, s, ssim_plane_of(a, c), reg, part + (size_t)blockIdx.y * part_words + blockIdx.x);
+}
+template <typename T> __global__ __launch_bounds__(NT) void k_ssim_fold(const SaoArgs<T> *args, const long long *part, int part_words, size_t out_off)
+{
+    __shared__ SsimShared s;
+    GpuExec ex;
+    const SaoArgs<T> &a = args[blockIdx.y];
+    const int c = (int)blockIdx.x, nr_y = ssim_regions(a.w, a.h), nr_c = ssim_regions(a.w >> 1, a.h >> 1);
+    ssim_fold_program(ex, s, c ? nr_c : nr_y, part + (size_t)blockIdx.y * part_words + ssim_first_region(nr_y, nr_c, c), (long long *)((uint8_t *)a.sse + out_off) + c);
+}
+int ssim_part_words(int w, int h) { return ssim_regions(w, h) + 2 * ssim_regions(w >> 1, h >> 1); }
+template <typename T> hipError_t launch_ssim(hipStream_t st, const SaoArgs<T> *d_args, int w, int h, int batch, long long *part, size_t out_off)
+{
+    if (w < 16 || h < 16 || (w & 7) || (h & 7) || (out_off & 7)) return hipErrorInvalidValue;
+    const int nr = ssim_part_words(w, h);
+    hipLaunchKernelGGL(k_ssim<T>, dim3((unsigned)nr, (unsigned)batch), dim3(NT), 0, st, d_args, part, nr);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(k_ssim_fold<T>, dim3(3, (unsigned)batch), dim3(NT), 0, st, d_args, (const long long *)part, nr, out_off);
+    return hipGetLastError();
+}
+
 // Start of a P step, one tiny launch for every lane: the step's cost parameters (QP from the rate controller, by value in the kernel
 // arguments) go into the lane's argument blocks — the rest of the blocks was uploaded with the chunk — and the per-picture accumulators
 // (SSE per plane + the rate estimate behind them: four 64-bit words at SaoArgs::sse) are zeroed.
@@ -543,6 +578,7 @@ int gfx950_device_count()
     template hipError_t launch_frame_sse<T>(hipStream_t, const SaoArgs<T> *, int);                                       \
     template hipError_t launch_sse_fold<T>(hipStream_t, const SaoArgs<T> *, int, int);                                   \
     template hipError_t launch_pic_hash<T>(hipStream_t, const SaoArgs<T> *, int, int, int, int, uint32_t *, size_t);           \
+    template hipError_t launch_ssim<T>(hipStream_t, const SaoArgs<T> *, int, int, int, long long *, size_t);                   \
     template hipError_t launch_begin_p_step<T>(hipStream_t, IntraArgs<T> *, InterArgs<T> *, SaoArgs<T> *, const StepParams &, int); \
     template hipError_t launch_extend_margin<T>(hipStream_t, Plane<T>, int, int, int, int);                             \
     template hipError_t launch_scene_diff<T>(hipStream_t, const ScenePic<T> *, unsigned long long *, int, int, int);            \
@@ -809,6 +845,25 @@ template <typename T> int stage_picture_hash(const void *const *s, int w, int h,
     return MIHEVC_OK;
 }
 
+// the SSIM kernels alone: a = source (a plain plane), b = reconstruction (reference layout: in its border), as in a session
+template <typename T> int stage_ssim(const void *const *a, const void *const *b, int w, int h, int64_t *sum)
+{
+    Planes3<T> src, rec;
+    if (src.alloc(w, h, false) || rec.alloc(w, h, true)) return MIHEVC_ENOMEM;
+    if (int e = src.upload(a)) return e;
+    if (int e = rec.upload(b)) return e;
+    DevBuf dargs, dpart, dout;
+    CK(dargs.alloc(sizeof(SaoArgs<T>))); CK(dpart.alloc((size_t)ssim_part_words(w, h) * sizeof(long long))); CK(dout.alloc(3 * sizeof(long long)));
+    SaoArgs<T> sa{};
+    for (int i = 0; i < 3; i++) { sa.src[i] = src.ro[i]; sa.out[i] = rec.rw[i]; }
+    sa.w = w; sa.h = h; sa.sse = dout.as<unsigned long long>();
+    CK(hipMemcpy(dargs.p, &sa, sizeof sa, hipMemcpyHostToDevice));
+    CK(launch_ssim<T>(0, dargs.as<SaoArgs<T>>(), w, h, 1, dpart.as<long long>(), 0));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(sum, dout.p, 3 * sizeof(long long), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -952,6 +1007,17 @@ int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *
     }
     if (int e = select_device(device)) return e;
     return with_depth(bit_depth, [&](auto t) { return stage_picture_hash<decltype(t)>(pl, w, h, hash_type, (uint32_t *)out); });
+}
+
+int mihevc_k_ssim(int device, const void *ay, const void *au, const void *av, const void *by, const void *bu, const void *bv, int w, int h, int bit_depth,
+                  int64_t sum_q32[3], int64_t windows[3])
+{
+    if (!ay || !au || !av || !by || !bu || !bv || !sum_q32 || !windows || !geometry_ok(w, h) || (bit_depth != 8 && bit_depth != 10)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *a[3] = {ay, au, av}, *b[3] = {by, bu, bv};
+    for (int c = 0; c < 3; c++) windows[c] = (int64_t)ssim_windows_x(c ? w / 2 : w) * ssim_windows_y(c ? h / 2 : h);
+    if (bit_depth == 8) return stage_ssim<uint8_t>(a, b, w, h, sum_q32);
+    return stage_ssim<uint16_t>(a, b, w, h, sum_q32);
 }
 
 #ifdef MIHEVC_PHASE_PROF

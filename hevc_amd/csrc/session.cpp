@@ -148,10 +148,11 @@ struct Packet {
     std::string error;      // the host coder refused the picture's levels (sign data hiding parity): mihevc_receive_packet fails with MIHEVC_EINVAL here
 };
 
-// symbol block of one picture: [cu | coef Y | coef U | coef V | sao | sse[3] | rate estimate | hash[3]]; the device twin carries the per-CTU squared errors
-// behind it (SaoArgs::sse_ctu: never copied to the host, k_sse_fold turns them into sse[3]).  hash: the CRC / checksum words of cfg.pic_hash 2 / 3 (k_pic_hash_fold)
+// symbol block of one picture: [cu | coef Y | coef U | coef V | sao | sse[3] | rate estimate | hash[3] | ssim[3]]; the device twin carries the per-CTU squared errors
+// behind it (SaoArgs::sse_ctu: never copied to the host, k_sse_fold turns them into sse[3]).  hash: the CRC / checksum words of cfg.pic_hash 2 / 3 (k_pic_hash_fold);
+// ssim: the int64 sums of cfg.ssim (k_ssim_fold).  Both sit in the 256 bytes that begin at sse: the block is no larger for them
 struct SymLayout {
-    size_t cu, cu_bytes, cy, cu_, cv, sao, sse, est, hash, total, sse_ctu, dev_total;
+    size_t cu, cu_bytes, cy, cu_, cv, sao, sse, est, hash, ssim, total, sse_ctu, dev_total;
     SymLayout(int w, int h)
     {
         size_t n8 = (size_t)(w / 8) * (h / 8), ny = (size_t)w * h, nctu = (size_t)((w + 31) / 32) * ((h + 31) / 32);
@@ -166,7 +167,8 @@ struct SymLayout {
         sse = al(sao + nctu * sizeof(mihevc_sao_ctu));
         est = sse + 3 * sizeof(unsigned long long);
         hash = est + sizeof(unsigned long long);
-        total = al(hash + 3 * sizeof(uint32_t));
+        ssim = (hash + 3 * sizeof(uint32_t) + 7) & ~(size_t)7;
+        total = al(ssim + 3 * sizeof(long long));
         sse_ctu = total;
         dev_total = al(sse_ctu + nctu * 3 * sizeof(uint32_t));
     }
@@ -242,6 +244,8 @@ struct mihevc_session {
     hipEvent_t ev_pre = nullptr, ev_args = nullptr;  // the chunk's centres are ready (st_pre) / the IDR step's k_intra_plan is through (compute stream: the argument blocks are on the device too)
     CachedBuf scene;                                 // per chunk: picture pointers / pitches in, difference sums out (k_scene_diff)
     std::vector<FrameRec> frames;             // by output index
+    struct Quality { unsigned long long sse[3]; long long ssim[3]; bool known; };
+    std::vector<Quality> quality;             // by output index (display order), written when the picture's symbols have landed (publish_picture)
     std::atomic<long long> entropy_ns{0};
     // ---- one slice of a picture whose slices exchange rows (cfg.slice_halo; csrc/slice_group.h)
     std::shared_ptr<SliceGroup> group;
@@ -256,6 +260,11 @@ struct mihevc_session {
     // ---- decoded picture hash (cfg.pic_hash)
     uint32_t *hash_part = nullptr;            // 2 / 3: segment partials of k_pic_hash, MAX_LANES pictures (device)
     size_t hash_part_bytes = 0;
+    // ---- per-picture SSIM (cfg.ssim)
+    long long *ssim_part = nullptr;           // region partials of k_ssim, MAX_LANES pictures (device)
+    long long ssim_total[3] = {0, 0, 0};      // sum of Q over every window of every published picture: an integer, so mihevc_stats.ssim_* does not depend on the
+                                              // order the CABAC jobs finish in (2 M windows of a 4320p picture x 2^32 x 500 000 pictures fit 63 bits)
+    size_t ssim_part_bytes = 0;
 };
 
 namespace {
@@ -276,6 +285,7 @@ int fail(mihevc_session *s, std::string msg)
     } while (0)
 
 size_t esize(const mihevc_session *s) { return s->is16 ? 2 : 1; }
+long long ssim_window_count(const mihevc_session *s, int c) { return (long long)ssim_windows_x(c ? s->w / 2 : s->w) * ssim_windows_y(c ? s->h / 2 : s->h); }
 size_t md5_pic_bytes(const mihevc_session *s) { return (size_t)s->w * s->h * 3 / 2 * esize(s); }
 
 // padded 0: a plain picture; 1: a reference picture with its PAD border all round; 2: a work picture with kSeamRows rows above and below (the rows the
@@ -415,6 +425,16 @@ void publish_picture(PictureJob *j)
     {
         std::lock_guard<std::mutex> l(s->m);
         s->stats.sse_y += (double)sse[0]; s->stats.sse_u += (double)sse[1]; s->stats.sse_v += (double)sse[2];
+        if ((size_t)index < s->quality.size()) {
+            auto &q = s->quality[(size_t)index];
+            const long long *sq = (const long long *)(b + sl.ssim);
+            for (int c = 0; c < 3; c++) {
+                q.sse[c] = sse[c];
+                q.ssim[c] = s->cfg.ssim ? sq[c] : 0;
+                s->ssim_total[c] += q.ssim[c];
+            }
+            q.known = true;
+        }
         s->stats.bytes_out += (int64_t)pk.data.size();
         if ((size_t)index < s->frames.size()) {
             auto &fr = s->frames[(size_t)index];
@@ -1124,6 +1144,11 @@ template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, 
     // decoded picture hash of the final pictures (coded area only: the border is the next step's pad), in front of the symbol copies that carry it.
     // The compute stream reuses these picture buffers two steps later, behind ev_copy of this step (rate_feedback)
     if (s->cfg.pic_hash >= 2) HIPCK(s, launch_pic_hash<T>(s->st_copy, dv.sao, s->w, s->h, B, s->cfg.pic_hash - 1, s->hash_part, sl.hash - sl.sse));
+    // SSIM of the same pictures against their sources.  The reconstructions are safe here as for the hash.  The sources: the chunk's source pictures are written by
+    // nothing while the chunk runs (uploads of the NEXT chunk's frames go to other buffers: a chunk's buffers return to the free list only at its end, behind
+    // hipStreamSynchronize(st_copy)), and planes borrowed from the caller (mihevc_send_frame_device) stay valid and unmodified until the picture's packet is out,
+    // which is behind ev_copy of this step
+    if (s->cfg.ssim) HIPCK(s, launch_ssim<T>(s->st_copy, dv.sao, s->w, s->h, B, s->ssim_part, sl.ssim - sl.sse));
     for (int g = 0; s->cfg.pic_hash == 1 && g < B; g++) {      // MD5: the picture to pinned memory for the CABAC job (no wait here)
         uint8_t *dst = s->lane[g].md5_host[slot];
         const size_t es = esize(s);
@@ -1240,7 +1265,7 @@ template <typename T> int encode_chunk(mihevc_session *s)
     c.bf = s->cfg.bframes > 0;
     if (s->cfg.bframes < 0) { if (int e = probe_bframes<T>(s, n, c.bf)) return e; }
     if (int e = alloc_chunk<T>(s, c)) return e;
-    { std::lock_guard<std::mutex> l(s->m); s->frames.resize((size_t)s->frames_in); }
+    { std::lock_guard<std::mutex> l(s->m); s->frames.resize((size_t)s->frames_in); s->quality.resize((size_t)s->frames_in); }
     // every step's argument blocks, uploaded once
     for (int t = 0; t < c.steps; t++)
         for (int g = 0; g < c.gl.batch[(size_t)t]; g++) build_step_args<T>(s, c, t, g);
@@ -1319,6 +1344,7 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     if (cfg->bit_depth != 8 && cfg->bit_depth != 10) return MIHEVC_EINVAL;
     if (cfg->sign_hide != 0 && cfg->sign_hide != 1) return MIHEVC_EINVAL;
     if (cfg->pic_hash < 0 || cfg->pic_hash > 3 || (cfg->pic_hash && cfg->slice_count > 1)) return MIHEVC_EINVAL;      // hashes of sliced pictures: not yet
+    if ((cfg->ssim != 0 && cfg->ssim != 1) || (cfg->ssim && cfg->slice_count > 1)) return MIHEVC_EINVAL;      // windows cross the seams; a band sees only its rows
     if (cfg->fps_num <= 0 || cfg->fps_den <= 0 || cfg->keyint < 1 || cfg->keyint > 240) return MIHEVC_EINVAL;
     if (cfg->bframes < -1 || cfg->bframes > 1 || (cfg->bframes && cfg->slice_count > 1)) return MIHEVC_EINVAL;      // B pictures: whole pictures only (for now)
     if (cfg->slice_count > 1) {        // one slice of a picture: a band of whole CTU rows (the last band takes the picture's remainder)
@@ -1366,6 +1392,10 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     if (ok && cfg->pic_hash >= 2) {
         s->hash_part_bytes = (size_t)MAX_LANES * pic_hash_part_words(s->w, s->h, (int)esize(s)) * sizeof(uint32_t);
         ok = BufferCache::get().alloc(s->device, s->hash_part_bytes, false, (void **)&s->hash_part) == hipSuccess;
+    }
+    if (ok && cfg->ssim) {
+        s->ssim_part_bytes = (size_t)MAX_LANES * ssim_part_words(s->w, s->h) * sizeof(long long);
+        ok = BufferCache::get().alloc(s->device, s->ssim_part_bytes, false, (void **)&s->ssim_part) == hipSuccess;
     }
     if (!ok) { mihevc_close(s); return MIHEVC_EDEVICE; }      // gives back what was acquired (event handles of the slots never reached stay null)
     if (cfg->slice_count > 1 && cfg->slice_halo) {
@@ -1524,6 +1554,8 @@ int mihevc_get_stats(const mihevc_session *s, mihevc_stats *out)
     std::lock_guard<std::mutex> l(const_cast<mihevc_session *>(s)->m);
     *out = s->stats;
     out->entropy_ms = (double)s->entropy_ns.load() / 1e6;
+    double *ssim[3] = {&out->ssim_y, &out->ssim_u, &out->ssim_v};
+    for (int c = 0; c < 3; c++) *ssim[c] = s->cfg.ssim ? (double)s->ssim_total[c] / ((double)ssim_window_count(s, c) * 4294967296.0) : 0.0;
     return MIHEVC_OK;
 }
 
@@ -1555,6 +1587,22 @@ int mihevc_get_frame_info(mihevc_session *s, int64_t index, int *qp, int *slice_
     if (qp) *qp = fr.qp;
     if (slice_type) *slice_type = fr.type;
     if (bits) *bits = fr.bits;
+    return MIHEVC_OK;
+}
+
+int mihevc_get_frame_quality(mihevc_session *s, int64_t index, uint64_t sse[3], int64_t ssim_q32[3], int64_t ssim_windows[3])
+{
+    if (!s) return MIHEVC_EINVAL;
+    if ((ssim_q32 || ssim_windows) && !s->cfg.ssim) return MIHEVC_ESTATE;
+    std::lock_guard<std::mutex> l(s->m);
+    if (index < 0 || (size_t)index >= s->quality.size()) return MIHEVC_ESTATE;
+    const auto &q = s->quality[(size_t)index];
+    if (!q.known) return MIHEVC_EAGAIN;
+    for (int c = 0; c < 3; c++) {
+        if (sse) sse[c] = q.sse[c];
+        if (ssim_q32) ssim_q32[c] = q.ssim[c];
+        if (ssim_windows) ssim_windows[c] = ssim_window_count(s, c);
+    }
     return MIHEVC_OK;
 }
 
@@ -1591,6 +1639,7 @@ void mihevc_close(mihevc_session *s)
         for (int k = 0; k < s->ring; k++) bc.release(s->device, md5_pic_bytes(s), true, L.md5_host[k]);
     }
     bc.release(s->device, s->hash_part_bytes, false, s->hash_part);
+    bc.release(s->device, s->ssim_part_bytes, false, s->ssim_part);
     for (CachedBuf *b : {&s->args, &s->scene, &s->low, &s->jobs, &s->probe}) { bc.release(s->device, b->cap, false, b->d); bc.release(s->device, b->cap, true, b->h); }
     for (int i = 0; i < kRing; i++) { if (s->ev_compute[i]) (void)hipEventDestroy(s->ev_compute[i]); if (s->ev_copy[i]) (void)hipEventDestroy(s->ev_copy[i]); }
     for (auto e : s->ev_pool) (void)hipEventDestroy(e);

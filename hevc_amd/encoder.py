@@ -54,10 +54,11 @@ def lanes_for(total_frames: int, keyint: int) -> int:
 
 
 def config_for(info: VideoInfo, crf: int, vbv_maxrate: int, vbv_bufsize: int, gop: int, level: str, tier: str,
-               master_display: str = "", max_cll: str = "", sign_hide: int = 0, pic_hash: int = 0) -> _lib.Config:
+               master_display: str = "", max_cll: str = "", sign_hide: int = 0, pic_hash: int = 0, ssim: int = 0) -> _lib.Config:
     """Map the reference's libx265 operating point (build_ffmpeg_params CPU branch) onto a mihevc_config.  sign_hide=1: sign data
     hiding (x265 signhide, on in its presets; off here by default until the measured gain decides).  pic_hash: decoded picture hash
-    SEI in every access unit, x265 hash= numbering (0 off, 1 MD5, 2 CRC, 3 checksum)."""
+    SEI in every access unit, x265 hash= numbering (0 off, 1 MD5, 2 CRC, 3 checksum).  ssim=1: per-picture SSIM on the device (x265 ssim),
+    read with Encoder.frame_quality() and stats().ssim_*; no bit of the stream depends on it."""
     from .utils import parse_master_display, parse_max_cll
     cfg = _lib.default_config()
     cfg.width, cfg.height = int(info.width), int(info.height)
@@ -74,6 +75,7 @@ def config_for(info: VideoInfo, crf: int, vbv_maxrate: int, vbv_bufsize: int, go
     cfg.gops_in_flight = lanes_for(int(getattr(info, 'nb_frames', 0) or 0), int(gop))
     cfg.sign_hide = int(sign_hide)
     cfg.pic_hash = int(pic_hash)
+    cfg.ssim = int(ssim)
     if hdr:   # the HDR10 set of core/utils.py:58-69
         cfg.colour_primaries, cfg.transfer, cfg.matrix = 9, 16, 9
         cfg.chroma_loc, cfg.aud, cfg.repeat_headers, cfg.hdr10, cfg.hrd = 0, 1, 1, 1, 1       # ... hrd=1:aud=1:chromaloc=0:repeat-headers=1
@@ -225,6 +227,21 @@ class Encoder:
         qp, st, bits = C.c_int(), C.c_int(), C.c_int64()
         self._check(self._lib.mihevc_get_frame_info(self._s, index, C.byref(qp), C.byref(st), C.byref(bits)), "get_frame_info")
         return qp.value, st.value, bits.value
+
+    def frame_quality(self, index: int) -> dict:
+        """Quality of output picture `index` (display order) over the coded size, per plane (Y, Cb, Cr): {"sse": squared error of the final reconstruction
+        against the source, "psnr": dB (99.0 at zero error), "ssim": mean SSIM of the picture's 8x8 windows, or None when the session runs without cfg.ssim,
+        "ssim_q32" / "ssim_windows": the exact integers behind it (None likewise)}"""
+        sse, q32, win = (C.c_uint64 * 3)(), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        on = bool(self.cfg.ssim)
+        self._check(self._lib.mihevc_get_frame_quality(self._s, index, sse, q32 if on else None, win if on else None), "get_frame_quality")
+        w, h = self.coded_size()
+        peak = float((1 << self.cfg.bit_depth) - 1)
+        n = (w * h, w * h // 4, w * h // 4)
+        return {"sse": [int(x) for x in sse],
+                "psnr": [99.0 if s == 0 else float(10 * np.log10(peak * peak * k / s)) for s, k in zip(sse, n)],
+                "ssim": [q / (k * 4294967296.0) for q, k in zip(q32, win)] if on else None,
+                "ssim_q32": [int(x) for x in q32] if on else None, "ssim_windows": [int(x) for x in win] if on else None}
 
     def psnr_y(self) -> float:
         st = self.stats()

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MIHEVC_ABI_VERSION 5
+#define MIHEVC_ABI_VERSION 6
 
 typedef enum {
     MIHEVC_OK = 0,
@@ -130,6 +130,15 @@ typedef struct mihevc_config {
                                        * can check the picture it decodes against.  0 (default): off; 1 MD5 (the final picture is copied to pinned host memory and hashed by
                                        * the CABAC job: a verification mode, host-bound); 2 CRC; 3 checksum (both on the device, on the copy stream beside the next step).
                                        * Any other value, or a value != 0 with slice_count > 1: MIHEVC_EINVAL at open and in mihevc_write_parameter_sets */
+    /* ---- ABI 6 ---- */
+    int32_t ssim;                     /* per-picture SSIM on the device (x265 ssim): 1 = every picture's source is compared with its final reconstruction (after deblocking
+                                       * and SAO: what a decoder outputs) over the CODED size, per colour component, by two small launches per step on the copy stream; the
+                                       * results come with mihevc_get_frame_quality and mihevc_stats.ssim_*.  The metric: SSIM on 8x8 windows at stride 4 with biased
+                                       * variances, C1 = (0.01 peak)^2, C2 = (0.03 peak)^2, in integers up to one double division per window, each window's value rounded
+                                       * to a multiple of 2^-32 and summed as int64 (csrc/kernels/ssim.h has it step by step): bit-exact and independent of scheduling.  It
+                                       * is the textbook form, not digit for digit the figure libx265 prints.  No bit of the stream and no decision depends on it.
+                                       * 0 (default): off, nothing is launched or allocated.  Any other value, or 1 with slice_count > 1 (windows cross the seams): MIHEVC_EINVAL
+                                       * at open and in mihevc_write_parameter_sets */
 } mihevc_config;
 
 typedef struct mihevc_session mihevc_session;
@@ -148,6 +157,9 @@ typedef struct mihevc_stats {
     double  stage_ms[8];
     int64_t stage_launches[8];
     int64_t stage_pictures[8];
+    /* ---- ABI 6 ---- */
+    double  ssim_y, ssim_u, ssim_v;   /* cfg.ssim: sum of the per-picture SSIM over the pictures counted in sse_* (mean = / frames_out once every packet is out), formed from the exact
+                                       * integer sum of mihevc_get_frame_quality's ssim_q32 over those pictures: / (ssim_windows * 2^32); 0 when off */
 } mihevc_stats;
 
 int  mihevc_abi_version(void);
@@ -199,6 +211,12 @@ int  mihevc_get_recon(mihevc_session *s, int64_t index, uint16_t *y, uint16_t *u
 int  mihevc_coded_size(const mihevc_session *s, int *w, int *h);
 /* QP, slice type (2 = IDR, 1 = P) and coded size in bits (-1 while CABAC is still running) of output picture `index` */
 int  mihevc_get_frame_info(mihevc_session *s, int64_t index, int *qp, int *slice_type, int64_t *bits);
+/* Quality of output picture `index` (display order, as mihevc_get_frame_info) over the coded size, per colour component (Y, Cb, Cr): sse = squared error of the
+ * final reconstruction against the source (PSNR = 10 log10(peak^2 samples / sse)); with cfg.ssim, ssim_q32 = the int64 sum over the picture's windows of each
+ * window's SSIM in units of 2^-32 and ssim_windows = their number ((W/4 - 1)(H/4 - 1) of a W x H plane): SSIM = ssim_q32 / (ssim_windows * 2^32).  Any of the three
+ * may be NULL.  MIHEVC_ESTATE: no such picture, or ssim_* asked of a session opened with cfg.ssim = 0; MIHEVC_EAGAIN: the picture's results have not reached the
+ * host yet (they come with its packet) */
+int  mihevc_get_frame_quality(mihevc_session *s, int64_t index, uint64_t sse[3], int64_t ssim_q32[3], int64_t ssim_windows[3]);
 const char *mihevc_strerror(int err);
 /* s = NULL: what the calling thread's last mihevc_encode_picture_host refused ("null session" when nothing) */
 const char *mihevc_last_error(const mihevc_session *s);
@@ -290,6 +308,11 @@ int mihevc_k_loop_filter(int device, const void *src_y, const void *src_u, const
  * multiples of 8): hash_type 0 MD5 (on the host; no device needed), 1 CRC, 2 checksum (the session's kernels).  out: hash_type 0 three 16-byte digests
  * (Y, Cb, Cr), else three uint32_t (a CRC in the low 16 bits) */
 int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *v, int width, int height, int bit_depth, int hash_type, void *out);
+
+/* SSIM (mihevc_config.ssim) of one picture pair, host planes as above: a = source, b = reconstruction.  The session's kernels.  sum_q32[c] / (windows[c] * 2^32) is
+ * the SSIM of component c */
+int mihevc_k_ssim(int device, const void *a_y, const void *a_u, const void *a_v, const void *b_y, const void *b_u, const void *b_v,
+                  int width, int height, int bit_depth, int64_t sum_q32[3], int64_t windows[3]);
 
 /* ---- host-only stages (no device needed): bitstream ---- */
 /* VPS+SPS+PPS (+SEI when hdr10) as Annex-B into buf; returns size or negative error */

@@ -3,8 +3,10 @@
 
 The quality half of BASELINE.json's metric asks for PSNR-Y parity with libx265 at matched bitrate (reference operating point:
 core/transcoder.py:398-411, `preset=slow`).  libx265 does not exist on this pool, so the instrument that CAN be kept is a reproducible
-RD curve of this encoder: 4 fixed QPs x {motion, stress, bars} -> (kb/s, PSNR-Y/U/V) and the BD-rate of any change against a stored
-run.  Every coding tool added from round 3 on states its BD-rate from this script (JSON under profiles/).
+RD curve of this encoder: 4 fixed QPs x {motion, stress, bars} -> (kb/s, PSNR-Y/U/V, SSIM-Y) and the BD-rate of any change against a stored
+run, by PSNR and by SSIM (the session's own per-picture SSIM, cfg.ssim: the mean over the pictures, and ssim_y_db = -10 log10(1 - ssim_y), the scale
+on which SSIM curves are near-linear in log-rate).  Stored runs from before the SSIM column compare by PSNR only.  Every coding tool added from round 3 on states its
+BD-rate from this script (JSON under profiles/).
 
     python tools/rd_curve.py --out profiles/r03_rd_base.json                       # needs an MI355X (no CPU fallback)
     python tools/rd_curve.py --out profiles/r03_rd_x.json --against profiles/r03_rd_base.json --set bframes=1
@@ -68,9 +70,21 @@ def compare(a, b):
         pb = [(p["kbps"], p["psnr_y"]) for p in b["clips"][clip]["points"]]
         out[clip] = {"bd_rate_pct": None if bd_rate(pa, pb) is None else round(bd_rate(pa, pb), 2),
                      "bd_psnr_db": None if bd_psnr(pa, pb) is None else round(bd_psnr(pa, pb), 3)}
-    vals = [v["bd_rate_pct"] for v in out.values() if v["bd_rate_pct"] is not None]
+        # the same integral over (kb/s, SSIM in dB); None where either run has no SSIM column
+        sa, sb = ([(p["kbps"], p["ssim_y_db"]) for p in x["clips"][clip]["points"] if p.get("ssim_y_db") is not None] for x in (a, b))
+        full = len(sa) == len(pa) and len(sb) == len(pb)
+        out[clip]["bd_rate_ssim_pct"] = None if not full or bd_rate(sa, sb) is None else round(bd_rate(sa, sb), 2)
+    clips = [v for v in out.values()]
+    vals = [v["bd_rate_pct"] for v in clips if v["bd_rate_pct"] is not None]
     out["mean_bd_rate_pct"] = round(float(np.mean(vals)), 2) if vals else None
+    vals = [v["bd_rate_ssim_pct"] for v in clips if v["bd_rate_ssim_pct"] is not None]
+    out["mean_bd_rate_ssim_pct"] = round(float(np.mean(vals)), 2) if vals and len(vals) == len(clips) else None
     return out
+
+
+def ssim_db(ssim):
+    """-10 log10(1 - SSIM); 99.0 at SSIM = 1, as PSNR at zero error"""
+    return 99.0 if ssim >= 1.0 else float(-10 * np.log10(1.0 - ssim))
 
 
 def run(args):
@@ -92,6 +106,7 @@ def run(args):
             cfg.width, cfg.height, cfg.bit_depth, cfg.qp, cfg.keyint, cfg.min_keyint = W, H, bd, qp, args.keyint, max(2, args.keyint // 2)
             cfg.level_idc = 120 if W * H <= 1920 * 1088 else 150 if W * H <= 3840 * 2176 else 180
             cfg.gops_in_flight = max(1, min(8, -(-N // args.keyint)))
+            cfg.ssim = 1                                   # decision-neutral: the stream is the one ssim = 0 gives (--set ssim=0 leaves the column out)
             for kv in args.set:
                 k, v = kv.split("=")
                 setattr(cfg, k, int(v))
@@ -110,6 +125,9 @@ def run(args):
             ps = [99.0 if s <= 0 else 10 * np.log10(peak * peak / (s / d)) for s, d in ((st.sse_y, npx), (st.sse_u, npx / 4), (st.sse_v, npx / 4))]
             pts.append({"qp": qp, "kbps": round(nbytes * 8 / (N / 30.0) / 1e3, 2), "psnr_y": round(float(ps[0]), 4), "psnr_u": round(float(ps[1]), 4),
                         "psnr_v": round(float(ps[2]), 4), "fps_host_buffers": round(N / dt, 1)})
+            if cfg.ssim:              # mean over the pictures of the per-picture SSIM of luma, as x265 reports it
+                pts[-1]["ssim_y"] = round(st.ssim_y / N, 6)
+                pts[-1]["ssim_y_db"] = round(ssim_db(st.ssim_y / N), 4)
             if cfg.bframes < 0:       # the adaptive decision of the last chunk: cost per CTU one / two pictures back, B pictures chosen
                 pts[-1]["b_probe"] = [int(st.reserved[0]), int(st.reserved[1]), int(st.reserved[2])]
             print(f"{name:7s} qp {qp}: {pts[-1]['kbps']:10.1f} kb/s  {pts[-1]['psnr_y']:.3f} dB  ({pts[-1]['fps_host_buffers']:.0f} fps) {pts[-1].get('b_probe', '')}", file=sys.stderr)
