@@ -13,6 +13,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -181,6 +182,11 @@ struct CachedBuf {
     size_t cap = 0;
 };
 
+constexpr int kGroups = 2;        // lane groups of a chunk's P/B steps: two launch sequences on two streams (encode_chunk)
+// sessions this process has open on a device.  A chunk runs as lane groups only while its session is the device's only one: a second session's launches already
+// fill the first one's launch tails, and with the process's four hardware queues two sessions of five busy streams each had their uploads and copies queue
+// behind kernels (bench.py's two-session leg from pinned host buffers: -5 %).  The stream does not depend on the choice.
+std::atomic<int> &open_sessions(int device) { static std::atomic<int> n[64]; return n[device & 63]; }
 constexpr int kSeamRows = 8;      // rows of the pre-deblock reconstruction exchanged either side of a seam (deblocking reads 4 and writes 3; one 8x8 grid row)
 
 }  // namespace
@@ -196,7 +202,8 @@ struct mihevc_session {
     std::atomic<bool> failed{false};     // sticky (fail()); mihevc_abort sets it from another thread
     int fail_code = MIHEVC_EDEVICE;      // what calls return once `failed` is set: MIHEVC_EINVAL when the host coder refused a picture
     std::string err;                     // written under `m` (mihevc_abort may run on another thread)
-    hipStream_t st_compute = nullptr, st_copy = nullptr, st_pre = nullptr;      // st_pre: the chunk's pre-search, beside the IDR step
+    hipStream_t st_compute = nullptr, st_copy = nullptr, st_pre = nullptr;      // st_pre: the chunk's pre-search, beside the IDR step; then the P/B steps of lane group 1
+    int lane_groups = kGroups;        // launch sequences the P/B steps of a chunk run as (MIHEVC_LANE_GROUPS, read at mihevc_open: 1 = one sequence on the compute stream)
     // uploads of host frames (mihevc_send_frame / _async) go through st_pre (idle outside a chunk's IDR step; a FOURTH stream per session made two of them share a
     // hardware queue: the copy stream's SSE pass and symbol copies then queued behind the compute stream's kernels, +10 ms of bubbles per 300-frame clip); the
     // chunk's first launch waits for ev_up
@@ -219,7 +226,8 @@ struct mihevc_session {
     };
     std::vector<Lane> lane;
     CachedBuf args;                   // argument blocks of a whole chunk (device + pinned staging)
-    hipEvent_t ev_compute[kRing] = {}, ev_copy[kRing] = {};
+    hipEvent_t ev_compute[kGroups][kRing] = {}, ev_copy[kGroups][kRing] = {};      // by (lane group, ring slot); step 0 (all lanes, one launch) uses group 0's slot 0
+    hipEvent_t ev_join = nullptr;     // behind the last step of lane group 1 (st_pre): the compute stream waits for it at the end of the chunk
     std::vector<hipEvent_t> ev_pool;   // profile_stages: start/stop pairs
     struct Mark { int stage, pictures; size_t ev; };
     std::vector<Mark> marks;
@@ -227,7 +235,7 @@ struct mihevc_session {
     ThreadPool *pool = nullptr;
     std::mutex m;
     std::condition_variable cv;
-    int jobs_open[kRing] = {0};
+    int jobs_open[kGroups][kRing] = {{0}};
     int ring = 8;                 // slots in use (<= kRing)
     int host_threads = 2;         // CABAC worker threads this session asked the process-wide pool for
     std::map<int64_t, Packet> packets;     // by output index
@@ -355,11 +363,11 @@ template <typename T> struct StepLayout {
 };
 template <typename T> struct StepView {
     IntraArgs<T> *intra; InterArgs<T> *inter; DeblockArgs<T> *dbk_v, *dbk_h; SaoArgs<T> *sao;
-    StepView(uint8_t *base, const StepLayout<T> &l, int t)
+    StepView(uint8_t *base, const StepLayout<T> &l, int t, int first = 0)      // first: entry the view begins at (a lane group's part of the arrays)
     {
         uint8_t *b = base + (size_t)t * l.total;
-        intra = (IntraArgs<T> *)(b + l.intra); inter = (InterArgs<T> *)(b + l.inter);
-        dbk_v = (DeblockArgs<T> *)(b + l.dbk_v); dbk_h = (DeblockArgs<T> *)(b + l.dbk_h); sao = (SaoArgs<T> *)(b + l.sao);
+        intra = (IntraArgs<T> *)(b + l.intra) + first; inter = (InterArgs<T> *)(b + l.inter) + first;
+        dbk_v = (DeblockArgs<T> *)(b + l.dbk_v) + first; dbk_h = (DeblockArgs<T> *)(b + l.dbk_h) + first; sao = (SaoArgs<T> *)(b + l.sao) + first;
     }
 };
 
@@ -370,7 +378,7 @@ template <typename T> Plane<const T> mkc(void *p, int stride) { return Plane<con
 // puts the access unit together and publishes the packet.  One part = the whole picture in one job, as before round 3.
 struct PictureJob {
     mihevc_session *s;
-    int slot, lane_i, slice_type, poc, qp, prev_gop_len, parts, n_tiles, dec_pos;      // poc: place in the GOP in display order, dec_pos: in decoding order
+    int grp, slot, lane_i, slice_type, poc, qp, prev_gop_len, parts, n_tiles, dec_pos;      // poc: place in the GOP in display order, dec_pos: in decoding order
     int64_t index, pts, dts, dec_index;      // index: display order (frame records, reconstructions); dec_index: decoding order (packets)
     bool first_of_stream, reorder;      // reorder: the stream announces B pictures (dts one frame early, output delay in the picture timing SEI)
     PictureSyms pic;
@@ -420,7 +428,7 @@ void publish_picture(PictureJob *j)
     pk.ready = true;
     auto t1 = std::chrono::steady_clock::now();
     s->entropy_ns += j->ns.load() + std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-    const int slot = j->slot;
+    const int grp = j->grp, slot = j->slot;
     const int64_t index = j->index;
     {
         std::lock_guard<std::mutex> l(s->m);
@@ -449,7 +457,7 @@ void publish_picture(PictureJob *j)
         s->packets[j->dec_index] = std::move(pk);
         s->frames_done++;
         delete j;
-        s->jobs_open[slot]--;
+        s->jobs_open[grp][slot]--;
         s->cv.notify_all();      // under the lock: mihevc_close may delete the session as soon as its last job has let go of the mutex
     }
 }
@@ -607,6 +615,14 @@ struct Halo {
     const RowCopy *jobs(int t, size_t part) const { return (const RowCopy *)(dj + (size_t)t * jl.total + part); }
 };
 
+// the lanes one launch sequence covers at a step: their entries in the step's argument arrays are [base, base + n), `lanes` in that order.  Step 0 is one part
+// of all lanes in lane order (base 0; Chunk::at places them)
+struct Part {
+    int grp = 0, base = 0, n = 0;
+    std::vector<int> lanes;
+    hipStream_t st = nullptr;
+};
+
 template <typename T> struct Chunk {
     const int n, gops, steps, ring;
     const int64_t first_index;                    // output index of pending[0]
@@ -617,6 +633,27 @@ template <typename T> struct Chunk {
     size_t need = 0, low_pic = 0;
     uint8_t *ha = nullptr, *da = nullptr, *low = nullptr; int16_t *cen = nullptr;      // argument blocks (host staging, device), pre-search pictures and centres
     Halo halo;
+    // Lane groups.  From step 1 on the lanes of a step run as `groups` independent launch sequences, each on its own stream: group 0 the even lanes on the
+    // compute stream, group 1 the odd lanes on st_pre.  Lanes are sorted longest GOP first and the active ones are a prefix, so alternating keeps the groups
+    // within one lane of each other as GOPs run out.  Every step's argument arrays hold group 0's lanes first, then group 1's: a group's launch is
+    // (array + group_base, group_size).
+    // The stream does not depend on `groups`: across lanes nothing is shared from step 1 on (pictures, tables, symbol blocks and frame records are per lane),
+    // and RateControl::decide_p reads only its own lane's records at fixed lags: CABAC sizes of steps <= t - (ring - 1), estimates of steps <= t - 2.  rho_pi,
+    // ratio_*, beta_bp and the budgets are constants of the chunk once step 0 is over.  Each group keeps those lags in its own steps (the wait for the
+    // slot's CABAC jobs, the wait for the symbol copy of step t - 2), so every lane sees the same inputs whichever group it is in.
+    int groups = 1;
+    int group_size(int grp, int t) const { const int B = gl.batch[(size_t)t]; return groups == 1 ? (grp ? 0 : B) : (B + 1 - grp) / 2; }
+    int group_base(int grp, int t) const { return grp ? group_size(0, t) : 0; }
+    int at(int t, int g) const { return groups == 1 ? g : group_base(g & 1, t) + g / 2; }      // lane g's entry in step t's argument arrays
+    Part part(const mihevc_session *s, int grp, int t) const
+    {
+        Part p;
+        p.grp = grp; p.st = grp ? s->st_pre : s->st_compute;
+        if (t == 0) { p.n = gl.batch[0]; for (int g = 0; g < p.n; g++) p.lanes.push_back(g); return p; }
+        p.base = group_base(grp, t); p.n = group_size(grp, t);
+        for (int k = 0; k < p.n; k++) p.lanes.push_back(groups == 1 ? k : 2 * k + grp);
+        return p;
+    }
     Chunk(const mihevc_session *s, int n_, GopLayout gl_)
         : n(n_), gops((int)gl_.glen.size()), steps(gl_.glen[0]), ring(s->ring), first_index(s->frames_in - n_), gl(std::move(gl_)), sl(s->w, s->h), lay(gops),
           flat_off((size_t)(steps + 1) * lay.total) {}
@@ -837,7 +874,8 @@ template <typename T> void build_step_args(mihevc_session *s, const Chunk<T> &c,
     mihevc_session::Lane &L = s->lane[g];
     mihevc_session::Src &src = s->pending[fi];
     StepView<T> hv(c.ha, c.lay, t);
-    struct { IntraArgs<T> &intra; InterArgs<T> &inter; DeblockArgs<T> &dbk_v, &dbk_h; SaoArgs<T> &sao; } A{hv.intra[g], hv.inter[g], hv.dbk_v[g], hv.dbk_h[g], hv.sao[g]};
+    const int a = c.at(t, g);
+    struct { IntraArgs<T> &intra; InterArgs<T> &inter; DeblockArgs<T> &dbk_v, &dbk_h; SaoArgs<T> &sao; } A{hv.intra[a], hv.inter[a], hv.dbk_v[a], hv.dbk_h[a], hv.sao[a]};
     uint8_t *sym = L.sym_dev[c.slot_of(t)];
     const CostParams P = prm_for(s, t == 0 ? s->qp_i : s->qp_p);      // provisional; the controller patches it per step
     for (int i = 0; i < 3; i++) {
@@ -911,8 +949,9 @@ template <typename T> void build_step_args(mihevc_session *s, const Chunk<T> &c,
 template <typename T> void patch_qp(mihevc_session *s, const Chunk<T> &c, int t, int g, int qp)
 {
     StepView<T> hv(c.ha, c.lay, t);
-    hv.intra[g].prm = hv.inter[g].prm = hv.sao[g].prm = prm_for(s, qp);
-    if (t > 0) { hv.intra[g].prm.tile_cols = s->ptiles.cols; hv.intra[g].prm.tile_rows = s->ptiles.rows; }
+    const int a = c.at(t, g);
+    hv.intra[a].prm = hv.inter[a].prm = hv.sao[a].prm = prm_for(s, qp);
+    if (t > 0) { hv.intra[a].prm.tile_cols = s->ptiles.cols; hv.intra[a].prm.tile_rows = s->ptiles.rows; }
     std::lock_guard<std::mutex> l(s->m);
     auto &fr = s->frames[c.fidx(g, t)];
     fr.qp = qp; fr.type = type_of_step(c.bf, t);
@@ -957,21 +996,21 @@ int lane_estimates(mihevc_session *s, const SymLayout &sl, int slot, const std::
 }
 std::vector<int> first_lanes(int n) { std::vector<int> v((size_t)n); std::iota(v.begin(), v.end(), 0); return v; }
 
-int mark(mihevc_session *s, int stage, int pictures, bool begin)       // bracket a stage with events when profiling
+int mark(mihevc_session *s, hipStream_t st, int stage, int pictures, bool begin)       // bracket a stage with events when profiling, on the stream its launch goes to
 {
     if (!s->cfg.profile_stages || (s->cfg.profile_stages == 2 && stage != 2)) return 0;      // 2: the dominant stage (inter_ctu) only
     size_t need_ev = s->marks.size() * 2 + 2;
     while (s->ev_pool.size() < need_ev) { hipEvent_t e; HIPCK(s, hipEventCreate(&e)); s->ev_pool.push_back(e); }
-    if (begin) { s->marks.push_back({stage, pictures, s->marks.size() * 2}); HIPCK(s, hipEventRecord(s->ev_pool[s->marks.back().ev], s->st_compute)); }
-    else HIPCK(s, hipEventRecord(s->ev_pool[s->marks.back().ev + 1], s->st_compute));
+    if (begin) { s->marks.push_back({stage, pictures, s->marks.size() * 2}); HIPCK(s, hipEventRecord(s->ev_pool[s->marks.back().ev], st)); }
+    else HIPCK(s, hipEventRecord(s->ev_pool[s->marks.back().ev + 1], st));
     return 0;
 }
-#define STAGE(idx, pics, call) do { if (int e_ = mark(s, idx, pics, true)) return e_; HIPCK(s, call); if (int e_ = mark(s, idx, pics, false)) return e_; } while (0)
+#define STAGE(st, idx, pics, call) do { if (int e_ = mark(s, st, idx, pics, true)) return e_; HIPCK(s, call); if (int e_ = mark(s, st, idx, pics, false)) return e_; } while (0)
 
 // rate feedback in front of step t (rate control only).  Slices with one rate plan: the CABAC sizes of step t - p_slots, summed over the slices.  Then, with
 // a fixed lag of two steps, the estimates of step t - 2: wait for its symbol copy (step t - 1 is already queued behind it, so the device never idles).  A fixed
 // lag makes the QP sequence reproducible.
-template <typename T> int rate_feedback(mihevc_session *s, const Chunk<T> &c, int t)
+template <typename T> int rate_feedback(mihevc_session *s, const Chunk<T> &c, const Part &p, int t)
 {
     const int p_slots = s->ring - 1;
     if (c.halo.on && s->rc.rc_on && t - p_slots >= 1) {
@@ -980,15 +1019,17 @@ template <typename T> int rate_feedback(mihevc_session *s, const Chunk<T> &c, in
         for (int g = 0; g < c.gl.batch[(size_t)(t - p_slots)]; g++) idx.push_back(c.fidx(g, t - p_slots));
         if (int e = slice_sums(s, idx, false)) return e;
     }
-    if (t >= 2) HIPCK(s, hipStreamWaitEvent(s->st_compute, s->ev_copy[c.slot_of(t - 2)], 0));      // the SSE pass of step t - 2 still reads the picture buffer this step reuses
+    // the copy-stream work of this group's step t - 2 (SSE, hash, SSIM) still reads the picture buffers this step reuses (step 0: all lanes, group 0's slot 0)
+    if (t >= 2) HIPCK(s, hipStreamWaitEvent(p.st, s->ev_copy[t == 2 ? 0 : p.grp][c.slot_of(t - 2)], 0));
     if (!s->rc.rc_on || t < 3) return 0;
-    const int j = t - 2, B = c.gl.batch[(size_t)j];
-    HIPCK(s, hipEventSynchronize(s->ev_copy[c.slot_of(j)]));
-    std::vector<double> v((size_t)B);
-    for (int g = 0; g < B; g++) v[(size_t)g] = (double)*(const unsigned long long *)(s->lane[g].sym_host[c.slot_of(j)] + c.sl.est);
+    const int j = t - 2;
+    const Part pj = c.part(s, p.grp, j);      // this group's lanes at step j (a superset of its lanes now)
+    HIPCK(s, hipEventSynchronize(s->ev_copy[p.grp][c.slot_of(j)]));
+    std::vector<double> v((size_t)pj.n);
+    for (int k = 0; k < pj.n; k++) v[(size_t)k] = (double)*(const unsigned long long *)(s->lane[pj.lanes[(size_t)k]].sym_host[c.slot_of(j)] + c.sl.est);
     if (int e = group_sum(s, v)) return e;
     std::lock_guard<std::mutex> l(s->m);
-    for (int g = 0; g < B; g++) { auto &fr = s->frames[c.fidx(g, j)]; if (!fr.est_known) { fr.est_q4 = (unsigned long long)v[(size_t)g]; fr.est_known = true; } }
+    for (int k = 0; k < pj.n; k++) { auto &fr = s->frames[c.fidx(pj.lanes[(size_t)k], j)]; if (!fr.est_known) { fr.est_q4 = (unsigned long long)v[(size_t)k]; fr.est_known = true; } }
     return 0;
 }
 
@@ -1003,14 +1044,15 @@ template <typename T> int rho_trial(mihevc_session *s, const Chunk<T> &c, const 
     std::vector<int> qp_trial((size_t)B1);
     for (int g = 0; g < B1; g++) {
         mihevc_session::Lane &L = s->lane[g];
+        const int a = c.at(1, g);      // the trial block is a copy of step 1's: its order
         qp_trial[(size_t)g] = RateControl::trial_qp(want[(size_t)g]);
-        tv.sao[g] = h0.sao[g];
-        tv.sao[g].sao = nullptr; tv.sao[g].sse = nullptr; tv.sao[g].sse_ctu = nullptr; tv.sao[g].cu = nullptr;
-        tv.sao[g].halo_top = tv.sao[g].halo_bottom = 0;      // the trial predicts from this band's own unfiltered picture with a replicated border
-        tv.inter[g] = h1.inter[g];
-        for (int i = 0; i < 3; i++) tv.inter[g].rec[i] = mk<T>(L.rec_p[1][i], L.rec_stride[i]);
-        tv.inter[g].prm = prm_for(s, qp_trial[(size_t)g]);
-        tv.inter[g].ip = nullptr;
+        tv.sao[a] = h0.sao[c.at(0, g)];
+        tv.sao[a].sao = nullptr; tv.sao[a].sse = nullptr; tv.sao[a].sse_ctu = nullptr; tv.sao[a].cu = nullptr;
+        tv.sao[a].halo_top = tv.sao[a].halo_bottom = 0;      // the trial predicts from this band's own unfiltered picture with a replicated border
+        tv.inter[a] = h1.inter[a];
+        for (int i = 0; i < 3; i++) tv.inter[a].rec[i] = mk<T>(L.rec_p[1][i], L.rec_stride[i]);
+        tv.inter[a].prm = prm_for(s, qp_trial[(size_t)g]);
+        tv.inter[a].ip = nullptr;
         HIPCK(s, hipMemsetAsync(L.sym_dev[c.slot_of(1)] + c.sl.sse, 0, 4 * sizeof(unsigned long long), s->st_compute));
     }
     HIPCK(s, hipMemcpyAsync(c.da + (size_t)tb * c.lay.total, c.ha + (size_t)tb * c.lay.total, c.lay.total, hipMemcpyHostToDevice, s->st_compute));
@@ -1034,7 +1076,7 @@ template <typename T> int idr_step(mihevc_session *s, const Chunk<T> &c, std::ve
     StepView<T> dv(c.da, c.lay, 0), hv(c.ha, c.lay, 0);
     HIPCK(s, hipMemcpyAsync(c.da, c.ha, c.lay.total, hipMemcpyHostToDevice, s->st_compute));
     for (int g = 0; g < B; g++) HIPCK(s, hipMemsetAsync(s->lane[g].sym_dev[0] + c.sl.sse, 0, 4 * sizeof(unsigned long long), s->st_compute));
-    STAGE(0, B, launch_intra_picture<T>(s->st_compute, dv.intra, s->ctus_w, s->ctus_h, B, s->tiles.cols, s->tiles.rows, s->cfg.pre_search ? s->ev_args : nullptr));
+    STAGE(s->st_compute, 0, B, launch_intra_picture<T>(s->st_compute, dv.intra, s->ctus_w, s->ctus_h, B, s->tiles.cols, s->tiles.rows, s->cfg.pre_search ? s->ev_args : nullptr));
     // cfg.pre_search: the search centres of EVERY picture of the chunk come from the 1/4-size SOURCE pictures (this picture against the one before it: nothing
     // in it waits for a reconstruction), in two launches on a stream of their own: the work (7 % of a clip's device time when it ran inside every step) sits
     // beside the anti-diagonal chain, which leaves most of the device idle, not beside k_intra_plan (both want the ALUs).  The first P step waits for ev_pre.
@@ -1064,11 +1106,11 @@ template <typename T> int idr_step(mihevc_session *s, const Chunk<T> &c, std::ve
             const int g = redo[k];
             qp_step[(size_t)g] = want[(size_t)g];
             patch_qp<T>(s, c, 0, g, qp_step[(size_t)g]);
-            hv.intra[B + (int)k] = hv.intra[g];
+            hv.intra[B + (int)k] = hv.intra[c.at(0, g)];
             HIPCK(s, hipMemsetAsync(s->lane[g].sym_dev[0] + c.sl.sse, 0, 4 * sizeof(unsigned long long), s->st_compute));
         }
         HIPCK(s, hipMemcpyAsync(c.da, c.ha, c.lay.total, hipMemcpyHostToDevice, s->st_compute));
-        STAGE(0, (int)redo.size(), launch_intra_picture<T>(s->st_compute, dv.intra + B, s->ctus_w, s->ctus_h, (int)redo.size(), s->tiles.cols, s->tiles.rows, nullptr));
+        STAGE(s->st_compute, 0, (int)redo.size(), launch_intra_picture<T>(s->st_compute, dv.intra + B, s->ctus_w, s->ctus_h, (int)redo.size(), s->tiles.cols, s->tiles.rows, nullptr));
         HIPCK(s, hipStreamSynchronize(s->st_compute));
         if (int e = lane_estimates(s, c.sl, 0, redo, e2)) return e;
         for (size_t k = 0; k < redo.size(); k++) ev[(size_t)redo[k]] = e2[k];
@@ -1080,10 +1122,12 @@ template <typename T> int idr_step(mihevc_session *s, const Chunk<T> &c, std::ve
 }
 
 // a P or B step: head, integer search, inter CTU programs (+ the intra second pass of P pictures)
-template <typename T> int inter_step(mihevc_session *s, const Chunk<T> &c, int t)
+template <typename T> int inter_step(mihevc_session *s, const Chunk<T> &c, const Part &p, int t)
 {
-    const int B = c.gl.batch[(size_t)t];
-    StepView<T> dv(c.da, c.lay, t), hv(c.ha, c.lay, t), pv(c.da, c.lay, t - 1);
+    const int B = p.n;
+    hipStream_t st = p.st;
+    // this part's entries of the step's arrays, and of the previous step's (the same lanes in the same order: a group's lanes only ever drop off its end)
+    StepView<T> dv(c.da, c.lay, t, p.base), hv(c.ha, c.lay, t, p.base), pv(c.da, c.lay, t - 1, c.group_base(p.grp, t - 1));
     // the step's QPs reach the device inside one tiny launch that also zeroes the slot's SSE + estimate accumulators; everything
     // else in the step's argument block went up with the chunk
     // The same launch pads the border of the previous step's pictures (nothing before this step's searches reads it) and makes the 1/4-size
@@ -1095,61 +1139,64 @@ template <typename T> int inter_step(mihevc_session *s, const Chunk<T> &c, int t
         // X2: the final reconstruction either side of the seams, straight out of the neighbours' pictures of the previous step, into the border
         // rows of this band's reference pictures (the pad below fills in their left / right ends and whatever lies beyond the whole picture)
         if (int e = wait_neighbours(s, c.halo, 2, s->gstep + t - 1)) return e;
-        HIPCK(s, launch_copy_rows(s->st_compute, c.halo.jobs(t, c.halo.jl.pull), B * 3 * c.halo.reach, 16));
+        HIPCK(s, launch_copy_rows(st, c.halo.jobs(t, c.halo.jl.pull), B * 3 * c.halo.reach, 16));
     }
-    HIPCK(s, launch_prep_p_step<T>(s->st_compute, pv.sao, (const PreArgs<T> *)nullptr, dv.intra, dv.inter, dv.sao, sp, s->w, s->h, B));
-    if (t == 1 && s->cfg.pre_search) HIPCK(s, hipStreamWaitEvent(s->st_compute, s->ev_pre, 0));      // the chunk's search centres (st_pre, under the IDR step)
+    HIPCK(s, launch_prep_p_step<T>(st, pv.sao, (const PreArgs<T> *)nullptr, dv.intra, dv.inter, dv.sao, sp, s->w, s->h, B));
+    if (t == 1 && s->cfg.pre_search) HIPCK(s, hipStreamWaitEvent(st, s->ev_pre, 0));      // the chunk's search centres (st_pre, under the IDR step)
     // stage 1 = the integer search around the chunk's search centres (a B picture: against both anchors)
     const bool bstep = type_of_step(c.bf, t) == 0;
-    if (int e_ = mark(s, 1, B, true)) return e_;
-    HIPCK(s, launch_me_search<T>(s->st_compute, dv.inter, s->n_ctu, B, s->me_range, 0));
-    if (bstep) HIPCK(s, launch_me_search<T>(s->st_compute, dv.inter, s->n_ctu, B, s->me_range, 1));
-    if (int e_ = mark(s, 1, B, false)) return e_;
-    if (bstep) STAGE(2, B, launch_inter_ctu_b<T>(s->st_compute, dv.inter, s->n_ctu, B, s->me_range));
-    else STAGE(2, B, launch_inter_ctu<T>(s->st_compute, dv.inter, s->n_ctu, B, s->me_range));
-    if (s->cfg.intra_in_p && !bstep) STAGE(7, B, launch_intra_p<T>(s->st_compute, dv.intra, s->n_ctu, B));
+    if (int e_ = mark(s, st, 1, B, true)) return e_;
+    HIPCK(s, launch_me_search<T>(st, dv.inter, s->n_ctu, B, s->me_range, 0));
+    if (bstep) HIPCK(s, launch_me_search<T>(st, dv.inter, s->n_ctu, B, s->me_range, 1));
+    if (int e_ = mark(s, st, 1, B, false)) return e_;
+    if (bstep) STAGE(st, 2, B, launch_inter_ctu_b<T>(st, dv.inter, s->n_ctu, B, s->me_range));
+    else STAGE(st, 2, B, launch_inter_ctu<T>(st, dv.inter, s->n_ctu, B, s->me_range));
+    if (s->cfg.intra_in_p && !bstep) STAGE(st, 7, B, launch_intra_p<T>(st, dv.intra, s->n_ctu, B));
     return 0;
 }
 
 // the loop filter of step t (with the rows the neighbour slices hand over), then the step's symbols to the host on the copy stream
-template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, int t)
+template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, const Part &p, int t)
 {
-    const int B = c.gl.batch[(size_t)t], slot = c.slot_of(t);
+    const int B = p.n, slot = c.slot_of(t);
+    hipStream_t st = p.st;
     const Halo &h = c.halo;
     const SymLayout &sl = c.sl;
     const long long G = s->gstep + t;
-    StepView<T> dv(c.da, c.lay, t);
+    StepView<T> dv(c.da, c.lay, t, p.base);
     if (h.on) {
         // X1: kSeamRows rows of the pre-deblock reconstruction + one row of CU records either side of every seam.  Every band puts its own first and last
         // rows where its neighbours can read them (the band's picture is deblocked in place right after), then takes the neighbours'
-        HIPCK(s, launch_copy_rows(s->st_compute, h.jobs(t, h.jl.exp), B * 8, 8));
-        HIPCK(s, hipEventRecord(s->ev_x1[G & 1], s->st_compute));
+        HIPCK(s, launch_copy_rows(st, h.jobs(t, h.jl.exp), B * 8, 8));
+        HIPCK(s, hipEventRecord(s->ev_x1[G & 1], st));
         s->group->announce(s->band, 1, G);
         if (int e = wait_neighbours(s, h, 1, G)) return e;
-        if (h.up + h.dn) HIPCK(s, launch_copy_rows(s->st_compute, h.jobs(t, h.jl.imp), B * 8, 8));
+        if (h.up + h.dn) HIPCK(s, launch_copy_rows(st, h.jobs(t, h.jl.imp), B * 8, 8));
     }
-    if (!s->cfg.sao) STAGE(3, B, launch_deblock<T>(s->st_compute, dv.dbk_v, dv.dbk_h, s->w, s->h + (h.on ? kSeamRows * (h.up + h.dn) : 0), B));
-    STAGE(4, B, launch_sao<T>(s->st_compute, dv.sao, s->w, s->h, B, s->cfg.sao != 0));
+    if (!s->cfg.sao) STAGE(st, 3, B, launch_deblock<T>(st, dv.dbk_v, dv.dbk_h, s->w, s->h + (h.on ? kSeamRows * (h.up + h.dn) : 0), B));
+    STAGE(st, 4, B, launch_sao<T>(st, dv.sao, s->w, s->h, B, s->cfg.sao != 0));
     if (h.on) {
-        HIPCK(s, hipEventRecord(s->ev_x2[G & 1], s->st_compute));
+        HIPCK(s, hipEventRecord(s->ev_x2[G & 1], st));
         s->group->announce(s->band, 2, G);
     }
-    HIPCK(s, hipEventRecord(s->ev_compute[slot], s->st_compute));      // (the border pad of these pictures is part of the next step's first launch)
-    HIPCK(s, hipStreamWaitEvent(s->st_copy, s->ev_compute[slot], 0));
+    HIPCK(s, hipEventRecord(s->ev_compute[p.grp][slot], st));      // (the border pad of these pictures is part of the next step's first launch)
+    HIPCK(s, hipStreamWaitEvent(s->st_copy, s->ev_compute[p.grp][slot], 0));
     // SSE (statistics only): the SAO programs left every CTU's squared error in the symbol block's device tail; one small launch on the copy stream, in
     // front of the symbol copies that carry its sums, adds them up.  (Until round 3 a pass of its own re-read source and reconstruction here: 7 MB per
     // picture and 25 us per step beside the compute stream.)  Without SAO that pass still runs: k_sao_apply is a plain copy and has no source.
     if (s->cfg.sao) HIPCK(s, launch_sse_fold<T>(s->st_copy, dv.sao, s->n_ctu, B));
     else HIPCK(s, launch_frame_sse<T>(s->st_copy, dv.sao, B));
     // decoded picture hash of the final pictures (coded area only: the border is the next step's pad), in front of the symbol copies that carry it.
-    // The compute stream reuses these picture buffers two steps later, behind ev_copy of this step (rate_feedback)
+    // The group's stream reuses these picture buffers two steps later, behind ev_copy of this step (rate_feedback).  The one copy stream takes both groups'
+    // work in turn, which also keeps the shared hash_part / ssim_part scratch to one launch at a time
     if (s->cfg.pic_hash >= 2) HIPCK(s, launch_pic_hash<T>(s->st_copy, dv.sao, s->w, s->h, B, s->cfg.pic_hash - 1, s->hash_part, sl.hash - sl.sse));
     // SSIM of the same pictures against their sources.  The reconstructions are safe here as for the hash.  The sources: the chunk's source pictures are written by
     // nothing while the chunk runs (uploads of the NEXT chunk's frames go to other buffers: a chunk's buffers return to the free list only at its end, behind
     // hipStreamSynchronize(st_copy)), and planes borrowed from the caller (mihevc_send_frame_device) stay valid and unmodified until the picture's packet is out,
     // which is behind ev_copy of this step
     if (s->cfg.ssim) HIPCK(s, launch_ssim<T>(s->st_copy, dv.sao, s->w, s->h, B, s->ssim_part, sl.ssim - sl.sse));
-    for (int g = 0; s->cfg.pic_hash == 1 && g < B; g++) {      // MD5: the picture to pinned memory for the CABAC job (no wait here)
+    for (int k = 0; s->cfg.pic_hash == 1 && k < B; k++) {      // MD5: the picture to pinned memory for the CABAC job (no wait here)
+        const int g = p.lanes[(size_t)k];
         uint8_t *dst = s->lane[g].md5_host[slot];
         const size_t es = esize(s);
         for (int i = 0; i < 3; i++) {
@@ -1158,42 +1205,46 @@ template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, 
             dst += (size_t)pw * ph * es;
         }
     }
-    for (int g = 0; g < B; g++) {   // CU records, then SAO parameters + SSE + rate estimate (the level planes were written to the host block directly)
+    for (int k = 0; k < B; k++) {   // CU records, then SAO parameters + SSE + rate estimate (the level planes were written to the host block directly)
+        const int g = p.lanes[(size_t)k];
         uint8_t *hd = s->lane[g].sym_host[slot], *dd = s->lane[g].sym_dev[slot];
         HIPCK(s, hipMemcpyAsync(hd + sl.cu, dd + sl.cu, sl.cu_bytes, hipMemcpyDeviceToHost, s->st_copy));
         HIPCK(s, hipMemcpyAsync(hd + sl.sao, dd + sl.sao, sl.total - sl.sao, hipMemcpyDeviceToHost, s->st_copy));
     }
-    for (int g = 0; s->keep_recon && g < B; g++) {
+    for (int k = 0; s->keep_recon && k < B; k++) {
+        const int g = p.lanes[(size_t)k];
         std::vector<uint16_t> &dst = s->recon[(int64_t)c.fidx(g, t)];
         const size_t es = esize(s);
         dst.assign((size_t)s->w * s->h * 3 / 2, 0);
         std::vector<uint8_t> tmp((size_t)s->w * s->h * 3 / 2 * es);
         size_t off = 0;
-        HIPCK(s, hipStreamSynchronize(s->st_compute));
+        HIPCK(s, hipStreamSynchronize(st));
         for (int i = 0; i < 3; i++) {
             int pw = i ? s->w / 2 : s->w, ph = i ? s->h / 2 : s->h;
             HIPCK(s, hipMemcpy2D(tmp.data() + off * es, pw * es, s->lane[g].rec_p[c.step(g, t).cur][i], s->lane[g].rec_stride[i] * es, pw * es, ph, hipMemcpyDeviceToHost));
             off += (size_t)pw * ph;
         }
-        for (size_t k = 0; k < dst.size(); k++) dst[k] = s->is16 ? ((uint16_t *)tmp.data())[k] : tmp[k];
+        for (size_t i = 0; i < dst.size(); i++) dst[i] = s->is16 ? ((uint16_t *)tmp.data())[i] : tmp[i];
     }
-    HIPCK(s, hipEventRecord(s->ev_copy[slot], s->st_copy));
+    HIPCK(s, hipEventRecord(s->ev_copy[p.grp][slot], s->st_copy));
     return 0;
 }
 #undef STAGE
 
 // CABAC of step t: one job per picture on the host pool, behind the step's symbol copy.  The pool's threads are shared by the pictures of the step
 // (their tiles, when the picture has several: cfg.p_tiles / IDR grid)
-template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, int t, const std::vector<int> &qp_step)
+template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, const Part &p, int t, const std::vector<int> &qp_step)
 {
-    const int B = c.gl.batch[(size_t)t], slot = c.slot_of(t);
-    { std::lock_guard<std::mutex> l(s->m); s->jobs_open[slot] += B; }
-    const int parts_wanted = std::max(1, s->host_threads / std::max(1, B));
-    for (int g = 0; g < B; g++) {
+    const int B = p.n, slot = c.slot_of(t);
+    { std::lock_guard<std::mutex> l(s->m); s->jobs_open[p.grp][slot] += B; }
+    // (the step's pictures, not the part's: what a picture's job is cut into, and with it the order its tiles are coded in, does not depend on the grouping)
+    const int parts_wanted = std::max(1, s->host_threads / std::max(1, c.gl.batch[(size_t)t]));
+    for (int k = 0; k < B; k++) {
+        const int g = p.lanes[(size_t)k];
         const GopStep gs = c.step(g, t);
         const int gstart = c.gl.gstart[(size_t)g];
         PictureJob *j = new PictureJob();
-        j->s = s; j->slot = slot; j->lane_i = g; j->index = (int64_t)c.fidx(g, t); j->pts = s->pending[gstart + gs.pos].pts;
+        j->s = s; j->grp = p.grp; j->slot = slot; j->lane_i = g; j->index = (int64_t)c.fidx(g, t); j->pts = s->pending[gstart + gs.pos].pts;
         // packets leave in DECODING order: place t of the GOP; dts = the pts of the frame at that place in display order, one frame earlier when
         // B pictures reorder (an anchor is decoded one picture before the B picture in front of it is shown)
         j->dec_index = c.first_index + gstart + t;
@@ -1202,7 +1253,7 @@ template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, int t,
         j->pic.ref_dist = gs.type == 1 ? gs.pos - gs.ref_pos : 0;
         j->dec_pos = t;
         j->prev_gop_len = c.gl.prev_len[(size_t)g];
-        j->slice_type = gs.type; j->poc = gs.pos; j->qp = qp_step[(size_t)g]; j->first_of_stream = j->dec_index == 0;
+        j->slice_type = gs.type; j->poc = gs.pos; j->qp = qp_step[(size_t)k]; j->first_of_stream = j->dec_index == 0;
         j->pic.slice_type = j->slice_type; j->pic.poc = gs.pos; j->pic.qp = j->qp;
         picture_symbols(s, j->slot, g, j->pic);
         j->n_tiles = picture_tiles(s->cfg, j->pic);
@@ -1210,7 +1261,7 @@ template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, int t,
         j->sub.resize((size_t)j->n_tiles);
         const bool md5 = s->cfg.pic_hash == 1;
         j->left.store(j->parts + (md5 ? 1 : 0));
-        hipEvent_t ev = s->ev_copy[j->slot];
+        hipEvent_t ev = s->ev_copy[p.grp][slot];
         for (int part = 0; part < j->parts; part++)
             s->pool->submit([s, j, part, ev] {
                 (void)hipSetDevice(s->device);          // worker threads start on device 0: wait on the event in its own device's context
@@ -1248,7 +1299,7 @@ template <typename T> int finish_rate(mihevc_session *s, const Chunk<T> &c)
 void wait_all_jobs(mihevc_session *s)
 {
     std::unique_lock<std::mutex> l(s->m);
-    s->cv.wait(l, [&] { int n = 0; for (int k = 0; k < kRing; k++) n += s->jobs_open[k]; return n == 0; });
+    s->cv.wait(l, [&] { int n = 0; for (int g = 0; g < kGroups; g++) for (int k = 0; k < kRing; k++) n += s->jobs_open[g][k]; return n == 0; });
 }
 
 // the pending pictures as closed GOPs in lock-step: step t launches each stage once for picture t of every GOP
@@ -1264,6 +1315,8 @@ template <typename T> int encode_chunk(mihevc_session *s)
     if (int e = setup_halo(s, c.gops, c.steps, c.halo)) return e;
     c.bf = s->cfg.bframes > 0;
     if (s->cfg.bframes < 0) { if (int e = probe_bframes<T>(s, n, c.bf)) return e; }
+    // slices that exchange rows: their announcements are ordered by one global step; another session on the device: see open_sessions
+    c.groups = c.halo.on || open_sessions(s->device).load() > 1 ? 1 : s->lane_groups;
     if (int e = alloc_chunk<T>(s, c)) return e;
     { std::lock_guard<std::mutex> l(s->m); s->frames.resize((size_t)s->frames_in); s->quality.resize((size_t)s->frames_in); }
     // every step's argument blocks, uploaded once
@@ -1277,21 +1330,37 @@ template <typename T> int encode_chunk(mihevc_session *s)
     HIPCK(s, hipEventCreate(&t_begin)); HIPCK(s, hipEventCreate(&t_end));
     HIPCK(s, hipEventRecord(t_begin, s->st_compute));
     const auto wall1 = std::chrono::steady_clock::now();
-    for (int t = 0; t < c.steps; t++) {
-        const int B = c.gl.batch[(size_t)t];
-        {   // the slot this step writes must have been drained by its previous CABAC jobs
-            std::unique_lock<std::mutex> l(s->m); s->cv.wait(l, [&] { return s->jobs_open[c.slot_of(t)] == 0; });
+    // Step 0 is one launch sequence for all lanes (the IDR decision reads every lane).  From step 1 on each lane group runs its own sequence on its own
+    // stream, group 0 then group 1 for every t: a blocking wait for one group's step t - 2 always has the other group's work queued behind it, and the
+    // device fills one sequence's launch tails and boundaries with the other's workgroups.
+    bool second = false;      // lane group 1 has work on st_pre
+    for (int t = 0; t < c.steps; t++)
+        for (int grp = 0; grp < (t == 0 ? 1 : c.groups); grp++) {
+            const Part p = c.part(s, grp, t);
+            if (!p.n) continue;      // (a step with one lane left is group 0's alone)
+            if (grp == 1 && !second) {      // group 1's first step: behind step 0 (compute stream); the search centres come down its own stream
+                HIPCK(s, hipStreamWaitEvent(p.st, s->ev_compute[0][0], 0));
+                second = true;
+            }
+            if (grp == 1) s->stats.reserved[6]++;      // steps that ran as two sequences
+            {   // the slot this step writes must have been drained by its previous CABAC jobs
+                std::unique_lock<std::mutex> l(s->m); s->cv.wait(l, [&] { return s->jobs_open[p.grp][c.slot_of(t)] == 0; });
+            }
+            if (int e = rate_feedback<T>(s, c, p, t)) return e;
+            std::vector<int> qp_step((size_t)p.n);
+            const bool history = s->rc.rc_on && type_of_step(c.bf, t) == 1;      // the P controller reads the lane's earlier pictures
+            for (int k = 0; k < p.n; k++) {
+                const int g = p.lanes[(size_t)k];
+                qp_step[(size_t)k] = s->rc.step_qp(g, t, history ? lane_records<T>(s, c, g, t) : std::vector<FrameRec>());
+                patch_qp<T>(s, c, t, g, qp_step[(size_t)k]);
+            }
+            if (int e = t == 0 ? idr_step<T>(s, c, qp_step) : inter_step<T>(s, c, p, t)) return e;
+            if (int e = filter_and_copy<T>(s, c, p, t)) return e;
+            hand_out<T>(s, c, p, t, qp_step);
         }
-        if (int e = rate_feedback<T>(s, c, t)) return e;
-        std::vector<int> qp_step((size_t)B);
-        const bool history = s->rc.rc_on && type_of_step(c.bf, t) == 1;      // the P controller reads the lane's earlier pictures
-        for (int g = 0; g < B; g++) {
-            qp_step[(size_t)g] = s->rc.step_qp(g, t, history ? lane_records<T>(s, c, g, t) : std::vector<FrameRec>());
-            patch_qp<T>(s, c, t, g, qp_step[(size_t)g]);
-        }
-        if (int e = t == 0 ? idr_step<T>(s, c, qp_step) : inter_step<T>(s, c, t)) return e;
-        if (int e = filter_and_copy<T>(s, c, t)) return e;
-        hand_out<T>(s, c, t, qp_step);
+    if (second) {      // the chunk's device time ends when both groups have
+        HIPCK(s, hipEventRecord(s->ev_join, s->st_pre));
+        HIPCK(s, hipStreamWaitEvent(s->st_compute, s->ev_join, 0));
     }
     HIPCK(s, hipEventRecord(t_end, s->st_compute));
     HIPCK(s, hipStreamSynchronize(s->st_compute));
@@ -1367,6 +1436,7 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     s->cfg = *cfg;
     if (s->cfg.sao < 0) s->cfg.sao = 1;
     s->device = device;
+    open_sessions(device)++;      // (mihevc_close takes it back, on the failure paths below too)
     CodedSize cs = coded_size(cfg->width, cfg->height);
     s->w = cs.w; s->h = cs.h;
     s->ctus_w = (s->w + CTU - 1) / CTU; s->ctus_h = (s->h + CTU - 1) / CTU; s->n_ctu = s->ctus_w * s->ctus_h;
@@ -1376,6 +1446,8 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     s->is16 = cfg->bit_depth > 8;
     s->keyint = cfg->keyint;
     s->lanes = cfg->gops_in_flight > 0 ? std::min(cfg->gops_in_flight, MAX_LANES) : 4;
+    // A/B switch: MIHEVC_LANE_GROUPS=1 runs the P/B steps of a chunk as one launch sequence on the compute stream; the stream is the same either way
+    if (const char *e = getenv("MIHEVC_LANE_GROUPS")) s->lane_groups = atoi(e) == 1 ? 1 : kGroups;
     s->me_range = cfg->me_range > 0 ? std::min(cfg->me_range, MAX_RANGE) : 15;   // 8 quads x 31 rows = 248 items: one pass of the 256-thread search
     // constant-quality operating point: P pictures at crf + 2, IDR pictures 3 below (x265's ipratio 1.4 ~ 3 QP)
     s->qp_p = cfg->qp >= 0 ? cfg->qp : std::min(51, std::max(0, cfg->crf + 2));
@@ -1384,9 +1456,10 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     write_parameter_sets(s->cfg, s->headers);
     bool ok = StreamCache::get().acquire(s->device, &s->st_compute) == hipSuccess && StreamCache::get().acquire(s->device, &s->st_copy) == hipSuccess &&
               StreamCache::get().acquire(s->device, &s->st_pre) == hipSuccess;
-    for (int i = 0; ok && i < kRing; i++)
-        ok = hipEventCreateWithFlags(&s->ev_compute[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s->ev_copy[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; ok && i < kGroups * kRing; i++)
+        ok = hipEventCreateWithFlags(&s->ev_compute[i / kRing][i % kRing], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&s->ev_copy[i / kRing][i % kRing], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&s->ev_pre, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s->ev_args, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming) == hipSuccess;
     if (ok && cfg->pic_hash >= 2) {
@@ -1641,15 +1714,17 @@ void mihevc_close(mihevc_session *s)
     bc.release(s->device, s->hash_part_bytes, false, s->hash_part);
     bc.release(s->device, s->ssim_part_bytes, false, s->ssim_part);
     for (CachedBuf *b : {&s->args, &s->scene, &s->low, &s->jobs, &s->probe}) { bc.release(s->device, b->cap, false, b->d); bc.release(s->device, b->cap, true, b->h); }
-    for (int i = 0; i < kRing; i++) { if (s->ev_compute[i]) (void)hipEventDestroy(s->ev_compute[i]); if (s->ev_copy[i]) (void)hipEventDestroy(s->ev_copy[i]); }
+    for (int g = 0; g < kGroups; g++)
+        for (int i = 0; i < kRing; i++) { if (s->ev_compute[g][i]) (void)hipEventDestroy(s->ev_compute[g][i]); if (s->ev_copy[g][i]) (void)hipEventDestroy(s->ev_copy[g][i]); }
     for (auto e : s->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {s->ev_pre, s->ev_args, s->ev_up}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {s->ev_pre, s->ev_args, s->ev_up, s->ev_join}) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++) {
         bc.release(s->device, s->x1_bytes, false, s->x1_export[k]);
         if (s->ev_x1[k]) (void)hipEventDestroy(s->ev_x1[k]);
         if (s->ev_x2[k]) (void)hipEventDestroy(s->ev_x2[k]);
     }
     for (hipStream_t st : {s->st_compute, s->st_copy, s->st_pre}) StreamCache::get().release(s->device, st);      // idle: synchronised above
+    open_sessions(s->device)--;
     delete s;
 }
 

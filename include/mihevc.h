@@ -149,7 +149,8 @@ typedef struct mihevc_stats {
     double  device_ms, entropy_ms;    /* accumulated device time (HIP events) and host CABAC time (sum over threads) */
     int32_t last_qp;
     int32_t reserved[7];              /* [0..2]: cfg.bframes = -1, the last probe; [3..5]: host microseconds of the chunks in front of their first launch, behind their last
-                                       * kernel (last symbol copies + the entropy coding still open), and in all: where wall time that is not device time goes */
+                                       * kernel (last symbol copies + the entropy coding still open), and in all: where wall time that is not device time goes;
+                                       * [6]: P/B steps that ran as two lane groups on two streams (0: one launch sequence, e.g. MIHEVC_LANE_GROUPS=1 in the environment at open) */
     /* per-stage device time, filled when cfg.profile_stages: sum of HIP-event intervals and number of launches.
      * index: 0 intra (plan + the anti-diagonal chain of a step), 1 me_search, 2 inter_ctu, 3 deblock (V+H; only without SAO: with SAO the loop filter is one kernel, counted
      * under 4), 4 sao (the whole loop filter: deblock of the CTU's tile + decide + apply + squared error), 5 border pad, 6 unused since ABI 2 (the SSE fold runs on the copy

@@ -5,6 +5,7 @@
   python tools/prof_summary.py pmc    <dir-with-*counter_collection.csv> [...]     -> per-kernel mean counter per dispatch
   python tools/prof_summary.py traffic <fetch-dir> <write-dir> <out.json>          -> HBM bytes per launch per kernel
   python tools/prof_summary.py pmcjson <out.json> <dir> [...]                      -> per-kernel VALU issue share (bench.py reads it)
+  python tools/prof_summary.py overlap <dir-with-*kernel_trace.csv>                -> kernels per hardware queue, and how long two queues ran kernels at once
 
 Normalisation of the SQ counters (stated because the raw numbers cannot be read without it): every value printed by `pmc` is the MEAN
 PER DISPATCH of what rocprofv3 wrote for that kernel.  On this pool rocprofv3 reports the SQ block of a subset of the shader engines
@@ -40,6 +41,30 @@ def stats(d):
         n, tot, mx = int(r['Calls']), int(r['TotalDurationNs']), int(r['MaxNs'])
         wo = (tot - mx) / max(1, n - 1) / 1e3
         print(f"{short(r['Name'])[:60]:60s} {n:7d} {tot / 1e6:10.3f} {float(r['AverageNs']) / 1e3:10.2f} {wo:10.2f} {mx / 1e3:10.1f} {float(r['Percentage']):6.2f}")
+
+
+def overlap(d):
+    """Do the launch sequences of two streams run side by side?  Per hardware queue: kernels and their summed time; then the time in which
+    kernels of at least one / at least two queues were running (a sweep over the start and end stamps of every dispatch)."""
+    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
+    per_q, ev = defaultdict(lambda: [0, 0]), []
+    for r in csv.DictReader(open(f)):
+        q, a, b = r.get("Queue_Id", "?"), int(r["Start_Timestamp"]), int(r["End_Timestamp"])
+        per_q[q][0] += 1
+        per_q[q][1] += b - a
+        ev += [(a, 1, q), (b, -1, q)]
+    for q, (n, ns) in sorted(per_q.items(), key=lambda kv: -kv[1][1]):
+        print(f"queue {q}: {n} kernels, {ns / 1e6:.3f} ms of kernel time")
+    ev.sort()
+    live, last, busy, two = defaultdict(int), None, 0, 0
+    for t, step, q in ev:
+        if last is not None:
+            n = sum(1 for v in live.values() if v > 0)
+            busy += (t - last) * (n >= 1)
+            two += (t - last) * (n >= 2)
+        live[q] += step
+        last = t
+    print(f"a kernel was running for {busy / 1e6:.3f} ms; kernels of two or more queues at once for {two / 1e6:.3f} ms ({100.0 * two / max(1, busy):.1f} %)")
 
 
 def pmc_means(d):
@@ -128,6 +153,8 @@ if __name__ == "__main__":
     cmd = sys.argv[1]
     if cmd == "stats":
         stats(sys.argv[2])
+    elif cmd == "overlap":
+        overlap(sys.argv[2])
     elif cmd == "pmc":
         pmc(sys.argv[2:])
     elif cmd == "traffic":
