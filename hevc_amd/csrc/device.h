@@ -55,8 +55,8 @@ int ssim_part_words(int w, int h);
 template <typename T> hipError_t launch_ssim(hipStream_t st, const SaoArgs<T> *d_args, int w, int h, int batch, long long *part, size_t out_off);
 constexpr int MAX_LANES = 16;
 struct StepParams { CostParams prm[MAX_LANES]; int p_tile_cols, p_tile_rows; };      // one P step's cost parameters per lane, passed by value; the P pictures' tile grid (intra second pass: availability)
-template <typename T> hipError_t launch_begin_p_step(hipStream_t st, IntraArgs<T> *ia, InterArgs<T> *ea, SaoArgs<T> *sa, const StepParams &p, int batch);
-// head of a P step in one launch: border pad of the pictures `prev` describes (nullptr: none), 1/4-size pictures for `pre` (nullptr: none), then launch_begin_p_step's work
+// head of a P step in one launch: border pad of the pictures `prev` describes (nullptr: none), 1/4-size pictures for `pre` (nullptr: none), then the step's
+// cost parameters (by value in `p`) into the lanes' argument blocks, and the four accumulators at SaoArgs::sse zeroed
 template <typename T> hipError_t launch_prep_p_step(hipStream_t st, const SaoArgs<T> *prev, const PreArgs<T> *pre, IntraArgs<T> *ia, InterArgs<T> *ea, SaoArgs<T> *sa,
                                                     const StepParams &p, int w, int h, int batch);
 

@@ -339,21 +339,6 @@ template <typename T> hipError_t launch_ssim(hipStream_t st, const SaoArgs<T> *d
     return hipGetLastError();
 }
 
-// Start of a P step, one tiny launch for every lane: the step's cost parameters (QP from the rate controller, by value in the kernel
-// arguments) go into the lane's argument blocks — the rest of the blocks was uploaded with the chunk — and the per-picture accumulators
-// (SSE per plane + the rate estimate behind them: four 64-bit words at SaoArgs::sse) are zeroed.
-template <typename T> __global__ __launch_bounds__(64) void k_begin_p_step(IntraArgs<T> *ia, InterArgs<T> *ea, SaoArgs<T> *sa, StepParams p)
-{
-    const int g = (int)blockIdx.x;
-    if (threadIdx.x == 0) {
-        CostParams c = p.prm[g];
-        ea[g].prm = c; sa[g].prm = c;
-        c.tile_cols = p.p_tile_cols; c.tile_rows = p.p_tile_rows;      // P pictures use PPS 0 (one tile, or cfg.p_tiles' grid)
-        ia[g].prm = c;
-    }
-    if (threadIdx.x < 4) sa[g].sse[threadIdx.x] = 0;
-}
-
 // Head of a P step in ONE launch (three tiny kernels before: every launch boundary on the compute stream costs ~6 us, a step had ten): the border pad of
 // the picture the previous step finished (only the next picture's searches read the border), the 1/4-size pictures of this step's source and reference,
 // and the step's cost parameters.  blockIdx.x selects the job, blockIdx.y the lane.
@@ -392,12 +377,6 @@ template <typename T> hipError_t launch_prep_p_step(hipStream_t st, const SaoArg
     const int n_pad = prev ? (pad_border_quads(w, h, PAD_Y) + 2 * pad_border_quads(w >> 1, h >> 1, PAD_C) + 255) / 256 : 0;
     const int n_low = pre ? (2 * (w >> 2) * (h >> 2) + 255) / 256 : 0;
     hipLaunchKernelGGL(k_prep_p_step<T>, dim3((unsigned)(n_pad + n_low + 1), (unsigned)batch), dim3(256), 0, st, prev, n_pad, pre, n_low, ia, ea, sa, p);
-    return hipGetLastError();
-}
-template <typename T> hipError_t launch_begin_p_step(hipStream_t st, IntraArgs<T> *ia, InterArgs<T> *ea, SaoArgs<T> *sa, const StepParams &p, int batch)
-{
-    if (batch > MAX_LANES) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_begin_p_step<T>, dim3((unsigned)batch), dim3(64), 0, st, ia, ea, sa, p);
     return hipGetLastError();
 }
 template <typename T> hipError_t launch_frame_sse(hipStream_t st, const SaoArgs<T> *d_args, int batch)
@@ -579,7 +558,6 @@ int gfx950_device_count()
     template hipError_t launch_sse_fold<T>(hipStream_t, const SaoArgs<T> *, int, int);                                   \
     template hipError_t launch_pic_hash<T>(hipStream_t, const SaoArgs<T> *, int, int, int, int, uint32_t *, size_t);           \
     template hipError_t launch_ssim<T>(hipStream_t, const SaoArgs<T> *, int, int, int, long long *, size_t);                   \
-    template hipError_t launch_begin_p_step<T>(hipStream_t, IntraArgs<T> *, InterArgs<T> *, SaoArgs<T> *, const StepParams &, int); \
     template hipError_t launch_extend_margin<T>(hipStream_t, Plane<T>, int, int, int, int);                             \
     template hipError_t launch_scene_diff<T>(hipStream_t, const ScenePic<T> *, unsigned long long *, int, int, int);            \
     template hipError_t alloc_plane<T>(DevPlane<T> &, int, int, int);                                                   \

@@ -26,6 +26,8 @@
 
 #include "bitstream.h"
 #include "device.h"
+#include "gop_plan.h"
+#include "host_pool.h"
 #include "md5.h"
 #include "ratectl.h"
 #include "slice_group.h"
@@ -37,110 +39,6 @@ namespace {
 constexpr int kRing = 12;     // symbol slots per lane (capacity): slot 0 holds the IDR picture, the rest rotate over the P steps.
                               // A session uses s->ring of them: 8 up to 1080p-class levels, 12 from level 5 (2160p+), where the CABAC of one
                               // picture (12 ms at 2160p, 45 ms at 4320p) outlasts five device steps when few GOP lanes are busy
-constexpr double kCutAbs = 8.0;          // scene cut: mean absolute difference of consecutive pictures above this many grey levels (8-bit scale) ...
-constexpr double kCutRatio = 1.8;        // ... and this many times the running mean over the ordinary pictures before it
-
-// Host worker pool for the CABAC jobs.  ONE pool per process, shared by every session and grown to the largest size a session asks for: a batch
-// codes many clips back to back, and starting / joining 16 threads per clip was 2 ms of every 80 ms 1080p clip (bench step_phases open + close).
-// The threads live until the process exits (they are parked on a condition variable); a session waits for ITS jobs, never for the threads.
-class ThreadPool {
-public:
-    static ThreadPool &shared(int n)
-    {
-        static ThreadPool *p = new ThreadPool();      // never destroyed: no join at process exit, the threads hold no session state
-        p->grow(n);
-        return *p;
-    }
-    void submit(std::function<void()> f)
-    {
-        {
-            std::lock_guard<std::mutex> l(m_);
-            q_.push_back(std::move(f));
-        }
-        cv_.notify_one();
-    }
-
-private:
-    void grow(int n)
-    {
-        std::lock_guard<std::mutex> l(m_);
-        while ((int)threads_.size() < n) { threads_.emplace_back([this] { run(); }); threads_.back().detach(); }
-    }
-    void run()
-    {
-        for (;;) {
-            std::function<void()> f;
-            {
-                std::unique_lock<std::mutex> l(m_);
-                cv_.wait(l, [this] { return !q_.empty(); });
-                f = std::move(q_.front());
-                q_.pop_front();
-            }
-            f();
-        }
-    }
-    std::vector<std::thread> threads_;
-    std::deque<std::function<void()>> q_;
-    std::mutex m_;
-    std::condition_variable cv_;
-};
-
-// Process-wide cache of device / pinned-host allocations keyed by (device, size): a batch transcodes many clips of
-// the same geometry back to back (gui/mainwindow.py queue), and hipMalloc/hipHostMalloc/hipFree cost tens of ms
-// per session otherwise (bench step_phases: close 51 ms).  Buffers return to the cache at mihevc_close.
-class BufferCache {
-public:
-    static BufferCache &get() { static BufferCache c; return c; }
-    hipError_t alloc(int dev, size_t n, bool pinned, void **out)
-    {
-        {
-            std::lock_guard<std::mutex> l(m_);
-            auto &v = free_[key(dev, n, pinned)];
-            if (!v.empty()) { *out = v.back(); v.pop_back(); bytes_ -= n; return hipSuccess; }
-        }
-        return pinned ? hipHostMalloc(out, n, hipHostMallocDefault) : hipMalloc(out, n);
-    }
-    void release(int dev, size_t n, bool pinned, void *p)
-    {
-        if (!p) return;
-        std::lock_guard<std::mutex> l(m_);
-        if (bytes_ + n > kMaxBytes) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); return; }
-        bytes_ += n;
-        free_[key(dev, n, pinned)].push_back(p);
-    }
-private:
-    static constexpr size_t kMaxBytes = (size_t)24 << 30;      // 24 GiB of 288: plenty for a few clip geometries
-    static std::string key(int dev, size_t n, bool pinned) { return std::to_string(dev) + (pinned ? "h" : "d") + std::to_string(n); }
-    std::mutex m_;
-    std::map<std::string, std::vector<void *>> free_;
-    size_t bytes_ = 0;
-};
-
-// the same for the sessions' two streams (create + destroy: about a millisecond per session)
-class StreamCache {
-public:
-    static StreamCache &get() { static StreamCache c; return c; }
-    hipError_t acquire(int dev, hipStream_t *out)
-    {
-        {
-            std::lock_guard<std::mutex> l(m_);
-            auto &v = free_[dev];
-            if (!v.empty()) { *out = v.back(); v.pop_back(); return hipSuccess; }
-        }
-        return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-    }
-    void release(int dev, hipStream_t st)
-    {
-        if (!st) return;
-        std::lock_guard<std::mutex> l(m_);
-        auto &v = free_[dev];
-        if (v.size() >= 16) { (void)hipStreamDestroy(st); return; }
-        v.push_back(st);
-    }
-private:
-    std::mutex m_;
-    std::map<int, std::vector<hipStream_t>> free_;
-};
 
 struct Packet {
     std::vector<uint8_t> data;
@@ -176,11 +74,7 @@ struct SymLayout {
 };
 
 // a session's scratch buffer from the process-wide cache (grow()): device memory, optionally with a pinned host twin of the same size
-struct CachedBuf {
-    void *d = nullptr;
-    uint8_t *h = nullptr;
-    size_t cap = 0;
-};
+struct CachedBuf { CachedBlock<uint8_t> d, h; };
 
 constexpr int kGroups = 2;        // lane groups of a chunk's P/B steps: two launch sequences on two streams (encode_chunk)
 // sessions this process has open on a device.  A chunk runs as lane groups only while its session is the device's only one: a second session's launches already
@@ -202,40 +96,42 @@ struct mihevc_session {
     std::atomic<bool> failed{false};     // sticky (fail()); mihevc_abort sets it from another thread
     int fail_code = MIHEVC_EDEVICE;      // what calls return once `failed` is set: MIHEVC_EINVAL when the host coder refused a picture
     std::string err;                     // written under `m` (mihevc_abort may run on another thread)
-    hipStream_t st_compute = nullptr, st_copy = nullptr, st_pre = nullptr;      // st_pre: the chunk's pre-search, beside the IDR step; then the P/B steps of lane group 1
+    CachedStream st_compute, st_copy, st_pre;      // st_pre: the chunk's pre-search, beside the IDR step; then the P/B steps of lane group 1
     int lane_groups = kGroups;        // launch sequences the P/B steps of a chunk run as (MIHEVC_LANE_GROUPS, read at mihevc_open: 1 = one sequence on the compute stream)
     // uploads of host frames (mihevc_send_frame / _async) go through st_pre (idle outside a chunk's IDR step; a FOURTH stream per session made two of them share a
     // hardware queue: the copy stream's SSE pass and symbol copies then queued behind the compute stream's kernels, +10 ms of bubbles per 300-frame clip); the
     // chunk's first launch waits for ev_up
-    hipEvent_t ev_up = nullptr;
+    Event ev_up{hipEventDisableTiming};
     bool up_pending = false;
     // source pictures of the current chunk (device), in display order
-    struct Src { void *base[3]; void *p[3]; int stride[3]; int64_t pts; bool borrowed; };      // borrowed: the caller's device planes, not copied
-    size_t plane_bytes[3][3] = {{0}};   // [kind: plain / padded reference / work][plane] allocation sizes (for the buffer cache)
+    struct Src { CachedBlock<uint8_t> mem[3]; void *p[3]; int stride[3]; int64_t pts; bool borrowed; };      // borrowed: the caller's device planes, not copied (mem is empty)
     std::vector<Src> pending;
     std::vector<Src> free_src;
     // per lane
+    // The vector moves a lane's handles when it grows; the blocks they own stay where they are, so the raw pointers in argument blocks, jobs and BandPub stay valid
     struct Lane {
-        void *rec_base[3][3], *rec_p[3][3]; int rec_stride[3];       // padded final reconstructions: the anchors ping-pong between 0 and 1; 2 = B pictures (cfg.bframes; never a reference)
-        void *work_base[3], *work_p[3]; int work_stride[3];           // pre-deblock / deblocked picture (unpadded)
-        int32_t *me = nullptr, *me1 = nullptr;      // integer-search tables (me1: list 1 of B pictures)
-        IpInfo *ip = nullptr;      // per CTU: inter pass -> intra second pass of P pictures
-        IntraPlan *plan = nullptr; // per CTU: k_intra_plan -> k_intra_diag (IDR pictures)
-        uint8_t *sym_dev[kRing] = {nullptr}, *sym_host[kRing] = {nullptr};
-        uint8_t *md5_host[kRing] = {nullptr};      // cfg.pic_hash 1: the final picture (coded size, Y U V without gaps), pinned, per ring slot
+        CachedBlock<uint8_t> rec_mem[3][3]; void *rec_p[3][3] = {}; int rec_stride[3] = {};       // padded final reconstructions: the anchors ping-pong between 0 and 1; 2 = B pictures (cfg.bframes; never a reference)
+        CachedBlock<uint8_t> work_mem[3]; void *work_p[3] = {}; int work_stride[3] = {};           // pre-deblock / deblocked picture (unpadded)
+        CachedBlock<int32_t> me, me1;      // integer-search tables (me1: list 1 of B pictures)
+        CachedBlock<IpInfo> ip;            // per CTU: inter pass -> intra second pass of P pictures
+        CachedBlock<IntraPlan> plan;       // per CTU: k_intra_plan -> k_intra_diag (IDR pictures)
+        CachedBlock<uint8_t> sym_dev[kRing], sym_host[kRing];
+        CachedBlock<uint8_t> md5_host[kRing];      // cfg.pic_hash 1: the final picture (coded size, Y U V without gaps), pinned, per ring slot
     };
     std::vector<Lane> lane;
     CachedBuf args;                   // argument blocks of a whole chunk (device + pinned staging)
-    hipEvent_t ev_compute[kGroups][kRing] = {}, ev_copy[kGroups][kRing] = {};      // by (lane group, ring slot); step 0 (all lanes, one launch) uses group 0's slot 0
-    hipEvent_t ev_join = nullptr;     // behind the last step of lane group 1 (st_pre): the compute stream waits for it at the end of the chunk
-    std::vector<hipEvent_t> ev_pool;   // profile_stages: start/stop pairs
+    // by (lane group, ring slot); step 0 (all lanes, one launch) uses group 0's slot 0.  compute: the step's pictures are final; copy: its symbols are on the
+    // host; jobs_open: its CABAC jobs still running (under `m`)
+    struct Slot { Event compute{hipEventDisableTiming}, copy{hipEventDisableTiming}; int jobs_open = 0; } slot[kGroups][kRing];
+    Event ev_join{hipEventDisableTiming};     // behind the last step of lane group 1 (st_pre): the compute stream waits for it at the end of the chunk
+    Event t_begin{hipEventDefault}, t_end{hipEventDefault};      // a chunk's device time (stats.device_ms)
+    std::vector<Event> ev_pool;        // profile_stages: start/stop pairs
     struct Mark { int stage, pictures; size_t ev; };
     std::vector<Mark> marks;
     // host side
     ThreadPool *pool = nullptr;
     std::mutex m;
     std::condition_variable cv;
-    int jobs_open[kGroups][kRing] = {{0}};
     int ring = 8;                 // slots in use (<= kRing)
     int host_threads = 2;         // CABAC worker threads this session asked the process-wide pool for
     std::map<int64_t, Packet> packets;     // by output index
@@ -246,33 +142,36 @@ struct mihevc_session {
     RateControl rc;                           // rate control (csrc/ratectl.h)
     CachedBuf probe;                          // cfg.bframes = -1: the probe's argument blocks
     int64_t pts_step = 1, first_pts = 0;      // pts distance of the first two frames: with B pictures dts = (pts of the frame at the packet's place in decoding order) - pts_step
-    int last_gop_len = 0;                     // length of the stream's previous GOP (picture timing SEI at the next IDR)
-    double scene_avg = 0;                     // running mean of the picture-to-picture difference over ordinary pictures (scene-cut detector)
+    GopState gop;                             // what the GOP planner carries from chunk to chunk (csrc/gop_plan.h)
     CachedBuf low;                                   // per chunk: 1/4-size SOURCE pictures of every picture, then the search centres of every picture (pre-search)
-    hipEvent_t ev_pre = nullptr, ev_args = nullptr;  // the chunk's centres are ready (st_pre) / the IDR step's k_intra_plan is through (compute stream: the argument blocks are on the device too)
+    Event ev_pre{hipEventDisableTiming}, ev_args{hipEventDisableTiming};  // the chunk's centres are ready (st_pre) / the IDR step's k_intra_plan is through (compute stream: the argument blocks are on the device too)
     CachedBuf scene;                                 // per chunk: picture pointers / pitches in, difference sums out (k_scene_diff)
     std::vector<FrameRec> frames;             // by output index
     struct Quality { unsigned long long sse[3]; long long ssim[3]; bool known; };
     std::vector<Quality> quality;             // by output index (display order), written when the picture's symbols have landed (publish_picture)
     std::atomic<long long> entropy_ns{0};
+    bool events_ok() const      // the events the session is constructed with (an Event that could not be created is empty)
+    {
+        bool ok = ev_up && ev_join && t_begin && t_end && ev_pre && ev_args;
+        for (auto &g : slot) for (auto &sl : g) ok = ok && sl.compute && sl.copy;
+        return ok;
+    }
     // ---- one slice of a picture whose slices exchange rows (cfg.slice_halo; csrc/slice_group.h)
     std::shared_ptr<SliceGroup> group;
     int band = 0, n_bands = 1;
     int band_h[kMaxBands] = {0};              // coded heights of all bands
     long long gstep = 0;                      // steps since the session was opened: the same in every band of the group
-    hipEvent_t ev_x1[2] = {nullptr, nullptr}, ev_x2[2] = {nullptr, nullptr};
-    void *x1_export[2] = {nullptr, nullptr};
-    size_t x1_part_bytes = 0, x1_lane_bytes = 0, x1_bytes = 0;
+    Event ev_x1[2], ev_x2[2];
+    CachedBlock<uint8_t> x1_export[2];
+    size_t x1_part_bytes = 0, x1_lane_bytes = 0;
     CachedBuf jobs;                           // row-copy job tables of a chunk (device + pinned staging)
     std::vector<int> peers_enabled;
     // ---- decoded picture hash (cfg.pic_hash)
-    uint32_t *hash_part = nullptr;            // 2 / 3: segment partials of k_pic_hash, MAX_LANES pictures (device)
-    size_t hash_part_bytes = 0;
+    CachedBlock<uint32_t> hash_part;          // 2 / 3: segment partials of k_pic_hash, MAX_LANES pictures (device)
     // ---- per-picture SSIM (cfg.ssim)
-    long long *ssim_part = nullptr;           // region partials of k_ssim, MAX_LANES pictures (device)
+    CachedBlock<long long> ssim_part;         // region partials of k_ssim, MAX_LANES pictures (device)
     long long ssim_total[3] = {0, 0, 0};      // sum of Q over every window of every published picture: an integer, so mihevc_stats.ssim_* does not depend on the
                                               // order the CABAC jobs finish in (2 M windows of a 4320p picture x 2^32 x 500 000 pictures fit 63 bits)
-    size_t ssim_part_bytes = 0;
 };
 
 namespace {
@@ -298,37 +197,36 @@ size_t md5_pic_bytes(const mihevc_session *s) { return (size_t)s->w * s->h * 3 /
 
 // padded 0: a plain picture; 1: a reference picture with its PAD border all round; 2: a work picture with kSeamRows rows above and below (the rows the
 // neighbour slices hand over for deblocking across seams; unused otherwise)
-int alloc_planes(mihevc_session *s, void *base[3], void *p[3], int stride[3], int padded)
+int alloc_planes(mihevc_session *s, CachedBlock<uint8_t> mem[3], void *p[3], int stride[3], int padded)
 {
     for (int i = 0; i < 3; i++) {
         int w = i ? s->w / 2 : s->w, h = i ? s->h / 2 : s->h, pad = padded == 1 ? (i ? PAD_C : PAD_Y) : 0, vm = padded == 2 ? (i ? kSeamRows / 2 : kSeamRows) : pad;
         stride[i] = (w + 2 * pad + 63) & ~63;
-        s->plane_bytes[padded][i] = (size_t)stride[i] * (h + 2 * vm) * esize(s);
-        HIPCK(s, BufferCache::get().alloc(s->device, s->plane_bytes[padded][i], false, &base[i]));
-        p[i] = (uint8_t *)base[i] + ((size_t)vm * stride[i] + pad) * esize(s);
+        HIPCK(s, mem[i].alloc(s->device, (size_t)stride[i] * (h + 2 * vm) * esize(s), false));
+        p[i] = mem[i] + ((size_t)vm * stride[i] + pad) * esize(s);
     }
     return 0;
 }
 
+// (a failure midway: the local lane gives back what it had taken)
 int ensure_lanes(mihevc_session *s, int n)
 {
     SymLayout sl(s->w, s->h);
     while ((int)s->lane.size() < n) {
         mihevc_session::Lane L;
-        memset(&L, 0, sizeof L);
         for (int k = 0; k < (s->cfg.bframes != 0 ? 3 : 2); k++)
-            if (int e = alloc_planes(s, L.rec_base[k], L.rec_p[k], L.rec_stride, 1)) return e;
-        if (int e = alloc_planes(s, L.work_base, L.work_p, L.work_stride, 2)) return e;
-        HIPCK(s, BufferCache::get().alloc(s->device, (size_t)s->n_ctu * 63 * sizeof(int32_t), false, (void **)&L.me));
-        if (s->cfg.bframes != 0) HIPCK(s, BufferCache::get().alloc(s->device, (size_t)s->n_ctu * 63 * sizeof(int32_t), false, (void **)&L.me1));
-        HIPCK(s, BufferCache::get().alloc(s->device, (size_t)s->n_ctu * sizeof(IpInfo), false, (void **)&L.ip));
-        HIPCK(s, BufferCache::get().alloc(s->device, (size_t)s->n_ctu * sizeof(IntraPlan), false, (void **)&L.plan));
+            if (int e = alloc_planes(s, L.rec_mem[k], L.rec_p[k], L.rec_stride, 1)) return e;
+        if (int e = alloc_planes(s, L.work_mem, L.work_p, L.work_stride, 2)) return e;
+        HIPCK(s, L.me.alloc(s->device, (size_t)s->n_ctu * 63 * sizeof(int32_t), false));
+        if (s->cfg.bframes != 0) HIPCK(s, L.me1.alloc(s->device, (size_t)s->n_ctu * 63 * sizeof(int32_t), false));
+        HIPCK(s, L.ip.alloc(s->device, (size_t)s->n_ctu * sizeof(IpInfo), false));
+        HIPCK(s, L.plan.alloc(s->device, (size_t)s->n_ctu * sizeof(IntraPlan), false));
         for (int k = 0; k < s->ring; k++) {
-            HIPCK(s, BufferCache::get().alloc(s->device, sl.dev_total, false, (void **)&L.sym_dev[k]));
-            HIPCK(s, BufferCache::get().alloc(s->device, sl.total, true, (void **)&L.sym_host[k]));
-            if (s->cfg.pic_hash == 1) HIPCK(s, BufferCache::get().alloc(s->device, md5_pic_bytes(s), true, (void **)&L.md5_host[k]));
+            HIPCK(s, L.sym_dev[k].alloc(s->device, sl.dev_total, false));
+            HIPCK(s, L.sym_host[k].alloc(s->device, sl.total, true));
+            if (s->cfg.pic_hash == 1) HIPCK(s, L.md5_host[k].alloc(s->device, md5_pic_bytes(s), true));
         }
-        s->lane.push_back(L);
+        s->lane.push_back(std::move(L));
     }
     return 0;
 }
@@ -336,15 +234,11 @@ int ensure_lanes(mihevc_session *s, int n)
 // grow a cached buffer to at least `need` bytes, rounded up with `round_mask` (the next session's chunk then finds a block of the same size in the cache)
 int grow(mihevc_session *s, CachedBuf &b, size_t need, size_t round_mask, bool with_host)
 {
-    if (need <= b.cap) return 0;
-    BufferCache &bc = BufferCache::get();
-    bc.release(s->device, b.cap, false, b.d);
-    bc.release(s->device, b.cap, true, b.h);
-    b = CachedBuf{};
+    if (need <= b.d.bytes()) return 0;
+    b.d.reset(); b.h.reset();
     const size_t cap = (need + round_mask) & ~round_mask;
-    HIPCK(s, bc.alloc(s->device, cap, false, &b.d));
-    b.cap = cap;
-    if (with_host) HIPCK(s, bc.alloc(s->device, cap, true, (void **)&b.h));
+    HIPCK(s, b.d.alloc(s->device, cap, false));
+    if (with_host) HIPCK(s, b.h.alloc(s->device, cap, true));
     return 0;
 }
 // argument blocks of one lock-step step: five arrays of `gops` entries each, so one launch per stage covers all lanes
@@ -457,7 +351,7 @@ void publish_picture(PictureJob *j)
         s->packets[j->dec_index] = std::move(pk);
         s->frames_done++;
         delete j;
-        s->jobs_open[grp][slot]--;
+        s->slot[grp][slot].jobs_open--;
         s->cv.notify_all();      // under the lock: mihevc_close may delete the session as soon as its last job has let go of the mutex
     }
 }
@@ -500,7 +394,7 @@ template <typename T> int scene_differences(mihevc_session *s, int n, std::vecto
     unsigned long long *d_out = (unsigned long long *)((uint8_t *)s->scene.d + ((in_bytes + 255) & ~(size_t)255));
     HIPCK(s, hipMemcpyAsync(s->scene.d, pics.data(), in_bytes, hipMemcpyHostToDevice, s->st_compute));
     HIPCK(s, hipMemsetAsync(d_out, 0, (size_t)n * sizeof(unsigned long long), s->st_compute));
-    HIPCK(s, launch_scene_diff<T>(s->st_compute, (const ScenePic<T> *)s->scene.d, d_out, s->w, s->h, n));
+    HIPCK(s, launch_scene_diff<T>(s->st_compute, (const ScenePic<T> *)s->scene.d.get(), d_out, s->w, s->h, n));
     HIPCK(s, hipMemcpyAsync(out.data(), d_out, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st_compute));
     HIPCK(s, hipStreamSynchronize(s->st_compute));
     return 0;
@@ -599,12 +493,6 @@ template <typename T> static int probe_bframes(mihevc_session *s, int n, bool &u
 }
 
 // ---- one chunk ------------------------------------------------------------------------------------------------------------------------------------
-// lanes by GOP length, longest first: the lanes that still have a picture at step t are then a prefix [0, batch[t])
-struct GopLayout {
-    std::vector<int> gstart, glen, prev_len;      // per lane: first picture (place in `pending`), length, length of the GOP before it in the stream
-    std::vector<int> batch;                       // per step: lanes with a picture
-};
-
 // the slices of one picture exchange rows (cfg.slice_halo; csrc/slice_group.h): the bands in reach and the chunk's row-copy job tables
 struct Halo {
     bool on = false;
@@ -663,73 +551,17 @@ template <typename T> struct Chunk {
     size_t fidx(int g, int t) const { return (size_t)(first_index + gl.gstart[(size_t)g] + step(g, t).pos); }
 };
 
-// GOP layout of the chunk.  Scene cuts (x265 scenecut + min-keyint, reference core/transcoder.py:401) divide the chunk into segments; every
-// segment is coded as the FEWEST closed GOPs keyint allows (the IDR count of an IDR-every-keyint layout), of near-equal length when
-// cfg.gop_balance is set: the lanes of the lock-step pipeline then run out together instead of idling behind a short last GOP (a 300-picture
-// clip at keyint 90 is 4 x 75 steps, not 90 steps of which 60 drive three lanes).  With gop_balance 0 a segment's IDRs sit every keyint pictures.
-// The cut detector is the mean absolute difference of every 4th sample of every 4th row between consecutive source pictures (k_scene_diff, one
-// launch for the chunk): a cut is a difference above kCutAbs grey levels that is also kCutRatio times the running mean over the ordinary
-// pictures before it, taken when every GOP of the segment it closes keeps at least min-keyint pictures.  A session that codes one slice of
+// GOP layout of the chunk (csrc/gop_plan.h).  Here: whether the scene-cut detector applies, and its one device call.  A session that codes one slice of
 // the picture sees only its band, and the slices of a picture must agree on its type: no cut detection there.
 template <typename T> int gop_layout(mihevc_session *s, int n, GopLayout &gl)
 {
-    const int keyint = s->keyint;
-    auto gops_of = [keyint](int len) { return (len + keyint - 1) / keyint; };
-    std::vector<int> seg{0};                  // segment starts
-    if (s->cfg.scenecut && s->cfg.slice_count <= 1 && n > 1 && s->cfg.min_keyint < keyint) {
-        std::vector<unsigned long long> diff((size_t)n, 0);
+    std::vector<unsigned long long> diff;
+    if (s->cfg.scenecut && s->cfg.slice_count <= 1 && n > 1 && s->cfg.min_keyint < s->keyint) {
+        diff.assign((size_t)n, 0);
         if (int e = scene_differences<T>(s, n, diff)) return e;
-        const double per = (double)((s->w + 3) / 4) * ((s->h + 3) / 4) * (1 << (s->cfg.bit_depth - 8));
-        int total = 0;                        // GOPs of the closed segments
-        // Until the running mean has seen an ordinary picture (a session's first pictures) the chunk's MEDIAN difference stands in for it: a cut or a
-        // flash at the session's second picture is then a jump like any other and never becomes the mean the next pictures are measured against
-        double median = 0;
-        if (s->scene_avg <= 0) {
-            std::vector<unsigned long long> sorted(diff.begin() + 1, diff.end());
-            std::nth_element(sorted.begin(), sorted.begin() + (ptrdiff_t)(sorted.size() / 2), sorted.end());
-            median = (double)sorted[sorted.size() / 2] / per;
-        }
-        auto is_jump = [&](int i) {
-            const double d = (double)diff[(size_t)i] / per, base = s->scene_avg > 0 ? s->scene_avg : median;
-            return d > kCutAbs && d > kCutRatio * base;
-        };
-        for (int i = 1; i < n; i++) {
-            const double d = (double)diff[(size_t)i] / per;
-            const int len = i - seg.back(), g = gops_of(len);
-            const bool jump = is_jump(i);
-            // a run of jumps (a flash: into the odd picture and out of it again) is cut at its LAST picture: the GOP then starts on the scene that stays,
-            // not on the flash it would have to predict everything from
-            const bool last_of_run = !(i + 1 < n && is_jump(i + 1));
-            const int shortest = s->cfg.gop_balance ? len / g : (len % keyint ? len % keyint : keyint);
-            // the GOP the cut opens must keep min-keyint pictures too: the next chunk starts with an IDR picture of its own (the stream's last chunk may end short)
-            const bool tail_ok = s->flushing || n - i >= std::max(1, s->cfg.min_keyint);
-            if (jump && last_of_run && tail_ok && shortest >= std::max(1, s->cfg.min_keyint) && total + g + gops_of(n - i) <= MAX_LANES) { total += g; seg.push_back(i); }
-            if (!jump) s->scene_avg = s->scene_avg > 0 ? 0.8 * s->scene_avg + 0.2 * d : d;      // ordinary pictures only: a jump says nothing about the new scene's motion
-        }
     }
-    std::vector<int> gstart_stream;
-    for (size_t k = 0; k < seg.size(); k++) {
-        const int a0 = seg[k], len = (k + 1 < seg.size() ? seg[k + 1] : n) - a0, g = gops_of(len);
-        if (s->cfg.gop_balance)
-            for (int j = 0, at = a0; j < g; at += len / g + (j < len % g), j++) gstart_stream.push_back(at);
-        else
-            for (int at = a0; at < a0 + len; at += keyint) gstart_stream.push_back(at);
-    }
-    const int gops = (int)gstart_stream.size();
-    std::vector<int> order((size_t)gops);
-    gl.gstart.assign((size_t)gops, 0); gl.glen.assign((size_t)gops, 0); gl.prev_len.assign((size_t)gops, 0);
-    for (int g = 0; g < gops; g++) order[(size_t)g] = g;
-    auto len_of = [&](int k) { return (k + 1 < gops ? gstart_stream[(size_t)k + 1] : n) - gstart_stream[(size_t)k]; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len_of(a) > len_of(b); });
-    for (int g = 0; g < gops; g++) {
-        const int k = order[(size_t)g];
-        gl.gstart[(size_t)g] = gstart_stream[(size_t)k]; gl.glen[(size_t)g] = len_of(k);
-        gl.prev_len[(size_t)g] = k > 0 ? len_of(k - 1) : s->last_gop_len;
-    }
-    s->last_gop_len = len_of(gops - 1);
-    gl.batch.assign((size_t)gl.glen[0], 0);
-    for (int g = 0; g < gops; g++)
-        for (int t = 0; t < gl.glen[(size_t)g]; t++) gl.batch[(size_t)t] = g + 1;
+    const double per = (double)((s->w + 3) / 4) * ((s->h + 3) / 4) * (1 << (s->cfg.bit_depth - 8));
+    gl = gop_plan(diff, per, n, s->keyint, s->cfg.min_keyint, s->cfg.gop_balance != 0, s->flushing, MAX_LANES, s->gop);
     return 0;
 }
 
@@ -1000,7 +832,7 @@ int mark(mihevc_session *s, hipStream_t st, int stage, int pictures, bool begin)
 {
     if (!s->cfg.profile_stages || (s->cfg.profile_stages == 2 && stage != 2)) return 0;      // 2: the dominant stage (inter_ctu) only
     size_t need_ev = s->marks.size() * 2 + 2;
-    while (s->ev_pool.size() < need_ev) { hipEvent_t e; HIPCK(s, hipEventCreate(&e)); s->ev_pool.push_back(e); }
+    while (s->ev_pool.size() < need_ev) { s->ev_pool.emplace_back(hipEventDefault); if (!s->ev_pool.back()) return fail(s, "hipEventCreate failed"); }
     if (begin) { s->marks.push_back({stage, pictures, s->marks.size() * 2}); HIPCK(s, hipEventRecord(s->ev_pool[s->marks.back().ev], st)); }
     else HIPCK(s, hipEventRecord(s->ev_pool[s->marks.back().ev + 1], st));
     return 0;
@@ -1020,11 +852,11 @@ template <typename T> int rate_feedback(mihevc_session *s, const Chunk<T> &c, co
         if (int e = slice_sums(s, idx, false)) return e;
     }
     // the copy-stream work of this group's step t - 2 (SSE, hash, SSIM) still reads the picture buffers this step reuses (step 0: all lanes, group 0's slot 0)
-    if (t >= 2) HIPCK(s, hipStreamWaitEvent(p.st, s->ev_copy[t == 2 ? 0 : p.grp][c.slot_of(t - 2)], 0));
+    if (t >= 2) HIPCK(s, hipStreamWaitEvent(p.st, s->slot[t == 2 ? 0 : p.grp][c.slot_of(t - 2)].copy, 0));
     if (!s->rc.rc_on || t < 3) return 0;
     const int j = t - 2;
     const Part pj = c.part(s, p.grp, j);      // this group's lanes at step j (a superset of its lanes now)
-    HIPCK(s, hipEventSynchronize(s->ev_copy[p.grp][c.slot_of(j)]));
+    HIPCK(s, hipEventSynchronize(s->slot[p.grp][c.slot_of(j)].copy));
     std::vector<double> v((size_t)pj.n);
     for (int k = 0; k < pj.n; k++) v[(size_t)k] = (double)*(const unsigned long long *)(s->lane[pj.lanes[(size_t)k]].sym_host[c.slot_of(j)] + c.sl.est);
     if (int e = group_sum(s, v)) return e;
@@ -1179,8 +1011,8 @@ template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, 
         HIPCK(s, hipEventRecord(s->ev_x2[G & 1], st));
         s->group->announce(s->band, 2, G);
     }
-    HIPCK(s, hipEventRecord(s->ev_compute[p.grp][slot], st));      // (the border pad of these pictures is part of the next step's first launch)
-    HIPCK(s, hipStreamWaitEvent(s->st_copy, s->ev_compute[p.grp][slot], 0));
+    HIPCK(s, hipEventRecord(s->slot[p.grp][slot].compute, st));      // (the border pad of these pictures is part of the next step's first launch)
+    HIPCK(s, hipStreamWaitEvent(s->st_copy, s->slot[p.grp][slot].compute, 0));
     // SSE (statistics only): the SAO programs left every CTU's squared error in the symbol block's device tail; one small launch on the copy stream, in
     // front of the symbol copies that carry its sums, adds them up.  (Until round 3 a pass of its own re-read source and reconstruction here: 7 MB per
     // picture and 25 us per step beside the compute stream.)  Without SAO that pass still runs: k_sao_apply is a plain copy and has no source.
@@ -1226,7 +1058,7 @@ template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, 
         }
         for (size_t i = 0; i < dst.size(); i++) dst[i] = s->is16 ? ((uint16_t *)tmp.data())[i] : tmp[i];
     }
-    HIPCK(s, hipEventRecord(s->ev_copy[p.grp][slot], s->st_copy));
+    HIPCK(s, hipEventRecord(s->slot[p.grp][slot].copy, s->st_copy));
     return 0;
 }
 #undef STAGE
@@ -1236,7 +1068,7 @@ template <typename T> int filter_and_copy(mihevc_session *s, const Chunk<T> &c, 
 template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, const Part &p, int t, const std::vector<int> &qp_step)
 {
     const int B = p.n, slot = c.slot_of(t);
-    { std::lock_guard<std::mutex> l(s->m); s->jobs_open[p.grp][slot] += B; }
+    { std::lock_guard<std::mutex> l(s->m); s->slot[p.grp][slot].jobs_open += B; }
     // (the step's pictures, not the part's: what a picture's job is cut into, and with it the order its tiles are coded in, does not depend on the grouping)
     const int parts_wanted = std::max(1, s->host_threads / std::max(1, c.gl.batch[(size_t)t]));
     for (int k = 0; k < B; k++) {
@@ -1261,7 +1093,7 @@ template <typename T> void hand_out(mihevc_session *s, const Chunk<T> &c, const 
         j->sub.resize((size_t)j->n_tiles);
         const bool md5 = s->cfg.pic_hash == 1;
         j->left.store(j->parts + (md5 ? 1 : 0));
-        hipEvent_t ev = s->ev_copy[p.grp][slot];
+        hipEvent_t ev = s->slot[p.grp][slot].copy;
         for (int part = 0; part < j->parts; part++)
             s->pool->submit([s, j, part, ev] {
                 (void)hipSetDevice(s->device);          // worker threads start on device 0: wait on the event in its own device's context
@@ -1299,7 +1131,7 @@ template <typename T> int finish_rate(mihevc_session *s, const Chunk<T> &c)
 void wait_all_jobs(mihevc_session *s)
 {
     std::unique_lock<std::mutex> l(s->m);
-    s->cv.wait(l, [&] { int n = 0; for (int g = 0; g < kGroups; g++) for (int k = 0; k < kRing; k++) n += s->jobs_open[g][k]; return n == 0; });
+    s->cv.wait(l, [&] { int n = 0; for (int g = 0; g < kGroups; g++) for (int k = 0; k < kRing; k++) n += s->slot[g][k].jobs_open; return n == 0; });
 }
 
 // the pending pictures as closed GOPs in lock-step: step t launches each stage once for picture t of every GOP
@@ -1326,9 +1158,7 @@ template <typename T> int encode_chunk(mihevc_session *s)
     if (c.halo.on) HIPCK(s, hipMemcpyAsync(c.halo.dj, c.halo.hj, (size_t)c.steps * c.halo.jl.total, hipMemcpyHostToDevice, s->st_compute));
     s->rc.begin_chunk(c.bf, c.gl.glen);
     // ---- lock-step over the GOPs
-    hipEvent_t t_begin, t_end;
-    HIPCK(s, hipEventCreate(&t_begin)); HIPCK(s, hipEventCreate(&t_end));
-    HIPCK(s, hipEventRecord(t_begin, s->st_compute));
+    HIPCK(s, hipEventRecord(s->t_begin, s->st_compute));
     const auto wall1 = std::chrono::steady_clock::now();
     // Step 0 is one launch sequence for all lanes (the IDR decision reads every lane).  From step 1 on each lane group runs its own sequence on its own
     // stream, group 0 then group 1 for every t: a blocking wait for one group's step t - 2 always has the other group's work queued behind it, and the
@@ -1339,12 +1169,12 @@ template <typename T> int encode_chunk(mihevc_session *s)
             const Part p = c.part(s, grp, t);
             if (!p.n) continue;      // (a step with one lane left is group 0's alone)
             if (grp == 1 && !second) {      // group 1's first step: behind step 0 (compute stream); the search centres come down its own stream
-                HIPCK(s, hipStreamWaitEvent(p.st, s->ev_compute[0][0], 0));
+                HIPCK(s, hipStreamWaitEvent(p.st, s->slot[0][0].compute, 0));
                 second = true;
             }
             if (grp == 1) s->stats.reserved[6]++;      // steps that ran as two sequences
             {   // the slot this step writes must have been drained by its previous CABAC jobs
-                std::unique_lock<std::mutex> l(s->m); s->cv.wait(l, [&] { return s->jobs_open[p.grp][c.slot_of(t)] == 0; });
+                std::unique_lock<std::mutex> l(s->m); s->cv.wait(l, [&] { return s->slot[p.grp][c.slot_of(t)].jobs_open == 0; });
             }
             if (int e = rate_feedback<T>(s, c, p, t)) return e;
             std::vector<int> qp_step((size_t)p.n);
@@ -1362,13 +1192,13 @@ template <typename T> int encode_chunk(mihevc_session *s)
         HIPCK(s, hipEventRecord(s->ev_join, s->st_pre));
         HIPCK(s, hipStreamWaitEvent(s->st_compute, s->ev_join, 0));
     }
-    HIPCK(s, hipEventRecord(t_end, s->st_compute));
+    HIPCK(s, hipEventRecord(s->t_end, s->st_compute));
     HIPCK(s, hipStreamSynchronize(s->st_compute));
     const auto wall2 = std::chrono::steady_clock::now();
     HIPCK(s, hipStreamSynchronize(s->st_copy));
     HIPCK(s, hipStreamSynchronize(s->st_pre));        // a chunk without P steps never waited for its pre-search: its buffers are reused by the next chunk
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, t_begin, t_end);
+    (void)hipEventElapsedTime(&ms, s->t_begin, s->t_end);
     s->stats.device_ms += ms;
     for (auto &mk : s->marks) {
         float e = 0;
@@ -1377,11 +1207,10 @@ template <typename T> int encode_chunk(mihevc_session *s)
         }
     }
     s->marks.clear();
-    (void)hipEventDestroy(t_begin); (void)hipEventDestroy(t_end);
     wait_all_jobs(s);                                 // all CABAC jobs of the chunk
     s->gstep += c.steps;
     if (int e = finish_rate<T>(s, c)) return e;
-    for (auto &src : s->pending) if (!src.borrowed) s->free_src.push_back(src);
+    for (auto &src : s->pending) if (!src.borrowed) s->free_src.push_back(std::move(src));
     s->pending.clear();
     const auto wall3 = std::chrono::steady_clock::now();
     auto us = [](auto a, auto b) { return (int32_t)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
@@ -1454,23 +1283,10 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     s->qp_i = std::max(0, s->qp_p - 3);
     s->stats.last_qp = s->qp_p;
     write_parameter_sets(s->cfg, s->headers);
-    bool ok = StreamCache::get().acquire(s->device, &s->st_compute) == hipSuccess && StreamCache::get().acquire(s->device, &s->st_copy) == hipSuccess &&
-              StreamCache::get().acquire(s->device, &s->st_pre) == hipSuccess;
-    for (int i = 0; ok && i < kGroups * kRing; i++)
-        ok = hipEventCreateWithFlags(&s->ev_compute[i / kRing][i % kRing], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&s->ev_copy[i / kRing][i % kRing], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&s->ev_pre, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s->ev_args, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming) == hipSuccess;
-    if (ok && cfg->pic_hash >= 2) {
-        s->hash_part_bytes = (size_t)MAX_LANES * pic_hash_part_words(s->w, s->h, (int)esize(s)) * sizeof(uint32_t);
-        ok = BufferCache::get().alloc(s->device, s->hash_part_bytes, false, (void **)&s->hash_part) == hipSuccess;
-    }
-    if (ok && cfg->ssim) {
-        s->ssim_part_bytes = (size_t)MAX_LANES * ssim_part_words(s->w, s->h) * sizeof(long long);
-        ok = BufferCache::get().alloc(s->device, s->ssim_part_bytes, false, (void **)&s->ssim_part) == hipSuccess;
-    }
-    if (!ok) { mihevc_close(s); return MIHEVC_EDEVICE; }      // gives back what was acquired (event handles of the slots never reached stay null)
+    bool ok = s->events_ok() && s->st_compute.acquire(device) == hipSuccess && s->st_copy.acquire(device) == hipSuccess && s->st_pre.acquire(device) == hipSuccess;
+    if (ok && cfg->pic_hash >= 2) ok = s->hash_part.alloc(device, (size_t)MAX_LANES * pic_hash_part_words(s->w, s->h, (int)esize(s)) * sizeof(uint32_t), false) == hipSuccess;
+    if (ok && cfg->ssim) ok = s->ssim_part.alloc(device, (size_t)MAX_LANES * ssim_part_words(s->w, s->h) * sizeof(long long), false) == hipSuccess;
+    if (!ok) { mihevc_close(s); return MIHEVC_EDEVICE; }      // gives back what was acquired
     if (cfg->slice_count > 1 && cfg->slice_halo) {
         // one slice of a picture whose slices exchange rows: meet the others (csrc/slice_group.h), and get the buffers the neighbours read
         s->n_bands = cfg->slice_count; s->band = cfg->slice_index;
@@ -1482,10 +1298,10 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
         const size_t es = s->is16 ? 2 : 1;
         s->x1_part_bytes = (((size_t)kSeamRows * s->w + (size_t)kSeamRows * (s->w / 2)) * es + (size_t)(s->w >> 3) * sizeof(mihevc_cu_rec) + 255) & ~(size_t)255;
         s->x1_lane_bytes = 2 * s->x1_part_bytes;
-        s->x1_bytes = s->x1_lane_bytes * kHaloLanes;
-        for (int k = 0; ok && k < 2; k++)
-            ok = BufferCache::get().alloc(s->device, s->x1_bytes, false, &s->x1_export[k]) == hipSuccess &&
-                 hipEventCreateWithFlags(&s->ev_x1[k], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s->ev_x2[k], hipEventDisableTiming) == hipSuccess;
+        for (int k = 0; ok && k < 2; k++) {
+            s->ev_x1[k] = Event(hipEventDisableTiming); s->ev_x2[k] = Event(hipEventDisableTiming);
+            ok = s->x1_export[k].alloc(device, s->x1_lane_bytes * kHaloLanes, false) == hipSuccess && s->ev_x1[k] && s->ev_x2[k];
+        }
         if (!ok || cfg->slice_group == 0) { mihevc_close(s); return cfg->slice_group == 0 ? MIHEVC_EINVAL : MIHEVC_EDEVICE; }
         s->group = SliceGroup::join(cfg->slice_group, cfg->slice_count);
     }
@@ -1514,11 +1330,11 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
     // wall time of handing 300 frames over).
     if (device_src && s->cfg.width == s->w && s->cfg.height == s->h && pitch_y >= s->w && pitch_c >= s->w / 2 &&
         ((uintptr_t)y & 3) == 0 && ((uintptr_t)u & 3) == 0 && ((uintptr_t)v & 3) == 0 && (pitch_y * es) % 4 == 0 && (pitch_c * es) % 4 == 0) {
-        for (int i = 0; i < 3; i++) { src.base[i] = nullptr; src.p[i] = const_cast<void *>(in[i]); src.stride[i] = i ? pitch_c : pitch_y; }
+        for (int i = 0; i < 3; i++) { src.p[i] = const_cast<void *>(in[i]); src.stride[i] = i ? pitch_c : pitch_y; }
         src.borrowed = true;
     } else {
-        if (!s->free_src.empty()) { src = s->free_src.back(); s->free_src.pop_back(); }
-        else if (int e = alloc_planes(s, src.base, src.p, src.stride, 0)) return e;
+        if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
+        else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;      // (a failure midway: `src` gives back the planes it had taken)
         src.borrowed = false;
         // uploads run on a stream of their own; the chunk's first launch waits for the event behind the last one.  The synchronous entry point waits
         // here (the caller may reuse its buffers on return), the asynchronous one returns with the copies in flight
@@ -1538,7 +1354,7 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
     }
     src.pts = pts;
     if (s->frames_in == 0) s->first_pts = pts; else if (s->frames_in == 1) s->pts_step = std::max<int64_t>(1, pts - s->first_pts);
-    s->pending.push_back(src);
+    s->pending.push_back(std::move(src));
     s->frames_in++;
     s->stats.frames_in = s->frames_in;
     if ((int)s->pending.size() >= s->lanes * s->keyint) return run_chunk(s);
@@ -1696,36 +1512,8 @@ void mihevc_close(mihevc_session *s)
     if (s->st_compute) (void)hipStreamSynchronize(s->st_compute);
     if (s->st_copy) (void)hipStreamSynchronize(s->st_copy);
     if (s->st_pre) (void)hipStreamSynchronize(s->st_pre);
-    BufferCache &bc = BufferCache::get();
-    SymLayout sl(s->w, s->h);
-    auto free3 = [&](void *b[3], int padded) { for (int i = 0; i < 3; i++) bc.release(s->device, s->plane_bytes[padded][i], false, b[i]); };
-    for (auto &x : s->pending) if (!x.borrowed) free3(x.base, 0);
-    for (auto &x : s->free_src) free3(x.base, 0);
-    for (auto &L : s->lane) {
-        free3(L.rec_base[0], 1); free3(L.rec_base[1], 1); free3(L.work_base, 2);
-        if (L.rec_base[2][0]) free3(L.rec_base[2], 1);
-        bc.release(s->device, (size_t)s->n_ctu * 63 * sizeof(int32_t), false, L.me);
-        bc.release(s->device, (size_t)s->n_ctu * 63 * sizeof(int32_t), false, L.me1);
-        bc.release(s->device, (size_t)s->n_ctu * sizeof(IpInfo), false, L.ip);
-        bc.release(s->device, (size_t)s->n_ctu * sizeof(IntraPlan), false, L.plan);
-        for (int k = 0; k < s->ring; k++) { bc.release(s->device, sl.dev_total, false, L.sym_dev[k]); bc.release(s->device, sl.total, true, L.sym_host[k]); }
-        for (int k = 0; k < s->ring; k++) bc.release(s->device, md5_pic_bytes(s), true, L.md5_host[k]);
-    }
-    bc.release(s->device, s->hash_part_bytes, false, s->hash_part);
-    bc.release(s->device, s->ssim_part_bytes, false, s->ssim_part);
-    for (CachedBuf *b : {&s->args, &s->scene, &s->low, &s->jobs, &s->probe}) { bc.release(s->device, b->cap, false, b->d); bc.release(s->device, b->cap, true, b->h); }
-    for (int g = 0; g < kGroups; g++)
-        for (int i = 0; i < kRing; i++) { if (s->ev_compute[g][i]) (void)hipEventDestroy(s->ev_compute[g][i]); if (s->ev_copy[g][i]) (void)hipEventDestroy(s->ev_copy[g][i]); }
-    for (auto e : s->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {s->ev_pre, s->ev_args, s->ev_up, s->ev_join}) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; k++) {
-        bc.release(s->device, s->x1_bytes, false, s->x1_export[k]);
-        if (s->ev_x1[k]) (void)hipEventDestroy(s->ev_x1[k]);
-        if (s->ev_x2[k]) (void)hipEventDestroy(s->ev_x2[k]);
-    }
-    for (hipStream_t st : {s->st_compute, s->st_copy, s->st_pre}) StreamCache::get().release(s->device, st);      // idle: synchronised above
     open_sessions(s->device)--;
-    delete s;
+    delete s;                   // every buffer, event and stream goes back through its handle; the streams are idle (synchronised above)
 }
 
 }  // extern "C"

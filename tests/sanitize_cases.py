@@ -62,3 +62,10 @@ for (w, h, qp, bd) in [(128, 96, 28, 8), (72, 72, 26, 10)]:
         assert util.same_analysis(want, got), (w, h, i, util.describe_diff(want, got))
         ref, _ = O.sao(srcs[i], O.deblock(want.rec, want.cu, bd), prm)
     print("ok intra second pass", w, h, bd, flush=True)
+
+# the GOP planner (csrc/gop_plan.h) under the sanitizers: no cuts, a flash and a cut, more cuts than lanes (tests/test_gop_plan_cpu.py checks what it returns)
+from tests import test_gop_plan_cpu as G
+for n, jumps, kw in [(300, [], {}), (200, [1, 60, 61, 140], {"scene_avg": 0.0}), (200, list(range(8, 200, 8)), {"scene_avg": 2.5, "last_gop_len": 75}), (2, [1], {})]:
+    for balance in (True, False):
+        G.check_against_reference(G.calm(n, jumps), n, 90, 1, balance, True, lib=emu.lib, **kw)
+print("ok gop plan", flush=True)

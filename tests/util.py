@@ -156,10 +156,10 @@ def psnr(a, b, peak=255.0):
 
 def stepped_library():
     """tests/emu/libkernel_emu.so: the kernel sources stepped on the CPU (a test harness: hevc_amd/ never loads it).  Rebuilt when a harness
-    source, a kernel header, the stage argument builders or the ABI header is newer than the library"""
+    source, a kernel header, the stage argument builders, the GOP planner or the ABI header is newer than the library"""
     so = EMU_DIR / "libkernel_emu.so"
     sources = sorted(EMU_DIR.glob("*.cpp"))
-    deps = sources + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "include" / "mihevc.h"]
+    deps = sources + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "hevc_amd" / "csrc" / "gop_plan.h", ROOT / "include" / "mihevc.h"]
     if not so.exists() or any(d.stat().st_mtime > so.stat().st_mtime for d in deps):
         tmp = so.with_name(f"libkernel_emu.{os.getpid()}.so")                  # renamed into place: a process that has the old one loaded keeps it
         try:
@@ -306,7 +306,7 @@ def run_pipeline(api_or_oracle, srcs, prm_i, prm_p, bd=8):
 
 
 def idr_positions(n, keyint, lanes=4, balance=True):
-    """IDR pictures of a session without scene cuts (hevc_amd/csrc/session.cpp encode_chunk): chunks of lanes x keyint pictures, every chunk coded as the
+    """IDR pictures of a session without scene cuts (hevc_amd/csrc/gop_plan.h gop_plan, one call per chunk; tests/test_gop_plan_cpu.py): chunks of lanes x keyint pictures, every chunk coded as the
     fewest GOPs keyint allows, of near-equal length (cfg.gop_balance, the default) or with an IDR every keyint pictures."""
     out, pos = [], 0
     while pos < n:
