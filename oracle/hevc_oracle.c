@@ -6,6 +6,7 @@
  * hevc_amd/csrc/kernels/ (HIP).  PARITY UNPINNED vs libx265 (no golden vectors exist; see header).
  */
 #include "hevc_oracle.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -748,7 +749,41 @@ static void intra_in_p_pass(const pix *src_y, const pix *src_u, const pix *src_v
                             const orc_params *prm, pix *rec_y, pix *rec_u, pix *rec_v, int rec_stride, int rec_cstride,
                             orc_cu_rec *cu, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v, const uint8_t *cand, const uint64_t *jinter);
 
-void orc_analyze_inter_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
+/* The search window and the vectors it yields may reach past the ORC_PAD border the caller's reference planes carry: a centre of +-56 (the pre-search's
+ * largest) with me_range 32 reads 88 + 8 samples outside the picture.  The kernels read every reference sample at a coordinate clamped to the padded
+ * plane, which holds the picture's edge samples, i.e. at a coordinate clamped to the picture.  The oracle gets the same by analysing against copies of
+ * the reference planes with a border as wide as the search can reach.  reach: luma samples outside the picture the analysis may touch.
+ * widen_ref relies on the caller's planes carrying the full ORC_PAD / ORC_PAD / 2 border (hevc_oracle.h says so at the entry points): it reads them
+ * out to exactly that distance. */
+#define REACH_EXTRA_COLUMNS 3    /* spanx - (2R + 1) <= 3: the row of candidates is widened to whole quads, to the right */
+#define REACH_FRACTION 1         /* the half- and quarter-sample rings move a vector by less than one whole sample */
+#define REACH_TAPS 4             /* the 8-tap luma filter reads 3 samples before and 4 after the position */
+#define REACH_CHROMA_TAPS 4      /* chroma: half the luma reach, rounded up, the 4-tap filter's 1 before / 2 after and the eighth-sample step; 4 covers them */
+static int search_reach(const int16_t *centers, int n_ctu, const orc_params *prm)
+{
+    int c = centers ? 0 : prm->pre_search ? 4 * ORC_PRE_RANGE : 0;
+    for (int i = 0; centers && i < 2 * n_ctu; i++) if (iabs(centers[i]) > c) c = iabs(centers[i]);
+    return c + prm->me_range + REACH_EXTRA_COLUMNS + REACH_FRACTION + REACH_TAPS;
+}
+typedef struct { pix *base[3]; const pix *org[3]; int stride, cstride; } wide_ref;
+static void widen_ref(wide_ref *o, const pix *y, const pix *u, const pix *v, int stride, int cstride, int w, int h, int reach)
+{
+    const pix *in[3] = {y, u, v};
+    for (int c = 0; c < 3; c++) {
+        int pw = c ? w / 2 : w, ph = c ? h / 2 : h, pad_in = c ? ORC_PAD / 2 : ORC_PAD, pad = c ? reach / 2 + REACH_CHROMA_TAPS : reach, is = c ? cstride : stride;
+        int os = pw + 2 * pad;
+        o->base[c] = (pix *)malloc(sizeof(pix) * (size_t)os * (ph + 2 * pad));
+        if (!o->base[c]) { fprintf(stderr, "hevc_oracle: out of memory widening a reference plane\n"); abort(); }      /* a test tool: nothing to fall back to */
+        for (int yy = -pad; yy < ph + pad; yy++)
+            for (int xx = -pad; xx < pw + pad; xx++)
+                o->base[c][(yy + pad) * os + xx + pad] = in[c][CLIP3(-pad_in, ph + pad_in - 1, yy) * is + CLIP3(-pad_in, pw + pad_in - 1, xx)];
+        o->org[c] = o->base[c] + pad * os + pad;
+        if (c) o->cstride = os; else o->stride = os;
+    }
+}
+static void free_ref(wide_ref *o) { for (int c = 0; c < 3; c++) free(o->base[c]); }
+
+static void analyze_inter_frame_padded(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
                              const pix *ref_y, const pix *ref_u, const pix *ref_v, int ref_stride, int ref_cstride,
                              int w, int h, const orc_params *prm, const int16_t *centers,
                              pix *rec_y, pix *rec_u, pix *rec_v, int rec_stride, int rec_cstride,
@@ -943,6 +978,24 @@ void orc_analyze_inter_frame(const pix *src_y, const pix *src_u, const pix *src_
     if (est) *est = estimate_bits(cu, coef_y, coef_u, coef_v, w, h, centers);
     free(own_centers);
 }
+void orc_analyze_inter_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
+                             const pix *ref_y, const pix *ref_u, const pix *ref_v, int ref_stride, int ref_cstride,
+                             int w, int h, const orc_params *prm, const int16_t *centers,
+                             pix *rec_y, pix *rec_u, pix *rec_v, int rec_stride, int rec_cstride,
+                             orc_cu_rec *cu, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v, int32_t *me_dump, uint64_t *est)
+{
+    const int reach = search_reach(centers, ((w + ORC_CTU - 1) / ORC_CTU) * ((h + ORC_CTU - 1) / ORC_CTU), prm);
+    if (reach <= ORC_PAD) {
+        analyze_inter_frame_padded(src_y, src_u, src_v, src_stride, src_cstride, ref_y, ref_u, ref_v, ref_stride, ref_cstride, w, h, prm, centers,
+                                   rec_y, rec_u, rec_v, rec_stride, rec_cstride, cu, coef_y, coef_u, coef_v, me_dump, est);
+        return;
+    }
+    wide_ref r;
+    widen_ref(&r, ref_y, ref_u, ref_v, ref_stride, ref_cstride, w, h, reach);
+    analyze_inter_frame_padded(src_y, src_u, src_v, src_stride, src_cstride, r.org[0], r.org[1], r.org[2], r.stride, r.cstride, w, h, prm, centers,
+                               rec_y, rec_u, rec_v, rec_stride, rec_cstride, cu, coef_y, coef_u, coef_v, me_dump, est);
+    free_ref(&r);
+}
 
 /* ================================================================================================
  * K1 + K3 : B picture (two reference pictures, one per list)
@@ -1043,7 +1096,7 @@ static void refine_fraction(const pix *src_y, int src_stride, const pix *ref_y, 
     }
 }
 
-void orc_analyze_b_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
+static void analyze_b_frame_padded(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
                          const pix *ref0_y, const pix *ref0_u, const pix *ref0_v, const pix *ref1_y, const pix *ref1_u, const pix *ref1_v,
                          int ref_stride, int ref_cstride, int w, int h, const orc_params *prm, const int16_t *centers0, const int16_t *centers1,
                          pix *rec_y, pix *rec_u, pix *rec_v, int rec_stride, int rec_cstride,
@@ -1149,6 +1202,26 @@ void orc_analyze_b_frame(const pix *src_y, const pix *src_u, const pix *src_v, i
         }
     free(sad8);
     if (est) *est = estimate_bits(cu, coef_y, coef_u, coef_v, w, h, centers0);
+}
+void orc_analyze_b_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
+                         const pix *ref0_y, const pix *ref0_u, const pix *ref0_v, const pix *ref1_y, const pix *ref1_u, const pix *ref1_v,
+                         int ref_stride, int ref_cstride, int w, int h, const orc_params *prm, const int16_t *centers0, const int16_t *centers1,
+                         pix *rec_y, pix *rec_u, pix *rec_v, int rec_stride, int rec_cstride,
+                         orc_cu_rec *cu, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v, int32_t *me_dump0, int32_t *me_dump1, uint64_t *est)
+{
+    const int n_ctu = ((w + ORC_CTU - 1) / ORC_CTU) * ((h + ORC_CTU - 1) / ORC_CTU);
+    const int r0 = search_reach(centers0, n_ctu, prm), r1 = search_reach(centers1, n_ctu, prm), reach = r0 > r1 ? r0 : r1;     /* (a B picture has no pre-search of its own) */
+    if (reach <= ORC_PAD) {
+        analyze_b_frame_padded(src_y, src_u, src_v, src_stride, src_cstride, ref0_y, ref0_u, ref0_v, ref1_y, ref1_u, ref1_v, ref_stride, ref_cstride, w, h, prm,
+                               centers0, centers1, rec_y, rec_u, rec_v, rec_stride, rec_cstride, cu, coef_y, coef_u, coef_v, me_dump0, me_dump1, est);
+        return;
+    }
+    wide_ref a, b;
+    widen_ref(&a, ref0_y, ref0_u, ref0_v, ref_stride, ref_cstride, w, h, reach);
+    widen_ref(&b, ref1_y, ref1_u, ref1_v, ref_stride, ref_cstride, w, h, reach);
+    analyze_b_frame_padded(src_y, src_u, src_v, src_stride, src_cstride, a.org[0], a.org[1], a.org[2], b.org[0], b.org[1], b.org[2], a.stride, a.cstride, w, h, prm,
+                           centers0, centers1, rec_y, rec_u, rec_v, rec_stride, rec_cstride, cu, coef_y, coef_u, coef_v, me_dump0, me_dump1, est);
+    free_ref(&a); free_ref(&b);
 }
 
 /* ================================================================================================

@@ -115,7 +115,10 @@ int  orc_mvd_bits(int d);
 void orc_pad_plane(pix *p, int stride, int w, int h, int pad);
 
 /* ---- frame-level stages: the definition of what each HIP stage must output ---- */
-/* K1+K3: inter (P) frame.  ref_* are padded planes (ORC_PAD / ORC_PAD/2); rec_* receive the pre-deblock
+/* K1+K3: inter (P) frame.  ref_* are padded planes: they MUST carry a border of exactly ORC_PAD luma / ORC_PAD/2 chroma samples of
+ * replicated edge on every side, readable at those offsets from the plane origins.  Where centres + me_range reach further out (e.g. +-56 with
+ * me_range 32), the function analyses against wider copies it makes from them, reading the border out to ORC_PAD: every sample beyond the
+ * picture equals the nearest picture sample, as the kernels' clamped reads give.  rec_* receive the pre-deblock
  * reconstruction; coef_* receive levels in TU-local raster at picture coordinates. */
 void orc_analyze_inter_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride,
                              const pix *ref_y, const pix *ref_u, const pix *ref_v, int ref_stride, int ref_cstride,
@@ -124,7 +127,7 @@ void orc_analyze_inter_frame(const pix *src_y, const pix *src_u, const pix *src_
                              orc_cu_rec *cu, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v,
                              int32_t *me_dump /* optional: per CTU 21*(mvx,mvy,cost) after integer search, or NULL */,
                              uint64_t *est /* optional: picture rate estimate in 1/16 bit */);
-/* K1+K3 for a B picture between two anchors: ref0_* = the anchor before it in display order (list 0), ref1_* = the one after it (list 1), both padded.
+/* K1+K3 for a B picture between two anchors: ref0_* = the anchor before it in display order (list 0), ref1_* = the one after it (list 1), both padded as for orc_analyze_inter_frame (the same ORC_PAD contract).
  * The quadtree is decided on the list-0 search exactly as in a P picture; every CU of the tree then also refines its list-1 vector and tries the
  * bi-prediction of the two refined vectors (8.5.3.3.4.2 default weighted average of the 14-bit predictions), and takes the cheapest of
  * SATD << 4 + lambda * (mvd bits + inter_pred_idc bins): list 0 (2 bins), list 1 (2), both (1); ties in that order.  centers0 / centers1: search

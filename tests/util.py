@@ -1,13 +1,16 @@
 """Shared helpers of the test-suite: deterministic synthetic pictures and array plumbing between the oracle
 (uint16 containers) and the product C ABI (uint8 planes at 8 bit, uint16 at 10 bit)."""
 import ctypes as C
+import functools
 import os
 import subprocess
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import hevc_analysis as A
 
 ROOT = Path(__file__).resolve().parents[1]
 EMU_DIR = ROOT / "tests" / "emu"
@@ -318,3 +321,200 @@ def idr_positions(n, keyint, lanes=4, balance=True):
             at += (m // g + (j < m % g)) if balance else keyint
         pos += m
     return out
+
+
+# ================================================================ cases of the decision audit (tests/test_analysis_independent.py on the CPU, tests/test_gpu_analysis_independent.py on the device)
+def flat_pair(w, h, bd):
+    v = 100 << (bd - 8)
+    f = O.Frame(np.full((h, w), v), np.full((h // 2, w // 2), v), np.full((h // 2, w // 2), v))
+    return f, f.copy()
+
+
+def periodic_pair(w, h, bd, low_bits=False):
+    """period 4 in both directions, the source two samples ahead of the reference: SAD 0 at every d = 2 mod 4, and (-2, -2), (2, -2), (-2, 2), (2, 2) cost the
+    same bits.  low_bits (10 bit): every sample of both pictures gets random two low bits, which the search must not see."""
+    f, g = np.array([20, 90, 200, 140]), np.array([0, 30, 10, 50])
+    yy, xx = np.mgrid[0:h + 2, 0:w + 2]
+    big = (f[xx % 4] + g[yy % 4]) << (bd - 8)
+    ref, cur = big[:h, :w].copy(), big[2:, 2:].copy()
+    if low_bits:
+        rng = np.random.default_rng(4)
+        ref, cur = (ref & ~3) | rng.integers(0, 4, ref.shape), (cur & ~3) | rng.integers(0, 4, cur.shape)
+    c = np.full((h // 2, w // 2), 128 << (bd - 8))
+    return O.Frame(cur, c, c), O.Frame(ref, c, c)
+
+
+SIZES = ((64, 64), (136, 72), (72, 104))
+RANGES = (8, 12, 15, 32)
+Case = namedtuple("Case", "id w h bd R kind shift centres pre_search")
+
+
+@functools.lru_cache(maxsize=None)
+def _base(w, h, bd):
+    return synth_frame(h + 256, w + 256, 5, bit_depth=bd)
+
+
+def crop(w, h, bd, ox, oy):
+    """a window of one larger synthetic picture: crop(s)(x) = crop(0)(x + s), a pure translation"""
+    b = _base(w, h, bd)
+    return O.Frame(b.y[128 + oy:128 + oy + h, 128 + ox:128 + ox + w].copy(), b.u[64 + oy // 2:64 + (oy + h) // 2, 64 + ox // 2:64 + (ox + w) // 2].copy(),
+                   b.v[64 + oy // 2:64 + (oy + h) // 2, 64 + ox // 2:64 + (ox + w) // 2].copy())
+
+
+def _search_cases():
+    """The cross product (kind x R x size x bit depth) is SAMPLED, not run in full: a case's size and bit depth follow from its kind, its R and its index
+    within that (kind, R) group alone, so adding or removing a case never moves another one, and every (R, size, bit depth) triple occurs."""
+    out, count = [], {}
+    kind_no = {"corner": 0, "extra": 1, "past": 2, "flat": 3, "periodic": 4, "lowbits": 5, "centres": 0, "presearch": 3}
+
+    def add(kind, R, shift, centres=None, pre=0):
+        i = count.get((kind, R), 0)
+        count[(kind, R)] = i + 1
+        n = i + kind_no[kind] + RANGES.index(R)
+        (w, h), bd = SIZES[n % 3], 10 if kind == "lowbits" else (8, 10)[(n // 3 + i) % 2]
+        out.append(Case(f"{kind}-R{R}-{w}x{h}-{bd}bit-{shift[0]}_{shift[1]}", w, h, bd, R, kind, shift, centres, pre))
+    for R in RANGES:
+        last = -R + A.search_span(R)[0] - 1
+        for s in ((-R, -R), (last, -R), (-R, R), (last, R)):
+            add("corner", R, s)
+        for dx in range(R + 1, last + 1):                                     # the columns the row is widened by: must be found
+            add("extra", R, (dx, 1))
+        add("past", R, (last + 1, 0))                                         # one position past the last column: must not be found
+        for shift in ((0, 0), (0, 0)):                                        # the tie pictures of the pinning tests, twice per R: two (size, bit depth) each
+            add("flat", R, shift)
+            add("periodic", R, shift)
+            add("lowbits", R, shift)
+    for R, shifts in ((32, ((-50, 44), (60, -58), (-80, -70), (70, 80), (-50, -60), (40, 52))), (15, ((-50, -60), (44, 50))), (8, ((40, 52),))):
+        for s in shifts:
+            add("centres", R, s, centres="corners")                           # explicit centres up to +-56: with R = 32 the window leaves the 80-sample border
+    for R in RANGES:
+        add("presearch", R, (38, -22), pre=1)
+        add("presearch", R, (-56, 56), pre=1)
+    out.append(Case("corner-R15-136x72-8bit-16_15", 136, 72, 8, 15, "corner", (16, 15), None, 0))      # the one triple the dealing above leaves out
+    assert {(c.R, c.w, c.bd) for c in out} == {(R, w, bd) for R in RANGES for w, _ in SIZES for bd in (8, 10)} and len({c.id for c in out}) == len(out)
+    return out
+
+
+SEARCH_CASES = _search_cases()
+B_CASE = Case("b-R12-136x72-8bit", 136, 72, 8, 12, "b", ((5, -3), (-6, 4)), None, 0)
+
+
+def case_pictures(c):
+    """(current picture, reference picture)"""
+    if c.kind == "flat":
+        return flat_pair(c.w, c.h, c.bd)
+    if c.kind in ("periodic", "lowbits"):
+        return periodic_pair(c.w, c.h, c.bd, low_bits=c.kind == "lowbits")
+    return crop(c.w, c.h, c.bd, *c.shift), crop(c.w, c.h, c.bd, 0, 0)
+
+
+def case_centres(c, salt=0):
+    """explicit centres of a case, or None"""
+    if c.centres is None:
+        return None
+    rng = np.random.default_rng(n_ctus(c.w, c.h) + salt)
+    pool = np.array([(-56, -56), (56, 56), (-56, 56), (56, -56), (-52, 44), (0, -56), (40, 12)], np.int16)
+    cen = pool[rng.integers(0, len(pool), n_ctus(c.w, c.h))]
+    cen[0] = (-56, -56)                                                       # CTU 0 at R = 32: reads from -88 on both axes
+    cen[-1] = (56, 56)
+    return np.ascontiguousarray(cen)
+
+
+def params_pair(qp, bd, R, **knobs):
+    """(oracle parameters, product parameters) for one QP, both from the product's mihevc_cost_params_for_qp"""
+    from hevc_amd import _lib
+    cp = _lib.cost_params(qp, bd, R)
+    prm = O.Params(cp.qp, cp.qp_c, cp.bit_depth, cp.lambda_sad_q4, cp.lambda_q4, cp.me_range)
+    for k, v in knobs.items():
+        setattr(cp, k, v)
+        setattr(prm, k, v)
+    return prm, cp
+
+
+def audit_search(c, cur, ref, lam, centres):
+    """the model's dump of one case; with pre_search the centres are the model's own too"""
+    if c.pre_search:
+        centres = A.pre_search(A.lowres(cur.y, c.bd), A.lowres(ref.y, c.bd))
+    return A.integer_search(cur.y, ref.y, c.bd, c.R, lam, centres)
+
+
+def check_planted(c, me, lam):
+    """what the case was built for, on the model's own answer"""
+    if c.kind not in ("corner", "extra", "past"):
+        return
+    hit = (me[:, 5:, 0] == 4 * c.shift[0]) & (me[:, 5:, 1] == 4 * c.shift[1])
+    if c.kind == "past":
+        assert not (me[:, :, 0] == 4 * c.shift[0]).any(), "a vector outside the candidate set"
+    else:
+        bits = A.mvd_bits(4 * c.shift[0]) + A.mvd_bits(4 * c.shift[1])
+        assert (me[:, 5:, 2][hit] == lam * bits).any(), "the planted displacement is in the candidate set and matches exactly: it must win"
+
+
+def first_diff(a, b):
+    i = np.argwhere((a != b).any(axis=-1))
+    return f"{len(i)} nodes differ, first (ctu, node) {i[0].tolist()}: {a[tuple(i[0])].tolist()} vs {b[tuple(i[0])].tolist()}" if len(i) else "equal"
+
+
+def b_case_pictures():
+    c = B_CASE
+    return crop(c.w, c.h, c.bd, 5, -3), crop(c.w, c.h, c.bd, 0, 0), crop(c.w, c.h, c.bd, 11, -7)
+
+
+def b_case_centres():
+    return np.tile(np.array([(-4, 2)], np.int16), (n_ctus(B_CASE.w, B_CASE.h), 1))
+
+
+SAO_QPS = (22, 32, 42)
+SaoCase = namedtuple("SaoCase", "id w h bd qp content")
+SAO_CASES = [SaoCase(f"{w}x{h}-{bd}bit-qp{qp}", w, h, bd, qp, "synth") for (w, h) in SIZES for bd in (8, 10) for qp in SAO_QPS]
+_env = next(e for e in ENVELOPE_STAGE_CASES if e[5] == "rails" and e[3] == 10 and e[2] == 45)
+SAO_CASES.append(SaoCase("rails-%dx%d-%dbit-qp%d" % (_env[0], _env[1], _env[3], _env[2]), _env[0], _env[1], _env[3], _env[2], "rails"))
+# the encoder's own pictures never made chroma take band offsets or the 45-degree class: a hand-made SAO input that does (planted_sao_input)
+SAO_CASES += [SaoCase(f"planted-64x64-{bd}bit-qp27", 64, 64, bd, 27, "planted") for bd in (8, 10)]
+CODED_SAO_CASES = [c for c in SAO_CASES if c.content != "planted"]
+
+
+def sao_case_sources(c):
+    """(I picture, P picture): the pictures of the search cases (a translation by (3, 1)), or envelope content with samples at both rails"""
+    if c.content == "synth":
+        return crop(c.w, c.h, c.bd, 0, 0), crop(c.w, c.h, c.bd, 3, 1)
+    return tuple(envelope_frame(c.content, c.h, c.w, c.bd, 3, shift=(2 * i, i)) for i in range(2))
+
+
+def planted_sao_input(c):
+    """(source, "deblocked"): luma untouched.  Chroma CTB 0: Cb 3 and Cr 2 grey levels too low everywhere: band offsets.  Chroma CTB 1: the source is a ramp
+    along x + y, the deblocked picture adds +-2 of noise: the two neighbours of the 45-degree class share the ramp's value, so that class alone sees the noise as
+    minima and maxima; to every other class the ramp makes each sample a monotone step (category 0)."""
+    sc = 1 << (c.bd - 8)
+    src = crop(c.w, c.h, c.bd, 0, 0)
+    yy, xx = np.mgrid[0:16, 0:16]
+    ramp = (8 * (xx + yy)) * sc
+    src.u[0:16, 16:32], src.v[0:16, 16:32] = ramp, ramp[::-1, ::-1]
+    d = src.copy()
+    d.u[0:16, 0:16] -= 3 * sc
+    d.v[0:16, 0:16] -= 2 * sc
+    rng = np.random.default_rng(8)
+    d.u[0:16, 16:32] += (2 * sc * rng.integers(0, 3, (16, 16))).astype(np.uint16)
+    d.v[0:16, 16:32] += (2 * sc * rng.integers(0, 3, (16, 16))).astype(np.uint16)
+    return src, d
+
+
+def planes3(f):
+    return f.y, f.u, f.v
+
+
+def sao_kinds(sp):
+    """what a parameter array exercises: 'off', 'band', 'edge0'..'edge3', per luma / chroma"""
+    out = set()
+    for i in range(2):
+        for t, k in zip(sp["type"][:, i], sp["eo_class"][:, i]):
+            out.add(("luma ", "chroma ")[i] + ("off", "band", "edge%d" % k)[t])
+    return out
+
+
+ALL_SAO_KINDS = {p + k for p in ("luma ", "chroma ") for k in ("off", "band", "edge0", "edge1", "edge2", "edge3")}
+
+
+def sao_diff(a, b):
+    i = np.nonzero([x.tobytes() != y.tobytes() for x, y in zip(a, b)])[0]
+    return f"{len(i)} CTUs differ, first {i[0]}: {a[i[0]]} vs {b[i[0]]}" if len(i) else "equal"
