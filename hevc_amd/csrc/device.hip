@@ -58,18 +58,11 @@ template <typename T> __global__ __launch_bounds__(NT, 3) void k_inter_ctu_b(con
     const int ctu = xcd_remap(blockIdx.x, n_ctu);
     if (ctu >= n_ctu) return;
     const InterArgs<T> &a = args[blockIdx.y];
-    const int R = a.prm.me_range;
+    const InterBLds l = inter_b_lds<T>(a.prm.me_range);
     InterShared<T> &s = *reinterpret_cast<InterShared<T> *>(smem);
-    size_t off = round16(sizeof(InterShared<T>));
-    T *wy = reinterpret_cast<T *>(smem + off);
-    off += round16(((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T));
-    T *wu = reinterpret_cast<T *>(smem + off);
-    off += round16(((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T));
-    T *wv = reinterpret_cast<T *>(smem + off);
-    off += round16(((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T));
-    BiShared *b = reinterpret_cast<BiShared *>(smem + off);
     GpuExec ex;
-    inter_ctu_program<T, GpuExec, true>(ex, s, wy, wu, wv, a, ctu, b);
+    inter_ctu_program<T, GpuExec, true>(ex, s, reinterpret_cast<T *>(smem + l.y), reinterpret_cast<T *>(smem + l.u), reinterpret_cast<T *>(smem + l.v), a, ctu,
+                                        reinterpret_cast<BiShared *>(smem + l.bi));
 }
 
 // stage A of the intra pictures: every CTU of every picture in flight plans its quadtree and modes on the source picture (kernels/intra.h);
@@ -413,8 +406,7 @@ template <typename T> hipError_t launch_inter_ctu(hipStream_t st, const InterArg
 
 template <typename T> hipError_t launch_inter_ctu_b(hipStream_t st, const InterArgs<T> *d_args, int n_ctu, int batch, int R)
 {
-    size_t smem = round16(sizeof(InterShared<T>)) + round16(((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T)) +
-                  2 * round16(((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T)) + round16(sizeof(BiShared));
+    const size_t smem = inter_b_lds<T>(R).bytes;
     hipError_t e = ensure_smem(k_inter_ctu_b<T>, smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((n_ctu + 7) >> 3) << 3), (unsigned)batch);

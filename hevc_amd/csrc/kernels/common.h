@@ -252,13 +252,17 @@ DEV void transpose_bytes4(const uint32_t (&r)[4], uint32_t (&c)[4])
 }
 
 // true when the predicate holds in every ACTIVE lane of the wave: lets a function pick a cheaper, value-identical path without diverging (a wave executes both sides of a branch its
-// lanes disagree on).  Stepped on the CPU a lane stands alone; the paths give the same values, so any choice is right there.
+// lanes disagree on).  Stepped on the CPU a lane stands alone; the paths give the same values, so any choice is right there: with g_emu_mixed_wave set
+// (tests only) the lane behaves as one of a wave whose lanes disagree and takes the general path whatever its own predicate.
+#if !MIHEVC_GPU
+inline bool g_emu_mixed_wave = false;
+#endif
 DEV bool wave_all(bool p)
 {
 #if MIHEVC_GPU
     return __all(p) != 0;
 #else
-    return p;
+    return p && !g_emu_mixed_wave;
 #endif
 }
 
@@ -386,37 +390,8 @@ DEV void store4(int16_t *p, int v0, int v1, int v2, int v3)
     store_u32_aligned(p, ((uint32_t)v0 & 0xffffu) | (uint32_t)v1 << 16);
     store_u32_aligned(p + 2, ((uint32_t)v2 & 0xffffu) | (uint32_t)v3 << 16);
 }
-// 15 consecutive samples base[idx .. idx+14] from an LDS image whose `base` is 4-byte aligned, fetched with aligned
+// 8 consecutive samples base[idx .. idx+7] from an LDS image whose `base` is 4-byte aligned, fetched with aligned
 // dword reads + v_alignbyte (unaligned ds_read_b64 stalls: SQ_LDS_UNALIGNED_STALL, profiles/r01_a_first)
-DEV void load_row15(const uint8_t *base, int idx, int (&px)[15])
-{
-    const int off = idx & 3;
-    const uint8_t *p = base + (idx - off);
-    uint32_t d[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) d[k] = load_u32_aligned(p + 4 * k);
-    uint32_t r[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) r[k] = align_bytes(d[k + 1], d[k], off);
-#pragma unroll
-    for (int i = 0; i < 15; i++) px[i] = (int)((r[i >> 2] >> (8 * (i & 3))) & 255);
-}
-DEV void load_row15(const uint16_t *base, int idx, int (&px)[15])
-{
-    const int off = idx & 1;
-    const uint16_t *p = base + (idx - off);
-    uint32_t d[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) d[k] = load_u32_aligned(p + 2 * k);
-    uint32_t r[8];
-#pragma unroll
-    for (int k = 0; k < 7; k++) r[k] = align_bytes(d[k + 1], d[k], 2 * off);
-    r[7] = align_bytes(0, d[7], 2 * off);
-#pragma unroll
-    for (int i = 0; i < 15; i++) px[i] = (int)((r[i >> 1] >> (16 * (i & 1))) & 65535);
-}
-
-// 8 consecutive samples base[idx .. idx+7], same aligned-read scheme
 DEV void load_row8(const uint8_t *base, int idx, int (&px)[8])
 {
     const int off = idx & 3;

@@ -416,6 +416,20 @@ HDI int mc_win_y(int R) { return (32 + 2 * (R + 3) + 8 + 3) & ~3; }
 HDI int mc_win_y_stride(int R) { return mc_win_y(R) + 4; }
 HDI int mc_win_c(int R) { return (16 + (R + 3) + 8 + 3) & ~3; }
 HDI int mc_win_c_stride(int R) { return mc_win_c(R) + 4; }
+// a window's image in LDS (16 samples of slack: the aligned dword reads of a row's filter reach past its last sample)
+template <typename T> HDI size_t mc_win_y_bytes(int R) { return ((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T); }
+template <typename T> HDI size_t mc_win_c_bytes(int R) { return ((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T); }
+HDI constexpr size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// per-CTU state of the list-1 / bi-prediction part of a B picture's CTU program (behind the windows in LDS; P pictures do not carry it)
+struct BiShared {
+    int mx0[21], my0[21];        // refined list-0 vectors (InterShared::mvx / mvy go on to hold list 1)
+    unsigned c0[21], cb[21];     // list-0 cost, bi-prediction SATD sum
+    uint8_t mode[21];            // 0: list 0, 1: list 1, 2: both
+    uint8_t tile_mode[16];
+    int tile_mv1x[16], tile_mv1y[16];
+    alignas(16) int16_t p0[1536];    // the 14-bit list-0 prediction of the CTU (Y, U, V as InterShared::pred), kept while the windows hold list 1
+};
 
 // Dynamic LDS of k_inter_ctu (P pictures): InterShared, and the luma, Cb and Cr windows, byte offsets from its start.  rs.scratch is idle from the
 // end of the fractional search until the residual is formed, and the windows are read only before that (motion compensation is their last reader,
@@ -424,221 +438,158 @@ HDI int mc_win_c_stride(int R) { return mc_win_c(R) + 4; }
 // 8 bit at me_range 15: luma and Cb inside, Cr behind.
 struct InterLds { size_t y, u, v, bytes; };
 template <typename T> HDI constexpr size_t inter_win_in() { return offsetof(InterShared<T>, rs) + offsetof(ResidualShared, scratch) + 4 * (size_t)FRAC_SCRATCH; }
-template <typename T> HDI constexpr size_t inter_win_out() { return (sizeof(InterShared<T>) + 15) & ~(size_t)15; }
+template <typename T> HDI constexpr size_t inter_win_out() { return align16(sizeof(InterShared<T>)); }
 template <typename T> HDI InterLds inter_lds(int R)
 {
-    const size_t n[3] = {((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16) * sizeof(T), ((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T),
-                         ((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16) * sizeof(T)};
+    const size_t n[3] = {mc_win_y_bytes<T>(R), mc_win_c_bytes<T>(R), mc_win_c_bytes<T>(R)};
     const size_t hi = offsetof(InterShared<T>, rs) + offsetof(ResidualShared, scratch) + sizeof(ResidualShared::scratch);
     size_t in = inter_win_in<T>(), out = inter_win_out<T>(), at[3];
     for (int i = 0; i < 3; i++) {
-        const size_t r = (n[i] + 15) & ~(size_t)15;
+        const size_t r = align16(n[i]);
         if (in + r <= hi) { at[i] = in; in += r; } else { at[i] = out; out += r; }
     }
     return InterLds{at[0], at[1], at[2], out};
 }
-
-// quarter-sample luma prediction of one 8x8 tile from the LDS window (8.5.3.3.3.1; the general 2-D form with the
-// {0,0,0,64,0,0,0,0} tap set for a zero fraction is exact for every case).  p00 = window sample at the tile's
-// integer position (element index i00 into the 4-byte aligned window image `win`).  When diff_src != nullptr returns the 8x8 Hadamard SATD of (src - pred), else writes pred.
-template <typename T>
-DEV int luma_tile(const T *win, int i00, int ws, int fx, int fy, int bit_depth, const T *diff_src, int src_stride, T *pred_out, int pred_stride)
+// Dynamic LDS of k_inter_ctu_b (B pictures): rs.scratch stays the bi-prediction trial's while the windows are read, so InterShared, the three windows
+// and BiShared lie one behind the other
+struct InterBLds { size_t y, u, v, bi, bytes; };
+template <typename T> HDI InterBLds inter_b_lds(int R)
 {
-    const int8_t *tx = g_tab.luma_tap[fx], *ty = g_tab.luma_tap[fy];
-    const int shift1 = bit_depth - 8, shift3 = 14 - bit_depth, maxv = (1 << bit_depth) - 1;
-    int acc[8][8];
+    InterBLds l;
+    l.y = inter_win_out<T>();
+    l.u = l.y + align16(mc_win_y_bytes<T>(R));
+    l.v = l.u + align16(mc_win_c_bytes<T>(R));
+    l.bi = l.v + align16(mc_win_c_bytes<T>(R));
+    l.bytes = l.bi + align16(sizeof(BiShared));
+    return l;
+}
+
+// ------------------------------------------------------------------------------------------ fractional-sample interpolation (8.5.3.3.3)
+// The eight taps of luma fraction f in the forms the dot products take: eight signed bytes in two dwords (v_dot4_i32_i8), or four (even, odd)
+// int16 pairs (v_dot2_i32_i16).  A row of 8-bit samples is filtered with the first, a row of 16-bit samples with the second.
+struct TapBytes { uint32_t lo, hi; };
+struct TapPairs { uint32_t p[4]; };
+DEV TapBytes tap_bytes(int f) { return TapBytes{load_u32(&g_tab.luma_tap[f][0]), load_u32(&g_tab.luma_tap[f][4])}; }
+DEV TapPairs tap_pairs(int f)
+{
+    TapPairs t;
 #pragma unroll
-    for (int j = 0; j < 8; j++)
+    for (int k = 0; k < 4; k++) t.p[k] = pack_lo16(g_tab.luma_tap[f][2 * k], g_tab.luma_tap[f][2 * k + 1]);
+    return t;
+}
+template <typename T> DEV auto row_taps(int f)
+{
+    if constexpr (sizeof(T) == 1) return tap_bytes(f); else return tap_pairs(f);
+}
+
+// The horizontal 8-tap filter of one window row: the four 14-bit-domain values whose first tap sits on window element idx (3 left of the first
+// output's integer sample).  8 bit: 8 v_dot4_i32_i8 on byte-realigned dwords.  Samples are biased to signed bytes (p - 128); the taps of every fraction
+// sum to 64, so the bias comes back as the constant 128 * 64 (the fractional search was 72 % of k_inter_ctu, VALU bound on 8 multiply-adds per output:
+// profiles/r01 ablation).  The window image is 4-byte aligned and read with aligned dwords only.
+DEV void luma_row4(const uint8_t *win, int idx, const TapBytes &t, int, int (&hv)[4])
+{
+    const int off = idx & 3;
+    const uint8_t *p = win + (idx - off);
+    uint32_t d[4], q[3];
 #pragma unroll
-        for (int i = 0; i < 8; i++) acc[j][i] = 0;
-    for (int r = 0; r < 15; r++) {                 // intermediate row r corresponds to reference row r - 3
-        int px[15];
-        load_row15(win, i00 + (r - 3) * ws - 3, px);
-        int hv[8];
+    for (int k = 0; k < 4; k++) d[k] = load_u32_aligned(p + 4 * k);
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int v = 0;
+    for (int k = 0; k < 3; k++) q[k] = align_bytes(d[k + 1], d[k], off) ^ 0x80808080u;      // bytes 4k..4k+3 of the row, signed
+    hv[0] = dot4_i8(q[0], t.lo, dot4_i8(q[1], t.hi, 128 * 64));
 #pragma unroll
-            for (int k = 0; k < 8; k++) v += tx[k] * px[i + k];
-            hv[i] = v >> shift1;
-        }
+    for (int i = 1; i < 4; i++) hv[i] = dot4_i8(align_bytes(q[1], q[0], i), t.lo, dot4_i8(align_bytes(q[2], q[1], i), t.hi, 128 * 64));
+}
+// 16 bit (Main10): samples are already int16 pairs in the window's dwords, so an output is 4 v_dot2_i32_i16 (odd outputs on dwords realigned by one
+// sample), shifted down to 14 bits (shift1 = bit_depth - 8)
+DEV void luma_row4(const uint16_t *win, int idx, const TapPairs &t, int shift1, int (&hv)[4])
+{
+    const int off = idx & 1;
+    const uint16_t *p = win + (idx - off);
+    uint32_t d[7], e[6], o[5];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            int k = r - j;
-            if (k >= 0 && k < 8) {
-                int t = ty[k];
+    for (int k = 0; k < 7; k++) d[k] = load_u32_aligned(p + 2 * k);
 #pragma unroll
-                for (int i = 0; i < 8; i++) acc[j][i] += t * hv[i];
+    for (int k = 0; k < 6; k++) e[k] = align_bytes(d[k + 1], d[k], 2 * off);     // samples (2k, 2k+1) of the row
+#pragma unroll
+    for (int k = 0; k < 5; k++) o[k] = align_bytes(e[k + 1], e[k], 2);           // samples (2k+1, 2k+2)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) v = dot2_i16((i & 1) ? o[(i >> 1) + k] : e[(i >> 1) + k], t.p[k], v);
+        hv[i] = v >> shift1;
+    }
+}
+
+// The sample primitives of motion compensation: the 14-bit intermediate predictions (predSamplesLX, before the weighting of 8.5.3.3.4.2) of four
+// horizontally adjacent luma samples starting at window element i00 (8.5.3.3.3.1; the general 2-D form with the {0,0,0,64,0,0,0,0} tap set for a
+// zero fraction is exact for every case), and of one chroma sample (8.5.3.3.3.2)
+template <typename T> DEV void luma_quad14(const T *win, int i00, int ws, int fx, int fy, int bit_depth, int (&out)[4])
+{
+    const auto tx = row_taps<T>(fx);
+    const int8_t *ty = g_tab.luma_tap[fy];
+    int acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        int hv[4];
+        luma_row4(win, i00 + (r - 3) * ws - 3, tx, bit_depth - 8, hv);
+        const int t = ty[r];
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[i] += t * hv[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) out[i] = acc[i] >> 6;
+}
+template <typename T> DEV int chroma_sample14(const T *p00, int ws, int fx, int fy, int bit_depth)
+{
+    const int8_t *tx = g_tab.chroma_tap[fx], *ty = g_tab.chroma_tap[fy];
+    const int shift1 = bit_depth - 8;
+    int acc = 0;
+    for (int r = 0; r < 4; r++) {
+        const T *row = p00 + (r - 1) * ws - 1;
+        int v = tx[0] * row[0] + tx[1] * row[1] + tx[2] * row[2] + tx[3] * row[3];
+        acc += ty[r] * (v >> shift1);
+    }
+    return acc >> 6;
+}
+// 8.5.3.3.4.2 default weighted sample prediction: one list, or the average of both
+DEV int weighted_uni(int p, int bit_depth) { const int sh = 14 - bit_depth; return clip3(0, (1 << bit_depth) - 1, (p + (1 << (sh - 1))) >> sh); }
+DEV int weighted_bi(int p0, int p1, int bit_depth) { const int sh = 15 - bit_depth; return clip3(0, (1 << bit_depth) - 1, (p0 + p1 + (1 << (sh - 1))) >> sh); }
+
+// ---- fractional search, two lanes per (tile, candidate): each lane owns 4 of the tile's 8 columns (a lane with a whole tile keeps 64 accumulators + filter
+// state live, which spilled at 4 workgroups per CU, and leaves half of the workgroup idle).
+// The 8-tap column filter as 4 v_dot2_i32_i16 on row PAIRS of the horizontally filtered rows (|hv| < 2^15 for every fraction) instead of 8 quarter-rate
+// 32-bit multiplies: intermediate row r (reference row r - 3) and the one before it feed output row j with the taps (2k, 2k + 1) where r - 1 - j = 2k
+DEV void luma_col_pair(int r, const int (&hv)[4], int (&prev)[4], const TapPairs &ty, int (&acc)[8][4])
+{
+    if (r > 0) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t pr = pack_lo16(prev[i], hv[i]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = r - 1 - 2 * k;
+                if (j >= 0 && j < 8) acc[j][i] = dot2_i16(pr, ty.p[k], acc[j][i]);
             }
         }
     }
-    const int off = 1 << (shift3 - 1);
 #pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int v = clip3(0, maxv, ((acc[j][i] >> 6) + off) >> shift3);
-            if (diff_src) acc[j][i] = (int)diff_src[j * src_stride + i] - v;
-            else pred_out[j * pred_stride + i] = (T)v;
-        }
-    return diff_src ? hadamard8_satd(acc) : 0;
+    for (int i = 0; i < 4; i++) prev[i] = hv[i];
 }
-
-// 8-bit specialisation of luma_tile: the horizontal 8-tap filter of one row is 16 v_dot4_i32_i8 on byte-realigned
-// dwords.  Samples are biased to signed bytes (p - 128); the taps of every fraction sum to 64, so the bias comes back
-// as the constant 128 * 64.  Results are identical to the generic form (the fractional search was 72 % of
-// k_inter_ctu, VALU bound on 8 multiply-adds per output: profiles/r01 ablation).
-DEV int luma_tile(const uint8_t *win, int i00, int ws, int fx, int fy, int bit_depth, const uint8_t *diff_src, int src_stride, uint8_t *pred_out,
-                  int pred_stride)
-{
-    const uint32_t tlo = load_u32(&g_tab.luma_tap[fx][0]), thi = load_u32(&g_tab.luma_tap[fx][4]);
-    // vertical taps as four (even, odd) int16 pairs: the 8-tap column filter is 4 v_dot2_i32_i16 on row PAIRS of the
-    // horizontally filtered samples (|hv| < 2^15 for every fraction) instead of 8 quarter-rate 32-bit multiplies
-    uint32_t typ[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) typ[m] = pack_lo16(g_tab.luma_tap[fy][2 * m], g_tab.luma_tap[fy][2 * m + 1]);
-    int acc[8][8], prev[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) acc[j][i] = 0;
-#pragma unroll
-    for (int r = 0; r < 15; r++) {
-        const int idx = i00 + (r - 3) * ws - 3, off = idx & 3;
-        const uint8_t *p = win + (idx - off);
-        uint32_t d[5], a[12];
-#pragma unroll
-        for (int k = 0; k < 5; k++) d[k] = load_u32_aligned(p + 4 * k);
-        uint32_t q[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) q[k] = align_bytes(d[k + 1], d[k], off) ^ 0x80808080u;      // bytes 4k..4k+3 of the row, signed
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            a[4 * k] = q[k];
-            a[4 * k + 1] = align_bytes(q[k + 1], q[k], 1);
-            a[4 * k + 2] = align_bytes(q[k + 1], q[k], 2);
-            a[4 * k + 3] = align_bytes(q[k + 1], q[k], 3);
-        }
-        int hv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) hv[i] = dot4_i8(a[i], tlo, dot4_i8(a[i + 4], thi, 128 * 64));
-        if (r > 0) {
-            // rows (r-1, r) feed output row j with taps (2m, 2m+1) where r - 1 - j = 2m
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const uint32_t pr = pack_lo16(prev[i], hv[i]);
-#pragma unroll
-                for (int m = 0; m < 4; m++) {
-                    const int j = r - 1 - 2 * m;
-                    if (j >= 0 && j < 8) acc[j][i] = dot2_i16(pr, typ[m], acc[j][i]);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) prev[i] = hv[i];
-    }
-    (void)bit_depth;
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int v = clip3(0, 255, ((acc[j][i] >> 6) + 32) >> 6);
-            if (diff_src) {
-                // source rows as two aligned dwords (the tile is 8-aligned in the CTU image): 64 single-byte LDS loads issued up
-                // front cost 64 VGPRs and pushed the kernel into scratch spills
-                const uint32_t w = load_u32_aligned(diff_src + j * src_stride + (i & 4));
-                acc[j][i] = (int)((w >> (8 * (i & 3))) & 255) - v;
-            } else pred_out[j * pred_stride + i] = (uint8_t)v;
-        }
-    return diff_src ? hadamard8_satd(acc) : 0;
-}
-
-// 16-bit specialisation (Main10): samples are already int16 pairs in the window's dwords, so the horizontal 8-tap filter is
-// 4 v_dot2_i32_i16 per output (odd outputs on dwords realigned by one sample), the column filter 4 v_dot2 on row pairs as in
-// the 8-bit form.  Intermediates stay below 2^15 (8.5.3.3.3: 14-bit intermediate precision), results equal the generic form.
-DEV int luma_tile(const uint16_t *win, int i00, int ws, int fx, int fy, int bit_depth, const uint16_t *diff_src, int src_stride, uint16_t *pred_out,
-                  int pred_stride)
-{
-    uint32_t txp[4], typ[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        txp[m] = pack_lo16(g_tab.luma_tap[fx][2 * m], g_tab.luma_tap[fx][2 * m + 1]);
-        typ[m] = pack_lo16(g_tab.luma_tap[fy][2 * m], g_tab.luma_tap[fy][2 * m + 1]);
-    }
-    const int shift1 = bit_depth - 8, shift3 = 14 - bit_depth, maxv = (1 << bit_depth) - 1;
-    int acc[8][8], prev[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) acc[j][i] = 0;
-#pragma unroll
-    for (int r = 0; r < 15; r++) {
-        const int idx = i00 + (r - 3) * ws - 3, off = idx & 1;
-        const uint16_t *p = win + (idx - off);
-        uint32_t d[9], e[8], o[7];
-#pragma unroll
-        for (int k = 0; k < 9; k++) d[k] = load_u32_aligned(p + 2 * k);
-#pragma unroll
-        for (int k = 0; k < 8; k++) e[k] = align_bytes(d[k + 1], d[k], 2 * off);     // samples (2k, 2k+1) of the row
-#pragma unroll
-        for (int k = 0; k < 7; k++) o[k] = align_bytes(e[k + 1], e[k], 2);           // samples (2k+1, 2k+2)
-        int hv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int v = 0;
-#pragma unroll
-            for (int m = 0; m < 4; m++) v = dot2_i16((i & 1) ? o[(i >> 1) + m] : e[(i >> 1) + m], txp[m], v);
-            hv[i] = v >> shift1;
-        }
-        if (r > 0) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const uint32_t pr = pack_lo16(prev[i], hv[i]);
-#pragma unroll
-                for (int m = 0; m < 4; m++) {
-                    const int j = r - 1 - 2 * m;
-                    if (j >= 0 && j < 8) acc[j][i] = dot2_i16(pr, typ[m], acc[j][i]);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) prev[i] = hv[i];
-    }
-    const int off3 = 1 << (shift3 - 1);
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            int v = clip3(0, maxv, ((acc[j][i] >> 6) + off3) >> shift3);
-            if (diff_src) acc[j][i] = (int)diff_src[j * src_stride + i] - v;
-            else pred_out[j * pred_stride + i] = (uint16_t)v;
-        }
-    return diff_src ? hadamard8_satd(acc) : 0;
-}
-
-// ---- fractional search, two lanes per (tile, candidate): each lane owns 4 of the tile's 8 columns.  The whole-tile form (luma_tile with a
-// source) kept 64 accumulators + filter state live and spilled at 4 workgroups per CU, and left half of the workgroup idle.
-// Difference (source - quarter-sample prediction, 8.5.3.3.3.1) of the 8 rows x 4 columns whose first integer sample is window element i00.
+// Difference (source - quarter-sample prediction, 8.5.3.3.3.1: weighted_uni of what luma_quad14 gives there) of the 8 rows x 4 columns whose first integer
+// sample is window element i00.  The one-pass paths and the general path are branches of one function: as functions of their own, behind a dispatcher, they
+// cost k_inter_ctu_b a step of occupancy at both bit depths (profiles/r07_a)
 DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int, const uint8_t *src, int src_stride, int (&m)[8][4])
 {
-    const uint32_t tlo = load_u32(&g_tab.luma_tap[fx][0]), thi = load_u32(&g_tab.luma_tap[fx][4]);
+    const TapBytes tx = tap_bytes(fx);
     // A zero fraction makes that direction's 8-tap filter the identity tap {0, 0, 0, 64, 0, 0, 0, 0}, and the general form below then multiplies by 64 and shifts by 6 again:
     // the same values come out of one filter pass.  Worth a branch only when the whole wave takes it (inter_ctu_program orders the ring so that a wave's two candidates
     // share their zero fraction: half of the first ring's waves, and the second ring's wherever the vectors stayed on whole samples).
     if (wave_all(fy == 0)) {          // horizontal filter only: rows 0 .. 7 of the block, no vertical pass
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const int idx = i00 + j * ws - 3, off = idx & 3;
-            const uint8_t *p = win + (idx - off);
-            uint32_t d[4], q[3];
-#pragma unroll
-            for (int k = 0; k < 4; k++) d[k] = load_u32_aligned(p + 4 * k);
-#pragma unroll
-            for (int k = 0; k < 3; k++) q[k] = align_bytes(d[k + 1], d[k], off) ^ 0x80808080u;
             int hv[4];
-            hv[0] = dot4_i8(q[0], tlo, dot4_i8(q[1], thi, 128 * 64));
-#pragma unroll
-            for (int i = 1; i < 4; i++) hv[i] = dot4_i8(align_bytes(q[1], q[0], i), tlo, dot4_i8(align_bytes(q[2], q[1], i), thi, 128 * 64));
+            luma_row4(win, i00 + j * ws - 3, tx, 0, hv);
             const uint32_t w = load_u32_aligned(src + j * src_stride);
 #pragma unroll
             for (int i = 0; i < 4; i++) m[j][i] = (int)((w >> (8 * i)) & 255) - clip3(0, 255, (hv[i] + 32) >> 6);      // ((64 hv >> 6) + 32) >> 6
@@ -646,7 +597,7 @@ DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int
         return;
     }
     if (wave_all(fx == 0)) {          // vertical filter only: the block's own 4 columns of rows -3 .. 11, no horizontal pass
-        const uint32_t vlo = load_u32(&g_tab.luma_tap[fy][0]), vhi = load_u32(&g_tab.luma_tap[fy][4]);
+        const TapBytes ty = tap_bytes(fy);
         const int idx = i00 - 3 * ws, off = idx & 3;
         uint32_t rows[15];           // four samples of every row, as signed bytes
 #pragma unroll
@@ -667,15 +618,13 @@ DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int
 #pragma unroll
             for (int i = 0; i < 4; i++) {       // output row j of column i: rows j .. j + 7 against the taps
                 const uint32_t lo = align_bytes(col[g + 1][i], col[g][i], sh), hi = align_bytes(col[g + 2][i], col[g + 1][i], sh);
-                const int v = dot4_i8(lo, vlo, dot4_i8(hi, vhi, 128 * 64));      // sum of tap x sample: what (64 x sample, filtered) >> 6 is
+                const int v = dot4_i8(lo, ty.lo, dot4_i8(hi, ty.hi, 128 * 64));      // sum of tap x sample: what (64 x sample, filtered) >> 6 is
                 m[j][i] = (int)((w >> (8 * i)) & 255) - clip3(0, 255, (v + 32) >> 6);
             }
         }
         return;
     }
-    uint32_t typ[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) typ[k] = pack_lo16(g_tab.luma_tap[fy][2 * k], g_tab.luma_tap[fy][2 * k + 1]);
+    const TapPairs ty = tap_pairs(fy);
     int acc[8][4], prev[4];
 #pragma unroll
     for (int j = 0; j < 8; j++)
@@ -683,30 +632,9 @@ DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int
         for (int i = 0; i < 4; i++) acc[j][i] = 0;
 #pragma unroll
     for (int r = 0; r < 15; r++) {
-        const int idx = i00 + (r - 3) * ws - 3, off = idx & 3;
-        const uint8_t *p = win + (idx - off);
-        uint32_t d[4], q[3];
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = load_u32_aligned(p + 4 * k);
-#pragma unroll
-        for (int k = 0; k < 3; k++) q[k] = align_bytes(d[k + 1], d[k], off) ^ 0x80808080u;      // bytes 4k..4k+3 of the row, signed
         int hv[4];
-        hv[0] = dot4_i8(q[0], tlo, dot4_i8(q[1], thi, 128 * 64));
-#pragma unroll
-        for (int i = 1; i < 4; i++) hv[i] = dot4_i8(align_bytes(q[1], q[0], i), tlo, dot4_i8(align_bytes(q[2], q[1], i), thi, 128 * 64));
-        if (r > 0) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint32_t pr = pack_lo16(prev[i], hv[i]);
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int j = r - 1 - 2 * k;
-                    if (j >= 0 && j < 8) acc[j][i] = dot2_i16(pr, typ[k], acc[j][i]);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) prev[i] = hv[i];
+        luma_row4(win, i00 + (r - 3) * ws - 3, tx, 0, hv);
+        luma_col_pair(r, hv, prev, ty, acc);
     }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -717,38 +645,14 @@ DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int
 }
 DEV void luma_half_diff(const uint16_t *win, int i00, int ws, int fx, int fy, int bit_depth, const uint16_t *src, int src_stride, int (&m)[8][4])
 {
-    uint32_t txp[4], typ[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        txp[k] = pack_lo16(g_tab.luma_tap[fx][2 * k], g_tab.luma_tap[fx][2 * k + 1]);
-        typ[k] = pack_lo16(g_tab.luma_tap[fy][2 * k], g_tab.luma_tap[fy][2 * k + 1]);
-    }
+    const TapPairs tx = tap_pairs(fx), ty = tap_pairs(fy);
     const int shift1 = bit_depth - 8, shift3 = 14 - bit_depth, maxv = (1 << bit_depth) - 1, off3 = 1 << (shift3 - 1);
-    // the horizontal 8-tap filter of intermediate row r (reference row r - 3): four 14-bit values
-    auto row_h = [&](int r, int (&hv)[4]) {
-        const int idx = i00 + (r - 3) * ws - 3, off = idx & 1;
-        const uint16_t *p = win + (idx - off);
-        uint32_t d[7], e[6], o[5];
-#pragma unroll
-        for (int k = 0; k < 7; k++) d[k] = load_u32_aligned(p + 2 * k);
-#pragma unroll
-        for (int k = 0; k < 6; k++) e[k] = align_bytes(d[k + 1], d[k], 2 * off);     // samples (2k, 2k+1) of the row
-#pragma unroll
-        for (int k = 0; k < 5; k++) o[k] = align_bytes(e[k + 1], e[k], 2);           // samples (2k+1, 2k+2)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            int v = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) v = dot2_i16((i & 1) ? o[(i >> 1) + k] : e[(i >> 1) + k], txp[k], v);
-            hv[i] = v >> shift1;
-        }
-    };
     // a zero fraction makes that direction's filter the identity (see the 8-bit form): one pass gives the same values; taken when the whole wave has it
     if (wave_all(fy == 0)) {          // horizontal only: the block's own 8 rows; 64 hv >> 6 = hv
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             int hv[4];
-            row_h(j + 3, hv);
+            luma_row4(win, i00 + j * ws - 3, tx, shift1, hv);
 #pragma unroll
             for (int i = 0; i < 4; i++) m[j][i] = (int)src[j * src_stride + i] - clip3(0, maxv, (hv[i] + off3) >> shift3);
         }
@@ -766,20 +670,8 @@ DEV void luma_half_diff(const uint16_t *win, int i00, int ws, int fx, int fy, in
         if (v_only) {
 #pragma unroll
             for (int i = 0; i < 4; i++) hv[i] = (int)win[i00 + (r - 3) * ws + i] << (6 - shift1);
-        } else row_h(r, hv);
-        if (r > 0) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint32_t pr = pack_lo16(prev[i], hv[i]);
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int j = r - 1 - 2 * k;
-                    if (j >= 0 && j < 8) acc[j][i] = dot2_i16(pr, typ[k], acc[j][i]);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) prev[i] = hv[i];
+        } else luma_row4(win, i00 + (r - 3) * ws - 3, tx, shift1, hv);
+        luma_col_pair(r, hv, prev, ty, acc);
     }
 #pragma unroll
     for (int j = 0; j < 8; j++)
@@ -817,117 +709,6 @@ template <typename T> DEV int luma_tile_int(const T *win, int i00, int ws, const
     }
     return hadamard8_satd(m);
 }
-
-// four horizontally adjacent predicted luma samples (8.5.3.3.3.1) starting at window element i00: the final motion
-// compensation of a CTU spread over all 256 lanes (16 tiles x 8 rows x 2 halves)
-template <typename T>
-DEV void luma_quad(const T *win, int i00, int ws, int fx, int fy, int bit_depth, T *out)
-{
-    const int8_t *tx = g_tab.luma_tap[fx], *ty = g_tab.luma_tap[fy];
-    const int shift1 = bit_depth - 8, shift3 = 14 - bit_depth, maxv = (1 << bit_depth) - 1;
-    int acc[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        int px[15];
-        load_row15(win, i00 + (r - 3) * ws - 3, px);
-        const int t = ty[r];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            int v = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) v += tx[k] * px[i + k];
-            acc[i] += t * (v >> shift1);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = (T)clip3(0, maxv, ((acc[i] >> 6) + (1 << (shift3 - 1))) >> shift3);
-}
-
-// 8-bit form of luma_quad: the horizontal 8-tap filter of a row's four outputs is 8 v_dot4_i32_i8 on byte-realigned dwords (samples biased to
-// signed bytes, the taps of every fraction sum to 64), as in luma_half_diff; same results as the generic form
-DEV void luma_quad(const uint8_t *win, int i00, int ws, int fx, int fy, int, uint8_t *out)
-{
-    const uint32_t tlo = load_u32(&g_tab.luma_tap[fx][0]), thi = load_u32(&g_tab.luma_tap[fx][4]);
-    const int8_t *ty = g_tab.luma_tap[fy];
-    int acc[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int idx = i00 + (r - 3) * ws - 3, off = idx & 3;
-        const uint8_t *p = win + (idx - off);
-        uint32_t d[4], q[3];
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = load_u32_aligned(p + 4 * k);
-#pragma unroll
-        for (int k = 0; k < 3; k++) q[k] = align_bytes(d[k + 1], d[k], off) ^ 0x80808080u;
-        const int t = ty[r];
-        acc[0] += t * dot4_i8(q[0], tlo, dot4_i8(q[1], thi, 128 * 64));
-#pragma unroll
-        for (int i = 1; i < 4; i++) acc[i] += t * dot4_i8(align_bytes(q[1], q[0], i), tlo, dot4_i8(align_bytes(q[2], q[1], i), thi, 128 * 64));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = (uint8_t)clip3(0, 255, ((acc[i] >> 6) + 32) >> 6);
-}
-
-template <typename T>
-DEV int chroma_sample(const T *p00, int ws, int fx, int fy, int bit_depth)
-{
-    const int8_t *tx = g_tab.chroma_tap[fx], *ty = g_tab.chroma_tap[fy];
-    const int shift1 = bit_depth - 8, shift3 = 14 - bit_depth, maxv = (1 << bit_depth) - 1;
-    int acc = 0;
-    for (int r = 0; r < 4; r++) {
-        const T *row = p00 + (r - 1) * ws - 1;
-        int v = tx[0] * row[0] + tx[1] * row[1] + tx[2] * row[2] + tx[3] * row[3];
-        acc += ty[r] * (v >> shift1);
-    }
-    return clip3(0, maxv, ((acc >> 6) + (1 << (shift3 - 1))) >> shift3);
-}
-
-// ---- B pictures: the 14-bit intermediate predictions of 8.5.3.3.3 (before the rounding of 8.5.3.3.4.2), four luma samples / one chroma sample
-template <typename T> DEV void luma_quad14(const T *win, int i00, int ws, int fx, int fy, int bit_depth, int (&out)[4])
-{
-    const int8_t *tx = g_tab.luma_tap[fx], *ty = g_tab.luma_tap[fy];
-    const int shift1 = bit_depth - 8;
-    int acc[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        int px[15];
-        load_row15(win, i00 + (r - 3) * ws - 3, px);
-        const int t = ty[r];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            int v = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) v += tx[k] * px[i + k];
-            acc[i] += t * (v >> shift1);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = acc[i] >> 6;
-}
-template <typename T> DEV int chroma_sample14(const T *p00, int ws, int fx, int fy, int bit_depth)
-{
-    const int8_t *tx = g_tab.chroma_tap[fx], *ty = g_tab.chroma_tap[fy];
-    const int shift1 = bit_depth - 8;
-    int acc = 0;
-    for (int r = 0; r < 4; r++) {
-        const T *row = p00 + (r - 1) * ws - 1;
-        int v = tx[0] * row[0] + tx[1] * row[1] + tx[2] * row[2] + tx[3] * row[3];
-        acc += ty[r] * (v >> shift1);
-    }
-    return acc >> 6;
-}
-// 8.5.3.3.4.2 default weighted sample prediction: one list, or the average of both
-DEV int weighted_uni(int p, int bit_depth) { const int sh = 14 - bit_depth; return clip3(0, (1 << bit_depth) - 1, (p + (1 << (sh - 1))) >> sh); }
-DEV int weighted_bi(int p0, int p1, int bit_depth) { const int sh = 15 - bit_depth; return clip3(0, (1 << bit_depth) - 1, (p0 + p1 + (1 << (sh - 1))) >> sh); }
-// per-CTU state of the list-1 / bi-prediction part of a B picture's CTU program (behind the windows in LDS; P pictures do not carry it)
-struct BiShared {
-    int mx0[21], my0[21];        // refined list-0 vectors (InterShared::mvx / mvy go on to hold list 1)
-    unsigned c0[21], cb[21];     // list-0 cost, bi-prediction SATD sum
-    uint8_t mode[21];            // 0: list 0, 1: list 1, 2: both
-    uint8_t tile_mode[16];
-    int tile_mv1x[16], tile_mv1y[16];
-    alignas(16) int16_t p0[1536];    // the 14-bit list-0 prediction of the CTU (Y, U, V as InterShared::pred), kept while the windows hold list 1
-};
 
 template <typename T, class Ex, bool BI = false>
 DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win_v, const InterArgs<T> &a, int ctu, BiShared *bsh = nullptr)
@@ -1127,6 +908,21 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
     }
     };
     refine(sx, sy, oy_x, oy_y);
+    // Motion compensation by the vector of each tile's CU.  Luma: lane tid has row (tid >> 1) & 7, columns 4 (tid & 1) .. + 3 of tile tid >> 4, four samples at
+    // lane_at(tid) in the CTU image; luma14 gives their 14-bit predictions from the luma window whose origin is (wox, woy).  Chroma: sample i (0 .. 511: Cb, then
+    // Cr) lies in tile chroma_tile(i); chroma14 gives its 14-bit prediction from the chroma windows whose origin is (cox, coy).
+    auto lane_at = [](int tid) { return ((tid >> 6) * 8 + ((tid >> 1) & 7)) * 32 + ((tid >> 4) & 3) * 8 + (tid & 1) * 4; };
+    auto luma14 = [&](int tid, int wox, int woy, int (&v)[4]) {
+        const int t = tid >> 4, node = s.tile_node[t], mx = s.mvx[node], my = s.mvy[node];
+        const int px = x0 + (t & 3) * 8 + (tid & 1) * 4 + (mx >> 2) - wox, py = y0 + (t >> 2) * 8 + ((tid >> 1) & 7) + (my >> 2) - woy;
+        luma_quad14<T>(win_y, py * wys + px, wys, mx & 3, my & 3, bd, v);
+    };
+    auto chroma_tile = [](int i) { return ((i >> 6) & 3) * 4 + ((i >> 2) & 3); };
+    auto chroma14 = [&](int i, int cox, int coy) {
+        const int x = i & 15, y = (i >> 4) & 15, node = s.tile_node[chroma_tile(i)], mx = s.mvx[node], my = s.mvy[node];
+        const int px = (x0 >> 1) + x + (mx >> 3) - cox, py = (y0 >> 1) + y + (my >> 3) - coy;
+        return chroma_sample14<T>((i >> 8 ? win_v : win_u) + py * wcs + px, wcs, mx & 7, my & 7, bd);
+    };
     if constexpr (BI) {
         // ---- B picture (oracle: orc_analyze_b_frame).  The tree and the list-0 vectors stand; every CU of the tree now refines its list-1 vector
         // (from its own node's integer search against the anchor AFTER this picture), tries the bi-prediction of the two refined vectors and takes the
@@ -1139,24 +935,14 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
         // fractional search's scratch area)
         ex.phase([&](int tid) {
             if (tid < 21) { b.mx0[tid] = s.mvx[tid]; b.my0[tid] = s.mvy[tid]; b.c0[tid] = s.cost[tid]; b.cb[tid] = 0; }
-            {
-                const int t = tid >> 4, j = (tid >> 1) & 7, hx = (tid & 1) * 4, txp = t & 3, typ = t >> 2;
-                if (s.rs.tu_log2[t]) {
-                    const int node = s.tile_node[t], mx = s.mvx[node], my = s.mvy[node];
-                    const int px = x0 + txp * 8 + hx + (mx >> 2) - oy_x, py = y0 + typ * 8 + j + (my >> 2) - oy_y;
-                    int v[4];
-                    luma_quad14<T>(win_y, py * wys + px, wys, mx & 3, my & 3, bd, v);
+            if (s.rs.tu_log2[tid >> 4]) {
+                int v[4];
+                luma14(tid, oy_x, oy_y, v);
 #pragma unroll
-                    for (int i = 0; i < 4; i++) b.p0[(typ * 8 + j) * 32 + txp * 8 + hx + i] = (int16_t)v[i];
-                }
+                for (int i = 0; i < 4; i++) b.p0[lane_at(tid) + i] = (int16_t)v[i];
             }
-            for (int i = tid; i < 512; i += NT) {
-                const int pl = i >> 8, k = i & 255, x = k & 15, y = k >> 4, t = (y >> 2) * 4 + (x >> 2);
-                if (!s.rs.tu_log2[t]) continue;
-                const int node = s.tile_node[t], mx = s.mvx[node], my = s.mvy[node];
-                const int px = (x0 >> 1) + x + (mx >> 3) - oc_x, py = (y0 >> 1) + y + (my >> 3) - oc_y;
-                b.p0[1024 + i] = (int16_t)chroma_sample14<T>((pl ? win_v : win_u) + py * wcs + px, wcs, mx & 7, my & 7, bd);
-            }
+            for (int i = tid; i < 512; i += NT)
+                if (s.rs.tu_log2[chroma_tile(i)]) b.p0[1024 + i] = (int16_t)chroma14(i, oc_x, oc_y);
         });
         // list-1 windows and integer vectors
         ex.phase([&](int tid) {
@@ -1181,16 +967,13 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
         refine(sx1, sy1, o1_x, o1_y);
         // bi-prediction of the two refined vectors: difference to the source per sample, then one lane per tile takes the 8x8 Hadamard sum
         ex.phase([&](int tid) {
-            const int t = tid >> 4, j = (tid >> 1) & 7, hx = (tid & 1) * 4, txp = t & 3, typ = t >> 2;
-            if (!s.rs.tu_log2[t]) return;
-            const int node = s.tile_node[t], mx = s.mvx[node], my = s.mvy[node];
-            const int px = x0 + txp * 8 + hx + (mx >> 2) - o1_x, py = y0 + typ * 8 + j + (my >> 2) - o1_y;
+            if (!s.rs.tu_log2[tid >> 4]) return;
             int v[4];
-            luma_quad14<T>(win_y, py * wys + px, wys, mx & 3, my & 3, bd, v);
+            luma14(tid, o1_x, o1_y, v);
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int at = (typ * 8 + j) * 32 + txp * 8 + hx + i;
-                s.rs.scratch[t * 64 + j * 8 + hx + i] = (uint32_t)((int)s.src[at] - weighted_bi((int)b.p0[at], v[i], bd));
+            for (int i = 0; i < 4; i++) {      // (lane tid's four samples of its tile's 8x8 difference block are elements 4 tid .. 4 tid + 3 of the 16 blocks)
+                const int at = lane_at(tid) + i;
+                s.rs.scratch[4 * tid + i] = (uint32_t)((int)s.src[at] - weighted_bi((int)b.p0[at], v[i], bd));
             }
         });
         ex.phase([&](int tid) {
@@ -1219,31 +1002,19 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
                 s.tile_mvx[tid] = mode != 1 ? b.mx0[node] : 0; s.tile_mvy[tid] = mode != 1 ? b.my0[node] : 0;
                 b.tile_mv1x[tid] = mode != 0 ? s.mvx[node] : 0; b.tile_mv1y[tid] = mode != 0 ? s.mvy[node] : 0;
             }
-            {
-                const int t = tid >> 4, j = (tid >> 1) & 7, hx = (tid & 1) * 4, txp = t & 3, typ = t >> 2;
-                if (s.rs.tu_log2[t]) {
-                    const int node = s.tile_node[t], mode = b.mode[node], mx = s.mvx[node], my = s.mvy[node];
-                    int v[4] = {0, 0, 0, 0};
-                    if (mode != 0) {
-                        const int px = x0 + txp * 8 + hx + (mx >> 2) - o1_x, py = y0 + typ * 8 + j + (my >> 2) - o1_y;
-                        luma_quad14<T>(win_y, py * wys + px, wys, mx & 3, my & 3, bd, v);
-                    }
+            if (s.rs.tu_log2[tid >> 4]) {
+                const int mode = b.mode[s.tile_node[tid >> 4]];
+                int v[4] = {0, 0, 0, 0};
+                if (mode != 0) luma14(tid, o1_x, o1_y, v);
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const int at = (typ * 8 + j) * 32 + txp * 8 + hx + i, p0 = (int)b.p0[at];
-                        s.pred[at] = (T)(mode == 0 ? weighted_uni(p0, bd) : mode == 1 ? weighted_uni(v[i], bd) : weighted_bi(p0, v[i], bd));
-                    }
+                for (int i = 0; i < 4; i++) {
+                    const int at = lane_at(tid) + i, p0 = (int)b.p0[at];
+                    s.pred[at] = (T)(mode == 0 ? weighted_uni(p0, bd) : mode == 1 ? weighted_uni(v[i], bd) : weighted_bi(p0, v[i], bd));
                 }
             }
             for (int i = tid; i < 512; i += NT) {
-                const int pl = i >> 8, k = i & 255, x = k & 15, y = k >> 4, t = (y >> 2) * 4 + (x >> 2);
-                if (!s.rs.tu_log2[t]) continue;
-                const int node = s.tile_node[t], mode = b.mode[node], mx = s.mvx[node], my = s.mvy[node], p0 = (int)b.p0[1024 + i];
-                int p1 = 0;
-                if (mode != 0) {
-                    const int px = (x0 >> 1) + x + (mx >> 3) - oc1_x, py = (y0 >> 1) + y + (my >> 3) - oc1_y;
-                    p1 = chroma_sample14<T>((pl ? win_v : win_u) + py * wcs + px, wcs, mx & 7, my & 7, bd);
-                }
+                if (!s.rs.tu_log2[chroma_tile(i)]) continue;
+                const int mode = b.mode[s.tile_node[chroma_tile(i)]], p0 = (int)b.p0[1024 + i], p1 = mode != 0 ? chroma14(i, oc1_x, oc1_y) : 0;
                 s.pred[1024 + i] = (T)(mode == 0 ? weighted_uni(p0, bd) : mode == 1 ? weighted_uni(p1, bd) : weighted_bi(p0, p1, bd));
             }
         });
@@ -1272,21 +1043,14 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
     if constexpr (!BI)
     ex.phase([&](int tid) {
         if (tid < 16) { s.tile_mvx[tid] = s.mvx[s.tile_node[tid]]; s.tile_mvy[tid] = s.mvy[s.tile_node[tid]]; }      // read by the output phase, behind barriers
-        {
-            const int t = tid >> 4, j = (tid >> 1) & 7, hx = (tid & 1) * 4, txp = t & 3, typ = t >> 2;
-            if (s.rs.tu_log2[t]) {
-                int mx = s.mvx[s.tile_node[t]], my = s.mvy[s.tile_node[t]];
-                int px = x0 + txp * 8 + hx + (mx >> 2) - oy_x, py = y0 + typ * 8 + j + (my >> 2) - oy_y;
-                luma_quad(win_y, py * wys + px, wys, mx & 3, my & 3, bd, s.pred + (typ * 8 + j) * 32 + txp * 8 + hx);
-            }
+        if (s.rs.tu_log2[tid >> 4]) {
+            int v[4];
+            luma14(tid, oy_x, oy_y, v);
+#pragma unroll
+            for (int i = 0; i < 4; i++) s.pred[lane_at(tid) + i] = (T)weighted_uni(v[i], bd);
         }
-        for (int i = tid; i < 512; i += NT) {
-            int pl = i >> 8, k = i & 255, x = k & 15, y = k >> 4, t = (y >> 2) * 4 + (x >> 2);
-            if (!s.rs.tu_log2[t]) continue;
-            int mx = s.mvx[s.tile_node[t]], my = s.mvy[s.tile_node[t]];
-            int px = (x0 >> 1) + x + (mx >> 3) - oc_x, py = (y0 >> 1) + y + (my >> 3) - oc_y;
-            s.pred[1024 + i] = (T)chroma_sample<T>((pl ? win_v : win_u) + py * wcs + px, wcs, mx & 7, my & 7, bd);
-        }
+        for (int i = tid; i < 512; i += NT)
+            if (s.rs.tu_log2[chroma_tile(i)]) s.pred[1024 + i] = (T)weighted_uni(chroma14(i, oc_x, oc_y), bd);
     });
     ex.phase([&](int tid) {
         for (int i = tid; i < 1536; i += NT) {

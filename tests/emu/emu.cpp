@@ -173,7 +173,7 @@ static int inter_frame(const void *const *s, const void *const *f0, const void *
         }
     }
     std::vector<uint8_t> win((size_t)me_win_elems(R) + 8);
-    std::vector<T> wy((size_t)mc_win_y(R) * mc_win_y_stride(R) + 16), wu((size_t)mc_win_c(R) * mc_win_c_stride(R) + 16), wv(wu.size());
+    std::vector<T> wy(mc_win_y_bytes<T>(R) / sizeof(T)), wu(mc_win_c_bytes<T>(R) / sizeof(T)), wv(wu.size());
     for (int list = 0; list < nref; list++) {
         const InterArgs<T> al = list ? list1_view(a) : a;
         for (int c = 0; c < n_ctu; c++) {
