@@ -41,6 +41,47 @@ class CostParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("qp", "qp_c", "bit_depth", "lambda_sad_q4", "lambda_q4", "me_range", "tile_cols", "tile_rows", "intra_nxn", "intra_in_p", "pre_search", "rdo_zero", "chroma_modes", "mc_top", "mc_bottom", "rdo_cg")]
 
 
+class SrcFormat(C.Structure):
+    """mihevc_src_format: the sample layout of a source handed to mihevc_send_frame_fmt / mihevc_k_convert_source"""
+    _fields_ = [(n, C.c_int32) for n in ("chroma", "semi_planar", "bit_depth", "msb_aligned")] + [("reserved", C.c_int32 * 4)]
+
+    def __eq__(self, other):
+        return isinstance(other, SrcFormat) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"SrcFormat(chroma={self.chroma}, semi_planar={self.semi_planar}, bit_depth={self.bit_depth}, msb_aligned={self.msb_aligned})"
+
+    def chroma_shape(self, width: int, height: int):
+        """(rows, elements per row) of a source chroma plane; a semi-planar one holds Cb and Cr side by side"""
+        return (height // 2 if self.chroma == 420 else height), (width if self.chroma == 444 else width // 2) * (2 if self.semi_planar else 1)
+
+    def frame_bytes(self, width: int, height: int) -> int:
+        rows, row = self.chroma_shape(width, height)
+        return (width * height + rows * row * (1 if self.semi_planar else 2)) * (2 if self.bit_depth > 8 else 1)
+
+
+SRC_DEVICE, SRC_ASYNC = 1, 2
+
+_SEMI_PLANAR = {"nv12": (420, 8), "nv16": (422, 8), "nv24": (444, 8), "p010le": (420, 10), "p016le": (420, 16), "p210le": (422, 10), "p216le": (422, 16),
+                "p410le": (444, 10), "p416le": (444, 16)}
+
+
+def src_format_for(pix_fmt: str):
+    """The SrcFormat of an ffmpeg pixel format name, or None for one the conversion does not cover (swapped semi-planar, packed, RGB, 4:1:1 / 4:1:0,
+    big endian, alpha).  yuvj* are the same layouts as yuv*: there is no range conversion."""
+    import re
+    name = (pix_fmt or "").lower()
+    if name in _SEMI_PLANAR:
+        chroma, depth = _SEMI_PLANAR[name]
+        return SrcFormat(chroma, 1, depth, 1 if depth > 8 else 0)
+    m = re.fullmatch(r"yuvj?(420|422|444)p(?:(9|10|12|14|16)le)?", name)
+    if not m or (m.group(2) and name.startswith("yuvj")):
+        return None
+    return SrcFormat(int(m.group(1)), 0, int(m.group(2) or 8), 0)
+
+
 # every symbol include/mihevc.h declares; tests/test_abi.py checks the header against this list and the .so
 EXPORTS = (
     "mihevc_abi_version", "mihevc_device_count", "mihevc_device_numa_node", "mihevc_config_default", "mihevc_open", "mihevc_send_frame", "mihevc_send_frame_async", "mihevc_sync_uploads", "mihevc_send_frame_device", "mihevc_send_frames_device",
@@ -48,6 +89,7 @@ EXPORTS = (
     "mihevc_get_recon", "mihevc_coded_size", "mihevc_get_frame_info", "mihevc_strerror", "mihevc_last_error", "mihevc_cost_params_for_qp", "mihevc_tile_grid", "mihevc_p_tile_grid", "mihevc_k_transform", "mihevc_k_transform_sdh",
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
+    "mihevc_send_frame_fmt", "mihevc_k_convert_source",
 )
 
 _lib = None
@@ -111,6 +153,8 @@ def load() -> C.CDLL:
     lib.mihevc_write_picture_hash_sei.argtypes = [C.POINTER(Config), i32, vp, vp, C.c_size_t]
     lib.mihevc_get_frame_quality.argtypes = [vp, i64, vp, vp, vp]
     lib.mihevc_k_ssim.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.mihevc_send_frame_fmt.argtypes = [vp, C.POINTER(SrcFormat), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_convert_source.argtypes = [i32, C.POINTER(SrcFormat), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

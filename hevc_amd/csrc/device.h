@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "kernels/common.h"
+#include "kernels/ingest.h"
 #include "kernels/inter.h"
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
@@ -65,6 +66,9 @@ template <typename T> struct ScenePic { const T *p; int stride; };
 template <typename T> hipError_t launch_scene_diff(hipStream_t st, const ScenePic<T> *pics, unsigned long long *out, int w, int h, int n);
 
 template <typename T> hipError_t launch_extend_margin(hipStream_t st, Plane<T> p, int sw, int sh, int pw, int ph);
+
+// source conversion (kernels/ingest.h): one launch writes the three coded-size planes of `a`, margins included.  in16 / out16: uint16 source elements / output samples
+hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool out16);
 
 // rows between the slices of one picture (csrc/slice_group.h): jobs[i] for i < n_jobs, one grid row of `blocks_per_job` workgroups each
 hipError_t launch_copy_rows(hipStream_t st, const RowCopy *d_jobs, int n_jobs, int blocks_per_job);

@@ -181,6 +181,22 @@ template <typename T> hipError_t launch_extend_margin(hipStream_t st, Plane<T> p
     return hipGetLastError();
 }
 
+// source conversion (kernels/ingest.h): one workgroup per tile of output samples, Y, then Cb, then Cr; the argument block travels by value
+template <typename TI, typename TO> __global__ __launch_bounds__(NT) void k_ingest(const IngestArgs a)
+{
+    GpuExec ex;
+    ingest_tile_program<TI, TO>(ex, a, (int)blockIdx.x);
+}
+hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool out16)
+{
+    const dim3 grid((unsigned)ingest_workgroups(a.pw, a.ph, a.semi)), block(NT);
+    if (in16 && out16) hipLaunchKernelGGL((k_ingest<uint16_t, uint16_t>), grid, block, 0, st, a);
+    else if (in16) hipLaunchKernelGGL((k_ingest<uint16_t, uint8_t>), grid, block, 0, st, a);
+    else if (out16) hipLaunchKernelGGL((k_ingest<uint8_t, uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_ingest<uint8_t, uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 // scene-cut detector: sum of |a - b| over every 4th sample of every 4th row of the luma planes of pictures blockIdx.y - 1... the pair
 // (blockIdx.y, blockIdx.y + 1) -> out[blockIdx.y + 1]; wave reduction by shuffles, one atomic per wave
 template <typename T> __global__ __launch_bounds__(256) void k_scene_diff(const ScenePic<T> *pics, unsigned long long *out, int w, int h)
@@ -834,6 +850,33 @@ template <typename T> int stage_ssim(const void *const *a, const void *const *b,
     return MIHEVC_OK;
 }
 
+// the conversion kernel alone: the source planes as the caller laid them out (pitches kept, so their alignment is the caller's), the output in planes of
+// 16-byte aligned stride
+template <typename TO>
+int stage_convert(const mihevc_src_format &f, const void *const *src, int w, int h, int pitch_y, int pitch_c, int out_depth, void *const *out)
+{
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    const struct { int w, h; } cd = {(w + 7) & ~7, (h + 7) & ~7};      // the coded size: rounded up to 8
+    DevBuf din[3];
+    Planes3<TO> dst;
+    if (dst.alloc(cd.w, cd.h, false)) return MIHEVC_ENOMEM;
+    const void *dsrc[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < (f.semi_planar ? 2 : 3); c++) {
+        const int row = c ? src_chroma_row(f, w) : w, rows = c ? src_chroma_rows(f, h) : h, pitch = c ? pitch_c : pitch_y;
+        // the source's own misalignment travels with it: the device copy starts at the same offset from a 16-byte boundary, and ends with the last sample
+        const size_t off = (size_t)(uintptr_t)src[c] & 15, bytes = ((size_t)pitch * (rows - 1) + row) * es;
+        CK(din[c].alloc(off + bytes));
+        CK(hipMemcpy(din[c].as<uint8_t>() + off, src[c], bytes, hipMemcpyHostToDevice));
+        dsrc[c] = din[c].as<uint8_t>() + off;
+    }
+    void *dptr[3]; int dstride[3];
+    for (int c = 0; c < 3; c++) { dptr[c] = dst.p[c].pl.p; dstride[c] = dst.p[c].pl.stride; }
+    const IngestArgs a = ingest_args(f, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, w, h, cd.w, cd.h, out_depth, dptr, dstride);
+    CK(launch_ingest(0, a, es == 2, sizeof(TO) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.download(out);
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -988,6 +1031,18 @@ int mihevc_k_ssim(int device, const void *ay, const void *au, const void *av, co
     for (int c = 0; c < 3; c++) windows[c] = (int64_t)ssim_windows_x(c ? w / 2 : w) * ssim_windows_y(c ? h / 2 : h);
     if (bit_depth == 8) return stage_ssim<uint8_t>(a, b, w, h, sum_q32);
     return stage_ssim<uint16_t>(a, b, w, h, sum_q32);
+}
+
+int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int width, int height, int pitch_y, int pitch_c,
+                            int out_bit_depth, void *out_y, void *out_u, void *out_v)
+{
+    if (!src_format_ok(fmt) || !y || !u || (!v && !fmt->semi_planar) || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
+    if (width < 16 || height < 16 || (width & 1) || (height & 1) || width > 8192 || height > 4352 || (out_bit_depth != 8 && out_bit_depth != 10)) return MIHEVC_EINVAL;
+    if (pitch_y < width || pitch_c < src_chroma_row(*fmt, width)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *src[3] = {y, u, v};
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(out_bit_depth, [&](auto t) { return stage_convert<decltype(t)>(*fmt, src, width, height, pitch_y, pitch_c, out_bit_depth, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

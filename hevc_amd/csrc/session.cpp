@@ -107,6 +107,10 @@ struct mihevc_session {
     struct Src { CachedBlock<uint8_t> mem[3]; void *p[3]; int stride[3]; int64_t pts; bool borrowed; };      // borrowed: the caller's device planes, not copied (mem is empty)
     std::vector<Src> pending;
     std::vector<Src> free_src;
+    // mihevc_send_frame_fmt, host planes: the raw planes in the SOURCE layout on their way to k_ingest.  Copy and conversion of a picture are neighbours on st_pre,
+    // so the next picture's copy comes behind this picture's kernel in stream order: one set serves every picture (a set per pending picture would be 12 MB
+    // each for a 1080p 4:4:4 16-bit source).  It grows when a larger format arrives (st_pre is synchronised first) and goes back with the session
+    CachedBlock<uint8_t> stage;
     // per lane
     // The vector moves a lane's handles when it grows; the blocks they own stay where they are, so the raw pointers in argument blocks, jobs and BandPub stay valid
     struct Lane {
@@ -1316,7 +1320,21 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     return MIHEVC_OK;
 }
 
-static int ingest(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
+// a source picture whose planes are filled (or on their way on st_pre): pts bookkeeping, and the chunk once it is complete
+static int enqueue_source(mihevc_session *s, mihevc_session::Src &&src, int64_t pts)
+{
+    src.pts = pts;
+    if (s->frames_in == 0) s->first_pts = pts; else if (s->frames_in == 1) s->pts_step = std::max<int64_t>(1, pts - s->first_pts);
+    s->pending.push_back(std::move(src));
+    s->frames_in++;
+    s->stats.frames_in = s->frames_in;
+    if ((int)s->pending.size() >= s->lanes * s->keyint) return run_chunk(s);
+    return MIHEVC_OK;
+}
+
+// may_borrow: device planes that need no margin may be coded where they are (the rule of mihevc_send_frame_device: valid until the packet is out); false: always copied,
+// so the caller's planes are free once the uploads are through (the rule of mihevc_send_frame_fmt)
+static int ingest(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async, bool may_borrow = true)
 {
     if (!s || !y || !u || !v) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
@@ -1328,7 +1346,7 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
     // Device planes whose size already is the coded size (no margin to fill) are used where they are: the header's contract keeps them valid and
     // unmodified until the picture's packet is out.  Saves three 2-D copies per frame (4 % of the device time of a 1080p clip, and most of the
     // wall time of handing 300 frames over).
-    if (device_src && s->cfg.width == s->w && s->cfg.height == s->h && pitch_y >= s->w && pitch_c >= s->w / 2 &&
+    if (may_borrow && device_src && s->cfg.width == s->w && s->cfg.height == s->h && pitch_y >= s->w && pitch_c >= s->w / 2 &&
         ((uintptr_t)y & 3) == 0 && ((uintptr_t)u & 3) == 0 && ((uintptr_t)v & 3) == 0 && (pitch_y * es) % 4 == 0 && (pitch_c * es) % 4 == 0) {
         for (int i = 0; i < 3; i++) { src.p[i] = const_cast<void *>(in[i]); src.stride[i] = i ? pitch_c : pitch_y; }
         src.borrowed = true;
@@ -1352,13 +1370,46 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
         if (!device_src && !async) HIPCK(s, hipStreamSynchronize(s->st_pre));     // caller's buffers may be reused on return
         else s->up_pending = true;
     }
-    src.pts = pts;
-    if (s->frames_in == 0) s->first_pts = pts; else if (s->frames_in == 1) s->pts_step = std::max<int64_t>(1, pts - s->first_pts);
-    s->pending.push_back(std::move(src));
-    s->frames_in++;
-    s->stats.frames_in = s->frames_in;
-    if ((int)s->pending.size() >= s->lanes * s->keyint) return run_chunk(s);
-    return MIHEVC_OK;
+    return enqueue_source(s, std::move(src), pts);
+}
+
+// A source in another layout (mihevc_send_frame_fmt; the arguments are checked): k_ingest writes the session's own planes, margin included, from the
+// caller's device planes or from the staging set the host planes are copied into
+static int ingest_fmt(mihevc_session *s, const mihevc_src_format &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
+{
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    mihevc_session::Src src;
+    if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
+    else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;
+    src.borrowed = false;
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    const int W = s->cfg.width, H = s->cfg.height, n_planes = f.semi_planar ? 2 : 3;
+    const void *in[3] = {y, u, f.semi_planar ? nullptr : v};
+    int pitch[3] = {pitch_y, pitch_c, pitch_c};
+    if (!device_src) {
+        size_t off[3], total = 0;
+        int spitch[3];
+        for (int c = 0; c < n_planes; c++) {
+            const int row = c ? src_chroma_row(f, W) : W, rows = c ? src_chroma_rows(f, H) : H;
+            spitch[c] = (row + 15) & ~15;          // rows begin 16-byte aligned: the kernel's widest loads
+            off[c] = total;
+            total += ((size_t)spitch[c] * rows * es + 255) & ~(size_t)255;
+        }
+        if (total > s->stage.bytes()) {
+            HIPCK(s, hipStreamSynchronize(s->st_pre));      // a conversion still reading the smaller set
+            HIPCK(s, s->stage.alloc(s->device, total, false));
+        }
+        for (int c = 0; c < n_planes; c++) {
+            const int row = c ? src_chroma_row(f, W) : W, rows = c ? src_chroma_rows(f, H) : H;
+            HIPCK(s, hipMemcpy2DAsync(s->stage + off[c], spitch[c] * es, in[c], pitch[c] * es, row * es, rows, hipMemcpyHostToDevice, s->st_pre));
+            in[c] = s->stage + off[c]; pitch[c] = spitch[c];
+        }
+    }
+    const IngestArgs a = ingest_args(f, in[0], in[1], in[2], pitch[0], pitch[1], W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
+    HIPCK(s, launch_ingest(s->st_pre, a, es == 2, s->is16));
+    if (!device_src && !async) HIPCK(s, hipStreamSynchronize(s->st_pre));     // caller's buffers may be reused on return
+    else s->up_pending = true;
+    return enqueue_source(s, std::move(src), pts);
 }
 
 int mihevc_send_frame(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
@@ -1379,6 +1430,20 @@ int mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, co
     for (int i = 0; i < n; i++)
         if (int e = ingest(s, y[i], u[i], v[i], pitch_y, pitch_c, first_pts + i, true, false)) return e;
     return MIHEVC_OK;
+}
+int mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    if (!s || !src_format_ok(fmt) || !y || !u || (!v && !fmt->semi_planar) || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
+    if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
+    if (pitch_y < s->cfg.width || pitch_c < src_chroma_row(*fmt, s->cfg.width)) return MIHEVC_EINVAL;
+    const bool device_src = (flags & MIHEVC_SRC_DEVICE) != 0, async = (flags & MIHEVC_SRC_ASYNC) != 0;
+    // the session's own layout: the existing route, copy and margin fill.  Device planes are copied too, never borrowed: this entry point lets the caller have
+    // them back after mihevc_sync_uploads, whatever the format
+    if (fmt->chroma == 420 && !fmt->semi_planar && fmt->bit_depth == s->cfg.bit_depth && !fmt->msb_aligned)
+        return ingest(s, y, u, v, pitch_y, pitch_c, pts, device_src, async, false);
+    if (s->failed) return s->fail_code;
+    if (s->flushed) return MIHEVC_ESTATE;
+    return ingest_fmt(s, *fmt, y, u, v, pitch_y, pitch_c, pts, device_src, async);
 }
 int mihevc_sync_uploads(mihevc_session *s)
 {

@@ -153,6 +153,41 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_async(self._s, y.ctypes.data, u.ctypes.data, v.ctypes.data, y.shape[1], u.shape[1], pts), "send_frame_async")
 
+    def send_fmt(self, fmt: _lib.SrcFormat, y, u, v, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_fmt: a picture of the session's display size in another sample layout (4:2:2 / 4:4:4, semi-planar, 8 .. 16 bit), converted on
+        the device.  numpy planes (uint8 at 8 bit, else uint16; a semi-planar source: `u` is the interleaved (rows, 2 x chroma width) plane and `v` is None)
+        are checked for shape and type here; torch tensors on the session's device are read where they are (MIHEVC_SRC_DEVICE): their producer must have
+        finished, and they must stay alive and unmodified until sync_uploads() or flush().  asynchronous (host planes): return with the upload in flight, under
+        the rules of send_async."""
+        c = self.cfg
+        rows, row = fmt.chroma_shape(c.width, c.height)
+        planes = [y, u] if fmt.semi_planar else [y, u, v]
+        shapes = [(c.height, c.width)] + [(rows, row)] * (len(planes) - 1)
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {fmt!r} at {c.width}x{c.height}")
+        flags = _lib.SRC_ASYNC if asynchronous else 0
+        if all(isinstance(p, np.ndarray) for p in planes):
+            dt = np.uint8 if fmt.bit_depth == 8 else np.uint16
+            if asynchronous:
+                if any(p.dtype != dt or not p.flags.c_contiguous for p in planes):
+                    raise ValueError("an asynchronous send_fmt needs C-contiguous planes of the format's element type")
+            elif any(p.dtype.itemsize != np.dtype(dt).itemsize for p in planes):
+                raise ValueError(f"{[str(p.dtype) for p in planes]} planes handed over as {fmt!r}")
+            else:
+                planes = [np.ascontiguousarray(p, dtype=dt) for p in planes]
+            ptrs, pitches = [p.ctypes.data for p in planes], [p.shape[1] for p in planes]
+        else:       # torch tensors on the device
+            es = 1 if fmt.bit_depth == 8 else 2
+            if any(not p.is_cuda or p.element_size() != es or p.stride(1) != 1 for p in planes):
+                raise ValueError("device planes must be tensors on the GPU of the format's element size with unit column stride")
+            ptrs, pitches, flags = [p.data_ptr() for p in planes], [p.stride(0) for p in planes], flags | _lib.SRC_DEVICE
+        if len(planes) == 3 and pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_fmt(self._s, C.byref(fmt), ptrs[0], ptrs[1], ptrs[2] if len(ptrs) == 3 else None, pitches[0], pitches[1], pts, flags),
+                    "send_frame_fmt")
+
     def sync_uploads(self):
         self._check(self._lib.mihevc_sync_uploads(self._s), "sync_uploads")
 
@@ -279,8 +314,11 @@ class ShardedEncoder:
                 item = q.get()
                 if item is None:
                     break
-                y, u, v, pts = item
-                enc.send(y, u, v, pts=pts)          # ctypes releases the GIL: the sessions run concurrently
+                y, u, v, pts, fmt = item
+                if fmt is None:
+                    enc.send(y, u, v, pts=pts)      # ctypes releases the GIL: the sessions run concurrently
+                else:
+                    enc.send_fmt(fmt, y, u, v, pts=pts)
                 self._collect(enc)
             if not self._aborted:
                 enc.flush()
@@ -295,14 +333,15 @@ class ShardedEncoder:
                 for data, pts, key in got:
                     self._out[pts] = (data, key)
 
-    def send(self, y, u, v):
+    def send(self, y, u, v, fmt=None):
+        """fmt: the planes' _lib.SrcFormat when they are not the session's own layout (Encoder.send_fmt)"""
         import queue
         k = (self._n_in // self.chunk) % len(self.devices)
         while True:                                 # a bounded queue whose worker has died must not block the caller for ever
             if self._err:
                 raise self._err[0]
             try:
-                self._q[k].put((y, u, v, self._n_in), timeout=0.2)
+                self._q[k].put((y, u, v, self._n_in, fmt), timeout=0.2)
                 break
             except queue.Full:
                 continue
@@ -527,13 +566,18 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
 
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
-    clip = yuvio.open_any(Path(file_path), info)
+    sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
+    clip = yuvio.open_any(Path(file_path), info, native_formats=not sliced)
     mux = None
     ok = False
     try:
         if clip.bit_depth > 8 and bit_depth_of(info) == 8:      # the file's own header outranks the probe (a y4m tagged C420p10 probed as SDR)
             info.pix_fmt = 'yuv420p10le'
         cfg = config_for(info, crf, maxrate, bufsize, gop, level, tier)
+        fmt = getattr(clip, 'src_format', None)     # not the session's own layout: converted on the device (send_fmt)
+        if fmt is not None and sliced:
+            logger.error("%s: a %r source cannot be split by rows", Path(file_path).name, fmt)
+            return 1
         total = clip.n_frames or total_frames
         wants_audio = bool(info.audio_channels and info.audio_channels > 0) and Path(file_path).suffix.lower() not in ('.y4m', '.yuv')
         video_path = Path(out_path).with_suffix('.video.mp4') if wants_audio else Path(out_path)
@@ -553,7 +597,10 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 for y, u, v in clip.frames():
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    sh.send(y, u, v)
+                    if fmt is None:
+                        sh.send(y, u, v)
+                    else:
+                        sh.send(y, u, v, fmt)
                     for data, pts, key in sh.ready():
                         mux.add_sample(data, pts, key)
                         n_out += 1
@@ -570,7 +617,10 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 for i, (y, u, v) in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    enc.send(y, u, v, pts=i)
+                    if fmt is None:
+                        enc.send(y, u, v, pts=i)
+                    else:
+                        enc.send_fmt(fmt, y, u, v, pts=i)
                     for data, pts, key, dts in enc.packets_dts():
                         mux.add_sample(data, pts, key, dts)
                         n_out += 1

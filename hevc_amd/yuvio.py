@@ -2,8 +2,10 @@
 
 The reference generates its test inputs with `ffmpeg -f lavfi -i testsrc=...` (tests/generate_test_videos.py:26-31)
 and decodes arbitrary containers inside ffmpeg (core/transcoder.py:461).  Neither is possible without ffmpeg, so
-the native path reads planar 4:2:0 directly (`.y4m`, or `.yuv` named `<stem>_<W>x<H>_<fps>[_10bit][_hdr].yuv`) and,
-when ffmpeg IS present, any other container through an `ffmpeg -f rawvideo` pipe.
+the native path reads planar 4:2:0 / 4:2:2 / 4:4:4 at 8 .. 16 bit directly (`.y4m`, or `.yuv` named
+`<stem>_<W>x<H>_<fps>[_422|_444][_<N>bit][_hdr].yuv`) and, when ffmpeg IS present, any other container through an `ffmpeg -f rawvideo` pipe.
+A clip that is not planar 4:2:0 at the session's depth carries its layout in `src_format` and yields planes in its own shapes: the session
+converts them on the device (Encoder.send_fmt).
 """
 from __future__ import annotations
 
@@ -18,20 +20,42 @@ from typing import Iterator, Optional, Tuple
 import numpy as np
 
 Planes = Tuple[np.ndarray, np.ndarray, np.ndarray]
-_YUV_NAME = re.compile(r'_(\d+)x(\d+)_(\d+(?:\.\d+)?)(?:fps)?(?:_(8|10)bit)?(?:_(hdr|sdr))?$', re.I)
+_YUV_NAME = re.compile(r'_(\d+)x(\d+)_(\d+(?:\.\d+)?)(?:fps)?(?:_(420|422|444))?(?:_(8|9|10|12|14|16)bit)?(?:_(hdr|sdr))?$', re.I)
+_Y4M_COLOUR = re.compile(r'C(420|422|444)(?:p(9|10|12|14|16)|jpeg|mpeg2|paldv)?$')
+
+
+def _planar_format(chroma: int, depth: int):
+    """(session bit depth, src_format): src_format is None for the plain layout, planar 4:2:0 at 8 or 10 bit"""
+    from ._lib import SrcFormat
+    return (10 if depth > 8 else 8), (None if chroma == 420 and depth in (8, 10) else SrcFormat(chroma, 0, depth, 0))
+
+
+def _split_frame(a: np.ndarray, w: int, h: int, fmt) -> Planes:
+    """one frame's elements -> planes: 4:2:0 without a format, else the format's own shapes (semi-planar: u is the interleaved plane, v is None)"""
+    if fmt is None:
+        return a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
+    rows, row = fmt.chroma_shape(w, h)
+    y, c = a[:w * h].reshape(h, w), a[w * h:]
+    if fmt.semi_planar:
+        return y, c.reshape(rows, row), None
+    return y, c[:rows * row].reshape(rows, row), c[rows * row:].reshape(rows, row)
 
 
 class Clip:
-    """A planar 4:2:0 clip on disk."""
+    """A planar clip on disk.  bit_depth: of the session that codes it (8, or 10 for anything deeper than 8); src_format: an _lib.SrcFormat when the
+    frames are not planar 4:2:0 at that depth (frames() then yields planes in the source's own shapes), else None."""
 
     def __init__(self, path: Path, width: int, height: int, fps: float, bit_depth: int, n_frames: int, data_offset: int,
-                 frame_header: int = 0, hdr: bool = False):
+                 frame_header: int = 0, hdr: bool = False, src_format=None):
         self.path, self.width, self.height, self.fps, self.bit_depth = Path(path), width, height, fps, bit_depth
         self.n_frames, self.data_offset, self.frame_header, self.hdr = n_frames, data_offset, frame_header, hdr
+        self.src_format = src_format
         self._f = open(self.path, 'rb')
 
     @property
     def frame_bytes(self) -> int:
+        if self.src_format is not None:
+            return self.src_format.frame_bytes(self.width, self.height)
         return self.width * self.height * 3 // 2 * (2 if self.bit_depth > 8 else 1)
 
     def frames(self) -> Iterator[Planes]:
@@ -46,8 +70,7 @@ class Clip:
             buf = self._f.read(self.frame_bytes)
             if len(buf) < self.frame_bytes:
                 return
-            a = np.frombuffer(buf, dt)
-            yield a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
+            yield _split_frame(np.frombuffer(buf, dt), w, h, self.src_format)
 
     def close(self):
         self._f.close()
@@ -61,7 +84,7 @@ def open_clip(path: Path) -> Clip:
         if not header.startswith(b'YUV4MPEG2'):
             raise ValueError('not a YUV4MPEG2 file')
         w = h = 0
-        fps, depth = 30.0, 8
+        fps, depth, chroma = 30.0, 8, 420
         for tok in header.split()[1:]:
             t = tok.decode()
             if t[0] == 'W':
@@ -72,31 +95,43 @@ def open_clip(path: Path) -> Clip:
                 n, d = t[1:].split(':')
                 fps = int(n) / int(d) if int(d) else 30.0
             elif t[0] == 'C':
-                if not t[1:].startswith('420'):
+                m = _Y4M_COLOUR.match(t)
+                if not m:
                     raise ValueError(f'unsupported chroma format {t}')
-                depth = 10 if 'p10' in t else 8
-        fb = w * h * 3 // 2 * (2 if depth > 8 else 1)
+                chroma, depth = int(m.group(1)), int(m.group(2) or 8)
+        depth, fmt = _planar_format(chroma, depth)
+        fb = fmt.frame_bytes(w, h) if fmt is not None else w * h * 3 // 2 * (2 if depth > 8 else 1)
         n_frames = (path.stat().st_size - len(header)) // (fb + 6)
-        return Clip(path, w, h, fps, depth, n_frames, len(header), frame_header=6, hdr=depth > 8 and 'hdr' in path.stem.lower())
+        return Clip(path, w, h, fps, depth, n_frames, len(header), frame_header=6, hdr=depth > 8 and 'hdr' in path.stem.lower(), src_format=fmt)
     m = _YUV_NAME.search(path.stem)
     if not m:
-        raise ValueError('raw .yuv needs <stem>_<W>x<H>_<fps>[_10bit][_hdr].yuv')
+        raise ValueError('raw .yuv needs <stem>_<W>x<H>_<fps>[_422|_444][_<N>bit][_hdr].yuv')
     w, h, fps = int(m.group(1)), int(m.group(2)), float(m.group(3))
-    depth = int(m.group(4) or 8)
-    fb = w * h * 3 // 2 * (2 if depth > 8 else 1)
-    return Clip(path, w, h, fps, depth, path.stat().st_size // fb, 0, hdr=(m.group(5) or '').lower() == 'hdr')
+    depth, fmt = _planar_format(int(m.group(4) or 420), int(m.group(5) or 8))
+    fb = fmt.frame_bytes(w, h) if fmt is not None else w * h * 3 // 2 * (2 if depth > 8 else 1)
+    return Clip(path, w, h, fps, depth, path.stat().st_size // fb, 0, hdr=(m.group(6) or '').lower() == 'hdr', src_format=fmt)
 
 
 class _PipeClip:
     """Any container decoded by an `ffmpeg -f rawvideo` child (only when ffmpeg exists on this host).  A decode error or a short
-    stream raises: a truncated clip must not come out as SUCCESS."""
+    stream raises: a truncated clip must not come out as SUCCESS.  A probed sample format the device conversion covers (_lib.src_format_for) is
+    asked for as it is, so swscale has nothing to do, and comes out with `src_format` set; anything else is asked for as planar 4:2:0, and so
+    are the full-range yuvj* formats: there is no range conversion on the device, swscale's stays in front of them."""
 
-    def __init__(self, path: Path, info):
+    def __init__(self, path: Path, info, native_formats: bool = True):
         self.width, self.height, self.fps = info.width, info.height, info.fps
         from .encoder import bit_depth_of
         self.bit_depth = bit_depth_of(info)
         self.n_frames = info.nb_frames or (int(info.duration * info.fps) if info.duration and info.fps else 0)
         pix = 'yuv420p10le' if self.bit_depth > 8 else 'yuv420p'
+        from ._lib import SrcFormat, src_format_for
+        name = (info.pix_fmt or '').lower()
+        fmt = None if name.startswith('yuvj') or not native_formats else src_format_for(name)
+        self.src_format = None
+        if fmt is not None:
+            pix = name
+            if fmt != SrcFormat(420, 0, self.bit_depth, 0):
+                self.src_format = fmt
         self._name = Path(path).name
         # stderr goes to a file, not a pipe: a damaged input can make `-v error` write more than a pipe buffer holds before the first frame, and a
         # child blocked on stderr while frames() blocks on stdout would hang the encode for ever instead of failing it
@@ -105,17 +140,16 @@ class _PipeClip:
                                    stdout=subprocess.PIPE, stderr=self._err)
 
     def frames(self) -> Iterator[Planes]:
-        w, h = self.width, self.height
-        fb = w * h * 3 // 2 * (2 if self.bit_depth > 8 else 1)
-        dt = np.dtype('<u2') if self.bit_depth > 8 else np.uint8
+        w, h, fmt = self.width, self.height, self.src_format
+        fb = fmt.frame_bytes(w, h) if fmt is not None else w * h * 3 // 2 * (2 if self.bit_depth > 8 else 1)
+        dt = np.dtype('<u2') if (fmt.bit_depth if fmt is not None else self.bit_depth) > 8 else np.uint8
         n = 0
         while True:
             buf = self._p.stdout.read(fb)
             if len(buf) < fb:
                 break
-            a = np.frombuffer(buf, dt)
             n += 1
-            yield a[:w * h].reshape(h, w), a[w * h:w * h * 5 // 4].reshape(h // 2, w // 2), a[w * h * 5 // 4:].reshape(h // 2, w // 2)
+            yield _split_frame(np.frombuffer(buf, dt), w, h, fmt)
         rc = self._p.wait()
         self._err.seek(0, 2)
         self._err.seek(max(0, self._err.tell() - 2000))
@@ -138,21 +172,24 @@ class _PipeClip:
             pass
 
 
-def open_any(path: Path, info=None):
+def open_any(path: Path, info=None, native_formats: bool = True):
+    """native_formats=False: a container's frames are asked of ffmpeg as planar 4:2:0 whatever its own format (for a consumer without send_fmt)"""
     path = Path(path)
     if path.suffix.lower() in ('.y4m', '.yuv'):
         return open_clip(path)
     if shutil.which('ffmpeg') is None:
         raise RuntimeError(f'{path.name}: only .y4m/.yuv can be read without ffmpeg on this host')
-    return _PipeClip(path, info)
+    return _PipeClip(path, info, native_formats)
 
 
-def write_y4m(path: Path, frames, width: int, height: int, fps=30, bit_depth: int = 8):
+def write_y4m(path: Path, frames, width: int, height: int, fps=30, bit_depth: int = 8, chroma: int = 420, src_depth: Optional[int] = None):
+    """chroma: 420 / 422 / 444, the frames' planes in that shape; src_depth: the samples' own depth (9 .. 16) when it is not bit_depth's 8 or 10"""
     fr = Fraction(str(fps)).limit_denominator(1001)
-    tag = 'C420p10' if bit_depth > 8 else 'C420jpeg'
+    depth = src_depth if src_depth else (10 if bit_depth > 8 else 8)
+    tag = f'C{chroma}p{depth}' if depth > 8 else ('C420jpeg' if chroma == 420 else f'C{chroma}')
     with open(path, 'wb') as f:
         f.write(f'YUV4MPEG2 W{width} H{height} F{fr.numerator}:{fr.denominator} Ip A1:1 {tag}\n'.encode())
-        dt = np.dtype('<u2') if bit_depth > 8 else np.uint8
+        dt = np.dtype('<u2') if depth > 8 else np.uint8
         for y, u, v in frames:
             f.write(b'FRAME\n')
             for p in (y, u, v):

@@ -194,6 +194,33 @@ int  mihevc_send_frame_device(mihevc_session *s, const void *y, const void *u, c
  * at the first error.  Chunks that fill up on the way are coded inside the call, as with the one-picture form. */
 int  mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, const void *const *u, const void *const *v,
                                int pitch_y, int pitch_c, int64_t first_pts);
+/* ---- added under ABI 6: sources that are not the session's own layout (symbols only: no existing struct or function changes) ----
+ * A picture of the session's DISPLAY size in another sample layout, converted on the device into the session's planar 4:2:0 planes at cfg.bit_depth
+ * (hevc_amd/csrc/kernels/ingest.h states the arithmetic; DESIGN.md repeats it): 4:2:2 and 4:4:4 chroma is filtered down (the siting of
+ * chroma_sample_loc_type 0), deeper samples are rounded half up once, shallower ones shifted up, values above 2^bit_depth - 1 in an lsb-aligned plane are
+ * clamped.  Covers ffmpeg's yuv420p / yuv422p / yuv444p (and yuvj*), yuv4xxp{9,10,12,14,16}le, nv12 / nv16 / nv24, p010le / p016le / p210le / p216le /
+ * p410le / p416le.  Not covered (MIHEVC_EINVAL; hevc_amd._lib.src_format_for gives None): swapped semi-planar (nv21), packed formats (yuyv422, uyvy422,
+ * v210), RGB / gbrp, 4:1:1 / 4:1:0, big endian, alpha; there is no range conversion. */
+typedef struct mihevc_src_format {
+    int32_t chroma;        /* 420, 422, 444 */
+    int32_t semi_planar;   /* 0: y, u, v planes; 1: y + interleaved CbCr in u (Cb in the even elements), v is ignored */
+    int32_t bit_depth;     /* significant bits 8..16; > 8: little-endian uint16 elements */
+    int32_t msb_aligned;   /* 1 (bit_depth > 8 only): the bits sit at the top of the word (P010 ...) */
+    int32_t reserved[4];   /* 0 */
+} mihevc_src_format;
+
+#define MIHEVC_SRC_DEVICE 1   /* y/u/v are device pointers */
+#define MIHEVC_SRC_ASYNC  2   /* return with the upload in flight (the rules of mihevc_send_frame_async) */
+
+/* pitch_y, pitch_c: in elements of the plane (an interleaved plane: >= twice the chroma width).  Host planes are copied as they are into a staging set of
+ * the session and converted from there; without MIHEVC_SRC_ASYNC the caller's planes may be reused on return.  With MIHEVC_SRC_DEVICE the kernel reads the
+ * caller's planes where they are: their producer must have finished before the call, and they must stay valid and unmodified until mihevc_sync_uploads or
+ * mihevc_flush has returned (for every format: the planes are always copied or converted, never coded where they lie).  A format that already is the session's layout (420, planar, bit_depth == cfg.bit_depth, not msb_aligned) gives the byte-identical
+ * stream of mihevc_send_frame.  MIHEVC_EINVAL, decided before any device call and leaving the session usable: NULL fmt, chroma other than the three values,
+ * bit_depth outside 8..16, msb_aligned with 8 bits, non-zero reserved, odd cfg.width / cfg.height, a pitch smaller than the plane, unknown flag bits,
+ * slice_count > 1.  MIHEVC_ESTATE after flush. */
+int  mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v,
+                           int pitch_y, int pitch_c, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -314,6 +341,13 @@ int mihevc_k_picture_hash(int device, const void *y, const void *u, const void *
  * the SSIM of component c */
 int mihevc_k_ssim(int device, const void *a_y, const void *a_u, const void *a_v, const void *b_y, const void *b_u, const void *b_v,
                   int width, int height, int bit_depth, int64_t sum_q32[3], int64_t windows[3]);
+
+/* added under ABI 6.  The conversion of mihevc_send_frame_fmt alone (the session's kernel), host buffers in and out: width x height is the display size (both
+ * even), out_* are planes of the CODED size (rounded up to 8; chroma half of it each way) with pitch = coded width, uint8_t when out_bit_depth == 8 and
+ * uint16_t when 10.  Arguments are validated first (MIHEVC_EINVAL), then MIHEVC_ENODEV without a device */
+int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void *y, const void *u, const void *v,
+                            int width, int height, int pitch_y, int pitch_c, int out_bit_depth,
+                            void *out_y, void *out_u, void *out_v);
 
 /* ---- host-only stages (no device needed): bitstream ---- */
 /* VPS+SPS+PPS (+SEI when hdr10) as Annex-B into buf; returns size or negative error */
