@@ -89,7 +89,7 @@ EXPORTS = (
     "mihevc_get_recon", "mihevc_coded_size", "mihevc_get_frame_info", "mihevc_strerror", "mihevc_last_error", "mihevc_cost_params_for_qp", "mihevc_tile_grid", "mihevc_p_tile_grid", "mihevc_k_transform", "mihevc_k_transform_sdh",
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
-    "mihevc_send_frame_fmt", "mihevc_k_convert_source",
+    "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan",
 )
 
 _lib = None
@@ -142,6 +142,7 @@ def load() -> C.CDLL:
     lib.mihevc_k_transform.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32]
     lib.mihevc_k_transform_sdh.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32]
     lib.mihevc_k_intra_frame.argtypes = [i32, vp, vp, vp, i32, i32, C.POINTER(CostParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mihevc_k_intra_plan.argtypes = [i32, vp, vp, vp, i32, i32, C.POINTER(CostParams), vp]
     lib.mihevc_k_inter_frame.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(CostParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mihevc_k_b_frame.argtypes = [i32] + [vp] * 9 + [i32, i32, C.POINTER(CostParams)] + [vp] * 12
     lib.mihevc_k_deblock.argtypes = [i32, vp, vp, vp, i32, i32, vp, i32]

@@ -430,17 +430,26 @@ template <typename T> hipError_t launch_inter_ctu_b(hipStream_t st, const InterA
     return hipGetLastError();
 }
 
+// stage A: every CTU of every picture at once (the first launch of launch_intra_picture; alone: mihevc_k_intra_plan)
+template <typename T> static hipError_t launch_intra_plan(hipStream_t st, const IntraArgs<T> *d_args, int n_ctu, int batch)
+{
+    const size_t smem = round16(sizeof(IntraShared<T>));
+    hipError_t e = ensure_smem(k_intra_plan<T>, smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_intra_plan<T>, dim3((unsigned)(((n_ctu + 7) >> 3) << 3), (unsigned)batch), dim3(NT), smem, st, d_args, n_ctu);
+    return hipGetLastError();
+}
+
 template <typename T> hipError_t launch_intra_picture(hipStream_t st, const IntraArgs<T> *d_args, int ctus_w, int ctus_h, int batch, int tile_cols, int tile_rows, hipEvent_t after_plan)
 {
     size_t smem = round16(sizeof(IntraShared<T>));
-    hipError_t e = ensure_smem(k_intra_plan<T>, smem);
-    if (e != hipSuccess) return e;
-    e = ensure_smem(k_intra_diag<T>, smem);
+    hipError_t e = ensure_smem(k_intra_diag<T>, smem);
     if (e != hipSuccess) return e;
     if (tile_cols < 1) tile_cols = 1;
     if (tile_rows < 1) tile_rows = 1;
     const int n_ctu = ctus_w * ctus_h;
-    hipLaunchKernelGGL(k_intra_plan<T>, dim3((unsigned)(((n_ctu + 7) >> 3) << 3), (unsigned)batch), dim3(NT), smem, st, d_args, n_ctu);      // stage A: every CTU at once
+    e = launch_intra_plan<T>(st, d_args, n_ctu, batch);
+    if (e != hipSuccess) return e;
     if (after_plan) { e = hipEventRecord(after_plan, st); if (e != hipSuccess) return e; }      // from here on the stream runs the latency-bound anti-diagonal chain
     // stage B, per tile one anti-diagonal at a time; uniform spacing: the widest column / tallest row is ceil(n_ctb / n_tiles)
     const int colw = (ctus_w + tile_cols - 1) / tile_cols, rowh = (ctus_h + tile_rows - 1) / tile_rows;
@@ -716,6 +725,27 @@ int stage_intra(const void *const *s, int w, int h, const mihevc_cost_params *pr
     return out.download(cu, coef, est);
 }
 
+// the plan of every CTU as k_intra_plan leaves it for the code stage (IntraArgs::plan); bytes the kernel never writes (mode / cmode of nodes outside the
+// picture, pad) come back as 0
+static_assert(sizeof(IntraPlan) == sizeof(mihevc_intra_plan) && sizeof(IntraPlan) == 64, "mihevc_intra_plan is IntraPlan");
+template <typename T> int stage_intra_plan(const void *const *s, int w, int h, const mihevc_cost_params *prm, mihevc_intra_plan *plan)
+{
+    Planes3<T> src;
+    if (src.alloc(w, h, false)) return MIHEVC_ENOMEM;
+    if (int e = src.upload(s)) return e;
+    const size_t n_ctu = (size_t)ctus_of(w) * ctus_of(h);
+    DevBuf dplan, dargs;
+    CK(dplan.alloc(n_ctu * sizeof(IntraPlan)));
+    const Plane<T> none[3]{};       // the plan stage reads the source only
+    const IntraArgs<T> a = intra_args<T>(src.ro, none, w, h, cost_params_of(*prm), AnalysisOut{nullptr, {nullptr, nullptr, nullptr}, nullptr}, dplan.as<IntraPlan>());
+    if (int e = to_device(dargs, &a)) return e;
+    CK(launch_intra_plan<T>(0, dargs.as<IntraArgs<T>>(), (int)n_ctu, 1));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(plan, dplan.p, n_ctu * sizeof(IntraPlan), hipMemcpyDeviceToHost));
+    intra_plan_clear_unwritten(plan, w, h);
+    return 0;
+}
+
 // A P picture (f1 == nullptr) against the reference f0: border pad, search centres from the 1/4-size pictures (prm->pre_search without centres0),
 // the list-0 search, the P CTU program, the intra second pass (prm->intra_in_p).  A B picture between the anchors f0 (list 0) and f1 (list 1):
 // border pad of both, the list-0 and list-1 searches, the B CTU program.  centers*, me_dump*: per list, optional
@@ -950,6 +980,16 @@ int mihevc_k_intra_frame(int device, const void *sy, const void *su, const void 
     void *r[3] = {ry, ru, rv};
     int16_t *c[3] = {cy, cu_, cv};
     return with_depth(prm->bit_depth, [&](auto t) { return stage_intra<decltype(t)>(s, w, h, prm, r, cu, c, est); });
+}
+
+int mihevc_k_intra_plan(int device, const void *sy, const void *su, const void *sv, int w, int h, const mihevc_cost_params *prm, mihevc_intra_plan *plan)
+{
+    if (!sy || !su || !sv || !prm || !plan || !geometry_ok(w, h)) return MIHEVC_EINVAL;
+    if (prm->tile_cols > ctus_of(w) || prm->tile_rows > ctus_of(h)) return MIHEVC_EINVAL;
+    if (prm->bit_depth != 8 && prm->bit_depth != 10) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *s[3] = {sy, su, sv};
+    return with_depth(prm->bit_depth, [&](auto t) { return stage_intra_plan<decltype(t)>(s, w, h, prm, plan); });
 }
 
 int mihevc_k_inter_frame(int device, const void *sy, const void *su, const void *sv, const void *fy, const void *fu, const void *fv, int w, int h,

@@ -45,6 +45,22 @@ IntraArgs<T> intra_args(const Plane<const T> *src, const Plane<T> *rec, int w, i
     return a;
 }
 
+// what a stage entry that returns the plan (mihevc_k_intra_plan and its stepped twin) does to the bytes k_intra_plan never writes: mode / cmode of the
+// nodes that do not lie wholly inside the picture, and pad, come back as 0
+inline void intra_plan_clear_unwritten(mihevc_intra_plan *plan, int w, int h)
+{
+    for (int cy = 0; cy < ctus_of(h); cy++)
+        for (int cx = 0; cx < ctus_of(w); cx++) {
+            mihevc_intra_plan &p = plan[cy * ctus_of(w) + cx];
+            p.pad = 0;
+            for (int nd = 0; nd < 21; nd++) {
+                const int q = nd < 5 ? nd - 1 : (nd - 5) >> 2, sub = (nd - 5) & 3, n = nd == 0 ? 32 : nd < 5 ? 16 : 8;      // host form of node_geom
+                const int x = nd == 0 ? 0 : (q & 1) * 16 + (nd < 5 ? 0 : (sub & 1) * 8), y = nd == 0 ? 0 : (q >> 1) * 16 + (nd < 5 ? 0 : (sub >> 1) * 8);
+                if (cx * CTU + x + n > w || cy * CTU + y + n > h) p.mode[nd] = p.cmode[nd] = 0;
+            }
+        }
+}
+
 // the intra second pass of a P picture on the inter pass's reconstruction, records and levels (tile grid: the P pictures' own, from prm)
 template <typename T> IntraArgs<T> intra_in_p_args(const InterArgs<T> &e)
 {

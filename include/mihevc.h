@@ -307,6 +307,18 @@ int mihevc_k_intra_frame(int device, const void *src_y, const void *src_u, const
                          const mihevc_cost_params *prm, void *rec_y, void *rec_u, void *rec_v,
                          mihevc_cu_rec *cu, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v,
                          uint64_t *est_bits_q4 /* optional: the picture's rate estimate in 1/16 bit (rate control input) */);
+/* added under ABI 6 (symbols only).  Stage A of mihevc_k_intra_frame alone: the intra PLAN of every CTU (raster order), as the plan kernel leaves it in
+ * device memory for the code stage — 64 bytes per CTU.  Index = quadtree node: 0 the 32x32, 1..4 the 16x16 in z-order, 5..20 the 8x8 (the four of 16x16
+ * number 1 first, each group in z-order).  chosen[n] = 1: node n is a leaf (a CU) of the planned tree; mode[n] / cmode[n]: the luma / chroma intra
+ * prediction mode planned for node n, 0..34, decided for EVERY node that lies wholly inside the picture, chosen or not.  A node that does not: chosen 0,
+ * and mode / cmode carry nothing (the kernel never writes them); this entry returns them and `pad` as 0.  DESIGN.md §6 has the rules.  prm as for
+ * mihevc_k_intra_frame (qp, qp_c, bit_depth, lambda_sad_q4, lambda_q4, tile_cols / tile_rows, chroma_modes are read); a tile grid with more columns /
+ * rows than the picture has CTUs: MIHEVC_EINVAL */
+typedef struct mihevc_intra_plan {
+    uint8_t chosen[21], mode[21], cmode[21], pad;
+} mihevc_intra_plan;
+int mihevc_k_intra_plan(int device, const void *src_y, const void *src_u, const void *src_v, int width, int height,
+                        const mihevc_cost_params *prm, mihevc_intra_plan *plan_out);
 /* K1+K3: inter picture analysis against one (unpadded) reference reconstruction */
 int mihevc_k_inter_frame(int device, const void *src_y, const void *src_u, const void *src_v,
                          const void *ref_y, const void *ref_u, const void *ref_v, int width, int height,

@@ -1277,7 +1277,8 @@ static int intra_mode_bits(const int cand[3], int mode)
  *   tree: bottom-up, split = lambda + children, whole = J + lambda, whole wins ties */
 typedef struct { uint8_t chosen[21], mode[21], cmode[21]; } intra_plan;
 
-static void intra_plan_ctu(const intra_ctx *c, int x0, int y0, intra_plan *pl)
+/* detail: NULL, or 21 records that receive every candidate's cost (orc_intra_plan_frame; diagnosis only, nothing is decided from them) */
+static void intra_plan_ctu(const intra_ctx *c, int x0, int y0, intra_plan *pl, orc_intra_plan_node *detail)
 {
     const orc_params *prm = c->prm;
     const int bd = prm->bit_depth, lam = prm->lambda_sad_q4;
@@ -1285,6 +1286,7 @@ static void intra_plan_ctu(const intra_ctx *c, int x0, int y0, intra_plan *pl)
     uint64_t J[21];
     pix ref[129], filt[129], pred[32 * 32];
     memset(pl, 0, sizeof *pl);
+    if (detail) memset(detail, 0, 21 * sizeof *detail);
     for (int nd = 0; nd < 21; nd++) {
         node_geom(nd, &nx[nd], &ny[nd], &nl[nd]);
         valid[nd] = x0 + nx[nd] + (1 << nl[nd]) <= c->w && y0 + ny[nd] + (1 << nl[nd]) <= c->h;
@@ -1316,6 +1318,7 @@ static void intra_plan_ctu(const intra_ctx *c, int x0, int y0, intra_plan *pl)
                 orc_intra_pred(filt, pred, n, log2n, mode, 0, bd);
                 uint32_t cst = ((uint32_t)orc_satd(s, c->sstride[0], pred, n, n, n) << 4) + (uint32_t)(lam * intra_mode_bits(cand, mode));
                 uint64_t key = ((uint64_t)cst << 6) | (uint32_t)mode;
+                if (detail) detail[nd].luma_cost[mode] = cst;
                 if (key < best) best = key;
             }
             const int mode = (int)(best & 63);
@@ -1336,6 +1339,7 @@ static void intra_plan_ctu(const intra_ctx *c, int x0, int y0, intra_plan *pl)
                         satd += (uint32_t)orc_satd(c->src[ci] + yc * c->sstride[ci] + xc, c->sstride[ci], pred, nc, nc, nc);
                     }
                     uint64_t key = ((uint64_t)((satd << 4) + (uint32_t)(lam * (k == 0 ? 1 : 3))) << 3) | (uint32_t)k;
+                    if (detail) detail[nd].chroma_cost[k] = (uint32_t)(key >> 3);
                     if (key < bestc) bestc = key;
                 }
                 int k = (int)(bestc & 7);
@@ -1361,6 +1365,7 @@ static void intra_plan_ctu(const intra_ctx *c, int x0, int y0, intra_plan *pl)
                     sse_total += sse; bits_total += bits;
                 }
                 J[nd] = ((uint64_t)sse_total << 4) + (((uint64_t)prm->lambda_q4 * (uint64_t)bits_total) >> 4);
+                if (detail) { detail[nd].j = J[nd]; detail[nd].sse = (uint64_t)sse_total; detail[nd].bits_q4 = (uint32_t)bits_total; }
             }
             (void)cost;
         }
@@ -1588,7 +1593,7 @@ static void intra_in_p_pass(const pix *src_y, const pix *src_u, const pix *src_v
                 for (int yy = 0; yy < bh / 8; yy++)
                     for (int xx = 0; xx < bw / 8; xx++) scu[yy * 4 + xx] = cu[((y0 >> 3) + yy) * c.w8 + (x0 >> 3) + xx];
                 intra_plan pl;
-                intra_plan_ctu(&c, x0, y0, &pl);
+                intra_plan_ctu(&c, x0, y0, &pl, NULL);
                 uint64_t jintra = intra_code_ctu(&c, x0, y0, &pl);
                 if (jintra < jinter[cy * wc + cx]) continue;
                 for (int ci = 0; ci < 3; ci++) {
@@ -1616,10 +1621,30 @@ void orc_analyze_intra_frame(const pix *src_y, const pix *src_u, const pix *src_
     for (int y = 0; y < h; y += ORC_CTU)
         for (int x = 0; x < w; x += ORC_CTU) {
             intra_plan pl;
-            intra_plan_ctu(&c, x, y, &pl);
+            intra_plan_ctu(&c, x, y, &pl, NULL);
             intra_code_ctu(&c, x, y, &pl);
         }
     if (est) *est = estimate_bits(cu, coef_y, coef_u, coef_v, w, h, NULL);
+}
+
+/* stage A alone: the plan of every CTU in raster order, 64 bytes each (chosen[21], mode[21], cmode[21], one 0 byte: the device's IntraPlan; mode /
+ * cmode of a node that is not wholly inside the picture: 0).  detail: NULL, or 21 records per CTU with the costs behind the decisions */
+void orc_intra_plan_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride, int w, int h, const orc_params *prm,
+                          uint8_t *plan, orc_intra_plan_node *detail)
+{
+    intra_ctx c;
+    memset(&c, 0, sizeof c);
+    c.src[0] = src_y; c.src[1] = src_u; c.src[2] = src_v;
+    c.sstride[0] = src_stride; c.sstride[1] = c.sstride[2] = src_cstride;
+    c.w = w; c.h = h; c.w8 = w >> 3; c.prm = prm;
+    int ctu = 0;
+    for (int y = 0; y < h; y += ORC_CTU)
+        for (int x = 0; x < w; x += ORC_CTU, ctu++) {
+            intra_plan pl;
+            intra_plan_ctu(&c, x, y, &pl, detail ? detail + 21 * ctu : NULL);
+            memcpy(plan + 64 * ctu, &pl, sizeof pl);
+            plan[64 * ctu + 63] = 0;
+        }
 }
 
 /* ================================================================================================

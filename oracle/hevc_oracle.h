@@ -147,6 +147,16 @@ void orc_analyze_intra_frame(const pix *src_y, const pix *src_u, const pix *src_
                              int w, int h, const orc_params *prm,
                              pix *rec_y, pix *rec_u, pix *rec_v, int rec_stride, int rec_cstride,
                              orc_cu_rec *cu, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v, uint64_t *est);
+/* the intra plan alone (stage A of orc_analyze_intra_frame): per CTU 64 bytes = chosen[21], mode[21], cmode[21], 0.  detail (optional, 21 per CTU,
+ * zero for nodes outside the picture): what every candidate cost, for diagnosis */
+typedef struct {
+    uint32_t luma_cost[35];     /* (SATD << 4) + lambda_sad_q4 * bits of every luma mode */
+    uint32_t chroma_cost[5];    /* the same of DM, planar, 26, 10, DC (all 0 with chroma_modes = 0) */
+    uint32_t bits_q4;           /* the node's estimated bits in 1/16 bit */
+    uint64_t sse, j;            /* squared error over Y + Cb + Cr, J = (sse << 4) + ((lambda_q4 * bits_q4) >> 4) */
+} orc_intra_plan_node;
+void orc_intra_plan_frame(const pix *src_y, const pix *src_u, const pix *src_v, int src_stride, int src_cstride, int w, int h, const orc_params *prm,
+                          uint8_t *plan, orc_intra_plan_node *detail);
 /* K4a: deblocking, in place on rec_* (clause 8.7.2) */
 void orc_deblock_frame(pix *rec_y, pix *rec_u, pix *rec_v, int stride, int cstride, int w, int h,
                        const orc_cu_rec *cu, int bit_depth, int deblock_chroma_qp_offset);

@@ -203,6 +203,22 @@ def analyze_intra(src: Frame, prm: Params) -> Analysis:
     return a
 
 
+INTRA_PLAN_DTYPE = np.dtype([("chosen", "u1", (21,)), ("mode", "u1", (21,)), ("cmode", "u1", (21,)), ("pad", "u1")])
+INTRA_PLAN_NODE_DTYPE = np.dtype([("luma_cost", "<u4", (35,)), ("chroma_cost", "<u4", (5,)), ("bits_q4", "<u4"), ("pad", "<u4"), ("sse", "<u8"), ("j", "<u8")])
+assert INTRA_PLAN_DTYPE.itemsize == 64 and INTRA_PLAN_NODE_DTYPE.itemsize == 184
+
+
+def intra_plan(src: Frame, prm: Params, detail=False):
+    """The intra plan of every CTU (orc_intra_plan_frame): INTRA_PLAN_DTYPE per CTU in raster order; with detail also (n_ctu, 21) INTRA_PLAN_NODE_DTYPE, the
+    costs of every candidate of every node (zero for nodes outside the picture)."""
+    h, w = src.shape
+    n_ctu = ((w + CTU - 1) // CTU) * ((h + CTU - 1) // CTU)
+    plan = np.zeros(n_ctu, INTRA_PLAN_DTYPE)
+    nodes = np.zeros((n_ctu, 21), INTRA_PLAN_NODE_DTYPE) if detail else None
+    lib().orc_intra_plan_frame(_p(src.y), _p(src.u), _p(src.v), w, w // 2, w, h, C.byref(prm), _p(plan), _p(nodes) if detail else None)
+    return (plan, nodes) if detail else plan
+
+
 def analyze_inter(src: Frame, ref: Frame, prm: Params, centers=None, dump_me=False) -> Analysis:
     """ref: the UNPADDED reference reconstruction; padding happens here"""
     h, w = src.shape

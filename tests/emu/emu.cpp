@@ -229,6 +229,23 @@ static int intra_frame(const void *const *s, int w, int h, const CostParams &prm
     return 0;
 }
 
+// stage A alone, every CTU in raster order: the twin of mihevc_k_intra_plan
+template <typename T> static int intra_plan(const void *const *s, int w, int h, const CostParams &prm, mihevc_intra_plan *plan)
+{
+    const Plane<T> none[3]{};
+    static_assert(sizeof(IntraPlan) == sizeof(mihevc_intra_plan), "mihevc_intra_plan is IntraPlan");
+    const int n_ctu = ctus_of(w) * ctus_of(h);
+    memset(plan, 0, (size_t)n_ctu * sizeof *plan);
+    const IntraArgs<T> a = intra_args<T>(Views<const T>(s, w).p, none, w, h, prm, AnalysisOut{nullptr, {nullptr, nullptr, nullptr}, nullptr}, (IntraPlan *)plan);
+    Stepper step;
+    for (int c = 0; c < n_ctu; c++) {
+        Shared<IntraShared<T>> is = fresh_shared<IntraShared<T>>();
+        if (!step(211u * (unsigned)c, [&](auto &ex) { intra_plan_program<T>(ex, *is, a, c % a.ctus_w, c / a.ctus_w); })) return -2;
+    }
+    intra_plan_clear_unwritten(plan, w, h);
+    return 0;
+}
+
 // row0 / y_org: deblock rows [row0, row0 + h) of a whole picture's planes as a picture of its own whose first y_org rows belong to the slice above
 // (DeblockArgs::y_org; the band extended by the rows its neighbours hand over, csrc/slice_group.h)
 template <typename T> static int deblock(void *const *r, int w, int h, const mihevc_cu_rec *cu, int bit_depth, int row0 = 0, int y_org = 0)
@@ -286,6 +303,12 @@ int emu_intra_frame(const void *sy, const void *su, const void *sv, int w, int h
     void *o[3] = {oy, ou, ov};
     int16_t *c[3] = {cy, cu_, cv};
     return with_depth(prm->bit_depth, [&](auto t) { return intra_frame<decltype(t)>(s, w, h, cost_params_of(*prm, sign_hide), o, cu, c, est); });
+}
+int emu_intra_plan(const void *sy, const void *su, const void *sv, int w, int h, const mihevc_cost_params *prm, mihevc_intra_plan *plan, int sign_hide)
+{
+    if (prm->tile_cols > ctus_of(w) || prm->tile_rows > ctus_of(h)) return MIHEVC_EINVAL;
+    const void *s[3] = {sy, su, sv};
+    return with_depth(prm->bit_depth, [&](auto t) { return intra_plan<decltype(t)>(s, w, h, cost_params_of(*prm, sign_hide), plan); });
 }
 int emu_deblock(void *y, void *u, void *v, int w, int h, const mihevc_cu_rec *cu, int bit_depth)
 {

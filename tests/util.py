@@ -1,5 +1,6 @@
 """Shared helpers of the test-suite: deterministic synthetic pictures and array plumbing between the oracle
 (uint16 containers) and the product C ABI (uint8 planes at 8 bit, uint16 at 10 bit)."""
+import collections
 import ctypes as C
 import functools
 import os
@@ -199,6 +200,14 @@ class StageApi:
                    ptr(a.coef_u), ptr(a.coef_v), C.byref(est))
         a.rec, a.est = to_frame(o), est.value
         return a
+
+    def intra_plan(self, src: O.Frame, prm):
+        """the plan stage alone (mihevc_k_intra_plan / emu_intra_plan): O.INTRA_PLAN_DTYPE per CTU"""
+        h, w = src.shape
+        s = planes(src, prm.bit_depth)
+        plan = np.zeros(n_ctus(w, h), O.INTRA_PLAN_DTYPE)
+        self._call("intra_plan", ptr(s[0]), ptr(s[1]), ptr(s[2]), w, h, C.byref(prm), ptr(plan))
+        return plan
 
     def inter(self, src: O.Frame, ref: O.Frame, prm, centers=None):
         return self._inter(src, [ref], prm, [centers])
@@ -518,3 +527,143 @@ ALL_SAO_KINDS = {p + k for p in ("luma ", "chroma ") for k in ("off", "band", "e
 def sao_diff(a, b):
     i = np.nonzero([x.tobytes() != y.tobytes() for x, y in zip(a, b)])[0]
     return f"{len(i)} CTUs differ, first {i[0]}: {a[i[0]]} vs {b[i[0]]}" if len(i) else "equal"
+
+
+# ================================================================ cases of the intra plan audit (tests/test_intra_plan_independent.py on the CPU, tests/test_gpu_intra_plan_independent.py on the device)
+PLAN_QPS = (22, 32, 42)
+PlanCase = namedtuple("PlanCase", "id w h bd qp chroma_modes content tiles lam", defaults=(None,))      # lam: None, or (lambda_sad_q4, lambda_q4) in place of the QP's own
+
+
+def _plan_cases():
+    out = [PlanCase(f"{w}x{h}-{bd}bit-qp{qp}-cm{cm}", w, h, bd, qp, cm, "synth", (1, 1)) for (w, h) in SIZES for bd in (8, 10) for qp in PLAN_QPS for cm in (0, 1)]
+    for e in ENVELOPE_STAGE_CASES:                                            # rails content at QP 45, both bit depths
+        if e[5] == "rails" and e[2] == 45:
+            out.append(PlanCase("rails-%dx%d-%dbit-qp45" % (e[0], e[1], e[3]), e[0], e[1], e[3], 45, 1, "rails", (1, 1)))
+    out += [PlanCase(f"drawn{i}-224x160-8bit-qp27", 224, 160, 8, 27, 1, f"drawn{i}", (1, 1)) for i in range(2)]     # the hand-drawn all-modes pictures
+    out.append(PlanCase("fan-224x160-10bit-qp30", 224, 160, 10, 30, 1, "fan", (1, 1)))
+    out.append(PlanCase("tiles2x2-40x40-8bit-qp32", 40, 40, 8, 32, 1, "synth", (2, 2)))     # 2 x 2 CTUs: the smallest picture a 2 x 2 grid fits
+    out.append(PlanCase("tiles2x2-136x72-10bit-qp27", 136, 72, 10, 27, 1, "synth", (2, 2)))
+    # the hand-made pictures of tests/test_intra_plan_independent.py whose answer hangs on an exact tie or on a threshold, so that the device meets them too:
+    # lambda_q4 = 0 on a flat CTU and on column stripes (whole == split == 0 at both levels of the tree), the DM tie (lambda_sad_q4 8: DM and horizontal cost
+    # 3000 each in CTU 3, node 8) and one less, the 32x32 reference line that passes the strong-smoothing test by one and the one that misses it
+    out.append(PlanCase("flat-32x32-8bit-lam0", 32, 32, 8, 22, 1, "flat", (1, 1), (38, 0)))
+    out.append(PlanCase("stripes-64x64-8bit-lam0", 64, 64, 8, 22, 1, "stripes", (1, 1), (38, 0)))
+    out.append(PlanCase("dmtie-64x64-8bit-lamsad8", 64, 64, 8, 22, 1, "synth", (1, 1), (8, 92)))
+    out.append(PlanCase("dmtie-64x64-8bit-lamsad7", 64, 64, 8, 22, 1, "synth", (1, 1), (7, 92)))
+    for bd in (8, 10):
+        out += [PlanCase(f"line{d}-96x64-{bd}bit-qp22", 96, 64, bd, 22, 1, f"line{d}", (1, 1)) for d in ((7, 8) if bd == 8 else (31, 32))]
+    assert len({c.id for c in out}) == len(out)
+    return out
+
+
+PLAN_CASES = _plan_cases()
+# the device file's share: 64x64 and 136x72, both bit depths, QP 22 and 42, chroma modes on, and the tiled cases
+GPU_PLAN_CASES = [c for c in PLAN_CASES if (c.content == "synth" and c.tiles == (1, 1) and (c.w, c.h) in ((64, 64), (136, 72)) and c.qp in (22, 42) and c.chroma_modes) or
+                  c.tiles != (1, 1) or c.lam is not None or c.content.startswith("line")]
+
+
+def fan_picture(w, h, bd):
+    """every CTU striped along the direction of one angular mode, 2..34 in raster order (then planar-like and flat CTUs): along a vertical mode of angle A
+    (Table 8-4, in 1/32 sample per row) the picture is constant on the lines x + y A / 32 = const, along a horizontal mode on y + x A / 32 = const.  The
+    encoder's own pictures and the drawn ones leave some of the 35 modes unpicked; here a block inside CTU k has mode 2 + k as its exact predictor."""
+    angle = (32, 26, 21, 17, 13, 9, 5, 2, 0, -2, -5, -9, -13, -17, -21, -26, -32, -26, -21, -17, -13, -9, -5, -2, 0, 2, 5, 9, 13, 17, 21, 26, 32)
+    rng = np.random.default_rng(12)
+    top = (1 << bd) - 1
+    prof = np.clip(np.repeat(rng.integers(top // 8, top - top // 8, 64), 3)[:160] + rng.integers(-2, 3, 160), 0, top)      # steps three lines wide
+    yy, xx = np.mgrid[0:32, 0:32]
+    y = np.zeros((h, w), np.int64)
+    for k, (cy, cx) in enumerate((cy, cx) for cy in range(0, h, 32) for cx in range(0, w, 32)):
+        if k < 33:
+            a = angle[k]
+            t = (32 * xx + a * yy if k + 2 >= 18 else 32 * yy + a * xx) + 32 * 32
+            f = t % 32
+            blk = ((32 - f) * prof[t // 32] + f * prof[t // 32 + 1] + 16) >> 5
+        else:
+            blk = np.full((32, 32), prof[k]) + (xx + yy if k == 33 else 0)
+        y[cy:cy + 32, cx:cx + 32] = blk[:h - cy, :w - cx]
+    c = (y[::2, ::2] + y[1::2, 1::2]) // 2
+    return O.Frame(y, c, top - c)
+
+
+STRIPE = (40, 200, 90, 160, 20, 230, 120, 60)
+PLAN_SOURCES = {}            # content -> function(w, h, bd) -> O.Frame, for pictures a test module makes (the drawn pictures: tests/test_intra_plan_independent.py)
+
+
+def smoothing_line_picture(w, h, bd, d):
+    """flat but for two samples of the row above CTU (1, 1): the 32x32 node's top reference line has |corner + last - 2 middle| = d (8.4.4.2.3)"""
+    v = 100 << (bd - 8)
+    y = np.full((h, w), v)
+    y[31, 63], y[31, 95] = v - 3, v + d - 6
+    c = np.full((h // 2, w // 2), 1 << (bd - 1))
+    return O.Frame(y, c, c)
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case_source(content, w, h, bd):
+    if content in PLAN_SOURCES:
+        return PLAN_SOURCES[content](w, h, bd)
+    if content == "synth":
+        return crop(w, h, bd, 0, 0)
+    if content == "fan":
+        return fan_picture(w, h, bd)
+    if content == "flat":
+        v = np.full((h, w), 1 << (bd - 1))
+        return O.Frame(v, v[::2, ::2], v[::2, ::2])
+    if content == "stripes":
+        col = np.tile(np.array(STRIPE * (w // 8)) << (bd - 8), (h, 1))
+        return O.Frame(col, col[::2, ::2], col[::2, ::2])
+    if content.startswith("line"):
+        return smoothing_line_picture(w, h, bd, int(content[4:]))
+    return envelope_frame(content, h, w, bd, 3)
+
+
+PLAN_COVERAGE = collections.Counter()                            # what the MODEL reached over every case it was asked for
+
+
+@functools.lru_cache(maxsize=None)
+def plan_model(content, w, h, bd, tiles):
+    """the model of one picture: the part of its work that does not depend on the cost parameters is done once for all QPs"""
+    from tests import hevc_intra_plan as M
+    return M.IntraPlanModel(planes3(plan_case_source(content, w, h, bd)), bd, tiles[0], tiles[1], PLAN_COVERAGE)
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case_want(c):
+    """(model's plan, oracle parameters, product parameters)"""
+    knobs = dict(chroma_modes=c.chroma_modes, tile_cols=c.tiles[0], tile_rows=c.tiles[1])
+    if c.lam is not None:
+        knobs.update(lambda_sad_q4=c.lam[0], lambda_q4=c.lam[1])
+    prm, cp = params_pair(c.qp, c.bd, 8, **knobs)
+    return plan_model(c.content, c.w, c.h, c.bd, c.tiles).plan(cp.qp, cp.qp_c, cp.lambda_sad_q4, cp.lambda_q4, c.chroma_modes), prm, cp
+
+
+def plan_diff(a, b):
+    for ctu in range(len(a)):
+        for f in ("chosen", "mode", "cmode", "pad"):
+            if not np.array_equal(a[ctu][f], b[ctu][f]):
+                nd = np.nonzero(np.atleast_1d(a[ctu][f] != b[ctu][f]))[0]
+                return f"CTU {ctu} {f}: nodes {nd.tolist()}: {np.atleast_1d(a[ctu][f])[nd].tolist()} vs {np.atleast_1d(b[ctu][f])[nd].tolist()}"
+    return "equal"
+
+
+def check_records_carry_the_plan(plan, cu, w, h, nxn):
+    """every CU record lies in a chosen leaf of its CTU's plan and has that leaf's size; its modes are the leaf's (records of an NxN CU: the size only)"""
+    from tests import hevc_analysis as A2
+    wc = (w + 31) // 32
+    seen = np.zeros(cu.shape, bool)
+    for ctu in range(len(plan)):
+        x0, y0 = ctu % wc * 32, ctu // wc * 32
+        for nd, (x, y, n) in enumerate(A2.NODES):
+            if not plan[ctu]["chosen"][nd]:
+                continue
+            r = cu[(y0 + y) // 8:(y0 + y + n) // 8, (x0 + x) // 8:(x0 + x + n) // 8]
+            assert r.size == (n // 8) ** 2 and not seen[(y0 + y) // 8:(y0 + y + n) // 8, (x0 + x) // 8:(x0 + x + n) // 8].any(), (ctu, nd)
+            seen[(y0 + y) // 8:(y0 + y + n) // 8, (x0 + x) // 8:(x0 + x + n) // 8] = True
+            assert (r["log2_size"] == n.bit_length() - 1).all(), f"CTU {ctu} node {nd}: the plan's leaf is {n}, the records say {r['log2_size'].tolist()}"
+            assert not (r["flags"] & 1).any()
+            is_nxn = (r["flags"] & 16) != 0
+            assert nxn or not is_nxn.any()
+            keep = ~is_nxn
+            assert (r["intra_mode"][..., 0][keep] == plan[ctu]["mode"][nd]).all() and (r["chroma_mode"][keep] == plan[ctu]["cmode"][nd]).all(), \
+                f"CTU {ctu} node {nd}: planned {plan[ctu]['mode'][nd]} / {plan[ctu]['cmode'][nd]}, coded {r['intra_mode'][..., 0].tolist()} / {r['chroma_mode'].tolist()}"
+    assert seen.all(), "a CU record outside every chosen leaf"
