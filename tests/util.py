@@ -667,3 +667,219 @@ def check_records_carry_the_plan(plan, cu, w, h, nxn):
             assert (r["intra_mode"][..., 0][keep] == plan[ctu]["mode"][nd]).all() and (r["chroma_mode"][keep] == plan[ctu]["cmode"][nd]).all(), \
                 f"CTU {ctu} node {nd}: planned {plan[ctu]['mode'][nd]} / {plan[ctu]['cmode'][nd]}, coded {r['intra_mode'][..., 0].tolist()} / {r['chroma_mode'].tolist()}"
     assert seen.all(), "a CU record outside every chosen leaf"
+
+
+# ================================================================ cases of the inter CTU program's audit (tests/test_inter_cu_independent.py on the CPU, tests/test_gpu_inter_cu_independent.py on the device)
+# content: "crop" = the search audit's pure translation by `shift`; "flat"; "warpG" = every G x G block of the current picture is the reference predicted at a
+# quarter-sample vector of its own through the standard's filter (tests/hevc_recon.py), + noise of +-`noise`; B pictures ("b-..."): the blocks are predicted from
+# list 0, list 1 or both.  "soft-" in front: the reference(s) at an eighth of their contrast, so that the ring's candidates predict nearly the same block and the
+# noise decides between them by a few units of SATD.  mvs: None = drawn per block from `seed` (|mv| < 4 me_range), or the vectors themselves, dealt to the blocks in raster order.
+InterCase = namedtuple("InterCase", "id w h bd R qp content seed shift noise mvs centres pre_search rdo_zero mc lam rdo_cg")
+
+
+def inter_case(id, w, h, bd, R, qp, content, seed=1, shift=(0, 0), noise=0, mvs=None, centres=None, pre_search=0, rdo_zero=0, mc=(0, 0), lam=None, rdo_cg=0):
+    return InterCase(id, w, h, bd, R, qp, content, seed, shift, noise, mvs, centres, pre_search, rdo_zero, mc, lam, rdo_cg)
+
+
+def warp_picture(refs, w, h, bd, g, seed, noise, mvs, lists, reach):
+    """refs: one or two O.Frame; every g x g block of the result is 8.5.3.3.3 + 8.5.3.3.4.2 of the references (reads clamped to the picture, as a decoder's)
+    at the block's own vector(s); lists: per block 0 / 1 / 2 (list 0, list 1, both), dealt in raster order like mvs.  -> (picture, [(x, y, lists, mv0, mv1)])"""
+    from tests import hevc_recon as HR
+    rng = np.random.default_rng(seed)
+    out = [np.zeros((h, w), np.int64), np.zeros((h // 2, w // 2), np.int64), np.zeros((h // 2, w // 2), np.int64)]
+    rp = [planes3(r) for r in refs]
+    blocks = []
+    for i, (y, x) in enumerate((y, x) for y in range(0, h, g) for x in range(0, w, g)):
+        mv = [tuple(mvs[(2 * i + l) % len(mvs)]) if mvs is not None else tuple(int(v) for v in rng.integers(-reach, reach + 1, 2)) for l in range(2)]
+        mode = lists[i % len(lists)]
+        bw, bh = min(g, w - x), min(g, h - y)
+        n = max(bw, bh)                                                  # (a block cut by the picture's edge is predicted whole and cropped)
+        for c in range(3):
+            sh = 1 if c else 0
+            mc = HR.mc_chroma if c else HR.mc_luma
+            p = HR.weighted_default([mc(rp[l][c].astype(np.int64), x >> sh, y >> sh, n >> sh, mv[l], bd) for l in range(2) if mode == 2 or mode == l], bd)
+            out[c][y >> sh:(y + bh) >> sh, x >> sh:(x + bw) >> sh] = p[:bh >> sh, :bw >> sh]
+        blocks.append((x, y, mode, mv[0], mv[1]))
+    if noise:
+        out = [np.clip(p + rng.integers(-noise, noise + 1, p.shape), 0, (1 << bd) - 1) for p in out]
+    return O.Frame(*out), blocks
+
+
+@functools.lru_cache(maxsize=None)
+def inter_case_pictures(c):
+    """(current picture, (reference,) or (list-0 anchor, list-1 anchor), planted blocks or None)"""
+    if c.content == "flat":
+        cur, ref = flat_pair(c.w, c.h, c.bd)
+        return cur, (ref,), None
+    if c.content == "crop":
+        return crop(c.w, c.h, c.bd, *c.shift), (crop(c.w, c.h, c.bd, 0, 0),), None
+    kind, g = c.content.rstrip("0123456789"), int(c.content[len(c.content.rstrip("0123456789")):])
+    soft = kind.startswith("soft-")
+    kind = kind[5:] if soft else kind
+
+    def anchor(ox, oy):
+        f = crop(c.w, c.h, c.bd, ox, oy)
+        if soft:
+            mid = 128 << (c.bd - 8)
+            f = O.Frame(*[(p.astype(np.int64) - mid) // 8 + mid for p in (f.y, f.u, f.v)])
+        return f
+    ref0 = anchor(0, 0)
+    reach = 4 * c.R - 6
+    if kind == "warp":
+        cur, blocks = warp_picture([ref0], c.w, c.h, c.bd, g, c.seed, c.noise, c.mvs, (0,), reach)
+        return cur, (ref0,), blocks
+    if kind in ("b-avg", "b-first", "b-second"):                  # the pins: the second anchor is the first, 2 samples to the right and 1 up, + noise of +-4, so both lists find
+        rng = np.random.default_rng(8)                             # the planted vectors (list 1's = list 0's - (8, -4)), each with an error that their average does not have
+        ref1 = O.Frame(*[np.clip(p.astype(np.int64) + rng.integers(-4, 5, p.shape) * (1 << (c.bd - 8)), 0, (1 << c.bd) - 1) for p in planes3(crop(c.w, c.h, c.bd, 2, -1))])
+    else:
+        ref1 = ref0 if kind == "b-same" else anchor(9, -5)
+    lists = {"b-avg": (2,), "b-first": (0,), "b-second": (1,), "b-same": (0,), "b-mix": (2, 0, 1, 1, 2, 0, 0)}[kind]
+    cur, blocks = warp_picture([ref0, ref1], c.w, c.h, c.bd, g, c.seed, c.noise, c.mvs, lists, reach)
+    return cur, (ref0, ref1), blocks
+
+
+def inter_case_centres(c, n_refs):
+    """per reference None or (n_ctu, 2)"""
+    if c.centres is None:
+        return [None] * n_refs
+    if c.centres == "corners":
+        return [case_centres(c, salt=l) for l in range(n_refs)]
+    return [np.tile(np.array([c.centres[l]], np.int16), (n_ctus(c.w, c.h), 1)) for l in range(n_refs)]
+
+
+def inter_case_params(c):
+    knobs = dict(pre_search=c.pre_search, rdo_zero=c.rdo_zero, mc_top=c.mc[0], mc_bottom=c.mc[1], rdo_cg=c.rdo_cg)
+    if c.lam is not None:
+        knobs.update(lambda_sad_q4=c.lam[0], lambda_q4=c.lam[1])
+    return params_pair(c.qp, c.bd, c.R, **knobs)
+
+
+INTER_COVERAGE = {}                                              # case id -> what the MODEL reached in it
+
+
+@functools.lru_cache(maxsize=None)
+def inter_case_want(c):
+    """(the model's analysis, the integer tables it started from, the centres given to the entry points): computed once per case"""
+    from tests import hevc_inter_cu as M
+    _, cp = inter_case_params(c)
+    cur, refs, _ = inter_case_pictures(c)
+    cen = inter_case_centres(c, len(refs))
+    given = list(cen)
+    if c.pre_search:
+        cen = [A.pre_search(A.lowres(cur.y, c.bd), A.lowres(refs[0].y, c.bd))]
+    cen_search = cen
+    if c.mc[0] or c.mc[1]:                                       # a slice: the search runs around the clamped centre
+        wc = (c.w + 31) // 32
+        cen_search = []
+        for k in cen:
+            k = np.zeros((n_ctus(c.w, c.h), 2), np.int16) if k is None else np.array(k, np.int16)
+            for i in range(len(k)):
+                k[i, 1] = M.clamp_centre_y(int(k[i, 1]), i // wc * 32, c.R, c.h, *c.mc)
+            cen_search.append(k)
+    me = [M.integer_table(cur.y, r.y, c.bd, c.R, cp.lambda_sad_q4, k, *c.mc) for r, k in zip(refs, cen_search)]
+    cov = INTER_COVERAGE[c.id] = collections.Counter()
+    want = M.analyse(planes3(cur), [planes3(r) for r in refs], me, c.bd, cp.qp, cp.qp_c, cp.lambda_sad_q4, cp.lambda_q4, c.R, cen, c.rdo_zero, c.mc[0], c.mc[1], cov)
+    return want, me, given
+
+
+def _inter_cases():
+    out = []
+    # the matrix: size x bit depth x me_range x QP x rdo_zero; content and noise follow from the index so that every grid size meets every size and depth
+    i = 0
+    for (w, h) in SIZES:
+        for bd in (8, 10):
+            for R in (8, 15):
+                for qp in SAO_QPS:
+                    for rz in (0, 1):
+                        g = (8, 16, 32)[(i // 2 + i // 12) % 3]
+                        out.append(inter_case(f"warp{g}-{w}x{h}-{bd}bit-R{R}-qp{qp}-rz{rz}", w, h, bd, R, qp, f"warp{g}", seed=i // 2, noise=(1 + i // 2 % 3) << (bd - 8), rdo_zero=rz))
+                        i += 1
+    for k, (w, h) in enumerate(SIZES):                               # translations, explicit centres up to +-56, the pre-search
+        bd = (8, 10)[k % 2]
+        out.append(inter_case(f"crop-{w}x{h}-{bd}bit-R8", w, h, bd, 8, 27, "crop", shift=(5, -3), rdo_zero=1))
+        out.append(inter_case(f"centres-{w}x{h}-{bd}bit-R15", w, h, bd, 15, 32, "crop", shift=(-50, 44), centres="corners", rdo_zero=k & 1))
+        out.append(inter_case(f"centres-{w}x{h}-{18 - bd}bit-R8", w, h, 18 - bd, 8, 22, "crop", shift=(40, 52), centres="corners", rdo_zero=1 - (k & 1)))
+        out.append(inter_case(f"presearch-{w}x{h}-{bd}bit-R8", w, h, bd, 8, 32, "crop", shift=(38, -22), pre_search=1, rdo_zero=1))
+        out.append(inter_case(f"presearch-{w}x{h}-{18 - bd}bit-R15", w, h, 18 - bd, 15, 27, "crop", shift=(-56, 56), pre_search=1))
+    for k, mc in enumerate(((1, 0), (0, 1), (1, 1))):                # slices: vertical motion planted in every block, towards and past the slice's rows
+        for j, (w, h) in enumerate(SIZES):
+            bd = (8, 10)[(k + j) % 2]
+            out.append(inter_case(f"slice{mc[0]}{mc[1]}-{w}x{h}-{bd}bit", w, h, bd, 8, 27, "warp8" if j == 1 else "warp16", seed=40 + 3 * k + j, noise=1 << (bd - 8),
+                                  rdo_zero=j & 1, mc=mc, centres=None if j else ((3, -5),), pre_search=1 if j == 2 else 0))
+    for k, (w, h) in enumerate(SIZES):                               # ties: lambda_sad_q4 = 0
+        bd = (8, 10)[k % 2]
+        out.append(inter_case(f"lam0-flat-{w}x{h}-{bd}bit", w, h, bd, 8, 27, "flat", lam=(0, 60)))
+        out.append(inter_case(f"lam0-warp16-{w}x{h}-{bd}bit", w, h, bd, 8, 27, "warp16", seed=70 + k, lam=(0, 60), rdo_zero=1))
+        out.append(inter_case(f"lam0-warp8-{w}x{h}-{18 - bd}bit", w, h, 18 - bd, 15, 32, "warp8", seed=80 + k, noise=1 << (10 - bd), lam=(0, 200 << (2 * (10 - bd))), rdo_zero=1))
+    out.append(inter_case("flat-64x64-8bit", 64, 64, 8, 8, 27, "flat"))
+    # B pictures
+    for k, (w, h) in enumerate(SIZES):
+        for j, bd in enumerate((8, 10)):
+            kind = ("b-mix", "b-same", "b-mix")[(k + j) % 3]
+            g = (16, 8, 32)[(k + j) % 3]
+            R, qp = (8, 15)[(k + j) % 2], SAO_QPS[(k + 2 * j) % 3]
+            out.append(inter_case(f"{kind}{g}-{w}x{h}-{bd}bit-R{R}-qp{qp}", w, h, bd, R, qp, f"{kind}{g}", seed=50 + 2 * k + j, noise=(k + j) % 3 << (bd - 8), rdo_zero=(k + j) & 1,
+                                  centres=None if k else ((2, -1), (-4, 2))))
+    out.append(inter_case("b-same16-64x64-8bit-lam0", 64, 64, 8, 8, 27, "b-same16", seed=61, lam=(0, 60)))
+    out.append(inter_case("b-mix16-136x72-8bit-lam0", 136, 72, 8, 8, 27, "b-mix16", seed=62, noise=1, lam=(0, 60), rdo_zero=1))
+    # low-contrast anchors + noise: the costs of a ring's candidates, of a node and its four children, of the three B keys lie a few units of SATD apart, so these are the
+    # cases in which HOW the SATD is rounded decides (per 8x8 tile, not once per CU: SATD_ROUNDING_CASES; seeds and noise chosen so that the model itself says so)
+    for kind, (w, h), bd, R, qp, noise, seed in (("soft-warp16", (136, 72), 8, 8, 32, 2, 203), ("soft-b-mix16", (136, 72), 8, 8, 32, 2, 201), ("soft-warp32", (64, 64), 8, 15, 22, 5, 200),
+                                                 ("soft-b-mix16", (64, 64), 10, 8, 32, 5, 204), ("soft-warp16", (72, 104), 8, 8, 32, 5, 202), ("soft-b-mix32", (72, 104), 8, 15, 22, 3, 201),
+                                                 ("soft-warp16", (136, 72), 10, 8, 32, 5, 200)):
+        out.append(inter_case(f"{kind}-{w}x{h}-{bd}bit-R{R}-qp{qp}-n{noise}", w, h, bd, R, qp, kind, seed=seed, noise=noise << (bd - 8), rdo_zero=seed & 1))
+    # rdo_cg > 0: the decisions do not depend on it
+    out.append(inter_case("rdocg-warp16-136x72-8bit", 136, 72, 8, 8, 32, "warp16", seed=90, noise=2, rdo_zero=1, rdo_cg=5))
+    out.append(inter_case("rdocg-b-mix16-72x104-10bit", 72, 104, 10, 8, 32, "b-mix16", seed=91, noise=4, rdo_zero=1, rdo_cg=5))
+    assert len({c.id for c in out}) == len(out)
+    return out
+
+
+INTER_CASES = _inter_cases()
+SATD_ROUNDING_CASES = [c for c in INTER_CASES if c.content.startswith("soft-")]
+
+
+def inter_diff(want, got, decisions_only=False):
+    """want: the model's Result; got: an O.Analysis of the oracle, the stepped kernel or the device.  '' when equal.  decisions_only: the tree, the vectors and the list flags"""
+    out = []
+    a, b = want.cu, got.cu
+    fields = ("log2_size", "mvx", "mvy", "intra_mode") if decisions_only else a.dtype.names
+    for f in fields:
+        if not np.array_equal(a[f], b[f]):
+            i = tuple(np.argwhere(a[f] != b[f])[0][:2])
+            out.append(f"cu.{f} at (row, column) {i}: model {a[i]} vs {b[i]}")
+    if decisions_only:
+        if not np.array_equal(a["flags"] & 0x61, b["flags"] & 0x61):
+            out.append("cu.flags (inter, list bits)")
+        return "; ".join(out)
+    for n, p, q in (("coef_y", want.coef[0], got.coef_y), ("coef_u", want.coef[1], got.coef_u), ("coef_v", want.coef[2], got.coef_v),
+                    ("rec.y", want.rec[0], got.rec.y), ("rec.u", want.rec[1], got.rec.u), ("rec.v", want.rec[2], got.rec.v)):
+        if not np.array_equal(p, q):
+            ys, xs = np.nonzero(np.asarray(p) != np.asarray(q))
+            out.append(f"{n}: {len(ys)} differ, first at x={xs[0]} y={ys[0]}: model {p[ys[0], xs[0]]} vs {q[ys[0], xs[0]]}")
+    if want.est != got.est:
+        out.append(f"estimate: model {want.est} vs {got.est}")
+    return "; ".join(out)
+
+
+def run_inter_case(api_or_oracle, c):
+    """the case through the oracle module or a StageApi, with the centres the case gives (None with the pre-search: the entry makes its own)"""
+    prm, cp = inter_case_params(c)
+    cur, refs, _ = inter_case_pictures(c)
+    cen = inter_case_centres(c, len(refs))
+    if api_or_oracle is O:
+        return O.analyze_inter(cur, refs[0], prm, cen[0], dump_me=True) if len(refs) == 1 else O.analyze_b(cur, refs[0], refs[1], prm, cen[0], cen[1], dump_me=True)
+    return api_or_oracle.inter(cur, refs[0], cp, cen[0]) if len(refs) == 1 else api_or_oracle.b(cur, refs[0], refs[1], cp, cen[0], cen[1])
+
+
+# hand-worked pictures of the inter audit (64x64, me_range 8, QP 27, no noise: every planted block is matched exactly); the device file runs them too
+PIN_MVS, PIN_B_MVS = ((13, -9), (0, 0), (14, -8), (0, 0), (-2, 6), (0, 0), (7, -3), (0, 0)), ((5, 2), (-3, 6))      # quarter, half in x, half in both, quarter
+PIN_SPLIT_MVS = ((4, 0), (0, 0), (-8, 4), (0, 0), (2, -4), (0, 0), (0, 6), (0, 0), (-5, -5), (0, 0), (7, 1), (0, 0), (-12, 9))    # block i of a P picture takes entry 2 i mod 13
+INTER_PINS = {c.id: c for c in (
+    inter_case("pin-flat", 64, 64, 8, 8, 27, "flat"),
+    inter_case("pin-planted", 64, 64, 8, 8, 27, "warp32", mvs=PIN_MVS),
+    inter_case("pin-split", 64, 64, 8, 8, 27, "warp16", mvs=PIN_SPLIT_MVS),
+    inter_case("pin-main10", 64, 64, 10, 8, 27, "warp32", mvs=PIN_MVS),
+    inter_case("pin-b-both", 64, 64, 8, 8, 27, "b-avg32", mvs=PIN_B_MVS),
+    inter_case("pin-b-list0", 64, 64, 8, 8, 27, "b-first32", mvs=PIN_B_MVS),
+    inter_case("pin-b-list1", 64, 64, 8, 8, 27, "b-second32", mvs=PIN_B_MVS))}
