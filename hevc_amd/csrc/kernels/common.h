@@ -162,7 +162,7 @@ DEV int node_of_tile(int level, int tx, int ty)
     return level == 1 ? 1 + q : 5 + q * 4 + (ty & 1) * 2 + (tx & 1);
 }
 
-// sum of absolute differences of 4 (8-bit) / 2 (16-bit) packed samples
+// sum of absolute differences of 4 packed 8-bit samples
 DEV uint32_t sad_packed_u8(uint32_t a, uint32_t b, uint32_t acc)
 {
 #if MIHEVC_GPU
@@ -172,33 +172,12 @@ DEV uint32_t sad_packed_u8(uint32_t a, uint32_t b, uint32_t acc)
     return acc;
 #endif
 }
-DEV uint32_t sad_packed_u16(uint32_t a, uint32_t b, uint32_t acc)
-{
-#if MIHEVC_GPU
-    return __builtin_amdgcn_sad_u16(a, b, acc);
-#else
-    for (int i = 0; i < 2; i++) acc += (uint32_t)iabs((int)((a >> (16 * i)) & 65535) - (int)((b >> (16 * i)) & 65535));
-    return acc;
-#endif
-}
 DEV uint32_t load_u32(const void *p)
 {
     uint32_t v;
     __builtin_memcpy(&v, p, 4);
     return v;
 }
-// SAD of one 8-sample row
-DEV uint32_t sad_row8(const uint8_t *a, const uint8_t *b, uint32_t acc)
-{
-    acc = sad_packed_u8(load_u32(a), load_u32(b), acc);
-    return sad_packed_u8(load_u32(a + 4), load_u32(b + 4), acc);
-}
-DEV uint32_t sad_row8(const uint16_t *a, const uint16_t *b, uint32_t acc)
-{
-    for (int i = 0; i < 8; i += 2) acc = sad_packed_u16(load_u32(a + i), load_u32(b + i), acc);
-    return acc;
-}
-
 // two 16-bit lanes per dword (VOP3P v_pk_add_u16 / v_pk_sub_i16 / v_pk_max_i16): the callers keep every value inside 16 bits
 DEV uint32_t pk_add16(uint32_t a, uint32_t b)
 {
@@ -320,38 +299,6 @@ DEV void copy_window(T *lds, int ls, const T *plane, int pstride, int ox, int oy
     }
 }
 
-// the workgroup's CTU source image (Y 32x32, then U, V 16x16; zero outside the picture) — dword loads for whole CTUs, all of a lane's
-// loads in flight together; sample-wise only for the partial CTUs at the right / bottom picture edge
-template <typename T>
-DEV void load_ctu_source(T *dst, const Plane<const T> (&src)[3], int x0, int y0, int w, int h, int tid)
-{
-    constexpr int per = 4 / (int)sizeof(T);
-    if (x0 + CTU <= w && y0 + CTU <= h) {
-        constexpr int ND = 1536 / per, IT = (ND + NT - 1) / NT;
-        uint32_t v[IT];
-#pragma unroll
-        for (int k = 0; k < IT; k++) {
-            const int d = tid + k * NT;
-            if (d < ND) {
-                const int i = d * per, pl = i < 1024 ? 0 : 1 + ((i - 1024) >> 8), kk = pl ? (i - 1024) & 255 : i, x = pl ? kk & 15 : kk & 31, y = pl ? kk >> 4 : kk >> 5;
-                v[k] = load_u32(src[pl].p + (size_t)((pl ? y0 >> 1 : y0) + y) * src[pl].stride + (pl ? x0 >> 1 : x0) + x);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < IT; k++) {
-            const int d = tid + k * NT;
-            if (d < ND) __builtin_memcpy(__builtin_assume_aligned(dst + d * per, 4), &v[k], 4);
-        }
-        return;
-    }
-    for (int i = tid; i < 1536; i += NT) {
-        int pl, x, y;
-        if (i < 1024) { pl = 0; x = i & 31; y = i >> 5; } else { int k = i - 1024; pl = 1 + (k >> 8); k &= 255; x = k & 15; y = k >> 4; }
-        const int gx = (pl ? x0 >> 1 : x0) + x, gy = (pl ? y0 >> 1 : y0) + y, pw = pl ? w >> 1 : w, ph = pl ? h >> 1 : h;
-        dst[i] = (gx < pw && gy < ph) ? src[pl].p[(size_t)gy * src[pl].stride + gx] : (T)0;
-    }
-}
-
 // a value that is the same in every lane, held in a scalar register: a 16-bit global load (no scalar form on gfx950) leaves it and everything
 // derived from it in VGPRs for the whole program otherwise
 DEV int wave_uniform(int v)
@@ -449,17 +396,20 @@ DEV uint32_t pack_lo16(int lo, int hi)
 #endif
 }
 
-// in-place 8x8 Hadamard SATD of a difference block held in registers: (sum |H d H| + 2) >> 2
-DEV int hadamard8_satd(int (&m)[8][8])
+// 8-point Hadamard butterflies in place
+DEV void butterfly8(int (&d)[8])
 {
 #pragma unroll
-    for (int y = 0; y < 8; y++) {
+    for (int st = 1; st < 8; st <<= 1)
 #pragma unroll
-        for (int st = 1; st < 8; st <<= 1)
+        for (int i = 0; i < 8; i++)
+            if (!(i & st)) { int p = d[i], q = d[i + st]; d[i] = p + q; d[i + st] = p - q; }
+}
+// in-place 8x8 Hadamard transform of a block held in registers: (sum |H d H| + 2) >> 2, with the DC term left out of the sum when AC
+template <bool AC> DEV int hadamard8_sum(int (&m)[8][8])
+{
 #pragma unroll
-            for (int i = 0; i < 8; i++)
-                if (!(i & st)) { int p = m[y][i], q = m[y][i + st]; m[y][i] = p + q; m[y][i + st] = p - q; }
-    }
+    for (int y = 0; y < 8; y++) butterfly8(m[y]);
     int s = 0;
 #pragma unroll
     for (int x = 0; x < 8; x++) {
@@ -469,35 +419,12 @@ DEV int hadamard8_satd(int (&m)[8][8])
             for (int i = 0; i < 8; i++)
                 if (!(i & st)) { int p = m[i][x], q = m[i + st][x]; m[i][x] = p + q; m[i + st][x] = p - q; }
 #pragma unroll
-        for (int i = 0; i < 8; i++) s += iabs(m[i][x]);
+        for (int i = 0; i < 8; i++) if (!AC || x || i) s += iabs(m[i][x]);
     }
     return (s + 2) >> 2;
 }
-
-// the same transform of a source tile with the DC term left out of the sum: its activity around its own mean
-DEV int hadamard8_ac(int (&m)[8][8])
-{
-#pragma unroll
-    for (int y = 0; y < 8; y++) {
-#pragma unroll
-        for (int st = 1; st < 8; st <<= 1)
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                if (!(i & st)) { int p = m[y][i], q = m[y][i + st]; m[y][i] = p + q; m[y][i + st] = p - q; }
-    }
-    int s = 0;
-#pragma unroll
-    for (int x = 0; x < 8; x++) {
-#pragma unroll
-        for (int st = 1; st < 8; st <<= 1)
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                if (!(i & st)) { int p = m[i][x], q = m[i + st][x]; m[i][x] = p + q; m[i + st][x] = p - q; }
-#pragma unroll
-        for (int i = 0; i < 8; i++) if (x || i) s += iabs(m[i][x]);
-    }
-    return (s + 2) >> 2;
-}
+DEV int hadamard8_satd(int (&m)[8][8]) { return hadamard8_sum<false>(m); }      // SATD of a difference block
+DEV int hadamard8_ac(int (&m)[8][8]) { return hadamard8_sum<true>(m); }         // a source tile's activity around its own mean
 
 // ------------------------------------------------------------------------------------------ executors
 #if MIHEVC_GPU

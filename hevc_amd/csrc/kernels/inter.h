@@ -678,24 +678,6 @@ DEV void luma_half_diff(const uint16_t *win, int i00, int ws, int fx, int fy, in
 #pragma unroll
         for (int i = 0; i < 4; i++) m[j][i] = (int)src[j * src_stride + i] - clip3(0, maxv, ((acc[j][i] >> 6) + off3) >> shift3);
 }
-// the half tile's share of the 8x8 Hadamard transform: all three vertical stages and the two horizontal stages inside its 4 columns;
-// the last horizontal stage pairs column c of the two halves (inter_ctu_program)
-DEV void hadamard_half(int (&m)[8][4])
-{
-#pragma unroll
-    for (int x = 0; x < 4; x++)
-#pragma unroll
-        for (int st = 1; st < 8; st <<= 1)
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                if (!(i & st)) { int p = m[i][x], q = m[i + st][x]; m[i][x] = p + q; m[i + st][x] = p - q; }
-#pragma unroll
-    for (int y = 0; y < 8; y++) {
-        const int p0 = m[y][0] + m[y][1], p1 = m[y][0] - m[y][1], p2 = m[y][2] + m[y][3], p3 = m[y][2] - m[y][3];
-        m[y][0] = p0 + p2; m[y][1] = p1 + p3; m[y][2] = p0 - p2; m[y][3] = p1 - p3;
-    }
-}
-
 // SATD of one 8x8 tile against the window at an INTEGER vector (both fractions zero: the prediction is the window itself)
 template <typename T> DEV int luma_tile_int(const T *win, int i00, int ws, const T *src, int src_stride)
 {
@@ -710,32 +692,48 @@ template <typename T> DEV int luma_tile_int(const T *win, int i00, int ws, const
     return hadamard8_satd(m);
 }
 
-template <typename T, class Ex, bool BI = false>
-DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win_v, const InterArgs<T> &a, int ctu, BiShared *bsh = nullptr)
+// the search centre's motion-compensation windows: picture position, in its plane, of the first sample of the luma and of the chroma windows
+struct WinOrigin { int yx, yy, cx, cy; };
+DEV WinOrigin win_origin(int x0, int y0, int sx, int sy, int R)
 {
-    const int R0 = a.prm.me_range, R = R0 + 3, bd = a.prm.bit_depth, lam = a.prm.lambda_sad_q4;
-    const int x0 = (ctu % a.ctus_w) * CTU, y0 = (ctu / a.ctus_w) * CTU;
-    const int mct = a.prm.mc_top, mcb = a.prm.mc_bottom;
-    const int sx = wave_uniform(a.centers ? a.centers[2 * ctu] : 0), sy0 = wave_uniform(a.centers ? a.centers[2 * ctu + 1] : 0);
-    const int sy = (mct || mcb) ? clamp_center_y(sy0, y0, R0, a.h, mct, mcb) : sy0;
-    const int wy = mc_win_y(R0), wys = mc_win_y_stride(R0), wc = mc_win_c(R0), wcs = mc_win_c_stride(R0);
-    const int oy_x = x0 + sx - R - 4, oy_y = y0 + sy - R - 4;                                  // luma window origin
-    const int oc_x = (x0 >> 1) + ((4 * sx - 4 * R - 3) >> 3) - 1, oc_y = (y0 >> 1) + ((4 * sy - 4 * R - 3) >> 3) - 1;
+    return WinOrigin{x0 + sx - R - 4, y0 + sy - R - 4, (x0 >> 1) + ((4 * sx - 4 * R - 3) >> 3) - 1, (y0 >> 1) + ((4 * sy - 4 * R - 3) >> 3) - 1};
+}
+// what every stage of the CTU program reads and none writes: workgroup-uniform values of the CTU (x0, y0: its luma origin; R: the windows' reach; sx, sy and o0: the
+// list-0 search centre and its windows' origin) and the windows in LDS.  Nothing that differs between lanes lives here, so nothing of it sits in a VGPR across a barrier.
+template <typename T> struct InterCtx {
+    int ctu, x0, y0, R, bd, lam, mct, mcb, sx, sy, wys, wcs;
+    T *win_y, *win_u, *win_v;
+    WinOrigin o0;
+};
+// the three windows of one reference picture (list 0 or list 1) around origin o
+template <typename T> DEV void load_windows(const InterCtx<T> &ctx, const InterArgs<T> &a, const Plane<const T> (&ref)[3], const WinOrigin &o, int tid)
+{
+    const int wy = mc_win_y(a.prm.me_range), wc = mc_win_c(a.prm.me_range);
+    copy_window<T>(ctx.win_y, ctx.wys, ref[0].p, ref[0].stride, o.yx, o.yy, wy, wy, -PAD_Y, a.w + PAD_Y - 1, -PAD_Y, a.h + PAD_Y - 1, tid);
+    copy_window<T>(ctx.win_u, ctx.wcs, ref[1].p, ref[1].stride, o.cx, o.cy, wc, wc, -PAD_C, (a.w >> 1) + PAD_C - 1, -PAD_C, (a.h >> 1) + PAD_C - 1, tid);
+    copy_window<T>(ctx.win_v, ctx.wcs, ref[2].p, ref[2].stride, o.cx, o.cy, wc, wc, -PAD_C, (a.w >> 1) + PAD_C - 1, -PAD_C, (a.h >> 1) + PAD_C - 1, tid);
+}
+// lambda x the bits of vector (mx, my), quarter samples, against the search centre (csx, csy), whole samples
+DEV int mv_cost(int lam, int mx, int my, int csx, int csy) { return lam * (mvd_bits(mx - 4 * csx) + mvd_bits(my - 4 * csy)); }
 
+// transform tables, source image, list-0 windows and integer vectors
+template <typename T, class Ex> DEV void inter_load(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
     ex.phase([&](int tid) {
         residual_init_lane(s.rs, tid);          // (transform tables and flags: nothing else in this phase touches them; a phase of their own was one more barrier)
-        load_ctu_source<T>(s.src, a.src, x0, y0, a.w, a.h, tid);
-        copy_window<T>(win_y, wys, a.ref[0].p, a.ref[0].stride, oy_x, oy_y, wy, wy, -PAD_Y, a.w + PAD_Y - 1, -PAD_Y, a.h + PAD_Y - 1, tid);
-        copy_window<T>(win_u, wcs, a.ref[1].p, a.ref[1].stride, oc_x, oc_y, wc, wc, -PAD_C, (a.w >> 1) + PAD_C - 1, -PAD_C, (a.h >> 1) + PAD_C - 1, tid);
-        copy_window<T>(win_v, wcs, a.ref[2].p, a.ref[2].stride, oc_x, oc_y, wc, wc, -PAD_C, (a.w >> 1) + PAD_C - 1, -PAD_C, (a.h >> 1) + PAD_C - 1, tid);
+        load_ctu_source<T>(s.src, a.src, ctx.x0, ctx.y0, a.w, a.h, tid);
+        load_windows(ctx, a, a.ref, ctx.o0, tid);
         if (tid < 21) {
-            const int32_t *m = a.me + ((size_t)ctu * 21 + tid) * 3;
+            const int32_t *m = a.me + ((size_t)ctx.ctu * 21 + tid) * 3;
             s.mvx[tid] = m[0]; s.mvy[tid] = m[1]; s.valid[tid] = m[2] >= 0; s.cost[tid] = 0; s.nsum[tid] = 0;
         }
     });
-    // SATD of every node at its INTEGER vector: the quadtree is decided on these (+ lambda * mvd bits), the fractional search then
-    // runs for the chosen CUs only — 16 tiles x 8 ring positions = 128 lanes = two full waves per round, instead of one
-    // pass per tree level (the search was 43 % of this kernel: profiles/r01)
+}
+// SATD of every node at its INTEGER vector: the quadtree is decided on these (+ lambda * mvd bits), the fractional search then
+// runs for the chosen CUs only — 16 tiles x 8 ring positions = 128 lanes = two full waves per round, instead of one
+// pass per tree level (the search was 43 % of this kernel: profiles/r01)
+template <typename T, class Ex> DEV void inter_tree(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
     ex.phase([&](int tid) {
         for (int u = tid; u < 3 * 16; u += NT) {
             int level = u >> 4, t = u & 15;
@@ -749,8 +747,8 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
             }
             s.alias[level][t] = (uint8_t)al;
             if (al != level) continue;
-            int px = x0 + txp * 8 + (s.mvx[node] >> 2) - oy_x, py = y0 + typ * 8 + (s.mvy[node] >> 2) - oy_y;
-            s.satd[level][0][t] = luma_tile_int<T>(win_y, py * wys + px, wys, s.src + typ * 8 * 32 + txp * 8, 32);
+            int px = ctx.x0 + txp * 8 + (s.mvx[node] >> 2) - ctx.o0.yx, py = ctx.y0 + typ * 8 + (s.mvy[node] >> 2) - ctx.o0.yy;
+            s.satd[level][0][t] = luma_tile_int<T>(ctx.win_y, py * ctx.wys + px, ctx.wys, s.src + ctu_index(0, txp * 8, typ * 8), 32);
         }
     });
     // every (level, tile) lane adds its tile's SATD (its own or the finer level's it aliases) to the node's sum
@@ -766,22 +764,22 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
     ex.wave_step([&](int tid) {
         if (tid >= 21) return;
         s.chosen[tid] = 0;
-        s.cost[tid] = s.valid[tid] ? (s.nsum[tid] << 4) + (unsigned)(lam * (mvd_bits(s.mvx[tid] - 4 * sx) + mvd_bits(s.mvy[tid] - 4 * sy))) : 0;
+        s.cost[tid] = s.valid[tid] ? (s.nsum[tid] << 4) + (unsigned)mv_cost(ctx.lam, s.mvx[tid], s.mvy[tid], ctx.sx, ctx.sy) : 0;
         if (tid == 0) { s.est = 0; s.ip_cost = 0; s.ip_act = 0; s.ip_tiles = 0; s.ip_sse = 0; }
     });
     ex.wave_step([&](int tid) {
         if (tid >= 4) return;
         const int q = tid;
-        unsigned js = (unsigned)(lam * 2);
-        for (int t = 0; t < 4; t++) if (s.valid[5 + 4 * q + t]) js += s.cost[5 + 4 * q + t] + (unsigned)(lam * 4);
-        const unsigned jw = s.cost[1 + q] + (unsigned)(lam * 4);
+        unsigned js = (unsigned)(ctx.lam * 2);
+        for (int t = 0; t < 4; t++) if (s.valid[5 + 4 * q + t]) js += s.cost[5 + 4 * q + t] + (unsigned)(ctx.lam * 4);
+        const unsigned jw = s.cost[1 + q] + (unsigned)(ctx.lam * 4);
         s.use16[q] = s.valid[1 + q] && jw <= js;
         s.j16[q] = s.use16[q] ? jw : js;
     });
     ex.wave_step([&](int tid) {
         if (tid != 0) return;
-        const unsigned js32 = (unsigned)(lam * 2) + s.j16[0] + s.j16[1] + s.j16[2] + s.j16[3];
-        s.use32 = s.valid[0] && s.cost[0] + (unsigned)(lam * 4) <= js32;
+        const unsigned js32 = (unsigned)(ctx.lam * 2) + s.j16[0] + s.j16[1] + s.j16[2] + s.j16[3];
+        s.use32 = s.valid[0] && s.cost[0] + (unsigned)(ctx.lam * 4) <= js32;
     });
     ex.phase([&](int tid) {
         if (tid >= 16) return;
@@ -792,9 +790,11 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
         s.rs.tu_log2[t] = inside ? (uint8_t)(node == 0 ? 5 : node < 5 ? 4 : 3) : 0;
         s.rs.tu_intra[t] = 0;
     });
-    // fractional refinement of the chosen CUs: half-pel ring, then quarter-pel ring (the centre's cost is known).  csx / csy: the search centre the
-    // vectors are priced against, wox / woy: origin of the luma window in LDS (a B picture refines list 1 with the same code after list 0)
-    auto refine = [&](const int csx, const int csy, const int wox, const int woy) {
+}
+// fractional refinement of the chosen CUs: half-pel ring, then quarter-pel ring (the centre's cost is known).  csx / csy: the search centre the
+// vectors are priced against, o: origin of the windows in LDS (a B picture refines list 1 with the same code after list 0)
+template <typename T, class Ex> DEV void inter_refine(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx, const int csx, const int csy, const WinOrigin &o)
+{
     for (int round = 0; round < 2; round++) {
         const int step = round == 0 ? 2 : 1;
         // 16 tiles x 8 ring positions x 2 column halves = the whole workgroup.  Wave-local steps: both lanes of a pair sit in one wave.  A lane keeps the
@@ -806,9 +806,9 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
             if (!s.rs.tu_log2[t]) return kept;
             const int txp = t & 3, typ = t >> 2, node = s.tile_node[t];
             const int mx = s.mvx[node] + kOff[k][0] * step, my = s.mvy[node] + kOff[k][1] * step;
-            const int px = x0 + txp * 8 + 4 * half + (mx >> 2) - wox, py = y0 + typ * 8 + (my >> 2) - woy;
+            const int px = ctx.x0 + txp * 8 + 4 * half + (mx >> 2) - o.yx, py = ctx.y0 + typ * 8 + (my >> 2) - o.yy;
             int m[8][4];
-            luma_half_diff((const T *)win_y, py * wys + px, wys, mx & 3, my & 3, bd, (const T *)(s.src + typ * 8 * 32 + txp * 8 + 4 * half), 32, m);
+            luma_half_diff((const T *)ctx.win_y, py * ctx.wys + px, ctx.wys, mx & 3, my & 3, ctx.bd, (const T *)(s.src + typ * 8 * 32 + txp * 8 + 4 * half), 32, m);
             {
                 // Differences are 9 bits at 8 bit, 11 at 10 bit; the five butterfly stages computed here grow them by 5: 255 x 32 and 1023 x 32 = 32736 both fit 16 bits, two values
                 // a dword (v_pk_add / sub_i16).  Rows 2r and
@@ -890,12 +890,12 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
             const unsigned satd = s.fsum[k - 1][node];
             s.fsum[k - 1][node] = 0;                                      // ready for the next round
             const int mx = s.mvx[node] + kOff[k][0] * step, my = s.mvy[node] + kOff[k][1] * step;
-            if (mct || mcb) {                    // a slice: candidates whose filter taps would reach across its edge are out
+            if (ctx.mct || ctx.mcb) {                    // a slice: candidates whose filter taps would reach across its edge are out
                 int nx, ny, nl;
                 node_geom(node, nx, ny, nl);
-                if (!mv_rows_ok(y0 + ny, 1 << nl, my, a.h, mct, mcb)) return;
+                if (!mv_rows_ok(ctx.y0 + ny, 1 << nl, my, a.h, ctx.mct, ctx.mcb)) return;
             }
-            const unsigned c = (satd << 4) + (unsigned)(lam * (mvd_bits(mx - 4 * csx) + mvd_bits(my - 4 * csy)));
+            const unsigned c = (satd << 4) + (unsigned)mv_cost(ctx.lam, mx, my, csx, csy);
             ex.atomic_min(&s.rbest[node], ((unsigned long long)c << 4) | (unsigned)k);
         });
         ex.phase([&](int tid) {
@@ -906,131 +906,131 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
             s.cost[tid] = (unsigned)(best >> 4);
         });
     }
-    };
-    refine(sx, sy, oy_x, oy_y);
-    // Motion compensation by the vector of each tile's CU.  Luma: lane tid has row (tid >> 1) & 7, columns 4 (tid & 1) .. + 3 of tile tid >> 4, four samples at
-    // lane_at(tid) in the CTU image; luma14 gives their 14-bit predictions from the luma window whose origin is (wox, woy).  Chroma: sample i (0 .. 511: Cb, then
-    // Cr) lies in tile chroma_tile(i); chroma14 gives its 14-bit prediction from the chroma windows whose origin is (cox, coy).
-    auto lane_at = [](int tid) { return ((tid >> 6) * 8 + ((tid >> 1) & 7)) * 32 + ((tid >> 4) & 3) * 8 + (tid & 1) * 4; };
-    auto luma14 = [&](int tid, int wox, int woy, int (&v)[4]) {
-        const int t = tid >> 4, node = s.tile_node[t], mx = s.mvx[node], my = s.mvy[node];
-        const int px = x0 + (t & 3) * 8 + (tid & 1) * 4 + (mx >> 2) - wox, py = y0 + (t >> 2) * 8 + ((tid >> 1) & 7) + (my >> 2) - woy;
-        luma_quad14<T>(win_y, py * wys + px, wys, mx & 3, my & 3, bd, v);
-    };
-    auto chroma_tile = [](int i) { return ((i >> 6) & 3) * 4 + ((i >> 2) & 3); };
-    auto chroma14 = [&](int i, int cox, int coy) {
-        const int x = i & 15, y = (i >> 4) & 15, node = s.tile_node[chroma_tile(i)], mx = s.mvx[node], my = s.mvy[node];
-        const int px = (x0 >> 1) + x + (mx >> 3) - cox, py = (y0 >> 1) + y + (my >> 3) - coy;
-        return chroma_sample14<T>((i >> 8 ? win_v : win_u) + py * wcs + px, wcs, mx & 7, my & 7, bd);
-    };
-    if constexpr (BI) {
-        // ---- B picture (oracle: orc_analyze_b_frame).  The tree and the list-0 vectors stand; every CU of the tree now refines its list-1 vector
-        // (from its own node's integer search against the anchor AFTER this picture), tries the bi-prediction of the two refined vectors and takes the
-        // cheapest of SATD << 4 + lambda * (mvd bits + inter_pred_idc bins): list 0 (2), list 1 (2), both (1); ties in that order.
-        BiShared &b = *bsh;
-        const int sx1 = a.centers1 ? a.centers1[2 * ctu] : 0, sy1 = a.centers1 ? a.centers1[2 * ctu + 1] : 0;
-        const int o1_x = x0 + sx1 - R - 4, o1_y = y0 + sy1 - R - 4;
-        const int oc1_x = (x0 >> 1) + ((4 * sx1 - 4 * R - 3) >> 3) - 1, oc1_y = (y0 >> 1) + ((4 * sy1 - 4 * R - 3) >> 3) - 1;
-        // the 14-bit list-0 prediction of every tile while the list-0 windows are still in LDS (rs.res cannot hold it: it shares its LDS with the
-        // fractional search's scratch area)
-        ex.phase([&](int tid) {
-            if (tid < 21) { b.mx0[tid] = s.mvx[tid]; b.my0[tid] = s.mvy[tid]; b.c0[tid] = s.cost[tid]; b.cb[tid] = 0; }
-            if (s.rs.tu_log2[tid >> 4]) {
-                int v[4];
-                luma14(tid, oy_x, oy_y, v);
-#pragma unroll
-                for (int i = 0; i < 4; i++) b.p0[lane_at(tid) + i] = (int16_t)v[i];
-            }
-            for (int i = tid; i < 512; i += NT)
-                if (s.rs.tu_log2[chroma_tile(i)]) b.p0[1024 + i] = (int16_t)chroma14(i, oc_x, oc_y);
-        });
-        // list-1 windows and integer vectors
-        ex.phase([&](int tid) {
-            copy_window<T>(win_y, wys, a.ref1[0].p, a.ref1[0].stride, o1_x, o1_y, wy, wy, -PAD_Y, a.w + PAD_Y - 1, -PAD_Y, a.h + PAD_Y - 1, tid);
-            copy_window<T>(win_u, wcs, a.ref1[1].p, a.ref1[1].stride, oc1_x, oc1_y, wc, wc, -PAD_C, (a.w >> 1) + PAD_C - 1, -PAD_C, (a.h >> 1) + PAD_C - 1, tid);
-            copy_window<T>(win_v, wcs, a.ref1[2].p, a.ref1[2].stride, oc1_x, oc1_y, wc, wc, -PAD_C, (a.w >> 1) + PAD_C - 1, -PAD_C, (a.h >> 1) + PAD_C - 1, tid);
-            if (tid < 21) {
-                const int32_t *m = a.me1 + ((size_t)ctu * 21 + tid) * 3;
-                s.mvx[tid] = m[0]; s.mvy[tid] = m[1]; s.nsum[tid] = 0;
-            }
-        });
-        ex.phase([&](int tid) {          // SATD of the tree's CUs at their list-1 integer vectors
-            if (tid >= 16 || !s.rs.tu_log2[tid]) return;
-            const int t = tid, txp = t & 3, typ = t >> 2, node = s.tile_node[t];
-            const int px = x0 + txp * 8 + (s.mvx[node] >> 2) - o1_x, py = y0 + typ * 8 + (s.mvy[node] >> 2) - o1_y;
-            ex.atomic_add(&s.nsum[node], (unsigned)luma_tile_int<T>(win_y, py * wys + px, wys, s.src + typ * 8 * 32 + txp * 8, 32));
-        });
-        ex.phase([&](int tid) {
-            if (tid < 21 && s.valid[tid] && s.chosen[tid])
-                s.cost[tid] = (s.nsum[tid] << 4) + (unsigned)(lam * (mvd_bits(s.mvx[tid] - 4 * sx1) + mvd_bits(s.mvy[tid] - 4 * sy1)));
-        });
-        refine(sx1, sy1, o1_x, o1_y);
-        // bi-prediction of the two refined vectors: difference to the source per sample, then one lane per tile takes the 8x8 Hadamard sum
-        ex.phase([&](int tid) {
-            if (!s.rs.tu_log2[tid >> 4]) return;
+}
+// Motion compensation by the vector of each tile's CU.  Luma: lane tid has row (tid >> 1) & 7, columns 4 (tid & 1) .. + 3 of tile tid >> 4, four samples at
+// mc_lane_at(tid) in the CTU image; mc_luma14 gives their 14-bit predictions from the luma window whose origin is o.  Chroma: sample i (0 .. 511: Cb, then
+// Cr) lies in tile mc_chroma_tile(i); mc_chroma14 gives its 14-bit prediction from the chroma windows whose origin is o.
+DEV int mc_lane_at(int tid) { return ctu_index(0, ((tid >> 4) & 3) * 8 + (tid & 1) * 4, (tid >> 6) * 8 + ((tid >> 1) & 7)); }
+DEV int mc_chroma_tile(int i) { return ((i >> 6) & 3) * 4 + ((i >> 2) & 3); }
+template <typename T> DEV void mc_luma14(const InterShared<T> &s, const InterCtx<T> &ctx, int tid, const WinOrigin &o, int (&v)[4])
+{
+    const int t = tid >> 4, node = s.tile_node[t], mx = s.mvx[node], my = s.mvy[node];
+    const int px = ctx.x0 + (t & 3) * 8 + (tid & 1) * 4 + (mx >> 2) - o.yx, py = ctx.y0 + (t >> 2) * 8 + ((tid >> 1) & 7) + (my >> 2) - o.yy;
+    luma_quad14<T>(ctx.win_y, py * ctx.wys + px, ctx.wys, mx & 3, my & 3, ctx.bd, v);
+}
+template <typename T> DEV int mc_chroma14(const InterShared<T> &s, const InterCtx<T> &ctx, int i, const WinOrigin &o)
+{
+    const int x = i & 15, y = (i >> 4) & 15, node = s.tile_node[mc_chroma_tile(i)], mx = s.mvx[node], my = s.mvy[node];
+    const int px = (ctx.x0 >> 1) + x + (mx >> 3) - o.cx, py = (ctx.y0 >> 1) + y + (my >> 3) - o.cy;
+    return chroma_sample14<T>((i >> 8 ? ctx.win_v : ctx.win_u) + py * ctx.wcs + px, ctx.wcs, mx & 7, my & 7, ctx.bd);
+}
+// ---- B picture (oracle: orc_analyze_b_frame).  The tree and the list-0 vectors stand; every CU of the tree now refines its list-1 vector
+// (from its own node's integer search against the anchor AFTER this picture), tries the bi-prediction of the two refined vectors and takes the
+// cheapest of SATD << 4 + lambda * (mvd bits + inter_pred_idc bins): list 0 (2), list 1 (2), both (1); ties in that order.
+template <typename T, class Ex> DEV void inter_b_block(Ex &ex, InterShared<T> &s, BiShared &b, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
+    const int sx1 = a.centers1 ? a.centers1[2 * ctx.ctu] : 0, sy1 = a.centers1 ? a.centers1[2 * ctx.ctu + 1] : 0;
+    const WinOrigin o1 = win_origin(ctx.x0, ctx.y0, sx1, sy1, ctx.R);
+    // the 14-bit list-0 prediction of every tile while the list-0 windows are still in LDS (rs.res cannot hold it: it shares its LDS with the
+    // fractional search's scratch area)
+    ex.phase([&](int tid) {
+        if (tid < 21) { b.mx0[tid] = s.mvx[tid]; b.my0[tid] = s.mvy[tid]; b.c0[tid] = s.cost[tid]; b.cb[tid] = 0; }
+        if (s.rs.tu_log2[tid >> 4]) {
             int v[4];
-            luma14(tid, o1_x, o1_y, v);
+            mc_luma14(s, ctx, tid, ctx.o0, v);
 #pragma unroll
-            for (int i = 0; i < 4; i++) {      // (lane tid's four samples of its tile's 8x8 difference block are elements 4 tid .. 4 tid + 3 of the 16 blocks)
-                const int at = lane_at(tid) + i;
-                s.rs.scratch[4 * tid + i] = (uint32_t)((int)s.src[at] - weighted_bi((int)b.p0[at], v[i], bd));
-            }
-        });
-        ex.phase([&](int tid) {
-            if (tid >= 16 || !s.rs.tu_log2[tid]) return;
-            int m[8][8];
+            for (int i = 0; i < 4; i++) b.p0[mc_lane_at(tid) + i] = (int16_t)v[i];
+        }
+        for (int i = tid; i < 512; i += NT)
+            if (s.rs.tu_log2[mc_chroma_tile(i)]) b.p0[CTU_LUMA + i] = (int16_t)mc_chroma14(s, ctx, i, ctx.o0);
+    });
+    // list-1 windows and integer vectors
+    ex.phase([&](int tid) {
+        load_windows(ctx, a, a.ref1, o1, tid);
+        if (tid < 21) {
+            const int32_t *m = a.me1 + ((size_t)ctx.ctu * 21 + tid) * 3;
+            s.mvx[tid] = m[0]; s.mvy[tid] = m[1]; s.nsum[tid] = 0;
+        }
+    });
+    ex.phase([&](int tid) {          // SATD of the tree's CUs at their list-1 integer vectors
+        if (tid >= 16 || !s.rs.tu_log2[tid]) return;
+        const int t = tid, txp = t & 3, typ = t >> 2, node = s.tile_node[t];
+        const int px = ctx.x0 + txp * 8 + (s.mvx[node] >> 2) - o1.yx, py = ctx.y0 + typ * 8 + (s.mvy[node] >> 2) - o1.yy;
+        ex.atomic_add(&s.nsum[node], (unsigned)luma_tile_int<T>(ctx.win_y, py * ctx.wys + px, ctx.wys, s.src + ctu_index(0, txp * 8, typ * 8), 32));
+    });
+    ex.phase([&](int tid) {
+        if (tid < 21 && s.valid[tid] && s.chosen[tid])
+            s.cost[tid] = (s.nsum[tid] << 4) + (unsigned)mv_cost(ctx.lam, s.mvx[tid], s.mvy[tid], sx1, sy1);
+    });
+    inter_refine(ex, s, a, ctx, sx1, sy1, o1);
+    // bi-prediction of the two refined vectors: difference to the source per sample, then one lane per tile takes the 8x8 Hadamard sum
+    ex.phase([&](int tid) {
+        if (!s.rs.tu_log2[tid >> 4]) return;
+        int v[4];
+        mc_luma14(s, ctx, tid, o1, v);
 #pragma unroll
-            for (int j = 0; j < 8; j++)
+        for (int i = 0; i < 4; i++) {      // (lane tid's four samples of its tile's 8x8 difference block are elements 4 tid .. 4 tid + 3 of the 16 blocks)
+            const int at = mc_lane_at(tid) + i;
+            s.rs.scratch[4 * tid + i] = (uint32_t)((int)s.src[at] - weighted_bi((int)b.p0[at], v[i], ctx.bd));
+        }
+    });
+    ex.phase([&](int tid) {
+        if (tid >= 16 || !s.rs.tu_log2[tid]) return;
+        int m[8][8];
 #pragma unroll
-                for (int i = 0; i < 8; i++) m[j][i] = (int)s.rs.scratch[tid * 64 + j * 8 + i];
-            ex.atomic_add(&b.cb[s.tile_node[tid]], (unsigned)hadamard8_satd(m));
-        });
-        ex.phase([&](int tid) {
-            if (tid >= 21 || !s.valid[tid] || !s.chosen[tid]) return;
-            const unsigned bits0 = (unsigned)(mvd_bits(b.mx0[tid] - 4 * sx) + mvd_bits(b.my0[tid] - 4 * sy)), bits1 = (unsigned)(mvd_bits(s.mvx[tid] - 4 * sx1) + mvd_bits(s.mvy[tid] - 4 * sy1));
-            const unsigned cbi = (b.cb[tid] << 4) + (unsigned)lam * (bits0 + bits1);
-            const unsigned long long k0 = (((unsigned long long)b.c0[tid] + (unsigned long long)(lam * 2)) << 2) | 0, k1 = (((unsigned long long)s.cost[tid] + (unsigned long long)(lam * 2)) << 2) | 1,
-                                     k2 = (((unsigned long long)cbi + (unsigned long long)lam) << 2) | 2;
-            const unsigned long long kb = k0 <= k1 ? (k0 <= k2 ? k0 : k2) : (k1 <= k2 ? k1 : k2);
-            b.mode[tid] = (uint8_t)(kb & 3);
-        });
-        // final prediction of every CU by its mode: list 0 from the 14-bit samples kept in BiShared::p0, list 1 from the windows, or their average
-        ex.phase([&](int tid) {
-            if (tid < 16) {
-                const int node = s.tile_node[tid], mode = b.mode[node];
-                b.tile_mode[tid] = (uint8_t)mode;
-                s.tile_mvx[tid] = mode != 1 ? b.mx0[node] : 0; s.tile_mvy[tid] = mode != 1 ? b.my0[node] : 0;
-                b.tile_mv1x[tid] = mode != 0 ? s.mvx[node] : 0; b.tile_mv1y[tid] = mode != 0 ? s.mvy[node] : 0;
-            }
-            if (s.rs.tu_log2[tid >> 4]) {
-                const int mode = b.mode[s.tile_node[tid >> 4]];
-                int v[4] = {0, 0, 0, 0};
-                if (mode != 0) luma14(tid, o1_x, o1_y, v);
+        for (int j = 0; j < 8; j++)
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int at = lane_at(tid) + i, p0 = (int)b.p0[at];
-                    s.pred[at] = (T)(mode == 0 ? weighted_uni(p0, bd) : mode == 1 ? weighted_uni(v[i], bd) : weighted_bi(p0, v[i], bd));
-                }
+            for (int i = 0; i < 8; i++) m[j][i] = (int)s.rs.scratch[tid * 64 + j * 8 + i];
+        ex.atomic_add(&b.cb[s.tile_node[tid]], (unsigned)hadamard8_satd(m));
+    });
+    ex.phase([&](int tid) {
+        if (tid >= 21 || !s.valid[tid] || !s.chosen[tid]) return;
+        const unsigned cbi = (b.cb[tid] << 4) + (unsigned)mv_cost(ctx.lam, b.mx0[tid], b.my0[tid], ctx.sx, ctx.sy) + (unsigned)mv_cost(ctx.lam, s.mvx[tid], s.mvy[tid], sx1, sy1);
+        const unsigned long long k0 = (((unsigned long long)b.c0[tid] + (unsigned long long)(ctx.lam * 2)) << 2) | 0, k1 = (((unsigned long long)s.cost[tid] + (unsigned long long)(ctx.lam * 2)) << 2) | 1,
+                                 k2 = (((unsigned long long)cbi + (unsigned long long)ctx.lam) << 2) | 2;
+        const unsigned long long kb = k0 <= k1 ? (k0 <= k2 ? k0 : k2) : (k1 <= k2 ? k1 : k2);
+        b.mode[tid] = (uint8_t)(kb & 3);
+    });
+    // final prediction of every CU by its mode: list 0 from the 14-bit samples kept in BiShared::p0, list 1 from the windows, or their average
+    ex.phase([&](int tid) {
+        if (tid < 16) {
+            const int node = s.tile_node[tid], mode = b.mode[node];
+            b.tile_mode[tid] = (uint8_t)mode;
+            s.tile_mvx[tid] = mode != 1 ? b.mx0[node] : 0; s.tile_mvy[tid] = mode != 1 ? b.my0[node] : 0;
+            b.tile_mv1x[tid] = mode != 0 ? s.mvx[node] : 0; b.tile_mv1y[tid] = mode != 0 ? s.mvy[node] : 0;
+        }
+        if (s.rs.tu_log2[tid >> 4]) {
+            const int mode = b.mode[s.tile_node[tid >> 4]];
+            int v[4] = {0, 0, 0, 0};
+            if (mode != 0) mc_luma14(s, ctx, tid, o1, v);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int at = mc_lane_at(tid) + i, p0 = (int)b.p0[at];
+                s.pred[at] = (T)(mode == 0 ? weighted_uni(p0, ctx.bd) : mode == 1 ? weighted_uni(v[i], ctx.bd) : weighted_bi(p0, v[i], ctx.bd));
             }
-            for (int i = tid; i < 512; i += NT) {
-                if (!s.rs.tu_log2[chroma_tile(i)]) continue;
-                const int mode = b.mode[s.tile_node[chroma_tile(i)]], p0 = (int)b.p0[1024 + i], p1 = mode != 0 ? chroma14(i, oc1_x, oc1_y) : 0;
-                s.pred[1024 + i] = (T)(mode == 0 ? weighted_uni(p0, bd) : mode == 1 ? weighted_uni(p1, bd) : weighted_bi(p0, p1, bd));
-            }
-        });
-    }
+        }
+        for (int i = tid; i < 512; i += NT) {
+            if (!s.rs.tu_log2[mc_chroma_tile(i)]) continue;
+            const int mode = b.mode[s.tile_node[mc_chroma_tile(i)]], p0 = (int)b.p0[CTU_LUMA + i], p1 = mode != 0 ? mc_chroma14(s, ctx, i, o1) : 0;
+            s.pred[CTU_LUMA + i] = (T)(mode == 0 ? weighted_uni(p0, ctx.bd) : mode == 1 ? weighted_uni(p1, ctx.bd) : weighted_bi(p0, p1, ctx.bd));
+        }
+    });
+}
+// P pictures: the hand-over to the intra second pass, then motion compensation of the chosen CUs
+template <typename T, class Ex> DEV void inter_predict_uni(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
     // (the tiles' vectors for the CU records are written by the motion compensation phase below: a phase of its own for 16 lanes was one more barrier for every CTU)
-    if (!BI && a.ip)
+    if (a.ip)
     ex.phase([&](int tid) {
         if (tid >= 64 && tid < 85 && s.valid[tid - 64] && s.chosen[tid - 64]) ex.atomic_add(&s.ip_cost, s.cost[tid - 64]);
         if (tid >= 128 && tid < 144 && s.rs.tu_log2[tid - 128]) ex.atomic_add(&s.ip_tiles, 1u);
     });
     // intra second-pass candidate (oracle: orc_analyze_inter_frame): the inter cost is above 4 per sample AND above the source's
     // own AC activity (8x8 Hadamard without the DC term).  The activity is only computed when the first test passes.
-    if (!BI && a.ip && s.ip_cost >= ((4u * 64u * s.ip_tiles) << 4)) {
+    if (a.ip && s.ip_cost >= ((4u * 64u * s.ip_tiles) << 4)) {
         ex.phase([&](int tid) {
             if (tid >= 16 || !s.rs.tu_log2[tid]) return;
-            const T *sp = s.src + (tid >> 2) * 8 * 32 + (tid & 3) * 8;
+            const T *sp = s.src + ctu_index(0, (tid & 3) * 8, (tid >> 2) * 8);
             int m[8][8];
 #pragma unroll
             for (int j = 0; j < 8; j++)
@@ -1040,75 +1040,81 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
         });
     }
     // motion compensation of the chosen CUs: every lane predicts 4 luma samples and 2 chroma samples
-    if constexpr (!BI)
     ex.phase([&](int tid) {
         if (tid < 16) { s.tile_mvx[tid] = s.mvx[s.tile_node[tid]]; s.tile_mvy[tid] = s.mvy[s.tile_node[tid]]; }      // read by the output phase, behind barriers
         if (s.rs.tu_log2[tid >> 4]) {
             int v[4];
-            luma14(tid, oy_x, oy_y, v);
+            mc_luma14(s, ctx, tid, ctx.o0, v);
 #pragma unroll
-            for (int i = 0; i < 4; i++) s.pred[lane_at(tid) + i] = (T)weighted_uni(v[i], bd);
+            for (int i = 0; i < 4; i++) s.pred[mc_lane_at(tid) + i] = (T)weighted_uni(v[i], ctx.bd);
         }
         for (int i = tid; i < 512; i += NT)
-            if (s.rs.tu_log2[chroma_tile(i)]) s.pred[1024 + i] = (T)weighted_uni(chroma14(i, oc_x, oc_y), bd);
+            if (s.rs.tu_log2[mc_chroma_tile(i)]) s.pred[CTU_LUMA + i] = (T)weighted_uni(mc_chroma14(s, ctx, i, ctx.o0), ctx.bd);
     });
+}
+// the residual of the whole CTU and its TU descriptors, then K3
+template <typename T, class Ex> DEV void inter_residual(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
     ex.phase([&](int tid) {
-        for (int i = tid; i < 1536; i += NT) {
+        for (int i = tid; i < CTU_SAMPLES; i += NT) {
             s.rs.res[i] = (int16_t)((int)s.src[i] - (int)s.pred[i]);
             s.rs.desc[i] = pack_loc(locate(s.rs, i));
         }
         if (tid < 48) { s.tu_dc[tid >> 4][tid & 15] = 0; s.tu_dz[tid >> 4][tid & 15] = 0; s.tu_bits[tid >> 4][tid & 15] = 0; }
         if (tid < 3) s.tu_zero[tid] = 0;
     });
-    residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, whole_ctu(), a.prm.rdo_cg > 0 ? (int)(((long long)a.prm.lambda_q4 * a.prm.rdo_cg) >> 1) : 0, a.prm.sign_hide);
-    // RD zero-out (oracle: code_tu_inter): a TU keeps its levels only if SSE_zero << 4 > (SSE_coded << 4) + (lambda * bits >> 4)
-    if (a.prm.rdo_zero) {
-        ex.phase([&](int tid) {
-            const int maxv = (1 << bd) - 1;
-            for (int i = 4 * tid; i < 1536; i += 4 * NT) {
-                SampleLoc l = locate(s.rs, i);
-                if (!l.log2n || !((s.rs.cbf[l.plane] >> l.tile0) & 1)) continue;
-                unsigned dc = 0, dz = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int sv = (int)s.src[i + j], pv = (int)s.pred[i + j], d0 = sv - pv, d1 = sv - clip3(0, maxv, pv + s.rs.res[i + j]);
-                    dz += (unsigned)(d0 * d0); dc += (unsigned)(d1 * d1);
-                }
-                if (dc) ex.atomic_add(&s.tu_dc[l.plane][l.tile0], dc);
-                if (dz) ex.atomic_add(&s.tu_dz[l.plane][l.tile0], dz);
-            }
-            for (int sb = tid; sb < 96; sb += NT) {       // level bits per 4x4 sub-block, summed per TU
-                int pl = sb < 64 ? 0 : 1 + ((sb - 64) >> 4), k = sb < 64 ? sb : (sb - 64) & 15;
-                int per = pl ? 4 : 8, bx = (k & (per - 1)) * 4, by = (k >> (pl ? 2 : 3)) * 4, stride = pl ? 16 : 32, base = pl ? 1024 + (pl - 1) * 256 : 0;
-                SampleLoc l = locate(s.rs, base + by * stride + bx);
-                if (!l.log2n || !((s.rs.cbf[l.plane] >> l.tile0) & 1)) continue;
-                int b = subblock_bits_q4(s.rs.lvl + base + by * stride + bx, stride);
-                if (b) ex.atomic_add(&s.tu_bits[pl][l.tile0], (unsigned)b);
-            }
-        });
-        ex.phase([&](int tid) {
-            if (tid >= 48) return;
-            const int pl = tid >> 4, t = tid & 15;
-            if (!((s.rs.cbf[pl] >> t) & 1) || !s.tu_bits[pl][t]) return;      // only a TU's first tile carries its cbf bit and sums
-            const unsigned long long jz = (unsigned long long)s.tu_dz[pl][t] << 4;
-            const unsigned long long jc = ((unsigned long long)s.tu_dc[pl][t] << 4) + (((unsigned long long)a.prm.lambda_q4 * (unsigned long long)(s.tu_bits[pl][t] + R_TU)) >> 4);
-            if (jz <= jc) ex.atomic_or(&s.tu_zero[pl], 1u << t);
-        });
-        ex.phase([&](int tid) {
-            for (int i = tid; i < 1536; i += NT) {
-                SampleLoc l = locate(s.rs, i);
-                if (l.log2n && ((s.tu_zero[l.plane] >> l.tile0) & 1)) { s.rs.lvl[i] = 0; s.rs.res[i] = 0; }
-            }
-            if (tid < 3) s.rs.cbf[tid] &= ~s.tu_zero[tid];       // (nothing in this phase reads cbf)
-        });
-    }
-    // reconstruction + outputs
+    residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, ctx.bd, whole_ctu(), a.prm.rdo_cg > 0 ? (int)(((long long)a.prm.lambda_q4 * a.prm.rdo_cg) >> 1) : 0, a.prm.sign_hide);
+}
+// RD zero-out (oracle: code_tu_inter): a TU keeps its levels only if SSE_zero << 4 > (SSE_coded << 4) + (lambda * bits >> 4)
+template <typename T, class Ex> DEV void inter_rd_zero_out(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
     ex.phase([&](int tid) {
-        const int maxv = (1 << bd) - 1;
-        for (int i = 4 * tid; i < 1536; i += 4 * NT) {      // four samples of one row per lane (a TU is at least 4 wide)
+        const int maxv = (1 << ctx.bd) - 1;
+        for (int i = 4 * tid; i < CTU_SAMPLES; i += 4 * NT) {
+            SampleLoc l = locate(s.rs, i);
+            if (!l.log2n || !((s.rs.cbf[l.plane] >> l.tile0) & 1)) continue;
+            unsigned dc = 0, dz = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int sv = (int)s.src[i + j], pv = (int)s.pred[i + j], d0 = sv - pv, d1 = sv - clip3(0, maxv, pv + s.rs.res[i + j]);
+                dz += (unsigned)(d0 * d0); dc += (unsigned)(d1 * d1);
+            }
+            if (dc) ex.atomic_add(&s.tu_dc[l.plane][l.tile0], dc);
+            if (dz) ex.atomic_add(&s.tu_dz[l.plane][l.tile0], dz);
+        }
+        for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {       // level bits per 4x4 sub-block, summed per TU
+            const SubBlock b = sub_block(sb);
+            SampleLoc l = locate(s.rs, b.at);
+            if (!l.log2n || !((s.rs.cbf[l.plane] >> l.tile0) & 1)) continue;
+            const int bits = subblock_bits_q4(s.rs.lvl + b.at, b.stride);
+            if (bits) ex.atomic_add(&s.tu_bits[b.plane][l.tile0], (unsigned)bits);
+        }
+    });
+    ex.phase([&](int tid) {
+        if (tid >= 48) return;
+        const int pl = tid >> 4, t = tid & 15;
+        if (!((s.rs.cbf[pl] >> t) & 1) || !s.tu_bits[pl][t]) return;      // only a TU's first tile carries its cbf bit and sums
+        const unsigned long long jz = (unsigned long long)s.tu_dz[pl][t] << 4;
+        const unsigned long long jc = ((unsigned long long)s.tu_dc[pl][t] << 4) + (((unsigned long long)a.prm.lambda_q4 * (unsigned long long)(s.tu_bits[pl][t] + R_TU)) >> 4);
+        if (jz <= jc) ex.atomic_or(&s.tu_zero[pl], 1u << t);
+    });
+    ex.phase([&](int tid) {
+        for (int i = tid; i < CTU_SAMPLES; i += NT) {
+            SampleLoc l = locate(s.rs, i);
+            if (l.log2n && ((s.tu_zero[l.plane] >> l.tile0) & 1)) { s.rs.lvl[i] = 0; s.rs.res[i] = 0; }
+        }
+        if (tid < 3) s.rs.cbf[tid] &= ~s.tu_zero[tid];       // (nothing in this phase reads cbf)
+    });
+}
+// reconstruction + outputs: samples, levels, CU records, rate estimate, the hand-over to the intra second pass
+template <typename T, class Ex, bool BI> DEV void inter_outputs(Ex &ex, InterShared<T> &s, BiShared *bsh, const InterArgs<T> &a, const InterCtx<T> &ctx)
+{
+    ex.phase([&](int tid) {
+        const int maxv = (1 << ctx.bd) - 1;
+        for (int i = 4 * tid; i < CTU_SAMPLES; i += 4 * NT) {      // four samples of one row per lane (a TU is at least 4 wide)
             SampleLoc l = locate(s.rs, i);
             if (!l.log2n) continue;
-            int gx = (l.plane ? x0 >> 1 : x0) + l.x, gy = (l.plane ? y0 >> 1 : y0) + l.y, v[4];
+            int gx = to_plane(l.plane, ctx.x0) + l.x, gy = to_plane(l.plane, ctx.y0) + l.y, v[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) v[j] = clip3(0, maxv, (int)s.pred[i + j] + s.rs.res[i + j]);
             store4(a.rec[l.plane].p + (ptrdiff_t)gy * a.rec[l.plane].stride + gx, v[0], v[1], v[2], v[3]);
@@ -1119,14 +1125,13 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
                 if (sse) ex.atomic_add(&s.ip_sse, (unsigned long long)sse);
             }
             if (!a.sparse_coef || ((s.rs.cbf[l.plane] >> l.tile0) & 1))
-                store4(a.coef[l.plane] + (size_t)gy * (l.plane ? a.w >> 1 : a.w) + gx, s.rs.lvl[i], s.rs.lvl[i + 1], s.rs.lvl[i + 2], s.rs.lvl[i + 3]);
+                store4(a.coef[l.plane] + (size_t)gy * to_plane(l.plane, a.w) + gx, s.rs.lvl[i], s.rs.lvl[i + 1], s.rs.lvl[i + 2], s.rs.lvl[i + 3]);
         }
         if (a.est || a.ip) {       // rate estimate: coefficient sub-block costs + a header per CU (oracle: inter estimate)
             unsigned e = 0;
-            for (int sb = tid; sb < 96; sb += NT) {
-                int pl = sb < 64 ? 0 : 1 + ((sb - 64) >> 4), k = sb < 64 ? sb : (sb - 64) & 15;
-                int per = pl ? 4 : 8, bx = (k & (per - 1)) * 4, by = (k >> (pl ? 2 : 3)) * 4, stride = pl ? 16 : 32, base = pl ? 1024 + (pl - 1) * 256 : 0, sh = pl ? 2 : 3;
-                if (s.rs.tu_log2[(by >> sh) * 4 + (bx >> sh)]) e += (unsigned)subblock_bits_q4(s.rs.lvl + base + by * stride + bx, stride);
+            for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {
+                const SubBlock b = sub_block(sb);
+                if (s.rs.tu_log2[b.tile]) e += (unsigned)subblock_bits_q4(s.rs.lvl + b.at, b.stride);
             }
             if (tid < 16 && s.rs.tu_log2[tid]) {
                 int nx, ny, nl;
@@ -1140,20 +1145,18 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
             int t = tid, txp = t & 3, typ = t >> 2, node = s.tile_node[t], nx, ny, nl;
             node_geom(node, nx, ny, nl);
             int t0 = (ny >> 3) * 4 + (nx >> 3);
-            mihevc_cu_rec r;
+            mihevc_cu_rec r{};      // intra_mode[1..3], cbf_y4 and padding zero
             r.log2_size = (uint8_t)nl;
-            r.flags = (uint8_t)(CU_INTER | ((s.rs.cbf[0] >> t0) & 1 ? CU_CBF_Y : 0) | ((s.rs.cbf[1] >> t0) & 1 ? CU_CBF_CB : 0) |
-                                ((s.rs.cbf[2] >> t0) & 1 ? CU_CBF_CR : 0));
+            r.flags = (uint8_t)(CU_INTER | cbf_flags(s.rs.cbf, t0));
             r.chroma_mode = 1; r.qp = (uint8_t)a.prm.qp;
-            r.intra_mode[0] = 1; r.intra_mode[1] = r.intra_mode[2] = r.intra_mode[3] = 0;
+            r.intra_mode[0] = 1;
             r.mvx = (int16_t)s.tile_mvx[t]; r.mvy = (int16_t)s.tile_mvy[t];
             if constexpr (BI) {        // which lists the CU predicts from; the list-1 vector lives in the bytes inter CUs do not use (include/mihevc.h)
                 const int mode = bsh->tile_mode[t], x1 = bsh->tile_mv1x[t], y1 = bsh->tile_mv1y[t];
                 r.flags |= (uint8_t)((mode != 0 ? CU_L1 : 0) | (mode == 1 ? CU_NOL0 : 0));
                 r.intra_mode[0] = (uint8_t)(x1 & 255); r.intra_mode[1] = (uint8_t)((x1 >> 8) & 255); r.intra_mode[2] = (uint8_t)(y1 & 255); r.intra_mode[3] = (uint8_t)((y1 >> 8) & 255);
             }
-            r.cbf_y4 = 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
-            a.cu[(size_t)((y0 >> 3) + typ) * (a.w >> 3) + (x0 >> 3) + txp] = r;
+            a.cu[(size_t)((ctx.y0 >> 3) + typ) * (a.w >> 3) + (ctx.x0 >> 3) + txp] = r;
         }
     });
     if (a.est || a.ip) ex.phase([&](int tid) {
@@ -1164,9 +1167,26 @@ DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win
             o.jinter = (s.ip_sse << 4) + (((unsigned long long)a.prm.lambda_q4 * (unsigned long long)s.est) >> 4);
             o.est = s.est;
             o.cand = s.ip_cost > (s.ip_act << 4) && s.ip_cost >= ((4u * 64u * s.ip_tiles) << 4);
-            a.ip[ctu] = o;
+            a.ip[ctx.ctu] = o;
         }
     });
+}
+
+template <typename T, class Ex, bool BI = false>
+DEV void inter_ctu_program(Ex &ex, InterShared<T> &s, T *win_y, T *win_u, T *win_v, const InterArgs<T> &a, int ctu, BiShared *bsh = nullptr)
+{
+    const int R0 = a.prm.me_range, R = R0 + 3, x0 = (ctu % a.ctus_w) * CTU, y0 = (ctu / a.ctus_w) * CTU, mct = a.prm.mc_top, mcb = a.prm.mc_bottom;
+    const int sx = wave_uniform(a.centers ? a.centers[2 * ctu] : 0), sy0 = wave_uniform(a.centers ? a.centers[2 * ctu + 1] : 0);
+    const int sy = (mct || mcb) ? clamp_center_y(sy0, y0, R0, a.h, mct, mcb) : sy0;
+    const InterCtx<T> ctx{ctu, x0, y0, R, a.prm.bit_depth, a.prm.lambda_sad_q4, mct, mcb, sx, sy, mc_win_y_stride(R0), mc_win_c_stride(R0), win_y, win_u, win_v, win_origin(x0, y0, sx, sy, R)};
+    inter_load(ex, s, a, ctx);
+    inter_tree(ex, s, a, ctx);
+    inter_refine(ex, s, a, ctx, sx, sy, ctx.o0);
+    if constexpr (BI) inter_b_block(ex, s, *bsh, a, ctx);
+    else inter_predict_uni(ex, s, a, ctx);
+    inter_residual(ex, s, a, ctx);
+    if (a.prm.rdo_zero) inter_rd_zero_out(ex, s, a, ctx);
+    inter_outputs<T, Ex, BI>(ex, s, bsh, a, ctx);
 }
 
 }  // namespace mihevc

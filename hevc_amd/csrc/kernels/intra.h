@@ -235,20 +235,8 @@ DEV void intra_tile_diff(const T *L, int log2n, int mode, int angle, int inv, in
     }
 }
 
-// 8.4.2 candModeList of the PU whose top-left luma sample is (px, py) in CTU coordinates (a CU, or a 4x4 PU of an NxN
-// CU).  A neighbouring NxN CU answers with the mode of the 4x4 PU that holds the neighbouring sample; the left CTU's
-// right column comes from s.left_cu; the CTU above is never consulted (8.4.2: DC).
-template <typename T> DEV void mpm_cand(const IntraShared<T> &s, int px, int py, bool left_ok, int (&cand)[3])
+DEV void cand_from(int ma, int mb, int (&cand)[3])       // 8.4.2 candModeList from the left (ma) and above (mb) modes
 {
-    int ma = 1, mb = 1;
-    if (px > 0 || left_ok) {
-        const mihevc_cu_rec &r = px > 0 ? s.cu_acc[(py >> 3) * 4 + ((px - 1) >> 3)] : s.left_cu[py >> 3];
-        if (!(r.flags & CU_INTER)) ma = r.intra_mode[(r.flags & CU_NXN) ? ((py >> 2) & 1) * 2 + (((px - 1) >> 2) & 1) : 0];
-    }
-    if (py > 0) {
-        const mihevc_cu_rec &r = s.cu_acc[((py - 1) >> 3) * 4 + (px >> 3)];
-        if (!(r.flags & CU_INTER)) mb = r.intra_mode[(r.flags & CU_NXN) ? (((py - 1) >> 2) & 1) * 2 + ((px >> 2) & 1) : 0];
-    }
     if (ma == mb) {
         if (ma < 2) { cand[0] = 0; cand[1] = 1; cand[2] = 26; }
         else { cand[0] = ma; cand[1] = 2 + ((ma + 29) & 31); cand[2] = 2 + ((ma - 2 + 1) & 31); }
@@ -256,6 +244,16 @@ template <typename T> DEV void mpm_cand(const IntraShared<T> &s, int px, int py,
         cand[0] = ma; cand[1] = mb;
         cand[2] = (ma != 0 && mb != 0) ? 0 : (ma != 1 && mb != 1) ? 1 : 26;
     }
+}
+// 8.4.2 candModeList of the PU whose top-left luma sample is (px, py) in CTU coordinates (a CU, or a 4x4 PU of an NxN
+// CU).  A neighbouring NxN CU answers with the mode of the 4x4 PU that holds the neighbouring sample; the left CTU's
+// right column comes from s.left_cu; the CTU above is never consulted (8.4.2: DC).
+template <typename T> DEV void mpm_cand(const IntraShared<T> &s, int px, int py, bool left_ok, int (&cand)[3])
+{
+    auto mode_at = [](const mihevc_cu_rec &r, int x, int y) { return (r.flags & CU_INTER) ? 1 : (int)r.intra_mode[(r.flags & CU_NXN) ? ((y >> 2) & 1) * 2 + ((x >> 2) & 1) : 0]; };
+    const int ma = px > 0 ? mode_at(s.cu_acc[(py >> 3) * 4 + ((px - 1) >> 3)], px - 1, py) : left_ok ? mode_at(s.left_cu[py >> 3], px - 1, py) : 1;
+    const int mb = py > 0 ? mode_at(s.cu_acc[((py - 1) >> 3) * 4 + (px >> 3)], px, py - 1) : 1;
+    cand_from(ma, mb, cand);
 }
 
 DEV bool intra_filter_on(int log2n, int mode)
@@ -304,16 +302,6 @@ DEV int ref_source(const unsigned *m, int i, int total)
 }
 DEV int level_first(int level) { return level == 0 ? 0 : level == 1 ? 1 : 5; }      // level 0 / 1 / 2 = the 32x32 / 16x16 / 8x8 nodes
 DEV int mode_bits_for(const int (&cand)[3], int mode) { return mode == cand[0] ? 2 : (mode == cand[1] || mode == cand[2]) ? 3 : 6; }
-DEV void cand_from(int ma, int mb, int (&cand)[3])       // 8.4.2 candModeList from the left (ma) and above (mb) modes
-{
-    if (ma == mb) {
-        if (ma < 2) { cand[0] = 0; cand[1] = 1; cand[2] = 26; }
-        else { cand[0] = ma; cand[1] = 2 + ((ma + 29) & 31); cand[2] = 2 + ((ma - 2 + 1) & 31); }
-    } else {
-        cand[0] = ma; cand[1] = mb;
-        cand[2] = (ma != 0 && mb != 0) ? 0 : (ma != 1 && mb != 1) ? 1 : 26;
-    }
-}
 // the plan's candidate list of a node: planned modes of the same-level nodes left of and above it inside the CTU, DC outside
 template <typename T> DEV void plan_cand(const IntraShared<T> &s, int node, int level, int (&cand)[3])
 {
@@ -325,23 +313,78 @@ template <typename T> DEV void plan_cand(const IntraShared<T> &s, int node, int 
     cand_from(ma, mb, cand);
 }
 
+// ------------------------------------------------------------------------------------------ rules both stages share
+// the neighbourhood image: sample (x, y) of a plane in CTU coordinates, x and y from -1 (the row above and the column left of the CTU)
+template <typename T> DEV T &nb(IntraShared<T> &s, int plane, int x, int y)
+{
+    return plane ? s.rec_c[plane - 1][(y + 1) * RC_STRIDE + x + 1] : s.rec_y[(y + 1) * RY_STRIDE + x + 1];
+}
+// 6.4.1: the neighbour at luma picture position (lx, ly) is available to the block whose z-scan address is z_cur: inside the picture and the tile, decoded earlier
+template <typename T> DEV bool ref_available(const IntraArgs<T> &a, const TileBox &tb, int lx, int ly, int z_cur)
+{
+    return lx >= tb.x_lo && ly >= tb.y_lo && lx < a.w && lx < tb.x_hi && ly < a.h && zaddr(lx, ly, a.ctus_w) < z_cur;
+}
+// 8.4.4.2.3: filtered sample i of the 4n + 1 luma reference samples L ([1 2 1], or the bi-linear form where a 32x32 block's references are flat)
+template <typename T> DEV int smooth_ref(const T *L, int n, int i, int bd)
+{
+    if (i == 0 || i == 4 * n) return L[i];
+    const int thr = 1 << (bd - 5);
+    if (n == 32 && iabs(L[64] + L[128] - 2 * L[96]) < thr && iabs(L[64] + L[0] - 2 * L[32]) < thr)
+        return i == 64 ? L[64] : i < 64 ? (i * L[64] + (64 - i) * L[0] + 32) >> 6 : ((128 - i) * L[64] + (i - 64) * L[128] + 32) >> 6;
+    return (L[i - 1] + 2 * L[i] + L[i + 1] + 2) >> 2;
+}
+// 8.4.4.2.5 dcVal of a block of 1 << lg samples per side
+template <typename T> DEV int dc_of(const T *L, int lg)
+{
+    const int np = 1 << lg;
+    int sum = np;
+    for (int i = 0; i < np; i++) sum += ref_top(L, np, i) + ref_left(L, np, i);
+    return sum >> (lg + 1);
+}
+// one lane's share of the LDS copies of the mode and quantiser tables and of the 4x4 matrices
+template <typename T> DEV void load_intra_tables(IntraShared<T> &s, int tid)
+{
+    if (tid >= 64 && tid < 99) { s.tab_angle[tid - 64] = (int16_t)mode_angle(tid - 64); s.tab_inv[tid - 64] = (int16_t)mode_inv_angle(tid - 64); }
+    if (tid >= 128 && tid < 134) { s.tab_qs[tid - 128] = g_tab.quant_scale[tid - 128]; s.tab_ls[tid - 128] = g_tab.level_scale[tid - 128]; }
+    if (tid < 32) s.nx_mat[tid >> 4][tid & 15] = tid < 16 ? g_tab.dst4[(tid >> 2) & 3][tid & 3] : g_tab.mat[((tid >> 2) & 3) * 8][tid & 3];
+}
+// the ring of the neighbourhood image from the picture `planes` (the source in the plan stage, the reconstruction in the code stage; zero outside the
+// picture): row -1 (cols -1..63 luma / -1..31 chroma) and column -1 (rows 0..31 / 0..15)
+template <typename T, typename P> DEV void load_ring(IntraShared<T> &s, const P (&planes)[3], int x0, int y0, int w, int h, int tid)
+{
+    for (int u = tid; u < 65 + 32 + 2 * (33 + 16); u += NT) {
+        int pl, k, row_len;
+        if (u < 97) { pl = 0; k = u; row_len = 65; } else { pl = 1 + (u - 97) / 49; k = (u - 97) % 49; row_len = 33; }
+        int xn, yn;
+        if (k < row_len) { xn = k - 1; yn = -1; } else { xn = -1; yn = k - row_len; }
+        const int gx = to_plane(pl, x0) + xn, gy = to_plane(pl, y0) + yn;
+        T v = 0;
+        if (gx >= 0 && gy >= 0 && gx < to_plane(pl, w) && gy < to_plane(pl, h)) v = planes[pl].p[(ptrdiff_t)gy * planes[pl].stride + gx];
+        nb(s, pl, xn, yn) = v;
+    }
+}
+// J of an intra CU: SSE << 4 + lambda x (mode bits, part mode / chroma mode / cbf bins, the TUs' level bits), in the oracle's units
+template <typename B> DEV unsigned long long intra_cu_cost(int lambda_q4, const int (&cand)[3], int mode, int cmode, const B (&tu_bits)[3], unsigned sse)
+{
+    unsigned bits = 16u * (unsigned)mode_bits_for(cand, mode) + 16 + 24 + (cmode != mode ? 32 : 0);
+    for (int p = 0; p < 3; p++) bits += tu_bits[p] ? (unsigned)tu_bits[p] + R_TU : 0;
+    return ((unsigned long long)sse << 4) + (((unsigned long long)lambda_q4 * (unsigned long long)bits) >> 4);
+}
+
 // ------------------------------------------------------------------------------------------ stage A: the plan
 // oracle/hevc_oracle.c intra_plan_ctu: every quadtree node of the CTU is costed on the SOURCE picture (its neighbours stand in for the
 // reconstruction, under the real availability rules), so the CTUs of a picture are independent: one launch plans them all, and the
 // 21 nodes of a CTU are worked on side by side — reference samples of all nodes, then 1680 (node, mode, tile) SATD units over the 256
 // lanes, the MPM-aware mode pick (a z-order chain per level, run by one wave per level), and per level one pass of prediction, K3
 // residual coding of the WHOLE CTU and distortion + rate per node; the tree is then decided bottom-up on those RD costs.
-template <typename T, class Ex>
-DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int ctu_x, int ctu_y)
+
+// tables, source image, node validity and the source neighbourhood image
+template <typename T, class Ex> DEV void plan_load(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, int y0)
 {
-    const int x0 = ctu_x * CTU, y0 = ctu_y * CTU, bd = a.prm.bit_depth;
-    const TileBox tb = tile_box(a, ctu_x, ctu_y);
     residual_init(ex, s.rs);
     ex.phase([&](int tid) {
         load_ctu_source<T>(s.src, a.src, x0, y0, a.w, a.h, tid);
-        if (tid >= 64 && tid < 99) { s.tab_angle[tid - 64] = (int16_t)mode_angle(tid - 64); s.tab_inv[tid - 64] = (int16_t)mode_inv_angle(tid - 64); }
-        if (tid >= 128 && tid < 134) { s.tab_qs[tid - 128] = g_tab.quant_scale[tid - 128]; s.tab_ls[tid - 128] = g_tab.level_scale[tid - 128]; }
-        if (tid < 32) s.nx_mat[tid >> 4][tid & 15] = tid < 16 ? g_tab.dst4[(tid >> 2) & 3][tid & 3] : g_tab.mat[((tid >> 2) & 3) * 8][tid & 3];
+        load_intra_tables(s, tid);
         if (tid >= 160 && tid < 181) {
             int nx, ny, nl;
             node_geom(tid - 160, nx, ny, nl);
@@ -350,26 +393,20 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
         }
         for (int i = tid; i < 21 * 35; i += NT) s.p_msum[i / 35][i % 35] = 0;
         for (int i = tid; i < 21 * 15; i += NT) s.p_av[i / 15][(i % 15) / 5][i % 5] = 0;
-        // source neighbourhood ring: row -1 (cols -1..63 luma / -1..31 chroma) and column -1 (rows 0..31 / 0..15)
-        for (int u = tid; u < 65 + 32 + 2 * (33 + 16); u += NT) {
-            int pl, k, row_len;
-            if (u < 97) { pl = 0; k = u; row_len = 65; } else { pl = 1 + (u - 97) / 49; k = (u - 97) % 49; row_len = 33; }
-            int xn, yn;
-            if (k < row_len) { xn = k - 1; yn = -1; } else { xn = -1; yn = k - row_len; }
-            const int pw = pl ? a.w >> 1 : a.w, ph = pl ? a.h >> 1 : a.h, gx = (pl ? x0 >> 1 : x0) + xn, gy = (pl ? y0 >> 1 : y0) + yn;
-            T v = 0;
-            if (gx >= 0 && gy >= 0 && gx < pw && gy < ph) v = a.src[pl].p[(ptrdiff_t)gy * a.src[pl].stride + gx];
-            if (pl == 0) s.rec_y[(yn + 1) * RY_STRIDE + xn + 1] = v; else s.rec_c[pl - 1][(yn + 1) * RC_STRIDE + xn + 1] = v;
-        }
+        load_ring(s, a.src, x0, y0, a.w, a.h, tid);
     });
     ex.phase([&](int tid) {      // the CTU's own source samples complete the neighbourhood image
-        for (int i = tid; i < 1536; i += NT) {
-            if (i < 1024) s.rec_y[((i >> 5) + 1) * RY_STRIDE + (i & 31) + 1] = s.src[i];
-            else { const int k = (i - 1024) & 255; s.rec_c[(i - 1024) >> 8][((k >> 4) + 1) * RC_STRIDE + (k & 15) + 1] = s.src[i]; }
+        for (int i = tid; i < CTU_SAMPLES; i += NT) {
+            const CtuSample c = ctu_sample(i);
+            nb(s, c.plane, c.x, c.y) = s.src[i];
         }
     });
-    // reference samples of every node and plane: availability + raw values, substitution (in place: an available sample keeps its value
-    // and only those are read), smoothing + DC
+}
+// reference samples of every node and plane: availability + raw values, substitution (in place: an available sample keeps its value
+// and only those are read), smoothing + DC
+template <typename T, class Ex> DEV void plan_refs(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, int y0, const TileBox &tb)
+{
+    const int bd = a.prm.bit_depth;
     auto for_refs = [&](int tid, auto &&f) {
         for (int level = 0; level < 3; level++) {
             const int n = 32 >> level, ty = 4 * n + 1, tc = 2 * n + 1, per = ty + 2 * tc, cnt = 1 << (2 * level);
@@ -385,10 +422,10 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
         for_refs(tid, [&](int nd, int n, int pl, int i) {
             int cx, cy, l2, xn, yn;
             node_geom(nd, cx, cy, l2);
-            ref_pos(pl ? cx >> 1 : cx, pl ? cy >> 1 : cy, pl ? n >> 1 : n, i, xn, yn);
-            const int sh = pl ? 1 : 0, lx = xn * (1 << sh) + x0, ly = yn * (1 << sh) + y0;
-            const bool ok = lx >= tb.x_lo && ly >= tb.y_lo && lx < a.w && lx < tb.x_hi && ly < a.h && zaddr(lx, ly, a.ctus_w) < zaddr(x0 + cx, y0 + cy, a.ctus_w);
-            const T v = ok ? (pl ? s.rec_c[pl - 1][(yn + 1) * RC_STRIDE + xn + 1] : s.rec_y[(yn + 1) * RY_STRIDE + xn + 1]) : (T)0;
+            ref_pos(to_plane(pl, cx), to_plane(pl, cy), to_plane(pl, n), i, xn, yn);
+            const int sh = pl ? 1 : 0;
+            const bool ok = ref_available(a, tb, xn * (1 << sh) + x0, yn * (1 << sh) + y0, zaddr(x0 + cx, y0 + cy, a.ctus_w));
+            const T v = ok ? nb(s, pl, xn, yn) : (T)0;
             if (pl) s.p_refc[nd][pl - 1][i] = v; else s.p_ref[nd][i] = v;
             if (ok) ex.atomic_or(&s.p_av[nd][pl][i >> 5], 1u << (i & 31));
         });
@@ -406,14 +443,7 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
             const int n = 32 >> level, total = 4 * n + 1, cnt = 1 << (2 * level);
             for (int u = tid; u < cnt * total; u += NT) {
                 const int i = u % total, nd = level_first(level) + u / total;
-                if (!s.p_valid[nd]) continue;
-                const T *L = s.p_ref[nd];
-                int v;
-                if (i == 0 || i == total - 1) v = L[i];
-                else if (n == 32 && iabs(L[64] + L[128] - 2 * L[96]) < (1 << (bd - 5)) && iabs(L[64] + L[0] - 2 * L[32]) < (1 << (bd - 5)))
-                    v = i == 64 ? L[64] : i < 64 ? (i * L[64] + (64 - i) * L[0] + 32) >> 6 : ((128 - i) * L[64] + (i - 64) * L[128] + 32) >> 6;
-                else v = (L[i - 1] + 2 * L[i] + L[i + 1] + 2) >> 2;
-                s.p_filt[nd][i] = (T)v;
+                if (s.p_valid[nd]) s.p_filt[nd][i] = (T)smooth_ref(s.p_ref[nd], n, i, bd);
             }
         }
         for (int u = tid; u < 63; u += NT) {
@@ -421,14 +451,14 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
             if (!s.p_valid[nd]) continue;
             int cx, cy, l2;
             node_geom(nd, cx, cy, l2);
-            const int np = pl ? 1 << (l2 - 1) : 1 << l2, lg = pl ? l2 - 1 : l2;
-            const T *L = pl ? s.p_refc[nd][pl - 1] : s.p_ref[nd];
-            int sum = np;
-            for (int i = 0; i < np; i++) sum += ref_top(L, np, i) + ref_left(L, np, i);
-            s.p_dc[nd][pl] = sum >> (lg + 1);
+            s.p_dc[nd][pl] = dc_of(pl ? s.p_refc[nd][pl - 1] : s.p_ref[nd], pl ? l2 - 1 : l2);
         }
     });
-    // 35 modes x every 8x8 tile of every node: 3 x 560 SATD units
+}
+// luma mode of every node: SATD of 35 modes x every 8x8 tile (3 x 560 units), then the MPM-aware pick
+template <typename T, class Ex> DEV void plan_rank_luma(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a)
+{
+    const int bd = a.prm.bit_depth;
     ex.phase([&](int tid) {
         for (int u = tid; u < 3 * 560; u += NT) {
             const int level = 2 - u / 560, v = u % 560;        // the 8x8 level first: its lanes diverge least
@@ -440,7 +470,7 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
             const int tiles = 1 << (l2 - 3), tx = (t % tiles) * 8, ty = (t / tiles) * 8;
             const T *L = intra_filter_on(l2, mode) ? s.p_filt[nd] : s.p_ref[nd];
             int m[8][8];
-            intra_tile_diff<T>(L, l2, mode, s.tab_angle[mode], s.tab_inv[mode], tx, ty, bd, s.p_dc[nd][0], s.src + (cy + ty) * 32 + cx + tx, 32, m);
+            intra_tile_diff<T>(L, l2, mode, s.tab_angle[mode], s.tab_inv[mode], tx, ty, bd, s.p_dc[nd][0], s.src + ctu_index(0, cx + tx, cy + ty), 32, m);
             ex.atomic_add(&s.p_msum[nd][mode], (unsigned)hadamard8_satd(m));
         }
     });
@@ -458,149 +488,144 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
             ex.atomic_min(&s.p_key[nd], ((unsigned long long)cost << 6) | (unsigned)mode);      // ties -> lowest mode
         });
     ex.phase([&](int) {});       // the wave steps carry no barrier: everybody waits here for the three chains
-    for (int level = 0; level < 3; level++) {
-        const int log2n = 5 - level, n = 1 << log2n, nc = n >> 1, l2c = log2n - 1, tw = nc >= 8 ? 8 : 4, ct = nc / tw, ntc = ct * ct;
-        const int cnt = 1 << (2 * level), first = level_first(level);
-        // intra_chroma_pred_mode: DM or planar / 26 / 10 / DC (a candidate equal to the luma mode stands for 34) by SATD over Cb + Cr +
-        // lambda * (1 bit DM, 3 bits otherwise), DM wins ties; every tile split into lines: one lane predicts a row and transforms it,
-        // a second phase finishes one column each
-        if (a.prm.chroma_modes) {
-            const int nline = cnt * 5 * 2 * ntc * tw;
-            ex.phase([&](int tid) {
-                for (int u = tid; u < nline; u += NT) {
-                    const int y = u % tw, t = (u / tw) % ntc, pl = 1 + (u / (tw * ntc)) % 2, k = (u / (tw * ntc * 2)) % 5, nk = u / (tw * ntc * 10), nd = first + nk;
-                    if (!s.p_valid[nd]) continue;
-                    const int mode = (int)(s.p_key[nd] & 63), base = k == 1 ? 0 : k == 2 ? 26 : k == 3 ? 10 : 1, m = k == 0 ? mode : (base == mode ? 34 : base);
-                    int cx, cy, l2;
-                    node_geom(nd, cx, cy, l2);
-                    const T *L = s.p_refc[nd][pl - 1];
-                    const int tx = (t % ct) * tw, ty = (t / ct) * tw, ang = s.tab_angle[m], inv = s.tab_inv[m];
-                    const int sbase = 1024 + (pl - 1) * 256 + ((cy >> 1) + ty + y) * 16 + (cx >> 1) + tx;
+}
+// chroma mode of the level's nodes: intra_chroma_pred_mode is DM or planar / 26 / 10 / DC (a candidate equal to the luma mode stands for 34) by SATD
+// over Cb + Cr + lambda * (1 bit DM, 3 bits otherwise), DM wins ties; every tile split into lines: one lane predicts a row and transforms it,
+// a second phase finishes one column each.  The last phase settles both modes of every node and sets the level's TUs up for plan_level_cost.
+template <typename T, class Ex> DEV void plan_rank_chroma(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int level)
+{
+    const int bd = a.prm.bit_depth, log2n = 5 - level, l2c = log2n - 1, nc = 16 >> level, tw = nc >= 8 ? 8 : 4, ct = nc / tw, ntc = ct * ct;      // tw: chroma SATD tile
+    const int cnt = 1 << (2 * level), first = level_first(level);
+    if (a.prm.chroma_modes) {
+        const int nline = cnt * 5 * 2 * ntc * tw;
+        ex.phase([&](int tid) {
+            for (int u = tid; u < nline; u += NT) {
+                const int y = u % tw, t = (u / tw) % ntc, pl = 1 + (u / (tw * ntc)) % 2, k = (u / (tw * ntc * 2)) % 5, nk = u / (tw * ntc * 10), nd = first + nk;
+                if (!s.p_valid[nd]) continue;
+                const int mode = (int)(s.p_key[nd] & 63), base = k == 1 ? 0 : k == 2 ? 26 : k == 3 ? 10 : 1, m = k == 0 ? mode : (base == mode ? 34 : base);
+                int cx, cy, l2;
+                node_geom(nd, cx, cy, l2);
+                const T *L = s.p_refc[nd][pl - 1];
+                const int tx = (t % ct) * tw, ty = (t / ct) * tw, ang = s.tab_angle[m], inv = s.tab_inv[m];
+                const int sbase = ctu_index(pl, (cx >> 1) + tx, (cy >> 1) + ty + y);
+                int d[8];
+#pragma unroll
+                for (int x = 0; x < 8; x++) d[x] = x < tw ? (int)s.src[sbase + x] - intra_sample<T>(L, l2c, m, ang, inv, tx + x, ty + y, pl, bd, s.p_dc[nd][pl]) : 0;
+                if (tw == 8) butterfly8(d);
+                else {
+                    const int p0 = d[0] + d[1], p1 = d[0] - d[1], p2 = d[2] + d[3], p3 = d[2] - d[3];
+                    d[0] = p0 + p2; d[1] = p1 + p3; d[2] = p0 - p2; d[3] = p1 - p3;
+                }
+                int16_t *o = s.p_crow + ((((nk * 5 + k) * 2 + (pl - 1)) * ntc + t) * tw + y) * tw;
+#pragma unroll
+                for (int x = 0; x < 8; x++) if (x < tw) o[x] = (int16_t)d[x];
+            }
+            for (int i = tid; i < 160; i += NT) s.p_craw[i] = 0;
+        });
+        ex.phase([&](int tid) {
+            for (int u = tid; u < nline; u += NT) {
+                const int x = u % tw, t = (u / tw) % ntc, pl = (u / (tw * ntc)) % 2, k = (u / (tw * ntc * 2)) % 5, nk = u / (tw * ntc * 10);
+                if (!s.p_valid[first + nk]) continue;
+                const int16_t *c = s.p_crow + (((nk * 5 + k) * 2 + pl) * ntc + t) * tw * tw + x;
+                int sum;
+                if (tw == 8) {
                     int d[8];
 #pragma unroll
-                    for (int x = 0; x < 8; x++) d[x] = x < tw ? (int)s.src[sbase + x] - intra_sample<T>(L, l2c, m, ang, inv, tx + x, ty + y, pl, bd, s.p_dc[nd][pl]) : 0;
-                    if (tw == 8) {
+                    for (int y = 0; y < 8; y++) d[y] = c[y * 8];
+                    butterfly8(d);
+                    sum = 0;
 #pragma unroll
-                        for (int st = 1; st < 8; st <<= 1)
-#pragma unroll
-                            for (int i = 0; i < 8; i++)
-                                if (!(i & st)) { int p = d[i], q = d[i + st]; d[i] = p + q; d[i + st] = p - q; }
-                    } else {
-                        const int p0 = d[0] + d[1], p1 = d[0] - d[1], p2 = d[2] + d[3], p3 = d[2] - d[3];
-                        d[0] = p0 + p2; d[1] = p1 + p3; d[2] = p0 - p2; d[3] = p1 - p3;
-                    }
-                    int16_t *o = s.p_crow + ((((nk * 5 + k) * 2 + (pl - 1)) * ntc + t) * tw + y) * tw;
-#pragma unroll
-                    for (int x = 0; x < 8; x++) if (x < tw) o[x] = (int16_t)d[x];
-                }
-                for (int i = tid; i < 160; i += NT) s.p_craw[i] = 0;
-            });
-            ex.phase([&](int tid) {
-                for (int u = tid; u < nline; u += NT) {
-                    const int x = u % tw, t = (u / tw) % ntc, pl = (u / (tw * ntc)) % 2, k = (u / (tw * ntc * 2)) % 5, nk = u / (tw * ntc * 10);
-                    if (!s.p_valid[first + nk]) continue;
-                    const int16_t *c = s.p_crow + (((nk * 5 + k) * 2 + pl) * ntc + t) * tw * tw + x;
-                    int sum;
-                    if (tw == 8) {
-                        int d[8];
-#pragma unroll
-                        for (int y = 0; y < 8; y++) d[y] = c[y * 8];
-#pragma unroll
-                        for (int st = 1; st < 8; st <<= 1)
-#pragma unroll
-                            for (int i = 0; i < 8; i++)
-                                if (!(i & st)) { int p = d[i], q = d[i + st]; d[i] = p + q; d[i + st] = p - q; }
-                        sum = 0;
-#pragma unroll
-                        for (int y = 0; y < 8; y++) sum += iabs(d[y]);
-                    } else {
-                        const int p0 = c[0] + c[4], p1 = c[0] - c[4], p2 = c[8] + c[12], p3 = c[8] - c[12];
-                        sum = iabs(p0 + p2) + iabs(p1 + p3) + iabs(p0 - p2) + iabs(p1 - p3);
-                    }
-                    ex.atomic_add(&s.p_craw[((nk * 5 + k) * 2 + pl) * ntc + t], (unsigned)sum);
-                }
-            });
-        }
-        ex.phase([&](int tid) {
-            if (tid < cnt && s.p_valid[first + tid]) {
-                const int nd = first + tid, mode = (int)(s.p_key[nd] & 63);
-                int cmode = mode;
-                if (a.prm.chroma_modes) {
-                    unsigned long long best = ~0ull;
-                    for (int k = 0; k < 5; k++) {
-                        unsigned satd = 0;          // per tile (sum |H d H| + 2) >> 2 for 8x8 tiles, (sum + 1) >> 1 for the 4x4 blocks
-                        for (int p = 0; p < 2 * ntc; p++) { const unsigned r = s.p_craw[(tid * 5 + k) * 2 * ntc + p]; satd += tw == 8 ? (r + 2) >> 2 : (r + 1) >> 1; }
-                        const unsigned long long key = ((unsigned long long)((satd << 4) + (unsigned)(a.prm.lambda_sad_q4 * (k == 0 ? 1 : 3))) << 3) | (unsigned)k;
-                        best = key < best ? key : best;
-                    }
-                    const int k = (int)(best & 7), base = k == 1 ? 0 : k == 2 ? 26 : k == 3 ? 10 : 1;
-                    if (k) cmode = base == mode ? 34 : base;
-                }
-                s.p_mode[nd] = (uint8_t)mode; s.p_cmode[nd] = (uint8_t)cmode;
-                s.p_sse[nd] = 0; s.p_bits[nd][0] = s.p_bits[nd][1] = s.p_bits[nd][2] = 0;
-            }
-            if (tid >= 64 && tid < 80) {
-                const int t = tid - 64;
-                s.rs.tu_log2[t] = s.p_valid[node_of_tile(level, t & 3, t >> 2)] ? (uint8_t)log2n : 0;
-                s.rs.tu_intra[t] = 1;
-            }
-            if (tid >= 96 && tid < 99) s.rs.cbf[tid - 96] = 0;
-        });
-        // RD cost of every node of the level with its modes: prediction (still from the source neighbourhood), K3 over the whole CTU,
-        // distortion and rate per node
-        ex.phase([&](int tid) {
-            for (int i = tid; i < 1536; i += NT) {
-                SampleLoc l = locate(s.rs, i);
-                s.rs.desc[i] = pack_loc(l);
-                if (!l.log2n) continue;
-                const int sh = l.plane ? 2 : 3, nd = node_of_tile(level, l.x >> sh, l.y >> sh);
-                int cx, cy, l2, v;
-                node_geom(nd, cx, cy, l2);
-                if (l.plane == 0) {
-                    const int mode = s.p_mode[nd];
-                    const T *L = intra_filter_on(log2n, mode) ? s.p_filt[nd] : s.p_ref[nd];
-                    v = intra_sample<T>(L, log2n, mode, s.tab_angle[mode], s.tab_inv[mode], l.x - cx, l.y - cy, 0, bd, s.p_dc[nd][0]);
+                    for (int y = 0; y < 8; y++) sum += iabs(d[y]);
                 } else {
-                    const int cm = s.p_cmode[nd];
-                    v = intra_sample<T>(s.p_refc[nd][l.plane - 1], l2c, cm, s.tab_angle[cm], s.tab_inv[cm], l.x - (cx >> 1), l.y - (cy >> 1), l.plane, bd, s.p_dc[nd][l.plane]);
+                    const int p0 = c[0] + c[4], p1 = c[0] - c[4], p2 = c[8] + c[12], p3 = c[8] - c[12];
+                    sum = iabs(p0 + p2) + iabs(p1 + p3) + iabs(p0 - p2) + iabs(p1 - p3);
                 }
-                s.pred[i] = (T)v;
-                s.rs.res[i] = (int16_t)((int)s.src[i] - v);
+                ex.atomic_add(&s.p_craw[((nk * 5 + k) * 2 + pl) * ntc + t], (unsigned)sum);
             }
-        });
-        residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, whole_ctu());      // no sign hiding: these levels are a cost estimate, intra_code_cu recodes every CU
-        ex.phase([&](int tid) {
-            const int maxv = (1 << bd) - 1;
-            for (int i = 4 * tid; i < 1536; i += 4 * NT) {
-                SampleLoc l = locate(s.rs, i);
-                if (!l.log2n) continue;
-                const int sh = l.plane ? 2 : 3;
-                unsigned sse = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) { const int d = (int)s.src[i + j] - clip3(0, maxv, (int)s.pred[i + j] + s.rs.res[i + j]); sse += (unsigned)(d * d); }
-                if (sse) ex.atomic_add(&s.p_sse[node_of_tile(level, l.x >> sh, l.y >> sh)], sse);
-            }
-            for (int sb = tid; sb < 96; sb += NT) {       // 64 luma + 16 + 16 chroma 4x4 sub-blocks
-                const int pl = sb < 64 ? 0 : 1 + ((sb - 64) >> 4), k = sb < 64 ? sb : (sb - 64) & 15;
-                const int per = pl ? 4 : 8, bx = (k & (per - 1)) * 4, by = (k >> (pl ? 2 : 3)) * 4, stride = pl ? 16 : 32, base = pl ? 1024 + (pl - 1) * 256 : 0, sh = pl ? 2 : 3;
-                const int tile = (by >> sh) * 4 + (bx >> sh);
-                if (!s.rs.tu_log2[tile]) continue;
-                const int b = subblock_bits_q4(s.rs.lvl + base + by * stride + bx, stride);
-                if (b) ex.atomic_add(&s.p_bits[node_of_tile(level, tile & 3, tile >> 2)][pl], (unsigned)b);
-            }
-        });
-        ex.phase([&](int tid) {
-            if (tid >= cnt) return;
-            const int nd = first + tid;
-            if (!s.p_valid[nd]) { s.p_j[nd] = 0; return; }
-            int cand[3];
-            plan_cand(s, nd, level, cand);
-            unsigned bits = 16u * (unsigned)mode_bits_for(cand, s.p_mode[nd]) + 16 + 24 + (s.p_cmode[nd] != s.p_mode[nd] ? 32 : 0);
-            for (int p = 0; p < 3; p++) bits += s.p_bits[nd][p] ? s.p_bits[nd][p] + R_TU : 0;
-            s.p_j[nd] = ((unsigned long long)s.p_sse[nd] << 4) + (((unsigned long long)a.prm.lambda_q4 * (unsigned long long)bits) >> 4);
         });
     }
-    // the tree, bottom-up (wave 0): split = lambda + children, whole = own + lambda, whole wins ties; a node that does not fit is split
+    ex.phase([&](int tid) {
+        if (tid < cnt && s.p_valid[first + tid]) {
+            const int nd = first + tid, mode = (int)(s.p_key[nd] & 63);
+            int cmode = mode;
+            if (a.prm.chroma_modes) {
+                unsigned long long best = ~0ull;
+                for (int k = 0; k < 5; k++) {
+                    unsigned satd = 0;          // per tile (sum |H d H| + 2) >> 2 for 8x8 tiles, (sum + 1) >> 1 for the 4x4 blocks
+                    for (int p = 0; p < 2 * ntc; p++) { const unsigned r = s.p_craw[(tid * 5 + k) * 2 * ntc + p]; satd += tw == 8 ? (r + 2) >> 2 : (r + 1) >> 1; }
+                    const unsigned long long key = ((unsigned long long)((satd << 4) + (unsigned)(a.prm.lambda_sad_q4 * (k == 0 ? 1 : 3))) << 3) | (unsigned)k;
+                    best = key < best ? key : best;
+                }
+                const int k = (int)(best & 7), base = k == 1 ? 0 : k == 2 ? 26 : k == 3 ? 10 : 1;
+                if (k) cmode = base == mode ? 34 : base;
+            }
+            s.p_mode[nd] = (uint8_t)mode; s.p_cmode[nd] = (uint8_t)cmode;
+            s.p_sse[nd] = 0; s.p_bits[nd][0] = s.p_bits[nd][1] = s.p_bits[nd][2] = 0;
+        }
+        if (tid >= 64 && tid < 80) {
+            const int t = tid - 64;
+            s.rs.tu_log2[t] = s.p_valid[node_of_tile(level, t & 3, t >> 2)] ? (uint8_t)log2n : 0;
+            s.rs.tu_intra[t] = 1;
+        }
+        if (tid >= 96 && tid < 99) s.rs.cbf[tid - 96] = 0;
+    });
+}
+// RD cost of every node of the level with its modes: prediction (still from the source neighbourhood), K3 over the whole CTU,
+// distortion and rate per node
+template <typename T, class Ex> DEV void plan_level_cost(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int level)
+{
+    const int bd = a.prm.bit_depth, log2n = 5 - level, l2c = log2n - 1, cnt = 1 << (2 * level), first = level_first(level);
+    ex.phase([&](int tid) {
+        for (int i = tid; i < CTU_SAMPLES; i += NT) {
+            SampleLoc l = locate(s.rs, i);
+            s.rs.desc[i] = pack_loc(l);
+            if (!l.log2n) continue;
+            const int sh = l.plane ? 2 : 3, nd = node_of_tile(level, l.x >> sh, l.y >> sh);
+            int cx, cy, l2, v;
+            node_geom(nd, cx, cy, l2);
+            if (l.plane == 0) {
+                const int mode = s.p_mode[nd];
+                const T *L = intra_filter_on(log2n, mode) ? s.p_filt[nd] : s.p_ref[nd];
+                v = intra_sample<T>(L, log2n, mode, s.tab_angle[mode], s.tab_inv[mode], l.x - cx, l.y - cy, 0, bd, s.p_dc[nd][0]);
+            } else {
+                const int cm = s.p_cmode[nd];
+                v = intra_sample<T>(s.p_refc[nd][l.plane - 1], l2c, cm, s.tab_angle[cm], s.tab_inv[cm], l.x - (cx >> 1), l.y - (cy >> 1), l.plane, bd, s.p_dc[nd][l.plane]);
+            }
+            s.pred[i] = (T)v;
+            s.rs.res[i] = (int16_t)((int)s.src[i] - v);
+        }
+    });
+    residual_pipeline(ex, s.rs, a.prm.qp, a.prm.qp_c, bd, whole_ctu());      // no sign hiding: these levels are a cost estimate, intra_code_cu recodes every CU
+    ex.phase([&](int tid) {
+        const int maxv = (1 << bd) - 1;
+        for (int i = 4 * tid; i < CTU_SAMPLES; i += 4 * NT) {
+            SampleLoc l = locate(s.rs, i);
+            if (!l.log2n) continue;
+            const int sh = l.plane ? 2 : 3;
+            unsigned sse = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) { const int d = (int)s.src[i + j] - clip3(0, maxv, (int)s.pred[i + j] + s.rs.res[i + j]); sse += (unsigned)(d * d); }
+            if (sse) ex.atomic_add(&s.p_sse[node_of_tile(level, l.x >> sh, l.y >> sh)], sse);
+        }
+        for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {
+            const SubBlock b = sub_block(sb);
+            if (!s.rs.tu_log2[b.tile]) continue;
+            const int bits = subblock_bits_q4(s.rs.lvl + b.at, b.stride);
+            if (bits) ex.atomic_add(&s.p_bits[node_of_tile(level, b.tile & 3, b.tile >> 2)][b.plane], (unsigned)bits);
+        }
+    });
+    ex.phase([&](int tid) {
+        if (tid >= cnt) return;
+        const int nd = first + tid;
+        if (!s.p_valid[nd]) { s.p_j[nd] = 0; return; }
+        int cand[3];
+        plan_cand(s, nd, level, cand);
+        s.p_j[nd] = intra_cu_cost(a.prm.lambda_q4, cand, s.p_mode[nd], s.p_cmode[nd], s.p_bits[nd], s.p_sse[nd]);
+    });
+}
+// the tree, bottom-up (wave 0): split = lambda + children, whole = own + lambda, whole wins ties; a node that does not fit is split
+template <typename T, class Ex> DEV void plan_tree(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int ctu_x, int ctu_y)
+{
     const unsigned long long lam_split = (unsigned long long)a.prm.lambda_q4;     // (lambda_q4 * 16) >> 4
     ex.wave_step([&](int tid) {
         if (tid >= 4) return;
@@ -627,6 +652,19 @@ DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
         }
     });
 }
+template <typename T, class Ex>
+DEV void intra_plan_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int ctu_x, int ctu_y)
+{
+    const int x0 = ctu_x * CTU, y0 = ctu_y * CTU;
+    plan_load(ex, s, a, x0, y0);
+    plan_refs(ex, s, a, x0, y0, tile_box(a, ctu_x, ctu_y));
+    plan_rank_luma(ex, s, a);
+    for (int level = 0; level < 3; level++) {
+        plan_rank_chroma(ex, s, a, level);
+        plan_level_cost(ex, s, a, level);
+    }
+    plan_tree(ex, s, a, ctu_x, ctu_y);
+}
 
 // ------------------------------------------------------------------------------------------ stage B: coding the planned CUs
 // one planned 2Nx2N CU (oracle intra_cu): reference samples from the reconstruction, prediction with the planned modes, K3, reconstruction
@@ -637,17 +675,16 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
     const int n = 1 << log2n, bd = a.prm.bit_depth;
     const Region rg{cx, cy, log2n};
     const int rcnt = rg.count();
-    const int gx = x0 + cx, gy = y0 + cy;        // picture coordinates of the CU
     ex.phase([&](int tid) {      // reference samples: availability + raw values for the three planes
         for (int u = tid; u < 3 * 129; u += NT) {
             const int pl = u / 129, i = u % 129, np = pl ? n >> 1 : n;
             if (i >= 4 * np + 1) continue;
             int xn, yn;
-            ref_pos(pl ? cx >> 1 : cx, pl ? cy >> 1 : cy, np, i, xn, yn);
-            const int sh = pl ? 1 : 0, lx = xn * (1 << sh) + x0, ly = yn * (1 << sh) + y0;      // luma picture position of the neighbour
-            const bool ok = lx >= tb.x_lo && ly >= tb.y_lo && lx < a.w && lx < tb.x_hi && ly < a.h && zaddr(lx, ly, a.ctus_w) < zaddr(gx, gy, a.ctus_w);
+            ref_pos(to_plane(pl, cx), to_plane(pl, cy), np, i, xn, yn);
+            const int sh = pl ? 1 : 0;
+            const bool ok = ref_available(a, tb, xn * (1 << sh) + x0, yn * (1 << sh) + y0, zaddr(x0 + cx, y0 + cy, a.ctus_w));
             if (ok) ex.atomic_or(&s.avmask[pl][i >> 5], 1u << (i & 31));
-            s.ref_raw[pl][i] = ok ? (pl ? s.rec_c[pl - 1][(yn + 1) * RC_STRIDE + xn + 1] : s.rec_y[(yn + 1) * RY_STRIDE + xn + 1]) : (T)0;
+            s.ref_raw[pl][i] = ok ? nb(s, pl, xn, yn) : (T)0;
         }
         if (tid == 0) {   // 8.4.2 candModeList from the CUs actually coded around this one (rate estimate only)
             int cand[3];
@@ -665,26 +702,8 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
         }
     });
     ex.phase([&](int tid) {      // smoothing filter for luma (8.4.4.2.3) + DC values + the CU's transform units
-        const T *L = s.ref[0];
-        const int total = 4 * n + 1;
-        bool strong = false;
-        if (n == 32) {
-            int thr = 1 << (bd - 5), c = L[64];
-            strong = iabs(c + L[128] - 2 * L[96]) < thr && iabs(c + L[0] - 2 * L[32]) < thr;
-        }
-        for (int i = tid; i < total; i += NT) {
-            int v;
-            if (i == 0 || i == total - 1) v = L[i];
-            else if (strong) v = i == 64 ? L[64] : i < 64 ? (i * L[64] + (64 - i) * L[0] + 32) >> 6 : ((128 - i) * L[64] + (i - 64) * L[128] + 32) >> 6;
-            else v = (L[i - 1] + 2 * L[i] + L[i + 1] + 2) >> 2;
-            s.filt[i] = (T)v;
-        }
-        if (tid >= 192 && tid < 195) {
-            const int pl = tid - 192, np = pl ? n >> 1 : n, lg = pl ? log2n - 1 : log2n;
-            int sum = np;
-            for (int i = 0; i < np; i++) sum += ref_top(s.ref[pl], np, i) + ref_left(s.ref[pl], np, i);
-            s.dc_val[pl] = sum >> (lg + 1);
-        }
+        for (int i = tid; i < 4 * n + 1; i += NT) s.filt[i] = (T)smooth_ref(s.ref[0], n, i, bd);
+        if (tid >= 192 && tid < 195) s.dc_val[tid - 192] = dc_of(s.ref[tid - 192], tid == 192 ? log2n : log2n - 1);
         if (tid >= 208 && tid < 224) {
             int t = tid - 208, tx = t & 3, ty = t >> 2;
             bool in = tx * 8 >= cx && tx * 8 < cx + n && ty * 8 >= cy && ty * 8 < cy + n;
@@ -719,38 +738,32 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
             SampleLoc l = locate(s.rs, i);
             if (!l.log2n) continue;
             int v = clip3(0, maxv, (int)s.pred[i] + s.rs.res[i]);
-            if (l.plane == 0) s.rec_y[(l.y + 1) * RY_STRIDE + l.x + 1] = (T)v;
-            else s.rec_c[l.plane - 1][(l.y + 1) * RC_STRIDE + l.x + 1] = (T)v;
+            nb(s, l.plane, l.x, l.y) = (T)v;
             int d = (int)s.src[i] - v;
             sse += (unsigned)(d * d);
             s.coef_acc[i] = s.rs.lvl[i];
         }
         if (sse) ex.atomic_add(&s.sse, sse);
-        for (int sb = tid; sb < 96; sb += NT) {       // 64 luma + 16 + 16 chroma 4x4 sub-blocks
-            int pl = sb < 64 ? 0 : 1 + ((sb - 64) >> 4), k = sb < 64 ? sb : (sb - 64) & 15;
-            int per = pl ? 4 : 8, bx = (k & (per - 1)) * 4, by = (k >> (pl ? 2 : 3)) * 4, stride = pl ? 16 : 32, base = pl ? 1024 + (pl - 1) * 256 : 0;
-            int sh = pl ? 2 : 3;
-            if (!s.rs.tu_log2[(by >> sh) * 4 + (bx >> sh)]) continue;
-            int b = subblock_bits_q4(s.rs.lvl + base + by * stride + bx, stride);
-            if (b) ex.atomic_add(&s.bits[pl], b);
+        for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {
+            const SubBlock b = sub_block(sb);
+            if (!s.rs.tu_log2[b.tile]) continue;
+            const int bits = subblock_bits_q4(s.rs.lvl + b.at, b.stride);
+            if (bits) ex.atomic_add(&s.bits[b.plane], bits);
         }
     });
     ex.phase([&](int tid) {
         int t0 = (cy >> 3) * 4 + (cx >> 3);
         if (tid < 16 && s.rs.tu_log2[tid]) {
-            mihevc_cu_rec r;
+            mihevc_cu_rec r{};      // vectors, cbf_y4 and padding zero
             r.log2_size = (uint8_t)log2n;
-            r.flags = (uint8_t)(((s.rs.cbf[0] >> t0) & 1 ? CU_CBF_Y : 0) | ((s.rs.cbf[1] >> t0) & 1 ? CU_CBF_CB : 0) | ((s.rs.cbf[2] >> t0) & 1 ? CU_CBF_CR : 0));
+            r.flags = (uint8_t)cbf_flags(s.rs.cbf, t0);
             r.chroma_mode = (uint8_t)cmode; r.qp = (uint8_t)a.prm.qp;
             r.intra_mode[0] = r.intra_mode[1] = r.intra_mode[2] = r.intra_mode[3] = (uint8_t)mode;
-            r.mvx = r.mvy = 0; r.cbf_y4 = 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
             s.cu_acc[tid] = r;
         }
         if (tid >= 64 && tid < 79) s.avmask[(tid - 64) / 5][(tid - 64) % 5] = 0;      // for the next CU's reference samples
         if (tid == 0) {
-            int bits = 16 * mode_bits_for(s.cand, mode) + 16 + 24 + (cmode != mode ? 32 : 0);
-            for (int p = 0; p < 3; p++) bits += s.bits[p] ? s.bits[p] + R_TU : 0;
-            s.j_cu = ((unsigned long long)s.sse << 4) + (((unsigned long long)a.prm.lambda_q4 * (unsigned long long)bits) >> 4);
+            s.j_cu = intra_cu_cost(a.prm.lambda_q4, s.cand, mode, cmode, s.bits, s.sse);
             s.nx_try = (int)((s.rs.cbf[0] >> t0) & 1);
         }
     });
@@ -764,24 +777,19 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
 // the modes by 4x4-Hadamard SATD, 16 lanes (one per sample) predict, transform (DST-VII luma / DCT chroma), quantise and
 // reconstruct on the 4x4 core of residual.h (oracle code_tu).
 template <typename T, class Ex>
-DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, int y0, int cx, int cy)
+DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, int y0, const TileBox &tb, int cx, int cy)
 {
-    const int ctu_x = x0 >> CTU_LOG2, ctu_y = y0 >> CTU_LOG2, bd = a.prm.bit_depth, maxv = (1 << bd) - 1;
-    const int tcn = a.prm.tile_cols > 1 ? a.prm.tile_cols : 1, trn = a.prm.tile_rows > 1 ? a.prm.tile_rows : 1;
-    const int tci = tile_of(ctu_x, tcn, a.ctus_w), tri = tile_of(ctu_y, trn, a.ctus_h);
-    const int tx_lo = tile_bd(tci, tcn, a.ctus_w) << CTU_LOG2, tx_hi = tile_bd(tci + 1, tcn, a.ctus_w) << CTU_LOG2;
-    const int ty_lo = tile_bd(tri, trn, a.ctus_h) << CTU_LOG2;
+    const int bd = a.prm.bit_depth, maxv = (1 << bd) - 1;
     const int tile = (cy >> 3) * 4 + (cx >> 3);
     Nx4<T> &w = s.nx;
     // the trial of CU column c runs on wave c: wave 0 of every workgroup tends to share one SIMD, and a serial chain pinned to
     // it left the other three SIMDs of the CU idle
     const int wbase = ((cx >> 3) & 3) * 64;
     ex.phase([&](int tid) {
-        if (tid < 96) {
-            int pl, x, y;
-            if (tid < 64) { pl = 0; x = cx + (tid & 7); y = cy + (tid >> 3); } else { int k = tid - 64; pl = 1 + (k >> 4); k &= 15; x = (cx >> 1) + (k & 3); y = (cy >> 1) + (k >> 2); }
-            s.nx_rec[tid] = pl ? s.rec_c[pl - 1][(y + 1) * RC_STRIDE + x + 1] : s.rec_y[(y + 1) * RY_STRIDE + x + 1];
-            s.nx_coef[tid] = s.coef_acc[(pl ? 1024 + (pl - 1) * 256 + y * 16 : y * 32) + x];
+        if (tid < CU8_SAMPLES) {
+            const CtuSample c = cu8_sample(cx, cy, tid);
+            s.nx_rec[tid] = nb(s, c.plane, c.x, c.y);
+            s.nx_coef[tid] = s.coef_acc[ctu_index(c.plane, c.x, c.y)];
         }
         if (tid == 0) {
             s.nx_cu = s.cu_acc[tile];
@@ -795,8 +803,8 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             w.av[0] = w.av[1] = 0; w.blk[0].nz = w.blk[1].nz = 0;
         }
     });
-    // one pass codes `nb` 4x4 blocks of the same kind side by side (lane group g = lane / 32): a luma PU (nb = 1) or Cb + Cr (nb = 2)
-    auto code_blocks = [&](int nb, int pl0, int bx, int by, int k) {
+    // one pass codes `nblk` 4x4 blocks of the same kind side by side (lane group g = lane / 32): a luma PU (nblk = 1) or Cb + Cr (nblk = 2)
+    auto code_blocks = [&](int nblk, int pl0, int bx, int by, int k) {
         const bool luma = pl0 == 0;
         const int sh = luma ? 0 : 1;
         const Quantiser qz(luma ? a.prm.qp : a.prm.qp_c, bd, 2, 1, s.tab_qs, s.tab_ls);
@@ -807,16 +815,15 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
         auto block_step = [&](int lanes, auto &&f) {
             ex.wave_step([&](int tid0) {
                 const int tid = tid0 - wbase, g = tid >> 5, i = tid & 31;
-                if (tid >= 0 && tid < 64 && g < nb && i < lanes) f(g, i);
+                if (tid >= 0 && tid < 64 && g < nblk && i < lanes) f(g, i);
             });
         };
         block_step(17, [&](int g, int i) {          // reference samples: availability (6.4.1 incl. tiles) + raw values
             const int pl = pl0 + g;
             int xn, yn;
-            if (i < 8) { xn = bx - 1; yn = by + 7 - i; } else if (i == 8) { xn = bx - 1; yn = by - 1; } else { xn = bx + i - 9; yn = by - 1; }
-            const int lx = x0 + xn * (1 << sh), ly = y0 + yn * (1 << sh);
-            const bool ok = lx >= tx_lo && ly >= ty_lo && lx < a.w && lx < tx_hi && ly < a.h && zaddr(lx, ly, a.ctus_w) < zc;
-            w.ref_raw[g][i] = ok ? (pl ? s.rec_c[pl - 1][(yn + 1) * RC_STRIDE + xn + 1] : s.rec_y[(yn + 1) * RY_STRIDE + xn + 1]) : (T)0;
+            ref_pos(bx, by, 4, i, xn, yn);
+            const bool ok = ref_available(a, tb, x0 + xn * (1 << sh), y0 + yn * (1 << sh), zc);
+            w.ref_raw[g][i] = ok ? nb(s, pl, xn, yn) : (T)0;
             if (ok) ex.atomic_or(&w.av[g], 1u << i);
         });
         block_step(17, [&](int g, int i) {          // substitution 8.4.4.2.2: nearest available below, else the first available
@@ -828,13 +835,11 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             if (tid < 0 || tid >= 64) return;   // 35 modes ranked by SATD + MPM-aware mode bits
             if (tid >= 35) return;
             const T *ref = w.ref[0];
-            int cand[3], m[16], sum = 4;
-            mpm_cand(s, bx, by, x0 > tx_lo, cand);
+            int cand[3], m[16];
+            mpm_cand(s, bx, by, x0 > tb.x_lo, cand);
+            const int ang = s.tab_angle[tid], inv = s.tab_inv[tid], dc = dc_of(ref, 2);
 #pragma unroll
-            for (int i = 0; i < 4; i++) sum += ref_top(ref, 4, i) + ref_left(ref, 4, i);
-            const int ang = s.tab_angle[tid], inv = s.tab_inv[tid], dc = sum >> 3;
-#pragma unroll
-            for (int i = 0; i < 16; i++) m[i] = (int)s.src[(by + (i >> 2)) * 32 + bx + (i & 3)] - intra_sample<T>(ref, 2, tid, ang, inv, i & 3, i >> 2, 0, bd, dc);
+            for (int i = 0; i < 16; i++) m[i] = (int)s.src[ctu_index(0, bx + (i & 3), by + (i >> 2))] - intra_sample<T>(ref, 2, tid, ang, inv, i & 3, i >> 2, 0, bd, dc);
 #pragma unroll
             for (int y = 0; y < 4; y++) {
                 int p0 = m[y * 4] + m[y * 4 + 1], p1 = m[y * 4] - m[y * 4 + 1], p2 = m[y * 4 + 2] + m[y * 4 + 3], p3 = m[y * 4 + 2] - m[y * 4 + 3];
@@ -846,19 +851,15 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
                 int p0 = m[x] + m[4 + x], p1 = m[x] - m[4 + x], p2 = m[8 + x] + m[12 + x], p3 = m[8 + x] - m[12 + x];
                 sat += iabs(p0 + p2) + iabs(p1 + p3) + iabs(p0 - p2) + iabs(p1 - p3);
             }
-            const int bits = tid == cand[0] ? 2 : (tid == cand[1] || tid == cand[2]) ? 3 : 6;
-            const unsigned cost = ((unsigned)((sat + 1) >> 1) << 4) + (unsigned)(a.prm.lambda_sad_q4 * bits);
+            const unsigned cost = ((unsigned)((sat + 1) >> 1) << 4) + (unsigned)(a.prm.lambda_sad_q4 * mode_bits_for(cand, tid));
             ex.atomic_min(&s.mode_key, ((unsigned long long)cost << 6) | (unsigned)tid);
         });
         block_step(16, [&](int g, int i) {          // prediction + residual, one lane per sample
             const int pl = pl0 + g, mode = luma ? (int)(s.mode_key & 63) : (int)s.cu_acc[tile].intra_mode[0];
             const T *ref = w.ref[g];
-            int sum = 4;
-#pragma unroll
-            for (int j = 0; j < 4; j++) sum += ref_top(ref, 4, j) + ref_left(ref, 4, j);
             const int x = i & 3, y = i >> 2;
-            const int v = intra_sample<T>(ref, 2, mode, s.tab_angle[mode], s.tab_inv[mode], x, y, pl, bd, sum >> 3);
-            const int sidx = luma ? (by + y) * 32 + bx + x : 1024 + (pl - 1) * 256 + (by + y) * 16 + bx + x;
+            const int v = intra_sample<T>(ref, 2, mode, s.tab_angle[mode], s.tab_inv[mode], x, y, pl, bd, dc_of(ref, 2));
+            const int sidx = ctu_index(pl, bx + x, by + y);
             w.pred[g][i] = (int16_t)v;
             w.blk[g].res[i] = (int16_t)((int)s.src[sidx] - v);
         });
@@ -874,8 +875,8 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
             const int pl = pl0 + g, x = i & 3, y = i >> 2, nz = (int)w.blk[g].nz;
             const int r = core4_inv_rows(M, w.blk[g], i, bd);
             const int v = clip3(0, maxv, (int)w.pred[g][i] + r);
-            const int sidx = luma ? (by + y) * 32 + bx + x : 1024 + (pl - 1) * 256 + (by + y) * 16 + bx + x;
-            if (luma) s.rec_y[(by + y + 1) * RY_STRIDE + bx + x + 1] = (T)v; else s.rec_c[pl - 1][(by + y + 1) * RC_STRIDE + bx + x + 1] = (T)v;
+            const int sidx = ctu_index(pl, bx + x, by + y);
+            nb(s, pl, bx + x, by + y) = (T)v;
             s.coef_acc[sidx] = w.blk[g].lvl[i];
             const int d = (int)s.src[sidx] - v, al = iabs((int)w.blk[g].lvl[i]);
             int bits = al ? rate_level(al) : 0;
@@ -884,8 +885,8 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
                 if (luma) {
                     const int mode = (int)(s.mode_key & 63);
                     int cand[3];
-                    mpm_cand(s, bx, by, x0 > tx_lo, cand);
-                    bits += 16 * (mode == cand[0] ? 2 : (mode == cand[1] || mode == cand[2]) ? 3 : 6);
+                    mpm_cand(s, bx, by, x0 > tb.x_lo, cand);
+                    bits += 16 * mode_bits_for(cand, mode);
                     s.cu_acc[tile].intra_mode[k] = (uint8_t)mode;
                     if (k == 0) s.cu_acc[tile].chroma_mode = (uint8_t)mode;
                     if (nz) { s.cu_acc[tile].cbf_y4 |= (uint8_t)(1 << k); s.cu_acc[tile].flags |= CU_CBF_Y; }
@@ -914,11 +915,10 @@ DEV void intra_cu_nxn(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0, 
     });
     ex.phase([&](int tid) {
         if (s.nx_keep) return;
-        if (tid < 96) {
-            int pl, x, y;
-            if (tid < 64) { pl = 0; x = cx + (tid & 7); y = cy + (tid >> 3); } else { int k = tid - 64; pl = 1 + (k >> 4); k &= 15; x = (cx >> 1) + (k & 3); y = (cy >> 1) + (k >> 2); }
-            if (pl) s.rec_c[pl - 1][(y + 1) * RC_STRIDE + x + 1] = s.nx_rec[tid]; else s.rec_y[(y + 1) * RY_STRIDE + x + 1] = s.nx_rec[tid];
-            s.coef_acc[(pl ? 1024 + (pl - 1) * 256 + y * 16 : y * 32) + x] = s.nx_coef[tid];
+        if (tid < CU8_SAMPLES) {
+            const CtuSample c = cu8_sample(cx, cy, tid);
+            nb(s, c.plane, c.x, c.y) = s.nx_rec[tid];
+            s.coef_acc[ctu_index(c.plane, c.x, c.y)] = s.nx_coef[tid];
         }
         if (tid == 0) s.cu_acc[tile] = s.nx_cu;
     });
@@ -937,30 +937,17 @@ DEV void intra_code_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
     ex.phase([&](int tid) {
         if (fresh) {
             load_ctu_source<T>(s.src, a.src, x0, y0, a.w, a.h, tid);
-            if (tid >= 64 && tid < 99) { s.tab_angle[tid - 64] = (int16_t)mode_angle(tid - 64); s.tab_inv[tid - 64] = (int16_t)mode_inv_angle(tid - 64); }
-            if (tid >= 128 && tid < 134) { s.tab_qs[tid - 128] = g_tab.quant_scale[tid - 128]; s.tab_ls[tid - 128] = g_tab.level_scale[tid - 128]; }
-            if (tid < 32) s.nx_mat[tid >> 4][tid & 15] = tid < 16 ? g_tab.dst4[(tid >> 2) & 3][tid & 3] : g_tab.mat[((tid >> 2) & 3) * 8][tid & 3];
+            load_intra_tables(s, tid);
             if (tid >= 160 && tid < 181) {
                 const IntraPlan &p = a.plan[ctu_y * a.ctus_w + ctu_x];
                 s.plan.chosen[tid - 160] = p.chosen[tid - 160]; s.plan.mode[tid - 160] = p.mode[tid - 160]; s.plan.cmode[tid - 160] = p.cmode[tid - 160];
             }
         }
-        for (int i = tid; i < 1536; i += NT) s.coef_acc[i] = 0;
+        for (int i = tid; i < CTU_SAMPLES; i += NT) s.coef_acc[i] = 0;
         if (tid == 0) s.est = 0;
         if (tid >= 224 && tid < 239) s.avmask[(tid - 224) / 5][(tid - 224) % 5] = 0;
         if (tid < 4 && x0 > 0 && y0 + tid * 8 < a.h) s.left_cu[tid] = a.cu[(size_t)((y0 >> 3) + tid) * (a.w >> 3) + ((x0 - 1) >> 3)];
-        // neighbourhood: row -1 (cols -1..63 luma / -1..31 chroma) and column -1 (rows 0..31 / 0..15) from the picture
-        for (int u = tid; u < 65 + 32 + 2 * (33 + 16); u += NT) {
-            int pl, k, row_len;
-            if (u < 97) { pl = 0; k = u; row_len = 65; } else { pl = 1 + (u - 97) / 49; k = (u - 97) % 49; row_len = 33; }
-            int xn, yn;
-            if (k < row_len) { xn = k - 1; yn = -1; } else { xn = -1; yn = k - row_len; }
-            int pw = pl ? a.w >> 1 : a.w, ph = pl ? a.h >> 1 : a.h;
-            int gx = (pl ? x0 >> 1 : x0) + xn, gy = (pl ? y0 >> 1 : y0) + yn;
-            T v = 0;
-            if (gx >= 0 && gy >= 0 && gx < pw && gy < ph) v = a.rec[pl].p[(ptrdiff_t)gy * a.rec[pl].stride + gx];
-            if (pl == 0) s.rec_y[(yn + 1) * RY_STRIDE + xn + 1] = v; else s.rec_c[pl - 1][(yn + 1) * RC_STRIDE + xn + 1] = v;
-        }
+        load_ring(s, a.rec, x0, y0, a.w, a.h, tid);      // the neighbours' reconstruction
     });
     // Which CUs run is uniform over the workgroup: plan.chosen is written once (above, or by the plan stage behind a barrier) and never
     // again; j_cu / nx_try are words the CU's last phase writes and nobody rewrites before the next CU's last phase.
@@ -973,7 +960,7 @@ DEV void intra_code_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
             const int bx = qx + (b & 1) * 8, by = qy + (b >> 1) * 8;
             any = true;
             intra_code_cu(ex, s, a, x0, y0, tb, bx, by, 3, s.plan.mode[5 + 4 * q + b], s.plan.cmode[5 + 4 * q + b]);
-            if (a.prm.intra_nxn && s.nx_try) intra_cu_nxn(ex, s, a, x0, y0, bx, by);
+            if (a.prm.intra_nxn && s.nx_try) intra_cu_nxn(ex, s, a, x0, y0, tb, bx, by);
             jctu += s.j_cu;
         }
         if (any) jctu += lam_split;
@@ -990,12 +977,12 @@ DEV void intra_code_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
     if (a.ip && jctu >= a.ip[ctu_y * a.ctus_w + ctu_x].jinter) return;
     // the CTU is final: reconstruction, levels and CU records to memory
     ex.phase([&](int tid) {
-        for (int i = 4 * tid; i < 1536; i += 4 * NT) {      // four samples of one row per lane, dword stores
-            int pl, x, y;
-            if (i < 1024) { pl = 0; x = i & 31; y = i >> 5; } else { int k = i - 1024; pl = 1 + (k >> 8); k &= 255; x = k & 15; y = k >> 4; }
-            int gx = (pl ? x0 >> 1 : x0) + x, gy = (pl ? y0 >> 1 : y0) + y, pw = pl ? a.w >> 1 : a.w, ph = pl ? a.h >> 1 : a.h;
+        for (int i = 4 * tid; i < CTU_SAMPLES; i += 4 * NT) {      // four samples of one row per lane, dword stores
+            const CtuSample c = ctu_sample(i);
+            const int pl = c.plane, x = c.x, y = c.y;
+            const int gx = to_plane(pl, x0) + x, gy = to_plane(pl, y0) + y, pw = to_plane(pl, a.w), ph = to_plane(pl, a.h);
             if (gx >= pw || gy >= ph) continue;            // widths are multiples of 4 in both planes: a quad is inside or outside
-            const T *r = pl ? &s.rec_c[pl - 1][(y + 1) * RC_STRIDE + x + 1] : &s.rec_y[(y + 1) * RY_STRIDE + x + 1];
+            const T *r = &nb(s, pl, x, y);
             store4(a.rec[pl].p + (ptrdiff_t)gy * a.rec[pl].stride + gx, r[0], r[1], r[2], r[3]);
             {
                 const int sh = pl ? 2 : 3, fl = s.cu_acc[(y >> sh) * 4 + (x >> sh)].flags;
@@ -1009,11 +996,10 @@ DEV void intra_code_program(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, in
         }
         if (a.est) {       // rate estimate of the final CTU: coefficient sub-block costs + 8 bits of header per CU
             unsigned e = 0;
-            for (int sb = tid; sb < 96; sb += NT) {
-                int pl = sb < 64 ? 0 : 1 + ((sb - 64) >> 4), k = sb < 64 ? sb : (sb - 64) & 15;
-                int per = pl ? 4 : 8, bx = (k & (per - 1)) * 4, by = (k >> (pl ? 2 : 3)) * 4, stride = pl ? 16 : 32, base = pl ? 1024 + (pl - 1) * 256 : 0;
-                int lx = pl ? bx * 2 : bx, ly = pl ? by * 2 : by;
-                if (x0 + lx < a.w && y0 + ly < a.h) e += (unsigned)subblock_bits_q4(s.coef_acc + base + by * stride + bx, stride);
+            for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {
+                const SubBlock b = sub_block(sb);
+                const int lx = b.plane ? b.bx * 2 : b.bx, ly = b.plane ? b.by * 2 : b.by;
+                if (x0 + lx < a.w && y0 + ly < a.h) e += (unsigned)subblock_bits_q4(s.coef_acc + b.at, b.stride);
             }
             if (tid < 16) {
                 int tx = (tid & 3) * 8, ty = (tid >> 2) * 8;

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "ctu_image.h"
 
 namespace mihevc {
 
@@ -273,7 +274,7 @@ template <typename T, class Ex> DEV void sao_ctu_program(Ex &ex, SaoShared<T> &s
             for (int j = 0; j < N + 2; j++) { up[j] = tp[ti - ts + j]; mid[j] = tp[ti + j]; dn[j] = tp[ti + ts + j]; }
 #pragma unroll
             for (int j = 0; j < N + 1; j++) h[j] = sgn3(mid[j + 1] - mid[j]);
-            const T *sp = s.src + (pl ? 1024 + ((pl - 1) << 8) + y * 16 + x : y * 32 + x);
+            const T *sp = s.src + ctu_index(pl, x, y);
             unsigned *pv = s.priv[pl][tid & 15];
             const bool yin = (gy > 0 || a.halo_top > 0) && (gy < ph - 1 || a.halo_bottom > 0);
 #pragma unroll
@@ -394,7 +395,7 @@ template <typename T, class Ex> DEV void sao_ctu_program(Ex &ex, SaoShared<T> &s
             if (N == 4) store4(dst, v[0], v[1], v[2], v[3]);
             else { dst[0] = (T)v[0]; dst[1] = (T)v[1]; }
             if (a.sse_ctu) {          // squared error of the strip into the lane's private copy (word 52 of a copy is the spare one, zero since phase 1)
-                const T *sp = s.src + (pl ? 1024 + ((pl - 1) << 8) + y * 16 + x : y * 32 + x);
+                const T *sp = s.src + ctu_index(pl, x, y);
                 unsigned e = 0;
 #pragma unroll
                 for (int i = 0; i < N; i++) { const int d = (int)sp[i] - v[i]; e += (unsigned)(d * d); }
@@ -425,13 +426,6 @@ template <typename T> DEV int sao_sample_value(const SaoArgs<T> &a, const mihevc
         if (k < 4) v = clip3(0, maxv, v + o.offset[pl][k]);
     }
     return v;
-}
-// one thread per sample of a plane-row segment; also usable with sao == nullptr (plain copy)
-template <typename T> DEV void sao_apply_sample(const SaoArgs<T> &a, int pl, int gx, int gy)
-{
-    int v = a.dbk[pl].p[(ptrdiff_t)gy * a.dbk[pl].stride + gx];
-    if (a.sao) v = sao_sample_value<T>(a, a.sao[(gy >> (pl ? 4 : 5)) * a.ctus_w + (gx >> (pl ? 4 : 5))], pl, gx, gy, v);
-    a.out[pl].p[(ptrdiff_t)gy * a.out[pl].stride + gx] = (T)v;
 }
 // one thread per four samples of a row (gx a multiple of 4: the quad lies in one CTU; plane widths are multiples of 4): one load and one
 // store per quad, the CTU's parameters fetched once, and CTUs without SAO are a plain copy

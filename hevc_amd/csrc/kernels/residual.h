@@ -1,7 +1,7 @@
 // hevc_amd/csrc/kernels/residual.h — K3: forward transform, quantisation, scaling, inverse transform and
 // reconstruction of all transform units of one CTU, executed by the CTU's workgroup on its LDS image.
 //
-// Index space: 1536 samples per CTU = 1024 luma (32x32) + 256 Cb (16x16) + 256 Cr.  The TU a sample belongs to is
+// Index space: the CTU image of ctu_image.h (1536 samples: luma, Cb, Cr).  The TU a sample belongs to is
 // looked up in `tu_log2[16]` (CU size per 8x8 luma tile, 0 = no TU there); chroma TUs are the co-located half-size
 // blocks.  Arithmetic: H.265 8.6.2-8.6.4 (scaling, transformation) for the decoder side; the conventional
 // two-stage integer forward transform and dead-zone quantiser for the encoder side — identical, term for term, to
@@ -9,6 +9,7 @@
 // Roofline note: 4 matrix passes of <=32 MACs per sample; the working set never leaves LDS (12 KiB per CTU).
 #pragma once
 #include "common.h"
+#include "ctu_image.h"
 
 namespace mihevc {
 
@@ -37,13 +38,11 @@ struct ResidualShared {
     int quant_scale[6], level_scale[6];   // LDS copies: no global-memory read on the per-sample path
 };
 
-struct SampleLoc {
-    int plane, x, y;           // coordinates inside the CTU's plane (luma 0..31, chroma 0..15)
+struct SampleLoc : CtuSample {      // where the sample is in the CTU image, and the TU that holds it
     int log2n, tx0, ty0;       // TU geometry in the same coordinates; log2n == 0: not covered
     int tile0;                 // 8x8 tile index of the TU origin (for the cbf word)
     int intra;
     int scan;                  // scanIdx of the TU (7.4.9.11): 0 diagonal, 1 horizontal, 2 vertical; locate() leaves it 0, intra callers set it
-    int stride, base;          // row stride and base offset of the plane inside the 1536-sample arrays
 };
 
 // A square luma region of the CTU (cx, cy, size 2^log2n) plus its two co-located chroma blocks: 1.5 n^2 samples.
@@ -51,31 +50,24 @@ struct SampleLoc {
 struct Region {
     int cx, cy, log2n;
     DEV int count() const { return (1 << (2 * log2n)) + (1 << (2 * log2n - 1)); }
-    DEV int index(int k) const      // k-th sample of the region -> index into the 1536-sample CTU arrays
+    // k-th block of (1 << lh) rows x (1 << lw) columns of the region (luma first, then Cb, Cr) -> index of its top-left sample in the CTU image
+    DEV int at(int k, int lw, int lh) const
     {
-        const int n2 = 1 << (2 * log2n);
-        if (k < n2) return (cy + (k >> log2n)) * 32 + cx + (k & ((1 << log2n) - 1));
-        k -= n2;
-        const int q = n2 >> 2, pl = k >= q, kk = pl ? k - q : k, l2 = log2n - 1;
-        return 1024 + pl * 256 + ((cy >> 1) + (kk >> l2)) * 16 + (cx >> 1) + (kk & ((1 << l2) - 1));
-    }
-    // k-th block of 2 rows x 4 columns (count() / 8 of them: luma first, then Cb, Cr) -> index of its top-left sample
-    DEV int block_index(int k) const
-    {
-        const int nb = 1 << (2 * log2n - 3);             // luma blocks: (n / 2) x (n / 4)
-        if (k < nb) { const int per = 1 << (log2n - 2); return (cy + 2 * (k >> (log2n - 2))) * 32 + cx + 4 * (k & (per - 1)); }
+        const int nb = 1 << (2 * log2n - lw - lh);             // luma blocks
+        if (k < nb) { const int per = log2n - lw; return ctu_index(0, cx + ((k & ((1 << per) - 1)) << lw), cy + ((k >> per) << lh)); }
         k -= nb;
-        const int q = nb >> 2, pl = k >= q, kk = pl ? k - q : k, l2 = log2n - 3;      // chroma plane: (n / 4) x (n / 8) blocks
-        return 1024 + pl * 256 + ((cy >> 1) + 2 * (kk >> l2)) * 16 + (cx >> 1) + 4 * (kk & ((1 << l2) - 1));
+        const int q = nb >> 2, pl = k >= q, kk = pl ? k - q : k, per = log2n - 1 - lw;
+        return ctu_index(1 + pl, (cx >> 1) + ((kk & ((1 << per) - 1)) << lw), (cy >> 1) + ((kk >> per) << lh));
     }
+    DEV int index(int k) const { return at(k, 0, 0); }              // k-th sample of count()
+    DEV int block_index(int k) const { return at(k, 2, 1); }        // k-th block of 2 rows x 4 columns, count() / 8 of them
 };
 DEV Region whole_ctu() { return Region{0, 0, 5}; }
 
 DEV SampleLoc locate(const ResidualShared &s, int idx)
 {
     SampleLoc l;
-    if (idx < 1024) { l.plane = 0; l.x = idx & 31; l.y = idx >> 5; l.stride = 32; l.base = 0; }
-    else { int i = idx - 1024; l.plane = 1 + (i >> 8); i &= 255; l.x = i & 15; l.y = i >> 4; l.stride = 16; l.base = 1024 + (l.plane - 1) * 256; }
+    static_cast<CtuSample &>(l) = ctu_sample(idx);
     int sh = l.plane ? 2 : 3;                       // samples per tile edge: 8 luma, 4 chroma
     int tile = (l.y >> sh) * 4 + (l.x >> sh);
     int lg = s.tu_log2[tile];
@@ -94,8 +86,7 @@ DEV uint32_t pack_loc(const SampleLoc &l) { return (uint32_t)l.log2n | (uint32_t
 DEV SampleLoc unpack_loc(uint32_t d, int idx)
 {
     SampleLoc l;
-    if (idx < 1024) { l.plane = 0; l.x = idx & 31; l.y = idx >> 5; l.stride = 32; l.base = 0; }
-    else { int i = idx - 1024; l.plane = 1 + (i >> 8); i &= 255; l.x = i & 15; l.y = i >> 4; l.stride = 16; l.base = 1024 + (l.plane - 1) * 256; }
+    static_cast<CtuSample &>(l) = ctu_sample(idx);
     l.log2n = (int)(d & 7); l.tx0 = (int)(d >> 3) & 31; l.ty0 = (int)(d >> 8) & 31; l.tile0 = (int)(d >> 13) & 15; l.intra = (int)(d >> 17) & 1; l.scan = (int)(d >> 18) & 3;
     return l;
 }
@@ -264,18 +255,22 @@ DEV int core4_inv_rows(const int16_t *M, const Block4 &b, int i, int bit_depth) 
 template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp, int qp_c, int bit_depth, Region rg, int cg_lam_q4 = 0, int sign_hide = 0)
 {
     const int nblk = rg.count() >> 3;
+    constexpr int kZero[2][4] = {};
     long long *cg_d = s.cg.d;
     int *cg_b = s.cg.b;
     // row stages (forward 1, inverse 2): out(y, u) = sum_p M-pair(p, u) . in(y, 2p..2p+1); column stages (forward 2, inverse 1):
-    // out(v, x) = sum_p M-pair(p, v) . in-row-pair(p, x), the row pairs of `tmp` being single dwords
+    // out(v, x) = sum_p M-pair(p, v) . in-row-pair(p, x), the row pairs of `tmp` being single dwords.  Both add to the caller's zeroed `acc`;
+    // round8 then rounds, shifts and clips the block's eight sums
+    auto round8 = [](int (&v)[2][4], auto &&f) {
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[j][i] = f(v[j][i]);
+    };
     auto row_stage = [&](const uint32_t *mat, const int16_t *in, const SampleLoc &l, int (&acc)[2][4]) {
         const int n = 1 << l.log2n, u4 = l.x - l.tx0;
         const uint32_t *m = mat + pair_off(l.log2n) + u4;
         const int16_t *r0 = in + l.base + l.y * l.stride + l.tx0, *r1 = r0 + l.stride;
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) acc[j][i] = 0;
         if (n == 4) {
             uint32_t d0[2], d1[2];
             load_x2(r0, d0); load_x2(r1, d1);
@@ -304,10 +299,6 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
         const int n = 1 << l.log2n, v2 = l.y - l.ty0;
         const uint32_t *m = mat + pair_off(l.log2n) + v2;
         const int16_t *t = s.tmp + l.base + l.ty0 * l.stride + 2 * l.x;
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) acc[j][i] = 0;
 #pragma unroll 4
         for (int p = 0; p < n / 2; p++) {
             uint32_t d[4], mm[2];
@@ -337,12 +328,9 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
             SampleLoc l = unpack_loc(s.desc[idx], idx);
             if (!l.log2n) continue;
             const int sh1 = l.log2n + bit_depth - 9;
-            int acc[2][4];
+            int acc[2][4] = {};
             row_stage(s.mp, s.res, l, acc);
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[j][i] = sh1 > 0 ? (acc[j][i] + (1 << (sh1 - 1))) >> sh1 : acc[j][i];
+            round8(acc, [&](int v) { return sh1 > 0 ? (v + (1 << (sh1 - 1))) >> sh1 : v; });
             store_pairs(l, acc);
         }
     });
@@ -352,12 +340,9 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
             SampleLoc l = unpack_loc(s.desc[idx], idx);
             if (!l.log2n) continue;
             const int sh2 = l.log2n + 6;
-            int acc[2][4];
+            int acc[2][4] = {};
             col_stage(s.mp, l, acc);
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[j][i] = clip3(-32768, 32767, (acc[j][i] + (1 << (sh2 - 1))) >> sh2);
+            round8(acc, [&](int v) { return clip3(-32768, 32767, (v + (1 << (sh2 - 1))) >> sh2); });
             store_rows(s.coef, l, acc);
         }
     });
@@ -366,14 +351,7 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
             const int idx = rg.block_index(k);
             SampleLoc l = unpack_loc(s.desc[idx], idx);
             int lev[2][4], deq[2][4];
-            if (!l.log2n) {
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) lev[j][i] = 0;
-                store_rows(s.lvl, l, lev);
-                continue;
-            }
+            if (!l.log2n) { store_rows(s.lvl, l, kZero); continue; }
             const Quantiser qz(l.plane ? qp_c : qp, bit_depth, l.log2n, l.intra, s.quant_scale, s.level_scale);
             const bool cg = cg_lam_q4 > 0 && !l.intra;
             int any = 0, bits = 0;
@@ -408,9 +386,8 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
             const long long d = cg_d[k] + cg_d[mate];
             const int bits = cg_b[k] + cg_b[mate] + R_SB, tsh = 2 * (15 - bit_depth - l.log2n);
             if (16 * d < ((((long long)cg_lam_q4 * bits) >> 4) << tsh)) {
-                const int zero[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-                store_rows(s.lvl, l, zero);
-                store_pairs(l, zero);
+                store_rows(s.lvl, l, kZero);
+                store_pairs(l, kZero);
             } else ex.atomic_or(&s.cbf[l.plane], 1u << l.tile0);
         }
     });
@@ -445,12 +422,9 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
             const int idx = rg.block_index(k);
             SampleLoc l = unpack_loc(s.desc[idx], idx);
             if (!l.log2n || !((s.cbf[l.plane] >> l.tile0) & 1)) continue;     // a TU without levels reconstructs to zero: nothing to invert
-            int acc[2][4];
+            int acc[2][4] = {};
             col_stage(s.mq, l, acc);
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[j][i] = clip3(-32768, 32767, (acc[j][i] + 64) >> 7);
+            round8(acc, [](int v) { return clip3(-32768, 32767, (v + 64) >> 7); });
             store_rows(s.coef, l, acc);
         }
     });
@@ -458,21 +432,11 @@ template <class Ex> DEV void residual_pipeline(Ex &ex, ResidualShared &s, int qp
         for (int k = tid; k < nblk; k += NT) {
             const int idx = rg.block_index(k);
             SampleLoc l = unpack_loc(s.desc[idx], idx);
-            int acc[2][4];
-            if (!l.log2n || !((s.cbf[l.plane] >> l.tile0) & 1)) {
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) acc[j][i] = 0;
-                store_rows(s.res, l, acc);
-                continue;
-            }
+            int acc[2][4] = {};
+            if (!l.log2n || !((s.cbf[l.plane] >> l.tile0) & 1)) { store_rows(s.res, l, kZero); continue; }
             const int sh = 20 - bit_depth;
             row_stage(s.mq, s.coef, l, acc);
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[j][i] = (int)(int16_t)((acc[j][i] + (1 << (sh - 1))) >> sh);
+            round8(acc, [&](int v) { return (int)(int16_t)((v + (1 << (sh - 1))) >> sh); });
             store_rows(s.res, l, acc);
         }
     });
