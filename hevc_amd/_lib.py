@@ -82,6 +82,54 @@ def src_format_for(pix_fmt: str):
     return SrcFormat(int(m.group(1)), 0, int(m.group(2) or 8), 0)
 
 
+class RgbFormat(C.Structure):
+    """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
+    _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
+
+    def __eq__(self, other):
+        return isinstance(other, RgbFormat) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"RgbFormat(layout={self.layout}, r={self.r}, g={self.g}, b={self.b}, sample={self.sample}, bit_depth={self.bit_depth}, matrix={self.matrix}, "
+                f"range={self.range})")
+
+    @property
+    def element_size(self) -> int:
+        return 4 if self.sample == 2 else 2 if self.sample == 1 or self.bit_depth > 8 else 1
+
+    def plane_shapes(self, width: int, height: int):
+        """the shapes of the source planes: three (height, width) planes, or one packed (height, layout * width) plane"""
+        return [(height, width)] * 3 if self.layout == 0 else [(height, self.layout * width)]
+
+    def frame_bytes(self, width: int, height: int) -> int:
+        return width * height * (self.layout or 3) * self.element_size
+
+
+_PACKED_RGB = {"rgb": (0, 1, 2), "bgr": (2, 1, 0)}
+
+
+def rgb_format_for(pix_fmt: str, matrix: int = 0, range: int = 0):
+    """The RgbFormat of an ffmpeg pixel format name, or None for one the RGB conversion does not cover (big endian, alpha planes, rgb565*, x2rgb10le, pal8,
+    gray*, and every Y'CbCr name: those are src_format_for's).  matrix / range: the struct's fields, 0 to follow the session"""
+    import re
+    name = (pix_fmt or "").lower()
+    m = re.fullmatch(r"gbrp(?:(9|10|12|14|16)le|(f32le))?", name)
+    if m:       # planes in G, B, R order
+        return RgbFormat(0, 2, 0, 1, 2 if m.group(2) else 0, 0 if m.group(2) else int(m.group(1) or 8), matrix, range)
+    m = re.fullmatch(r"(rgb|bgr)(24|48le)", name)
+    if m:
+        return RgbFormat(3, *_PACKED_RGB[m.group(1)], 0, 8 if m.group(2) == "24" else 16, matrix, range)
+    m = re.fullmatch(r"(rgb|bgr)(?:[a0]|(a64le))", name)
+    if m:
+        return RgbFormat(4, *_PACKED_RGB[m.group(1)], 0, 16 if m.group(2) else 8, matrix, range)
+    m = re.fullmatch(r"[a0](rgb|bgr)", name)
+    if m:
+        return RgbFormat(4, *(i + 1 for i in _PACKED_RGB[m.group(1)]), 0, 8, matrix, range)
+    return None
+
+
 # every symbol include/mihevc.h declares; tests/test_abi.py checks the header against this list and the .so
 EXPORTS = (
     "mihevc_abi_version", "mihevc_device_count", "mihevc_device_numa_node", "mihevc_config_default", "mihevc_open", "mihevc_send_frame", "mihevc_send_frame_async", "mihevc_sync_uploads", "mihevc_send_frame_device", "mihevc_send_frames_device",
@@ -89,7 +137,7 @@ EXPORTS = (
     "mihevc_get_recon", "mihevc_coded_size", "mihevc_get_frame_info", "mihevc_strerror", "mihevc_last_error", "mihevc_cost_params_for_qp", "mihevc_tile_grid", "mihevc_p_tile_grid", "mihevc_k_transform", "mihevc_k_transform_sdh",
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
-    "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan",
+    "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
 )
 
 _lib = None
@@ -156,6 +204,8 @@ def load() -> C.CDLL:
     lib.mihevc_k_ssim.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.mihevc_send_frame_fmt.argtypes = [vp, C.POINTER(SrcFormat), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_convert_source.argtypes = [i32, C.POINTER(SrcFormat), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_send_frame_rgb.argtypes = [vp, C.POINTER(RgbFormat), vp, vp, vp, i32, i64, i32]
+    lib.mihevc_k_convert_rgb.argtypes = [i32, C.POINTER(RgbFormat), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

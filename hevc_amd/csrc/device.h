@@ -7,6 +7,7 @@
 
 #include "kernels/common.h"
 #include "kernels/ingest.h"
+#include "kernels/ingest_rgb.h"
 #include "kernels/inter.h"
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
@@ -69,6 +70,8 @@ template <typename T> hipError_t launch_extend_margin(hipStream_t st, Plane<T> p
 
 // source conversion (kernels/ingest.h): one launch writes the three coded-size planes of `a`, margins included.  in16 / out16: uint16 source elements / output samples
 hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool out16);
+// RGB source conversion (kernels/ingest_rgb.h).  sample: mihevc_rgb_format::sample; elem_size: bytes of a source element
+hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample, int elem_size, bool out16);
 
 // rows between the slices of one picture (csrc/slice_group.h): jobs[i] for i < n_jobs, one grid row of `blocks_per_job` workgroups each
 hipError_t launch_copy_rows(hipStream_t st, const RowCopy *d_jobs, int n_jobs, int blocks_per_job);

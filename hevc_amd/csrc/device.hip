@@ -197,6 +197,27 @@ hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool ou
     return hipGetLastError();
 }
 
+// RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
+template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
+{
+    GpuExec ex;
+    ingest_rgb_tile_program<TI, FLT, TO>(ex, a, (int)blockIdx.x);
+}
+template <typename TO> static void launch_ingest_rgb_to(hipStream_t st, const IngestRgbArgs &a, int sample, int elem_size)
+{
+    const dim3 grid((unsigned)ingest_rgb_workgroups(a.pw, a.ph)), block(NT);
+    if (sample == 2) hipLaunchKernelGGL((k_ingest_rgb<uint32_t, true, TO>), grid, block, 0, st, a);
+    else if (sample == 1) hipLaunchKernelGGL((k_ingest_rgb<uint16_t, true, TO>), grid, block, 0, st, a);
+    else if (elem_size == 2) hipLaunchKernelGGL((k_ingest_rgb<uint16_t, false, TO>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_ingest_rgb<uint8_t, false, TO>), grid, block, 0, st, a);
+}
+hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample, int elem_size, bool out16)
+{
+    if (out16) launch_ingest_rgb_to<uint16_t>(st, a, sample, elem_size);
+    else launch_ingest_rgb_to<uint8_t>(st, a, sample, elem_size);
+    return hipGetLastError();
+}
+
 // scene-cut detector: sum of |a - b| over every 4th sample of every 4th row of the luma planes of pictures blockIdx.y - 1... the pair
 // (blockIdx.y, blockIdx.y + 1) -> out[blockIdx.y + 1]; wave reduction by shuffles, one atomic per wave
 template <typename T> __global__ __launch_bounds__(256) void k_scene_diff(const ScenePic<T> *pics, unsigned long long *out, int w, int h)
@@ -907,6 +928,30 @@ int stage_convert(const mihevc_src_format &f, const void *const *src, int w, int
     return dst.download(out);
 }
 
+// the RGB conversion kernel alone, as stage_convert: the planes keep their pitch and their offset from a 16-byte boundary, and end with their last sample
+template <typename TO>
+int stage_convert_rgb(const mihevc_rgb_format &f, const void *const *src, int w, int h, int pitch, int out_depth, void *const *out)
+{
+    const size_t es = (size_t)rgb_elem_size(f);
+    const struct { int w, h; } cd = {(w + 7) & ~7, (h + 7) & ~7};
+    DevBuf din[3];
+    Planes3<TO> dst;
+    if (dst.alloc(cd.w, cd.h, false)) return MIHEVC_ENOMEM;
+    const void *dsrc[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < rgb_planes(f); c++) {
+        const size_t off = (size_t)(uintptr_t)src[c] & 15, bytes = ((size_t)pitch * (h - 1) + rgb_row_elems(f, w)) * es;
+        CK(din[c].alloc(off + bytes));
+        CK(hipMemcpy(din[c].as<uint8_t>() + off, src[c], bytes, hipMemcpyHostToDevice));
+        dsrc[c] = din[c].as<uint8_t>() + off;
+    }
+    void *dptr[3]; int dstride[3];
+    for (int c = 0; c < 3; c++) { dptr[c] = dst.p[c].pl.p; dstride[c] = dst.p[c].pl.stride; }
+    const IngestRgbArgs a = ingest_rgb_args(f, f.matrix, f.range == 2, dsrc[0], dsrc[1], dsrc[2], pitch, w, h, cd.w, cd.h, out_depth, dptr, dstride);
+    CK(launch_ingest_rgb(0, a, f.sample, (int)es, sizeof(TO) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.download(out);
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -1083,6 +1128,18 @@ int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void
     const void *src[3] = {y, u, v};
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(out_bit_depth, [&](auto t) { return stage_convert<decltype(t)>(*fmt, src, width, height, pitch_y, pitch_c, out_bit_depth, out); });
+}
+
+int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2, int width, int height, int pitch,
+                         int out_bit_depth, void *out_y, void *out_u, void *out_v)
+{
+    if (!rgb_format_ok(fmt) || !rgb_matrix_ok(fmt->matrix) || fmt->range == 0 || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
+    const void *src[3] = {p0, p1, p2};
+    if (!rgb_planes_ok(*fmt, src, pitch, width)) return MIHEVC_EINVAL;
+    if (width < 16 || height < 16 || (width & 1) || (height & 1) || width > 8192 || height > 4352 || (out_bit_depth != 8 && out_bit_depth != 10)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(out_bit_depth, [&](auto t) { return stage_convert_rgb<decltype(t)>(*fmt, src, width, height, pitch, out_bit_depth, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

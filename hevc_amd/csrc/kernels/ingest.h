@@ -1,6 +1,7 @@
 // hevc_amd/csrc/kernels/ingest.h — source conversion (mihevc_send_frame_fmt, mihevc_k_convert_source): a 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar, 8 .. 16 bit
 // source picture -> the session's own planar 4:2:0 planes at 8 or 10 bit, margin included.  Integers only, so that the device, the stepped kernel (tests/emu)
-// and the numpy model (tests/ingest_ref.py) agree bit for bit.  The definition (normative; DESIGN.md repeats it):
+// and the numpy model (tests/ingest_ref.py) agree bit for bit.  R'G'B' sources take the same road with a colour matrix in front: ingest_rgb.h, which builds on
+// the loads, stores and alignment classes of this file.  The definition (normative; DESIGN.md repeats it):
 //   picture  W x H (display size, both even); chroma planes W/2 x H/2 (420), W/2 x H (422), W x H (444).  B = significant bits of a source sample (8 .. 16),
 //            D = the session's bit depth (8 or 10)
 //   sample   the raw element r is a uint8 when B == 8, else a little-endian uint16.  msb_aligned (P010, P210 ...): v = r >> (16 - B); else v = min(r, 2^B - 1)

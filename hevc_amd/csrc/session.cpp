@@ -1412,6 +1412,37 @@ static int ingest_fmt(mihevc_session *s, const mihevc_src_format &f, const void 
     return enqueue_source(s, std::move(src), pts);
 }
 
+// An RGB source (mihevc_send_frame_rgb; the arguments are checked, matrix and range resolved): as ingest_fmt, with k_ingest_rgb and the same staging set
+static int ingest_rgb(mihevc_session *s, const mihevc_rgb_format &f, int matrix, bool full, const void *const *p, int pitch, int64_t pts, bool device_src, bool async)
+{
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    mihevc_session::Src src;
+    if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
+    else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;
+    src.borrowed = false;
+    const size_t es = (size_t)rgb_elem_size(f);
+    const int W = s->cfg.width, H = s->cfg.height, n_planes = rgb_planes(f), row = rgb_row_elems(f, W);
+    const void *in[3] = {p[0], p[1], p[2]};
+    if (!device_src) {
+        const int spitch = (row + 15) & ~15;           // rows begin 16-byte aligned: the kernel's widest loads
+        const size_t plane = ((size_t)spitch * H * es + 255) & ~(size_t)255, total = plane * n_planes;
+        if (total > s->stage.bytes()) {
+            HIPCK(s, hipStreamSynchronize(s->st_pre));      // a conversion still reading the smaller set
+            HIPCK(s, s->stage.alloc(s->device, total, false));
+        }
+        for (int c = 0; c < n_planes; c++) {
+            HIPCK(s, hipMemcpy2DAsync(s->stage + plane * c, spitch * es, in[c], pitch * es, row * es, H, hipMemcpyHostToDevice, s->st_pre));
+            in[c] = s->stage + plane * c;
+        }
+        pitch = spitch;
+    }
+    const IngestRgbArgs a = ingest_rgb_args(f, matrix, full, in[0], in[1], in[2], pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
+    HIPCK(s, launch_ingest_rgb(s->st_pre, a, f.sample, (int)es, s->is16));
+    if (!device_src && !async) HIPCK(s, hipStreamSynchronize(s->st_pre));     // caller's buffers may be reused on return
+    else s->up_pending = true;
+    return enqueue_source(s, std::move(src), pts);
+}
+
 int mihevc_send_frame(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
 {
     return ingest(s, y, u, v, pitch_y, pitch_c, pts, false, false);
@@ -1444,6 +1475,18 @@ int mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const
     if (s->failed) return s->fail_code;
     if (s->flushed) return MIHEVC_ESTATE;
     return ingest_fmt(s, *fmt, y, u, v, pitch_y, pitch_c, pts, device_src, async);
+}
+int mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2, int pitch, int64_t pts, int flags)
+{
+    if (!s || !rgb_format_ok(fmt) || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
+    const int matrix = fmt->matrix ? fmt->matrix : s->cfg.matrix;
+    const void *p[3] = {p0, p1, p2};
+    if (!rgb_matrix_ok(matrix) || !rgb_planes_ok(*fmt, p, pitch, s->cfg.width)) return MIHEVC_EINVAL;
+    if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
+    if (s->failed) return s->fail_code;
+    if (s->flushed) return MIHEVC_ESTATE;
+    const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
+    return ingest_rgb(s, *fmt, matrix, full, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
 }
 int mihevc_sync_uploads(mihevc_session *s)
 {

@@ -188,6 +188,67 @@ class Encoder:
         self._check(self._lib.mihevc_send_frame_fmt(self._s, C.byref(fmt), ptrs[0], ptrs[1], ptrs[2] if len(ptrs) == 3 else None, pitches[0], pitches[1], pts, flags),
                     "send_frame_fmt")
 
+    def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
+        Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
+        layout); uint8 at 8 bit, uint16 above, float16 / float32 for the float formats.  numpy planes are checked for shape and type here; torch tensors on the
+        session's device are read where they are (MIHEVC_SRC_DEVICE) under the rules of send_fmt, and so is `asynchronous`."""
+        c = self.cfg
+        shapes = fmt.plane_shapes(c.width, c.height)
+        planes = list(planes)
+        if fmt.layout and len(planes) == 1 and planes[0] is not None and tuple(planes[0].shape) == (c.height, c.width, fmt.layout):
+            if isinstance(planes[0], np.ndarray) or planes[0].is_contiguous():
+                planes[0] = planes[0].reshape(c.height, c.width * fmt.layout)
+        if len(planes) != len(shapes) or any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {fmt!r} at {c.width}x{c.height}")
+        flags = _lib.SRC_ASYNC if asynchronous else 0
+        es = fmt.element_size
+        if all(isinstance(p, np.ndarray) for p in planes):
+            dt = np.dtype({1: np.float16, 2: np.float32}[fmt.sample]) if fmt.sample else np.dtype(np.uint8 if es == 1 else np.uint16)
+            if asynchronous:
+                if any(p.dtype != dt or not p.flags.c_contiguous for p in planes):
+                    raise ValueError("an asynchronous send_rgb needs C-contiguous planes of the format's element type")
+            elif any(p.dtype.itemsize != es or (p.dtype.kind == "f") != bool(fmt.sample) for p in planes):
+                raise ValueError(f"{[str(p.dtype) for p in planes]} planes handed over as {fmt!r}")
+            else:
+                planes = [np.ascontiguousarray(p).view(dt) for p in planes]
+            ptrs, pitches = [p.ctypes.data for p in planes], [p.shape[1] for p in planes]
+        else:       # torch tensors on the device
+            if any(isinstance(p, np.ndarray) or not p.is_cuda or p.element_size() != es or p.is_floating_point() != bool(fmt.sample) or p.stride(1) != 1 for p in planes):
+                raise ValueError("device planes must be tensors on the GPU of the format's element type with unit column stride")
+            ptrs, pitches, flags = [p.data_ptr() for p in planes], [p.stride(0) for p in planes], flags | _lib.SRC_DEVICE
+        if len(set(pitches)) != 1:
+            raise ValueError("the three planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        ptrs += [None] * (3 - len(ptrs))
+        self._check(self._lib.mihevc_send_frame_rgb(self._s, C.byref(fmt), ptrs[0], ptrs[1], ptrs[2], pitches[0], pts, flags), "send_frame_rgb")
+
+    def send_rgb_tensor(self, t, pts: Optional[int] = None, asynchronous: bool = False):
+        """send_rgb for one tensor in R, G, B order: (3, H, W) of uint8, 16-bit integers (int16 carries the bits of a uint16), float16 or float32 in [0, 1],
+        or (H, W, 3) / (H, W, 4) of uint8 (a fourth element is ignored).  The format is built here; matrix and range follow the session.  A tensor on the session's
+        device is read where it is; a layout the kernel cannot read (column stride other than 1, pixels not side by side) raises ValueError."""
+        kind = str(getattr(t, "dtype", "")).rsplit(".", 1)[-1]      # the tensor is taken by its interface: the package does not import torch
+        if not hasattr(t, "data_ptr") or t.dim() != 3:
+            raise ValueError("send_rgb_tensor takes a (3, H, W) or (H, W, 3 | 4) torch tensor")
+        if t.shape[0] == 3 and kind in ("uint8", "int16", "uint16", "float16", "float32"):
+            sample = 1 if kind == "float16" else 2 if kind == "float32" else 0
+            fmt = _lib.RgbFormat(0, 0, 1, 2, sample, 0 if sample else 8 if kind == "uint8" else 16)
+            if t.stride(2) != 1 or t.stride(1) < t.shape[2]:
+                raise ValueError(f"strides {tuple(t.stride())}: the kernel reads rows of adjacent samples")
+            planes = [t[0], t[1], t[2]]
+        elif t.shape[2] in (3, 4) and kind == "uint8":
+            fmt = _lib.RgbFormat(int(t.shape[2]), 0, 1, 2, 0, 8)
+            if t.stride(2) != 1 or t.stride(1) != t.shape[2] or t.stride(0) < t.shape[1] * t.shape[2]:
+                raise ValueError(f"strides {tuple(t.stride())}: the kernel reads rows of adjacent pixels")
+            planes = [t.as_strided((t.shape[0], t.shape[1] * t.shape[2]), (t.stride(0), 1))]
+        else:
+            raise ValueError(f"a {tuple(t.shape)} {t.dtype} tensor is no RGB picture this entry takes")
+        if not t.is_cuda:
+            planes = [p.contiguous().numpy() for p in planes]
+            planes = [p.view(np.uint16) if p.dtype == np.int16 else p for p in planes]
+        self.send_rgb(fmt, *planes, pts=pts, asynchronous=asynchronous)
+
     def sync_uploads(self):
         self._check(self._lib.mihevc_sync_uploads(self._s), "sync_uploads")
 
@@ -317,6 +378,8 @@ class ShardedEncoder:
                 y, u, v, pts, fmt = item
                 if fmt is None:
                     enc.send(y, u, v, pts=pts)      # ctypes releases the GIL: the sessions run concurrently
+                elif isinstance(fmt, _lib.RgbFormat):
+                    enc.send_rgb(fmt, *[p for p in (y, u, v) if p is not None], pts=pts)
                 else:
                     enc.send_fmt(fmt, y, u, v, pts=pts)
                 self._collect(enc)
@@ -334,7 +397,8 @@ class ShardedEncoder:
                     self._out[pts] = (data, key)
 
     def send(self, y, u, v, fmt=None):
-        """fmt: the planes' _lib.SrcFormat when they are not the session's own layout (Encoder.send_fmt)"""
+        """fmt: the planes' _lib.SrcFormat when they are not the session's own layout (Encoder.send_fmt), or their _lib.RgbFormat (Encoder.send_rgb; a packed
+        source: y is the packed plane, u and v are None)"""
         import queue
         k = (self._n_in // self.chunk) % len(self.devices)
         while True:                                 # a bounded queue whose worker has died must not block the caller for ever
@@ -558,16 +622,18 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
-                devices=None, row_split: bool = False) -> int:
+                devices=None, row_split: bool = False, native_rgb: bool = False) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
-    the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535)."""
+    the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
+    formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
+    probed matrix, BT.709 when that is `gbr` or unknown."""
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
 
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
     sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
-    clip = yuvio.open_any(Path(file_path), info, native_formats=not sliced)
+    clip = yuvio.open_any(Path(file_path), info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
     mux = None
     ok = False
     try:
@@ -575,6 +641,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             info.pix_fmt = 'yuv420p10le'
         cfg = config_for(info, crf, maxrate, bufsize, gop, level, tier)
         fmt = getattr(clip, 'src_format', None)     # not the session's own layout: converted on the device (send_fmt)
+        rgb = getattr(clip, 'rgb_format', None)     # an RGB source: matrixed and decimated on the device (send_rgb)
+        if rgb is not None:
+            fmt = rgb
+            if cfg.matrix not in (1, 5, 6, 9):
+                cfg.matrix = 1
         if fmt is not None and sliced:
             logger.error("%s: a %r source cannot be split by rows", Path(file_path).name, fmt)
             return 1
@@ -594,9 +665,10 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if devices and len(devices) > 1:            # one clip over several GPUs: GOP chunks round-robin, or every picture split by CTU rows
             sh = SlicedEncoder(cfg, devices) if row_split else ShardedEncoder(cfg, devices)
             try:
-                for y, u, v in clip.frames():
+                for planes in clip.frames():
                     if stop_event is not None and stop_event.is_set():
                         return 1
+                    y, u, v = (tuple(planes) + (None, None))[:3]
                     if fmt is None:
                         sh.send(y, u, v)
                     else:
@@ -614,13 +686,15 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 sh.close()                          # joins the workers (abort) before any session is closed
         else:
             with Encoder(cfg, device=device or 0) as enc:
-                for i, (y, u, v) in enumerate(clip.frames()):
+                for i, planes in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
                     if fmt is None:
-                        enc.send(y, u, v, pts=i)
+                        enc.send(*planes, pts=i)
+                    elif rgb is not None:
+                        enc.send_rgb(fmt, *planes, pts=i)
                     else:
-                        enc.send_fmt(fmt, y, u, v, pts=i)
+                        enc.send_fmt(fmt, *planes, pts=i)
                     for data, pts, key, dts in enc.packets_dts():
                         mux.add_sample(data, pts, key, dts)
                         n_out += 1

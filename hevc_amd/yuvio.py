@@ -116,9 +116,11 @@ class _PipeClip:
     """Any container decoded by an `ffmpeg -f rawvideo` child (only when ffmpeg exists on this host).  A decode error or a short
     stream raises: a truncated clip must not come out as SUCCESS.  A probed sample format the device conversion covers (_lib.src_format_for) is
     asked for as it is, so swscale has nothing to do, and comes out with `src_format` set; anything else is asked for as planar 4:2:0, and so
-    are the full-range yuvj* formats: there is no range conversion on the device, swscale's stays in front of them."""
+    are the full-range yuvj* formats: there is no range conversion on the device, swscale's stays in front of them.  rgb_formats (opt-in): a probed
+    RGB format of _lib.rgb_format_for is asked for as it is too, and the clip carries `rgb_format`: frames() then yields the three planes in the
+    format's own order, or the one packed (height, layout * width) plane, for Encoder.send_rgb; a source deeper than 8 bit makes a 10-bit session."""
 
-    def __init__(self, path: Path, info, native_formats: bool = True):
+    def __init__(self, path: Path, info, native_formats: bool = True, rgb_formats: bool = False):
         self.width, self.height, self.fps = info.width, info.height, info.fps
         from .encoder import bit_depth_of
         self.bit_depth = bit_depth_of(info)
@@ -132,6 +134,13 @@ class _PipeClip:
             pix = name
             if fmt != SrcFormat(420, 0, self.bit_depth, 0):
                 self.src_format = fmt
+        self.rgb_format = None
+        if rgb_formats and native_formats and fmt is None:
+            from ._lib import rgb_format_for
+            self.rgb_format = rgb_format_for(name)
+            if self.rgb_format is not None:
+                pix = name
+                self.bit_depth = 10 if self.bit_depth > 8 or self.rgb_format.element_size > 1 else 8
         self._name = Path(path).name
         # stderr goes to a file, not a pipe: a damaged input can make `-v error` write more than a pipe buffer holds before the first frame, and a
         # child blocked on stderr while frames() blocks on stdout would hang the encode for ever instead of failing it
@@ -140,16 +149,22 @@ class _PipeClip:
                                    stdout=subprocess.PIPE, stderr=self._err)
 
     def frames(self) -> Iterator[Planes]:
-        w, h, fmt = self.width, self.height, self.src_format
+        w, h, fmt, rgb = self.width, self.height, self.src_format, self.rgb_format
         fb = fmt.frame_bytes(w, h) if fmt is not None else w * h * 3 // 2 * (2 if self.bit_depth > 8 else 1)
         dt = np.dtype('<u2') if (fmt.bit_depth if fmt is not None else self.bit_depth) > 8 else np.uint8
+        if rgb is not None:
+            fb = rgb.frame_bytes(w, h)
+            dt = np.dtype('<f4') if rgb.sample == 2 else np.dtype('<f2') if rgb.sample == 1 else np.dtype('<u2') if rgb.element_size == 2 else np.uint8
         n = 0
         while True:
             buf = self._p.stdout.read(fb)
             if len(buf) < fb:
                 break
             n += 1
-            yield _split_frame(np.frombuffer(buf, dt), w, h, fmt)
+            if rgb is not None:
+                yield tuple(np.frombuffer(buf, dt).reshape(len(rgb.plane_shapes(w, h)), *rgb.plane_shapes(w, h)[0]))
+            else:
+                yield _split_frame(np.frombuffer(buf, dt), w, h, fmt)
         rc = self._p.wait()
         self._err.seek(0, 2)
         self._err.seek(max(0, self._err.tell() - 2000))
@@ -172,14 +187,15 @@ class _PipeClip:
             pass
 
 
-def open_any(path: Path, info=None, native_formats: bool = True):
-    """native_formats=False: a container's frames are asked of ffmpeg as planar 4:2:0 whatever its own format (for a consumer without send_fmt)"""
+def open_any(path: Path, info=None, native_formats: bool = True, rgb_formats: bool = False):
+    """native_formats=False: a container's frames are asked of ffmpeg as planar 4:2:0 whatever its own format (for a consumer without send_fmt).
+    rgb_formats=True: a container probed as an RGB format of _lib.rgb_format_for is asked for as it is (for a consumer with send_rgb)"""
     path = Path(path)
     if path.suffix.lower() in ('.y4m', '.yuv'):
         return open_clip(path)
     if shutil.which('ffmpeg') is None:
         raise RuntimeError(f'{path.name}: only .y4m/.yuv can be read without ffmpeg on this host')
-    return _PipeClip(path, info, native_formats)
+    return _PipeClip(path, info, native_formats, rgb_formats)
 
 
 def write_y4m(path: Path, frames, width: int, height: int, fps=30, bit_depth: int = 8, chroma: int = 420, src_depth: Optional[int] = None):

@@ -200,7 +200,7 @@ int  mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, c
  * chroma_sample_loc_type 0), deeper samples are rounded half up once, shallower ones shifted up, values above 2^bit_depth - 1 in an lsb-aligned plane are
  * clamped.  Covers ffmpeg's yuv420p / yuv422p / yuv444p (and yuvj*), yuv4xxp{9,10,12,14,16}le, nv12 / nv16 / nv24, p010le / p016le / p210le / p216le /
  * p410le / p416le.  Not covered (MIHEVC_EINVAL; hevc_amd._lib.src_format_for gives None): swapped semi-planar (nv21), packed formats (yuyv422, uyvy422,
- * v210), RGB / gbrp, 4:1:1 / 4:1:0, big endian, alpha; there is no range conversion. */
+ * v210), 4:1:1 / 4:1:0, big endian, alpha; there is no range conversion.  RGB / gbrp sources: mihevc_send_frame_rgb below. */
 typedef struct mihevc_src_format {
     int32_t chroma;        /* 420, 422, 444 */
     int32_t semi_planar;   /* 0: y, u, v planes; 1: y + interleaved CbCr in u (Cb in the even elements), v is ignored */
@@ -221,6 +221,33 @@ typedef struct mihevc_src_format {
  * slice_count > 1.  MIHEVC_ESTATE after flush. */
 int  mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v,
                            int pitch_y, int pitch_c, int64_t pts, int flags);
+/* ---- added under ABI 6: RGB sources (symbols only) ----
+ * A full-range R'G'B' picture of the session's DISPLAY size, planar or packed, integers of 8 .. 16 significant bits (lsb aligned; uint8 at 8 bit, else
+ * little-endian uint16; values above 2^bit_depth - 1 are clamped) or IEEE half / single floats in [0, 1] (planes only; clamped, NaN is 0).  One kernel
+ * launch applies the colour matrix, scales to the limited or full range of cfg.bit_depth, filters chroma down to 4:2:0 (the siting and taps of the 4:4:4 case
+ * of mihevc_send_frame_fmt) and fills the margin; hevc_amd/csrc/kernels/ingest_rgb.h states the integer arithmetic, DESIGN.md 6d repeats it.  Covers ffmpeg's
+ * gbrp, gbrp{9,10,12,14,16}le, gbrpf32le, rgb24 / bgr24, rgba / bgra / argb / abgr / rgb0 / bgr0 / 0rgb / 0bgr, rgb48le / bgr48le, rgba64le / bgra64le
+ * (hevc_amd._lib.rgb_format_for).  A fourth element of a packed pixel is ignored.  Neither the session's signalled matrix nor its range changes: the caller opens
+ * the session with the cfg.matrix / cfg.full_range it wants in the stream, and matrix = 0 / range = 0 here follow them. */
+typedef struct mihevc_rgb_format {
+    int32_t layout;      /* 0 three planes; 3 / 4: packed, that many elements per pixel */
+    int32_t r, g, b;     /* planar: which of p0..p2 holds the component; packed: its element index inside the pixel */
+    int32_t sample;      /* 0 unsigned integer, 1 IEEE half, 2 IEEE single (layout 0 only) */
+    int32_t bit_depth;   /* sample 0: 8..16; floats: 0 */
+    int32_t matrix;      /* 0: the session's cfg.matrix; else 1, 5, 6, 9 */
+    int32_t range;       /* 0: the session's cfg.full_range; 1 limited; 2 full */
+    int32_t reserved[4]; /* 0 */
+} mihevc_rgb_format;
+/* pitch: elements per row, the same for every plane (a packed plane: >= layout * width).  Ownership, staging, stream ordering and flags are those of
+ * mihevc_send_frame_fmt: host planes are copied into the session's staging set and converted from there, and without MIHEVC_SRC_ASYNC they may be reused on
+ * return; with MIHEVC_SRC_DEVICE the kernel reads the planes where they are, and they must stay valid and unmodified until mihevc_sync_uploads or mihevc_flush
+ * has returned.  A packed source has one plane, p0; p1 and p2 are not read.  MIHEVC_EINVAL, decided before any device call and leaving the session usable: a
+ * NULL fmt or a NULL plane the layout needs, a plane whose address is not a multiple of the element size, a layout other than 0 / 3 / 4, component
+ * indices out of range or not distinct, a depth outside 8..16 (floats: other than 0), floats with a packed layout, non-zero reserved, a matrix that resolves to
+ * anything other than 1 / 5 / 6 / 9 (a session whose cfg.matrix is 0 or 2 with matrix = 0 included), a range above 2, odd cfg.width / cfg.height, a pitch smaller
+ * than the row, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush. */
+int  mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2,
+                           int pitch, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -360,6 +387,11 @@ int mihevc_k_ssim(int device, const void *a_y, const void *a_u, const void *a_v,
 int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void *y, const void *u, const void *v,
                             int width, int height, int pitch_y, int pitch_c, int out_bit_depth,
                             void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  The conversion of mihevc_send_frame_rgb alone (the session's kernel), host buffers in and out; sizes and output planes as
+ * mihevc_k_convert_source.  There is no session to follow: fmt->matrix must be 1 / 5 / 6 / 9 and fmt->range 1 or 2.  Validated first (MIHEVC_EINVAL), then
+ * MIHEVC_ENODEV without a device */
+int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2,
+                         int width, int height, int pitch, int out_bit_depth, void *out_y, void *out_u, void *out_v);
 
 /* ---- host-only stages (no device needed): bitstream ---- */
 /* VPS+SPS+PPS (+SEI when hdr10) as Annex-B into buf; returns size or negative error */
