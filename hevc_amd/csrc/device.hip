@@ -901,55 +901,66 @@ template <typename T> int stage_ssim(const void *const *a, const void *const *b,
     return MIHEVC_OK;
 }
 
-// the conversion kernel alone: the source planes as the caller laid them out (pitches kept, so their alignment is the caller's), the output in planes of
-// 16-byte aligned stride
+// A source plane of a converter as the caller laid it out: the device copy keeps the pitch and starts at the same offset from a 16-byte boundary, so its
+// alignment class is the caller's, and it ends with the last sample of the last row.  row, pitch: in elements of es bytes; p becomes the device copy
+int upload_as_laid_out(DevBuf &d, const void *&p, int row, int rows, int pitch, size_t es)
+{
+    const size_t off = (size_t)(uintptr_t)p & 15, bytes = ((size_t)pitch * (rows - 1) + row) * es;
+    CK(d.alloc(off + bytes));
+    CK(hipMemcpy(d.as<uint8_t>() + off, p, bytes, hipMemcpyHostToDevice));
+    p = d.as<uint8_t>() + off;
+    return MIHEVC_OK;
+}
+// the output of a converter: planes of the coded size (the display size rounded up to 8) and of 16-byte aligned stride
+template <typename TO> struct ConvertOut {
+    Planes3<TO> planes;
+    int w, h, stride[3];
+    void *p[3];
+    int alloc(int sw, int sh)
+    {
+        w = (sw + 7) & ~7; h = (sh + 7) & ~7;
+        if (planes.alloc(w, h, false)) return MIHEVC_ENOMEM;
+        for (int c = 0; c < 3; c++) { p[c] = planes.p[c].pl.p; stride[c] = planes.p[c].pl.stride; }
+        return MIHEVC_OK;
+    }
+};
+bool convert_geometry_ok(int w, int h, int out_depth)
+{
+    return w >= 16 && h >= 16 && !(w & 1) && !(h & 1) && w <= 8192 && h <= 4352 && (out_depth == 8 || out_depth == 10);
+}
+
+// the conversion kernel alone
 template <typename TO>
 int stage_convert(const mihevc_src_format &f, const void *const *src, int w, int h, int pitch_y, int pitch_c, int out_depth, void *const *out)
 {
     const size_t es = f.bit_depth > 8 ? 2 : 1;
-    const struct { int w, h; } cd = {(w + 7) & ~7, (h + 7) & ~7};      // the coded size: rounded up to 8
     DevBuf din[3];
-    Planes3<TO> dst;
-    if (dst.alloc(cd.w, cd.h, false)) return MIHEVC_ENOMEM;
-    const void *dsrc[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0; c < (f.semi_planar ? 2 : 3); c++) {
-        const int row = c ? src_chroma_row(f, w) : w, rows = c ? src_chroma_rows(f, h) : h, pitch = c ? pitch_c : pitch_y;
-        // the source's own misalignment travels with it: the device copy starts at the same offset from a 16-byte boundary, and ends with the last sample
-        const size_t off = (size_t)(uintptr_t)src[c] & 15, bytes = ((size_t)pitch * (rows - 1) + row) * es;
-        CK(din[c].alloc(off + bytes));
-        CK(hipMemcpy(din[c].as<uint8_t>() + off, src[c], bytes, hipMemcpyHostToDevice));
-        dsrc[c] = din[c].as<uint8_t>() + off;
-    }
-    void *dptr[3]; int dstride[3];
-    for (int c = 0; c < 3; c++) { dptr[c] = dst.p[c].pl.p; dstride[c] = dst.p[c].pl.stride; }
-    const IngestArgs a = ingest_args(f, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, w, h, cd.w, cd.h, out_depth, dptr, dstride);
+    ConvertOut<TO> dst;
+    if (int e = dst.alloc(w, h)) return e;
+    const void *dsrc[3] = {src[0], src[1], f.semi_planar ? nullptr : src[2]};
+    for (int c = 0; c < (f.semi_planar ? 2 : 3); c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? src_chroma_row(f, w) : w, c ? src_chroma_rows(f, h) : h, c ? pitch_c : pitch_y, es)) return e;
+    const IngestArgs a = ingest_args(f, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, w, h, dst.w, dst.h, out_depth, dst.p, dst.stride);
     CK(launch_ingest(0, a, es == 2, sizeof(TO) == 2));
     CK(hipDeviceSynchronize());
-    return dst.download(out);
+    return dst.planes.download(out);
 }
 
-// the RGB conversion kernel alone, as stage_convert: the planes keep their pitch and their offset from a 16-byte boundary, and end with their last sample
+// the RGB conversion kernel alone
 template <typename TO>
 int stage_convert_rgb(const mihevc_rgb_format &f, const void *const *src, int w, int h, int pitch, int out_depth, void *const *out)
 {
     const size_t es = (size_t)rgb_elem_size(f);
-    const struct { int w, h; } cd = {(w + 7) & ~7, (h + 7) & ~7};
     DevBuf din[3];
-    Planes3<TO> dst;
-    if (dst.alloc(cd.w, cd.h, false)) return MIHEVC_ENOMEM;
-    const void *dsrc[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0; c < rgb_planes(f); c++) {
-        const size_t off = (size_t)(uintptr_t)src[c] & 15, bytes = ((size_t)pitch * (h - 1) + rgb_row_elems(f, w)) * es;
-        CK(din[c].alloc(off + bytes));
-        CK(hipMemcpy(din[c].as<uint8_t>() + off, src[c], bytes, hipMemcpyHostToDevice));
-        dsrc[c] = din[c].as<uint8_t>() + off;
-    }
-    void *dptr[3]; int dstride[3];
-    for (int c = 0; c < 3; c++) { dptr[c] = dst.p[c].pl.p; dstride[c] = dst.p[c].pl.stride; }
-    const IngestRgbArgs a = ingest_rgb_args(f, f.matrix, f.range == 2, dsrc[0], dsrc[1], dsrc[2], pitch, w, h, cd.w, cd.h, out_depth, dptr, dstride);
+    ConvertOut<TO> dst;
+    if (int e = dst.alloc(w, h)) return e;
+    const void *dsrc[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < rgb_planes(f); c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], rgb_row_elems(f, w), h, pitch, es)) return e;
+    const IngestRgbArgs a = ingest_rgb_args(f, f.matrix, f.range == 2, dsrc[0], dsrc[1], dsrc[2], pitch, w, h, dst.w, dst.h, out_depth, dst.p, dst.stride);
     CK(launch_ingest_rgb(0, a, f.sample, (int)es, sizeof(TO) == 2));
     CK(hipDeviceSynchronize());
-    return dst.download(out);
+    return dst.planes.download(out);
 }
 
 int select_device(int device)
@@ -1121,8 +1132,7 @@ int mihevc_k_ssim(int device, const void *ay, const void *au, const void *av, co
 int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int width, int height, int pitch_y, int pitch_c,
                             int out_bit_depth, void *out_y, void *out_u, void *out_v)
 {
-    if (!src_format_ok(fmt) || !y || !u || (!v && !fmt->semi_planar) || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
-    if (width < 16 || height < 16 || (width & 1) || (height & 1) || width > 8192 || height > 4352 || (out_bit_depth != 8 && out_bit_depth != 10)) return MIHEVC_EINVAL;
+    if (!src_format_ok(fmt) || !y || !u || (!v && !fmt->semi_planar) || !out_y || !out_u || !out_v || !convert_geometry_ok(width, height, out_bit_depth)) return MIHEVC_EINVAL;
     if (pitch_y < width || pitch_c < src_chroma_row(*fmt, width)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
     const void *src[3] = {y, u, v};
@@ -1135,8 +1145,7 @@ int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p
 {
     if (!rgb_format_ok(fmt) || !rgb_matrix_ok(fmt->matrix) || fmt->range == 0 || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
     const void *src[3] = {p0, p1, p2};
-    if (!rgb_planes_ok(*fmt, src, pitch, width)) return MIHEVC_EINVAL;
-    if (width < 16 || height < 16 || (width & 1) || (height & 1) || width > 8192 || height > 4352 || (out_bit_depth != 8 && out_bit_depth != 10)) return MIHEVC_EINVAL;
+    if (!rgb_planes_ok(*fmt, src, pitch, width) || !convert_geometry_ok(width, height, out_bit_depth)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(out_bit_depth, [&](auto t) { return stage_convert_rgb<decltype(t)>(*fmt, src, width, height, pitch, out_bit_depth, out); });

@@ -21,7 +21,9 @@
 // 4); lanes side by side take runs side by side.  A run inside the display area reads its source rows in chunks of 16, 8 or 4 bytes, the widest the plane's
 // base address and pitch allow (IngestArgs::align, the same for every lane: a uniform branch), or element by element; a run that reaches into the margin, and
 // the left tap of the 4:4:4 filter, read single elements at clamped coordinates.  No access the source states is wider than its alignment (the stepped harness counts them) and none lies outside
-// the rows of the source; what the compiler makes of the narrow paths on the device is kept apart by ingest_keep_apart, which no test of the device build checks.
+// the rows of the source; what the compiler makes of the narrow paths on the device is kept apart by ingest_keep_apart: the device tests run every alignment
+// class and check what comes out, not the width of the accesses.  ingest_load, ingest_element and ingest_store serve k_ingest_rgb too: one copy of the
+// chunk paths, behind one access hook.
 #pragma once
 #include "common.h"
 
@@ -89,8 +91,8 @@ inline IngestArgs ingest_args(const mihevc_src_format &f, const void *y, const v
     return a;
 }
 
-// every chunk load and every store passes here with its address and its width in bytes: nothing in the product; the stepped harness (tests/emu/ingest.cpp) defines
-// the hook before it includes this file and counts the accesses whose address is not a multiple of their width
+// every chunk load, every load through ingest_element and every store passes here with its address and its width in bytes: nothing in the product; the stepped
+// harnesses (tests/emu/ingest_planes.h) define the hook before they include this file and count the accesses whose address is not a multiple of their width
 #ifndef MIHEVC_INGEST_ACCESS
 #define MIHEVC_INGEST_ACCESS(p, bytes) ((void)0)
 #endif
@@ -116,6 +118,13 @@ template <int CB> DEV void ingest_chunk(const void *p, uint32_t (&w)[CB / 4])
         w[0] = v[0]; w[1] = v[1];
     } else w[0] = load_u32_aligned(p);
 }
+// one element, kept apart from its neighbours: the narrowest path of ingest_load, and the single pixels of k_ingest_rgb
+template <typename TI> DEV void ingest_element(const TI *p, int &v)
+{
+    MIHEVC_INGEST_ACCESS(p, sizeof(TI));
+    v = (int)*p;
+    ingest_keep_apart();
+}
 // N elements from p in chunks of CB bytes (p is CB-aligned)
 template <typename TI, int N, int CB> DEV void ingest_load_chunks(const TI *p, int (&v)[N])
 {
@@ -129,7 +138,8 @@ template <typename TI, int N, int CB> DEV void ingest_load_chunks(const TI *p, i
 #pragma unroll
         for (int k = 0; k < per; k++) {
             if constexpr (sizeof(TI) == 1) v[c * per + k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
-            else v[c * per + k] = (int)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+            else if constexpr (sizeof(TI) == 2) v[c * per + k] = (int)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+            else v[c * per + k] = (int)w[k];
         }
     }
 }
@@ -142,7 +152,7 @@ template <typename TI, int N> DEV void ingest_load(const TI *p, int al, int (&v)
     if (al >= 8) { ingest_load_chunks<TI, N, 8>(p, v); return; }
     if (al >= 4) { ingest_load_chunks<TI, N, 4>(p, v); return; }
 #pragma unroll
-    for (int k = 0; k < N; k++) { v[k] = (int)p[k]; ingest_keep_apart(); }
+    for (int k = 0; k < N; k++) ingest_element(p + k, v[k]);
 }
 
 // ING_RUN samples (`full`), or the first half of them, to p: one vector store either way

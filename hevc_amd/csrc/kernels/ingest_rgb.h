@@ -22,9 +22,8 @@
 // know an order; an unused fourth element meets a zero coefficient.  A block inside the display area reads its rows in chunks of 16, 8 or 4 bytes, the widest
 // that the base addresses and the pitch allow (IngestRgbArgs::align: a uniform branch), or element by element; a block that reaches into the margin, and the left
 // tap, read single elements at clamped coordinates.  A block of a packed row is RGB_BW x 3 or x 4 elements: a multiple of 16 bytes for every element type, so
-// 3-byte pixels take the same chunks as everything else and a pixel may straddle two of them.
-// The hooked loads and stores are this file's own (MIHEVC_INGEST_RGB_ACCESS): the stepped library holds the harness of ingest.h too, with a counter of its own
-// behind MIHEVC_INGEST_ACCESS, and an inline function must have one body in every file of a library.
+// 3-byte pixels take the same chunks as everything else and a pixel may straddle two of them.  The chunk loads, the element load and the stores are those of
+// ingest.h (ingest_load, ingest_element, ingest_store), behind its one access hook.
 #pragma once
 #include "ingest.h"
 
@@ -120,12 +119,6 @@ inline IngestRgbArgs ingest_rgb_args(const mihevc_rgb_format &f, int matrix, boo
     return a;
 }
 
-// every load and every store passes here with its address and its width in bytes: nothing in the product; the stepped harness (tests/emu/ingest_rgb.cpp)
-// defines the hook before it includes this file and counts the accesses whose address is not a multiple of their width
-#ifndef MIHEVC_INGEST_RGB_ACCESS
-#define MIHEVC_INGEST_RGB_ACCESS(p, bytes) ((void)0)
-#endif
-
 // ---- the float rule.  No contraction can arise: the one product feeds rint, not a sum
 DEV float rgb_float_of_bits(uint32_t b)
 {
@@ -154,61 +147,6 @@ template <typename TI, bool FLT> DEV int rgb_value(int raw, int vmax)
     else return rgb_unit_to_16(rgb_float_of_bits((uint32_t)raw));
 }
 
-// ---- loads
-template <typename TI> DEV int rgb_element(const TI *p)
-{
-    MIHEVC_INGEST_RGB_ACCESS(p, sizeof(TI));
-    const int v = (int)*p;
-    ingest_keep_apart();
-    return v;
-}
-// N elements from p in chunks of CB bytes (p is CB-aligned)
-template <typename TI, int N, int CB> DEV void rgb_load_chunks(const TI *p, int (&v)[N])
-{
-    constexpr int per = CB / (int)sizeof(TI);
-#pragma unroll
-    for (int c = 0; c < N / per; c++) {
-        uint32_t w[CB / 4];
-        MIHEVC_INGEST_RGB_ACCESS(p + c * per, CB);
-        ingest_chunk<CB>(p + c * per, w);
-        if constexpr (CB < 16) ingest_keep_apart();
-#pragma unroll
-        for (int k = 0; k < per; k++) {
-            if constexpr (sizeof(TI) == 1) v[c * per + k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
-            else if constexpr (sizeof(TI) == 2) v[c * per + k] = (int)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-            else v[c * per + k] = (int)w[k];
-        }
-    }
-}
-// N elements of one row (N elements are a multiple of 16 bytes, and so is the offset of p in its row); al: IngestRgbArgs::align
-template <typename TI, int N> DEV void rgb_load(const TI *p, int al, int (&v)[N])
-{
-    static_assert(N * sizeof(TI) % 16 == 0, "a block of a row is a whole number of 16-byte chunks");
-    if (al >= 16) { rgb_load_chunks<TI, N, 16>(p, v); return; }
-    if (al >= 8) { rgb_load_chunks<TI, N, 8>(p, v); return; }
-    if (al >= 4) { rgb_load_chunks<TI, N, 4>(p, v); return; }
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = rgb_element(p + k);
-}
-
-// ING_RUN samples (`full`), or the first half of them, to p: one vector store either way
-DEV void rgb_store(uint8_t *p, const int (&o)[ING_RUN], bool full)
-{
-    const uint32_t w0 = (uint32_t)o[0] | (uint32_t)o[1] << 8 | (uint32_t)o[2] << 16 | (uint32_t)o[3] << 24;
-    const uint32_t w1 = (uint32_t)o[4] | (uint32_t)o[5] << 8 | (uint32_t)o[6] << 16 | (uint32_t)o[7] << 24;
-    MIHEVC_INGEST_RGB_ACCESS(p, full ? 8 : 4);
-    if (full) *(ingest_u32x2 *)__builtin_assume_aligned(p, 8) = ingest_u32x2{w0, w1};
-    else store_u32_aligned(p, w0);
-}
-DEV void rgb_store(uint16_t *p, const int (&o)[ING_RUN], bool full)
-{
-    const uint32_t w0 = (uint32_t)o[0] | (uint32_t)o[1] << 16, w1 = (uint32_t)o[2] | (uint32_t)o[3] << 16;
-    const uint32_t w2 = (uint32_t)o[4] | (uint32_t)o[5] << 16, w3 = (uint32_t)o[6] | (uint32_t)o[7] << 16;
-    MIHEVC_INGEST_RGB_ACCESS(p, full ? 16 : 8);
-    if (full) *(ingest_u32x4 *)__builtin_assume_aligned(p, 16) = ingest_u32x4{w0, w1, w2, w3};
-    else *(ingest_u32x2 *)__builtin_assume_aligned(p, 8) = ingest_u32x2{w0, w1};
-}
-
 // ---- one pixel
 struct RgbT { int64_t y, cb, cr; };
 // E values of a pixel's planes / elements -> t[0 .. 2]
@@ -229,7 +167,10 @@ template <typename TI, bool FLT, int EPP> DEV RgbT rgb_pixel_at(const IngestRgbA
     constexpr int E = EPP == 1 ? 3 : EPP;
     int e[E];
 #pragma unroll
-    for (int k = 0; k < E; k++) e[k] = rgb_value<TI, FLT>(rgb_element(EPP == 1 ? row[k] + x : row[0] + (ptrdiff_t)x * EPP + k), a.vmax);
+    for (int k = 0; k < E; k++) {
+        ingest_element(EPP == 1 ? row[k] + x : row[0] + (ptrdiff_t)x * EPP + k, e[k]);
+        e[k] = rgb_value<TI, FLT>(e[k], a.vmax);
+    }
     return rgb_matrix<E>(a, e);
 }
 DEV int rgb_luma(const IngestRgbArgs &a, int64_t t) { return imax(imin((int)((t + ((int64_t)1 << (a.S - 1))) >> a.S) + a.oY, a.peak), 0); }
@@ -247,7 +188,8 @@ template <typename TI, bool FLT, int EPP> DEV void rgb_row(const IngestRgbArgs &
         int v[EPP == 1 ? 3 : 1][RGB_BW * EPP];
 #pragma unroll
         for (int c = 0; c < (EPP == 1 ? 3 : 1); c++) {
-            rgb_load<TI, RGB_BW * EPP>(row[c] + (ptrdiff_t)x0 * EPP, a.align, v[c]);
+            static_assert(RGB_BW * EPP * sizeof(TI) % 16 == 0, "a block of a row is a whole number of 16-byte chunks");
+            ingest_load<TI, RGB_BW * EPP>(row[c] + (ptrdiff_t)x0 * EPP, a.align, v[c]);
 #pragma unroll
             for (int i = 0; i < RGB_BW * EPP; i++) v[c][i] = rgb_value<TI, FLT>(v[c][i], a.vmax);
         }
@@ -301,11 +243,11 @@ template <typename TI, bool FLT, typename TO, int EPP> DEV void rgb_block(const 
         int o[ING_RUN];
 #pragma unroll
         for (int k = 0; k < ING_RUN; k++) o[k] = Y[k];
-        rgb_store(p, o, true);
+        ingest_store(p, o, true);
         if (!wide) return;
 #pragma unroll
         for (int k = 0; k < ING_RUN; k++) o[k] = Y[ING_RUN + k];
-        rgb_store(p + ING_RUN, o, true);
+        ingest_store(p + ING_RUN, o, true);
     };
 #pragma unroll 1
     for (int r = 0; r < 2; r++) {
@@ -319,7 +261,7 @@ template <typename TI, bool FLT, typename TO, int EPP> DEV void rgb_block(const 
         int o[ING_RUN];
 #pragma unroll
         for (int k = 0; k < ING_RUN; k++) o[k] = rgb_chroma(a, T[c][k]);
-        rgb_store((TO *)a.dst[1 + c] + (ptrdiff_t)j * a.dstride[1 + c] + x0 / 2, o, wide);
+        ingest_store((TO *)a.dst[1 + c] + (ptrdiff_t)j * a.dstride[1 + c] + x0 / 2, o, wide);
     }
 }
 

@@ -1332,6 +1332,49 @@ static int enqueue_source(mihevc_session *s, mihevc_session::Src &&src, int64_t 
     return MIHEVC_OK;
 }
 
+// the planes a source picture is written to: a set the last chunk gave back, or new ones (a failure midway: `src` gives back the planes it had taken)
+static int take_src(mihevc_session *s, mihevc_session::Src &src)
+{
+    if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
+    else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;
+    src.borrowed = false;
+    return MIHEVC_OK;
+}
+
+// Uploads and conversions run on st_pre; the chunk's first launch waits for the event behind the last one.  wait: the synchronous entry points of host planes
+// wait here (the caller may reuse its buffers on return), the others return with the work in flight
+static int finish_ingest(mihevc_session *s, mihevc_session::Src &&src, int64_t pts, bool wait)
+{
+    if (wait) HIPCK(s, hipStreamSynchronize(s->st_pre));
+    else s->up_pending = true;
+    return enqueue_source(s, std::move(src), pts);
+}
+
+// a plane of a source on its way to a converter: row and pitch in elements
+struct SrcPlane { const void *p; int row, rows, pitch; };
+// Host planes go through the staging set: laid out one behind the other with rows that begin 16-byte aligned (the kernels' widest loads), copied on st_pre;
+// p and pitch of every plane then name its copy.  Device planes stay where they are
+static int stage_planes(mihevc_session *s, SrcPlane *pl, int n, size_t es, bool device_src)
+{
+    if (device_src) return MIHEVC_OK;
+    size_t off[3], total = 0;
+    int spitch[3];
+    for (int c = 0; c < n; c++) {
+        spitch[c] = (pl[c].row + 15) & ~15;
+        off[c] = total;
+        total += ((size_t)spitch[c] * pl[c].rows * es + 255) & ~(size_t)255;
+    }
+    if (total > s->stage.bytes()) {
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // a conversion still reading the smaller set
+        HIPCK(s, s->stage.alloc(s->device, total, false));
+    }
+    for (int c = 0; c < n; c++) {
+        HIPCK(s, hipMemcpy2DAsync(s->stage + off[c], spitch[c] * es, pl[c].p, pl[c].pitch * es, pl[c].row * es, pl[c].rows, hipMemcpyHostToDevice, s->st_pre));
+        pl[c].p = s->stage + off[c]; pl[c].pitch = spitch[c];
+    }
+    return MIHEVC_OK;
+}
+
 // may_borrow: device planes that need no margin may be coded where they are (the rule of mihevc_send_frame_device: valid until the packet is out); false: always copied,
 // so the caller's planes are free once the uploads are through (the rule of mihevc_send_frame_fmt)
 static int ingest(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async, bool may_borrow = true)
@@ -1350,97 +1393,52 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
         ((uintptr_t)y & 3) == 0 && ((uintptr_t)u & 3) == 0 && ((uintptr_t)v & 3) == 0 && (pitch_y * es) % 4 == 0 && (pitch_c * es) % 4 == 0) {
         for (int i = 0; i < 3; i++) { src.p[i] = const_cast<void *>(in[i]); src.stride[i] = i ? pitch_c : pitch_y; }
         src.borrowed = true;
-    } else {
-        if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
-        else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;      // (a failure midway: `src` gives back the planes it had taken)
-        src.borrowed = false;
-        // uploads run on a stream of their own; the chunk's first launch waits for the event behind the last one.  The synchronous entry point waits
-        // here (the caller may reuse its buffers on return), the asynchronous one returns with the copies in flight
-        for (int i = 0; i < 3; i++) {
-            int pw = i ? s->w / 2 : s->w, ph = i ? s->h / 2 : s->h;               // coded plane size
-            int sw = i ? s->cfg.width / 2 : s->cfg.width, sh = i ? s->cfg.height / 2 : s->cfg.height, pitch = i ? pitch_c : pitch_y;
-            if (pitch < sw) return MIHEVC_EINVAL;
-            HIPCK(s, hipMemcpy2DAsync(src.p[i], src.stride[i] * es, in[i], pitch * es, sw * es, sh, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
-            // replicate the last column/row into the coded-size margin (the conformance window crops it again)
-            if (pw > sw || ph > sh) {
-                if (s->is16) HIPCK(s, launch_extend_margin<uint16_t>(s->st_pre, Plane<uint16_t>{(uint16_t *)src.p[i], src.stride[i]}, sw, sh, pw, ph));
-                else HIPCK(s, launch_extend_margin<uint8_t>(s->st_pre, Plane<uint8_t>{(uint8_t *)src.p[i], src.stride[i]}, sw, sh, pw, ph));
-            }
-        }
-        if (!device_src && !async) HIPCK(s, hipStreamSynchronize(s->st_pre));     // caller's buffers may be reused on return
-        else s->up_pending = true;
+        return enqueue_source(s, std::move(src), pts);
     }
-    return enqueue_source(s, std::move(src), pts);
+    if (int e = take_src(s, src)) return e;
+    for (int i = 0; i < 3; i++) {
+        int pw = i ? s->w / 2 : s->w, ph = i ? s->h / 2 : s->h;               // coded plane size
+        int sw = i ? s->cfg.width / 2 : s->cfg.width, sh = i ? s->cfg.height / 2 : s->cfg.height, pitch = i ? pitch_c : pitch_y;
+        if (pitch < sw) return MIHEVC_EINVAL;
+        HIPCK(s, hipMemcpy2DAsync(src.p[i], src.stride[i] * es, in[i], pitch * es, sw * es, sh, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
+        // replicate the last column/row into the coded-size margin (the conformance window crops it again)
+        if (pw > sw || ph > sh) {
+            if (s->is16) HIPCK(s, launch_extend_margin<uint16_t>(s->st_pre, Plane<uint16_t>{(uint16_t *)src.p[i], src.stride[i]}, sw, sh, pw, ph));
+            else HIPCK(s, launch_extend_margin<uint8_t>(s->st_pre, Plane<uint8_t>{(uint8_t *)src.p[i], src.stride[i]}, sw, sh, pw, ph));
+        }
+    }
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
 // A source in another layout (mihevc_send_frame_fmt; the arguments are checked): k_ingest writes the session's own planes, margin included, from the
-// caller's device planes or from the staging set the host planes are copied into
+// caller's device planes or from their copies in the staging set
 static int ingest_fmt(mihevc_session *s, const mihevc_src_format &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
 {
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     mihevc_session::Src src;
-    if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
-    else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;
-    src.borrowed = false;
+    if (int e = take_src(s, src)) return e;
     const size_t es = f.bit_depth > 8 ? 2 : 1;
-    const int W = s->cfg.width, H = s->cfg.height, n_planes = f.semi_planar ? 2 : 3;
-    const void *in[3] = {y, u, f.semi_planar ? nullptr : v};
-    int pitch[3] = {pitch_y, pitch_c, pitch_c};
-    if (!device_src) {
-        size_t off[3], total = 0;
-        int spitch[3];
-        for (int c = 0; c < n_planes; c++) {
-            const int row = c ? src_chroma_row(f, W) : W, rows = c ? src_chroma_rows(f, H) : H;
-            spitch[c] = (row + 15) & ~15;          // rows begin 16-byte aligned: the kernel's widest loads
-            off[c] = total;
-            total += ((size_t)spitch[c] * rows * es + 255) & ~(size_t)255;
-        }
-        if (total > s->stage.bytes()) {
-            HIPCK(s, hipStreamSynchronize(s->st_pre));      // a conversion still reading the smaller set
-            HIPCK(s, s->stage.alloc(s->device, total, false));
-        }
-        for (int c = 0; c < n_planes; c++) {
-            const int row = c ? src_chroma_row(f, W) : W, rows = c ? src_chroma_rows(f, H) : H;
-            HIPCK(s, hipMemcpy2DAsync(s->stage + off[c], spitch[c] * es, in[c], pitch[c] * es, row * es, rows, hipMemcpyHostToDevice, s->st_pre));
-            in[c] = s->stage + off[c]; pitch[c] = spitch[c];
-        }
-    }
-    const IngestArgs a = ingest_args(f, in[0], in[1], in[2], pitch[0], pitch[1], W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
+    const int W = s->cfg.width, H = s->cfg.height, crow = src_chroma_row(f, W), crows = src_chroma_rows(f, H);
+    SrcPlane pl[3] = {{y, W, H, pitch_y}, {u, crow, crows, pitch_c}, {v, crow, crows, pitch_c}};
+    if (int e = stage_planes(s, pl, f.semi_planar ? 2 : 3, es, device_src)) return e;
+    const IngestArgs a = ingest_args(f, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
     HIPCK(s, launch_ingest(s->st_pre, a, es == 2, s->is16));
-    if (!device_src && !async) HIPCK(s, hipStreamSynchronize(s->st_pre));     // caller's buffers may be reused on return
-    else s->up_pending = true;
-    return enqueue_source(s, std::move(src), pts);
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
-// An RGB source (mihevc_send_frame_rgb; the arguments are checked, matrix and range resolved): as ingest_fmt, with k_ingest_rgb and the same staging set
+// An RGB source (mihevc_send_frame_rgb; the arguments are checked, matrix and range resolved): as ingest_fmt, with k_ingest_rgb
 static int ingest_rgb(mihevc_session *s, const mihevc_rgb_format &f, int matrix, bool full, const void *const *p, int pitch, int64_t pts, bool device_src, bool async)
 {
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     mihevc_session::Src src;
-    if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
-    else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;
-    src.borrowed = false;
+    if (int e = take_src(s, src)) return e;
     const size_t es = (size_t)rgb_elem_size(f);
-    const int W = s->cfg.width, H = s->cfg.height, n_planes = rgb_planes(f), row = rgb_row_elems(f, W);
-    const void *in[3] = {p[0], p[1], p[2]};
-    if (!device_src) {
-        const int spitch = (row + 15) & ~15;           // rows begin 16-byte aligned: the kernel's widest loads
-        const size_t plane = ((size_t)spitch * H * es + 255) & ~(size_t)255, total = plane * n_planes;
-        if (total > s->stage.bytes()) {
-            HIPCK(s, hipStreamSynchronize(s->st_pre));      // a conversion still reading the smaller set
-            HIPCK(s, s->stage.alloc(s->device, total, false));
-        }
-        for (int c = 0; c < n_planes; c++) {
-            HIPCK(s, hipMemcpy2DAsync(s->stage + plane * c, spitch * es, in[c], pitch * es, row * es, H, hipMemcpyHostToDevice, s->st_pre));
-            in[c] = s->stage + plane * c;
-        }
-        pitch = spitch;
-    }
-    const IngestRgbArgs a = ingest_rgb_args(f, matrix, full, in[0], in[1], in[2], pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
+    const int W = s->cfg.width, H = s->cfg.height, row = rgb_row_elems(f, W);
+    SrcPlane pl[3] = {{p[0], row, H, pitch}, {p[1], row, H, pitch}, {p[2], row, H, pitch}};
+    if (int e = stage_planes(s, pl, rgb_planes(f), es, device_src)) return e;
+    const IngestRgbArgs a = ingest_rgb_args(f, matrix, full, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
     HIPCK(s, launch_ingest_rgb(s->st_pre, a, f.sample, (int)es, s->is16));
-    if (!device_src && !async) HIPCK(s, hipStreamSynchronize(s->st_pre));     // caller's buffers may be reused on return
-    else s->up_pending = true;
-    return enqueue_source(s, std::move(src), pts);
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
 int mihevc_send_frame(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
@@ -1462,29 +1460,31 @@ int mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, co
         if (int e = ingest(s, y[i], u[i], v[i], pitch_y, pitch_c, first_pts + i, true, false)) return e;
     return MIHEVC_OK;
 }
+// What the converting entries refuse, in the order in which the errors win.  args_ok: the entry's own checks of its arguments
+static int refuse_source(const mihevc_session *s, bool args_ok, int flags)
+{
+    if (!args_ok || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
+    if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
+    if (s->failed) return s->fail_code;
+    return s->flushed ? MIHEVC_ESTATE : MIHEVC_OK;
+}
 int mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {
-    if (!s || !src_format_ok(fmt) || !y || !u || (!v && !fmt->semi_planar) || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
-    if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
-    if (pitch_y < s->cfg.width || pitch_c < src_chroma_row(*fmt, s->cfg.width)) return MIHEVC_EINVAL;
+    const bool args_ok = s && src_format_ok(fmt) && y && u && (v || fmt->semi_planar) && pitch_y >= s->cfg.width && pitch_c >= src_chroma_row(*fmt, s->cfg.width);
+    if (int e = refuse_source(s, args_ok, flags)) return e;
     const bool device_src = (flags & MIHEVC_SRC_DEVICE) != 0, async = (flags & MIHEVC_SRC_ASYNC) != 0;
     // the session's own layout: the existing route, copy and margin fill.  Device planes are copied too, never borrowed: this entry point lets the caller have
     // them back after mihevc_sync_uploads, whatever the format
     if (fmt->chroma == 420 && !fmt->semi_planar && fmt->bit_depth == s->cfg.bit_depth && !fmt->msb_aligned)
         return ingest(s, y, u, v, pitch_y, pitch_c, pts, device_src, async, false);
-    if (s->failed) return s->fail_code;
-    if (s->flushed) return MIHEVC_ESTATE;
     return ingest_fmt(s, *fmt, y, u, v, pitch_y, pitch_c, pts, device_src, async);
 }
 int mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2, int pitch, int64_t pts, int flags)
 {
-    if (!s || !rgb_format_ok(fmt) || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
-    const int matrix = fmt->matrix ? fmt->matrix : s->cfg.matrix;
     const void *p[3] = {p0, p1, p2};
-    if (!rgb_matrix_ok(matrix) || !rgb_planes_ok(*fmt, p, pitch, s->cfg.width)) return MIHEVC_EINVAL;
-    if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
-    if (s->failed) return s->fail_code;
-    if (s->flushed) return MIHEVC_ESTATE;
+    const bool fmt_ok = s && rgb_format_ok(fmt);
+    const int matrix = !fmt_ok ? 0 : fmt->matrix ? fmt->matrix : s->cfg.matrix;
+    if (int e = refuse_source(s, fmt_ok && rgb_matrix_ok(matrix) && rgb_planes_ok(*fmt, p, pitch, s->cfg.width), flags)) return e;
     const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
     return ingest_rgb(s, *fmt, matrix, full, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
 }

@@ -153,6 +153,26 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_async(self._s, y.ctypes.data, u.ctypes.data, v.ctypes.data, y.shape[1], u.shape[1], pts), "send_frame_async")
 
+    @staticmethod
+    def _source_planes(fmt, planes, dt, es, floats, asynchronous, who):
+        """The planes of a source in the format `fmt` -> (pointers, pitches in elements, flags).  numpy planes: of the dtype `dt` and C-contiguous when `asynchronous` (no
+        copy is made), else of its element size `es` and made so here; otherwise torch tensors on the device, read where they are.  floats: whether the samples
+        are floats, which the planes must match; None: only the element size counts.  who: the caller, for the messages."""
+        flags = _lib.SRC_ASYNC if asynchronous else 0
+        if all(isinstance(p, np.ndarray) for p in planes):
+            if asynchronous:
+                if any(p.dtype != dt or not p.flags.c_contiguous for p in planes):
+                    raise ValueError(f"an asynchronous {who} needs C-contiguous planes of the format's element type")
+            elif any(p.dtype.itemsize != es or (floats is not None and (p.dtype.kind == "f") != floats) for p in planes):
+                raise ValueError(f"{[str(p.dtype) for p in planes]} planes handed over as {fmt!r}")
+            else:
+                planes = [np.ascontiguousarray(p, dtype=dt) for p in planes]      # (same size and kind: the bits stay)
+            return [p.ctypes.data for p in planes], [p.shape[1] for p in planes], flags
+        if any(isinstance(p, np.ndarray) or not p.is_cuda or p.element_size() != es or (floats is not None and p.is_floating_point() != floats) or p.stride(1) != 1
+               for p in planes):
+            raise ValueError(f"device planes must be tensors on the GPU of the format's element {'size' if floats is None else 'type'} with unit column stride")
+        return [p.data_ptr() for p in planes], [p.stride(0) for p in planes], flags | _lib.SRC_DEVICE
+
     def send_fmt(self, fmt: _lib.SrcFormat, y, u, v, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_fmt: a picture of the session's display size in another sample layout (4:2:2 / 4:4:4, semi-planar, 8 .. 16 bit), converted on
         the device.  numpy planes (uint8 at 8 bit, else uint16; a semi-planar source: `u` is the interleaved (rows, 2 x chroma width) plane and `v` is None)
@@ -165,22 +185,8 @@ class Encoder:
         shapes = [(c.height, c.width)] + [(rows, row)] * (len(planes) - 1)
         if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
             raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {fmt!r} at {c.width}x{c.height}")
-        flags = _lib.SRC_ASYNC if asynchronous else 0
-        if all(isinstance(p, np.ndarray) for p in planes):
-            dt = np.uint8 if fmt.bit_depth == 8 else np.uint16
-            if asynchronous:
-                if any(p.dtype != dt or not p.flags.c_contiguous for p in planes):
-                    raise ValueError("an asynchronous send_fmt needs C-contiguous planes of the format's element type")
-            elif any(p.dtype.itemsize != np.dtype(dt).itemsize for p in planes):
-                raise ValueError(f"{[str(p.dtype) for p in planes]} planes handed over as {fmt!r}")
-            else:
-                planes = [np.ascontiguousarray(p, dtype=dt) for p in planes]
-            ptrs, pitches = [p.ctypes.data for p in planes], [p.shape[1] for p in planes]
-        else:       # torch tensors on the device
-            es = 1 if fmt.bit_depth == 8 else 2
-            if any(not p.is_cuda or p.element_size() != es or p.stride(1) != 1 for p in planes):
-                raise ValueError("device planes must be tensors on the GPU of the format's element size with unit column stride")
-            ptrs, pitches, flags = [p.data_ptr() for p in planes], [p.stride(0) for p in planes], flags | _lib.SRC_DEVICE
+        es = 1 if fmt.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(fmt, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_fmt")
         if len(planes) == 3 and pitches[1] != pitches[2]:
             raise ValueError("the two chroma planes must share one pitch")
         pts = self._pts if pts is None else pts
@@ -201,22 +207,9 @@ class Encoder:
                 planes[0] = planes[0].reshape(c.height, c.width * fmt.layout)
         if len(planes) != len(shapes) or any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
             raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {fmt!r} at {c.width}x{c.height}")
-        flags = _lib.SRC_ASYNC if asynchronous else 0
         es = fmt.element_size
-        if all(isinstance(p, np.ndarray) for p in planes):
-            dt = np.dtype({1: np.float16, 2: np.float32}[fmt.sample]) if fmt.sample else np.dtype(np.uint8 if es == 1 else np.uint16)
-            if asynchronous:
-                if any(p.dtype != dt or not p.flags.c_contiguous for p in planes):
-                    raise ValueError("an asynchronous send_rgb needs C-contiguous planes of the format's element type")
-            elif any(p.dtype.itemsize != es or (p.dtype.kind == "f") != bool(fmt.sample) for p in planes):
-                raise ValueError(f"{[str(p.dtype) for p in planes]} planes handed over as {fmt!r}")
-            else:
-                planes = [np.ascontiguousarray(p).view(dt) for p in planes]
-            ptrs, pitches = [p.ctypes.data for p in planes], [p.shape[1] for p in planes]
-        else:       # torch tensors on the device
-            if any(isinstance(p, np.ndarray) or not p.is_cuda or p.element_size() != es or p.is_floating_point() != bool(fmt.sample) or p.stride(1) != 1 for p in planes):
-                raise ValueError("device planes must be tensors on the GPU of the format's element type with unit column stride")
-            ptrs, pitches, flags = [p.data_ptr() for p in planes], [p.stride(0) for p in planes], flags | _lib.SRC_DEVICE
+        dt = np.dtype({1: np.float16, 2: np.float32}[fmt.sample]) if fmt.sample else np.dtype(np.uint8 if es == 1 else np.uint16)
+        ptrs, pitches, flags = self._source_planes(fmt, planes, dt, es, bool(fmt.sample), asynchronous, "send_rgb")
         if len(set(pitches)) != 1:
             raise ValueError("the three planes must share one pitch")
         pts = self._pts if pts is None else pts

@@ -4,69 +4,31 @@
 // tests/test_ingest_rgb_cpu.py builds from this file and tests/ingest_rgb_asan_main.cc), with a pitch wider than the row and the alignment the case asks for;
 // the output planes are filled with a garbage pattern first, and the samples between the coded width and the stride must still hold it afterwards.
 // hevc_amd/ never loads this library.
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-
-// the kernel header's access hook: loads and stores whose address is not a multiple of their width
-static int g_rgb_misaligned = 0;
-#define MIHEVC_INGEST_RGB_ACCESS(p, bytes) ((void)(g_rgb_misaligned += ((uintptr_t)(p) % (unsigned)(bytes)) != 0))
+#include "ingest_planes.h"
 #include "../../hevc_amd/csrc/kernels/ingest_rgb.h"
 
 using namespace mihevc;
 
 namespace {
 
-// align: 16, 8, 4: the source planes' base address and pitch are multiples of it and of nothing larger; 1: base one element off, odd pitch
+// align: the alignment class of the source planes (IngestSrcPlane)
 template <typename TI, bool FLT, typename TO>
 int run(const mihevc_rgb_format &f, const void *const *src, int w, int h, int out_depth, int order, int align, void *const *out, int *stats)
 {
-    const int pw = (w + 7) & ~7, ph = (h + 7) & ~7, planes = rgb_planes(f), row = rgb_row_elems(f, w);
-    void *sbase[3] = {nullptr, nullptr, nullptr};
-    const void *sp[3] = {nullptr, nullptr, nullptr};
-    const int unit = align > (int)sizeof(TI) ? align / (int)sizeof(TI) : 1;                 // elements
-    int pitch = ((row + unit - 1) / unit + 1) * unit;
-    if (align < 16 && (pitch / unit) % 2 == 0) pitch += unit;                               // an odd multiple: not a multiple of the next power of two
-    const size_t off = align == 16 ? 0 : align == 1 ? sizeof(TI) : (size_t)align;           // bytes from a 64-byte boundary
-    const size_t bytes = ((size_t)pitch * (h - 1) + row) * sizeof(TI);
-    for (int c = 0; c < planes; c++) {
-        if (posix_memalign(&sbase[c], 64, off + bytes)) return -5;                          // ends with the last sample of the last row
-        memset(sbase[c], 0x5A, off + bytes);
-        TI *p = (TI *)((uint8_t *)sbase[c] + off);
-        for (int r = 0; r < h; r++) memcpy(p + (size_t)r * pitch, (const TI *)src[c] + (size_t)r * row, (size_t)row * sizeof(TI));
-        sp[c] = p;
-    }
-    constexpr TO kGarbage = (TO)0xA5A5;
-    TO *op[3];
-    void *obase[3];
-    int ostride[3];
-    for (int c = 0; c < 3; c++) {
-        const int pwo = c ? pw / 2 : pw, pho = c ? ph / 2 : ph;
-        ostride[c] = ((pwo + 15) & ~15) + 16;
-        obase[c] = aligned_alloc(64, ((size_t)ostride[c] * pho * sizeof(TO) + 63) & ~(size_t)63);
-        op[c] = (TO *)obase[c];
-        for (size_t i = 0; i < (size_t)ostride[c] * pho; i++) op[c][i] = kGarbage;
-    }
-    void *dst[3] = {op[0], op[1], op[2]};
-    const IngestRgbArgs a = ingest_rgb_args(f, f.matrix, f.range == 2, sp[0], sp[1], sp[2], pitch, w, h, pw, ph, out_depth, dst, ostride);
+    const int pw = (w + 7) & ~7, ph = (h + 7) & ~7;
+    IngestSrcPlane<TI> sp[3];
+    for (int c = 0; c < rgb_planes(f); c++)
+        if (!sp[c].place(src[c], rgb_row_elems(f, w), h, align)) return -5;
+    IngestOutPlanes<TO> op(pw, ph);
+    const IngestRgbArgs a = ingest_rgb_args(f, f.matrix, f.range == 2, sp[0].p, sp[1].p, sp[2].p, sp[0].pitch, w, h, pw, ph, out_depth, op.dst, op.stride);
     stats[2] = a.align;
     SeqExec ex;
     ex.order = order;
-    g_rgb_misaligned = 0;
+    g_ingest_misaligned = 0;
     const int nwg = ingest_rgb_workgroups(pw, ph);
     for (int wg = 0; wg <= nwg; wg++) ingest_rgb_tile_program<TI, FLT, TO>(ex, a, wg);     // one past the last: writes nothing
-    stats[0] = g_rgb_misaligned;
-    int spilled = 0;
-    for (int c = 0; c < 3; c++) {
-        const int pwo = c ? pw / 2 : pw, pho = c ? ph / 2 : ph;
-        for (int r = 0; r < pho; r++) {
-            memcpy((TO *)out[c] + (size_t)r * pwo, op[c] + (size_t)r * ostride[c], (size_t)pwo * sizeof(TO));
-            for (int x = pwo; x < ostride[c]; x++) spilled += op[c][(size_t)r * ostride[c] + x] != kGarbage;
-        }
-        free(obase[c]);
-        free(sbase[c]);
-    }
-    stats[1] = spilled;
+    stats[0] = g_ingest_misaligned;
+    stats[1] = op.copy_back(out);
     return 0;
 }
 
@@ -96,7 +58,7 @@ int emu_ingest_rgb_matrix(int matrix, int full, int bits, int out_depth, int *m,
 }
 
 // fmt: a mihevc_rgb_format with matrix and range explicit; p0 .. p2: tight source planes (pitch = row; packed: p0 only); w x h: display size; out_*: tight planes
-// of the coded size, uint8 at out_depth 8, uint16 at 10; order: SeqExec thread order; align: 16 / 8 / 4 / 1 (see run).  stats[0]: misaligned accesses (must
+// of the coded size, uint8 at out_depth 8, uint16 at 10; order: SeqExec thread order; align: 16 / 8 / 4 / 1 (IngestSrcPlane).  stats[0]: misaligned accesses (must
 // be 0), stats[1]: samples written outside the coded width (must be 0), stats[2]: the alignment class the kernel ran with.  Returns 0, or -3
 int emu_ingest_rgb(const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2, int w, int h, int out_depth, int order, int align, void *out_y,
                    void *out_u, void *out_v, int *stats)

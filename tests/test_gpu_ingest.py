@@ -9,7 +9,8 @@ import pytest
 
 from tests import ingest_ref as R
 from tests import util
-from tests.test_ingest_cpu import COMBOS, combo_id, same_planes, src_format
+from tests.ingest_common import H, N, W, alignment_class, base_cfg, device_planes, drain, same_planes, view_of_class
+from tests.test_ingest_cpu import COMBOS, combo_id, src_format
 
 pytestmark = pytest.mark.gpu
 
@@ -50,23 +51,16 @@ def test_stage_equals_model_at_1080p(lib, name, depth):
     assert not diff, diff
 
 
+@pytest.mark.parametrize("cls", [1, 4, 8])
 @pytest.mark.parametrize("f,depth", [(R.Format(444, 0, 8, 0), 8), (R.Format(444, 1, 16, 1), 10)], ids=["u8", "u16"])
-def test_stage_with_misaligned_planes(lib, f, depth):
-    """the planes start one element into a buffer and their pitch is odd: the element-wise path on the device"""
+def test_stage_with_misaligned_planes(lib, f, depth, cls):
+    """the planes' addresses and pitches allow chunks of `cls` bytes and no wider: the element-wise (1), 4-byte and 8-byte paths on the device"""
     w, h = 70, 38
     src = R.random_source(f, w, h, 9)
-    wide, views = [], []
-    for p in src:
-        if p is None:
-            views.append(None)
-            continue
-        pitch = (p.shape[1] + 2) | 1
-        buf = np.zeros(1 + pitch * p.shape[0], p.dtype)
-        v = np.lib.stride_tricks.as_strided(buf[1:], p.shape, (pitch * p.itemsize, p.itemsize))
-        v[...] = p
-        wide.append(buf)
-        views.append(v)
-    assert views[0].ctypes.data % 16 and (views[1].strides[0] // views[1].itemsize) % 2
+    views = [None if p is None else view_of_class(p, cls) for p in src]
+    assert all(alignment_class(v.ctypes.data) == alignment_class(v.strides[0]) == cls for v in views if v is not None)
+    if cls == 1:
+        assert views[0].ctypes.data % 16 and (views[1].strides[0] // views[1].itemsize) % 2
     pitches = (views[0].strides[0] // views[0].itemsize, views[1].strides[0] // views[1].itemsize)
     if not f.semi_planar:
         assert views[2].strides == views[1].strides
@@ -75,16 +69,7 @@ def test_stage_with_misaligned_planes(lib, f, depth):
 
 
 # ------------------------------------------------------------------------------------------------ 2. sessions
-W, H, N = 100, 70, 5
 SESSION_FORMATS = {"yuv422p10le": 10, "nv12": 8, "yuv444p12le": 10}
-
-
-def base_cfg(depth):
-    from hevc_amd import _lib
-    cfg = _lib.default_config()
-    cfg.width, cfg.height, cfg.bit_depth, cfg.keyint, cfg.min_keyint, cfg.scenecut, cfg.qp, cfg.me_range, cfg.gops_in_flight = W, H, depth, 3, 2, 0, 28, 12, 1
-    cfg.level_idc = 93
-    return cfg
 
 
 @functools.lru_cache(maxsize=None)
@@ -108,12 +93,6 @@ def clip(name):
     return out
 
 
-def drain(enc, keep_recon=False):
-    enc.flush()
-    stream = b"".join(d for d, _, _ in enc.packets())
-    return (stream, [enc.recon(i) for i in range(N)]) if keep_recon else stream
-
-
 @functools.lru_cache(maxsize=None)
 def reference_stream(name):
     """the stream (and reconstructions) of a session fed the MODEL's 4:2:0 pictures, display size, through mihevc_send_frame"""
@@ -124,13 +103,6 @@ def reference_stream(name):
             y, u, v = R.convert(f, *src, depth)
             enc.send(y[:H, :W], u[:H // 2, :W // 2], v[:H // 2, :W // 2])
         return drain(enc, keep_recon=True)
-
-
-def device_planes(planes):
-    import torch
-    out = [None if p is None else torch.from_numpy(p.view(np.int16) if p.dtype.itemsize == 2 else p).cuda() for p in planes]
-    torch.cuda.synchronize()
-    return out
 
 
 @pytest.mark.parametrize("route", ["sync", "async", "device"])

@@ -11,7 +11,8 @@ import pytest
 
 from tests import ingest_rgb_ref as R
 from tests import util
-from tests.test_ingest_rgb_cpu import COMBOS, MATRICES, OUT_DEPTHS, combo_id, plane_ptrs, planar, rgb_format, same_planes
+from tests.ingest_common import H, N, W, alignment_class, base_cfg, device_planes, drain, same_planes, view_of_class
+from tests.test_ingest_rgb_cpu import COMBOS, MATRICES, OUT_DEPTHS, combo_id, plane_ptrs, planar, rgb_format
 
 pytestmark = pytest.mark.gpu
 
@@ -51,36 +52,24 @@ def test_stage_equals_model_at_1080p(lib, name, depth):
     assert not diff, diff
 
 
+@pytest.mark.parametrize("cls", [1, 4, 8])
 @pytest.mark.parametrize("name,depth", [("rgb24", 8), ("gbrp16le", 10)])
-def test_stage_with_misaligned_planes(lib, name, depth):
-    """the planes start one element into a buffer and their pitch is odd: the element-wise path on the device"""
+def test_stage_with_misaligned_planes(lib, name, depth, cls):
+    """the planes' addresses and pitch allow chunks of `cls` bytes and no wider: the element-wise (1), 4-byte and 8-byte paths on the device"""
     f, (w, h) = R.FORMATS[name], (70, 38)
     src = R.random_source(f, w, h, 9)
-    pitch = (src[0].shape[1] + 2) | 1
-    wide, views = [], []
-    for p in src:
-        buf = np.zeros(1 + pitch * p.shape[0], p.dtype)
-        v = np.lib.stride_tricks.as_strided(buf[1:], p.shape, (pitch * p.itemsize, p.itemsize))
-        v[...] = p
-        wide.append(buf)
-        views.append(v)
-    assert all(v.ctypes.data % 16 == v.itemsize for v in views) and pitch % 2
+    views = [view_of_class(p, cls) for p in src]
+    pitch = views[0].strides[0] // views[0].itemsize
+    assert all(alignment_class(v.ctypes.data) == alignment_class(v.strides[0]) == cls and v.strides == views[0].strides for v in views)
+    if cls == 1:
+        assert all(v.ctypes.data % 16 == v.itemsize for v in views) and pitch % 2
     diff = same_planes(k_convert(lib, f, views, w, h, 9, True, depth, pitch), R.convert(f, src, 9, True, depth))
     assert not diff, diff
 
 
 # ------------------------------------------------------------------------------------------------ 2. sessions
-W, H, N = 100, 70, 5
 # name -> (format, session depth, matrix and range of the format: 0 / None follow the session, which signals BT.709 limited)
 SESSIONS = {"bgra": (R.FORMATS["bgra"], 8, 0, None), "gbrp12le": (R.FORMATS["gbrp12le"], 10, 9, True), "f32": (planar(0, 2), 10, 0, None)}
-
-
-def base_cfg(depth):
-    from hevc_amd import _lib
-    cfg = _lib.default_config()
-    cfg.width, cfg.height, cfg.bit_depth, cfg.keyint, cfg.min_keyint, cfg.scenecut, cfg.qp, cfg.me_range, cfg.gops_in_flight = W, H, depth, 3, 2, 0, 28, 12, 1
-    cfg.level_idc = 93
-    return cfg
 
 
 @functools.lru_cache(maxsize=None)
@@ -108,12 +97,6 @@ def clip(name, w=W, h=H):
     return out
 
 
-def drain(enc, keep_recon=False):
-    enc.flush()
-    stream = b"".join(d for d, _, _ in enc.packets())
-    return (stream, [enc.recon(i) for i in range(N)]) if keep_recon else stream
-
-
 def model_planes(name, src, w=W, h=H):
     f, depth, matrix, full = SESSIONS[name]
     y, u, v = R.convert(f, src, matrix or 1, bool(full), depth)
@@ -133,13 +116,6 @@ def reference_stream(name):
 def session_format(name):
     f, _, matrix, full = SESSIONS[name]
     return rgb_format(f, matrix, full)
-
-
-def device_planes(planes):
-    import torch
-    out = [torch.from_numpy(p.view(np.int16) if p.dtype.kind == "u" and p.dtype.itemsize == 2 else p).cuda() for p in planes]
-    torch.cuda.synchronize()
-    return out
 
 
 @pytest.mark.parametrize("route", ["sync", "async", "device"])

@@ -11,7 +11,7 @@ import pytest
 from hevc_amd import _lib, probe, yuvio
 from tests import ingest_ref as R
 from tests import util
-from tests.test_host_robustness import FAKE_FFMPEG
+from tests.ingest_common import fake_ffmpeg, info, pix_fmt_asked, same_planes      # noqa: F401 (fake_ffmpeg: a fixture)
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -116,14 +116,6 @@ def emu_convert(emu, f, src, w, h, depth, order=0, align=16):
     assert stats[0] == 0, f"{stats[0]} misaligned chunk accesses"
     assert stats[1] == 0, f"{stats[1]} samples written outside the coded width"
     return out, (stats[2], stats[3])
-
-
-def same_planes(got, want):
-    for name, g, w in zip("Y Cb Cr".split(), got, want):
-        if not np.array_equal(g, w):
-            ys, xs = np.nonzero(g != w)
-            return f"{name}: {len(ys)} samples differ, first at x={xs[0]} y={ys[0]}: {g[ys[0], xs[0]]} vs {w[ys[0], xs[0]]}"
-    return ""
 
 
 def test_sizes_meet_the_tile_edges(emu):
@@ -331,27 +323,6 @@ def test_raw_yuv_names_take_chroma_and_depth_tokens(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ 7. the ffmpeg pipe front end
-@pytest.fixture
-def fake_ffmpeg(tmp_path, monkeypatch):
-    b = tmp_path / "bin"
-    b.mkdir()
-    f = b / "ffmpeg"
-    f.write_text(FAKE_FFMPEG)
-    f.chmod(0o755)
-    monkeypatch.setenv("PATH", f"{b}:/usr/bin:/bin")
-    monkeypatch.setenv("FAKE_LOG", str(tmp_path / "ffmpeg.log"))
-    return tmp_path / "ffmpeg.log"
-
-
-def info(pix, w=64, h=48, n=3):
-    return probe.VideoInfo(w, h, 30.0, "bt709", "bt709", "bt709", pix, "", "", 0, False, "eng", n, n / 30.0)
-
-
-def pix_fmt_asked(log):
-    argv = log.read_text().split("\n")[-2].split()
-    return argv[argv.index("-pix_fmt") + 1]
-
-
 def test_pipe_clip_asks_for_the_probed_format(fake_ffmpeg, tmp_path, monkeypatch):
     monkeypatch.setenv("FAKE_FRAMES", "3")
     monkeypatch.setenv("FAKE_FB", str((64 * 48 + 2 * 32 * 48) * 2))

@@ -3,6 +3,7 @@ the definition evaluated in exact rationals; the kernel program of hevc_amd/csrc
 bit, for every layout, component order, sample type and depth; the host's integer coefficients; the new entry points without a device; the ABI struct; the
 pixel format table; the ffmpeg pipe front end with a stand-in ffmpeg."""
 import ctypes as C
+import functools
 import itertools
 import math
 import subprocess
@@ -15,7 +16,8 @@ import pytest
 from hevc_amd import _lib, probe, yuvio
 from tests import ingest_rgb_ref as R
 from tests import util
-from tests.test_host_robustness import FAKE_FFMPEG
+from tests.ingest_common import fake_ffmpeg, pix_fmt_asked, same_planes      # noqa: F401 (fake_ffmpeg: a fixture)
+from tests.ingest_common import info as common_info
 
 ROOT = Path(__file__).resolve().parents[1]
 MATRICES, DEPTHS, OUT_DEPTHS = (1, 5, 6, 9), (8, 10, 12, 16), (8, 10)
@@ -200,14 +202,6 @@ def emu_convert(emu, f, src, w, h, matrix, full, depth, order=0, align=16):
     assert stats[0] == 0, f"{stats[0]} misaligned accesses"
     assert stats[1] == 0, f"{stats[1]} samples written outside the coded width"
     return out, stats[2]
-
-
-def same_planes(got, want):
-    for name, g, w in zip("Y Cb Cr".split(), got, want):
-        if not np.array_equal(g, w):
-            ys, xs = np.nonzero(g != w)
-            return f"{name}: {len(ys)} samples differ, first at x={xs[0]} y={ys[0]}: {g[ys[0], xs[0]]} vs {w[ys[0], xs[0]]}"
-    return ""
 
 
 def test_host_coefficients_equal_the_rational_ones(emu):
@@ -421,25 +415,7 @@ def test_rgb_format_for_covers_the_name_table():
 
 
 # ------------------------------------------------------------------------------------------------ 7. the ffmpeg pipe front end
-@pytest.fixture
-def fake_ffmpeg(tmp_path, monkeypatch):
-    b = tmp_path / "bin"
-    b.mkdir()
-    f = b / "ffmpeg"
-    f.write_text(FAKE_FFMPEG)
-    f.chmod(0o755)
-    monkeypatch.setenv("PATH", f"{b}:/usr/bin:/bin")
-    monkeypatch.setenv("FAKE_LOG", str(tmp_path / "ffmpeg.log"))
-    return tmp_path / "ffmpeg.log"
-
-
-def info(pix, w=64, h=48, n=3):
-    return probe.VideoInfo(w, h, 30.0, "bt709", "bt709", "gbr", pix, "", "", 0, False, "eng", n, n / 30.0)
-
-
-def pix_fmt_asked(log):
-    argv = log.read_text().split("\n")[-2].split()
-    return argv[argv.index("-pix_fmt") + 1]
+info = functools.partial(common_info, matrix="gbr")
 
 
 def test_pipe_clip_asks_for_rgb_only_when_told_to(fake_ffmpeg, tmp_path, monkeypatch):

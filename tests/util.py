@@ -160,10 +160,10 @@ def psnr(a, b, peak=255.0):
 
 def stepped_library():
     """tests/emu/libkernel_emu.so: the kernel sources stepped on the CPU (a test harness: hevc_amd/ never loads it).  Rebuilt when a harness
-    source, a kernel header, the stage argument builders, the GOP planner or the ABI header is newer than the library"""
+    source or header, a kernel header, the stage argument builders, the GOP planner or the ABI header is newer than the library"""
     so = EMU_DIR / "libkernel_emu.so"
     sources = sorted(EMU_DIR.glob("*.cpp"))
-    deps = sources + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "hevc_amd" / "csrc" / "gop_plan.h", ROOT / "include" / "mihevc.h"]
+    deps = sources + list(EMU_DIR.glob("*.h")) + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "hevc_amd" / "csrc" / "gop_plan.h", ROOT / "include" / "mihevc.h"]
     if not so.exists() or any(d.stat().st_mtime > so.stat().st_mtime for d in deps):
         tmp = so.with_name(f"libkernel_emu.{os.getpid()}.so")                  # renamed into place: a process that has the old one loaded keeps it
         try:
