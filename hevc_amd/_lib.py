@@ -82,6 +82,14 @@ def src_format_for(pix_fmt: str):
     return SrcFormat(int(m.group(1)), 0, int(m.group(2) or 8), 0)
 
 
+class ScaleSrc(C.Structure):
+    """mihevc_scale_src: size and depth of a planar 4:2:0 source handed to mihevc_send_frame_scaled / mihevc_k_scale_source"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bit_depth")] + [("reserved", C.c_int32 * 5)]
+
+    def __repr__(self):
+        return f"ScaleSrc(width={self.width}, height={self.height}, bit_depth={self.bit_depth})"
+
+
 class RgbFormat(C.Structure):
     """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
     _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
@@ -138,6 +146,7 @@ EXPORTS = (
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
     "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
+    "mihevc_send_frame_scaled", "mihevc_k_scale_source",
 )
 
 _lib = None
@@ -206,6 +215,8 @@ def load() -> C.CDLL:
     lib.mihevc_k_convert_source.argtypes = [i32, C.POINTER(SrcFormat), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.mihevc_send_frame_rgb.argtypes = [vp, C.POINTER(RgbFormat), vp, vp, vp, i32, i64, i32]
     lib.mihevc_k_convert_rgb.argtypes = [i32, C.POINTER(RgbFormat), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_send_frame_scaled.argtypes = [vp, C.POINTER(ScaleSrc), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_scale_source.argtypes = [i32, C.POINTER(ScaleSrc), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -12,6 +12,7 @@
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
 #include "kernels/pichash.h"
+#include "kernels/scale.h"
 #include "kernels/ssim.h"
 
 namespace mihevc {
@@ -72,6 +73,8 @@ template <typename T> hipError_t launch_extend_margin(hipStream_t st, Plane<T> p
 hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool out16);
 // RGB source conversion (kernels/ingest_rgb.h).  sample: mihevc_rgb_format::sample; elem_size: bytes of a source element
 hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample, int elem_size, bool out16);
+// downscaling source (kernels/scale.h): one launch writes the three coded-size planes of `a`, margins included, from a source of another size
+hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out16);
 
 // rows between the slices of one picture (csrc/slice_group.h): jobs[i] for i < n_jobs, one grid row of `blocks_per_job` workgroups each
 hipError_t launch_copy_rows(hipStream_t st, const RowCopy *d_jobs, int n_jobs, int blocks_per_job);

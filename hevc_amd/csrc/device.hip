@@ -1,6 +1,7 @@
 // hevc_amd/csrc/device.hip — __global__ entry points, launchers and the per-stage C-ABI functions (mihevc_k_*).
 #include "device.h"
 #include "md5.h"
+#include "scale_taps.h"
 #include "stage_args.h"
 
 #include <cstdio>
@@ -194,6 +195,24 @@ hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool ou
     else if (in16) hipLaunchKernelGGL((k_ingest<uint16_t, uint8_t>), grid, block, 0, st, a);
     else if (out16) hipLaunchKernelGGL((k_ingest<uint8_t, uint16_t>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_ingest<uint8_t, uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+// downscaling source (kernels/scale.h): one workgroup per tile of SC_TW x SC_TH output samples, Y, then Cb, then Cr; the argument block travels by value.
+// 40,960 bytes of LDS and 72 / 74 VGPRs: four workgroups per CU (4 waves per SIMD), which take the CU's 160 KB of LDS exactly
+template <typename TI, typename TO> __global__ __launch_bounds__(NT, 4) void k_scale(const ScaleArgs a)
+{
+    __shared__ __align__(16) ScaleShared s;
+    GpuExec ex;
+    scale_tile_program<TI, TO>(ex, s, a, (int)blockIdx.x);
+}
+hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out16)
+{
+    const dim3 grid((unsigned)scale_workgroups(a.pw, a.ph)), block(NT);
+    if (in16 && out16) hipLaunchKernelGGL((k_scale<uint16_t, uint16_t>), grid, block, 0, st, a);
+    else if (in16) hipLaunchKernelGGL((k_scale<uint16_t, uint8_t>), grid, block, 0, st, a);
+    else if (out16) hipLaunchKernelGGL((k_scale<uint8_t, uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_scale<uint8_t, uint8_t>), grid, block, 0, st, a);
     return hipGetLastError();
 }
 
@@ -963,6 +982,31 @@ int stage_convert_rgb(const mihevc_rgb_format &f, const void *const *src, int w,
     return dst.planes.download(out);
 }
 
+// the scaling kernel alone
+template <typename TO>
+int stage_scale(const mihevc_scale_src &f, const void *const *src, int pitch_y, int pitch_c, int dw, int dh, int out_depth, void *const *out)
+{
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    ScaleBlock blk;
+    if (!scale_block_build(f.width, f.height, dw, dh, SC_TH, SC_ROWS, blk)) return MIHEVC_EINVAL;
+    DevBuf din[3], dtab;
+    ConvertOut<TO> dst;
+    if (int e = dst.alloc(dw, dh)) return e;
+    const void *dsrc[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < 3; c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? f.width / 2 : f.width, c ? f.height / 2 : f.height, c ? pitch_c : pitch_y, es)) return e;
+    CK(dtab.alloc(blk.bytes.size()));
+    CK(hipMemcpy(dtab.p, blk.bytes.data(), blk.bytes.size(), hipMemcpyHostToDevice));
+    const int32_t *first[4];
+    const int16_t *coef[4];
+    for (int k = 0; k < 4; k++) { first[k] = (const int32_t *)(dtab.as<uint8_t>() + blk.first[k]); coef[k] = (const int16_t *)(dtab.as<uint8_t>() + blk.coef[k]); }
+    const ScaleArgs a = scale_args(f.bit_depth, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, f.width, f.height, dw, dh, dst.w, dst.h, out_depth, dst.p, dst.stride,
+                                   first, coef, blk.taps);
+    CK(launch_scale(0, a, es == 2, sizeof(TO) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.planes.download(out);
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -1149,6 +1193,18 @@ int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(out_bit_depth, [&](auto t) { return stage_convert_rgb<decltype(t)>(*fmt, src, width, height, pitch, out_bit_depth, out); });
+}
+
+int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int dst_width, int dst_height,
+                          int out_bit_depth, void *out_y, void *out_u, void *out_v)
+{
+    if (!scale_src_ok(src) || !y || !u || !v || !out_y || !out_u || !out_v || !convert_geometry_ok(dst_width, dst_height, out_bit_depth)) return MIHEVC_EINVAL;
+    if (!scale_geometry_ok(src->width, src->height, dst_width, dst_height) || src->width > 4 * 8192 || src->height > 4 * 4352) return MIHEVC_EINVAL;
+    if (pitch_y < src->width || pitch_c < src->width / 2) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *p[3] = {y, u, v};
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(out_bit_depth, [&](auto t) { return stage_scale<decltype(t)>(*src, p, pitch_y, pitch_c, dst_width, dst_height, out_bit_depth, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

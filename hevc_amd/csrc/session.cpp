@@ -30,6 +30,7 @@
 #include "host_pool.h"
 #include "md5.h"
 #include "ratectl.h"
+#include "scale_taps.h"
 #include "slice_group.h"
 
 using namespace mihevc;
@@ -111,6 +112,11 @@ struct mihevc_session {
     // so the next picture's copy comes behind this picture's kernel in stream order: one set serves every picture (a set per pending picture would be 12 MB
     // each for a 1080p 4:4:4 16-bit source).  It grows when a larger format arrives (st_pre is synchronised first) and goes back with the session
     CachedBlock<uint8_t> stage;
+    // mihevc_send_frame_scaled: the four coefficient tables (csrc/scale_taps.h) of the last source size, built and uploaded once per size; the host copy lives as
+    // long as the device block it is copied from on st_pre
+    CachedBlock<uint8_t> scale_tab;
+    ScaleBlock scale_host;
+    int scale_sw = 0, scale_sh = 0;
     // per lane
     // The vector moves a lane's handles when it grows; the blocks they own stay where they are, so the raw pointers in argument blocks, jobs and BandPub stay valid
     struct Lane {
@@ -1441,6 +1447,37 @@ static int ingest_rgb(mihevc_session *s, const mihevc_rgb_format &f, int matrix,
     return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
+// A source of another size (mihevc_send_frame_scaled; the arguments are checked): k_scale writes the session's own planes, margin included, from the caller's
+// device planes or from their copies in the staging set.  The tables of a new source size are built before the first device call
+static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
+{
+    const int W = s->cfg.width, H = s->cfg.height;
+    const bool fresh = s->scale_sw != f.width || s->scale_sh != f.height;
+    ScaleBlock blk;
+    if (fresh && !scale_block_build(f.width, f.height, W, H, SC_TH, SC_ROWS, blk)) return MIHEVC_EINVAL;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    if (fresh) {
+        s->scale_sw = s->scale_sh = 0;
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // a launch still reading the tables of the size before
+        HIPCK(s, s->scale_tab.alloc(s->device, blk.bytes.size(), false));
+        s->scale_host = std::move(blk);
+        HIPCK(s, hipMemcpyAsync(s->scale_tab, s->scale_host.bytes.data(), s->scale_host.bytes.size(), hipMemcpyHostToDevice, s->st_pre));
+        s->scale_sw = f.width; s->scale_sh = f.height;
+    }
+    mihevc_session::Src src;
+    if (int e = take_src(s, src)) return e;
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    SrcPlane pl[3] = {{y, f.width, f.height, pitch_y}, {u, f.width / 2, f.height / 2, pitch_c}, {v, f.width / 2, f.height / 2, pitch_c}};
+    if (int e = stage_planes(s, pl, 3, es, device_src)) return e;
+    const int32_t *first[4];
+    const int16_t *coef[4];
+    for (int k = 0; k < 4; k++) { first[k] = (const int32_t *)(s->scale_tab + s->scale_host.first[k]); coef[k] = (const int16_t *)(s->scale_tab + s->scale_host.coef[k]); }
+    const ScaleArgs a = scale_args(f.bit_depth, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, f.width, f.height, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride,
+                                   first, coef, s->scale_host.taps);
+    HIPCK(s, launch_scale(s->st_pre, a, es == 2, s->is16));
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
+}
+
 int mihevc_send_frame(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
 {
     return ingest(s, y, u, v, pitch_y, pitch_c, pts, false, false);
@@ -1487,6 +1524,13 @@ int mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const
     if (int e = refuse_source(s, fmt_ok && rgb_matrix_ok(matrix) && rgb_planes_ok(*fmt, p, pitch, s->cfg.width), flags)) return e;
     const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
     return ingest_rgb(s, *fmt, matrix, full, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+}
+int mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const bool args_ok = s && scale_src_ok(src) && y && u && v && scale_geometry_ok(src->width, src->height, s->cfg.width, s->cfg.height) &&
+                         pitch_y >= src->width && pitch_c >= src->width / 2;
+    if (int e = refuse_source(s, args_ok, flags)) return e;
+    return ingest_scaled(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
 }
 int mihevc_sync_uploads(mihevc_session *s)
 {

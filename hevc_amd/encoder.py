@@ -194,6 +194,24 @@ class Encoder:
         self._check(self._lib.mihevc_send_frame_fmt(self._s, C.byref(fmt), ptrs[0], ptrs[1], ptrs[2] if len(ptrs) == 3 else None, pitches[0], pitches[1], pts, flags),
                     "send_frame_fmt")
 
+    def send_scaled(self, width: int, height: int, y, u, v, bit_depth: Optional[int] = None, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_scaled: a planar 4:2:0 picture of width x height samples (per axis between the session's size and four times it), scaled down
+        to the session's size on the device.  bit_depth: significant bits of a source sample, 8 .. 16 (None: the session's).  numpy planes (uint8 at 8 bit,
+        else uint16) are checked for shape and type here; torch tensors on the device are read where they are (MIHEVC_SRC_DEVICE) under the rules of
+        send_fmt, and several sessions may be fed from the same tensors.  asynchronous (host planes): the rules of send_async."""
+        src = _lib.ScaleSrc(int(width), int(height), int(self.cfg.bit_depth if bit_depth is None else bit_depth))
+        planes = [y, u, v]
+        shapes = [(src.height, src.width)] + [(src.height // 2, src.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {src!r}")
+        es = 1 if src.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(src, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_scaled")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_scaled(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_scaled")
+
     def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
         Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
@@ -615,18 +633,24 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
-                devices=None, row_split: bool = False, native_rgb: bool = False) -> int:
+                devices=None, row_split: bool = False, native_rgb: bool = False, size=None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
-    probed matrix, BT.709 when that is `gbr` or unknown."""
+    probed matrix, BT.709 when that is `gbr` or unknown.  size=(w, h): the session, its level and the MP4 track take this size and every picture of the source,
+    delivered at its own size, is scaled down on the device (Encoder.send_scaled): planar 4:2:0 sources on one device only, per axis at most 4:1."""
+    import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
 
+    src_size = (int(info.width), int(info.height))
+    if size is not None:        # rate, level and track follow the coded size; the clip below is still opened at the source's own
+        src_info, info = info, copy.copy(info)
+        info.width, info.height = int(size[0]), int(size[1])
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
     sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
-    clip = yuvio.open_any(Path(file_path), info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
+    clip = yuvio.open_any(Path(file_path), info if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
     mux = None
     ok = False
     try:
@@ -639,6 +663,13 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             fmt = rgb
             if cfg.matrix not in (1, 5, 6, 9):
                 cfg.matrix = 1
+        if size is not None:
+            fmt420 = fmt is None or (rgb is None and fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned)
+            if not fmt420 or (devices and len(devices) > 1):
+                logger.error("%s: size= takes a planar 4:2:0 source on one device (%r)", Path(file_path).name, fmt)
+                return 1
+            src_size = (int(clip.width), int(clip.height))
+            src_depth = int(fmt.bit_depth) if fmt is not None else int(clip.bit_depth)
         if fmt is not None and sliced:
             logger.error("%s: a %r source cannot be split by rows", Path(file_path).name, fmt)
             return 1
@@ -682,7 +713,9 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 for i, planes in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    if fmt is None:
+                    if size is not None:
+                        enc.send_scaled(src_size[0], src_size[1], *planes, bit_depth=src_depth, pts=i)
+                    elif fmt is None:
                         enc.send(*planes, pts=i)
                     elif rgb is not None:
                         enc.send_rgb(fmt, *planes, pts=i)

@@ -248,6 +248,25 @@ typedef struct mihevc_rgb_format {
  * than the row, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush. */
 int  mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2,
                            int pitch, int64_t pts, int flags);
+/* ---- added under ABI 6: sources of another SIZE (symbols only) ----
+ * A planar 4:2:0 picture of src->width x src->height samples at src->bit_depth, scaled down on the device into the session's planes of cfg.width x cfg.height
+ * at cfg.bit_depth by a separable 16-tap polyphase Catmull-Rom filter with an exact integer definition (hevc_amd/csrc/kernels/scale.h and
+ * hevc_amd/csrc/scale_taps.h state the arithmetic).  Per axis cfg size <= source size <= 4 x cfg size, the axes independent; equal sizes give the conversion of
+ * mihevc_send_frame_fmt for a planar 4:2:0 source.  Elements are uint8 at 8 bit, else little-endian uint16, lsb aligned, values above 2^bit_depth - 1 clamped;
+ * chroma is sited as chroma_sample_loc_type 0 on both sides.  No sample aspect ratio is signalled: the caller chooses sizes of one shape. */
+typedef struct mihevc_scale_src {
+    int32_t width, height;   /* the source picture: both even, >= 16 */
+    int32_t bit_depth;       /* significant bits 8..16 */
+    int32_t reserved[5];     /* 0 */
+} mihevc_scale_src;
+/* pitch_y, pitch_c: in elements.  Flags, ownership, staging and stream ordering are those of mihevc_send_frame_fmt: host planes are copied into the session's
+ * staging set and scaled from there, and without MIHEVC_SRC_ASYNC they may be reused on return; with MIHEVC_SRC_DEVICE the kernel reads the planes where they
+ * are (several sessions may read the same planes), and they must stay valid and unmodified until mihevc_sync_uploads or mihevc_flush has returned.
+ * MIHEVC_EINVAL, decided before any device call and leaving the session usable: NULL src or plane, odd sizes or sizes below 16 (cfg.width / cfg.height
+ * included), a size ratio outside [1, 4] on either axis, bit_depth outside 8..16, non-zero reserved, a pitch smaller than the plane, unknown flag bits,
+ * slice_count > 1.  MIHEVC_ESTATE after flush. */
+int  mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, const void *y, const void *u, const void *v,
+                              int pitch_y, int pitch_c, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -392,6 +411,11 @@ int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void
  * MIHEVC_ENODEV without a device */
 int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2,
                          int width, int height, int pitch, int out_bit_depth, void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  The scaler of mihevc_send_frame_scaled alone (the session's kernel), host buffers in and out: src names the source planes y / u / v,
+ * dst_width x dst_height is the display size of the output, out_* are planes of its CODED size as in mihevc_k_convert_source.  Validated first
+ * (MIHEVC_EINVAL: what mihevc_send_frame_scaled refuses, an out_bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
+int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
+                          int dst_width, int dst_height, int out_bit_depth, void *out_y, void *out_u, void *out_v);
 
 /* ---- host-only stages (no device needed): bitstream ---- */
 /* VPS+SPS+PPS (+SEI when hdr10) as Annex-B into buf; returns size or negative error */
