@@ -146,7 +146,7 @@ EXPORTS = (
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
     "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
-    "mihevc_send_frame_scaled", "mihevc_k_scale_source",
+    "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff",
 )
 
 _lib = None
@@ -217,6 +217,7 @@ def load() -> C.CDLL:
     lib.mihevc_k_convert_rgb.argtypes = [i32, C.POINTER(RgbFormat), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.mihevc_send_frame_scaled.argtypes = [vp, C.POINTER(ScaleSrc), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_scale_source.argtypes = [i32, C.POINTER(ScaleSrc), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_k_scene_diff.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
     _lib = lib
     return lib
 

@@ -943,6 +943,27 @@ template <typename TO> struct ConvertOut {
         return MIHEVC_OK;
     }
 };
+// the scene-cut sums of n consecutive pictures as a session takes them: launch_scene_diff on zeroed sums; the planes keep the pitches they come with
+template <typename T> int stage_scene_diff(const void *const *luma, const int32_t *pitch, int n, int w, int h, uint64_t *out)
+{
+    std::vector<DevBuf> planes((size_t)n);
+    std::vector<ScenePic<T>> pics((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const size_t bytes = (size_t)pitch[i] * h * sizeof(T);
+        CK(planes[(size_t)i].alloc(bytes));
+        CK(hipMemcpy(planes[(size_t)i].p, luma[i], bytes, hipMemcpyHostToDevice));
+        pics[(size_t)i] = ScenePic<T>{planes[(size_t)i].template as<const T>(), pitch[i]};
+    }
+    DevBuf dpics, dout;
+    if (int e = to_device(dpics, pics.data(), (size_t)n)) return e;
+    CK(dout.alloc((size_t)n * sizeof(unsigned long long)));
+    CK(hipMemset(dout.p, 0, (size_t)n * sizeof(unsigned long long)));
+    CK(launch_scene_diff<T>(0, dpics.as<const ScenePic<T>>(), dout.as<unsigned long long>(), w, h, n));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+
 bool convert_geometry_ok(int w, int h, int out_depth)
 {
     return w >= 16 && h >= 16 && !(w & 1) && !(h & 1) && w <= 8192 && h <= 4352 && (out_depth == 8 || out_depth == 10);
@@ -1090,6 +1111,15 @@ int mihevc_k_intra_plan(int device, const void *sy, const void *su, const void *
     if (int e = select_device(device)) return e;
     const void *s[3] = {sy, su, sv};
     return with_depth(prm->bit_depth, [&](auto t) { return stage_intra_plan<decltype(t)>(s, w, h, prm, plan); });
+}
+
+int mihevc_k_scene_diff(int device, const void *const *luma, const int32_t *pitch, int n, int w, int h, int bit_depth, uint64_t *out)
+{
+    if (!luma || !pitch || !out || n < 1 || w < 1 || h < 1 || w > 8192 || h > 4352 || (bit_depth != 8 && bit_depth != 10)) return MIHEVC_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!luma[i] || pitch[i] < w) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return with_depth(bit_depth, [&](auto t) { return stage_scene_diff<decltype(t)>(luma, pitch, n, w, h, out); });
 }
 
 int mihevc_k_inter_frame(int device, const void *sy, const void *su, const void *sv, const void *fy, const void *fu, const void *fv, int w, int h,

@@ -417,6 +417,14 @@ int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p
 int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
                           int dst_width, int dst_height, int out_bit_depth, void *out_y, void *out_u, void *out_v);
 
+/* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
+ * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
+ * at least 1.  out[i], i >= 1: the sum of |luma[i - 1][y][x] - luma[i][y][x]| over every 4th sample of every 4th row (x, y = 0 mod 4) inside width x height;
+ * out[0] = 0.  n = 1 is allowed and gives out[0] = 0.  Refused before anything is launched (MIHEVC_EINVAL): n < 1, a null plane, a pitch below width, a bit depth
+ * other than 8 / 10; then MIHEVC_ENODEV without a device */
+int mihevc_k_scene_diff(int device, const void *const *luma, const int32_t *pitch /* samples */, int n, int width, int height, int bit_depth,
+                        uint64_t *out /* n; out[0] = 0 */);
+
 /* ---- host-only stages (no device needed): bitstream ---- */
 /* VPS+SPS+PPS (+SEI when hdr10) as Annex-B into buf; returns size or negative error */
 int mihevc_write_parameter_sets(const mihevc_config *cfg, uint8_t *buf, size_t cap);

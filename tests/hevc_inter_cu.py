@@ -1,6 +1,7 @@
 """A third statement of the inter CTU program: what `mihevc_k_inter_frame` / `mihevc_k_b_frame` decide AFTER the integer search — the quadtree of
 every CTU, the half- and quarter-sample vector of every CU, the list-0 / list-1 / bi-prediction choice of B pictures, the RD zero-out of inter TUs,
-the CU records, levels, pre-deblock reconstruction and the picture's rate estimate.
+the RD zero-out of their 4x4 coefficient groups (`rdo_cg`, DESIGN.md §6b: `group_zero_out`), sign data hiding behind it, the CU records, levels, pre-deblock reconstruction
+and the picture's rate estimate.
 
 Written from the documents alone: DESIGN.md §6 ("Decision rules of the inter CTU program, in words"), the comments of include/mihevc.h
 (`mihevc_cu_rec`) and H.265 8.5.3.3.3 / 8.5.3.3.4.2 through tests/hevc_recon.py.  Not from hevc_amd/csrc/kernels/inter.h and not from
@@ -10,13 +11,14 @@ prediction block comes from `mc_luma`, the Hadamard transform is a matrix produc
 first minimum is taken.
 
 Imports: numpy, the standard library, tests/hevc_analysis.py (node geometry, mvd bits, the integer search that `integer_table` starts from), tests/hevc_recon.py (8.5.3.3.3, default weighted
-prediction) and tests/transform_ref.py (K3) (tests/test_syntax_independent.py checks it)."""
+prediction), tests/transform_ref.py (K3) and tests/sdh_ref.py (the sign data hiding rule) (tests/test_syntax_independent.py checks it)."""
 import collections
 
 import numpy as np
 
 from tests import hevc_analysis as A
 from tests import hevc_recon as R
+from tests import sdh_ref as SDH
 from tests import transform_ref as K3
 
 CTU = 32
@@ -90,6 +92,34 @@ def sub_block_bits(levels):
     return bits
 
 
+def group_zero_out(coef, lvl, deq, log2n, bit_depth, lambda_q4, k):
+    """DESIGN.md §6b (`rdo_cg`), include/mihevc.h: the RD zero-out of the 4x4 coefficient groups of one inter TU.  coef: its forward coefficients,
+    lvl: its levels, deq: its scaled levels (clipped to 16 bit), all n x n.  Dropping a group adds D = sum r (2 c - r) of squared coefficient error over
+    its non-zero levels and saves its levels' bits + one sub-block of the rate model; the group goes when
+    16 D < (((lambda_q4 k >> 1) bits) >> 4) << 2 (15 - bitDepth - log2n).  -> {(group row, group column): (D, bits, threshold, dropped)} of the groups
+    that hold a level.  Plain integers, one group after the other."""
+    n = 1 << log2n
+    lam = (int(lambda_q4) * int(k)) >> 1
+    shift = 2 * (15 - bit_depth - log2n)
+    out = {}
+    for gy in range(0, n, 4):
+        for gx in range(0, n, 4):
+            d, bits, any_level = 0, R_SB, False
+            for y in range(gy, gy + 4):
+                for x in range(gx, gx + 4):
+                    a = int(lvl[y][x])
+                    if a == 0:
+                        continue
+                    any_level = True
+                    c, r = int(coef[y][x]), int(deq[y][x])
+                    d += r * (2 * c - r)
+                    bits += level_rate(abs(a))
+            if any_level:
+                threshold = ((lam * bits) >> 4) << shift
+                out[gy >> 2, gx >> 2] = (d, bits, threshold, 16 * d < threshold)
+    return out
+
+
 def integer_table(cur_y, ref_y, bit_depth, me_range, lambda_sad_q4, centres, mc_top=0, mc_bottom=0):
     """the 21-node integer table the program starts from: A.integer_search; in a slice (*Slices*), which that model does not state, the same
     rules walked candidate by candidate: a vertical displacement that takes the node's rows (luma, or chroma at its half-sample phase) out of the slice is
@@ -135,14 +165,15 @@ class Result:
         self.ctus = []
 
 
-def analyse(src, refs, tables, bit_depth, qp, qp_c, lambda_sad_q4, lambda_q4, me_range, centres=None, rdo_zero=0, mc_top=0, mc_bottom=0, cov=None):
+def analyse(src, refs, tables, bit_depth, qp, qp_c, lambda_sad_q4, lambda_q4, me_range, centres=None, rdo_zero=0, mc_top=0, mc_bottom=0, cov=None, rdo_cg=0, sign_hide=0):
     """src: (Y, Cb, Cr) of the coded size; refs: one (P picture) or two (B picture: list 0, list 1) such triples, unpadded: reads beyond the picture
     are clamped to it; tables: per reference the (n_ctu, 21, 3) integer-search dump (A.integer_search); centres: per reference None or (n_ctu, 2)
     whole samples, as they were given to the search.
 
     Result.ctus[i]: {"leaves": [node ...], "node_cost": {node: integer-vector cost}, "tree": (whole / split pairs),
     "rounds": {(node, list, round): ([9 costs or None], winner, [9 rows-admissible flags])}, "mv": {node: [mv per list]},
-    "keys": {node: [3 keys]}, "mode": {node: 0 / 1 / 2}, "tus": {(node, plane): (jz, jc, zeroed)}}"""
+    "keys": {node: [3 keys]}, "mode": {node: 0 / 1 / 2}, "tus": {(node, plane): (jz, jc, zeroed)},
+    "groups": {(node, plane): {(group row, group column): (D, bits, threshold, dropped)}} (rdo_cg > 0: group_zero_out)}"""
     cov = cov if cov is not None else collections.Counter()
     sp = [np.asarray(p).astype(np.int64) for p in src]
     rp = [[np.asarray(p).astype(np.int64) for p in r] for r in refs]
@@ -185,7 +216,7 @@ def analyse(src, refs, tables, bit_depth, qp, qp_c, lambda_sad_q4, lambda_q4, me
             sx, sy = int(cen[l][ctu, 0]), int(cen[l][ctu, 1])
             centre.append((sx, clamp_centre_y(sy, y0, me_range, h, mc_top, mc_bottom) if slice_ else sy))
         valid = [int(tables[0][ctu, nd, 2]) >= 0 for nd in range(21)]
-        info = {"leaves": [], "node_cost": {}, "rounds": {}, "mv": {}, "keys": {}, "mode": {}, "tus": {}}
+        info = {"leaves": [], "node_cost": {}, "rounds": {}, "mv": {}, "keys": {}, "mode": {}, "tus": {}, "groups": {}}
         # ---- node cost at the integer vector
         c0 = {}
         for nd, (nx, ny, n) in enumerate(NODES):
@@ -249,8 +280,37 @@ def analyse(src, refs, tables, bit_depth, qp, qp_c, lambda_sad_q4, lambda_q4, me
                 mc = R.mc_chroma if c else R.mc_luma
                 pred = R.weighted_default([mc(rp[l][c], px, py, m, mvs[l], bd) for l in used], bd)
                 blk = sp[c][py:py + m, px:px + m]
-                lvl, res = K3.reference((blk - pred)[None], m.bit_length() - 1, q, bd, False)
-                lvl, res = lvl[0], res[0]
+                log2m = m.bit_length() - 1
+                coef = K3.forward((blk - pred)[None], log2m, bd)
+                lvl = K3.quantise(coef, log2m, q, bd, False)
+                deq = K3.scale(lvl, log2m, q, bd)
+                coef, lvl, deq = coef[0], lvl[0], deq[0]
+                thinned = False
+                if rdo_cg > 0 and lvl.any():                      # the group drop: before the cbf, the TU zero-out and the estimate
+                    groups = info["groups"][nd, c] = group_zero_out(coef, lvl, deq, log2m, bd, lambda_q4, rdo_cg)
+                    where = ("luma" if c == 0 else "chroma", m)
+                    for (gr, gc), (dist, gbits, thr, drop) in groups.items():
+                        cov["group", where, "dropped" if drop else "kept"] += 1
+                        if 16 * dist == thr:
+                            cov["group equality"] += 1
+                        if drop:
+                            lvl[4 * gr:4 * gr + 4, 4 * gc:4 * gc + 4] = 0
+                            deq[4 * gr:4 * gr + 4, 4 * gc:4 * gc + 4] = 0
+                            thinned = True
+                    if not lvl.any():
+                        cov["group drop emptied a TU"] += 1
+                if sign_hide and lvl.any():                       # sign data hiding: after the group decisions, before the TU zero-out; inter TUs scan diagonally
+                    qq = q + 6 * (bd - 8)
+                    before = lvl.copy()
+                    for gr in range(0, m, 4):
+                        for gc in range(0, m, 4):
+                            SDH.hide_group(lvl[gr:gr + 4, gc:gc + 4], coef[gr:gr + 4, gc:gc + 4], 0, K3.QUANT_SCALE[qq % 6], 14 + qq // 6 + (15 - bd - log2m))
+                            if not np.array_equal(before[gr:gr + 4, gc:gc + 4], lvl[gr:gr + 4, gc:gc + 4]):
+                                cov["sign hiding adjusted a group"] += 1
+                                if thinned:
+                                    cov["sign hiding adjusted a group", "in a TU that lost a group"] += 1
+                    deq = K3.scale(lvl, log2m, q, bd)
+                res = K3.inverse(deq[None], log2m, bd)[0] if lvl.any() else np.zeros_like(lvl)
                 if rdo_zero and lvl.any():
                     dz, dc = blk - pred, blk - np.clip(pred + res, 0, maxv)
                     jz = int((dz * dz).sum()) << 4
@@ -262,6 +322,8 @@ def analyse(src, refs, tables, bit_depth, qp, qp_c, lambda_sad_q4, lambda_q4, me
                         cov["zero-out tie"] += 1
                     if zero:
                         lvl, res = np.zeros_like(lvl), np.zeros_like(res)
+                        if thinned:
+                            cov["group drop thinned, zero-out removed"] += 1
                 if lvl.any():
                     flags |= F_CBF[c]
                     cu_bits += R_TU + sub_block_bits(lvl)

@@ -60,6 +60,8 @@ def test_no_gpu_means_loud_failure_not_fallback():
     assert lib.mihevc_open(C.byref(cfg), 0, C.byref(s)) == _lib.ENODEV and not s.value
     z = np.zeros((64, 64), np.int16)
     assert lib.mihevc_k_transform(0, z.ctypes.data, z.ctypes.data, z.ctypes.data, 1, 3, 22, 8, 1, 0) == _lib.ENODEV
+    planes, pitch, sums = (C.c_void_p * 2)(z.ctypes.data, z.ctypes.data), (C.c_int32 * 2)(64, 64), (C.c_uint64 * 2)()
+    assert lib.mihevc_k_scene_diff(0, planes, pitch, 2, 64, 32, 8, sums) == _lib.ENODEV
     from hevc_amd.encoder import Encoder
     with pytest.raises(_lib.MihevcError) as e:
         Encoder(cfg)

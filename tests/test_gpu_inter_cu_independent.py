@@ -1,6 +1,7 @@
 """GPU: what the real gfx950 kernels `k_inter_ctu` / `k_inter_ctu_b` decide (through mihevc_k_inter_frame / mihevc_k_b_frame) held to tests/hevc_inter_cu.py,
 the brute-force numpy model written from DESIGN.md §6, WITHOUT the oracle in between: every case of util.INTER_CASES (64x64 / 136x72 / 72x104, 8 and 10 bit,
-me_range 8 / 15, QP 22 / 32 / 42, rdo_zero 0 / 1, explicit centres, the pre-search, slices, lambda_sad_q4 = 0, B pictures) and the hand-worked pictures of
+me_range 8 / 15, QP 22 / 32 / 42, rdo_zero 0 / 1, explicit centres, the pre-search, slices, lambda_sad_q4 = 0, B pictures, the residual-rich pictures with
+rdo_cg 0 / 2 / 5 / 8: records, levels, reconstruction and estimate of every case) and the hand-worked pictures (the group drop at its equality among them) of
 tests/test_inter_cu_independent.py, its CPU twin (oracle, stepped kernel sources, the coverage count).  The model's answer is computed once per case."""
 import numpy as np
 import pytest
@@ -34,5 +35,5 @@ def test_device_analysis_equals_the_model(api, c):
     for l, m in enumerate(me):
         t = got.me if len(me) == 1 else got.me[l]
         assert np.array_equal(t, m), f"integer table, list {l}: device != model: " + util.first_diff(t, m)
-    d = inter_diff(want, got, decisions_only=c.rdo_cg > 0)
+    d = inter_diff(want, got)
     assert not d, "device != model: " + d

@@ -13,6 +13,7 @@ import pytest
 from hevc_amd import _lib
 from oracle import oracle as O
 from tests import util
+from tests.sdh_ref import hide_group, scan4, scan_idx  # noqa: F401  (the rule itself: tests/sdh_ref.py)
 
 GOLDEN = Path(__file__).parent / "golden"
 _spec = importlib.util.spec_from_file_location("make_sdh_goldens", GOLDEN / "make_sdh_goldens.py")
@@ -21,70 +22,6 @@ _spec.loader.exec_module(S)
 WANT = json.loads((GOLDEN / "streams_sdh.json").read_text())
 
 QUANT_SCALE = (26214, 23302, 20560, 18396, 16384, 14564)
-
-
-def scan4(scan):
-    """raster positions (y * 4 + x) of scan positions 0..15 of a 4x4 group: 6.5.3 up-right diagonal, 6.5.4 horizontal, 6.5.5 vertical"""
-    if scan == 1:
-        return [y * 4 + x for y in range(4) for x in range(4)]
-    if scan == 2:
-        return [y * 4 + x for x in range(4) for y in range(4)]
-    out, x, y = [], 0, 0
-    while len(out) < 16:
-        while y >= 0:
-            if x < 4 and y < 4:
-                out.append(y * 4 + x)
-            y, x = y - 1, x + 1
-        y, x = x, 0
-    return out
-
-
-def scan_idx(log2n, c_idx, mode):
-    """7.4.9.11"""
-    if log2n == 2 or (log2n == 3 and c_idx == 0):
-        if 6 <= mode <= 14:
-            return 2
-        if 22 <= mode <= 30:
-            return 1
-    return 0
-
-
-def hide_group(lv, c, scan, qs, qbits):
-    """the parity adjustment of one 4x4 group (lv, c: 4x4 levels and forward coefficients; lv is changed in place), as the issue states it"""
-    order = scan4(scan)
-    L = [int(lv[p // 4, p % 4]) for p in order]
-    cf = [int(c[p // 4, p % 4]) for p in order]
-    nz = [n for n in range(16) if L[n]]
-    if not nz or nz[-1] - nz[0] <= 3:
-        return
-    first, last = nz[0], nz[-1]
-    sf = int(L[first] < 0)
-    if sum(abs(v) for v in L) & 1 == sf:
-        return
-    best = None
-    for n in range(last, -1, -1):
-        a, u = abs(L[n]), abs(cf[n]) * qs
-        delta = (u - (a << qbits)) >> (qbits - 8)
-        if a:
-            if delta > 0:
-                chg, cost = 1, -delta
-            elif n == first and a == 1:
-                continue
-            else:
-                chg, cost = -1, delta
-        else:
-            if n < first and int(cf[n] < 0) != sf:
-                continue
-            chg, cost = 1, -delta
-        if best is None or cost < best[0]:
-            best = (cost, n, chg)
-    _, n, chg = best
-    a = abs(L[n])
-    if chg == 1 and a == 32767:
-        chg = -1
-    a += chg
-    p = order[n]
-    lv[p // 4, p % 4] = a if cf[n] >= 0 else -a
 
 
 def reference(res, log2n, qp, bd, intra, scan, dst=False):

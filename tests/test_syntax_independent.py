@@ -24,14 +24,16 @@ HERE = Path(__file__).resolve().parent
 # the independent modules and what each may import besides the standard library and numpy
 INDEPENDENT = {"hevc_syntax.py": set(), "hevc_recon.py": {"tests.hevc_syntax", "tests.pichash_ref"}, "pichash_ref.py": set(),
                "hevc_analysis.py": {"tests.hevc_syntax", "tests.hevc_recon"},    # the numpy model of the encoder-side decisions (tests/test_analysis_independent.py)
+               "sdh_ref.py": set(),                                            # the sign data hiding rule (tests/test_sign_hiding_cpu.py)
+               "scene_ref.py": set(),                                          # the scene-cut sums (tests/test_gpu_scene_diff.py)
                "transform_ref.py": set(),                                      # K3 in numpy int64 (tests/test_transform_reference.py)
                "hevc_intra_plan.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref"},    # the intra plan (tests/test_intra_plan_independent.py)
-               "hevc_inter_cu.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref"}}      # the inter CTU program (tests/test_inter_cu_independent.py)
+               "hevc_inter_cu.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref", "tests.sdh_ref"}}      # the inter CTU program (tests/test_inter_cu_independent.py)
 
 
 def test_the_reader_imports_only_the_standard_library_and_numpy():
     """tests/hevc_syntax.py, tests/hevc_recon.py (with the stdlib-and-numpy tests/pichash_ref.py it uses), tests/hevc_analysis.py, tests/hevc_intra_plan.py and
-    tests/hevc_inter_cu.py (with tests/transform_ref.py) load nothing of hevc_amd/ or oracle/"""
+    tests/hevc_inter_cu.py (with tests/transform_ref.py and tests/sdh_ref.py) and tests/scene_ref.py load nothing of hevc_amd/ or oracle/"""
     for module, allowed in INDEPENDENT.items():
         tree = ast.parse((HERE / module).read_text())
         names = set()

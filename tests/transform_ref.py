@@ -46,26 +46,45 @@ def _fits16(x, what):
     assert x.min() >= I16[0] and x.max() <= I16[1], f"{what} leaves 16 bits: {x.min()}..{x.max()}"
 
 
-def reference(res, log2n, qp, bit_depth, intra, dst=False):
-    """res: (blocks, n, n) residuals -> (levels, reconstructed residuals), both (blocks, n, n) int64.  Forward: rows, shift log2n + bd - 9
-    (16-bit intermediate, checked), columns, shift log2n + 6, clip to 16 bit.  Quantiser: qP = qp + 6 (bd - 8), qbits = 14 + qP / 6 +
-    (15 - bd - log2n), offset 171 (intra) / 85 (inter) << (qbits - 9), magnitude at most 32767.  Scaling (8.6.4.1, m = 16): bdShift =
-    bd + log2n - 5, clip to 16 bit.  Inverse (8.6.4.2): columns, (x + 64) >> 7, clip to 16 bit; rows, shift 20 - bd (16-bit, checked).
-    A block without a non-zero level reconstructs to zero."""
+def forward(res, log2n, bit_depth, dst=False):
+    """res: (blocks, n, n) residuals -> coefficients.  Rows, shift log2n + bd - 9 (16-bit intermediate, checked), columns, shift log2n + 6, clip to 16 bit"""
     t = matrix(log2n, dst)
     r = np.asarray(res, np.int64)
     tmp = _round_shift(np.einsum("bxy,uy->bxu", r, t), log2n + bit_depth - 9)      # tmp[y][u] = sum_x r[y][x] T[u][x]
     _fits16(tmp, "forward stage 1")
-    coef = np.clip(_round_shift(np.einsum("vy,byu->bvu", t, tmp), log2n + 6), *I16)
+    return np.clip(_round_shift(np.einsum("vy,byu->bvu", t, tmp), log2n + 6), *I16)
+
+
+def quantise(coef, log2n, qp, bit_depth, intra):
+    """coefficients -> levels: qP = qp + 6 (bd - 8), qbits = 14 + qP / 6 + (15 - bd - log2n), offset 171 (intra) / 85 (inter) << (qbits - 9),
+    magnitude at most 32767"""
     q = qp + 6 * (bit_depth - 8)
     qbits = 14 + q // 6 + (15 - bit_depth - log2n)
     add = (171 if intra else 85) << (qbits - 9)
     mag = np.minimum((np.abs(coef) * QUANT_SCALE[q % 6] + add) >> qbits, 32767)
-    lvl = np.where(coef < 0, -mag, mag)
+    return np.where(coef < 0, -mag, mag)
+
+
+def scale(lvl, log2n, qp, bit_depth):
+    """levels -> scaled levels (8.6.4.1, m = 16): bdShift = bd + log2n - 5, clip to 16 bit"""
+    q = qp + 6 * (bit_depth - 8)
     bd_shift = bit_depth + log2n - 5
-    deq = np.clip((lvl * 16 * LEVEL_SCALE[q % 6] << (q // 6)) + (1 << (bd_shift - 1)) >> bd_shift, *I16)
+    return np.clip((np.asarray(lvl, np.int64) * 16 * LEVEL_SCALE[q % 6] << (q // 6)) + (1 << (bd_shift - 1)) >> bd_shift, *I16)
+
+
+def inverse(deq, log2n, bit_depth, dst=False):
+    """scaled levels -> residuals (8.6.4.2): columns, (x + 64) >> 7, clip to 16 bit; rows, shift 20 - bd (16-bit, checked)"""
+    t = matrix(log2n, dst)
     g = np.clip((np.einsum("jy,bjx->byx", t, deq) + 64) >> 7, *I16)                  # columns: g[y][x] = sum_j T[j][y] d[j][x]
     rec = _round_shift(np.einsum("byj,jx->byx", g, t), 20 - bit_depth)               # rows: r[y][x] = sum_j g[y][j] T[j][x]
     _fits16(rec, "inverse stage 2")
+    return rec
+
+
+def reference(res, log2n, qp, bit_depth, intra, dst=False):
+    """res: (blocks, n, n) residuals -> (levels, reconstructed residuals), both (blocks, n, n) int64: forward, quantise, scale, inverse (above).
+    A block without a non-zero level reconstructs to zero."""
+    lvl = quantise(forward(res, log2n, bit_depth, dst), log2n, qp, bit_depth, intra)
+    rec = inverse(scale(lvl, log2n, qp, bit_depth), log2n, bit_depth, dst)
     rec[~lvl.any(axis=(1, 2))] = 0
     return lvl, rec

@@ -674,11 +674,15 @@ def check_records_carry_the_plan(plan, cu, w, h, nxn):
 # quarter-sample vector of its own through the standard's filter (tests/hevc_recon.py), + noise of +-`noise`; B pictures ("b-..."): the blocks are predicted from
 # list 0, list 1 or both.  "soft-" in front: the reference(s) at an eighth of their contrast, so that the ring's candidates predict nearly the same block and the
 # noise decides between them by a few units of SATD.  mvs: None = drawn per block from `seed` (|mv| < 4 me_range), or the vectors themselves, dealt to the blocks in raster order.
-InterCase = namedtuple("InterCase", "id w h bd R qp content seed shift noise mvs centres pre_search rdo_zero mc lam rdo_cg")
+# lam: None = the lambdas of the QP, or (lambda_sad_q4, lambda_q4) with None for the QP's own.  plant: ((plane, x, y, n, dc, e), ...): after everything else the n x n block at
+# (x, y) of the current picture's plane gets dc added to every sample and (n = 8) e x (+ - - + + - - +) by rows: the fifth basis function of the 8-point transform down
+# the columns, so that an exactly predicted block has the coefficients (0, 0) and (4, 0) alone
+InterCase = namedtuple("InterCase", "id w h bd R qp content seed shift noise mvs centres pre_search rdo_zero mc lam rdo_cg plant")
+PLANT_ROWS = (1, -1, -1, 1, 1, -1, -1, 1)
 
 
-def inter_case(id, w, h, bd, R, qp, content, seed=1, shift=(0, 0), noise=0, mvs=None, centres=None, pre_search=0, rdo_zero=0, mc=(0, 0), lam=None, rdo_cg=0):
-    return InterCase(id, w, h, bd, R, qp, content, seed, shift, noise, mvs, centres, pre_search, rdo_zero, mc, lam, rdo_cg)
+def inter_case(id, w, h, bd, R, qp, content, seed=1, shift=(0, 0), noise=0, mvs=None, centres=None, pre_search=0, rdo_zero=0, mc=(0, 0), lam=None, rdo_cg=0, plant=()):
+    return InterCase(id, w, h, bd, R, qp, content, seed, shift, noise, mvs, centres, pre_search, rdo_zero, mc, lam, rdo_cg, plant)
 
 
 def warp_picture(refs, w, h, bd, g, seed, noise, mvs, lists, reach):
@@ -705,9 +709,27 @@ def warp_picture(refs, w, h, bd, g, seed, noise, mvs, lists, reach):
     return O.Frame(*out), blocks
 
 
-@functools.lru_cache(maxsize=None)
 def inter_case_pictures(c):
     """(current picture, (reference,) or (list-0 anchor, list-1 anchor), planted blocks or None)"""
+    cur, refs, blocks = _inter_case_pictures(c._replace(id="", qp=0, lam=None, rdo_zero=0, rdo_cg=0))       # (what the pictures do not depend on)
+    return cur, refs, blocks
+
+
+@functools.lru_cache(maxsize=None)
+def _inter_case_pictures(c):
+    cur, refs, blocks = _inter_case_pictures_unplanted(c._replace(plant=()))
+    if c.plant:
+        planes = [p.astype(np.int64) for p in planes3(cur)]
+        for plane, x, y, n, dc, e in c.plant:
+            assert n == 8 or not e
+            planes[plane][y:y + n, x:x + n] += dc + e * np.array(PLANT_ROWS * (n // 8))[:, None]
+            assert planes[plane].min() >= 0 and planes[plane].max() < 1 << c.bd
+        cur = O.Frame(*planes)
+    return cur, refs, blocks
+
+
+@functools.lru_cache(maxsize=None)
+def _inter_case_pictures_unplanted(c):
     if c.content == "flat":
         cur, ref = flat_pair(c.w, c.h, c.bd)
         return cur, (ref,), None
@@ -750,7 +772,7 @@ def inter_case_centres(c, n_refs):
 def inter_case_params(c):
     knobs = dict(pre_search=c.pre_search, rdo_zero=c.rdo_zero, mc_top=c.mc[0], mc_bottom=c.mc[1], rdo_cg=c.rdo_cg)
     if c.lam is not None:
-        knobs.update(lambda_sad_q4=c.lam[0], lambda_q4=c.lam[1])
+        knobs.update({k: v for k, v in (("lambda_sad_q4", c.lam[0]), ("lambda_q4", c.lam[1])) if v is not None})
     return params_pair(c.qp, c.bd, c.R, **knobs)
 
 
@@ -758,8 +780,9 @@ INTER_COVERAGE = {}                                              # case id -> wh
 
 
 @functools.lru_cache(maxsize=None)
-def inter_case_want(c):
-    """(the model's analysis, the integer tables it started from, the centres given to the entry points): computed once per case"""
+def inter_case_want(c, sign_hide=0):
+    """(the model's analysis, the integer tables it started from, the centres given to the entry points): computed once per case.  sign_hide = 1 (no field of a case:
+    the frame stage entries and the oracle do not take it; the stepped kernels do): counted under INTER_COVERAGE[c.id + "+sdh"]"""
     from tests import hevc_inter_cu as M
     _, cp = inter_case_params(c)
     cur, refs, _ = inter_case_pictures(c)
@@ -777,8 +800,9 @@ def inter_case_want(c):
                 k[i, 1] = M.clamp_centre_y(int(k[i, 1]), i // wc * 32, c.R, c.h, *c.mc)
             cen_search.append(k)
     me = [M.integer_table(cur.y, r.y, c.bd, c.R, cp.lambda_sad_q4, k, *c.mc) for r, k in zip(refs, cen_search)]
-    cov = INTER_COVERAGE[c.id] = collections.Counter()
-    want = M.analyse(planes3(cur), [planes3(r) for r in refs], me, c.bd, cp.qp, cp.qp_c, cp.lambda_sad_q4, cp.lambda_q4, c.R, cen, c.rdo_zero, c.mc[0], c.mc[1], cov)
+    cov = INTER_COVERAGE[c.id + ("+sdh" if sign_hide else "")] = collections.Counter()
+    want = M.analyse(planes3(cur), [planes3(r) for r in refs], me, c.bd, cp.qp, cp.qp_c, cp.lambda_sad_q4, cp.lambda_q4, c.R, cen, c.rdo_zero, c.mc[0], c.mc[1], cov, rdo_cg=c.rdo_cg,
+                     sign_hide=sign_hide)
     return want, me, given
 
 
@@ -828,30 +852,43 @@ def _inter_cases():
                                                  ("soft-b-mix16", (64, 64), 10, 8, 32, 5, 204), ("soft-warp16", (72, 104), 8, 8, 32, 5, 202), ("soft-b-mix32", (72, 104), 8, 15, 22, 3, 201),
                                                  ("soft-warp16", (136, 72), 10, 8, 32, 5, 200)):
         out.append(inter_case(f"{kind}-{w}x{h}-{bd}bit-R{R}-qp{qp}-n{noise}", w, h, bd, R, qp, kind, seed=seed, noise=noise << (bd - 8), rdo_zero=seed & 1))
-    # rdo_cg > 0: the decisions do not depend on it
+    # rdo_cg > 0: these two pictures carry almost no residual (6 and 27 coded groups); the residual-rich ones follow
     out.append(inter_case("rdocg-warp16-136x72-8bit", 136, 72, 8, 8, 32, "warp16", seed=90, noise=2, rdo_zero=1, rdo_cg=5))
     out.append(inter_case("rdocg-b-mix16-72x104-10bit", 72, 104, 10, 8, 32, "b-mix16", seed=91, noise=4, rdo_zero=1, rdo_cg=5))
+    # B pictures in which one CU's list-1 key EQUALS its bi-prediction key with list 0 dearer: 16 (SATD_1 - SATD_bi) = lambda_sad_q4 (mv_bits_0 - 1); found with the model
+    # alone (tools/find_b_key_tie.py): what holds the order of list 1 against both lists on equal cost
+    out.append(inter_case("b-tie12-b-mix8-64x64-8bit-lam16", 64, 64, 8, 8, 27, "b-mix8", seed=302, noise=3, lam=(16, None)))
+    out.append(inter_case("b-tie12-b-mix8-136x72-10bit-lam32", 136, 72, 10, 8, 27, "b-mix8", seed=300, noise=1 << 2, lam=(32, None)))
+    # residual-rich pictures: noise of +-6 .. 8 at QP 22 / 27 leaves hundreds of coded 4x4 groups, so that the group drop (rdo_cg), the TU zero-out and the
+    # estimate work on real levels; each picture once with its rdo_cg and once at rdo_cg = 0 with the TU zero-out on
+    for (w, h), bd, qp, content, seed, noise, cg, rz in RICH_PICTURES:
+        out.append(inter_case(f"rich-{content}-{w}x{h}-{bd}bit-qp{qp}-s{seed}-cg{cg}-rz{rz}", w, h, bd, 8, qp, content, seed=seed, noise=noise << (bd - 8), rdo_zero=rz, rdo_cg=cg))
+        out.append(inter_case(f"rich-{content}-{w}x{h}-{bd}bit-qp{qp}-s{seed}-cg0-rz1", w, h, bd, 8, qp, content, seed=seed, noise=noise << (bd - 8), rdo_zero=1))
     assert len({c.id for c in out}) == len(out)
     return out
 
 
+RICH_PICTURES = (((136, 72), 8, 22, "warp8", 5, 6, 2, 1), ((72, 104), 10, 22, "warp16", 5, 6, 5, 1), ((64, 64), 8, 22, "warp32", 5, 8, 8, 0), ((64, 64), 10, 27, "warp8", 6, 7, 5, 1),
+                 ((136, 72), 10, 27, "warp16", 7, 6, 2, 0), ((72, 104), 8, 27, "warp32", 8, 8, 5, 1), ((64, 64), 8, 27, "warp16", 9, 7, 2, 1), ((136, 72), 10, 22, "warp32", 10, 8, 5, 0),
+                 ((72, 104), 8, 22, "warp8", 11, 6, 8, 1), ((64, 64), 10, 22, "warp16", 5, 6, 8, 1), ((136, 72), 8, 27, "warp32", 12, 7, 8, 0), ((72, 104), 10, 27, "warp8", 13, 8, 2, 1),
+                 ((136, 72), 8, 22, "b-mix16", 14, 6, 5, 1), ((72, 104), 10, 22, "warp32", 15, 7, 2, 0), ((64, 64), 8, 22, "warp8", 16, 8, 5, 0), ((64, 64), 10, 22, "warp32", 17, 6, 5, 1))
 INTER_CASES = _inter_cases()
+RICH_CASES = [c for c in INTER_CASES if c.id.startswith("rich-")]
+# the four of them that also run with sign data hiding, on the CPU against the stepped kernels: 8 and 10 bit, P and B, rdo_cg 5 and 0
+SIGN_HIDE_CASES = [c for c in RICH_CASES if c.id in ("rich-b-mix16-136x72-8bit-qp22-s14-cg5-rz1", "rich-b-mix16-136x72-8bit-qp22-s14-cg0-rz1",
+                                                     "rich-warp16-72x104-10bit-qp22-s5-cg5-rz1", "rich-warp32-136x72-10bit-qp22-s10-cg0-rz1")]
+assert len(SIGN_HIDE_CASES) == 4
 SATD_ROUNDING_CASES = [c for c in INTER_CASES if c.content.startswith("soft-")]
 
 
-def inter_diff(want, got, decisions_only=False):
-    """want: the model's Result; got: an O.Analysis of the oracle, the stepped kernel or the device.  '' when equal.  decisions_only: the tree, the vectors and the list flags"""
+def inter_diff(want, got):
+    """want: the model's Result; got: an O.Analysis of the oracle, the stepped kernel or the device.  '' when equal"""
     out = []
     a, b = want.cu, got.cu
-    fields = ("log2_size", "mvx", "mvy", "intra_mode") if decisions_only else a.dtype.names
-    for f in fields:
+    for f in a.dtype.names:
         if not np.array_equal(a[f], b[f]):
             i = tuple(np.argwhere(a[f] != b[f])[0][:2])
             out.append(f"cu.{f} at (row, column) {i}: model {a[i]} vs {b[i]}")
-    if decisions_only:
-        if not np.array_equal(a["flags"] & 0x61, b["flags"] & 0x61):
-            out.append("cu.flags (inter, list bits)")
-        return "; ".join(out)
     for n, p, q in (("coef_y", want.coef[0], got.coef_y), ("coef_u", want.coef[1], got.coef_u), ("coef_v", want.coef[2], got.coef_v),
                     ("rec.y", want.rec[0], got.rec.y), ("rec.u", want.rec[1], got.rec.u), ("rec.v", want.rec[2], got.rec.v)):
         if not np.array_equal(p, q):
@@ -883,3 +920,28 @@ INTER_PINS = {c.id: c for c in (
     inter_case("pin-b-both", 64, 64, 8, 8, 27, "b-avg32", mvs=PIN_B_MVS),
     inter_case("pin-b-list0", 64, 64, 8, 8, 27, "b-first32", mvs=PIN_B_MVS),
     inter_case("pin-b-list1", 64, 64, 8, 8, 27, "b-second32", mvs=PIN_B_MVS))}
+
+
+# hand-worked coefficient-group drops (rdo_cg = 2: the group's lambda is lambda_q4 itself): every block is matched exactly, one block carries a planted residual.
+# GROUP_PINS[name]: the planted block (plane, x, y, n, dc, e), QP, and the lambda_q4 at which 16 D EQUALS the threshold of the DC group; the cases run at that lambda_q4,
+# one below and one above
+GROUP_PINS = {"8x8-8bit": (8, "warp8", PIN_SPLIT_MVS, (0, 16, 16, 8, 4, 0), 32, 1428), "8x8-10bit": (10, "warp8", PIN_SPLIT_MVS, (0, 16, 16, 8, 8, 0), 24, 5120),
+              "32x32-8bit": (8, "warp32", PIN_MVS, (0, 32, 0, 32, 1, 0), 32, 1428), "32x32-10bit": (10, "warp32", PIN_MVS, (0, 32, 0, 32, 2, 0), 24, 5120)}
+for _name, (_bd, _content, _mvs, _plant, _qp, _lq) in GROUP_PINS.items():
+    for _step, _tag in ((-1, "below"), (0, "equal"), (1, "above")):
+        INTER_PINS[f"pin-cg-{_name}-{_tag}"] = inter_case(f"pin-cg-{_name}-{_tag}", 64, 64, _bd, 8, _qp, _content, mvs=_mvs, rdo_cg=2, lam=(None, _lq + _step), plant=(_plant,))
+# two groups in one 8x8 TU, (0, 0) and (1, 0): at lambda_q4 = 1500 the first goes and the second stays
+INTER_PINS["pin-cg-one-of-two"] = inter_case("pin-cg-one-of-two", 64, 64, 8, 8, 32, "warp8", mvs=PIN_SPLIT_MVS, rdo_cg=2, lam=(None, 1500), plant=((0, 16, 16, 8, 4, 8),))
+
+
+# ================================================================ the scene-cut sums (mihevc_k_scene_diff; tests/scene_ref.py is the reference)
+def scene_diff(lib, planes, width, height, bit_depth, device=0, pitches=None):
+    """planes: n 2-D arrays (uint8 at 8 bit, uint16 at 10), each of `height` rows; a plane's row length is its pitch -> (return code, [n sums])"""
+    import ctypes as C
+    n = len(planes)
+    keep = [np.ascontiguousarray(p) for p in planes]
+    ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in keep])
+    pitch = (C.c_int32 * max(n, 1))(*(pitches if pitches is not None else [p.shape[1] for p in keep]))
+    out = (C.c_uint64 * max(n, 1))(*([0xdeadbeef] * max(n, 1)))
+    rc = lib.mihevc_k_scene_diff(device, ptrs, pitch, n, width, height, bit_depth, out)
+    return rc, list(out)[:n]
