@@ -90,6 +90,14 @@ class ScaleSrc(C.Structure):
         return f"ScaleSrc(width={self.width}, height={self.height}, bit_depth={self.bit_depth})"
 
 
+class Deint(C.Structure):
+    """mihevc_deint: field order and output rate of the interlaced frames handed to mihevc_send_frame_deint"""
+    _fields_ = [(n, C.c_int32) for n in ("tff", "field_rate")] + [("reserved", C.c_int32 * 6)]
+
+    def __repr__(self):
+        return f"Deint(tff={self.tff}, field_rate={self.field_rate})"
+
+
 class RgbFormat(C.Structure):
     """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
     _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
@@ -146,7 +154,7 @@ EXPORTS = (
     "mihevc_k_intra_frame", "mihevc_k_inter_frame", "mihevc_k_b_frame", "mihevc_k_deblock", "mihevc_k_sao", "mihevc_k_loop_filter", "mihevc_write_parameter_sets",
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
     "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
-    "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff",
+    "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff", "mihevc_send_frame_deint", "mihevc_k_deinterlace",
 )
 
 _lib = None
@@ -218,6 +226,8 @@ def load() -> C.CDLL:
     lib.mihevc_send_frame_scaled.argtypes = [vp, C.POINTER(ScaleSrc), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_scale_source.argtypes = [i32, C.POINTER(ScaleSrc), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.mihevc_k_scene_diff.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.mihevc_send_frame_deint.argtypes = [vp, C.POINTER(Deint), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_deinterlace.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

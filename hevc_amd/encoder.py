@@ -212,6 +212,27 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_scaled(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_scaled")
 
+    def send_deint(self, y, u, v, tff: bool = True, field_rate: bool = False, asynchronous: bool = False, pts: Optional[int] = None):
+        """mihevc_send_frame_deint: a woven interlaced frame of the session's display size, planar 4:2:0 at the session's depth, deinterlaced on the device
+        (DESIGN.md §6f).  tff: the top field (even rows) is the first in time.  field_rate: two pictures per frame, pts and pts + 1: the session is opened at
+        twice the frame rate and pts counts field periods (the default pts advances by 2).  The frame's picture(s) come out once the next frame has arrived,
+        the last frame's with flush().  Width even, height a multiple of 4, both at least 16; field order and rate are those of the first call.  numpy planes
+        are checked for shape and type here; torch tensors on the device are read where they are (MIHEVC_SRC_DEVICE) under the rules of send_fmt.
+        asynchronous (host planes): the rules of send_async."""
+        c = self.cfg
+        mode = _lib.Deint(int(bool(tff)), int(bool(field_rate)))
+        planes = [y, u, v]
+        shapes = [(c.height, c.width)] + [(c.height // 2, c.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of the session")
+        es = 1 if c.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(mode, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_deint")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + (2 if field_rate else 1)
+        self._check(self._lib.mihevc_send_frame_deint(self._s, C.byref(mode), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_deint")
+
     def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
         Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
@@ -633,16 +654,45 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
-                devices=None, row_split: bool = False, native_rgb: bool = False, size=None) -> int:
+                devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
+                tff: Optional[bool] = None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
     probed matrix, BT.709 when that is `gbr` or unknown.  size=(w, h): the session, its level and the MP4 track take this size and every picture of the source,
-    delivered at its own size, is scaled down on the device (Encoder.send_scaled): planar 4:2:0 sources on one device only, per axis at most 4:1."""
+    delivered at its own size, is scaled down on the device (Encoder.send_scaled): planar 4:2:0 sources on one device only, per axis at most 4:1.
+    deinterlace: the source's frames are woven interlaced frames, deinterlaced on the device (Encoder.send_deint).  'frame': one picture per
+    frame; 'field': one per field, so the session, its level, the rate figures and the MP4 track run at twice the frame rate; 'auto': 'frame' when the source
+    says it is interlaced (the y4m header's It / Ib tag, else ffprobe's field_order), nothing otherwise.  tff: the field order, None to take the source's word
+    (top field first when it has none).  Planar 4:2:0 sources at the session's depth on one device; not together with size= or native_rgb."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
 
+    deint = None            # (top field first, field rate) once deinterlacing is on
+    clip_info = info        # what the clip is opened with: the source's own rate and frame count
+    if deinterlace is not None:
+        if deinterlace not in ('frame', 'field', 'auto') or size is not None or native_rgb or (devices and len(devices) > 1):
+            logger.error("%s: deinterlace=%r takes 'frame', 'field' or 'auto', one device, and neither size= nor native_rgb", Path(file_path).name, deinterlace)
+            return 1
+        order = tff
+        if order is None:
+            suffix = Path(file_path).suffix.lower()
+            if suffix == '.y4m':
+                probe_clip = yuvio.open_clip(Path(file_path))
+                order = {'t': True, 'b': False}.get(probe_clip.interlace)
+                probe_clip.close()
+            elif suffix != '.yuv':
+                from .probe import probe_field_order
+                order = probe_field_order(Path(file_path))
+            if order is None and deinterlace != 'auto':
+                order = True
+        if order is not None:
+            deint = (bool(order), deinterlace == 'field')
+        if deint and deint[1]:
+            info = copy.copy(info)
+            info.fps = float(info.fps or 30.0) * 2
+            info.nb_frames = int(getattr(info, 'nb_frames', 0) or 0) * 2
     src_size = (int(info.width), int(info.height))
     if size is not None:        # rate, level and track follow the coded size; the clip below is still opened at the source's own
         src_info, info = info, copy.copy(info)
@@ -650,7 +700,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
     sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
-    clip = yuvio.open_any(Path(file_path), info if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
+    clip = yuvio.open_any(Path(file_path), (clip_info if deint else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
     mux = None
     ok = False
     try:
@@ -673,7 +723,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if fmt is not None and sliced:
             logger.error("%s: a %r source cannot be split by rows", Path(file_path).name, fmt)
             return 1
-        total = clip.n_frames or total_frames
+        if deint and (fmt is not None or sliced or cfg.width % 2 or cfg.height % 4 or min(cfg.width, cfg.height) < 16):
+            logger.error("%s: deinterlace= takes a planar 4:2:0 source at the session's depth, width even, height a multiple of 4 (%r, %dx%d)",
+                         Path(file_path).name, fmt, cfg.width, cfg.height)
+            return 1
+        total = (clip.n_frames or total_frames) * (2 if deint and deint[1] else 1)
         wants_audio = bool(info.audio_channels and info.audio_channels > 0) and Path(file_path).suffix.lower() not in ('.y4m', '.yuv')
         video_path = Path(out_path).with_suffix('.video.mp4') if wants_audio else Path(out_path)
         mux = mp4.Mp4Writer(video_path, cfg)
@@ -713,7 +767,9 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 for i, planes in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    if size is not None:
+                    if deint:
+                        enc.send_deint(*planes, tff=deint[0], field_rate=deint[1], pts=i * (2 if deint[1] else 1))
+                    elif size is not None:
                         enc.send_scaled(src_size[0], src_size[1], *planes, bit_depth=src_depth, pts=i)
                     elif fmt is None:
                         enc.send(*planes, pts=i)

@@ -152,6 +152,25 @@ def probe_raw(file_path: Path) -> Optional[VideoInfo]:
         clip.close()
 
 
+def top_field_first_of(field_order: str) -> Optional[bool]:
+    """ffprobe's field_order -> True (top field first: 'tt', 'tb'), False (bottom first: 'bb', 'bt'), None (progressive, unknown, absent: not interlaced)"""
+    return {'tt': True, 'tb': True, 'bb': False, 'bt': False}.get((field_order or '').strip().lower())
+
+
+def probe_field_order(file_path: Path) -> Optional[bool]:
+    """top_field_first_of the first video stream's field_order as ffprobe reports it; None when there is none, or no ffprobe.  Beside VideoInfo, which keeps the
+    reference's fields: only encode_file(deinterlace='auto') asks."""
+    try:
+        out = subprocess.run(['ffprobe', '-v', 'quiet', '-print_format', 'json', '-show_streams', str(file_path)],
+                             capture_output=True, text=True, check=True, encoding='utf-8')
+        for st in json.loads(out.stdout).get('streams', []):
+            if st.get('codec_type') == 'video':
+                return top_field_first_of(st.get('field_order', ''))
+    except Exception as exc:
+        logger.debug('field order probe failed for %s: %s', Path(file_path).name, exc)
+    return None
+
+
 def probe_media(file_path: Path) -> VideoInfo:
     """ffprobe the file; raw .y4m/.yuv are read natively; any error -> the reference's fallback."""
     file_path = Path(file_path)

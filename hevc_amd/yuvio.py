@@ -46,7 +46,8 @@ class Clip:
     frames are not planar 4:2:0 at that depth (frames() then yields planes in the source's own shapes), else None."""
 
     def __init__(self, path: Path, width: int, height: int, fps: float, bit_depth: int, n_frames: int, data_offset: int,
-                 frame_header: int = 0, hdr: bool = False, src_format=None):
+                 frame_header: int = 0, hdr: bool = False, src_format=None, interlace: str = 'p'):
+        self.interlace = interlace      # the y4m interlace tag: 'p' progressive, 't' top field first, 'b' bottom field first ('m' mixed); raw .yuv: 'p'
         self.path, self.width, self.height, self.fps, self.bit_depth = Path(path), width, height, fps, bit_depth
         self.n_frames, self.data_offset, self.frame_header, self.hdr = n_frames, data_offset, frame_header, hdr
         self.src_format = src_format
@@ -84,7 +85,7 @@ def open_clip(path: Path) -> Clip:
         if not header.startswith(b'YUV4MPEG2'):
             raise ValueError('not a YUV4MPEG2 file')
         w = h = 0
-        fps, depth, chroma = 30.0, 8, 420
+        fps, depth, chroma, interlace = 30.0, 8, 420, 'p'
         for tok in header.split()[1:]:
             t = tok.decode()
             if t[0] == 'W':
@@ -94,6 +95,8 @@ def open_clip(path: Path) -> Clip:
             elif t[0] == 'F':
                 n, d = t[1:].split(':')
                 fps = int(n) / int(d) if int(d) else 30.0
+            elif t[0] == 'I' and len(t) == 2:
+                interlace = t[1]
             elif t[0] == 'C':
                 m = _Y4M_COLOUR.match(t)
                 if not m:
@@ -102,7 +105,8 @@ def open_clip(path: Path) -> Clip:
         depth, fmt = _planar_format(chroma, depth)
         fb = fmt.frame_bytes(w, h) if fmt is not None else w * h * 3 // 2 * (2 if depth > 8 else 1)
         n_frames = (path.stat().st_size - len(header)) // (fb + 6)
-        return Clip(path, w, h, fps, depth, n_frames, len(header), frame_header=6, hdr=depth > 8 and 'hdr' in path.stem.lower(), src_format=fmt)
+        return Clip(path, w, h, fps, depth, n_frames, len(header), frame_header=6, hdr=depth > 8 and 'hdr' in path.stem.lower(), src_format=fmt,
+                    interlace=interlace)
     m = _YUV_NAME.search(path.stem)
     if not m:
         raise ValueError('raw .yuv needs <stem>_<W>x<H>_<fps>[_422|_444][_<N>bit][_hdr].yuv')
@@ -198,13 +202,17 @@ def open_any(path: Path, info=None, native_formats: bool = True, rgb_formats: bo
     return _PipeClip(path, info, native_formats, rgb_formats)
 
 
-def write_y4m(path: Path, frames, width: int, height: int, fps=30, bit_depth: int = 8, chroma: int = 420, src_depth: Optional[int] = None):
-    """chroma: 420 / 422 / 444, the frames' planes in that shape; src_depth: the samples' own depth (9 .. 16) when it is not bit_depth's 8 or 10"""
+def write_y4m(path: Path, frames, width: int, height: int, fps=30, bit_depth: int = 8, chroma: int = 420, src_depth: Optional[int] = None,
+              interlace: str = 'p'):
+    """chroma: 420 / 422 / 444, the frames' planes in that shape; src_depth: the samples' own depth (9 .. 16) when it is not bit_depth's 8 or 10; interlace: the
+    header's I tag, 'p' progressive, 't' / 'b' woven frames with the top / bottom field first"""
+    if interlace not in ('p', 't', 'b'):
+        raise ValueError(f'interlace tag {interlace!r}')
     fr = Fraction(str(fps)).limit_denominator(1001)
     depth = src_depth if src_depth else (10 if bit_depth > 8 else 8)
     tag = f'C{chroma}p{depth}' if depth > 8 else ('C420jpeg' if chroma == 420 else f'C{chroma}')
     with open(path, 'wb') as f:
-        f.write(f'YUV4MPEG2 W{width} H{height} F{fr.numerator}:{fr.denominator} Ip A1:1 {tag}\n'.encode())
+        f.write(f'YUV4MPEG2 W{width} H{height} F{fr.numerator}:{fr.denominator} I{interlace} A1:1 {tag}\n'.encode())
         dt = np.dtype('<u2') if depth > 8 else np.uint8
         for y, u, v in frames:
             f.write(b'FRAME\n')

@@ -267,6 +267,29 @@ typedef struct mihevc_scale_src {
  * slice_count > 1.  MIHEVC_ESTATE after flush. */
 int  mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, const void *y, const void *u, const void *v,
                               int pitch_y, int pitch_c, int64_t pts, int flags);
+/* ---- added under ABI 6: INTERLACED sources (symbols only) ----
+ * A woven interlaced frame of the session's DISPLAY size, planar 4:2:0 at cfg.bit_depth (uint8 at 8 bit, else little-endian uint16, values above
+ * 2^bit_depth - 1 clamped), deinterlaced on the device into progressive pictures by a motion-adaptive, edge-directed filter in the manner of yadif with an exact
+ * integer definition (hevc_amd/csrc/kernels/deint.h states the arithmetic).  The rows of one field are kept, the others are interpolated from the
+ * frame before, the frame itself and the frame after; the first frame stands in for its missing predecessor and the last one for its missing successor.
+ * Frame-rate mode gives one picture per frame (the first field's rows kept), field-rate mode two: the first field's with the frame's pts, the second field's with
+ * pts + 1, so the caller numbers pts in field periods and opens the session at twice the frame rate.  The stream stays progressive (HEVC has no interlaced
+ * coding tools).  Not covered: inverse telecine and field matching, other filters, other layouts or depths than the session's, scaling in the same pass,
+ * parity changes inside a clip, sliced sessions, pic_struct signalling. */
+typedef struct mihevc_deint {
+    int32_t tff;          /* 1: top field first, 0: bottom field first */
+    int32_t field_rate;   /* 0: one picture per frame; 1: two (pts, pts + 1) */
+    int32_t reserved[6];  /* 0 */
+} mihevc_deint;
+/* pitch_y, pitch_c: in elements.  The frame is copied into a ring of three source-size pictures the session owns (allocated at the first call), host planes on
+ * the upload stream, device planes device to device.  Flags and ownership are those of mihevc_send_frame_fmt: host planes may be reused on return unless
+ * MIHEVC_SRC_ASYNC is set, device planes (MIHEVC_SRC_DEVICE) after mihevc_sync_uploads or mihevc_flush.  A frame's picture(s) are produced when the NEXT frame
+ * arrives, the last frame's by mihevc_flush; mihevc_stats.frames_in counts pictures.  MIHEVC_EINVAL, decided before any device call and leaving the session
+ * usable: NULL d or plane, tff or field_rate outside {0, 1}, non-zero reserved, a tff or field_rate other than that of the session's first deinterlaced frame,
+ * cfg.width odd, cfg.height not a multiple of 4, either below 16, a pitch smaller than the plane, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after
+ * flush; and every OTHER entry that sends a frame returns MIHEVC_ESTATE while a deinterlaced frame is pending (sent, its pictures not yet produced). */
+int  mihevc_send_frame_deint(mihevc_session *s, const mihevc_deint *d, const void *y, const void *u, const void *v,
+                             int pitch_y, int pitch_c, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -416,6 +439,14 @@ int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p
  * (MIHEVC_EINVAL: what mihevc_send_frame_scaled refuses, an out_bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
 int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
                           int dst_width, int dst_height, int out_bit_depth, void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  The deinterlacer of mihevc_send_frame_deint alone (the session's kernel), host buffers in and out: prev / cur / next name the Y, Cb and Cr
+ * planes of three frames of width x height samples at bit_depth (they may name the same planes), one pitch_y and one pitch_c for all of them, in elements; keep:
+ * parity of the rows that are kept, second: 1 when that field is the later one of its frame; out_* are planes of the CODED size as in mihevc_k_convert_source.
+ * Validated first (MIHEVC_EINVAL: a NULL plane, width odd, height not a multiple of 4, either below 16, a short pitch, a bit_depth other than 8 or 10, keep or
+ * second outside {0, 1}), then MIHEVC_ENODEV without a device */
+int mihevc_k_deinterlace(int device, const void *const prev[3], const void *const cur[3], const void *const next[3],
+                         int width, int height, int pitch_y, int pitch_c, int bit_depth, int keep, int second,
+                         void *out_y, void *out_u, void *out_v);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
