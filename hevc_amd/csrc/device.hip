@@ -663,7 +663,7 @@ __global__ __launch_bounds__(NT) void k_transform_blocks(const int16_t *res, int
             int x = i & 31, y = i >> 5, blk = first + (y >> log2n) * (32 >> log2n) + (x >> log2n);
             if (blk < n_blocks) s.res[i] = res[(size_t)blk * n * n + (y & (n - 1)) * n + (x & (n - 1))];
         }
-        for (int i = tid; i < 1536; i += NT) { SampleLoc l = locate(s, i); l.scan = scan; s.desc[i] = pack_loc(l); }
+        fill_desc(s, whole_ctu(), tid, [&](const SampleLoc &) { return scan; });
     });
     residual_pipeline(ex, s, qp, qp, bit_depth, whole_ctu(), 0, sign_hide);
     ex.phase([&](int tid) {

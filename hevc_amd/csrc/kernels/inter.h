@@ -407,7 +407,7 @@ template <typename T> struct InterShared {
     unsigned tu_dc[3][16], tu_dz[3][16], tu_bits[3][16], tu_zero[3];   // RD zero-out: per TU (plane, first 8x8 tile) SSE coded / zeroed, level bits
     // the motion-compensation windows T winY[(40 + 2R)^2 (stride padded)], T winU[(24 + R)^2], T winV[...]: inside rs.scratch or behind this struct (inter_lds)
 };
-// the fractional search's share of rs.scratch (dwords): the pair exchange, 8 per lane, then one SATD share per lane
+// the lane-pair SATDs' share of rs.scratch (satd_lane_pairs: the fractional search and the tree's integer vectors), dwords: the pair exchange, 8 per lane, then one SATD share per lane
 constexpr int FRAC_PAIR_SUM = 8 * NT;
 constexpr int FRAC_SCRATCH = FRAC_PAIR_SUM + NT;
 static_assert(FRAC_SCRATCH <= (int)(sizeof(ResidualShared::scratch) / 4), "the fractional search's exchange must fit rs.scratch");
@@ -691,6 +691,110 @@ template <typename T> DEV int luma_tile_int(const T *win, int i00, int ws, const
     }
     return hadamard8_satd(m);
 }
+// 4 consecutive samples base[idx .. idx + 3] of a window (load_row8's narrower form: aligned dword reads inside the span load_row8 reads for the tile)
+DEV void load_row4(const uint8_t *base, int idx, int (&px)[4])
+{
+    const int off = idx & 3;
+    const uint8_t *p = base + (idx - off);
+    const uint32_t r = align_bytes(load_u32_aligned(p + 4), load_u32_aligned(p), off);
+#pragma unroll
+    for (int i = 0; i < 4; i++) px[i] = (int)((r >> (8 * i)) & 255);
+}
+DEV void load_row4(const uint16_t *base, int idx, int (&px)[4])
+{
+    const int off = idx & 1;
+    const uint16_t *p = base + (idx - off);
+    const uint32_t d0 = load_u32_aligned(p), d1 = load_u32_aligned(p + 2), d2 = load_u32_aligned(p + 4);
+    const uint32_t r0 = align_bytes(d1, d0, 2 * off), r1 = align_bytes(d2, d1, 2 * off);
+    px[0] = (int)(r0 & 65535); px[1] = (int)(r0 >> 16); px[2] = (int)(r1 & 65535); px[3] = (int)(r1 >> 16);
+}
+// Difference (source - window) of the 8 rows x 4 columns whose first sample is window element i00: an INTEGER vector, the prediction is the window itself
+template <typename T> DEV void luma_half_diff_int(const T *win, int i00, int ws, const T *src, int src_stride, int (&m)[8][4])
+{
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        int px[4];
+        load_row4(win, i00 + j * ws, px);
+#pragma unroll
+        for (int i = 0; i < 4; i++) m[j][i] = (int)src[j * src_stride + i] - px[i];
+    }
+}
+
+// ---- SATD of 8x8 tiles on lane PAIRS: lanes 2u and 2u + 1 (one wave) own columns 0 .. 3 and 4 .. 7 of item u.  diff(tid, m) fills the lane's 8 rows x 4 columns
+// of differences and returns true, or returns false when the lane has no item (both lanes of a pair alike).  Afterwards rs.scratch[FRAC_PAIR_SUM + tid] holds the lane's
+// share: the tile's SATD, the value hadamard8_satd gives, is (share of 2u + share of 2u + 1 + 2) >> 2.  Wave-local steps, no workgroup barrier: a lane keeps the rows it
+// finishes (4 half .. 4 half + 3) in registers and passes only the other four rows to its partner through rs.scratch (8 dwords a lane)
+struct SatdKept { uint32_t v[2][4]; bool on; };
+template <typename T, class Ex, class Diff> DEV void satd_lane_pairs(Ex &ex, ResidualShared &rs, Diff &&diff)
+{
+    wave_chain(ex, [&](int tid) -> SatdKept {
+        const int half = tid & 1;
+        SatdKept kept{};
+        int m[8][4];
+        if (!diff(tid, m)) return kept;
+        kept.on = true;
+        // Differences are 9 bits at 8 bit, 11 at 10 bit; the five butterfly stages computed here grow them by 5: 255 x 32 and 1023 x 32 = 32736 both fit 16 bits, two values
+        // a dword (v_pk_add / sub_i16).  Rows 2r and
+        // 2r + 1 of a column share a dword: the butterflies between rows 2 and 4 apart and between columns 1 and 2 apart are whole-dword operations (4 stages x 16
+        // packed operations; the one-value form took 160), the stage across the halves follows the exchange, and the stage INSIDE a dword is never computed:
+        // it is the last one, and |a + b| + |a - b| = 2 max(|a|, |b|).
+        uint32_t P[4][4];
+#pragma unroll
+        for (int r2 = 0; r2 < 4; r2++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) P[r2][c] = perm_bytes((uint32_t)m[2 * r2 + 1][c], (uint32_t)m[2 * r2][c], 0x05040100u);
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const uint32_t a0 = pk_add16(P[0][c], P[1][c]), a1 = pk_sub16(P[0][c], P[1][c]), a2 = pk_add16(P[2][c], P[3][c]), a3 = pk_sub16(P[2][c], P[3][c]);
+            P[0][c] = pk_add16(a0, a2); P[1][c] = pk_add16(a1, a3); P[2][c] = pk_sub16(a0, a2); P[3][c] = pk_sub16(a1, a3);
+        }
+        uint32_t o[4][4];      // chunk r2 = rows 2 r2, 2 r2 + 1 of the four columns
+#pragma unroll
+        for (int r2 = 0; r2 < 4; r2++) {
+            const uint32_t p0 = pk_add16(P[r2][0], P[r2][1]), p1 = pk_sub16(P[r2][0], P[r2][1]), p2 = pk_add16(P[r2][2], P[r2][3]), p3 = pk_sub16(P[r2][2], P[r2][3]);
+            o[r2][0] = pk_add16(p0, p2); o[r2][1] = pk_add16(p1, p3); o[r2][2] = pk_sub16(p0, p2); o[r2][3] = pk_sub16(p1, p3);
+        }
+        uint32_t *x = rs.scratch + tid * 8;
+        const int sw = ((tid >> 2) ^ (tid >> 3)) & 1;
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            uint32_t send[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) { kept.v[c][i] = half ? o[2 + c][i] : o[c][i]; send[i] = half ? o[c][i] : o[2 + c][i]; }
+            store_x4(x + 4 * (c ^ sw), send);
+        }
+        return kept;
+    }, [&](int tid, const SatdKept &kept) {      // the last butterfly stage across the halves: this lane takes rows 4 half .. 4 half + 3
+        if (!kept.on) return;
+        // the partner's chunks of these rows.  Slot c of lane l sits at dword 8 l + 4 (c ^ sw), sw = bit 2 ^ bit 3 of l (the same for both lanes of a
+        // pair): the eight-lane groups of ds_write_b128 and the sixteen-lane groups of ds_read_b128 then touch every bank once
+        const uint32_t *xp = rs.scratch + (tid ^ 1) * 8;
+        const int sw = ((tid >> 2) ^ (tid >> 3)) & 1;
+        unsigned sum = 0;
+        // packed form: the stage across the halves on whole dwords, then 2 max(|lo|, |hi|) per dword for the stage inside it + the absolute sum.  At 8 bit |values| <= 255 x 32
+        // here, so eight maxima still fit the 16-bit lanes of an accumulator; at 10 bit (1023 x 32) every maximum is widened.  |a + b| and |a - b| do not
+        // depend on which half is a: the lane's own rows and its partner's enter in either order
+        uint32_t acc[2] = {0, 0};
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            uint32_t vb[4];
+            load_x4(xp + 4 * (c ^ sw), vb);
+            const uint32_t (&va)[4] = kept.v[c];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+#pragma unroll
+                for (int sgn = 0; sgn < 2; sgn++) {
+                    const uint32_t v = sgn ? pk_sub16(va[i], vb[i]) : pk_add16(va[i], vb[i]);
+                    const uint32_t av = pk_max_i16(v, pk_sub16(0u, v));                  // |lo|, |hi|
+                    const uint32_t mx = pk_max_i16(av, (av >> 16) | (av << 16));          // both lanes: max(|lo|, |hi|)
+                    if constexpr (sizeof(T) == 1) acc[c] = pk_add16(acc[c], mx); else sum += mx & 0xffffu;
+                }
+            }
+        }
+        if constexpr (sizeof(T) == 1) sum = (acc[0] & 0xffffu) + (acc[1] & 0xffffu);
+        rs.scratch[FRAC_PAIR_SUM + tid] = 2u * sum;
+    });
+}
 
 // the search centre's motion-compensation windows: picture position, in its plane, of the first sample of the luma and of the chroma windows
 struct WinOrigin { int yx, yy, cx, cy; };
@@ -734,22 +838,31 @@ template <typename T, class Ex> DEV void inter_load(Ex &ex, InterShared<T> &s, c
 // pass per tree level (the search was 43 % of this kernel: profiles/r01)
 template <typename T, class Ex> DEV void inter_tree(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
 {
-    ex.phase([&](int tid) {
-        for (int u = tid; u < 3 * 16; u += NT) {
-            int level = u >> 4, t = u & 15;
-            int txp = t & 3, typ = t >> 2, node = node_of_tile(level, txp, typ);
-            if (!s.valid[node]) continue;
-            // identical vectors give identical tile SATDs: let the finest level that shares the vector do the work
-            int al = level;
-            for (int fl = 2; fl > level; fl--) {
-                int fn = node_of_tile(fl, txp, typ);
-                if (s.valid[fn] && s.mvx[fn] == s.mvx[node] && s.mvy[fn] == s.mvy[node]) { al = fl; break; }
-            }
-            s.alias[level][t] = (uint8_t)al;
-            if (al != level) continue;
-            int px = ctx.x0 + txp * 8 + (s.mvx[node] >> 2) - ctx.o0.yx, py = ctx.y0 + typ * 8 + (s.mvy[node] >> 2) - ctx.o0.yy;
-            s.satd[level][0][t] = luma_tile_int<T>(ctx.win_y, py * ctx.wys + px, ctx.wys, s.src + ctu_index(0, txp * 8, typ * 8), 32);
+    // 3 levels x 16 tiles x 2 column halves = 96 lanes (one lane a tile, a whole unpacked 8x8 Hadamard each, was a stretch of 48 lanes of wave 0 with the other waves
+    // at the barrier).  Both lanes of a pair work the alias out for themselves; the even one records it
+    satd_lane_pairs<T>(ex, s.rs, [&](int tid, int (&m)[8][4]) {
+        const int u = tid >> 1, half = tid & 1, level = u >> 4, t = u & 15;
+        if (u >= 3 * 16) return false;
+        const int txp = t & 3, typ = t >> 2, node = node_of_tile(level, txp, typ);
+        if (!s.valid[node]) return false;
+        // identical vectors give identical tile SATDs: let the finest level that shares the vector do the work
+        int al = level;
+        for (int fl = 2; fl > level; fl--) {
+            int fn = node_of_tile(fl, txp, typ);
+            if (s.valid[fn] && s.mvx[fn] == s.mvx[node] && s.mvy[fn] == s.mvy[node]) { al = fl; break; }
         }
+        if (!half) s.alias[level][t] = (uint8_t)al;
+        if (al != level) return false;
+        const int px = ctx.x0 + txp * 8 + 4 * half + (s.mvx[node] >> 2) - ctx.o0.yx, py = ctx.y0 + typ * 8 + (s.mvy[node] >> 2) - ctx.o0.yy;
+        luma_half_diff_int<T>(ctx.win_y, py * ctx.wys + px, ctx.wys, s.src + ctu_index(0, txp * 8 + 4 * half, typ * 8), 32, m);
+        return true;
+    });
+    ex.phase([&](int tid) {      // (the pair's lanes sit in one wave: its shares are there without a barrier; the SATDs are read across waves, behind this one)
+        const int u = tid >> 1, level = u >> 4, t = u & 15;
+        if ((tid & 1) || u >= 3 * 16) return;
+        const int node = node_of_tile(level, t & 3, t >> 2);
+        if (!s.valid[node] || s.alias[level][t] != level) return;
+        s.satd[level][0][t] = (int)((s.rs.scratch[FRAC_PAIR_SUM + tid] + s.rs.scratch[FRAC_PAIR_SUM + tid + 1] + 2) >> 2);
     });
     // every (level, tile) lane adds its tile's SATD (its own or the finer level's it aliases) to the node's sum
     ex.phase([&](int tid) {
@@ -797,83 +910,15 @@ template <typename T, class Ex> DEV void inter_refine(Ex &ex, InterShared<T> &s,
 {
     for (int round = 0; round < 2; round++) {
         const int step = round == 0 ? 2 : 1;
-        // 16 tiles x 8 ring positions x 2 column halves = the whole workgroup.  Wave-local steps: both lanes of a pair sit in one wave.  A lane keeps the
-        // rows it finishes (4 half .. 4 half + 3) in registers and passes only the other four rows to its partner through rs.scratch
-        struct Kept { uint32_t v[2][4]; };
-        wave_chain(ex, [&](int tid) -> Kept {
+        // 16 tiles x 8 ring positions x 2 column halves = the whole workgroup
+        satd_lane_pairs<T>(ex, s.rs, [&](int tid, int (&m)[8][4]) {
             const int u = tid >> 1, half = tid & 1, k = kRingSlot[u >> 4], t = u & 15;
-            Kept kept{};
-            if (!s.rs.tu_log2[t]) return kept;
+            if (!s.rs.tu_log2[t]) return false;
             const int txp = t & 3, typ = t >> 2, node = s.tile_node[t];
             const int mx = s.mvx[node] + kOff[k][0] * step, my = s.mvy[node] + kOff[k][1] * step;
             const int px = ctx.x0 + txp * 8 + 4 * half + (mx >> 2) - o.yx, py = ctx.y0 + typ * 8 + (my >> 2) - o.yy;
-            int m[8][4];
             luma_half_diff((const T *)ctx.win_y, py * ctx.wys + px, ctx.wys, mx & 3, my & 3, ctx.bd, (const T *)(s.src + typ * 8 * 32 + txp * 8 + 4 * half), 32, m);
-            {
-                // Differences are 9 bits at 8 bit, 11 at 10 bit; the five butterfly stages computed here grow them by 5: 255 x 32 and 1023 x 32 = 32736 both fit 16 bits, two values
-                // a dword (v_pk_add / sub_i16).  Rows 2r and
-                // 2r + 1 of a column share a dword: the butterflies between rows 2 and 4 apart and between columns 1 and 2 apart are whole-dword operations (4 stages x 16
-                // packed operations; the one-value form took 160), the stage across the halves follows the exchange, and the stage INSIDE a dword is never computed:
-                // it is the last one, and |a + b| + |a - b| = 2 max(|a|, |b|).
-                uint32_t P[4][4];
-#pragma unroll
-                for (int r2 = 0; r2 < 4; r2++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) P[r2][c] = perm_bytes((uint32_t)m[2 * r2 + 1][c], (uint32_t)m[2 * r2][c], 0x05040100u);
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const uint32_t a0 = pk_add16(P[0][c], P[1][c]), a1 = pk_sub16(P[0][c], P[1][c]), a2 = pk_add16(P[2][c], P[3][c]), a3 = pk_sub16(P[2][c], P[3][c]);
-                    P[0][c] = pk_add16(a0, a2); P[1][c] = pk_add16(a1, a3); P[2][c] = pk_sub16(a0, a2); P[3][c] = pk_sub16(a1, a3);
-                }
-                uint32_t o[4][4];      // chunk r2 = rows 2 r2, 2 r2 + 1 of the four columns
-#pragma unroll
-                for (int r2 = 0; r2 < 4; r2++) {
-                    const uint32_t p0 = pk_add16(P[r2][0], P[r2][1]), p1 = pk_sub16(P[r2][0], P[r2][1]), p2 = pk_add16(P[r2][2], P[r2][3]), p3 = pk_sub16(P[r2][2], P[r2][3]);
-                    o[r2][0] = pk_add16(p0, p2); o[r2][1] = pk_add16(p1, p3); o[r2][2] = pk_sub16(p0, p2); o[r2][3] = pk_sub16(p1, p3);
-                }
-                uint32_t *x = s.rs.scratch + tid * 8;
-                const int sw = ((tid >> 2) ^ (tid >> 3)) & 1;
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-                    uint32_t send[4];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) { kept.v[c][i] = half ? o[2 + c][i] : o[c][i]; send[i] = half ? o[c][i] : o[2 + c][i]; }
-                    store_x4(x + 4 * (c ^ sw), send);
-                }
-            }
-            return kept;
-        }, [&](int tid, const Kept &kept) {      // the last butterfly stage across the halves: this lane takes rows 4 half .. 4 half + 3
-            const int u = tid >> 1, t = u & 15;
-            if (!s.rs.tu_log2[t]) return;
-            // the partner's chunks of these rows.  Slot c of lane l sits at dword 8 l + 4 (c ^ sw), sw = bit 2 ^ bit 3 of l (the same for both lanes of a
-            // pair): the eight-lane groups of ds_write_b128 and the sixteen-lane groups of ds_read_b128 then touch every bank once
-            const uint32_t *xp = s.rs.scratch + (tid ^ 1) * 8;
-            const int sw = ((tid >> 2) ^ (tid >> 3)) & 1;
-            unsigned sum = 0;
-            {
-                // packed form: the stage across the halves on whole dwords, then 2 max(|lo|, |hi|) per dword for the stage inside it + the absolute sum.  At 8 bit |values| <= 255 x 32
-                // here, so eight maxima still fit the 16-bit lanes of an accumulator; at 10 bit (1023 x 32) every maximum is widened.  |a + b| and |a - b| do not
-                // depend on which half is a: the lane's own rows and its partner's enter in either order
-                uint32_t acc[2] = {0, 0};
-#pragma unroll
-                for (int c = 0; c < 2; c++) {
-                    uint32_t vb[4];
-                    load_x4(xp + 4 * (c ^ sw), vb);
-                    const uint32_t (&va)[4] = kept.v[c];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-#pragma unroll
-                        for (int sgn = 0; sgn < 2; sgn++) {
-                            const uint32_t v = sgn ? pk_sub16(va[i], vb[i]) : pk_add16(va[i], vb[i]);
-                            const uint32_t av = pk_max_i16(v, pk_sub16(0u, v));                  // |lo|, |hi|
-                            const uint32_t mx = pk_max_i16(av, (av >> 16) | (av << 16));          // both lanes: max(|lo|, |hi|)
-                            if constexpr (sizeof(T) == 1) acc[c] = pk_add16(acc[c], mx); else sum += mx & 0xffffu;
-                        }
-                    }
-                }
-                if constexpr (sizeof(T) == 1) sum = (acc[0] & 0xffffu) + (acc[1] & 0xffffu);
-                s.rs.scratch[FRAC_PAIR_SUM + tid] = 2u * sum;
-            }
+            return true;
         });
         ex.phase([&](int tid) {
             const int u = tid >> 1, k = kRingSlot[u >> 4], t = u & 15;
@@ -1056,9 +1101,21 @@ template <typename T, class Ex> DEV void inter_predict_uni(Ex &ex, InterShared<T
 template <typename T, class Ex> DEV void inter_residual(Ex &ex, InterShared<T> &s, const InterArgs<T> &a, const InterCtx<T> &ctx)
 {
     ex.phase([&](int tid) {
-        for (int i = tid; i < CTU_SAMPLES; i += NT) {
-            s.rs.res[i] = (int16_t)((int)s.src[i] - (int)s.pred[i]);
-            s.rs.desc[i] = pack_loc(locate(s.rs, i));
+        // lane k < 192 owns 2x4 block k, the unit residual_pipeline works on (a block never straddles a TU): one TU lookup, the block's descriptor at its origin,
+        // and its two rows of differences as packed 16-bit pairs
+        const Region rg = whole_ctu();
+        for (int k = tid; k < CTU_SAMPLES / 8; k += NT) {
+            const int idx = rg.block_index(k);
+            const SampleLoc l = locate(s.rs, idx);
+            s.rs.desc[idx] = pack_loc(l);
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int at = idx + j * l.stride;
+                uint32_t sv[2], pv[2];
+                load4_pk(s.src + at, sv); load4_pk(s.pred + at, pv);
+                const uint32_t d[2] = {pk_sub16(sv[0], pv[0]), pk_sub16(sv[1], pv[1])};
+                store_x2(s.rs.res + at, d);
+            }
         }
         if (tid < 48) { s.tu_dc[tid >> 4][tid & 15] = 0; s.tu_dz[tid >> 4][tid & 15] = 0; s.tu_bits[tid >> 4][tid & 15] = 0; }
         if (tid < 3) s.tu_zero[tid] = 0;
@@ -1070,23 +1127,35 @@ template <typename T, class Ex> DEV void inter_rd_zero_out(Ex &ex, InterShared<T
 {
     ex.phase([&](int tid) {
         const int maxv = (1 << ctx.bd) - 1;
-        for (int i = 4 * tid; i < CTU_SAMPLES; i += 4 * NT) {
-            SampleLoc l = locate(s.rs, i);
+        const Region rg = whole_ctu();
+        for (int k = tid; k < CTU_SAMPLES / 8; k += NT) {        // one lane per 2x4 block: one TU lookup and one atomic per sum for its eight samples
+            const int idx = rg.block_index(k);
+            const SampleLoc l = locate(s.rs, idx);
             if (!l.log2n || !((s.rs.cbf[l.plane] >> l.tile0) & 1)) continue;
             unsigned dc = 0, dz = 0;
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int sv = (int)s.src[i + j], pv = (int)s.pred[i + j], d0 = sv - pv, d1 = sv - clip3(0, maxv, pv + s.rs.res[i + j]);
-                dz += (unsigned)(d0 * d0); dc += (unsigned)(d1 * d1);
+            for (int j = 0; j < 2; j++) {
+                const int at = idx + j * l.stride;
+                uint32_t sv[2], pv[2], rv[2];
+                load4_pk(s.src + at, sv); load4_pk(s.pred + at, pv); load4_pk(s.rs.res + at, rv);
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int sh = 16 * (i & 1), sm = (int)((sv[i >> 1] >> sh) & 0xffffu), pm = (int)((pv[i >> 1] >> sh) & 0xffffu), r = (int)(int16_t)(rv[i >> 1] >> sh);
+                    const int d0 = sm - pm, d1 = sm - clip3(0, maxv, pm + r);
+                    dz += (unsigned)(d0 * d0); dc += (unsigned)(d1 * d1);
+                }
             }
             if (dc) ex.atomic_add(&s.tu_dc[l.plane][l.tile0], dc);
             if (dz) ex.atomic_add(&s.tu_dz[l.plane][l.tile0], dz);
         }
-        for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {       // level bits per 4x4 sub-block, summed per TU
+        // level bits per 4x4 sub-block, summed per TU and kept for the rate estimate of inter_outputs (0 where there is no TU or no level); on the last 96 lanes, so
+        // that waves 0 and 1 have the blocks alone
+        if (tid >= NT - CTU_SUBBLOCKS) {
+            const int sb = tid - (NT - CTU_SUBBLOCKS);
             const SubBlock b = sub_block(sb);
-            SampleLoc l = locate(s.rs, b.at);
-            if (!l.log2n || !((s.rs.cbf[l.plane] >> l.tile0) & 1)) continue;
-            const int bits = subblock_bits_q4(s.rs.lvl + b.at, b.stride);
+            const SampleLoc l = locate(s.rs, b.at);
+            const int bits = l.log2n && ((s.rs.cbf[l.plane] >> l.tile0) & 1) ? subblock_bits_q4(s.rs.lvl + b.at, b.stride) : 0;
+            s.rs.post.sb_bits[sb] = bits;
             if (bits) ex.atomic_add(&s.tu_bits[b.plane][l.tile0], (unsigned)bits);
         }
     });
@@ -1099,9 +1168,14 @@ template <typename T, class Ex> DEV void inter_rd_zero_out(Ex &ex, InterShared<T
         if (jz <= jc) ex.atomic_or(&s.tu_zero[pl], 1u << t);
     });
     ex.phase([&](int tid) {
-        for (int i = tid; i < CTU_SAMPLES; i += NT) {
-            SampleLoc l = locate(s.rs, i);
-            if (l.log2n && ((s.tu_zero[l.plane] >> l.tile0) & 1)) { s.rs.lvl[i] = 0; s.rs.res[i] = 0; }
+        const Region rg = whole_ctu();
+        for (int k = tid; k < CTU_SAMPLES / 8; k += NT) {        // the dropped TUs' levels and residual, a 2x4 block a lane
+            const int idx = rg.block_index(k);
+            const SampleLoc l = locate(s.rs, idx);
+            if (!l.log2n || !((s.tu_zero[l.plane] >> l.tile0) & 1)) continue;
+            const uint32_t z[2] = {0, 0};
+#pragma unroll
+            for (int j = 0; j < 2; j++) { store_x2(s.rs.lvl + idx + j * l.stride, z); store_x2(s.rs.res + idx + j * l.stride, z); }
         }
         if (tid < 3) s.rs.cbf[tid] &= ~s.tu_zero[tid];       // (nothing in this phase reads cbf)
     });
@@ -1111,24 +1185,47 @@ template <typename T, class Ex, bool BI> DEV void inter_outputs(Ex &ex, InterSha
 {
     ex.phase([&](int tid) {
         const int maxv = (1 << ctx.bd) - 1;
-        for (int i = 4 * tid; i < CTU_SAMPLES; i += 4 * NT) {      // four samples of one row per lane (a TU is at least 4 wide)
-            SampleLoc l = locate(s.rs, i);
+        const Region rg = whole_ctu();
+        for (int k = tid; k < CTU_SAMPLES / 8; k += NT) {      // a 2x4 block per lane (a TU is at least 4x4: one lookup for its two rows of four samples)
+            const int idx = rg.block_index(k);
+            const SampleLoc l = locate(s.rs, idx);
             if (!l.log2n) continue;
-            int gx = to_plane(l.plane, ctx.x0) + l.x, gy = to_plane(l.plane, ctx.y0) + l.y, v[4];
+            const int gx = to_plane(l.plane, ctx.x0) + l.x, gy = to_plane(l.plane, ctx.y0) + l.y;
+            const bool levels = !a.sparse_coef || ((s.rs.cbf[l.plane] >> l.tile0) & 1);
+            unsigned sse = 0;
 #pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = clip3(0, maxv, (int)s.pred[i + j] + s.rs.res[i + j]);
-            store4(a.rec[l.plane].p + (ptrdiff_t)gy * a.rec[l.plane].stride + gx, v[0], v[1], v[2], v[3]);
-            if (a.ip) {
-                unsigned sse = 0;
+            for (int j = 0; j < 2; j++) {
+                const int at = idx + j * l.stride;
+                uint32_t pv[2], rv[2];
+                int v[4];
+                load4_pk(s.pred + at, pv); load4_pk(s.rs.res + at, rv);
 #pragma unroll
-                for (int j = 0; j < 4; j++) { const int d = (int)s.src[i + j] - v[j]; sse += (unsigned)(d * d); }
-                if (sse) ex.atomic_add(&s.ip_sse, (unsigned long long)sse);
+                for (int i = 0; i < 4; i++) v[i] = clip3(0, maxv, (int)((pv[i >> 1] >> (16 * (i & 1))) & 0xffffu) + (int)(int16_t)(rv[i >> 1] >> (16 * (i & 1))));
+                store4(a.rec[l.plane].p + (ptrdiff_t)(gy + j) * a.rec[l.plane].stride + gx, v[0], v[1], v[2], v[3]);
+                if (a.ip) {
+                    uint32_t sv[2];
+                    load4_pk(s.src + at, sv);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) { const int d = (int)((sv[i >> 1] >> (16 * (i & 1))) & 0xffffu) - v[i]; sse += (unsigned)(d * d); }
+                }
+                if (levels) {
+                    uint32_t lv[2];
+                    load4_pk(s.rs.lvl + at, lv);
+                    int16_t *c = a.coef[l.plane] + (size_t)(gy + j) * to_plane(l.plane, a.w) + gx;
+                    store_u32_aligned(c, lv[0]); store_u32_aligned(c + 2, lv[1]);      // (store4 of the four levels, already packed)
+                }
             }
-            if (!a.sparse_coef || ((s.rs.cbf[l.plane] >> l.tile0) & 1))
-                store4(a.coef[l.plane] + (size_t)gy * to_plane(l.plane, a.w) + gx, s.rs.lvl[i], s.rs.lvl[i + 1], s.rs.lvl[i + 2], s.rs.lvl[i + 3]);
+            if (sse) ex.atomic_add(&s.ip_sse, (unsigned long long)sse);
         }
         if (a.est || a.ip) {       // rate estimate: coefficient sub-block costs + a header per CU (oracle: inter estimate)
             unsigned e = 0;
+            if (a.prm.rdo_zero) {          // the zero-out stage left every sub-block's bits: those of the TUs it kept are the estimate's
+                if (tid >= NT - CTU_SUBBLOCKS) {
+                    const int sb = tid - (NT - CTU_SUBBLOCKS);
+                    const SampleLoc l = locate(s.rs, sub_block(sb).at);
+                    if (l.log2n && !((s.tu_zero[l.plane] >> l.tile0) & 1)) e += (unsigned)s.rs.post.sb_bits[sb];
+                }
+            } else
             for (int sb = tid; sb < CTU_SUBBLOCKS; sb += NT) {
                 const SubBlock b = sub_block(sb);
                 if (s.rs.tu_log2[b.tile]) e += (unsigned)subblock_bits_q4(s.rs.lvl + b.at, b.stride);

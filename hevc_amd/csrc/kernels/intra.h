@@ -576,9 +576,9 @@ template <typename T, class Ex> DEV void plan_level_cost(Ex &ex, IntraShared<T> 
 {
     const int bd = a.prm.bit_depth, log2n = 5 - level, l2c = log2n - 1, cnt = 1 << (2 * level), first = level_first(level);
     ex.phase([&](int tid) {
+        fill_desc(s.rs, whole_ctu(), tid, [](const SampleLoc &) { return 0; });
         for (int i = tid; i < CTU_SAMPLES; i += NT) {
             SampleLoc l = locate(s.rs, i);
-            s.rs.desc[i] = pack_loc(l);
             if (!l.log2n) continue;
             const int sh = l.plane ? 2 : 3, nd = node_of_tile(level, l.x >> sh, l.y >> sh);
             int cx, cy, l2, v;
@@ -716,11 +716,10 @@ DEV void intra_code_cu(Ex &ex, IntraShared<T> &s, const IntraArgs<T> &a, int x0,
         const int cang = s.tab_angle[cmode], cinv = s.tab_inv[cmode], ang = s.tab_angle[mode], inv = s.tab_inv[mode];
         const T *L = intra_filter_on(log2n, mode) ? s.filt : s.ref[0];
         const int lscan = scan_idx_of(log2n, 0, mode), cscan = scan_idx_of(log2n - 1, 1, cmode);
+        fill_desc(s.rs, rg, tid, [&](const SampleLoc &l) { return l.plane ? cscan : lscan; });
         for (int k = tid; k < rcnt; k += NT) {
             const int i = rg.index(k);
             SampleLoc l = locate(s.rs, i);
-            l.scan = l.plane ? cscan : lscan;
-            s.rs.desc[i] = pack_loc(l);
             if (!l.log2n) continue;
             int v;
             if (l.plane == 0) v = intra_sample<T>(L, log2n, mode, ang, inv, l.x - cx, l.y - cy, 0, bd, s.dc_val[0]);

@@ -27,9 +27,11 @@ struct ResidualShared {
     alignas(16) int16_t tmp[1536];         // stage intermediates, row-pair interleaved: element (r, c) at (r & ~1) * stride + 2c + (r & 1)
     alignas(16) int16_t coef[1536];        // transform coefficients / inverse stage-1 output (natural layout)
     alignas(16) int16_t lvl[1536];         // quantised levels (TU-local raster at CTU coordinates)
-    uint32_t desc[1536];       // per sample: TU geometry, written by the caller while it forms the residual
+    uint32_t desc[1536];       // TU geometry (pack_loc), indexed by sample but DEFINED ONLY AT THE ORIGIN OF EACH 2x4 BLOCK of the caller's region (Region::block_index):
+                               // the entries residual_pipeline reads.  The caller writes them (fill_desc, or its own loop over the blocks) while it forms the residual
     };
     alignas(16) uint32_t scratch[4608];    // the same 18 KB for a caller's own use while no residual is in flight (k_inter_ctu: fractional search)
+    struct { alignas(16) int16_t res_[1536]; int sb_bits[CTU_SUBBLOCKS]; } post;      // over `tmp`, which is idle once the inverse transform is done: a caller's level bits per 4x4 sub-block (k_inter_ctu: RD zero-out, then the rate estimate)
     struct { alignas(16) long long d[192]; int b[192]; } cg;      // over `res`, which is idle between the forward and the inverse transform: per 2x4 block, its share of a coefficient group's distortion and bits
     };
     uint8_t tu_log2[16];       // per 8x8 luma tile: log2 of the TU (= CU) size, 0 = none
@@ -91,11 +93,30 @@ DEV SampleLoc unpack_loc(uint32_t d, int idx)
     return l;
 }
 
+// the descriptors residual_pipeline reads for region rg: one per 2x4 block, at the block's origin, each written by one lane.  scan(l): the TU's scanIdx
+template <class Scan> DEV void fill_desc(ResidualShared &s, Region rg, int tid, Scan &&scan)
+{
+    for (int k = tid; k < (rg.count() >> 3); k += NT) {
+        const int idx = rg.block_index(k);
+        SampleLoc l = locate(s, idx);
+        l.scan = scan(l);
+        s.desc[idx] = pack_loc(l);
+    }
+}
+
 // 16 / 8 bytes of an LDS image whose address is 16- / 8-byte aligned as one ds_read_b128 / ds_read_b64 (and the matching stores)
 DEV void load_x4(const void *p, uint32_t (&v)[4]) { __builtin_memcpy(v, __builtin_assume_aligned(p, 16), 16); }
 DEV void load_x2(const void *p, uint32_t (&v)[2]) { __builtin_memcpy(v, __builtin_assume_aligned(p, 8), 8); }
 DEV void store_x4(void *p, const uint32_t (&v)[4]) { __builtin_memcpy(__builtin_assume_aligned(p, 16), v, 16); }
 DEV void store_x2(void *p, const uint32_t (&v)[2]) { __builtin_memcpy(__builtin_assume_aligned(p, 8), v, 8); }
+// four horizontally adjacent entries of a CTU image (p 4-entry aligned) as the 16-bit pairs (e0, e1), (e2, e3) the packed helpers of common.h work on
+DEV void load4_pk(const uint8_t *p, uint32_t (&v)[2])
+{
+    const uint32_t d = load_u32_aligned(p);
+    v[0] = perm_bytes(0u, d, 0x04010400u); v[1] = perm_bytes(0u, d, 0x04030402u);      // (selector 4: a zero byte)
+}
+DEV void load4_pk(const uint16_t *p, uint32_t (&v)[2]) { load_x2(p, v); }
+DEV void load4_pk(const int16_t *p, uint32_t (&v)[2]) { load_x2(p, v); }
 
 // scanIdx of a TU (7.4.9.11): mode-dependent for intra 4x4 TUs and 8x8 luma TUs, diagonal otherwise
 DEV int scan_idx_of(int log2n, int c_idx, int mode)
