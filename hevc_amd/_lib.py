@@ -7,6 +7,7 @@ header declares is absent, and every encode entry point returns MIHEVC_ENODEV on
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 from pathlib import Path
 
@@ -98,6 +99,35 @@ class Deint(C.Structure):
         return f"Deint(tff={self.tff}, field_rate={self.field_rate})"
 
 
+class Denoise(C.Structure):
+    """mihevc_denoise: the four thresholds, in 8-bit units, of the frames handed to mihevc_send_frame_denoise / mihevc_k_denoise"""
+    _fields_ = [(n, C.c_int32) for n in ("luma_spatial", "luma_temporal", "chroma_spatial", "chroma_temporal")] + [("reserved", C.c_int32 * 4)]
+
+    def __repr__(self):
+        return f"Denoise({self.luma_spatial}, {self.luma_temporal}, {self.chroma_spatial}, {self.chroma_temporal})"
+
+
+# denoise level -> (luma_spatial, luma_temporal, chroma_spatial, chroma_temporal); level 0: the filter is the identity (DESIGN.md §6g has the tables behind them)
+DENOISE_LEVELS = ((0, 0, 0, 0), (3, 4, 3, 4), (5, 7, 5, 7), (8, 11, 8, 11))
+
+
+def denoise_level(n: int) -> Denoise:
+    """the preset of level n in 0 .. 3"""
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n < len(DENOISE_LEVELS):
+        raise ValueError(f"denoise level {n!r}: 0 .. {len(DENOISE_LEVELS) - 1}")
+    return Denoise(*DENOISE_LEVELS[n])
+
+
+def denoise_strength(s) -> Denoise:
+    """a level 0 .. 3, or four thresholds 0 .. 255 (luma_spatial, luma_temporal, chroma_spatial, chroma_temporal)"""
+    if isinstance(s, int):
+        return denoise_level(s)
+    t = () if isinstance(s, (str, bytes)) else tuple(s)
+    if len(t) != 4 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= 255 for v in t):
+        raise ValueError(f"denoise strength {s!r}: a level 0 .. 3 or four thresholds 0 .. 255")
+    return Denoise(*(int(v) for v in t))
+
+
 class RgbFormat(C.Structure):
     """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
     _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
@@ -155,6 +185,7 @@ EXPORTS = (
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
     "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
     "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff", "mihevc_send_frame_deint", "mihevc_k_deinterlace",
+    "mihevc_send_frame_denoise", "mihevc_k_denoise",
 )
 
 _lib = None
@@ -228,6 +259,8 @@ def load() -> C.CDLL:
     lib.mihevc_k_scene_diff.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
     lib.mihevc_send_frame_deint.argtypes = [vp, C.POINTER(Deint), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_deinterlace.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_send_frame_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_denoise.argtypes = [i32, C.POINTER(Denoise), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

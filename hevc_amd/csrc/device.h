@@ -7,6 +7,7 @@
 
 #include "kernels/common.h"
 #include "kernels/deint.h"
+#include "kernels/denoise.h"
 #include "kernels/ingest.h"
 #include "kernels/ingest_rgb.h"
 #include "kernels/inter.h"
@@ -78,6 +79,8 @@ hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample,
 hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out16);
 // deinterlacing source (kernels/deint.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth
 hipError_t launch_deint(hipStream_t st, const DeintArgs &a, bool is16);
+// denoising source (kernels/denoise.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth
+hipError_t launch_denoise(hipStream_t st, const DenoiseArgs &a, bool is16);
 
 // rows between the slices of one picture (csrc/slice_group.h): jobs[i] for i < n_jobs, one grid row of `blocks_per_job` workgroups each
 hipError_t launch_copy_rows(hipStream_t st, const RowCopy *d_jobs, int n_jobs, int blocks_per_job);

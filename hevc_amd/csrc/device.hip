@@ -232,6 +232,22 @@ hipError_t launch_deint(hipStream_t st, const DeintArgs &a, bool is16)
     return hipGetLastError();
 }
 
+// denoising source (kernels/denoise.h): one workgroup per tile of DN_TW x DN_TH output samples, Y, then Cb, then Cr; the argument block travels by value.
+// 29,376 bytes of LDS: four workgroups per CU (4 waves per SIMD, at most 128 VGPRs) take 115 KB of the CU's 160
+template <typename T> __global__ __launch_bounds__(NT, 4) void k_denoise(const DenoiseArgs a)
+{
+    __shared__ __align__(16) DenoiseShared s;
+    GpuExec ex;
+    denoise_tile_program<T>(ex, s, a, (int)blockIdx.x);
+}
+hipError_t launch_denoise(hipStream_t st, const DenoiseArgs &a, bool is16)
+{
+    const dim3 grid((unsigned)deint_workgroups(a.f.pw, a.f.ph)), block(NT);
+    if (is16) hipLaunchKernelGGL((k_denoise<uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_denoise<uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 // RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
 template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
 {
@@ -1064,6 +1080,26 @@ int stage_deint(const void *const *prev, const void *const *cur, const void *con
     return dst.planes.download(out);
 }
 
+// the denoising kernel alone
+template <typename T>
+int stage_denoise(const mihevc_denoise &dn, const void *const *prev, const void *const *cur, const void *const *next, int w, int h, int pitch_y, int pitch_c, int depth,
+                  void *const *out)
+{
+    DevBuf din[9];
+    ConvertOut<T> dst;
+    if (int e = dst.alloc(w, h)) return e;
+    const void *d[3][3];
+    for (int f = 0; f < 3; f++)
+        for (int c = 0; c < 3; c++) {
+            d[f][c] = (f == 0 ? prev : f == 1 ? cur : next)[c];
+            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
+        }
+    const DenoiseArgs a = denoise_args(dn, depth, d[0], d[1], d[2], pitch_y, pitch_c, w, h, dst.w, dst.h, dst.p, dst.stride);
+    CK(launch_denoise(0, a, sizeof(T) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.planes.download(out);
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -1284,6 +1320,18 @@ int mihevc_k_deinterlace(int device, const void *const prev[3], const void *cons
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(bit_depth, [&](auto t) { return stage_deint<decltype(t)>(prev, cur, next, width, height, pitch_y, pitch_c, bit_depth, keep, second, out); });
+}
+
+int mihevc_k_denoise(int device, const mihevc_denoise *dn, const void *const prev[3], const void *const cur[3], const void *const next[3], int width, int height,
+                     int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v)
+{
+    if (!denoise_strength_ok(dn) || !prev || !cur || !next || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
+    for (int c = 0; c < 3; c++)
+        if (!prev[c] || !cur[c] || !next[c]) return MIHEVC_EINVAL;
+    if (!denoise_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(bit_depth, [&](auto t) { return stage_denoise<decltype(t)>(*dn, prev, cur, next, width, height, pitch_y, pitch_c, bit_depth, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

@@ -117,15 +117,19 @@ struct mihevc_session {
     CachedBlock<uint8_t> scale_tab;
     ScaleBlock scale_host;
     int scale_sw = 0, scale_sh = 0;
-    // mihevc_send_frame_deint: a ring of three source-size pictures (display size, rows that begin 16-byte aligned), allocated at the first call; frame k lies in
-    // slot k % 3.  Copies and k_deint launches are neighbours on st_pre, so a slot is overwritten in stream order behind the last launch that read it.
-    // deint_n: frames taken; deint_pending: the last of them has not produced its picture(s) yet (the next frame or mihevc_flush does that)
-    CachedBlock<uint8_t> deint_ring[3];
-    void *deint_p[3][3] = {};
-    int deint_pitch[3] = {};
-    int64_t deint_n = 0, deint_pts = 0;
+    // mihevc_send_frame_deint, mihevc_send_frame_denoise: a ring of three source-size pictures (display size, rows that begin 16-byte aligned), allocated at the
+    // first call; frame k lies in slot k % 3.  Copies and k_deint / k_denoise launches are neighbours on st_pre, so a slot is overwritten in stream order behind
+    // the last launch that read it.  src_ring_kind: the entry that filled the ring first (a pending frame keeps every other entry out until flush, so it is the only
+    // one); src_ring_n: frames taken; src_ring_pending: the last of them has not produced its picture(s) yet (the next frame or mihevc_flush does that)
+    enum { RING_NONE = 0, RING_DEINT, RING_DENOISE };
+    CachedBlock<uint8_t> src_ring[3];
+    void *src_ring_p[3][3] = {};
+    int src_ring_pitch[3] = {};
+    int64_t src_ring_n = 0, src_ring_pts = 0;
+    int src_ring_kind = RING_NONE;
+    bool src_ring_pending = false;
     int deint_tff = 0, deint_field_rate = 0;
-    bool deint_pending = false;
+    mihevc_denoise denoise_pending = {};      // the strengths of the pending frame
     // per lane
     // The vector moves a lane's handles when it grows; the blocks they own stay where they are, so the raw pointers in argument blocks, jobs and BandPub stay valid
     struct Lane {
@@ -1396,7 +1400,7 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
 {
     if (!s || !y || !u || !v) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
-    if (s->flushed || s->deint_pending) return MIHEVC_ESTATE;      // (a deinterlaced frame waits for its successor: no other picture may come between)
+    if (s->flushed || s->src_ring_pending) return MIHEVC_ESTATE;      // (a deinterlaced or denoised frame waits for its successor: no other picture may come between)
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     mihevc_session::Src src;
     const void *in[3] = {y, u, v};
@@ -1487,53 +1491,61 @@ static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const voi
     return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
-// The picture(s) of deinterlaced frame k (mihevc_send_frame_deint): P = frame k - 1 (the first frame: itself), C = frame k, N = frame k + 1 (has_next; the last
-// frame: itself).  k_deint writes the session's own planes, margin included, out of the ring; frame-rate mode keeps the first field's rows, field-rate mode
-// follows with the second field's picture at pts + 1
-static int deint_emit(mihevc_session *s, int64_t k, bool has_next, bool wait)
+// The picture(s) of frame k of the ring (mihevc_send_frame_deint, mihevc_send_frame_denoise): P = frame k - 1 (the first frame: itself), C = frame k, N = frame k + 1
+// (has_next; the last frame: itself).  k_deint / k_denoise write the session's own planes, margin included, out of the ring.  Deinterlacing: frame-rate mode
+// keeps the first field's rows, field-rate mode follows with the second field's picture at pts + 1.  Denoising: one picture, with the strengths frame k came with
+static int ring_emit(mihevc_session *s, int64_t k, bool has_next, bool wait)
 {
-    s->deint_pending = false;
-    void *const *C = s->deint_p[k % 3], *const *P = s->deint_p[(k > 0 ? k - 1 : k) % 3], *const *N = s->deint_p[(has_next ? k + 1 : k) % 3];
+    s->src_ring_pending = false;
+    void *const *C = s->src_ring_p[k % 3], *const *P = s->src_ring_p[(k > 0 ? k - 1 : k) % 3], *const *N = s->src_ring_p[(has_next ? k + 1 : k) % 3];
+    const bool denoise = s->src_ring_kind == mihevc_session::RING_DENOISE;
     const int first = s->deint_tff ? 0 : 1;
-    for (int f = 0; f <= s->deint_field_rate; f++) {
+    for (int f = 0; f <= (denoise ? 0 : s->deint_field_rate); f++) {
         mihevc_session::Src src;
         if (int e = take_src(s, src)) return e;
-        const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, s->deint_pitch[0], s->deint_pitch[1], s->cfg.width, s->cfg.height, s->w, s->h, f ? 1 - first : first, f,
-                                       src.p, src.stride);
-        HIPCK(s, launch_deint(s->st_pre, a, s->is16));
-        if (int e = finish_ingest(s, std::move(src), s->deint_pts + f, wait)) return e;
+        if (denoise) {
+            const DenoiseArgs a = denoise_args(s->denoise_pending, s->cfg.bit_depth, P, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], s->cfg.width, s->cfg.height, s->w, s->h,
+                                               src.p, src.stride);
+            HIPCK(s, launch_denoise(s->st_pre, a, s->is16));
+        } else {
+            const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], s->cfg.width, s->cfg.height, s->w, s->h, f ? 1 - first : first, f,
+                                           src.p, src.stride);
+            HIPCK(s, launch_deint(s->st_pre, a, s->is16));
+        }
+        if (int e = finish_ingest(s, std::move(src), s->src_ring_pts + f, wait)) return e;
     }
     return MIHEVC_OK;
 }
 
-// An interlaced frame (mihevc_send_frame_deint; the arguments are checked): into its slot of the ring, then the picture(s) of the frame before it
-static int ingest_deint(mihevc_session *s, const mihevc_deint &d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
+// A frame of kind `kind` (mihevc_send_frame_deint, mihevc_send_frame_denoise; the arguments are checked): into its slot of the ring, then the picture(s) of the frame
+// before it.  Returns with src_ring_pts still that of the frame before: the caller sets what belongs to the new frame
+static int ingest_ring(mihevc_session *s, int kind, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
 {
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     const size_t es = esize(s);
     const int W = s->cfg.width, H = s->cfg.height;
-    if (!s->deint_ring[0]) {
-        s->deint_pitch[0] = (W + 15) & ~15; s->deint_pitch[1] = s->deint_pitch[2] = (W / 2 + 15) & ~15;
-        const size_t by = ((size_t)s->deint_pitch[0] * H * es + 255) & ~(size_t)255, bc = ((size_t)s->deint_pitch[1] * (H / 2) * es + 255) & ~(size_t)255;
+    if (!s->src_ring[0]) {
+        s->src_ring_pitch[0] = (W + 15) & ~15; s->src_ring_pitch[1] = s->src_ring_pitch[2] = (W / 2 + 15) & ~15;
+        const size_t by = ((size_t)s->src_ring_pitch[0] * H * es + 255) & ~(size_t)255, bc = ((size_t)s->src_ring_pitch[1] * (H / 2) * es + 255) & ~(size_t)255;
         for (int k = 0; k < 3; k++) {
-            HIPCK(s, s->deint_ring[k].alloc(s->device, by + 2 * bc, false));
-            s->deint_p[k][0] = s->deint_ring[k]; s->deint_p[k][1] = s->deint_ring[k] + by; s->deint_p[k][2] = s->deint_ring[k] + by + bc;
+            HIPCK(s, s->src_ring[k].alloc(s->device, by + 2 * bc, false));
+            s->src_ring_p[k][0] = s->src_ring[k]; s->src_ring_p[k][1] = s->src_ring[k] + by; s->src_ring_p[k][2] = s->src_ring[k] + by + bc;
         }
-        s->deint_tff = d.tff; s->deint_field_rate = d.field_rate;
+        s->src_ring_kind = kind;
     }
-    const int64_t k = s->deint_n;
+    const int64_t k = s->src_ring_n;
     const void *in[3] = {y, u, v};
     for (int c = 0; c < 3; c++)
-        HIPCK(s, hipMemcpy2DAsync(s->deint_p[k % 3][c], s->deint_pitch[c] * es, in[c], (c ? pitch_c : pitch_y) * es, (c ? W / 2 : W) * es, c ? H / 2 : H,
+        HIPCK(s, hipMemcpy2DAsync(s->src_ring_p[k % 3][c], s->src_ring_pitch[c] * es, in[c], (c ? pitch_c : pitch_y) * es, (c ? W / 2 : W) * es, c ? H / 2 : H,
                                   device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
-    s->deint_n = k + 1;
+    s->src_ring_n = k + 1;
     const bool wait = !device_src && !async;
     int e = MIHEVC_OK;
-    if (k > 0) e = deint_emit(s, k - 1, true, wait);      // (deint_pts is still the pts of frame k - 1)
+    if (k > 0) e = ring_emit(s, k - 1, true, wait);      // (src_ring_pts and denoise_pending are still those of frame k - 1)
     else if (wait) HIPCK(s, hipStreamSynchronize(s->st_pre));
     else s->up_pending = true;
-    s->deint_pts = pts;
-    s->deint_pending = true;
+    s->src_ring_pts = pts;
+    s->src_ring_pending = true;
     return e;
 }
 
@@ -1557,12 +1569,12 @@ int mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, co
     return MIHEVC_OK;
 }
 // What the converting entries refuse, in the order in which the errors win.  args_ok: the entry's own checks of its arguments
-static int refuse_source(const mihevc_session *s, bool args_ok, int flags, bool deint = false)
+static int refuse_source(const mihevc_session *s, bool args_ok, int flags, int kind = mihevc_session::RING_NONE)
 {
     if (!args_ok || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
     if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
     if (s->failed) return s->fail_code;
-    return s->flushed || (s->deint_pending && !deint) ? MIHEVC_ESTATE : MIHEVC_OK;
+    return s->flushed || (s->src_ring_pending && s->src_ring_kind != kind) ? MIHEVC_ESTATE : MIHEVC_OK;
 }
 int mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {
@@ -1593,10 +1605,20 @@ int mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, con
 }
 int mihevc_send_frame_deint(mihevc_session *s, const mihevc_deint *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {
-    const bool args_ok = s && deint_mode_ok(d) && y && u && v && (s->deint_n == 0 || (d->tff == s->deint_tff && d->field_rate == s->deint_field_rate)) &&
+    const bool args_ok = s && deint_mode_ok(d) && y && u && v && (s->src_ring_kind != mihevc_session::RING_DEINT || (d->tff == s->deint_tff && d->field_rate == s->deint_field_rate)) &&
                          deint_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width && pitch_c >= s->cfg.width / 2;
-    if (int e = refuse_source(s, args_ok, flags, true)) return e;
-    return ingest_deint(s, *d, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_DEINT)) return e;
+    if (s->src_ring_kind == mihevc_session::RING_NONE) { s->deint_tff = d->tff; s->deint_field_rate = d->field_rate; }
+    return ingest_ring(s, mihevc_session::RING_DEINT, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+}
+int mihevc_send_frame_denoise(mihevc_session *s, const mihevc_denoise *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const bool args_ok = s && denoise_strength_ok(d) && y && u && v && denoise_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width &&
+                         pitch_c >= s->cfg.width / 2;
+    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_DENOISE)) return e;
+    const int e = ingest_ring(s, mihevc_session::RING_DENOISE, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+    s->denoise_pending = *d;      // (the picture of the frame before has been launched with its own)
+    return e;
 }
 int mihevc_sync_uploads(mihevc_session *s)
 {
@@ -1613,9 +1635,9 @@ int mihevc_flush(mihevc_session *s)
     if (!s) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
     if (s->flushed) return MIHEVC_OK;
-    if (s->deint_pending) {      // the last interlaced frame: its successor is itself
+    if (s->src_ring_pending) {      // the last frame of the ring: its successor is itself
         if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-        if (int e = deint_emit(s, s->deint_n - 1, false, false)) return e;
+        if (int e = ring_emit(s, s->src_ring_n - 1, false, false)) return e;
     }
     s->flushing = true;
     int e = run_chunk(s);

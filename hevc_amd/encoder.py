@@ -233,6 +233,27 @@ class Encoder:
         self._pts = pts + (2 if field_rate else 1)
         self._check(self._lib.mihevc_send_frame_deint(self._s, C.byref(mode), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_deint")
 
+    def send_denoise(self, y, u, v, strength=2, asynchronous: bool = False, pts: Optional[int] = None):
+        """mihevc_send_frame_denoise: a progressive frame of the session's display size, planar 4:2:0 at the session's depth, denoised on the device by the
+        motion-adaptive spatio-temporal filter of DESIGN.md §6g.  strength: a level 0 .. 3 (_lib.denoise_level), a tuple (luma_spatial, luma_temporal,
+        chroma_spatial, chroma_temporal) of thresholds 0 .. 255 in 8-bit units, or a _lib.Denoise; it belongs to this frame and may change from frame to frame.
+        The frame's picture comes out once the next frame has arrived, the last frame's with flush().  Width and height even and at least 16.  numpy planes are
+        checked for shape and type here; torch tensors on the device are read where they are (MIHEVC_SRC_DEVICE) under the rules of send_fmt.  asynchronous
+        (host planes): the rules of send_async."""
+        c = self.cfg
+        dn = strength if isinstance(strength, _lib.Denoise) else _lib.denoise_strength(strength)
+        planes = [y, u, v]
+        shapes = [(c.height, c.width)] + [(c.height // 2, c.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of the session")
+        es = 1 if c.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(dn, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_denoise")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_denoise(self._s, C.byref(dn), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_denoise")
+
     def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
         Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
@@ -655,7 +676,7 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
-                tff: Optional[bool] = None) -> int:
+                tff: Optional[bool] = None, denoise=None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -664,11 +685,24 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     deinterlace: the source's frames are woven interlaced frames, deinterlaced on the device (Encoder.send_deint).  'frame': one picture per
     frame; 'field': one per field, so the session, its level, the rate figures and the MP4 track run at twice the frame rate; 'auto': 'frame' when the source
     says it is interlaced (the y4m header's It / Ib tag, else ffprobe's field_order), nothing otherwise.  tff: the field order, None to take the source's word
-    (top field first when it has none).  Planar 4:2:0 sources at the session's depth on one device; not together with size= or native_rgb."""
+    (top field first when it has none).  Planar 4:2:0 sources at the session's depth on one device; not together with size= or native_rgb.
+    denoise: a level 1 .. 3 or a tuple of four thresholds (Encoder.send_denoise): every frame is denoised on the device in front of the session.
+    None and 0: nothing changes.  Planar 4:2:0 sources at the session's depth on one device; not together with deinterlace=, size=, native_rgb, sliced sessions or several devices."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
 
+    if denoise is not None and not (isinstance(denoise, int) and not isinstance(denoise, bool) and denoise == 0):
+        try:
+            denoise, bad = _lib.denoise_strength(denoise), False
+        except (TypeError, ValueError):
+            bad = True
+        if bad or deinterlace is not None or size is not None or native_rgb or (devices and len(devices) > 1):      # (several devices: sharded or sliced)
+            logger.error("%s: denoise=%r takes a level 0 .. 3 or four thresholds 0 .. 255, one device, and none of deinterlace=, size=, native_rgb",
+                         Path(file_path).name, denoise)
+            return 1
+    else:
+        denoise = None
     deint = None            # (top field first, field rate) once deinterlacing is on
     clip_info = info        # what the clip is opened with: the source's own rate and frame count
     if deinterlace is not None:
@@ -727,6 +761,9 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             logger.error("%s: deinterlace= takes a planar 4:2:0 source at the session's depth, width even, height a multiple of 4 (%r, %dx%d)",
                          Path(file_path).name, fmt, cfg.width, cfg.height)
             return 1
+        if denoise is not None and (fmt is not None or cfg.width % 2 or cfg.height % 2 or min(cfg.width, cfg.height) < 16):
+            logger.error("%s: denoise= takes a planar 4:2:0 source at the session's depth, width and height even (%r, %dx%d)", Path(file_path).name, fmt, cfg.width, cfg.height)
+            return 1
         total = (clip.n_frames or total_frames) * (2 if deint and deint[1] else 1)
         wants_audio = bool(info.audio_channels and info.audio_channels > 0) and Path(file_path).suffix.lower() not in ('.y4m', '.yuv')
         video_path = Path(out_path).with_suffix('.video.mp4') if wants_audio else Path(out_path)
@@ -769,6 +806,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                         return 1
                     if deint:
                         enc.send_deint(*planes, tff=deint[0], field_rate=deint[1], pts=i * (2 if deint[1] else 1))
+                    elif denoise is not None:
+                        enc.send_denoise(*planes, strength=denoise, pts=i)
                     elif size is not None:
                         enc.send_scaled(src_size[0], src_size[1], *planes, bit_depth=src_depth, pts=i)
                     elif fmt is None:

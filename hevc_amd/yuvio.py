@@ -237,12 +237,15 @@ class SyntheticClip:
     i.i.d. grain (sigma 2 LSB at 8 bit, 8 LSB at 10 bit) re-seeded per frame — the headline workload.
     `stress`: what a translational search and a per-GOP rate plan do not like — the texture ZOOMS (scale 1 .. 1.5 and back), the whole picture FADES to
     dark and back, twelve small occluders move on their own paths, one hard cut (frame n/2: another texture) and a one-frame white flash (frame n/4):
-    for the rate-control / scene-cut / conformance tests, not a benchmark."""
+    for the rate-control / scene-cut / conformance tests, not a benchmark.
+    grain, still (`motion` only; the defaults change nothing): the grain's sigma is multiplied by `grain` (0: the grain-free picture the noisy one was made
+    from); `still`: texture and rectangles stay where frame 0 has them, only the grain changes from frame to frame."""
 
-    def __init__(self, pattern: str, seed: int, width: int, height: int, n_frames: int, bit_depth: int = 8, fps: float = 30.0):
+    def __init__(self, pattern: str, seed: int, width: int, height: int, n_frames: int, bit_depth: int = 8, fps: float = 30.0, grain: float = 1.0, still: bool = False):
         assert pattern in ('bars', 'motion', 'stress')
         self.pattern, self.seed, self.width, self.height, self.n_frames, self.bit_depth, self.fps = pattern, seed, width, height, n_frames, bit_depth, fps
         self.hdr = bit_depth > 8
+        self.grain, self.still = float(grain), bool(still)
         self._tex = None
 
     def _texture(self):
@@ -302,19 +305,21 @@ class SyntheticClip:
         else:
             t = self._texture()
             th, tw = t.shape[0] // 2, t.shape[1] // 2
-            r0, c0 = (1 * i) % th, (3 * i) % tw
+            m = 0 if self.still else i          # the frame whose geometry this one has
+            r0, c0 = (1 * m) % th, (3 * m) % tw
             win = t[r0:r0 + h, c0:c0 + w]
             y = 126 + 38 * win
             # two rectangles on independent paths
             for k, (rw, rh, vx, vy, lum) in enumerate(((w // 8, h // 6, 5, 2, 200), (w // 10, h // 5, -4, 3, 60))):
-                x0 = (w // 4 * (k + 1) + vx * i) % max(1, w - rw)
-                y0 = (h // 3 * (k + 1) + vy * i) % max(1, h - rh)
+                x0 = (w // 4 * (k + 1) + vx * m) % max(1, w - rw)
+                y0 = (h // 3 * (k + 1) + vy * m) % max(1, h - rh)
                 y[y0:y0 + rh, x0:x0 + rw] = lum
             g = np.random.default_rng((self.seed + 1) * 100003 + i)
-            y = y + 2.0 * g.standard_normal((h, w), dtype=np.float32)
+            gy, gc = np.float32(2.0 * self.grain), np.float32(self.grain)
+            y = y + gy * g.standard_normal((h, w), dtype=np.float32)
             yy, xx = np.mgrid[0:h // 2, 0:w // 2]
-            u = 128 + 24 * win[::2, ::2] + g.standard_normal((h // 2, w // 2), dtype=np.float32)
-            v = 128 - 24 * win[::2, ::2] + 10 * np.sin((xx + 3 * i / 2) / 40.0).astype(np.float32) + g.standard_normal((h // 2, w // 2), dtype=np.float32)
+            u = 128 + 24 * win[::2, ::2] + gc * g.standard_normal((h // 2, w // 2), dtype=np.float32)
+            v = 128 - 24 * win[::2, ::2] + 10 * np.sin((xx + 3 * m / 2) / 40.0).astype(np.float32) + gc * g.standard_normal((h // 2, w // 2), dtype=np.float32)
             y, u, v = y * sc, u * sc, v * sc
         dt = np.uint16 if bd > 8 else np.uint8
         return (np.clip(np.rint(y), lo, hi).astype(dt), np.clip(np.rint(u), lo, hi + 5 * sc).astype(dt), np.clip(np.rint(v), lo, hi + 5 * sc).astype(dt))

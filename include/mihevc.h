@@ -290,6 +290,27 @@ typedef struct mihevc_deint {
  * flush; and every OTHER entry that sends a frame returns MIHEVC_ESTATE while a deinterlaced frame is pending (sent, its pictures not yet produced). */
 int  mihevc_send_frame_deint(mihevc_session *s, const mihevc_deint *d, const void *y, const void *u, const void *v,
                              int pitch_y, int pitch_c, int64_t pts, int flags);
+/* ---- added under ABI 6: NOISY sources (symbols only) ----
+ * A progressive frame of the session's DISPLAY size, planar 4:2:0 at cfg.bit_depth (uint8 at 8 bit, else little-endian uint16, values above 2^bit_depth - 1
+ * clamped), denoised on the device by a motion-adaptive spatio-temporal filter with an exact integer definition (hevc_amd/csrc/kernels/denoise.h
+ * states the arithmetic): every output sample is a weighted mean of the sample, its eight neighbours and the co-sited samples of the frame before and the frame
+ * after, each weight a threshold minus a difference, so that edges, impulses and moving areas pass as they are.  The first frame stands in for its missing
+ * predecessor and the last one for its missing successor.  The four strengths are thresholds in 8-bit units (shifted left by bit_depth - 8); all zero leaves the
+ * frame as it is.  Not covered: motion-compensated or block-matching filters, other layouts or depths than the session's, scaling, deinterlacing or RGB in the
+ * same session, sliced sessions, noise-level estimation. */
+typedef struct mihevc_denoise {
+    int32_t luma_spatial, luma_temporal;       /* 0 .. 255 */
+    int32_t chroma_spatial, chroma_temporal;   /* 0 .. 255 */
+    int32_t reserved[4];                       /* 0 */
+} mihevc_denoise;
+/* pitch_y, pitch_c: in elements.  The frame is copied into the ring of three source-size pictures that mihevc_send_frame_deint uses too; flags and ownership are
+ * those of mihevc_send_frame_deint.  A frame's picture is produced when the NEXT frame arrives, the last frame's by mihevc_flush; mihevc_stats.frames_in counts
+ * pictures.  The strengths sent with a frame apply to that frame's picture and may change from frame to frame.  MIHEVC_EINVAL, decided before any device call
+ * and leaving the session usable: NULL d or plane, a strength outside 0 .. 255, non-zero reserved, cfg.width or cfg.height odd or below 16, a pitch smaller than
+ * the plane, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush; every OTHER entry that sends a frame, mihevc_send_frame_deint included, returns
+ * MIHEVC_ESTATE while a denoised frame is pending (sent, its picture not yet produced), and this one does while a deinterlaced frame is pending. */
+int  mihevc_send_frame_denoise(mihevc_session *s, const mihevc_denoise *d, const void *y, const void *u, const void *v,
+                               int pitch_y, int pitch_c, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -447,6 +468,13 @@ int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y
 int mihevc_k_deinterlace(int device, const void *const prev[3], const void *const cur[3], const void *const next[3],
                          int width, int height, int pitch_y, int pitch_c, int bit_depth, int keep, int second,
                          void *out_y, void *out_u, void *out_v);
+
+/* added under ABI 6.  The denoiser of mihevc_send_frame_denoise alone (the session's kernel), host buffers in and out: prev / cur / next name the Y, Cb and Cr
+ * planes of three frames of width x height samples at bit_depth (they may name the same planes), one pitch_y and one pitch_c for all of them, in elements; out_*
+ * are planes of the CODED size as in mihevc_k_convert_source.  Validated first (MIHEVC_EINVAL: what mihevc_send_frame_denoise refuses, a bit_depth other than 8
+ * or 10), then MIHEVC_ENODEV without a device */
+int mihevc_k_denoise(int device, const mihevc_denoise *d, const void *const prev[3], const void *const cur[3], const void *const next[3],
+                     int width, int height, int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height

@@ -11,6 +11,7 @@ BD-rate from this script (JSON under profiles/).
     python tools/rd_curve.py --out profiles/r03_rd_base.json                       # needs an MI355X (no CPU fallback)
     python tools/rd_curve.py --out profiles/r03_rd_x.json --against profiles/r03_rd_base.json --set bframes=1
     python tools/rd_curve.py --compare profiles/a.json profiles/b.json             # no GPU: BD-rate of b against a
+    python tools/rd_curve.py --denoise-table --out profiles/denoise.json           # the table of DESIGN.md §6g: denoise levels 0 .. 3 on the grain clips
 
 Fixed-QP runs (cfg.qp = QP for P pictures, IDR 3 below, the session's rule), no VBV: the curve is the encoder's, not the rate controller's.
 """
@@ -143,6 +144,61 @@ def run(args):
     print(json.dumps({k: v for k, v in res.items() if k != "clips"} | {"clips": {c: [(p["kbps"], p["psnr_y"]) for p in v["points"]] for c, v in res["clips"].items()}}))
 
 
+def run_denoise(args):
+    """The table of DESIGN.md §6g: the `motion` clip (the benchmark's: texture and rectangles moving under grain) and the same clip held still under the same grain,
+    at the four QPs and denoise levels 0 .. 3 (Encoder.send_denoise; level 0 is plain send).  Per point: kb/s, and the luma PSNR of the decoded pictures (the
+    session's reconstruction, display area) against the noisy source and against the grain-free source the generator renders with grain=0.  The session's own
+    SSE is of no use here: it is taken against the denoised picture"""
+    from hevc_amd import _lib
+    from hevc_amd.encoder import Encoder
+    from hevc_amd.yuvio import SyntheticClip
+    if _lib.load().mihevc_device_count() < 1:
+        raise SystemExit("rd_curve.py needs an MI355X (the native path has no CPU fallback)")
+    W, H, N, bd = args.width, args.height, args.frames, args.bit_depth
+    peak = float((1 << bd) - 1)
+    res = {"width": W, "height": H, "frames": N, "bit_depth": bd, "qps": list(QPS), "levels": [list(t) for t in _lib.DENOISE_LEVELS], "clips": {}}
+    for name, still in (("motion", False), ("still", True)):
+        noisy = [SyntheticClip("motion", 0, W, H, N, bit_depth=bd, still=still).frame(i) for i in range(N)]
+        clean = [SyntheticClip("motion", 0, W, H, N, bit_depth=bd, still=still, grain=0.0).frame(i)[0].astype(np.int32) for i in range(N)]
+        src_y = [f[0].astype(np.int32) for f in noisy]
+        rows = []
+        for level in range(len(_lib.DENOISE_LEVELS)):
+            for qp in QPS:
+                cfg = _lib.default_config()
+                cfg.width, cfg.height, cfg.bit_depth, cfg.qp, cfg.keyint, cfg.min_keyint = W, H, bd, qp, args.keyint, max(2, args.keyint // 2)
+                cfg.level_idc = 120 if W * H <= 1920 * 1088 else 150 if W * H <= 3840 * 2176 else 180
+                cfg.gops_in_flight = max(1, min(8, -(-N // args.keyint)))
+                for kv in args.set:
+                    k, v = kv.split("=")
+                    setattr(cfg, k, int(v))
+                nbytes = 0
+                with Encoder(cfg, device=args.device, keep_recon=True) as enc:
+                    for i, (y, u, v) in enumerate(noisy):
+                        if level:
+                            enc.send_denoise(y, u, v, strength=level, pts=i)
+                        else:
+                            enc.send(y, u, v, pts=i)
+                        nbytes += sum(len(p[0]) for p in enc.packets())
+                    enc.flush()
+                    nbytes += sum(len(p[0]) for p in enc.packets())
+                    assert enc.stats().frames_out == N
+                    sse_n = sse_c = 0.0
+                    for i in range(N):
+                        rec = enc.recon(i)[0][:H, :W].astype(np.int32)
+                        sse_n += float(((rec - src_y[i]) ** 2).sum())
+                        sse_c += float(((rec - clean[i]) ** 2).sum())
+                ps = [10 * np.log10(peak * peak / (s / (N * W * H))) for s in (sse_n, sse_c)]
+                rows.append({"level": level, "qp": qp, "kbps": round(nbytes * 8 / (N / 30.0) / 1e3, 2), "psnr_y_noisy": round(float(ps[0]), 3), "psnr_y_clean": round(float(ps[1]), 3)})
+                print(f"{name:7s} level {level} qp {qp}: {rows[-1]['kbps']:10.1f} kb/s  {ps[0]:.3f} dB against the source, {ps[1]:.3f} dB against the grain-free source", file=sys.stderr)
+        sse_in = sum(float(((a - b) ** 2).sum()) for a, b in zip(src_y, clean))
+        res["clips"][name] = {"source_psnr_y_clean": round(float(10 * np.log10(peak * peak / (sse_in / (N * W * H)))), 3), "points": rows}
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
@@ -156,7 +212,11 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--clips", nargs="+", default=list(CLIPS))
     ap.add_argument("--set", nargs="*", default=[], metavar="FIELD=INT", help="mihevc_config fields to override, e.g. rdo_cg=3 bframes=1")
+    ap.add_argument("--denoise-table", action="store_true", help="denoise levels 0 .. 3 on the moving and the still grain clip (DESIGN.md §6g) instead of the RD run")
     args = ap.parse_args()
+    if args.denoise_table:
+        run_denoise(args)
+        return
     if args.compare:
         print(json.dumps(compare(json.load(open(args.compare[0])), json.load(open(args.compare[1]))), indent=1))
         return
