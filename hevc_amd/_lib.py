@@ -99,6 +99,20 @@ class Deint(C.Structure):
         return f"Deint(tff={self.tff}, field_rate={self.field_rate})"
 
 
+class Fieldmatch(C.Structure):
+    """mihevc_fieldmatch: declared field order and what inverse telecine does with the frames handed to mihevc_send_frame_fieldmatch"""
+    _fields_ = [(n, C.c_int32) for n in ("tff", "decimate", "deint")] + [("reserved", C.c_int32 * 5)]
+
+    def __repr__(self):
+        return f"Fieldmatch(tff={self.tff}, decimate={self.decimate}, deint={self.deint})"
+
+
+class FmFrame(C.Structure):
+    """mihevc_fm_frame: what mihevc_get_fieldmatch_info tells about one frame: the metrics (c, p, n), the match, and where the picture went"""
+    _fields_ = [("comb_sum", C.c_uint64 * 3), ("comb_block", C.c_uint32 * 3), ("dup_sum", C.c_uint64), ("dup_block", C.c_uint32), ("match", C.c_int32),
+                ("deinterlaced", C.c_int32), ("dropped", C.c_int32), ("picture", C.c_int64)]
+
+
 class Denoise(C.Structure):
     """mihevc_denoise: the four thresholds, in 8-bit units, of the frames handed to mihevc_send_frame_denoise / mihevc_k_denoise"""
     _fields_ = [(n, C.c_int32) for n in ("luma_spatial", "luma_temporal", "chroma_spatial", "chroma_temporal")] + [("reserved", C.c_int32 * 4)]
@@ -185,7 +199,8 @@ EXPORTS = (
     "mihevc_encode_picture_host", "mihevc_k_picture_hash", "mihevc_write_picture_hash_sei", "mihevc_get_frame_quality", "mihevc_k_ssim",
     "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
     "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff", "mihevc_send_frame_deint", "mihevc_k_deinterlace",
-    "mihevc_send_frame_denoise", "mihevc_k_denoise",
+    "mihevc_send_frame_denoise", "mihevc_k_denoise", "mihevc_send_frame_fieldmatch", "mihevc_get_fieldmatch_info", "mihevc_k_fieldmatch_metrics",
+    "mihevc_k_fieldmatch_weave",
 )
 
 _lib = None
@@ -261,6 +276,10 @@ def load() -> C.CDLL:
     lib.mihevc_k_deinterlace.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.mihevc_send_frame_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_denoise.argtypes = [i32, C.POINTER(Denoise), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_send_frame_fieldmatch.argtypes = [vp, C.POINTER(Fieldmatch), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_get_fieldmatch_info.argtypes = [vp, i64, C.POINTER(FmFrame)]
+    lib.mihevc_k_fieldmatch_metrics.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.mihevc_k_fieldmatch_weave.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -8,6 +8,7 @@
 #include "kernels/common.h"
 #include "kernels/deint.h"
 #include "kernels/denoise.h"
+#include "kernels/fieldmatch.h"
 #include "kernels/ingest.h"
 #include "kernels/ingest_rgb.h"
 #include "kernels/inter.h"
@@ -81,6 +82,10 @@ hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out1
 hipError_t launch_deint(hipStream_t st, const DeintArgs &a, bool is16);
 // denoising source (kernels/denoise.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth
 hipError_t launch_denoise(hipStream_t st, const DenoiseArgs &a, bool is16);
+// inverse telecine (kernels/fieldmatch.h).  Metrics: k_fm_metrics over the luma tiles of `a` into a.part, then k_fm_fold into out[8] (device memory; nothing
+// to zero in front).  Weave: one launch writes the three coded-size planes of `a` (cur: the kept rows, prev: the others), margins included
+hipError_t launch_fm_metrics(hipStream_t st, const FmArgs &a, unsigned long long *out, bool is16);
+hipError_t launch_fm_weave(hipStream_t st, const DeintArgs &a, bool is16);
 
 // rows between the slices of one picture (csrc/slice_group.h): jobs[i] for i < n_jobs, one grid row of `blocks_per_job` workgroups each
 hipError_t launch_copy_rows(hipStream_t st, const RowCopy *d_jobs, int n_jobs, int blocks_per_job);

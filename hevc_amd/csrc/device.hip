@@ -248,6 +248,41 @@ hipError_t launch_denoise(hipStream_t st, const DenoiseArgs &a, bool is16)
     return hipGetLastError();
 }
 
+// inverse telecine (kernels/fieldmatch.h).  k_fm_metrics: one workgroup per luma tile of FM_TW x FM_TH samples, 28,560 bytes of LDS: four workgroups per CU take
+// 112 KB of the CU's 160.  k_fm_fold: one workgroup over their partials.  k_fm_weave: the deinterlacer's tiles, no LDS
+template <typename T> __global__ __launch_bounds__(NT, 4) void k_fm_metrics(const FmArgs a)
+{
+    __shared__ __align__(16) FmShared s;
+    GpuExec ex;
+    fm_metrics_program<T>(ex, s, a, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(NT) void k_fm_fold(const unsigned long long *part, int n, unsigned long long *out)
+{
+    __shared__ __align__(16) FmShared s;
+    GpuExec ex;
+    fm_fold_program(ex, s, part, n, out);
+}
+template <typename T> __global__ __launch_bounds__(NT) void k_fm_weave(const DeintArgs a)
+{
+    GpuExec ex;
+    fm_weave_program<T>(ex, a, (int)blockIdx.x);
+}
+hipError_t launch_fm_metrics(hipStream_t st, const FmArgs &a, unsigned long long *out, bool is16)
+{
+    const int n = fm_workgroups(a.w, a.h);
+    if (is16) hipLaunchKernelGGL((k_fm_metrics<uint16_t>), dim3((unsigned)n), dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((k_fm_metrics<uint8_t>), dim3((unsigned)n), dim3(NT), 0, st, a);
+    hipLaunchKernelGGL(k_fm_fold, dim3(1), dim3(NT), 0, st, a.part, n, out);
+    return hipGetLastError();
+}
+hipError_t launch_fm_weave(hipStream_t st, const DeintArgs &a, bool is16)
+{
+    const dim3 grid((unsigned)deint_workgroups(a.pw, a.ph)), block(NT);
+    if (is16) hipLaunchKernelGGL((k_fm_weave<uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_fm_weave<uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 // RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
 template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
 {
@@ -1100,6 +1135,39 @@ int stage_denoise(const mihevc_denoise &dn, const void *const *prev, const void 
     return dst.planes.download(out);
 }
 
+// the metrics kernels of inverse telecine alone
+template <typename T> int stage_fm_metrics(const void *prev, const void *cur, const void *next, int w, int h, int pitch, int depth, int keep, uint64_t *out)
+{
+    DevBuf din[3], dpart;
+    const void *d[3] = {prev, cur, next};
+    for (int f = 0; f < 3; f++)
+        if (int e = upload_as_laid_out(din[f], d[f], w, h, pitch, sizeof(T))) return e;
+    const size_t n = (size_t)fm_workgroups(w, h);
+    CK(dpart.alloc((n + 1) * 8 * sizeof(unsigned long long)));
+    unsigned long long *part = dpart.as<unsigned long long>();
+    CK(launch_fm_metrics(0, fm_args(depth, d[0], d[1], d[2], pitch, w, h, keep, part), part + n * 8, sizeof(T) == 2));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, part + n * 8, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+// the weave kernel of inverse telecine alone
+template <typename T> int stage_fm_weave(const void *const *cur, const void *const *other, int w, int h, int pitch_y, int pitch_c, int depth, int keep, void *const *out)
+{
+    DevBuf din[6];
+    ConvertOut<T> dst;
+    if (int e = dst.alloc(w, h)) return e;
+    const void *d[2][3];
+    for (int f = 0; f < 2; f++)
+        for (int c = 0; c < 3; c++) {
+            d[f][c] = (f ? other : cur)[c];
+            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
+        }
+    const DeintArgs a = deint_args(depth, d[1], d[0], d[1], pitch_y, pitch_c, w, h, dst.w, dst.h, keep, 0, dst.p, dst.stride);
+    CK(launch_fm_weave(0, a, sizeof(T) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.planes.download(out);
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -1332,6 +1400,28 @@ int mihevc_k_denoise(int device, const mihevc_denoise *dn, const void *const pre
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(bit_depth, [&](auto t) { return stage_denoise<decltype(t)>(*dn, prev, cur, next, width, height, pitch_y, pitch_c, bit_depth, out); });
+}
+
+int mihevc_k_fieldmatch_metrics(int device, const void *prev_y, const void *cur_y, const void *next_y, int width, int height, int pitch, int bit_depth, int keep,
+                                uint64_t out[8])
+{
+    if (!prev_y || !cur_y || !next_y || !out || !deint_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch < width) return MIHEVC_EINVAL;
+    if (keep != 0 && keep != 1) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return with_depth(bit_depth, [&](auto t) { return stage_fm_metrics<decltype(t)>(prev_y, cur_y, next_y, width, height, pitch, bit_depth, keep, out); });
+}
+
+int mihevc_k_fieldmatch_weave(int device, const void *const cur[3], const void *const other[3], int width, int height, int pitch_y, int pitch_c, int bit_depth,
+                              int keep, void *out_y, void *out_u, void *out_v)
+{
+    if (!cur || !other || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
+    for (int c = 0; c < 3; c++)
+        if (!cur[c] || !other[c]) return MIHEVC_EINVAL;
+    if (!deint_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
+    if (keep != 0 && keep != 1) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(bit_depth, [&](auto t) { return stage_fm_weave<decltype(t)>(cur, other, width, height, pitch_y, pitch_c, bit_depth, keep, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

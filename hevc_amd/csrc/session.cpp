@@ -26,6 +26,7 @@
 
 #include "bitstream.h"
 #include "device.h"
+#include "fieldmatch_plan.h"
 #include "gop_plan.h"
 #include "host_pool.h"
 #include "md5.h"
@@ -121,7 +122,7 @@ struct mihevc_session {
     // first call; frame k lies in slot k % 3.  Copies and k_deint / k_denoise launches are neighbours on st_pre, so a slot is overwritten in stream order behind
     // the last launch that read it.  src_ring_kind: the entry that filled the ring first (a pending frame keeps every other entry out until flush, so it is the only
     // one); src_ring_n: frames taken; src_ring_pending: the last of them has not produced its picture(s) yet (the next frame or mihevc_flush does that)
-    enum { RING_NONE = 0, RING_DEINT, RING_DENOISE };
+    enum { RING_NONE = 0, RING_DEINT, RING_DENOISE, RING_FIELDMATCH };
     CachedBlock<uint8_t> src_ring[3];
     void *src_ring_p[3][3] = {};
     int src_ring_pitch[3] = {};
@@ -130,6 +131,18 @@ struct mihevc_session {
     bool src_ring_pending = false;
     int deint_tff = 0, deint_field_rate = 0;
     mihevc_denoise denoise_pending = {};      // the strengths of the pending frame
+    // mihevc_send_frame_fieldmatch: the frames go through the same ring.  fm_open: from the first fieldmatch frame until flush no other entry
+    // sends a frame.  fm_dev: the partials of k_fm_metrics and the eight folded numbers behind them; fm_host: their pinned copy, valid behind ev_fm.  fm_frames:
+    // what was decided, by frame (decided: mihevc_get_fieldmatch_info may hand it out; under `m`).  fm_held: decimate: the filled pictures of the open cycle with
+    // their frames' numbers; fm_pictures: pictures handed on so far
+    bool fm_open = false;
+    mihevc_fieldmatch fm_mode = {};
+    CachedBlock<uint8_t> fm_dev, fm_host;
+    Event ev_fm;
+    struct FmFrame { mihevc_fm_frame info; bool decided; };
+    std::vector<FmFrame> fm_frames;
+    std::vector<std::pair<Src, int64_t>> fm_held;
+    int64_t fm_pictures = 0, fm_first_pts = 0;
     // per lane
     // The vector moves a lane's handles when it grows; the blocks they own stay where they are, so the raw pointers in argument blocks, jobs and BandPub stay valid
     struct Lane {
@@ -1400,7 +1413,7 @@ static int ingest(mihevc_session *s, const void *y, const void *u, const void *v
 {
     if (!s || !y || !u || !v) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
-    if (s->flushed || s->src_ring_pending) return MIHEVC_ESTATE;      // (a deinterlaced or denoised frame waits for its successor: no other picture may come between)
+    if (s->flushed || s->src_ring_pending || s->fm_open) return MIHEVC_ESTATE;      // (a deinterlaced or denoised frame waits for its successor: no other picture may come between; fieldmatch cycles are not interleaved)
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     mihevc_session::Src src;
     const void *in[3] = {y, u, v};
@@ -1517,6 +1530,72 @@ static int ring_emit(mihevc_session *s, int64_t k, bool has_next, bool wait)
     return MIHEVC_OK;
 }
 
+// decimate: the held pictures go on in order, all but the one at `drop` (-1: a partial cycle comes out whole), whose planes go back to free_src
+static int fm_release(mihevc_session *s, int drop, bool wait)
+{
+    auto held = std::move(s->fm_held);
+    s->fm_held.clear();
+    int e = MIHEVC_OK;
+    for (size_t i = 0; i < held.size(); i++) {
+        const bool dropped = (int)i == drop;
+        {
+            std::lock_guard<std::mutex> l(s->m);
+            auto &f = s->fm_frames[(size_t)held[i].second];
+            f.info.dropped = dropped; f.info.picture = dropped || e ? -1 : s->fm_pictures; f.decided = true;
+        }
+        if (dropped || e) { s->free_src.push_back(std::move(held[i].first)); continue; }
+        e = finish_ingest(s, std::move(held[i].first), s->fm_first_pts + s->fm_pictures++, wait);
+    }
+    return e;
+}
+
+// Frame k of the ring is decided (mihevc_send_frame_fieldmatch): P, C, N as ring_emit.  The metrics of the frame are taken on st_pre and copied to
+// pinned memory behind ev_fm; the host waits for that event only, plans (csrc/fieldmatch_plan.h) and launches the weave, or the deinterlacer, into a Src.
+// Without decimate the picture goes on with its frame's pts; with it the picture is held until its cycle's fifth frame is decided
+static int fm_decide(mihevc_session *s, int64_t k, bool has_next, bool wait)
+{
+    s->src_ring_pending = false;
+    void *const *C = s->src_ring_p[k % 3], *const *P = s->src_ring_p[(k > 0 ? k - 1 : k) % 3], *const *N = s->src_ring_p[(has_next ? k + 1 : k) % 3];
+    const int W = s->cfg.width, H = s->cfg.height, keep = s->fm_mode.tff ? 0 : 1;
+    const size_t nwg = (size_t)fm_workgroups(W, H);
+    unsigned long long *const part = (unsigned long long *)s->fm_dev.get(), *const host = (unsigned long long *)s->fm_host.get();
+    HIPCK(s, launch_fm_metrics(s->st_pre, fm_args(s->cfg.bit_depth, P[0], C[0], N[0], s->src_ring_pitch[0], W, H, keep, part), part + nwg * 8, s->is16));
+    HIPCK(s, hipMemcpyAsync(host, part + nwg * 8, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st_pre));
+    HIPCK(s, hipEventRecord(s->ev_fm, s->st_pre));
+    HIPCK(s, hipEventSynchronize(s->ev_fm));
+    FmMetrics m = fm_metrics_of(host);
+    if (k == 0) fm_first_frame(m);
+    const int match = fm_match(m);
+    const bool fallback = fm_falls_back(m, match, s->fm_mode.deint != 0);
+    mihevc_session::Src src;
+    if (int e = take_src(s, src)) return e;
+    if (fallback) {
+        const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], W, H, s->w, s->h, keep, 0, src.p, src.stride);
+        HIPCK(s, launch_deint(s->st_pre, a, s->is16));
+    } else {
+        void *const *X = match == 0 ? C : match == 1 ? P : N;
+        const DeintArgs a = deint_args(s->cfg.bit_depth, X, C, X, s->src_ring_pitch[0], s->src_ring_pitch[1], W, H, s->w, s->h, keep, 0, src.p, src.stride);
+        HIPCK(s, launch_fm_weave(s->st_pre, a, s->is16));
+    }
+    mihevc_fm_frame info = {};
+    for (int i = 0; i < 3; i++) { info.comb_sum[i] = m.comb_sum[i]; info.comb_block[i] = m.comb_block[i]; }
+    info.dup_sum = m.dup_sum; info.dup_block = m.dup_block; info.match = match; info.deinterlaced = fallback; info.dropped = 0;
+    info.picture = s->fm_mode.decimate ? -1 : s->fm_pictures;
+    {
+        std::lock_guard<std::mutex> l(s->m);
+        s->fm_frames[(size_t)k] = {info, !s->fm_mode.decimate};
+    }
+    if (!s->fm_mode.decimate) { s->fm_pictures++; return finish_ingest(s, std::move(src), s->src_ring_pts, wait); }
+    s->fm_held.emplace_back(std::move(src), k);
+    if ((int)s->fm_held.size() < kFmCycle) return MIHEVC_OK;
+    FmMetrics cycle[kFmCycle] = {};
+    for (int i = 0; i < kFmCycle; i++) {
+        const mihevc_fm_frame &f = s->fm_frames[(size_t)s->fm_held[(size_t)i].second].info;
+        cycle[i].dup_sum = f.dup_sum; cycle[i].dup_block = f.dup_block;
+    }
+    return fm_release(s, fm_drop(cycle), wait);
+}
+
 // A frame of kind `kind` (mihevc_send_frame_deint, mihevc_send_frame_denoise; the arguments are checked): into its slot of the ring, then the picture(s) of the frame
 // before it.  Returns with src_ring_pts still that of the frame before: the caller sets what belongs to the new frame
 static int ingest_ring(mihevc_session *s, int kind, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
@@ -1541,7 +1620,7 @@ static int ingest_ring(mihevc_session *s, int kind, const void *y, const void *u
     s->src_ring_n = k + 1;
     const bool wait = !device_src && !async;
     int e = MIHEVC_OK;
-    if (k > 0) e = ring_emit(s, k - 1, true, wait);      // (src_ring_pts and denoise_pending are still those of frame k - 1)
+    if (k > 0) e = kind == mihevc_session::RING_FIELDMATCH ? fm_decide(s, k - 1, true, wait) : ring_emit(s, k - 1, true, wait);      // (src_ring_pts and denoise_pending are still those of frame k - 1)
     else if (wait) HIPCK(s, hipStreamSynchronize(s->st_pre));
     else s->up_pending = true;
     s->src_ring_pts = pts;
@@ -1574,6 +1653,7 @@ static int refuse_source(const mihevc_session *s, bool args_ok, int flags, int k
     if (!args_ok || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
     if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
     if (s->failed) return s->fail_code;
+    if (s->fm_open && kind != mihevc_session::RING_FIELDMATCH) return MIHEVC_ESTATE;      // (from the first fieldmatch frame until flush)
     return s->flushed || (s->src_ring_pending && s->src_ring_kind != kind) ? MIHEVC_ESTATE : MIHEVC_OK;
 }
 int mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
@@ -1620,6 +1700,36 @@ int mihevc_send_frame_denoise(mihevc_session *s, const mihevc_denoise *d, const 
     s->denoise_pending = *d;      // (the picture of the frame before has been launched with its own)
     return e;
 }
+int mihevc_send_frame_fieldmatch(mihevc_session *s, const mihevc_fieldmatch *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const bool args_ok = s && fieldmatch_mode_ok(d) && y && u && v &&
+                         (!s->fm_open || (d->tff == s->fm_mode.tff && d->decimate == s->fm_mode.decimate && d->deint == s->fm_mode.deint)) &&
+                         deint_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width && pitch_c >= s->cfg.width / 2;
+    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_FIELDMATCH)) return e;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    if (!s->fm_open) {
+        const size_t bytes = ((size_t)fm_workgroups(s->cfg.width, s->cfg.height) + 1) * 8 * sizeof(unsigned long long);
+        if (!s->ev_fm) s->ev_fm = Event(hipEventDisableTiming);
+        if (!s->ev_fm) return fail(s, "mihevc_send_frame_fieldmatch: no event");
+        HIPCK(s, s->fm_dev.alloc(s->device, (bytes + 255) & ~(size_t)255, false));
+        HIPCK(s, s->fm_host.alloc(s->device, 256, true));
+        s->fm_mode = *d; s->fm_first_pts = pts; s->fm_open = true;
+    }
+    {
+        std::lock_guard<std::mutex> l(s->m);
+        s->fm_frames.push_back({{}, false});
+    }
+    return ingest_ring(s, mihevc_session::RING_FIELDMATCH, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+}
+int mihevc_get_fieldmatch_info(mihevc_session *s, int64_t frame, mihevc_fm_frame *out)
+{
+    if (!s || !out) return MIHEVC_EINVAL;
+    std::lock_guard<std::mutex> l(s->m);
+    if (frame < 0 || (size_t)frame >= s->fm_frames.size()) return MIHEVC_EINVAL;
+    if (!s->fm_frames[(size_t)frame].decided) return MIHEVC_EAGAIN;
+    *out = s->fm_frames[(size_t)frame].info;
+    return MIHEVC_OK;
+}
 int mihevc_sync_uploads(mihevc_session *s)
 {
     if (!s) return MIHEVC_EINVAL;
@@ -1637,7 +1747,10 @@ int mihevc_flush(mihevc_session *s)
     if (s->flushed) return MIHEVC_OK;
     if (s->src_ring_pending) {      // the last frame of the ring: its successor is itself
         if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-        if (int e = ring_emit(s, s->src_ring_n - 1, false, false)) return e;
+        if (s->src_ring_kind == mihevc_session::RING_FIELDMATCH) {      // and what is left of an open cycle comes out whole
+            if (int e = fm_decide(s, s->src_ring_n - 1, false, false)) return e;
+            if (int e = fm_release(s, -1, false)) return e;
+        } else if (int e = ring_emit(s, s->src_ring_n - 1, false, false)) return e;
     }
     s->flushing = true;
     int e = run_chunk(s);

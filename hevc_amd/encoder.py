@@ -233,6 +233,36 @@ class Encoder:
         self._pts = pts + (2 if field_rate else 1)
         self._check(self._lib.mihevc_send_frame_deint(self._s, C.byref(mode), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_deint")
 
+    def send_fieldmatch(self, y, u, v, tff: bool = True, decimate: bool = True, deint: bool = True, asynchronous: bool = False, pts: Optional[int] = None):
+        """mihevc_send_frame_fieldmatch: a woven frame of the session's display size, planar 4:2:0 at the session's depth, that carries film in fields (3:2
+        pulldown): inverse telecine on the device.  tff: the declared field order.  decimate: of every five frames the repeat is dropped and the
+        pictures are numbered pts_first, pts_first + 1, ...: the session is opened at 4/5 of the source rate.  deint: frames that stay combed are deinterlaced.
+        A frame is decided once the next one has arrived, the last one with flush(); with decimate its picture waits for the cycle's fifth frame.  Every call
+        waits for the metrics of the frame before, so an asynchronous one returns with less in flight than send_async does.  Geometry, planes and the mode of
+        the first call: the rules of send_deint; no other send_* may follow before flush()."""
+        c = self.cfg
+        mode = _lib.Fieldmatch(int(bool(tff)), int(bool(decimate)), int(bool(deint)))
+        planes = [y, u, v]
+        shapes = [(c.height, c.width)] + [(c.height // 2, c.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of the session")
+        es = 1 if c.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(mode, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_fieldmatch")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_fieldmatch(self._s, C.byref(mode), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_fieldmatch")
+
+    def fieldmatch_info(self, i: int):
+        """mihevc_get_fieldmatch_info: the _lib.FmFrame of fieldmatch frame i (metrics, match, deinterlaced, dropped, picture), or None while it is undecided"""
+        out = _lib.FmFrame()
+        rc = self._lib.mihevc_get_fieldmatch_info(self._s, int(i), C.byref(out))
+        if rc == _lib.EAGAIN:
+            return None
+        self._check(rc, "get_fieldmatch_info")
+        return out
+
     def send_denoise(self, y, u, v, strength=2, asynchronous: bool = False, pts: Optional[int] = None):
         """mihevc_send_frame_denoise: a progressive frame of the session's display size, planar 4:2:0 at the session's depth, denoised on the device by the
         motion-adaptive spatio-temporal filter of DESIGN.md §6g.  strength: a level 0 .. 3 (_lib.denoise_level), a tuple (luma_spatial, luma_temporal,
@@ -685,7 +715,10 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     deinterlace: the source's frames are woven interlaced frames, deinterlaced on the device (Encoder.send_deint).  'frame': one picture per
     frame; 'field': one per field, so the session, its level, the rate figures and the MP4 track run at twice the frame rate; 'auto': 'frame' when the source
     says it is interlaced (the y4m header's It / Ib tag, else ffprobe's field_order), nothing otherwise.  tff: the field order, None to take the source's word
-    (top field first when it has none).  Planar 4:2:0 sources at the session's depth on one device; not together with size= or native_rgb.
+    (top field first when it has none).  Planar 4:2:0 sources at the session's depth on one device; not together with size= or native_rgb.  'ivtc' and 'match':
+    the frames carry film in fields (3:2 pulldown) and go through inverse telecine instead (Encoder.send_fieldmatch), with the same exclusions and
+    field-order lookup: 'ivtc' matches fields and drops one frame of every five, so the session, its level, the progress total and the MP4 track run at exactly
+    4/5 of the source rate (30000/1001 gives 24000/1001); 'match' only matches fields and keeps the rate.  'auto' keeps meaning the deinterlacer.
     denoise: a level 1 .. 3 or a tuple of four thresholds (Encoder.send_denoise): every frame is denoised on the device in front of the session.
     None and 0: nothing changes.  Planar 4:2:0 sources at the session's depth on one device; not together with deinterlace=, size=, native_rgb, sliced sessions or several devices."""
     import copy
@@ -704,10 +737,12 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     else:
         denoise = None
     deint = None            # (top field first, field rate) once deinterlacing is on
+    ivtc = None             # (top field first, decimate) once inverse telecine is on
+    ivtc_rate = None        # 'ivtc': the session's rate, 4/5 of the source's as a fraction
     clip_info = info        # what the clip is opened with: the source's own rate and frame count
     if deinterlace is not None:
-        if deinterlace not in ('frame', 'field', 'auto') or size is not None or native_rgb or (devices and len(devices) > 1):
-            logger.error("%s: deinterlace=%r takes 'frame', 'field' or 'auto', one device, and neither size= nor native_rgb", Path(file_path).name, deinterlace)
+        if deinterlace not in ('frame', 'field', 'auto', 'ivtc', 'match') or size is not None or native_rgb or (devices and len(devices) > 1):
+            logger.error("%s: deinterlace=%r takes 'frame', 'field', 'auto', 'ivtc' or 'match', one device, and neither size= nor native_rgb", Path(file_path).name, deinterlace)
             return 1
         order = tff
         if order is None:
@@ -721,7 +756,15 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 order = probe_field_order(Path(file_path))
             if order is None and deinterlace != 'auto':
                 order = True
-        if order is not None:
+        if deinterlace in ('ivtc', 'match'):
+            ivtc = (bool(order), deinterlace == 'ivtc')
+            if ivtc[1]:
+                from fractions import Fraction
+                ivtc_rate = Fraction(str(info.fps or 30.0)).limit_denominator(1001) * Fraction(4, 5)
+                info = copy.copy(info)
+                info.fps = float(ivtc_rate)
+                info.nb_frames = int(getattr(info, 'nb_frames', 0) or 0) * 4 // 5
+        elif order is not None:
             deint = (bool(order), deinterlace == 'field')
         if deint and deint[1]:
             info = copy.copy(info)
@@ -734,13 +777,15 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
     sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
-    clip = yuvio.open_any(Path(file_path), (clip_info if deint else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
+    clip = yuvio.open_any(Path(file_path), (clip_info if deint or ivtc else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
     mux = None
     ok = False
     try:
         if clip.bit_depth > 8 and bit_depth_of(info) == 8:      # the file's own header outranks the probe (a y4m tagged C420p10 probed as SDR)
             info.pix_fmt = 'yuv420p10le'
         cfg = config_for(info, crf, maxrate, bufsize, gop, level, tier)
+        if ivtc_rate is not None:
+            cfg.fps_num, cfg.fps_den = ivtc_rate.numerator, ivtc_rate.denominator
         fmt = getattr(clip, 'src_format', None)     # not the session's own layout: converted on the device (send_fmt)
         rgb = getattr(clip, 'rgb_format', None)     # an RGB source: matrixed and decimated on the device (send_rgb)
         if rgb is not None:
@@ -757,7 +802,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if fmt is not None and sliced:
             logger.error("%s: a %r source cannot be split by rows", Path(file_path).name, fmt)
             return 1
-        if deint and (fmt is not None or sliced or cfg.width % 2 or cfg.height % 4 or min(cfg.width, cfg.height) < 16):
+        if (deint or ivtc) and (fmt is not None or sliced or cfg.width % 2 or cfg.height % 4 or min(cfg.width, cfg.height) < 16):
             logger.error("%s: deinterlace= takes a planar 4:2:0 source at the session's depth, width even, height a multiple of 4 (%r, %dx%d)",
                          Path(file_path).name, fmt, cfg.width, cfg.height)
             return 1
@@ -765,6 +810,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             logger.error("%s: denoise= takes a planar 4:2:0 source at the session's depth, width and height even (%r, %dx%d)", Path(file_path).name, fmt, cfg.width, cfg.height)
             return 1
         total = (clip.n_frames or total_frames) * (2 if deint and deint[1] else 1)
+        if ivtc and ivtc[1]:
+            total = total * 4 // 5
         wants_audio = bool(info.audio_channels and info.audio_channels > 0) and Path(file_path).suffix.lower() not in ('.y4m', '.yuv')
         video_path = Path(out_path).with_suffix('.video.mp4') if wants_audio else Path(out_path)
         mux = mp4.Mp4Writer(video_path, cfg)
@@ -806,6 +853,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                         return 1
                     if deint:
                         enc.send_deint(*planes, tff=deint[0], field_rate=deint[1], pts=i * (2 if deint[1] else 1))
+                    elif ivtc:
+                        enc.send_fieldmatch(*planes, tff=ivtc[0], decimate=ivtc[1], deint=True, pts=i)
                     elif denoise is not None:
                         enc.send_denoise(*planes, strength=denoise, pts=i)
                     elif size is not None:

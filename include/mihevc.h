@@ -274,7 +274,7 @@ int  mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, co
  * frame before, the frame itself and the frame after; the first frame stands in for its missing predecessor and the last one for its missing successor.
  * Frame-rate mode gives one picture per frame (the first field's rows kept), field-rate mode two: the first field's with the frame's pts, the second field's with
  * pts + 1, so the caller numbers pts in field periods and opens the session at twice the frame rate.  The stream stays progressive (HEVC has no interlaced
- * coding tools).  Not covered: inverse telecine and field matching, other filters, other layouts or depths than the session's, scaling in the same pass,
+ * coding tools).  Inverse telecine and field matching: mihevc_send_frame_fieldmatch.  Not covered: other filters, other layouts or depths than the session's, scaling in the same pass,
  * parity changes inside a clip, sliced sessions, pic_struct signalling. */
 typedef struct mihevc_deint {
     int32_t tff;          /* 1: top field first, 0: bottom field first */
@@ -311,6 +311,45 @@ typedef struct mihevc_denoise {
  * MIHEVC_ESTATE while a denoised frame is pending (sent, its picture not yet produced), and this one does while a deinterlaced frame is pending. */
 int  mihevc_send_frame_denoise(mihevc_session *s, const mihevc_denoise *d, const void *y, const void *u, const void *v,
                                int pitch_y, int pitch_c, int64_t pts, int flags);
+/* ---- added under ABI 6: TELECINED sources (symbols only) ----
+ * Woven frames of the session's DISPLAY size, planar 4:2:0 at cfg.bit_depth (uint8 at 8 bit, else little-endian uint16, values above 2^bit_depth - 1 clamped),
+ * that carry film in fields (3:2 pulldown): inverse telecine on the device with an exact integer definition (hevc_amd/csrc/kernels/fieldmatch.h
+ * states the metrics, hevc_amd/csrc/fieldmatch_plan.h the decisions).  Field matching: the rows of the declared first field of a frame are kept and woven with
+ * the other rows of the frame itself (c), of the frame before (p) or of the frame after (n), whichever combs least; nothing is interpolated.  deint: a frame
+ * whose best match is still combed (video passages, orphan fields at edits) becomes the picture mihevc_send_frame_deint gives in frame-rate mode.  decimate:
+ * of every cycle of five frames, counted from the first, the one that differs least from the frame before it is dropped; the j-th picture that comes out takes
+ * pts_first + j, so the caller opens the session at 4/5 of the source rate; a last cycle of fewer than five frames comes out whole.  Without decimate a picture
+ * takes its frame's pts.  Not covered: other cadences and variable cycles, variable-frame-rate output, blended fields, pic_struct signalling, scaling, denoising
+ * or RGB in the same session, sliced sessions. */
+typedef struct mihevc_fieldmatch {
+    int32_t tff;          /* 1: top field first, 0: bottom field first (the DECLARED order; the n match serves a clip whose order is the opposite) */
+    int32_t decimate;     /* 1: drop one frame of every five */
+    int32_t deint;        /* 1: deinterlace frames that stay combed */
+    int32_t reserved[5];  /* 0 */
+} mihevc_fieldmatch;
+/* pitch_y, pitch_c: in elements.  The frame is copied into the ring of three source-size pictures that mihevc_send_frame_deint uses too; flags and ownership are
+ * those of mihevc_send_frame_deint.  Frame k is decided when frame k + 1 arrives, the last frame by mihevc_flush: its metrics are taken on the device, the call
+ * waits for them (and so for everything sent before, the new frame's upload included: with MIHEVC_SRC_ASYNC it returns with less in flight than the other
+ * entries do) and launches the picture.  With decimate the pictures of the open cycle are held until its fifth frame is decided.  mihevc_stats.frames_in counts
+ * pictures.  MIHEVC_EINVAL, decided before any device call and leaving the session usable: NULL d or plane, a field of d outside {0, 1}, non-zero reserved, a
+ * mode other than that of the session's first fieldmatch frame, cfg.width odd, cfg.height not a multiple of 4, either below 16, a pitch smaller than the plane,
+ * unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush, and while a deinterlaced or denoised frame is pending; every OTHER entry that sends a frame
+ * returns MIHEVC_ESTATE from the first fieldmatch frame until flush. */
+int  mihevc_send_frame_fieldmatch(mihevc_session *s, const mihevc_fieldmatch *d, const void *y, const void *u, const void *v,
+                                  int pitch_y, int pitch_c, int64_t pts, int flags);
+typedef struct mihevc_fm_frame {
+    uint64_t comb_sum[3];     /* S_c, S_p, S_n */
+    uint32_t comb_block[3];   /* K_c, K_p, K_n */
+    uint64_t dup_sum;         /* DS (the first frame: all-ones) */
+    uint32_t dup_block;       /* DB (the first frame: all-ones) */
+    int32_t match;            /* 0 c, 1 p, 2 n */
+    int32_t deinterlaced;     /* 1: the picture is the deinterlacer's */
+    int32_t dropped;          /* 1: decimated */
+    int64_t picture;          /* output index, -1 dropped */
+} mihevc_fm_frame;
+/* What was decided for fieldmatch frame `frame` (0-based, in the order sent).  MIHEVC_EAGAIN until it is decided: the frame has arrived but the next one (or
+ * flush) has not, or, with decimate, its cycle is still open; MIHEVC_EINVAL: NULL, or a frame that was never sent. */
+int  mihevc_get_fieldmatch_info(mihevc_session *s, int64_t frame, mihevc_fm_frame *out);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -475,6 +514,19 @@ int mihevc_k_deinterlace(int device, const void *const prev[3], const void *cons
  * or 10), then MIHEVC_ENODEV without a device */
 int mihevc_k_denoise(int device, const mihevc_denoise *d, const void *const prev[3], const void *const cur[3], const void *const next[3],
                      int width, int height, int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v);
+
+/* added under ABI 6.  The metrics of mihevc_send_frame_fieldmatch alone (k_fm_metrics and its fold, the session's kernels), host buffers in and out: prev_y /
+ * cur_y / next_y name the luma planes of three frames of width x height samples at bit_depth (they may name the same plane), one pitch for all of them, in
+ * elements; keep: parity of the rows of the declared first field.  out: S_c S_p S_n K_c K_p K_n DS DB as the kernel takes them (the all-ones of a clip's first
+ * frame are the session's).  Validated first (MIHEVC_EINVAL: a NULL pointer, width odd, height not a multiple of 4, either below 16, a short pitch, a bit_depth
+ * other than 8 or 10, keep outside {0, 1}), then MIHEVC_ENODEV without a device */
+int mihevc_k_fieldmatch_metrics(int device, const void *prev_y, const void *cur_y, const void *next_y, int width, int height, int pitch, int bit_depth, int keep,
+                                uint64_t out[8]);
+/* added under ABI 6.  The weave of mihevc_send_frame_fieldmatch alone (k_fm_weave, the session's kernel), host buffers in and out: cur / other name the Y, Cb
+ * and Cr planes of the frame whose rows of parity keep are taken and of the frame that gives the other rows (they may name the same planes); out_* are planes of
+ * the CODED size as in mihevc_k_convert_source.  Validated first (MIHEVC_EINVAL: as mihevc_k_deinterlace), then MIHEVC_ENODEV without a device */
+int mihevc_k_fieldmatch_weave(int device, const void *const cur[3], const void *const other[3], int width, int height, int pitch_y, int pitch_c, int bit_depth,
+                              int keep, void *out_y, void *out_u, void *out_v);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
