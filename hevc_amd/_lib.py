@@ -142,6 +142,14 @@ def denoise_strength(s) -> Denoise:
     return Denoise(*(int(v) for v in t))
 
 
+class Lut3dSrc(C.Structure):
+    """mihevc_lut3d_src: depth, matrix and range of the planar 4:2:0 frames handed to mihevc_send_frame_lut3d / mihevc_k_lut3d"""
+    _fields_ = [(n, C.c_int32) for n in ("bit_depth", "matrix", "full_range")] + [("reserved", C.c_int32 * 4)]
+
+    def __repr__(self):
+        return f"Lut3dSrc(bit_depth={self.bit_depth}, matrix={self.matrix}, full_range={self.full_range})"
+
+
 class RgbFormat(C.Structure):
     """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
     _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
@@ -200,7 +208,7 @@ EXPORTS = (
     "mihevc_send_frame_fmt", "mihevc_k_convert_source", "mihevc_k_intra_plan", "mihevc_send_frame_rgb", "mihevc_k_convert_rgb",
     "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff", "mihevc_send_frame_deint", "mihevc_k_deinterlace",
     "mihevc_send_frame_denoise", "mihevc_k_denoise", "mihevc_send_frame_fieldmatch", "mihevc_get_fieldmatch_info", "mihevc_k_fieldmatch_metrics",
-    "mihevc_k_fieldmatch_weave",
+    "mihevc_k_fieldmatch_weave", "mihevc_set_lut3d", "mihevc_send_frame_lut3d", "mihevc_k_lut3d",
 )
 
 _lib = None
@@ -280,6 +288,9 @@ def load() -> C.CDLL:
     lib.mihevc_get_fieldmatch_info.argtypes = [vp, i64, C.POINTER(FmFrame)]
     lib.mihevc_k_fieldmatch_metrics.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.mihevc_k_fieldmatch_weave.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_set_lut3d.argtypes = [vp, i32, vp]
+    lib.mihevc_send_frame_lut3d.argtypes = [vp, C.POINTER(Lut3dSrc), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_lut3d.argtypes = [i32, C.POINTER(Lut3dSrc), i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i32)]
     _lib = lib
     return lib
 

@@ -14,6 +14,7 @@
 #include "kernels/inter.h"
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
+#include "kernels/lut3d.h"
 #include "kernels/pichash.h"
 #include "kernels/scale.h"
 #include "kernels/ssim.h"
@@ -76,6 +77,8 @@ template <typename T> hipError_t launch_extend_margin(hipStream_t st, Plane<T> p
 hipError_t launch_ingest(hipStream_t st, const IngestArgs &a, bool in16, bool out16);
 // RGB source conversion (kernels/ingest_rgb.h).  sample: mihevc_rgb_format::sample; elem_size: bytes of a source element
 hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample, int elem_size, bool out16);
+// colour table (kernels/lut3d.h): one launch writes the three coded-size planes of a.out, margins included.  in16 / out16: uint16 source elements / output samples
+hipError_t launch_lut3d(hipStream_t st, const Lut3dArgs &a, bool in16, bool out16);
 // downscaling source (kernels/scale.h): one launch writes the three coded-size planes of `a`, margins included, from a source of another size
 hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out16);
 // deinterlacing source (kernels/deint.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth

@@ -304,6 +304,24 @@ hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample,
     return hipGetLastError();
 }
 
+// colour table (kernels/lut3d.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, as k_ingest_rgb.  A lane's block of 16 x 2 pixels keeps
+// 128 independent table loads in flight and needs 178 .. 185 registers for them; two workgroups per CU (two waves per SIMD, 256 registers each) is the bound that
+// builds without scratch: at three the compiler spills 48 .. 76 bytes per lane, at four over 200
+template <typename TI, typename TO> __global__ __launch_bounds__(NT, 2) void k_lut3d(const Lut3dArgs a)
+{
+    GpuExec ex;
+    lut3d_tile_program<TI, TO>(ex, a, (int)blockIdx.x);
+}
+hipError_t launch_lut3d(hipStream_t st, const Lut3dArgs &a, bool in16, bool out16)
+{
+    const dim3 grid((unsigned)ingest_rgb_workgroups(a.out.pw, a.out.ph)), block(NT);
+    if (in16 && out16) hipLaunchKernelGGL((k_lut3d<uint16_t, uint16_t>), grid, block, 0, st, a);
+    else if (in16) hipLaunchKernelGGL((k_lut3d<uint16_t, uint8_t>), grid, block, 0, st, a);
+    else if (out16) hipLaunchKernelGGL((k_lut3d<uint8_t, uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_lut3d<uint8_t, uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 // scene-cut detector: sum of |a - b| over every 4th sample of every 4th row of the luma planes of pictures blockIdx.y - 1... the pair
 // (blockIdx.y, blockIdx.y + 1) -> out[blockIdx.y + 1]; wave reduction by shuffles, one atomic per wave
 template <typename T> __global__ __launch_bounds__(256) void k_scene_diff(const ScenePic<T> *pics, unsigned long long *out, int w, int h)
@@ -1070,6 +1088,31 @@ int stage_convert_rgb(const mihevc_rgb_format &f, const void *const *src, int w,
     return dst.planes.download(out);
 }
 
+// the colour table kernel alone; out: the caller's planes with their own strides
+template <typename TO>
+int stage_lut3d(const mihevc_lut3d_src &f, int n, const uint16_t *table, const void *const *src, int w, int h, int pitch_y, int pitch_c, int out_depth, int out_matrix,
+                bool out_full, void *const *out, const int *out_stride)
+{
+    const size_t es = f.bit_depth > 8 ? 2 : 1, entries = (size_t)n * n * n;
+    DevBuf din[3], dtab;
+    ConvertOut<TO> dst;
+    if (int e = dst.alloc(w, h)) return e;
+    const void *dsrc[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < 3; c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, es)) return e;
+    std::vector<uint16_t> packed(entries * 4);
+    lut3d_pack(n, table, packed.data());
+    if (int e = to_device(dtab, packed.data(), packed.size())) return e;
+    const Lut3dArgs a = lut3d_args(f, n, dtab.p, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, w, h, dst.w, dst.h, out_depth, out_matrix, out_full, dst.p, dst.stride);
+    CK(launch_lut3d(0, a, es == 2, sizeof(TO) == 2));
+    CK(hipDeviceSynchronize());
+    for (int c = 0; c < 3; c++) {
+        const auto &pl = dst.planes.p[c];
+        CK(hipMemcpy2D(out[c], out_stride[c] * sizeof(TO), pl.pl.p, pl.pl.stride * sizeof(TO), pl.w * sizeof(TO), pl.h, hipMemcpyDeviceToHost));
+    }
+    return MIHEVC_OK;
+}
+
 // the scaling kernel alone
 template <typename TO>
 int stage_scale(const mihevc_scale_src &f, const void *const *src, int pitch_y, int pitch_c, int dw, int dh, int out_depth, void *const *out)
@@ -1363,6 +1406,21 @@ int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(out_bit_depth, [&](auto t) { return stage_convert_rgb<decltype(t)>(*fmt, src, width, height, pitch, out_bit_depth, out); });
+}
+
+int mihevc_k_lut3d(int device, const mihevc_lut3d_src *src, int n, const uint16_t *table, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
+                   int width, int height, int out_bit_depth, int out_matrix, int out_full_range, void *const out[3], const int out_stride[3])
+{
+    if (!lut3d_src_ok(src) || !lut3d_n_ok(n) || !table || !rgb_matrix_ok(out_matrix) || (out_full_range != 0 && out_full_range != 1)) return MIHEVC_EINVAL;
+    if (!convert_geometry_ok(width, height, out_bit_depth) || !lut3d_planes_ok(*src, y, u, v, pitch_y, pitch_c, width) || !out || !out_stride) return MIHEVC_EINVAL;
+    const int pw = (width + 7) & ~7;
+    for (int c = 0; c < 3; c++)
+        if (!out[c] || out_stride[c] < (c ? pw / 2 : pw)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *p[3] = {y, u, v};
+    return with_depth(out_bit_depth, [&](auto t) {
+        return stage_lut3d<decltype(t)>(*src, n, table, p, width, height, pitch_y, pitch_c, out_bit_depth, out_matrix, out_full_range != 0, out, out_stride);
+    });
 }
 
 int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int dst_width, int dst_height,

@@ -118,6 +118,13 @@ struct mihevc_session {
     CachedBlock<uint8_t> scale_tab;
     ScaleBlock scale_host;
     int scale_sw = 0, scale_sh = 0;
+    // mihevc_set_lut3d, mihevc_send_frame_lut3d: the packed table of lut_n points per axis (0: none) in one device block of the largest size,
+    // so a new table of any size overwrites the old one in stream order on st_pre, behind every k_lut3d launch that reads it and in front of the next.  It is
+    // copied from one of two pinned blocks, taken in turn; a block is written again only behind the event of the copy that read it, two tables back
+    CachedBlock<uint8_t> lut_dev, lut_host[2];
+    Event ev_lut[2];
+    int lut_n = 0;
+    int64_t lut_sets = 0;
     // mihevc_send_frame_deint, mihevc_send_frame_denoise: a ring of three source-size pictures (display size, rows that begin 16-byte aligned), allocated at the
     // first call; frame k lies in slot k % 3.  Copies and k_deint / k_denoise launches are neighbours on st_pre, so a slot is overwritten in stream order behind
     // the last launch that read it.  src_ring_kind: the entry that filled the ring first (a pending frame keeps every other entry out until flush, so it is the only
@@ -1473,6 +1480,22 @@ static int ingest_rgb(mihevc_session *s, const mihevc_rgb_format &f, int matrix,
     return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
+// A source through the colour table (mihevc_send_frame_lut3d; the arguments are checked, a table is set): as ingest_fmt, with k_lut3d
+static int ingest_lut3d(mihevc_session *s, const mihevc_lut3d_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
+{
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    mihevc_session::Src src;
+    if (int e = take_src(s, src)) return e;
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    const int W = s->cfg.width, H = s->cfg.height;
+    SrcPlane pl[3] = {{y, W, H, pitch_y}, {u, W / 2, H / 2, pitch_c}, {v, W / 2, H / 2, pitch_c}};
+    if (int e = stage_planes(s, pl, 3, es, device_src)) return e;
+    const Lut3dArgs a = lut3d_args(f, s->lut_n, s->lut_dev.get(), pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, W, H, s->w, s->h, s->cfg.bit_depth, s->cfg.matrix,
+                                   s->cfg.full_range != 0, src.p, src.stride);
+    HIPCK(s, launch_lut3d(s->st_pre, a, es == 2, s->is16));
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
+}
+
 // A source of another size (mihevc_send_frame_scaled; the arguments are checked): k_scale writes the session's own planes, margin included, from the caller's
 // device planes or from their copies in the staging set.  The tables of a new source size are built before the first device call
 static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
@@ -1675,6 +1698,32 @@ int mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const
     if (int e = refuse_source(s, fmt_ok && rgb_matrix_ok(matrix) && rgb_planes_ok(*fmt, p, pitch, s->cfg.width), flags)) return e;
     const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
     return ingest_rgb(s, *fmt, matrix, full, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+}
+int mihevc_set_lut3d(mihevc_session *s, int n, const uint16_t *table)
+{
+    if (!s || s->cfg.slice_count > 1 || (table && !lut3d_n_ok(n))) return MIHEVC_EINVAL;
+    if (s->failed) return s->fail_code;
+    if (!table) { s->lut_n = 0; return MIHEVC_OK; }
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    const size_t cap = ((size_t)LUT_MAX_N * LUT_MAX_N * LUT_MAX_N * LUT_ENTRY_BYTES + 255) & ~(size_t)255;
+    const int k = (int)(s->lut_sets & 1);
+    if (!s->lut_dev) HIPCK(s, s->lut_dev.alloc(s->device, cap, false));
+    if (!s->lut_host[k]) {
+        s->ev_lut[k] = Event(hipEventDisableTiming);
+        if (!s->ev_lut[k]) return fail(s, "mihevc_set_lut3d: no event");
+        HIPCK(s, s->lut_host[k].alloc(s->device, cap, true));
+    } else HIPCK(s, hipEventSynchronize(s->ev_lut[k]));      // the copy of the table before the last one
+    lut3d_pack(n, table, (uint16_t *)s->lut_host[k].get());
+    HIPCK(s, hipMemcpyAsync(s->lut_dev, s->lut_host[k], (size_t)n * n * n * LUT_ENTRY_BYTES, hipMemcpyHostToDevice, s->st_pre));
+    HIPCK(s, hipEventRecord(s->ev_lut[k], s->st_pre));
+    s->lut_n = n; s->lut_sets++;
+    return MIHEVC_OK;
+}
+int mihevc_send_frame_lut3d(mihevc_session *s, const mihevc_lut3d_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const bool args_ok = s && lut3d_src_ok(src) && s->lut_n && rgb_matrix_ok(s->cfg.matrix) && lut3d_planes_ok(*src, y, u, v, pitch_y, pitch_c, s->cfg.width);
+    if (int e = refuse_source(s, args_ok, flags)) return e;
+    return ingest_lut3d(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
 }
 int mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {

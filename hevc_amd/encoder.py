@@ -284,6 +284,36 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_denoise(self._s, C.byref(dn), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_denoise")
 
+    def set_lut3d(self, table):
+        """mihevc_set_lut3d: the 3D colour table send_lut3d interpolates in: an (n, n, n, 3) array indexed [b][g][r][c], the order of a .cube
+        file, 2 <= n <= 65; uint16 entries 0 .. 65535, or floats in [0, 1] that go through lut3d.quantise first.  It is copied before the call returns and may be
+        replaced between frames: frames already sent keep the table they were sent under.  None drops the table."""
+        if table is None:
+            self._check(self._lib.mihevc_set_lut3d(self._s, 0, None), "set_lut3d")
+            return
+        from . import lut3d
+        t = lut3d.as_uint16(table)
+        self._check(self._lib.mihevc_set_lut3d(self._s, t.shape[0], t.ctypes.data), "set_lut3d")
+
+    def send_lut3d(self, y, u, v, bit_depth: int, matrix: int, full_range: bool = False, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_lut3d: a planar 4:2:0 Y'CbCr picture of the session's display size at bit_depth 8, 10 or 12 with its own matrix (1, 5, 6 or 9) and
+        range, taken through the table of set_lut3d on the device and coded with the session's matrix, range and depth (an HDR master into an SDR stream).
+        numpy planes (uint8 at 8 bit, else uint16) are checked for shape and type here; torch tensors on the device are read where they are
+        (MIHEVC_SRC_DEVICE) under the rules of send_fmt.  asynchronous (host planes): the rules of send_async."""
+        c = self.cfg
+        src = _lib.Lut3dSrc(int(bit_depth), int(matrix), 1 if full_range else 0)
+        planes = [y, u, v]
+        shapes = [(c.height, c.width)] + [(c.height // 2, c.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of the session")
+        es = 1 if src.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(src, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_lut3d")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_lut3d(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_lut3d")
+
     def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
         Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
@@ -706,7 +736,7 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
-                tff: Optional[bool] = None, denoise=None) -> int:
+                tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -720,7 +750,12 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     field-order lookup: 'ivtc' matches fields and drops one frame of every five, so the session, its level, the progress total and the MP4 track run at exactly
     4/5 of the source rate (30000/1001 gives 24000/1001); 'match' only matches fields and keeps the rate.  'auto' keeps meaning the deinterlacer.
     denoise: a level 1 .. 3 or a tuple of four thresholds (Encoder.send_denoise): every frame is denoised on the device in front of the session.
-    None and 0: nothing changes.  Planar 4:2:0 sources at the session's depth on one device; not together with deinterlace=, size=, native_rgb, sliced sessions or several devices."""
+    None and 0: nothing changes.  Planar 4:2:0 sources at the session's depth on one device; not together with deinterlace=, size=, native_rgb, sliced sessions or several devices.
+    lut: every frame goes through a 3D colour table on the device (Encoder.send_lut3d): the path of a .cube file, an (n, n, n, 3) array, or
+    'hdr-to-sdr' for the built-in table of lut3d.hdr_to_sdr (the transfer from the probe, PQ unless it says HLG; peak_nits from the probed master_display when
+    there is one).  The session opens as SDR whatever the probe says of the source: 8 bit (lut_bit_depth=10: Main10), colour description 1/1/1, no HDR10 SEI, the
+    level and tier of an SDR clip; the reader keeps delivering the source's own planar 4:2:0 frames at 8, 10 or 12 bit, and the source's matrix is the probed one
+    (BT.2020 for HDR, else BT.709 when unknown).  One device; not together with size=, native_rgb, deinterlace= or denoise=."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
@@ -736,10 +771,36 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             return 1
     else:
         denoise = None
+    clip_info = info        # what the clip is opened with: the source's own description, rate and frame count
+    lut_table = None        # the uint16 table once lut= is on
+    if lut is not None:
+        from . import lut3d
+        if denoise is not None or deinterlace is not None or size is not None or native_rgb or (devices and len(devices) > 1) or lut_bit_depth not in (8, 10):
+            logger.error("%s: lut= takes a .cube path, an (n, n, n, 3) table or 'hdr-to-sdr', lut_bit_depth 8 or 10, one device, and none of size=, native_rgb, "
+                         "deinterlace=, denoise=", Path(file_path).name)
+            return 1
+        try:
+            if isinstance(lut, str) and lut == 'hdr-to-sdr':
+                from .utils import parse_master_display
+                transfer = 'hlg' if (info.color_transfer or '').lower() == 'arib-std-b67' else 'pq'
+                peak = parse_master_display(info.master_display).lum[0] / 10000.0 if (info.master_display or '').strip() else 1000.0
+                lut_table = lut3d.hdr_to_sdr(65, transfer, min(max(peak, lut3d.SDR_PEAK_NITS), 10000.0))
+            elif isinstance(lut, (str, Path)):
+                lut_table = lut3d.quantise(lut3d.read_cube(lut))
+            else:
+                lut_table = lut3d.as_uint16(lut)
+        except (OSError, TypeError, ValueError) as e:
+            logger.error("%s: lut=%r: %s", Path(file_path).name, lut if isinstance(lut, (str, Path)) else type(lut).__name__, e)
+            return 1
+        lut_src_matrix = _COLOUR_CODES["matrix"].get(info.color_space, 9 if info.hdr else 1)
+        lut_src_full = (info.pix_fmt or '').lower().startswith('yuvj')
+        info = copy.copy(info)      # the session, its level and the track are those of an SDR clip
+        info.hdr, info.master_display, info.max_cll = False, '', ''
+        info.color_primaries = info.color_transfer = info.color_space = 'bt709'
+        info.pix_fmt = 'yuv420p10le' if lut_bit_depth == 10 else 'yuv420p'
     deint = None            # (top field first, field rate) once deinterlacing is on
     ivtc = None             # (top field first, decimate) once inverse telecine is on
     ivtc_rate = None        # 'ivtc': the session's rate, 4/5 of the source's as a fraction
-    clip_info = info        # what the clip is opened with: the source's own rate and frame count
     if deinterlace is not None:
         if deinterlace not in ('frame', 'field', 'auto', 'ivtc', 'match') or size is not None or native_rgb or (devices and len(devices) > 1):
             logger.error("%s: deinterlace=%r takes 'frame', 'field', 'auto', 'ivtc' or 'match', one device, and neither size= nor native_rgb", Path(file_path).name, deinterlace)
@@ -777,11 +838,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
     sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
-    clip = yuvio.open_any(Path(file_path), (clip_info if deint or ivtc else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
+    clip = yuvio.open_any(Path(file_path), (clip_info if deint or ivtc or lut_table is not None else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
     mux = None
     ok = False
     try:
-        if clip.bit_depth > 8 and bit_depth_of(info) == 8:      # the file's own header outranks the probe (a y4m tagged C420p10 probed as SDR)
+        if lut_table is None and clip.bit_depth > 8 and bit_depth_of(info) == 8:      # the file's own header outranks the probe (a y4m tagged C420p10 probed as SDR)
             info.pix_fmt = 'yuv420p10le'
         cfg = config_for(info, crf, maxrate, bufsize, gop, level, tier)
         if ivtc_rate is not None:
@@ -792,6 +853,13 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             fmt = rgb
             if cfg.matrix not in (1, 5, 6, 9):
                 cfg.matrix = 1
+        if lut_table is not None:
+            lut_src_depth = int(fmt.bit_depth) if fmt is not None else int(clip.bit_depth)
+            planar420 = rgb is None and (fmt is None or (fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned))
+            if not planar420 or lut_src_depth not in (8, 10, 12) or sliced or cfg.width % 2 or cfg.height % 2 or min(cfg.width, cfg.height) < 16:
+                logger.error("%s: lut= takes a planar 4:2:0 source at 8, 10 or 12 bit, width and height even (%r, %dx%d)", Path(file_path).name, fmt, cfg.width, cfg.height)
+                return 1
+            fmt = None
         if size is not None:
             fmt420 = fmt is None or (rgb is None and fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned)
             if not fmt420 or (devices and len(devices) > 1):
@@ -848,10 +916,14 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 sh.close()                          # joins the workers (abort) before any session is closed
         else:
             with Encoder(cfg, device=device or 0) as enc:
+                if lut_table is not None:
+                    enc.set_lut3d(lut_table)
                 for i, planes in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    if deint:
+                    if lut_table is not None:
+                        enc.send_lut3d(*planes, bit_depth=lut_src_depth, matrix=lut_src_matrix, full_range=lut_src_full, pts=i)
+                    elif deint:
                         enc.send_deint(*planes, tff=deint[0], field_rate=deint[1], pts=i * (2 if deint[1] else 1))
                     elif ivtc:
                         enc.send_fieldmatch(*planes, tff=ivtc[0], decimate=ivtc[1], deint=True, pts=i)

@@ -248,6 +248,33 @@ typedef struct mihevc_rgb_format {
  * than the row, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush. */
 int  mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2,
                            int pitch, int64_t pts, int flags);
+/* ---- added under ABI 6: sources through a COLOUR TABLE (symbols only) ----
+ * A 3D lookup table with tetrahedral interpolation between the source's colours and the session's: an HDR master into an SDR stream, log footage into Rec.709, a
+ * grade shipped as a .cube file.  The source is a planar 4:2:0 Y'CbCr picture of the session's DISPLAY size at 8, 10 or 12 bit (uint8 at 8 bit, else little-endian
+ * uint16, lsb aligned, values above 2^bit_depth - 1 clamped) with its own matrix and range.  One kernel launch brings chroma to the luma grid, converts to
+ * R'G'B' at 16 bit, looks every pixel up in the table and goes on as mihevc_send_frame_rgb does for a 16-bit source: the session's matrix and range, cfg.bit_depth,
+ * 4:2:0, margin.  Integers throughout; hevc_amd/csrc/kernels/lut3d.h states the arithmetic, DESIGN.md 6i repeats it.  Not covered: RGB, 4:2:2 and 4:4:4 sources,
+ * 1D shaper tables, other interpolations, per-scene tone mapping, scaling, deinterlacing or denoising in the same pass, sliced sessions.
+ *
+ * mihevc_set_lut3d: table holds n^3 x 3 uint16 in host memory in the order of a .cube file, table[((b * n + g) * n + r) * 3 + c], input and output 0 .. 65535 for
+ * 0.0 .. 1.0; it is copied before the call returns.  The table may be replaced between frames: frames already sent keep the table they were sent under (the copy
+ * is ordered behind their launches on the upload stream; the device is not waited for).  table == NULL drops the table.  MIHEVC_EINVAL: n outside 2 .. 65 with a
+ * table, slice_count > 1. */
+int  mihevc_set_lut3d(mihevc_session *s, int n, const uint16_t *table);
+typedef struct mihevc_lut3d_src {
+    int32_t bit_depth;    /* 8, 10 or 12 */
+    int32_t matrix;       /* of the source: 1, 5, 6 or 9 */
+    int32_t full_range;   /* of the source: 0 limited, 1 full */
+    int32_t reserved[4];  /* 0 */
+} mihevc_lut3d_src;
+/* pitch_y, pitch_c: in elements.  Flags, staging, ownership and stream ordering are those of mihevc_send_frame_fmt.  The output matrix and range are the
+ * session's cfg.matrix and cfg.full_range, as mihevc_send_frame_rgb resolves them with matrix = 0 and range = 0.  MIHEVC_EINVAL, decided before any device call
+ * and leaving the session usable: NULL src or plane, a depth other than 8 / 10 / 12, a source matrix other than 1 / 5 / 6 / 9, full_range outside {0, 1}, non-zero
+ * reserved, no table set, a cfg.matrix other than 1 / 5 / 6 / 9, odd cfg.width / cfg.height, a pitch smaller than the plane, a plane whose address is not a
+ * multiple of the element size, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush.  The entry keeps no ring: it mixes with mihevc_send_frame and
+ * mihevc_send_frame_fmt as they mix with each other. */
+int  mihevc_send_frame_lut3d(mihevc_session *s, const mihevc_lut3d_src *src, const void *y, const void *u, const void *v,
+                             int pitch_y, int pitch_c, int64_t pts, int flags);
 /* ---- added under ABI 6: sources of another SIZE (symbols only) ----
  * A planar 4:2:0 picture of src->width x src->height samples at src->bit_depth, scaled down on the device into the session's planes of cfg.width x cfg.height
  * at cfg.bit_depth by a separable 16-tap polyphase Catmull-Rom filter with an exact integer definition (hevc_amd/csrc/kernels/scale.h and
@@ -494,6 +521,13 @@ int mihevc_k_convert_source(int device, const mihevc_src_format *fmt, const void
  * MIHEVC_ENODEV without a device */
 int mihevc_k_convert_rgb(int device, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2,
                          int width, int height, int pitch, int out_bit_depth, void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  The kernel of mihevc_send_frame_lut3d alone (the session's kernel), host buffers in and out: table as mihevc_set_lut3d takes it; sizes as
+ * mihevc_k_convert_source; out[c] are planes of the CODED size with out_stride[c] samples per row (>= the coded width of the plane), uint8_t when out_bit_depth
+ * == 8 and uint16_t when 10.  There is no session to follow: out_matrix must be 1 / 5 / 6 / 9, out_full_range 0 or 1.  Validated first (MIHEVC_EINVAL: what
+ * mihevc_send_frame_lut3d and mihevc_set_lut3d refuse, a NULL table or output, a short stride), then MIHEVC_ENODEV without a device */
+int mihevc_k_lut3d(int device, const mihevc_lut3d_src *src, int n, const uint16_t *table, const void *y, const void *u, const void *v,
+                   int pitch_y, int pitch_c, int width, int height, int out_bit_depth, int out_matrix, int out_full_range,
+                   void *const out[3], const int out_stride[3]);
 /* added under ABI 6.  The scaler of mihevc_send_frame_scaled alone (the session's kernel), host buffers in and out: src names the source planes y / u / v,
  * dst_width x dst_height is the display size of the output, out_* are planes of its CODED size as in mihevc_k_convert_source.  Validated first
  * (MIHEVC_EINVAL: what mihevc_send_frame_scaled refuses, an out_bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
