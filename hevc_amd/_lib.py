@@ -142,6 +142,29 @@ def denoise_strength(s) -> Denoise:
     return Denoise(*(int(v) for v in t))
 
 
+class Interpolate(C.Structure):
+    """mihevc_interpolate: factor (2, 3 or 4 pictures per frame), mode (0 motion compensated, 1 blend) and scene threshold (0 .. 255 in 8-bit units, 0 off) of the
+    frames handed to mihevc_send_frame_interpolate / mihevc_k_mcfi_render"""
+    _fields_ = [(n, C.c_int32) for n in ("factor", "mode", "scene_threshold")] + [("reserved", C.c_int32 * 5)]
+
+    def __repr__(self):
+        return f"Interpolate(factor={self.factor}, mode={self.mode}, scene_threshold={self.scene_threshold})"
+
+
+INTERP_MODES = {"mc": 0, "blend": 1}
+
+
+def interpolate_mode(factor, mode="mc", scene_threshold: int = 10) -> Interpolate:
+    """factor 2 .. 4, mode 'mc' or 'blend', scene_threshold 0 .. 255"""
+    if isinstance(factor, bool) or not isinstance(factor, int) or not 2 <= factor <= 4:
+        raise ValueError(f"interpolate factor {factor!r}: 2, 3 or 4")
+    if mode not in INTERP_MODES:
+        raise ValueError(f"interpolate mode {mode!r}: 'mc' or 'blend'")
+    if isinstance(scene_threshold, bool) or not isinstance(scene_threshold, int) or not 0 <= scene_threshold <= 255:
+        raise ValueError(f"scene_threshold {scene_threshold!r}: 0 .. 255")
+    return Interpolate(factor, INTERP_MODES[mode], scene_threshold)
+
+
 class Lut3dSrc(C.Structure):
     """mihevc_lut3d_src: depth, matrix and range of the planar 4:2:0 frames handed to mihevc_send_frame_lut3d / mihevc_k_lut3d"""
     _fields_ = [(n, C.c_int32) for n in ("bit_depth", "matrix", "full_range")] + [("reserved", C.c_int32 * 4)]
@@ -209,6 +232,7 @@ EXPORTS = (
     "mihevc_send_frame_scaled", "mihevc_k_scale_source", "mihevc_k_scene_diff", "mihevc_send_frame_deint", "mihevc_k_deinterlace",
     "mihevc_send_frame_denoise", "mihevc_k_denoise", "mihevc_send_frame_fieldmatch", "mihevc_get_fieldmatch_info", "mihevc_k_fieldmatch_metrics",
     "mihevc_k_fieldmatch_weave", "mihevc_set_lut3d", "mihevc_send_frame_lut3d", "mihevc_k_lut3d",
+    "mihevc_send_frame_interpolate", "mihevc_k_mcfi_vectors", "mihevc_k_mcfi_render",
 )
 
 _lib = None
@@ -291,6 +315,9 @@ def load() -> C.CDLL:
     lib.mihevc_set_lut3d.argtypes = [vp, i32, vp]
     lib.mihevc_send_frame_lut3d.argtypes = [vp, C.POINTER(Lut3dSrc), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_lut3d.argtypes = [i32, C.POINTER(Lut3dSrc), i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i32)]
+    lib.mihevc_send_frame_interpolate.argtypes = [vp, C.POINTER(Interpolate), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_mcfi_vectors.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_k_mcfi_render.argtypes = [i32, C.POINTER(Interpolate), i32, C.POINTER(vp), C.POINTER(vp), vp, C.c_uint64, i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -15,6 +15,7 @@
 #include "kernels/intra.h"
 #include "kernels/loopfilter.h"
 #include "kernels/lut3d.h"
+#include "kernels/mcfi.h"
 #include "kernels/pichash.h"
 #include "kernels/scale.h"
 #include "kernels/ssim.h"
@@ -89,6 +90,12 @@ hipError_t launch_denoise(hipStream_t st, const DenoiseArgs &a, bool is16);
 // to zero in front).  Weave: one launch writes the three coded-size planes of `a` (cur: the kept rows, prev: the others), margins included
 hipError_t launch_fm_metrics(hipStream_t st, const FmArgs &a, unsigned long long *out, bool is16);
 hipError_t launch_fm_weave(hipStream_t st, const DeintArgs &a, bool is16);
+// frame-rate multiplication (kernels/mcfi.h).  Vectors: k_mcfi_search over the block tiles of `a`, then k_mcfi_field (median, fallback, the fold of D) into
+// f.v and f.dsum (device memory; nothing to zero in front).  Render: one launch writes the three coded-size planes of `a`, margins included
+hipError_t launch_mcfi_search(hipStream_t st, const McfiSearchArgs &a, bool is16);
+hipError_t launch_mcfi_field(hipStream_t st, const McfiFieldArgs &f, bool is16);
+hipError_t launch_mcfi_vectors(hipStream_t st, const McfiSearchArgs &a, const McfiFieldArgs &f, bool is16);      // the two above, in this order
+hipError_t launch_mcfi_render(hipStream_t st, const McfiRenderArgs &a, bool is16);
 
 // rows between the slices of one picture (csrc/slice_group.h): jobs[i] for i < n_jobs, one grid row of `blocks_per_job` workgroups each
 hipError_t launch_copy_rows(hipStream_t st, const RowCopy *d_jobs, int n_jobs, int blocks_per_job);

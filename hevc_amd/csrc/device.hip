@@ -283,6 +283,54 @@ hipError_t launch_fm_weave(hipStream_t st, const DeintArgs &a, bool is16)
     return hipGetLastError();
 }
 
+// frame-rate multiplication (kernels/mcfi.h).  k_mcfi_search: one workgroup per tile of MC_SB x MC_SB blocks, 37,892 bytes of LDS: four workgroups per CU take
+// 148 KB of the CU's 160.  k_mcfi_field: sixteen blocks per workgroup and one more workgroup for the fold of D.  k_mcfi_render: one workgroup per tile of
+// MR_TW x MR_TH output samples, Y, then Cb, then Cr, 62,760 bytes of LDS: two workgroups per CU take 123 KB
+template <typename T> __global__ __launch_bounds__(NT, 4) void k_mcfi_search(const McfiSearchArgs a)
+{
+    __shared__ __align__(16) McfiSearchShared s;
+    GpuExec ex;
+    mcfi_search_program<T>(ex, s, a, (int)blockIdx.x);
+}
+template <typename T> __global__ __launch_bounds__(NT, 4) void k_mcfi_field(const McfiFieldArgs a)
+{
+    __shared__ __align__(16) McfiFieldShared s;
+    GpuExec ex;
+    mcfi_field_program<T>(ex, s, a, (int)blockIdx.x);
+}
+template <typename T> __global__ __launch_bounds__(NT, 2) void k_mcfi_render(const McfiRenderArgs a)
+{
+    __shared__ __align__(16) McfiRenderShared s;
+    GpuExec ex;
+    mcfi_render_program<T>(ex, s, a, (int)blockIdx.x);
+}
+hipError_t launch_mcfi_search(hipStream_t st, const McfiSearchArgs &a, bool is16)
+{
+    const dim3 grid((unsigned)mcfi_search_workgroups(a.w, a.h)), block(NT);
+    if (is16) hipLaunchKernelGGL((k_mcfi_search<uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_mcfi_search<uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_mcfi_field(hipStream_t st, const McfiFieldArgs &f, bool is16)
+{
+    const dim3 grid((unsigned)mcfi_field_workgroups(f.w, f.h)), block(NT);
+    if (is16) hipLaunchKernelGGL((k_mcfi_field<uint16_t>), grid, block, 0, st, f);
+    else hipLaunchKernelGGL((k_mcfi_field<uint8_t>), grid, block, 0, st, f);
+    return hipGetLastError();
+}
+hipError_t launch_mcfi_vectors(hipStream_t st, const McfiSearchArgs &a, const McfiFieldArgs &f, bool is16)
+{
+    const hipError_t e = launch_mcfi_search(st, a, is16);
+    return e != hipSuccess ? e : launch_mcfi_field(st, f, is16);
+}
+hipError_t launch_mcfi_render(hipStream_t st, const McfiRenderArgs &a, bool is16)
+{
+    const dim3 grid((unsigned)mcfi_render_workgroups(a.pw, a.ph)), block(NT);
+    if (is16) hipLaunchKernelGGL((k_mcfi_render<uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_mcfi_render<uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 // RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
 template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
 {
@@ -1211,6 +1259,48 @@ template <typename T> int stage_fm_weave(const void *const *cur, const void *con
     return dst.planes.download(out);
 }
 
+// the vector kernels of frame-rate multiplication alone
+template <typename T> int stage_mcfi_vectors(const void *cur, const void *next, int w, int h, int pitch, int depth, int16_t *v0, int16_t *v, uint64_t *scene_sum)
+{
+    DevBuf din[2], blk;
+    const void *d[2] = {cur, next};
+    for (int f = 0; f < 2; f++)
+        if (int e = upload_as_laid_out(din[f], d[f], w, h, pitch, sizeof(T))) return e;
+    const McfiLayout l = mcfi_layout(w, h);
+    CK(blk.alloc(l.bytes));
+    const McfiSearchArgs a = mcfi_search_args(depth, d[0], d[1], pitch, w, h, blk.as<uint8_t>());
+    CK(launch_mcfi_vectors(0, a, mcfi_field_args(a, blk.as<uint8_t>()), sizeof(T) == 2));
+    CK(hipDeviceSynchronize());
+    const size_t nb = (size_t)mcfi_blocks(w) * mcfi_blocks(h);
+    CK(hipMemcpy(v0, blk.as<uint8_t>() + l.v0, nb * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(v, blk.as<uint8_t>() + l.v, nb * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(scene_sum, blk.as<uint8_t>() + l.dsum, 8, hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+// the render kernel of frame-rate multiplication alone
+template <typename T>
+int stage_mcfi_render(const mihevc_interpolate &m, int j, const void *const *cur, const void *const *next, const int16_t *v, uint64_t scene_sum, int w, int h, int pitch_y,
+                      int pitch_c, int depth, void *const *out)
+{
+    DevBuf din[6], dv, dsum;
+    ConvertOut<T> dst;
+    if (int e = dst.alloc(w, h)) return e;
+    const void *d[2][3];
+    for (int f = 0; f < 2; f++)
+        for (int c = 0; c < 3; c++) {
+            d[f][c] = (f ? next : cur)[c];
+            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
+        }
+    if (v)
+        if (int e = to_device(dv, v, (size_t)mcfi_blocks(w) * mcfi_blocks(h) * 2)) return e;
+    const unsigned long long sum = scene_sum;
+    if (int e = to_device(dsum, &sum)) return e;
+    const McfiRenderArgs a = mcfi_render_args(m, j, depth, d[0], d[1], pitch_y, pitch_c, w, h, dst.w, dst.h, dv.as<int16_t>(), dsum.as<unsigned long long>(), dst.p, dst.stride);
+    CK(launch_mcfi_render(0, a, sizeof(T) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.planes.download(out);
+}
+
 int select_device(int device)
 {
     int n = 0;
@@ -1480,6 +1570,26 @@ int mihevc_k_fieldmatch_weave(int device, const void *const cur[3], const void *
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(bit_depth, [&](auto t) { return stage_fm_weave<decltype(t)>(cur, other, width, height, pitch_y, pitch_c, bit_depth, keep, out); });
+}
+
+int mihevc_k_mcfi_vectors(int device, const void *cur_y, const void *next_y, int width, int height, int pitch, int bit_depth, int16_t *v0, int16_t *v, uint64_t *scene_sum)
+{
+    if (!cur_y || !next_y || !v0 || !v || !scene_sum || !mcfi_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch < width) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return with_depth(bit_depth, [&](auto t) { return stage_mcfi_vectors<decltype(t)>(cur_y, next_y, width, height, pitch, bit_depth, v0, v, scene_sum); });
+}
+
+int mihevc_k_mcfi_render(int device, const mihevc_interpolate *d, int j, const void *const cur[3], const void *const next[3], const int16_t *v, uint64_t scene_sum,
+                         int width, int height, int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v)
+{
+    if (!mcfi_mode_ok(d) || j < 0 || j >= d->factor || !cur || !next || !out_y || !out_u || !out_v || (!v && d->mode == 0)) return MIHEVC_EINVAL;
+    for (int c = 0; c < 3; c++)
+        if (!cur[c] || !next[c]) return MIHEVC_EINVAL;
+    if (!mcfi_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
+    if (v && !mcfi_vectors_ok(v, (size_t)mcfi_blocks(width) * mcfi_blocks(height))) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(bit_depth, [&](auto t) { return stage_mcfi_render<decltype(t)>(*d, j, cur, next, v, scene_sum, width, height, pitch_y, pitch_c, bit_depth, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

@@ -125,11 +125,11 @@ struct mihevc_session {
     Event ev_lut[2];
     int lut_n = 0;
     int64_t lut_sets = 0;
-    // mihevc_send_frame_deint, mihevc_send_frame_denoise: a ring of three source-size pictures (display size, rows that begin 16-byte aligned), allocated at the
+    // mihevc_send_frame_deint, mihevc_send_frame_denoise, mihevc_send_frame_fieldmatch, mihevc_send_frame_interpolate: a ring of three source-size pictures (display size, rows that begin 16-byte aligned), allocated at the
     // first call; frame k lies in slot k % 3.  Copies and k_deint / k_denoise launches are neighbours on st_pre, so a slot is overwritten in stream order behind
     // the last launch that read it.  src_ring_kind: the entry that filled the ring first (a pending frame keeps every other entry out until flush, so it is the only
     // one); src_ring_n: frames taken; src_ring_pending: the last of them has not produced its picture(s) yet (the next frame or mihevc_flush does that)
-    enum { RING_NONE = 0, RING_DEINT, RING_DENOISE, RING_FIELDMATCH };
+    enum { RING_NONE = 0, RING_DEINT, RING_DENOISE, RING_FIELDMATCH, RING_MCFI };
     CachedBlock<uint8_t> src_ring[3];
     void *src_ring_p[3][3] = {};
     int src_ring_pitch[3] = {};
@@ -138,6 +138,10 @@ struct mihevc_session {
     bool src_ring_pending = false;
     int deint_tff = 0, deint_field_rate = 0;
     mihevc_denoise denoise_pending = {};      // the strengths of the pending frame
+    // mihevc_send_frame_interpolate: mcfi_pending: factor and mode of the session's first interpolated frame, the scene threshold of the pending
+    // one; mcfi_dev: vectors, SAD0(0), the parts of D and D (mcfi_layout), written and read in stream order on st_pre
+    mihevc_interpolate mcfi_pending = {};
+    CachedBlock<uint8_t> mcfi_dev;
     // mihevc_send_frame_fieldmatch: the frames go through the same ring.  fm_open: from the first fieldmatch frame until flush no other entry
     // sends a frame.  fm_dev: the partials of k_fm_metrics and the eight folded numbers behind them; fm_host: their pinned copy, valid behind ev_fm.  fm_frames:
     // what was decided, by frame (decided: mihevc_get_fieldmatch_info may hand it out; under `m`).  fm_held: decimate: the filled pictures of the open cycle with
@@ -1528,13 +1532,34 @@ static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const voi
 }
 
 // The picture(s) of frame k of the ring (mihevc_send_frame_deint, mihevc_send_frame_denoise): P = frame k - 1 (the first frame: itself), C = frame k, N = frame k + 1
-// (has_next; the last frame: itself).  k_deint / k_denoise write the session's own planes, margin included, out of the ring.  Deinterlacing: frame-rate mode
-// keeps the first field's rows, field-rate mode follows with the second field's picture at pts + 1.  Denoising: one picture, with the strengths frame k came with
+// (has_next; the last frame: itself).  k_deint / k_denoise / k_mcfi_render write the session's own planes, margin included, out of the ring.  Deinterlacing: frame-rate mode
+// keeps the first field's rows, field-rate mode follows with the second field's picture at pts + 1.  Denoising: one picture, with the strengths frame k came with.
+// Interpolation (mihevc_send_frame_interpolate): the vectors of the pair (C, N), then `factor` pictures at pts + j; the last frame: its own picture only
 static int ring_emit(mihevc_session *s, int64_t k, bool has_next, bool wait)
 {
     s->src_ring_pending = false;
     void *const *C = s->src_ring_p[k % 3], *const *P = s->src_ring_p[(k > 0 ? k - 1 : k) % 3], *const *N = s->src_ring_p[(has_next ? k + 1 : k) % 3];
     const bool denoise = s->src_ring_kind == mihevc_session::RING_DENOISE;
+    if (s->src_ring_kind == mihevc_session::RING_MCFI) {      // the pictures between C and N; the last frame: itself (picture 0 of a blend with any N)
+        mihevc_interpolate m = s->mcfi_pending;
+        if (!has_next) m.mode = 1;
+        const int W = s->cfg.width, H = s->cfg.height;
+        const McfiLayout l = mcfi_layout(W, H);
+        uint8_t *const blk = s->mcfi_dev.get();
+        if (m.mode == 0) {
+            const McfiSearchArgs a = mcfi_search_args(s->cfg.bit_depth, C[0], N[0], s->src_ring_pitch[0], W, H, blk);
+            HIPCK(s, launch_mcfi_vectors(s->st_pre, a, mcfi_field_args(a, blk), s->is16));
+        }
+        for (int j = 0; j < (has_next ? m.factor : 1); j++) {
+            mihevc_session::Src src;
+            if (int e = take_src(s, src)) return e;
+            const McfiRenderArgs a = mcfi_render_args(m, j, s->cfg.bit_depth, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], W, H, s->w, s->h, (const int16_t *)(blk + l.v),
+                                                      (const unsigned long long *)(blk + l.dsum), src.p, src.stride);
+            HIPCK(s, launch_mcfi_render(s->st_pre, a, s->is16));
+            if (int e = finish_ingest(s, std::move(src), s->src_ring_pts + j, wait)) return e;
+        }
+        return MIHEVC_OK;
+    }
     const int first = s->deint_tff ? 0 : 1;
     for (int f = 0; f <= (denoise ? 0 : s->deint_field_rate); f++) {
         mihevc_session::Src src;
@@ -1747,6 +1772,21 @@ int mihevc_send_frame_denoise(mihevc_session *s, const mihevc_denoise *d, const 
     if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_DENOISE)) return e;
     const int e = ingest_ring(s, mihevc_session::RING_DENOISE, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
     s->denoise_pending = *d;      // (the picture of the frame before has been launched with its own)
+    return e;
+}
+int mihevc_send_frame_interpolate(mihevc_session *s, const mihevc_interpolate *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const bool args_ok = s && mcfi_mode_ok(d) && y && u && v &&
+                         (s->src_ring_kind != mihevc_session::RING_MCFI || (d->factor == s->mcfi_pending.factor && d->mode == s->mcfi_pending.mode)) &&
+                         mcfi_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width && pitch_c >= s->cfg.width / 2;
+    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_MCFI)) return e;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    if (!s->mcfi_dev) {
+        HIPCK(s, s->mcfi_dev.alloc(s->device, (mcfi_layout(s->cfg.width, s->cfg.height).bytes + 255) & ~(size_t)255, false));
+        s->mcfi_pending = *d;
+    }
+    const int e = ingest_ring(s, mihevc_session::RING_MCFI, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+    s->mcfi_pending.scene_threshold = d->scene_threshold;      // (the pictures of the frame before have been launched with its own)
     return e;
 }
 int mihevc_send_frame_fieldmatch(mihevc_session *s, const mihevc_fieldmatch *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)

@@ -284,6 +284,27 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_denoise(self._s, C.byref(dn), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_denoise")
 
+    def send_interpolate(self, y, u, v, factor: int = 2, mode: str = 'mc', scene_threshold: int = 10, asynchronous: bool = False, pts: Optional[int] = None):
+        """mihevc_send_frame_interpolate: a progressive frame of the session's display size, planar 4:2:0 at the session's depth; between it and the next frame
+        factor - 1 pictures are interpolated on the device (DESIGN.md §6j).  factor: 2, 3 or 4 pictures per frame; mode: 'mc' (motion compensated) or 'blend';
+        both are those of the session's first call.  scene_threshold: 0 .. 255 in 8-bit units of mean absolute luma difference, 0 for no scene check; a pair of
+        frames above it repeats its nearer frame.  Frame k's pictures come out at pts, pts + 1, .. once the next frame has arrived, the last frame's own picture
+        with flush(): the caller numbers pts `factor` apart (the default does) and opens the session at factor times the source rate.  Width and height even and
+        at least 16.  Planes and asynchronous: the rules of send_denoise."""
+        c = self.cfg
+        m = _lib.interpolate_mode(factor, mode, scene_threshold)
+        planes = [y, u, v]
+        shapes = [(c.height, c.width)] + [(c.height // 2, c.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of the session")
+        es = 1 if c.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(m, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_interpolate")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + m.factor
+        self._check(self._lib.mihevc_send_frame_interpolate(self._s, C.byref(m), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_interpolate")
+
     def set_lut3d(self, table):
         """mihevc_set_lut3d: the 3D colour table send_lut3d interpolates in: an (n, n, n, 3) array indexed [b][g][r][c], the order of a .cube
         file, 2 <= n <= 65; uint16 entries 0 .. 65535, or floats in [0, 1] that go through lut3d.quantise first.  It is copied before the call returns and may be
@@ -736,7 +757,7 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
-                tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8) -> int:
+                tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc') -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -755,7 +776,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     'hdr-to-sdr' for the built-in table of lut3d.hdr_to_sdr (the transfer from the probe, PQ unless it says HLG; peak_nits from the probed master_display when
     there is one).  The session opens as SDR whatever the probe says of the source: 8 bit (lut_bit_depth=10: Main10), colour description 1/1/1, no HDR10 SEI, the
     level and tier of an SDR clip; the reader keeps delivering the source's own planar 4:2:0 frames at 8, 10 or 12 bit, and the source's matrix is the probed one
-    (BT.2020 for HDR, else BT.709 when unknown).  One device; not together with size=, native_rgb, deinterlace= or denoise=."""
+    (BT.2020 for HDR, else BT.709 when unknown).  One device; not together with size=, native_rgb, deinterlace= or denoise=.
+    interpolate: 2, 3 or 4: the frame rate is multiplied on the device (Encoder.send_interpolate), interp_mode 'mc' by motion-compensated
+    interpolation, 'blend' by blending; the session, its level, the rate figures and the MP4 track run at that multiple of the probed rate, n frames give
+    interpolate * (n - 1) + 1 pictures, and the progress total counts pictures.  None: nothing changes.  Planar 4:2:0 sources at the session's depth on one
+    device; not together with size=, native_rgb, deinterlace=, denoise= or lut=."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
@@ -772,6 +797,15 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     else:
         denoise = None
     clip_info = info        # what the clip is opened with: the source's own description, rate and frame count
+    if interpolate is not None:
+        if (isinstance(interpolate, bool) or not isinstance(interpolate, int) or interpolate not in (2, 3, 4) or interp_mode not in _lib.INTERP_MODES or denoise is not None
+                or lut is not None or deinterlace is not None or size is not None or native_rgb or (devices and len(devices) > 1)):
+            logger.error("%s: interpolate=%r takes 2, 3 or 4, interp_mode 'mc' or 'blend', one device, and none of size=, native_rgb, deinterlace=, denoise=, lut=",
+                         Path(file_path).name, interpolate)
+            return 1
+        info = copy.copy(info)      # the session, its level and the track run at the multiplied rate
+        info.fps = float(info.fps or 30.0) * interpolate
+        info.nb_frames = max((int(getattr(info, 'nb_frames', 0) or 0) - 1) * interpolate + 1, 0)
     lut_table = None        # the uint16 table once lut= is on
     if lut is not None:
         from . import lut3d
@@ -838,7 +872,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(info)
     level, tier = calculate_apple_hevc_level(info)
     sliced = bool(row_split and devices and len(devices) > 1)      # SlicedEncoder takes planar 4:2:0 only
-    clip = yuvio.open_any(Path(file_path), (clip_info if deint or ivtc or lut_table is not None else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
+    clip = yuvio.open_any(Path(file_path), (clip_info if deint or ivtc or lut_table is not None or interpolate is not None else info) if size is None else src_info, native_formats=not sliced, rgb_formats=native_rgb and not sliced)
     mux = None
     ok = False
     try:
@@ -877,7 +911,12 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if denoise is not None and (fmt is not None or cfg.width % 2 or cfg.height % 2 or min(cfg.width, cfg.height) < 16):
             logger.error("%s: denoise= takes a planar 4:2:0 source at the session's depth, width and height even (%r, %dx%d)", Path(file_path).name, fmt, cfg.width, cfg.height)
             return 1
+        if interpolate is not None and (fmt is not None or cfg.width % 2 or cfg.height % 2 or min(cfg.width, cfg.height) < 16):
+            logger.error("%s: interpolate= takes a planar 4:2:0 source at the session's depth, width and height even (%r, %dx%d)", Path(file_path).name, fmt, cfg.width, cfg.height)
+            return 1
         total = (clip.n_frames or total_frames) * (2 if deint and deint[1] else 1)
+        if interpolate is not None:
+            total = (total - 1) * interpolate + 1
         if ivtc and ivtc[1]:
             total = total * 4 // 5
         wants_audio = bool(info.audio_channels and info.audio_channels > 0) and Path(file_path).suffix.lower() not in ('.y4m', '.yuv')
@@ -929,6 +968,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                         enc.send_fieldmatch(*planes, tff=ivtc[0], decimate=ivtc[1], deint=True, pts=i)
                     elif denoise is not None:
                         enc.send_denoise(*planes, strength=denoise, pts=i)
+                    elif interpolate is not None:
+                        enc.send_interpolate(*planes, factor=interpolate, mode=interp_mode, pts=i * interpolate)
                     elif size is not None:
                         enc.send_scaled(src_size[0], src_size[1], *planes, bit_depth=src_depth, pts=i)
                     elif fmt is None:

@@ -377,6 +377,30 @@ typedef struct mihevc_fm_frame {
 /* What was decided for fieldmatch frame `frame` (0-based, in the order sent).  MIHEVC_EAGAIN until it is decided: the frame has arrived but the next one (or
  * flush) has not, or, with decimate, its cycle is still open; MIHEVC_EINVAL: NULL, or a frame that was never sent. */
 int  mihevc_get_fieldmatch_info(mihevc_session *s, int64_t frame, mihevc_fm_frame *out);
+/* ---- added under ABI 6: FRAME-RATE MULTIPLICATION (symbols only) ----
+ * Progressive frames of the session's DISPLAY size, planar 4:2:0 at cfg.bit_depth (uint8 at 8 bit, else little-endian uint16, values above 2^bit_depth - 1
+ * clamped), between which factor - 1 pictures are interpolated on the device with an exact integer definition (hevc_amd/csrc/kernels/mcfi.h
+ * states the arithmetic).  Mode mc: one bilateral vector per 8x8 luma block from a two-level block search (+-36 luma samples of motion per frame), smoothed by a
+ * 3x3 median, zeroed where it does not beat the zero vector; the pictures are rendered with overlapped blocks and bilinear fetches from both frames; a pair whose
+ * mean absolute luma difference exceeds scene_threshold (8-bit units; 0: no check) is a scene cut and repeats its nearer frame instead.  Mode blend: the weighted
+ * mean of the two frames.  Not covered: sub-sample vectors, wider ranges, occlusion reasoning, variable block sizes, arbitrary output rates and rate reduction,
+ * scaling, deinterlacing, denoising, inverse telecine, RGB or colour tables in the same session, sliced sessions, other layouts or depths than the session's. */
+typedef struct mihevc_interpolate {
+    int32_t factor;            /* 2, 3 or 4: pictures per frame */
+    int32_t mode;              /* 0: motion compensated, 1: blend */
+    int32_t scene_threshold;   /* 0 .. 255, 0: off (10 is a fair default) */
+    int32_t reserved[5];       /* 0 */
+} mihevc_interpolate;
+/* pitch_y, pitch_c: in elements.  The frame is copied into the ring of three source-size pictures that mihevc_send_frame_deint uses too; flags and ownership are
+ * those of mihevc_send_frame_deint.  When frame k + 1 arrives, frame k yields its `factor` pictures at pts_k + j, j = 0 .. factor - 1: the caller numbers pts in
+ * the session's time base with consecutive frames `factor` apart and opens the session at factor times the source rate.  mihevc_flush gives the last frame's
+ * j = 0 picture only: n frames give factor (n - 1) + 1 pictures.  The call never waits for the device on account of the scene check: the render kernel reads the
+ * sum itself.  mihevc_stats.frames_in counts pictures.  MIHEVC_EINVAL, decided before any device call and leaving the session usable: NULL d or plane, a factor
+ * outside 2 .. 4, a mode outside {0, 1}, a scene_threshold outside 0 .. 255, non-zero reserved, a factor or mode other than that of the session's first
+ * interpolated frame, cfg.width or cfg.height odd or below 16, a pitch smaller than the plane, unknown flag bits, slice_count > 1.  MIHEVC_ESTATE after flush,
+ * and while a frame of another ring entry is pending; every OTHER entry that sends a frame returns MIHEVC_ESTATE while an interpolated frame is pending. */
+int  mihevc_send_frame_interpolate(mihevc_session *s, const mihevc_interpolate *d, const void *y, const void *u, const void *v,
+                                   int pitch_y, int pitch_c, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -561,6 +585,18 @@ int mihevc_k_fieldmatch_metrics(int device, const void *prev_y, const void *cur_
  * the CODED size as in mihevc_k_convert_source.  Validated first (MIHEVC_EINVAL: as mihevc_k_deinterlace), then MIHEVC_ENODEV without a device */
 int mihevc_k_fieldmatch_weave(int device, const void *const cur[3], const void *const other[3], int width, int height, int pitch_y, int pitch_c, int bit_depth,
                               int keep, void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  The vector search of mihevc_send_frame_interpolate alone (k_mcfi_search and k_mcfi_field, the session's kernels), host buffers in and out:
+ * cur_y / next_y are the luma planes of frames k and k + 1, pitch in elements; v0 and v take ceil(height / 8) x ceil(width / 8) pairs (vx, vy): the field of the
+ * search and the final one; *scene_sum takes D.  Validated first (MIHEVC_EINVAL: NULL, width or height odd or below 16 or beyond the session limits, a pitch
+ * below width, a bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
+int mihevc_k_mcfi_vectors(int device, const void *cur_y, const void *next_y, int width, int height, int pitch, int bit_depth, int16_t *v0, int16_t *v,
+                          uint64_t *scene_sum);
+/* added under ABI 6.  Picture j of mihevc_send_frame_interpolate alone (k_mcfi_render, the session's kernel), host buffers in and out: cur / next name the Y, Cb
+ * and Cr planes of frames k and k + 1; v is a field as mihevc_k_mcfi_vectors gives it, but the CALLER's (not read under mode blend, where it may be NULL);
+ * scene_sum is D; out_* are planes of the CODED size as in mihevc_k_convert_source.  Validated first (MIHEVC_EINVAL: what mihevc_send_frame_interpolate
+ * refuses, j outside 0 .. factor - 1, a component of v outside [-18, 18], a bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
+int mihevc_k_mcfi_render(int device, const mihevc_interpolate *d, int j, const void *const cur[3], const void *const next[3], const int16_t *v, uint64_t scene_sum,
+                         int width, int height, int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
