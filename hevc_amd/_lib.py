@@ -173,6 +173,15 @@ class Lut3dSrc(C.Structure):
         return f"Lut3dSrc(bit_depth={self.bit_depth}, matrix={self.matrix}, full_range={self.full_range})"
 
 
+class UpscaleSrc(C.Structure):
+    """mihevc_upscale_src: size, depth, sharpening gain (sixteenths, 0 .. 64) and anti-ringing strength (eighths, 0 .. 8) of a planar 4:2:0 source handed to
+    mihevc_send_frame_upscaled / mihevc_k_upscale_source"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bit_depth", "sharpen", "antiring")] + [("reserved", C.c_int32 * 3)]
+
+    def __repr__(self):
+        return f"UpscaleSrc(width={self.width}, height={self.height}, bit_depth={self.bit_depth}, sharpen={self.sharpen}, antiring={self.antiring})"
+
+
 class RgbFormat(C.Structure):
     """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
     _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
@@ -233,6 +242,7 @@ EXPORTS = (
     "mihevc_send_frame_denoise", "mihevc_k_denoise", "mihevc_send_frame_fieldmatch", "mihevc_get_fieldmatch_info", "mihevc_k_fieldmatch_metrics",
     "mihevc_k_fieldmatch_weave", "mihevc_set_lut3d", "mihevc_send_frame_lut3d", "mihevc_k_lut3d",
     "mihevc_send_frame_interpolate", "mihevc_k_mcfi_vectors", "mihevc_k_mcfi_render",
+    "mihevc_send_frame_upscaled", "mihevc_k_upscale_source",
 )
 
 _lib = None
@@ -318,6 +328,8 @@ def load() -> C.CDLL:
     lib.mihevc_send_frame_interpolate.argtypes = [vp, C.POINTER(Interpolate), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_mcfi_vectors.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.mihevc_k_mcfi_render.argtypes = [i32, C.POINTER(Interpolate), i32, C.POINTER(vp), C.POINTER(vp), vp, C.c_uint64, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_send_frame_upscaled.argtypes = [vp, C.POINTER(UpscaleSrc), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_k_upscale_source.argtypes = [i32, C.POINTER(UpscaleSrc), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     _lib = lib
     return lib
 

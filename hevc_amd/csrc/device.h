@@ -19,6 +19,7 @@
 #include "kernels/pichash.h"
 #include "kernels/scale.h"
 #include "kernels/ssim.h"
+#include "kernels/upscale.h"
 
 namespace mihevc {
 
@@ -82,6 +83,8 @@ hipError_t launch_ingest_rgb(hipStream_t st, const IngestRgbArgs &a, int sample,
 hipError_t launch_lut3d(hipStream_t st, const Lut3dArgs &a, bool in16, bool out16);
 // downscaling source (kernels/scale.h): one launch writes the three coded-size planes of `a`, margins included, from a source of another size
 hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out16);
+// upscaling source (kernels/upscale.h): one launch writes the three coded-size planes of `a`, margins included, from a smaller source
+hipError_t launch_upscale(hipStream_t st, const UpscaleArgs &a, bool in16, bool out16);
 // deinterlacing source (kernels/deint.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth
 hipError_t launch_deint(hipStream_t st, const DeintArgs &a, bool is16);
 // denoising source (kernels/denoise.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth

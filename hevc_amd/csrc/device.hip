@@ -331,6 +331,24 @@ hipError_t launch_mcfi_render(hipStream_t st, const McfiRenderArgs &a, bool is16
     return hipGetLastError();
 }
 
+// upscaling source (kernels/upscale.h): one workgroup per tile of UP_TW x UP_TH output samples, Y, then Cb, then Cr; the argument block travels by value.
+// 15,984 bytes of LDS; the launch bounds ask for eight workgroups per CU (8 waves per SIMD, 64 VGPRs), which the registers allow
+template <typename TI, typename TO> __global__ __launch_bounds__(NT, 8) void k_upscale(const UpscaleArgs a)
+{
+    __shared__ __align__(16) UpscaleShared s;
+    GpuExec ex;
+    upscale_tile_program<TI, TO>(ex, s, a, (int)blockIdx.x);
+}
+hipError_t launch_upscale(hipStream_t st, const UpscaleArgs &a, bool in16, bool out16)
+{
+    const dim3 grid((unsigned)upscale_workgroups(a.pw, a.ph)), block(NT);
+    if (in16 && out16) hipLaunchKernelGGL((k_upscale<uint16_t, uint16_t>), grid, block, 0, st, a);
+    else if (in16) hipLaunchKernelGGL((k_upscale<uint16_t, uint8_t>), grid, block, 0, st, a);
+    else if (out16) hipLaunchKernelGGL((k_upscale<uint8_t, uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_upscale<uint8_t, uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
 // RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
 template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
 {
@@ -1186,6 +1204,33 @@ int stage_scale(const mihevc_scale_src &f, const void *const *src, int pitch_y, 
     return dst.planes.download(out);
 }
 
+// the upscaling kernel alone
+template <typename TO>
+int stage_upscale(const mihevc_upscale_src &f, const void *const *src, int pitch_y, int pitch_c, int dw, int dh, int out_depth, void *const *out)
+{
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    UpscaleBlock blk;
+    if (!upscale_block_build(f.width, f.height, dw, dh, UP_TH, UP_HALO, UP_ROWS, blk)) return MIHEVC_EINVAL;
+    DevBuf din[3], dtab;
+    ConvertOut<TO> dst;
+    if (int e = dst.alloc(dw, dh)) return e;
+    const void *dsrc[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < 3; c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? f.width / 2 : f.width, c ? f.height / 2 : f.height, c ? pitch_c : pitch_y, es)) return e;
+    CK(dtab.alloc(blk.bytes.size()));
+    CK(hipMemcpy(dtab.p, blk.bytes.data(), blk.bytes.size(), hipMemcpyHostToDevice));
+    const int32_t *first[4], *near[4];
+    const int16_t *coef[4];
+    for (int k = 0; k < 4; k++) {
+        first[k] = (const int32_t *)(dtab.as<uint8_t>() + blk.first[k]); near[k] = (const int32_t *)(dtab.as<uint8_t>() + blk.near[k]);
+        coef[k] = (const int16_t *)(dtab.as<uint8_t>() + blk.coef[k]);
+    }
+    const UpscaleArgs a = upscale_args(f, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, dw, dh, dst.w, dst.h, out_depth, dst.p, dst.stride, first, near, coef);
+    CK(launch_upscale(0, a, es == 2, sizeof(TO) == 2));
+    CK(hipDeviceSynchronize());
+    return dst.planes.download(out);
+}
+
 // the deinterlacing kernel alone
 template <typename T>
 int stage_deint(const void *const *prev, const void *const *cur, const void *const *next, int w, int h, int pitch_y, int pitch_c, int depth, int keep, int second,
@@ -1590,6 +1635,18 @@ int mihevc_k_mcfi_render(int device, const mihevc_interpolate *d, int j, const v
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(bit_depth, [&](auto t) { return stage_mcfi_render<decltype(t)>(*d, j, cur, next, v, scene_sum, width, height, pitch_y, pitch_c, bit_depth, out); });
+}
+
+int mihevc_k_upscale_source(int device, const mihevc_upscale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int dst_width, int dst_height,
+                            int out_bit_depth, void *out_y, void *out_u, void *out_v)
+{
+    if (!upscale_src_ok(src) || !y || !u || !v || !out_y || !out_u || !out_v || !convert_geometry_ok(dst_width, dst_height, out_bit_depth)) return MIHEVC_EINVAL;
+    if (!upscale_geometry_ok(src->width, src->height, dst_width, dst_height)) return MIHEVC_EINVAL;
+    if (pitch_y < src->width || pitch_c < src->width / 2) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *p[3] = {y, u, v};
+    void *out[3] = {out_y, out_u, out_v};
+    return with_depth(out_bit_depth, [&](auto t) { return stage_upscale<decltype(t)>(*src, p, pitch_y, pitch_c, dst_width, dst_height, out_bit_depth, out); });
 }
 
 #ifdef MIHEVC_PHASE_PROF

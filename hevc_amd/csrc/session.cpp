@@ -118,6 +118,10 @@ struct mihevc_session {
     CachedBlock<uint8_t> scale_tab;
     ScaleBlock scale_host;
     int scale_sw = 0, scale_sh = 0;
+    // mihevc_send_frame_upscaled: its own block of tables (scale_taps.h, upscale_block_build) of the last source size, kept as scale_tab is
+    CachedBlock<uint8_t> upscale_tab;
+    UpscaleBlock upscale_host;
+    int upscale_sw = 0, upscale_sh = 0;
     // mihevc_set_lut3d, mihevc_send_frame_lut3d: the packed table of lut_n points per axis (0: none) in one device block of the largest size,
     // so a new table of any size overwrites the old one in stream order on st_pre, behind every k_lut3d launch that reads it and in front of the next.  It is
     // copied from one of two pinned blocks, taken in turn; a block is written again only behind the event of the copy that read it, two tables back
@@ -1531,6 +1535,38 @@ static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const voi
     return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
+// A smaller source (mihevc_send_frame_upscaled; the arguments are checked): as ingest_scaled, with k_upscale and the session's own block of its tables
+static int ingest_upscaled(mihevc_session *s, const mihevc_upscale_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
+{
+    const int W = s->cfg.width, H = s->cfg.height;
+    const bool fresh = s->upscale_sw != f.width || s->upscale_sh != f.height;
+    UpscaleBlock blk;
+    if (fresh && !upscale_block_build(f.width, f.height, W, H, UP_TH, UP_HALO, UP_ROWS, blk)) return MIHEVC_EINVAL;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    if (fresh) {
+        s->upscale_sw = s->upscale_sh = 0;
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // a launch still reading the tables of the size before
+        HIPCK(s, s->upscale_tab.alloc(s->device, blk.bytes.size(), false));
+        s->upscale_host = std::move(blk);
+        HIPCK(s, hipMemcpyAsync(s->upscale_tab, s->upscale_host.bytes.data(), s->upscale_host.bytes.size(), hipMemcpyHostToDevice, s->st_pre));
+        s->upscale_sw = f.width; s->upscale_sh = f.height;
+    }
+    mihevc_session::Src src;
+    if (int e = take_src(s, src)) return e;
+    const size_t es = f.bit_depth > 8 ? 2 : 1;
+    SrcPlane pl[3] = {{y, f.width, f.height, pitch_y}, {u, f.width / 2, f.height / 2, pitch_c}, {v, f.width / 2, f.height / 2, pitch_c}};
+    if (int e = stage_planes(s, pl, 3, es, device_src)) return e;
+    const int32_t *first[4], *near[4];
+    const int16_t *coef[4];
+    for (int k = 0; k < 4; k++) {
+        first[k] = (const int32_t *)(s->upscale_tab + s->upscale_host.first[k]); near[k] = (const int32_t *)(s->upscale_tab + s->upscale_host.near[k]);
+        coef[k] = (const int16_t *)(s->upscale_tab + s->upscale_host.coef[k]);
+    }
+    const UpscaleArgs a = upscale_args(f, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride, first, near, coef);
+    HIPCK(s, launch_upscale(s->st_pre, a, es == 2, s->is16));
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
+}
+
 // The picture(s) of frame k of the ring (mihevc_send_frame_deint, mihevc_send_frame_denoise): P = frame k - 1 (the first frame: itself), C = frame k, N = frame k + 1
 // (has_next; the last frame: itself).  k_deint / k_denoise / k_mcfi_render write the session's own planes, margin included, out of the ring.  Deinterlacing: frame-rate mode
 // keeps the first field's rows, field-rate mode follows with the second field's picture at pts + 1.  Denoising: one picture, with the strengths frame k came with.
@@ -1756,6 +1792,13 @@ int mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, con
                          pitch_y >= src->width && pitch_c >= src->width / 2;
     if (int e = refuse_source(s, args_ok, flags)) return e;
     return ingest_scaled(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+}
+int mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const bool args_ok = s && upscale_src_ok(src) && y && u && v && upscale_geometry_ok(src->width, src->height, s->cfg.width, s->cfg.height) &&
+                         pitch_y >= src->width && pitch_c >= src->width / 2;
+    if (int e = refuse_source(s, args_ok, flags)) return e;
+    return ingest_upscaled(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
 }
 int mihevc_send_frame_deint(mihevc_session *s, const mihevc_deint *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {

@@ -335,6 +335,25 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_lut3d(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_lut3d")
 
+    def send_upscaled(self, width: int, height: int, y, u, v, bit_depth: Optional[int] = None, sharpen: int = 8, antiring: int = 8, pts: Optional[int] = None,
+                      asynchronous: bool = False):
+        """mihevc_send_frame_upscaled: a planar 4:2:0 picture of width x height samples (per axis between a quarter of the session's size and that size), enlarged
+        to the session's size on the device: Catmull-Rom interpolation, blended `antiring` eighths (0 .. 8) into the range of the two nearest
+        samples, then on luma a limited 3x3 sharpener of gain `sharpen` sixteenths (0 .. 64, 0: off); both may change from picture to picture.  bit_depth,
+        the planes and asynchronous: as send_scaled."""
+        src = _lib.UpscaleSrc(int(width), int(height), int(self.cfg.bit_depth if bit_depth is None else bit_depth), int(sharpen), int(antiring))
+        planes = [y, u, v]
+        shapes = [(src.height, src.width)] + [(src.height // 2, src.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {src!r}")
+        es = 1 if src.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(src, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_upscaled")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_upscaled(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_upscaled")
+
     def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
         Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
@@ -734,6 +753,16 @@ class SlicedEncoder:
             e.close()
 
 
+def upscale_target(w: int, h: int, target_height: int = 0) -> Tuple[int, int]:
+    """The size the reference's upscaling tool gives a w x h clip: target_height 0 picks 1080 lines below 1080, 2160 below 2160, else the source's own height; a
+    non-zero target_height is taken as given.  scale = target_height / h and width = int(w * scale), in its floating-point arithmetic, the width then lowered to
+    the next even number (4:2:0)."""
+    if target_height == 0:
+        target_height = 1080 if h < 1080 else 2160 if h < 2160 else h
+    scale = target_height / h
+    return int(w * scale) & ~1, int(target_height)
+
+
 def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) -> bool:
     """The native path writes video only; the reference always carries the source's audio as AAC (core/transcoder.py:423-450,480-489).
     When the source has audio (only container inputs can, and those need ffmpeg to be decoded at all) the video track is copied and the
@@ -757,7 +786,8 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
-                tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc') -> int:
+                tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc',
+                upscale=None, sharpen: int = 8, antiring: int = 8) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -780,7 +810,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     interpolate: 2, 3 or 4: the frame rate is multiplied on the device (Encoder.send_interpolate), interp_mode 'mc' by motion-compensated
     interpolation, 'blend' by blending; the session, its level, the rate figures and the MP4 track run at that multiple of the probed rate, n frames give
     interpolate * (n - 1) + 1 pictures, and the progress total counts pictures.  None: nothing changes.  Planar 4:2:0 sources at the session's depth on one
-    device; not together with size=, native_rgb, deinterlace=, denoise= or lut=."""
+    device; not together with size=, native_rgb, deinterlace=, denoise= or lut=.
+    upscale: (w, h), a target height, or 'auto' for upscale_target's rule: the session, its level and the MP4 track take that size and every picture of the
+    source, delivered at its own size, is enlarged on the device (Encoder.send_upscaled) with sharpen (0 .. 64 sixteenths) and antiring (0 .. 8
+    eighths).  None: nothing changes.  Planar 4:2:0 sources on one device, per axis between 1:1 and 1:4; not together with size=, native_rgb, deinterlace=,
+    denoise=, lut=, interpolate=, sliced sessions or several devices."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
@@ -796,6 +830,36 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             return 1
     else:
         denoise = None
+    if upscale is not None:
+        sw0, sh0 = int(info.width), int(info.height)
+        if (size is not None or native_rgb or deinterlace is not None or denoise is not None or lut is not None or interpolate is not None or (devices and len(devices) > 1)
+                or isinstance(sharpen, bool) or not isinstance(sharpen, int) or not 0 <= sharpen <= 64 or isinstance(antiring, bool) or not isinstance(antiring, int)
+                or not 0 <= antiring <= 8):
+            logger.error("%s: upscale=%r takes (w, h), a height or 'auto', sharpen 0 .. 64, antiring 0 .. 8, one device, and none of size=, native_rgb, deinterlace=, "
+                         "denoise=, lut=, interpolate=", Path(file_path).name, upscale)
+            return 1
+        try:
+            if isinstance(upscale, str):
+                if upscale != 'auto':
+                    raise ValueError(upscale)
+                target = upscale_target(sw0, sh0, 0)
+            elif isinstance(upscale, int) and not isinstance(upscale, bool):
+                if upscale < 1:
+                    raise ValueError(upscale)
+                target = upscale_target(sw0, sh0, upscale)
+            else:
+                target = (int(upscale[0]), int(upscale[1]))
+                if len(upscale) != 2:
+                    raise ValueError(upscale)
+        except (TypeError, ValueError, IndexError):
+            logger.error("%s: upscale=%r takes (w, h), a height or 'auto'", Path(file_path).name, upscale)
+            return 1
+        if (target[0] % 2 or target[1] % 2 or sw0 % 2 or sh0 % 2 or min(sw0, sh0) < 16 or not sw0 <= target[0] <= 4 * sw0 or not sh0 <= target[1] <= 4 * sh0):
+            logger.error("%s: upscale=%r: %dx%d to %dx%d is not an enlargement of even sizes by 1 .. 4 per axis", Path(file_path).name, upscale, sw0, sh0, target[0], target[1])
+            return 1
+        upscale, size = target, target      # from here on the road of size=: the session takes the target, the clip is opened at the source's own size
+    else:
+        upscale = None
     clip_info = info        # what the clip is opened with: the source's own description, rate and frame count
     if interpolate is not None:
         if (isinstance(interpolate, bool) or not isinstance(interpolate, int) or interpolate not in (2, 3, 4) or interp_mode not in _lib.INTERP_MODES or denoise is not None
@@ -897,7 +961,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if size is not None:
             fmt420 = fmt is None or (rgb is None and fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned)
             if not fmt420 or (devices and len(devices) > 1):
-                logger.error("%s: size= takes a planar 4:2:0 source on one device (%r)", Path(file_path).name, fmt)
+                logger.error("%s: %s takes a planar 4:2:0 source on one device (%r)", Path(file_path).name, "size=" if upscale is None else "upscale=", fmt)
                 return 1
             src_size = (int(clip.width), int(clip.height))
             src_depth = int(fmt.bit_depth) if fmt is not None else int(clip.bit_depth)
@@ -970,6 +1034,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                         enc.send_denoise(*planes, strength=denoise, pts=i)
                     elif interpolate is not None:
                         enc.send_interpolate(*planes, factor=interpolate, mode=interp_mode, pts=i * interpolate)
+                    elif upscale is not None:
+                        enc.send_upscaled(src_size[0], src_size[1], *planes, bit_depth=src_depth, sharpen=sharpen, antiring=antiring, pts=i)
                     elif size is not None:
                         enc.send_scaled(src_size[0], src_size[1], *planes, bit_depth=src_depth, pts=i)
                     elif fmt is None:

@@ -401,6 +401,31 @@ typedef struct mihevc_interpolate {
  * and while a frame of another ring entry is pending; every OTHER entry that sends a frame returns MIHEVC_ESTATE while an interpolated frame is pending. */
 int  mihevc_send_frame_interpolate(mihevc_session *s, const mihevc_interpolate *d, const void *y, const void *u, const void *v,
                                    int pitch_y, int pitch_c, int64_t pts, int flags);
+/* ---- added under ABI 6: sources SMALLER than the session (symbols only) ----
+ * A planar 4:2:0 picture of src->width x src->height samples at src->bit_depth, enlarged on the device into the session's planes of cfg.width x cfg.height at
+ * cfg.bit_depth, with an exact integer definition (hevc_amd/csrc/kernels/upscale.h and hevc_amd/csrc/scale_taps.h state the arithmetic): separable
+ * 4-tap Catmull-Rom interpolation at the positions of mihevc_send_frame_scaled (the cubic is not stretched), after each pass a blend of `antiring` eighths towards
+ * the range of the two samples around the position (8: the result never leaves it, so an edge grows no halo; 0: the plain cubic), then on luma a 3x3 sharpener of
+ * gain `sharpen` sixteenths (centre against a 1-2-1 blur) whose result is clamped to the range of its 3x3 neighbourhood, so it cannot overshoot (0: off).  Per
+ * axis source size <= cfg size <= 4 x source size, the axes independent; equal sizes with sharpen 0 give the conversion of mihevc_send_frame_fmt for a planar
+ * 4:2:0 source.  Elements are uint8 at 8 bit, else little-endian uint16, lsb aligned, values above 2^bit_depth - 1 clamped; chroma is sited as
+ * chroma_sample_loc_type 0 on both sides.  The constants (cubic, clamp to the two nearest samples, the blur, the gain scale) are a proposal and were not tuned.
+ * Not covered: learned super-resolution, edge-directed interpolation, ratios above 4, one axis enlarged and the other reduced, sources that are not planar
+ * 4:2:0, the other source filters in the same picture, sliced sessions, sample aspect ratio. */
+typedef struct mihevc_upscale_src {
+    int32_t width, height;   /* the source picture: both even, >= 16 */
+    int32_t bit_depth;       /* significant bits 8..16 */
+    int32_t sharpen;         /* 0..64, sixteenths (8 is a fair default) */
+    int32_t antiring;        /* 0..8, eighths (8 is a fair default) */
+    int32_t reserved[3];     /* 0 */
+} mihevc_upscale_src;
+/* pitch_y, pitch_c: in elements.  Flags, ownership, staging and stream ordering are those of mihevc_send_frame_scaled.  sharpen and antiring may change from
+ * frame to frame; the session keeps the tables of the last source size.  MIHEVC_EINVAL, decided before any device call and leaving the session usable: NULL src
+ * or plane, odd sizes or sizes below 16 (cfg.width / cfg.height included), a source larger than the session or smaller than a quarter of it on either axis,
+ * bit_depth outside 8..16, sharpen outside 0..64, antiring outside 0..8, non-zero reserved, a pitch smaller than the plane, unknown flag bits, slice_count > 1.
+ * MIHEVC_ESTATE after flush. */
+int  mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src, const void *y, const void *u, const void *v,
+                                int pitch_y, int pitch_c, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -597,6 +622,11 @@ int mihevc_k_mcfi_vectors(int device, const void *cur_y, const void *next_y, int
  * refuses, j outside 0 .. factor - 1, a component of v outside [-18, 18], a bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
 int mihevc_k_mcfi_render(int device, const mihevc_interpolate *d, int j, const void *const cur[3], const void *const next[3], const int16_t *v, uint64_t scene_sum,
                          int width, int height, int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  The upscaler of mihevc_send_frame_upscaled alone (k_upscale, the session's kernel), host buffers in and out: src names the source planes
+ * y / u / v, dst_width x dst_height is the display size of the output, out_* are planes of its CODED size as in mihevc_k_convert_source.  Validated first
+ * (MIHEVC_EINVAL: what mihevc_send_frame_upscaled refuses, an out_bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
+int mihevc_k_upscale_source(int device, const mihevc_upscale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
+                            int dst_width, int dst_height, int out_bit_depth, void *out_y, void *out_u, void *out_v);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
