@@ -20,8 +20,9 @@ __device__ __forceinline__ int xcd_remap(int b, int n)
     return (b & 7) * chunk + (b >> 3);
 }
 
-// list 1: the search of a B picture against the anchor after it (InterArgs::ref1 / centers1 / me1)
-template <typename T> __global__ __launch_bounds__(NT, 5) void k_me_search(const InterArgs<T> *args, int n_ctu, int list)
+// list 1: the search of a B picture against the anchor after it (InterArgs::ref1 / centers1 / me1).  RANGE: me_range as a compile-time constant
+// (15, the default of a session: launch_me_search picks it) or 0 for any range (me_search_program)
+template <typename T, int RANGE> __global__ __launch_bounds__(NT, 5) void k_me_search(const InterArgs<T> *args, int n_ctu, int list)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int ctu = xcd_remap(blockIdx.x, n_ctu);
@@ -31,8 +32,8 @@ template <typename T> __global__ __launch_bounds__(NT, 5) void k_me_search(const
     GpuExec ex;
     if (list) {
         const InterArgs<T> a = list1_view(args[blockIdx.y]);
-        me_search_program<T>(ex, s, win, a, ctu);
-    } else me_search_program<T>(ex, s, win, args[blockIdx.y], ctu);
+        me_search_program<T, RANGE>(ex, s, win, a, ctu);
+    } else me_search_program<T, RANGE>(ex, s, win, args[blockIdx.y], ctu);
 }
 
 // 5 workgroups per CU at 8 bit (89 VGPRs, no scratch; the windows overlay the residual area, inter_lds: 31,440 B of LDS at me_range 15), 3 at
@@ -593,10 +594,11 @@ template <typename K> static hipError_t ensure_smem(K kernel, size_t bytes)
 template <typename T> hipError_t launch_me_search(hipStream_t st, const InterArgs<T> *d_args, int n_ctu, int batch, int R, int list)
 {
     size_t smem = round16(sizeof(MeShared<T>)) + round16((size_t)me_win_elems(R));      // the window holds 8-bit samples for every T
-    hipError_t e = ensure_smem(k_me_search<T>, smem);
+    auto kernel = R == 15 ? k_me_search<T, 15> : k_me_search<T, 0>;
+    hipError_t e = ensure_smem(kernel, smem);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)(((n_ctu + 7) >> 3) << 3), (unsigned)batch);
-    hipLaunchKernelGGL(k_me_search<T>, grid, dim3(NT), smem, st, d_args, n_ctu, list);
+    hipLaunchKernelGGL(kernel, grid, dim3(NT), smem, st, d_args, n_ctu, list);
     return hipGetLastError();
 }
 

@@ -385,6 +385,30 @@ DEV int dot2_i16(uint32_t a, uint32_t b, int acc)
     return acc + (int)(int16_t)(a & 0xffff) * (int)(int16_t)(b & 0xffff) + (int)(int16_t)(a >> 16) * (int)(int16_t)(b >> 16);
 #endif
 }
+// The first dot of a chain, whose start value is a constant or shared with other chains.  The plain forms above select the two-address v_dot4c / v_dot2c
+// (vdst is the accumulator), so a chain's start value costs a v_mov_b32 into every accumulator first.  With the clamp bit the three-address v_dot4_i32_i8 /
+// v_dot2_i32_i16 is selected: the start value is an operand (an inline constant, or one register for every chain).  The clamp saturates at the ends of int32,
+// which no sum of these callers comes near (|sum| < 2^24), so the value is the plain form's.
+DEV int dot4_i8_start(uint32_t a, uint32_t b, int start)
+{
+#if MIHEVC_GPU
+    return __builtin_amdgcn_sdot4((int)a, (int)b, start, true);
+#else
+    return dot4_i8(a, b, start);
+#endif
+}
+DEV int dot2_i16_start(uint32_t a, uint32_t b, int start)
+{
+#if MIHEVC_GPU
+    typedef short v2s __attribute__((ext_vector_type(2)));
+    v2s va, vb;
+    __builtin_memcpy(&va, &a, 4);
+    __builtin_memcpy(&vb, &b, 4);
+    return __builtin_amdgcn_sdot2(va, vb, start, true);
+#else
+    return dot2_i16(a, b, start);
+#endif
+}
 
 // (lo & 0xffff) | (hi << 16): two 16-bit values into one dword (v_perm_b32)
 DEV uint32_t pack_lo16(int lo, int hi)

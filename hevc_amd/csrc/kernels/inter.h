@@ -220,11 +220,14 @@ HDI int me_win_stride(int R)
 HDI int me_win_elems(int R) { return (32 + 2 * R) * me_win_stride(R) + 16; }
 
 // SADs of the four 8x8 blocks of one block row (8 CTU rows x 32 samples) at the 4 horizontal positions of a quad.
-// src: CTU source rows (stride 32); ref: window at (row + dy, 4 * quad) — 4-byte aligned; out[block][position]
-DEV void quad_block_row(const uint8_t *src, const uint8_t *ref, int ws, unsigned (&out)[4][4])
+// src: CTU source rows (stride 32); ref: window at (row + dy, 4 * quad) — 4-byte aligned; out[block][position].
+// ROWS: rows per pass of the loop.  2 from a runtime ws.  4 where ws is a compile-time constant: the reads of four rows reach from one base register with
+// immediate offsets (255 dwords), two address instructions a pass, and the kernel stays clear of the 96-VGPR cap (77; two rows a pass, scheduled for
+// latency, took 96 and spilled at 16 bit)
+template <int ROWS> DEV void quad_block_row(const uint8_t *src, const uint8_t *ref, int ws, unsigned (&out)[4][4])
 {
     uint64_t acc[4] = {0, 0, 0, 0};
-#pragma unroll 2
+#pragma unroll(ROWS)
     for (int r = 0; r < 8; r++) {
         uint32_t rr[9], cc[8];
 #pragma unroll
@@ -259,15 +262,17 @@ DEV void copy_window_msb(uint8_t *lds, int ls, const uint8_t *plane, int pstride
     copy_window<uint8_t>(lds, ls, plane, pstride, ox, oy, w, h, lo_x, hi_x, lo_y, hi_y, tid);
 }
 
-template <typename T, class Ex>
+// RANGE: the search range as a compile-time constant (the caller vouches that a.prm.me_range has that value), or 0 for the range of the arguments.  With the
+// window's row stride known, the SAD rows' LDS addresses are immediates of the reads; from a runtime stride they were ten address instructions per two rows
+template <typename T, int RANGE = 0, class Ex>
 DEV void me_search_program(Ex &ex, MeShared<T> &s, uint8_t *win, const InterArgs<T> &a, int ctu)
 {
     const int msb = sizeof(T) == 1 ? 0 : a.prm.bit_depth - 8;       // bits dropped from every sample for the search
 
-    const int R = a.prm.me_range, spany = 2 * R + 1, spanx = me_spanx(R), quads = spanx >> 2, ws = me_win_stride(R), ww = me_win_w(R), wh = 32 + 2 * R;
+    const int R = RANGE ? RANGE : a.prm.me_range, spany = 2 * R + 1, spanx = me_spanx(R), quads = spanx >> 2, ws = me_win_stride(R), ww = me_win_w(R), wh = 32 + 2 * R;
     const int x0 = (ctu % a.ctus_w) * CTU, y0 = (ctu / a.ctus_w) * CTU;
     const int mct = a.prm.mc_top, mcb = a.prm.mc_bottom;
-    const int sx = a.centers ? a.centers[2 * ctu] : 0, sy0 = a.centers ? a.centers[2 * ctu + 1] : 0;
+    const int sx = wave_uniform(a.centers ? a.centers[2 * ctu] : 0), sy0 = wave_uniform(a.centers ? a.centers[2 * ctu + 1] : 0);
     const int sy = (mct || mcb) ? clamp_center_y(sy0, y0, R, a.h, mct, mcb) : sy0;
     ex.phase([&](int tid) {
         if (sizeof(T) == 1 && x0 + CTU <= a.w && y0 + CTU <= a.h) {      // whole 8-bit CTU: one dword per lane
@@ -354,7 +359,7 @@ DEV void me_search_program(Ex &ex, MeShared<T> &s, uint8_t *win, const InterArgs
                 for (int r2 = 0; r2 < 2; r2++) {
                     const int br = half * 2 + r2;
                     unsigned o[4][4];
-                    quad_block_row(srcp + br * 8 * 32, win + (br * 8 + dyi) * ws + 4 * q, ws, o);
+                    quad_block_row<(RANGE ? 4 : 2)>(srcp + br * 8 * 32, win + (br * 8 + dyi) * ws + 4 * q, ws, o);
 #pragma unroll
                     for (int b = 0; b < 4; b++) {
 #pragma unroll
@@ -412,8 +417,17 @@ constexpr int FRAC_PAIR_SUM = 8 * NT;
 constexpr int FRAC_SCRATCH = FRAC_PAIR_SUM + NT;
 static_assert(FRAC_SCRATCH <= (int)(sizeof(ResidualShared::scratch) / 4), "the fractional search's exchange must fit rs.scratch");
 // motion-compensation windows cover every vector the search can return: |mv| <= R + 3 (widened horizontal span)
-HDI int mc_win_y(int R) { return (32 + 2 * (R + 3) + 8 + 3) & ~3; }
-HDI int mc_win_y_stride(int R) { return mc_win_y(R) + 4; }
+HDI constexpr int mc_win_y(int R) { return (32 + 2 * (R + 3) + 8 + 3) & ~3; }
+HDI constexpr int mc_win_y_stride(int R) { return mc_win_y(R) + 4; }
+// the luma window's rows are a whole number of dwords apart at both sample sizes (4 samples: 4 or 8 bytes).  luma_half_diff relies on it: it splits a block's first
+// window element into an aligned dword and an offset inside it once, and that offset then holds for every row of the block
+HDI constexpr bool mc_win_y_rows_dword_aligned()
+{
+    for (int R = 0; R <= MAX_RANGE; R++)
+        if (mc_win_y_stride(R) % 4 != 0) return false;
+    return true;
+}
+static_assert(mc_win_y_rows_dword_aligned(), "mc_win_y_stride must be a multiple of 4 samples");
 HDI int mc_win_c(int R) { return (16 + (R + 3) + 8 + 3) & ~3; }
 HDI int mc_win_c_stride(int R) { return mc_win_c(R) + 4; }
 // a window's image in LDS (16 samples of slack: the aligned dword reads of a row's filter reach past its last sample)
@@ -482,29 +496,28 @@ template <typename T> DEV auto row_taps(int f)
     if constexpr (sizeof(T) == 1) return tap_bytes(f); else return tap_pairs(f);
 }
 
-// The horizontal 8-tap filter of one window row: the four 14-bit-domain values whose first tap sits on window element idx (3 left of the first
-// output's integer sample).  8 bit: 8 v_dot4_i32_i8 on byte-realigned dwords.  Samples are biased to signed bytes (p - 128); the taps of every fraction
-// sum to 64, so the bias comes back as the constant 128 * 64 (the fractional search was 72 % of k_inter_ctu, VALU bound on 8 multiply-adds per output:
-// profiles/r01 ablation).  The window image is 4-byte aligned and read with aligned dwords only.
-DEV void luma_row4(const uint8_t *win, int idx, const TapBytes &t, int, int (&hv)[4])
+// The horizontal 8-tap filter of one window row: four outputs whose first tap sits `off` samples behind the aligned dword p (3 left of the first output's
+// integer sample).  8 bit: 8 v_dot4_i32_i8 on byte-realigned dwords.  Samples are biased to signed bytes (p - 128) and the chain starts from 0, so the outputs
+// are hv' = sum of tap x (p - 128) = (the 14-bit-domain value) - LUMA_ROW_BIAS: the taps of every fraction sum to 64.  |hv'| <= 128 * 112, so it packs into
+// 16 bits for luma_col_pair like the value itself.  Every caller puts the bias back where it costs nothing (the start value of its vertical sums, or its rounding
+// constant); as the start of the chains here the literal was a v_mov_b32 into each of the four accumulators of every row (the fractional search was 72 % of
+// k_inter_ctu, VALU bound on 8 multiply-adds per output: profiles/r01 ablation).  The window image is 4-byte aligned and read with aligned dwords only.
+constexpr int LUMA_ROW_BIAS = 128 * 64;
+DEV void luma_row4_at(const uint8_t *p, int off, const TapBytes &t, int, int (&hv)[4])
 {
-    const int off = idx & 3;
-    const uint8_t *p = win + (idx - off);
     uint32_t d[4], q[3];
 #pragma unroll
     for (int k = 0; k < 4; k++) d[k] = load_u32_aligned(p + 4 * k);
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = align_bytes(d[k + 1], d[k], off) ^ 0x80808080u;      // bytes 4k..4k+3 of the row, signed
-    hv[0] = dot4_i8(q[0], t.lo, dot4_i8(q[1], t.hi, 128 * 64));
+    hv[0] = dot4_i8(q[0], t.lo, dot4_i8_start(q[1], t.hi, 0));
 #pragma unroll
-    for (int i = 1; i < 4; i++) hv[i] = dot4_i8(align_bytes(q[1], q[0], i), t.lo, dot4_i8(align_bytes(q[2], q[1], i), t.hi, 128 * 64));
+    for (int i = 1; i < 4; i++) hv[i] = dot4_i8(align_bytes(q[1], q[0], i), t.lo, dot4_i8_start(align_bytes(q[2], q[1], i), t.hi, 0));
 }
 // 16 bit (Main10): samples are already int16 pairs in the window's dwords, so an output is 4 v_dot2_i32_i16 (odd outputs on dwords realigned by one
-// sample), shifted down to 14 bits (shift1 = bit_depth - 8)
-DEV void luma_row4(const uint16_t *win, int idx, const TapPairs &t, int shift1, int (&hv)[4])
+// sample), shifted down to 14 bits (shift1 = bit_depth - 8); no bias
+DEV void luma_row4_at(const uint16_t *p, int off, const TapPairs &t, int shift1, int (&hv)[4])
 {
-    const int off = idx & 1;
-    const uint16_t *p = win + (idx - off);
     uint32_t d[7], e[6], o[5];
 #pragma unroll
     for (int k = 0; k < 7; k++) d[k] = load_u32_aligned(p + 2 * k);
@@ -514,12 +527,16 @@ DEV void luma_row4(const uint16_t *win, int idx, const TapPairs &t, int shift1, 
     for (int k = 0; k < 5; k++) o[k] = align_bytes(e[k + 1], e[k], 2);           // samples (2k+1, 2k+2)
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        int v = 0;
+        int v = dot2_i16_start((i & 1) ? o[i >> 1] : e[i >> 1], t.p[0], 0);
 #pragma unroll
-        for (int k = 0; k < 4; k++) v = dot2_i16((i & 1) ? o[(i >> 1) + k] : e[(i >> 1) + k], t.p[k], v);
+        for (int k = 1; k < 4; k++) v = dot2_i16((i & 1) ? o[(i >> 1) + k] : e[(i >> 1) + k], t.p[k], v);
         hv[i] = v >> shift1;
     }
 }
+// what the outputs of luma_row4_at lack of the 14-bit-domain value
+template <typename T> constexpr int luma_row_bias() { return sizeof(T) == 1 ? LUMA_ROW_BIAS : 0; }
+// A window element index split into its aligned dword (elements) and the offset inside it: 4 samples a dword at 8 bit, 2 at 16
+template <typename T> DEV int dword_offset(int idx) { return idx & (4 / (int)sizeof(T) - 1); }
 
 // The sample primitives of motion compensation: the 14-bit intermediate predictions (predSamplesLX, before the weighting of 8.5.3.3.4.2) of four
 // horizontally adjacent luma samples starting at window element i00 (8.5.3.3.3.1; the general 2-D form with the {0,0,0,64,0,0,0,0} tap set for a
@@ -528,11 +545,14 @@ template <typename T> DEV void luma_quad14(const T *win, int i00, int ws, int fx
 {
     const auto tx = row_taps<T>(fx);
     const int8_t *ty = g_tab.luma_tap[fy];
-    int acc[4] = {0, 0, 0, 0};
+    const int idx = i00 - 3 * ws - 3, off = dword_offset<T>(idx);
+    int acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[i] = 64 * luma_row_bias<T>();      // the vertical taps sum to 64 too
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         int hv[4];
-        luma_row4(win, i00 + (r - 3) * ws - 3, tx, bit_depth - 8, hv);
+        luma_row4_at(win + (idx - off) + r * ws, off, tx, bit_depth - 8, hv);
         const int t = ty[r];
 #pragma unroll
         for (int i = 0; i < 4; i++) acc[i] += t * hv[i];
@@ -560,7 +580,9 @@ DEV int weighted_bi(int p0, int p1, int bit_depth) { const int sh = 15 - bit_dep
 // state live, which spilled at 4 workgroups per CU, and leaves half of the workgroup idle).
 // The 8-tap column filter as 4 v_dot2_i32_i16 on row PAIRS of the horizontally filtered rows (|hv| < 2^15 for every fraction) instead of 8 quarter-rate
 // 32-bit multiplies: intermediate row r (reference row r - 3) and the one before it feed output row j with the taps (2k, 2k + 1) where r - 1 - j = 2k
-DEV void luma_col_pair(int r, const int (&hv)[4], int (&prev)[4], const TapPairs &ty, int (&acc)[8][4])
+// `start`: what every sum starts from (the caller's own register, one for all 32 sums).  Output row j meets its first pair at r = j + 1 (k = 0); that dot takes `start`
+// as its third operand and acc[j] needs no value before it (as zeroed accumulators each sum began with a register copy in front of its first v_dot2c)
+DEV void luma_col_pair(int r, const int (&hv)[4], int (&prev)[4], const TapPairs &ty, int start, int (&acc)[8][4])
 {
     if (r > 0) {
 #pragma unroll
@@ -569,7 +591,7 @@ DEV void luma_col_pair(int r, const int (&hv)[4], int (&prev)[4], const TapPairs
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int j = r - 1 - 2 * k;
-                if (j >= 0 && j < 8) acc[j][i] = dot2_i16(pr, ty.p[k], acc[j][i]);
+                if (j >= 0 && j < 8) acc[j][i] = k == 0 ? dot2_i16_start(pr, ty.p[0], start) : dot2_i16(pr, ty.p[k], acc[j][i]);
             }
         }
     }
@@ -578,7 +600,9 @@ DEV void luma_col_pair(int r, const int (&hv)[4], int (&prev)[4], const TapPairs
 }
 // Difference (source - quarter-sample prediction, 8.5.3.3.3.1: weighted_uni of what luma_quad14 gives there) of the 8 rows x 4 columns whose first integer
 // sample is window element i00.  The one-pass paths and the general path are branches of one function: as functions of their own, behind a dispatcher, they
-// cost k_inter_ctu_b a step of occupancy at both bit depths (profiles/r07_a)
+// cost k_inter_ctu_b a step of occupancy at both bit depths (profiles/r07_a).  ws: the window's row stride, a multiple of 4 samples (mc_win_y_rows_dword_aligned).
+// Each path splits the first window element it reads into an aligned dword and the offset inside it ONCE: rows are whole dwords apart, so every row of the block
+// is `row0 + r * ws` at the same offset, one address instruction a row (split row by row it was five)
 DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int, const uint8_t *src, int src_stride, int (&m)[8][4])
 {
     const TapBytes tx = tap_bytes(fx);
@@ -586,23 +610,26 @@ DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int
     // the same values come out of one filter pass.  Worth a branch only when the whole wave takes it (inter_ctu_program orders the ring so that a wave's two candidates
     // share their zero fraction: half of the first ring's waves, and the second ring's wherever the vectors stayed on whole samples).
     if (wave_all(fy == 0)) {          // horizontal filter only: rows 0 .. 7 of the block, no vertical pass
+        const int idx = i00 - 3, off = idx & 3;
+        const uint8_t *row0 = win + (idx - off);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             int hv[4];
-            luma_row4(win, i00 + j * ws - 3, tx, 0, hv);
+            luma_row4_at(row0 + j * ws, off, tx, 0, hv);
             const uint32_t w = load_u32_aligned(src + j * src_stride);
 #pragma unroll
-            for (int i = 0; i < 4; i++) m[j][i] = (int)((w >> (8 * i)) & 255) - clip3(0, 255, (hv[i] + 32) >> 6);      // ((64 hv >> 6) + 32) >> 6
+            for (int i = 0; i < 4; i++) m[j][i] = (int)((w >> (8 * i)) & 255) - clip3(0, 255, (hv[i] + (LUMA_ROW_BIAS + 32)) >> 6);      // ((64 hv >> 6) + 32) >> 6
         }
         return;
     }
     if (wave_all(fx == 0)) {          // vertical filter only: the block's own 4 columns of rows -3 .. 11, no horizontal pass
         const TapBytes ty = tap_bytes(fy);
         const int idx = i00 - 3 * ws, off = idx & 3;
+        const uint8_t *row0 = win + (idx - off);
         uint32_t rows[15];           // four samples of every row, as signed bytes
 #pragma unroll
         for (int r = 0; r < 15; r++) {
-            const uint8_t *p = win + (idx - off) + r * ws;
+            const uint8_t *p = row0 + r * ws;
             rows[r] = align_bytes(load_u32_aligned(p + 4), load_u32_aligned(p), off) ^ 0x80808080u;
         }
         uint32_t col[4][4];          // [rows 4g .. 4g + 3][column]: the rows' bytes transposed (row 15 does not exist: zero)
@@ -618,23 +645,22 @@ DEV void luma_half_diff(const uint8_t *win, int i00, int ws, int fx, int fy, int
 #pragma unroll
             for (int i = 0; i < 4; i++) {       // output row j of column i: rows j .. j + 7 against the taps
                 const uint32_t lo = align_bytes(col[g + 1][i], col[g][i], sh), hi = align_bytes(col[g + 2][i], col[g + 1][i], sh);
-                const int v = dot4_i8(lo, ty.lo, dot4_i8(hi, ty.hi, 128 * 64));      // sum of tap x sample: what (64 x sample, filtered) >> 6 is
-                m[j][i] = (int)((w >> (8 * i)) & 255) - clip3(0, 255, (v + 32) >> 6);
+                const int v = dot4_i8(lo, ty.lo, dot4_i8_start(hi, ty.hi, 0));      // sum of tap x (sample - 128): what (64 x sample, filtered) >> 6 is, less the bias
+                m[j][i] = (int)((w >> (8 * i)) & 255) - clip3(0, 255, (v + (LUMA_ROW_BIAS + 32)) >> 6);
             }
         }
         return;
     }
     const TapPairs ty = tap_pairs(fy);
+    const int idx = i00 - 3 * ws - 3, off = idx & 3;
+    const uint8_t *row0 = win + (idx - off);
+    const int start = 64 * LUMA_ROW_BIAS;       // sum of ty x (hv' + bias) = sum of ty x hv' + 64 x bias: the rows' bias, once per vertical sum
     int acc[8][4], prev[4];
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc[j][i] = 0;
 #pragma unroll
     for (int r = 0; r < 15; r++) {
         int hv[4];
-        luma_row4(win, i00 + (r - 3) * ws - 3, tx, 0, hv);
-        luma_col_pair(r, hv, prev, ty, acc);
+        luma_row4_at(row0 + r * ws, off, tx, 0, hv);
+        luma_col_pair(r, hv, prev, ty, start, acc);
     }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -649,29 +675,29 @@ DEV void luma_half_diff(const uint16_t *win, int i00, int ws, int fx, int fy, in
     const int shift1 = bit_depth - 8, shift3 = 14 - bit_depth, maxv = (1 << bit_depth) - 1, off3 = 1 << (shift3 - 1);
     // a zero fraction makes that direction's filter the identity (see the 8-bit form): one pass gives the same values; taken when the whole wave has it
     if (wave_all(fy == 0)) {          // horizontal only: the block's own 8 rows; 64 hv >> 6 = hv
+        const int idx = i00 - 3, off = idx & 1;
+        const uint16_t *row0 = win + (idx - off);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             int hv[4];
-            luma_row4(win, i00 + j * ws - 3, tx, shift1, hv);
+            luma_row4_at(row0 + j * ws, off, tx, shift1, hv);
 #pragma unroll
             for (int i = 0; i < 4; i++) m[j][i] = (int)src[j * src_stride + i] - clip3(0, maxv, (hv[i] + off3) >> shift3);
         }
         return;
     }
     const bool v_only = wave_all(fx == 0);      // vertical only: the horizontal pass of a whole-sample column is the sample x 64 >> shift1
+    const int idx = i00 - 3 * ws - 3, off = idx & 1;
+    const uint16_t *row0 = win + (idx - off);
     int acc[8][4], prev[4];
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc[j][i] = 0;
 #pragma unroll
     for (int r = 0; r < 15; r++) {
         int hv[4];
         if (v_only) {
 #pragma unroll
             for (int i = 0; i < 4; i++) hv[i] = (int)win[i00 + (r - 3) * ws + i] << (6 - shift1);
-        } else luma_row4(win, i00 + (r - 3) * ws - 3, tx, shift1, hv);
-        luma_col_pair(r, hv, prev, ty, acc);
+        } else luma_row4_at(row0 + r * ws, off, tx, shift1, hv);
+        luma_col_pair(r, hv, prev, ty, 0, acc);
     }
 #pragma unroll
     for (int j = 0; j < 8; j++)
