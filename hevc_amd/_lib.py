@@ -182,6 +182,20 @@ class UpscaleSrc(C.Structure):
         return f"UpscaleSrc(width={self.width}, height={self.height}, bit_depth={self.bit_depth}, sharpen={self.sharpen}, antiring={self.antiring})"
 
 
+class SrModel(C.Structure):
+    """mihevc_sr_model: scale (4 or 2) and number of RRDBs of the RRDBNet whose flat weights go with it (hevc_amd.sr.load_rrdbnet)"""
+    _fields_ = [("scale", C.c_int32), ("blocks", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+    def __repr__(self):
+        return f"SrModel(scale={self.scale}, blocks={self.blocks})"
+
+
+class SrConvDesc(C.Structure):
+    """mihevc_sr_conv_desc: one launch of k_sr_conv as mihevc_k_sr_conv takes it"""
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "up", "planar", "act", "n_res", "in_ch", "in_off", "cin", "cin_real", "out_ch", "out_off", "cout",
+                                          "r1_ch", "r1_off", "r2_ch", "r2_off")] + [(n, C.c_float) for n in ("slope", "a1", "a2")])
+
+
 class RgbFormat(C.Structure):
     """mihevc_rgb_format: the sample layout of an RGB source handed to mihevc_send_frame_rgb / mihevc_k_convert_rgb"""
     _fields_ = [(n, C.c_int32) for n in ("layout", "r", "g", "b", "sample", "bit_depth", "matrix", "range")] + [("reserved", C.c_int32 * 4)]
@@ -243,6 +257,7 @@ EXPORTS = (
     "mihevc_k_fieldmatch_weave", "mihevc_set_lut3d", "mihevc_send_frame_lut3d", "mihevc_k_lut3d",
     "mihevc_send_frame_interpolate", "mihevc_k_mcfi_vectors", "mihevc_k_mcfi_render",
     "mihevc_send_frame_upscaled", "mihevc_k_upscale_source",
+    "mihevc_set_sr_model", "mihevc_send_frame_sr", "mihevc_k_sr_conv", "mihevc_k_sr_input", "mihevc_k_sr_network",
 )
 
 _lib = None
@@ -330,6 +345,11 @@ def load() -> C.CDLL:
     lib.mihevc_k_mcfi_render.argtypes = [i32, C.POINTER(Interpolate), i32, C.POINTER(vp), C.POINTER(vp), vp, C.c_uint64, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.mihevc_send_frame_upscaled.argtypes = [vp, C.POINTER(UpscaleSrc), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_k_upscale_source.argtypes = [i32, C.POINTER(UpscaleSrc), vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.mihevc_set_sr_model.argtypes = [vp, C.POINTER(SrModel), vp, C.c_size_t]
+    lib.mihevc_send_frame_sr.argtypes = [vp, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, i64, i32]
+    lib.mihevc_k_sr_conv.argtypes = [i32, C.POINTER(SrConvDesc), vp, vp, vp, vp, vp, vp]
+    lib.mihevc_k_sr_input.argtypes = [i32, C.POINTER(RgbFormat), i32, i32, i32, vp, vp, vp, i32, vp]
+    lib.mihevc_k_sr_network.argtypes = [i32, C.POINTER(SrModel), vp, C.c_size_t, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, vp]
     _lib = lib
     return lib
 

@@ -20,6 +20,7 @@
 #include "kernels/scale.h"
 #include "kernels/ssim.h"
 #include "kernels/upscale.h"
+#include "sr_net.h"
 
 namespace mihevc {
 
@@ -85,6 +86,13 @@ hipError_t launch_lut3d(hipStream_t st, const Lut3dArgs &a, bool in16, bool out1
 hipError_t launch_scale(hipStream_t st, const ScaleArgs &a, bool in16, bool out16);
 // upscaling source (kernels/upscale.h): one launch writes the three coded-size planes of `a`, margins included, from a smaller source
 hipError_t launch_upscale(hipStream_t st, const UpscaleArgs &a, bool in16, bool out16);
+// learned super-resolution (kernels/sr_conv.h).  One convolution: cin, cout as padded (cin a multiple of 32 up to 192; cout 32 or 64, planar: 16); a shape
+// the network has no instance for is hipErrorInvalidValue, never another path
+hipError_t launch_sr_conv(hipStream_t st, const SrConvArgs &a, int cin, int cout, bool planar);
+// the source -> the input tensor.  sample: mihevc_rgb_format::sample; elem_size: bytes of a source element
+hipError_t launch_sr_input(hipStream_t st, const SrInputArgs &a, int sample, int elem_size);
+// every launch of `net` (sr_net.h) over an arena and packed weights in device memory; the input tensor of tw x th pixels is in the arena's X
+hipError_t launch_sr_network(hipStream_t st, const SrNet &net, uint8_t *arena, const uint16_t *wpk, const float *bias, int tw, int th);
 // deinterlacing source (kernels/deint.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth
 hipError_t launch_deint(hipStream_t st, const DeintArgs &a, bool is16);
 // denoising source (kernels/denoise.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth

@@ -350,6 +350,54 @@ hipError_t launch_upscale(hipStream_t st, const UpscaleArgs &a, bool in16, bool 
     return hipGetLastError();
 }
 
+// learned super-resolution (kernels/sr_conv.h): one workgroup per tile of SR_TW x SR_TH output pixels, every output channel of the layer.  Two workgroups per
+// CU: the input tile of 192 channels takes 72,000 bytes of LDS
+template <int CIN, int NB, bool PLANAR> __global__ __launch_bounds__(NT, SR_PER_CU) void k_sr_conv(const SrConvArgs a)
+{
+    __shared__ __align__(16) SrShared<CIN> s;
+    GpuExec ex;
+    sr_conv_program<CIN, NB, PLANAR>(ex, s, a, (int)blockIdx.x);
+}
+template <typename TI, bool FLT> __global__ __launch_bounds__(NT) void k_sr_input(const SrInputArgs a)
+{
+    GpuExec ex;
+    sr_input_program<TI, FLT>(ex, a, (int)blockIdx.x);
+}
+hipError_t launch_sr_conv(hipStream_t st, const SrConvArgs &a, int cin, int cout, bool planar)
+{
+    const dim3 grid((unsigned)sr_conv_workgroups(a.w, a.h)), block(NT);
+    if (planar && cin == 64 && cout == 16) hipLaunchKernelGGL((k_sr_conv<64, 1, true>), grid, block, 0, st, a);
+    else if (planar) return hipErrorInvalidValue;
+    else if (cin == 32 && cout == 64) hipLaunchKernelGGL((k_sr_conv<32, 4, false>), grid, block, 0, st, a);
+    else if (cin == 64 && cout == 64) hipLaunchKernelGGL((k_sr_conv<64, 4, false>), grid, block, 0, st, a);
+    else if (cin == 192 && cout == 64) hipLaunchKernelGGL((k_sr_conv<192, 4, false>), grid, block, 0, st, a);
+    else if (cin == 64 && cout == 32) hipLaunchKernelGGL((k_sr_conv<64, 2, false>), grid, block, 0, st, a);
+    else if (cin == 96 && cout == 32) hipLaunchKernelGGL((k_sr_conv<96, 2, false>), grid, block, 0, st, a);
+    else if (cin == 128 && cout == 32) hipLaunchKernelGGL((k_sr_conv<128, 2, false>), grid, block, 0, st, a);
+    else if (cin == 160 && cout == 32) hipLaunchKernelGGL((k_sr_conv<160, 2, false>), grid, block, 0, st, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_sr_input(hipStream_t st, const SrInputArgs &a, int sample, int elem_size)
+{
+    const int f = a.unshuffle ? 2 : 1;
+    const dim3 grid((unsigned)sr_input_workgroups(a.sw / f, a.sh / f)), block(NT);
+    if (sample == 2) hipLaunchKernelGGL((k_sr_input<uint32_t, true>), grid, block, 0, st, a);
+    else if (sample == 1) hipLaunchKernelGGL((k_sr_input<uint16_t, true>), grid, block, 0, st, a);
+    else if (elem_size == 2) hipLaunchKernelGGL((k_sr_input<uint16_t, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_sr_input<uint8_t, false>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_sr_network(hipStream_t st, const SrNet &net, uint8_t *arena, const uint16_t *wpk, const float *bias, int tw, int th)
+{
+    hipError_t err = hipSuccess;
+    sr_for_each_launch(net, arena, wpk, bias, tw, th, [&](int cin, int cout, bool planar, const SrConvArgs &a) {
+        err = launch_sr_conv(st, a, cin, cout, planar);
+        return err != hipSuccess;
+    });
+    return err;
+}
+
 // RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
 template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
 {
@@ -1233,6 +1281,55 @@ int stage_upscale(const mihevc_upscale_src &f, const void *const *src, int pitch
     return dst.planes.download(out);
 }
 
+// one convolution alone
+int stage_sr_conv(const mihevc_sr_conv_desc &d, const uint16_t *in, const float *weights, const float *bias, const uint16_t *r1, const uint16_t *r2, uint16_t *out)
+{
+    const int cout_pad = d.planar ? SR_M : d.cout, sw = d.up ? (d.width + 1) / 2 : d.width, sh = d.up ? (d.height + 1) / 2 : d.height;
+    const size_t px = (size_t)d.width * d.height, out_n = px * (d.planar ? 3 : d.out_ch);
+    std::vector<uint16_t> wpk(sr_packed_halves(cout_pad, d.cin));
+    std::vector<float> b((size_t)cout_pad, 0.0f);
+    sr_pack_layer(weights, d.cout, d.cin_real, cout_pad, d.cin, wpk.data());
+    for (int c = 0; c < d.cout; c++) b[(size_t)c] = bias[c];
+    DevBuf din, dw, db, dr1, dr2, dout;
+    if (int e = to_device(din, in, (size_t)sw * sh * d.in_ch)) return e;
+    if (int e = to_device(dw, wpk.data(), wpk.size())) return e;
+    if (int e = to_device(db, b.data(), b.size())) return e;
+    if (d.n_res >= 1) if (int e = to_device(dr1, r1, px * d.r1_ch)) return e;
+    if (d.n_res >= 2) if (int e = to_device(dr2, r2, px * d.r2_ch)) return e;
+    if (int e = to_device(dout, out, out_n)) return e;
+    SrConvArgs a;
+    a.in = din.as<const uint16_t>(); a.out = dout.as<uint16_t>(); a.wpk = dw.as<const uint16_t>(); a.bias = db.as<const float>();
+    a.r1 = dr1.as<const uint16_t>(); a.r2 = dr2.as<const uint16_t>();
+    a.in_ch = d.in_ch; a.in_off = d.in_off; a.out_ch = d.out_ch; a.out_off = d.out_off; a.r1_ch = d.r1_ch; a.r1_off = d.r1_off; a.r2_ch = d.r2_ch; a.r2_off = d.r2_off;
+    a.w = d.width; a.h = d.height; a.up = d.up; a.act = d.act; a.n_res = d.n_res; a.slope = d.slope; a.a1 = d.a1; a.a2 = d.a2;
+    CK(launch_sr_conv(0, a, d.cin, cout_pad, d.planar != 0));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, out_n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+// the input kernel, and with a network everything behind it
+int stage_sr(const mihevc_rgb_format &f, int scale, const SrNet *net, int sw, int sh, const void *const *src, int pitch, uint16_t *out)
+{
+    const int fct = scale == 2 ? 2 : 1, tw = sw / fct, th = sh / fct;
+    DevBuf din[3], arena, dw, db;
+    const void *dsrc[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < rgb_planes(f); c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], rgb_row_elems(f, sw), sh, pitch, (size_t)rgb_elem_size(f))) return e;
+    size_t off[SR_BUFS];
+    const size_t total = sr_arena_layout(tw, th, off), bytes = net ? total : off[SR_X + 1];
+    if (arena.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
+    CK(launch_sr_input(0, sr_input_args(f, scale, sw, sh, dsrc, pitch, (uint16_t *)(arena.as<uint8_t>() + off[SR_X])), f.sample, rgb_elem_size(f)));
+    if (net) {
+        if (int e = to_device(dw, net->wpk.data(), net->wpk.size())) return e;
+        if (int e = to_device(db, net->bias.data(), net->bias.size())) return e;
+        CK(launch_sr_network(0, *net, arena.as<uint8_t>(), dw.as<const uint16_t>(), db.as<const float>(), tw, th));
+    }
+    CK(hipDeviceSynchronize());
+    if (net) CK(hipMemcpy(out, arena.as<uint8_t>() + off[SR_OUT], (size_t)tw * th * 16 * 3 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    else CK(hipMemcpy(out, arena.as<uint8_t>() + off[SR_X], (size_t)tw * th * SR_CIN0 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+
 // the deinterlacing kernel alone
 template <typename T>
 int stage_deint(const void *const *prev, const void *const *cur, const void *const *next, int w, int h, int pitch_y, int pitch_c, int depth, int keep, int second,
@@ -1649,6 +1746,50 @@ int mihevc_k_upscale_source(int device, const mihevc_upscale_src *src, const voi
     const void *p[3] = {y, u, v};
     void *out[3] = {out_y, out_u, out_v};
     return with_depth(out_bit_depth, [&](auto t) { return stage_upscale<decltype(t)>(*src, p, pitch_y, pitch_c, dst_width, dst_height, out_bit_depth, out); });
+}
+
+// what a single k_sr_conv launch can be
+static bool sr_conv_desc_ok(const mihevc_sr_conv_desc *d)
+{
+    if (!d || d->width < 1 || d->height < 1 || d->width > 32768 || d->height > 32768 || (d->up | d->planar | d->act) & ~1 || d->n_res < 0 || d->n_res > 2) return false;
+    if (d->planar && d->n_res) return false;      // (the planar instance's 64 lanes would read 16 residual channels; the network's last layer has none)
+    if (d->cin < SR_K || d->cin > SR_MAX_CIN || d->cin % SR_K || d->cin_real < 1 || d->cin_real > d->cin) return false;
+    if (d->in_ch % 8 || d->in_off % 8 || d->in_off < 0 || d->in_off + d->cin > d->in_ch) return false;
+    if (d->planar ? d->cout != 3 || d->cin != 64 : (d->cout != 32 && d->cout != 64) || d->out_ch % 8 || d->out_off % 8 || d->out_off < 0 || d->out_off + d->cout > d->out_ch) return false;
+    if (!d->planar && !((d->cout == 64 && (d->cin == 32 || d->cin == 64 || d->cin == 192)) || (d->cout == 32 && d->cin >= 64 && d->cin <= 160))) return false;
+    const int c = d->planar ? 8 : d->cout;
+    if (d->n_res >= 1 && (d->r1_ch % 8 || d->r1_off % 8 || d->r1_off < 0 || d->r1_off + c > d->r1_ch)) return false;
+    if (d->n_res >= 2 && (d->r2_ch % 8 || d->r2_off % 8 || d->r2_off < 0 || d->r2_off + c > d->r2_ch)) return false;
+    return true;
+}
+int mihevc_k_sr_conv(int device, const mihevc_sr_conv_desc *d, const uint16_t *in, const float *weights, const float *bias, const uint16_t *r1, const uint16_t *r2,
+                     uint16_t *out)
+{
+    if (!sr_conv_desc_ok(d) || !in || !weights || !bias || !out || (d->n_res >= 1 && !r1) || (d->n_res >= 2 && !r2)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return stage_sr_conv(*d, in, weights, bias, r1, r2, out);
+}
+
+int mihevc_k_sr_input(int device, const mihevc_rgb_format *fmt, int scale, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch,
+                      uint16_t *out)
+{
+    const void *src[3] = {p0, p1, p2};
+    if (!rgb_format_ok(fmt) || (scale != 2 && scale != 4) || !sr_geometry_ok(scale, src_width, src_height) || !out || !rgb_planes_ok(*fmt, src, pitch, src_width))
+        return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return stage_sr(*fmt, scale, nullptr, src_width, src_height, src, pitch, out);
+}
+
+int mihevc_k_sr_network(int device, const mihevc_sr_model *model, const float *weights, size_t count, const mihevc_rgb_format *fmt, int src_width, int src_height,
+                        const void *p0, const void *p1, const void *p2, int pitch, uint16_t *out)
+{
+    const void *src[3] = {p0, p1, p2};
+    if (!sr_model_ok(model) || !weights || count != sr_net_count(model->scale, model->blocks) || !rgb_format_ok(fmt) || !out) return MIHEVC_EINVAL;
+    if (!sr_geometry_ok(model->scale, src_width, src_height) || !rgb_planes_ok(*fmt, src, pitch, src_width)) return MIHEVC_EINVAL;
+    SrNet net;
+    if (!sr_net_build(model->scale, model->blocks, weights, count, net)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return stage_sr(*fmt, model->scale, &net, src_width, src_height, src, pitch, out);
 }
 
 #ifdef MIHEVC_PHASE_PROF

@@ -451,6 +451,28 @@ DEV int hadamard8_satd(int (&m)[8][8]) { return hadamard8_sum<false>(m); }      
 DEV int hadamard8_ac(int (&m)[8][8]) { return hadamard8_sum<true>(m); }         // a source tile's activity around its own mean
 
 // ------------------------------------------------------------------------------------------ executors
+// Operands of the executors' one collective operation, mfma_phase (kernels/sr_conv.h): a lane's A or B fragment of v_mfma_f32_16x16x32_f16 is eight IEEE
+// halves, kept as their 16 raw bytes; its share of the 16 x 16 fp32 result is four floats.  The lane maps (lane l of the wave's 64):
+//   A[row = l & 15][k = 8 (l >> 4) + j]   B[k = 8 (l >> 4) + j][col = l & 15]   in element j = 0 .. 7 of the fragment
+//   D[row = 4 (l >> 4) + i][col = l & 15]                                      in element i = 0 .. 3 of the result
+typedef uint32_t mfma_frag __attribute__((vector_size(16), may_alias));
+typedef float mfma_acc __attribute__((vector_size(16)));
+// exact: a half's 11 significant bits and its exponents -24 .. 15 all fit a float32
+DEV float half_bits_to_float(uint32_t h)
+{
+#if MIHEVC_GPU && defined(__HIP_DEVICE_COMPILE__)
+    const uint16_t b16 = (uint16_t)h;      // v_cvt_f32_f16: the same values, subnormal halves included
+    _Float16 v;
+    __builtin_memcpy(&v, &b16, 2);
+    return (float)v;
+#else
+    const uint32_t e = (h >> 10) & 31u, m = h & 1023u, b = e == 31 ? 0x7f800000u | m << 13 : (e + 112u) << 23 | m << 13;
+    float f;
+    __builtin_memcpy(&f, &b, 4);
+    const float mag = e == 0 ? (float)(int)m * 0x1p-24f : f;
+    return (h & 0x8000u) ? -mag : mag;
+#endif
+}
 #if MIHEVC_GPU
 #ifdef MIHEVC_PHASE_PROF
 __device__ unsigned long long g_phase_prof[8 * 1024 * 3];
@@ -506,6 +528,35 @@ struct GpuExec {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+    // A phase that is one chain of matrix products per wave: acc[i][j] = sum over steps of A_i x B_j (16 x 32 times 32 x 16 each, fp32 sums in the
+    // hardware's order), then epi(tid, acc) with the lane's share of every result, then the barrier.  load(tid, step, a, b) fills the lane's fragments
+    template <int NA, int NB, class L, class E> DEV void mfma_phase(int steps, L &&load, E &&epi)
+    {
+        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        const int tid = lane_id();
+        f4 acc[NA][NB];
+#pragma unroll
+        for (int i = 0; i < NA; i++)
+#pragma unroll
+            for (int j = 0; j < NB; j++) acc[i][j] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int s = 0; s < steps; s++) {
+            mfma_frag a[NA], b[NB];
+            load(tid, s, a, b);
+#pragma unroll
+            for (int i = 0; i < NA; i++)
+#pragma unroll
+                for (int j = 0; j < NB; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a[i]), __builtin_bit_cast(h8, b[j]), acc[i][j], 0, 0, 0);
+        }
+        mfma_acc out[NA][NB];
+#pragma unroll
+        for (int i = 0; i < NA; i++)
+#pragma unroll
+            for (int j = 0; j < NB; j++) out[i][j] = __builtin_bit_cast(mfma_acc, acc[i][j]);
+        epi(tid, out);
+        __syncthreads();
+    }
     DEV void atomic_add(int *p, int v) { atomicAdd(p, v); }
     DEV void atomic_add(unsigned *p, unsigned v) { atomicAdd(p, v); }
     DEV void atomic_add(unsigned long long *p, unsigned long long v) { atomicAdd(p, v); }
@@ -554,6 +605,38 @@ struct SeqExec {      // sequential stepping of a phase program (tests/emu)
     }
     template <class F> void phase(F &&f) { run(f); }
     template <class F> void wave_step(F &&f) { run(f); }
+    // GpuExec::mfma_phase stepped: per wave and step, the 64 lanes' fragments are gathered (in the executor's thread order), every product is worked out
+    // from the lane maps stated above in double and rounded to fp32 once per step, and each lane is handed its share.  Only the device run proves that
+    // the maps are the hardware's; this proves the tiling and the addressing around them.
+    template <int NA, int NB, class L, class E> void mfma_phase(int steps, L &&load, E &&epi)
+    {
+        mfma_acc acc[NT][NA][NB];
+        mfma_frag fa[NT][NA], fb[NT][NB];
+        for (int t = 0; t < NT; t++)
+            for (int i = 0; i < NA; i++)
+                for (int j = 0; j < NB; j++) acc[t][i][j] = mfma_acc{0.0f, 0.0f, 0.0f, 0.0f};
+        double A[16][32], B[32][16];      // one product's matrices, unpacked once
+        for (int s = 0; s < steps; s++) {
+            run([&](int t) { load(t, s, fa[t], fb[t]); });
+            for (int w0 = 0; w0 < NT; w0 += 64)
+                for (int i = 0; i < NA; i++)
+                    for (int j = 0; j < NB; j++) {
+                        for (int l = 0; l < 64; l++)
+                            for (int e = 0; e < 8; e++) {
+                                A[l & 15][8 * (l >> 4) + e] = (double)half_bits_to_float((fa[w0 + l][i][e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                                B[8 * (l >> 4) + e][l & 15] = (double)half_bits_to_float((fb[w0 + l][j][e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                            }
+                        for (int l = 0; l < 64; l++)
+                            for (int r = 0; r < 4; r++) {
+                                const int row = 4 * (l >> 4) + r, col = l & 15;
+                                double sum = (double)acc[w0 + l][i][j][r];
+                                for (int k = 0; k < 32; k++) sum += A[row][k] * B[k][col];
+                                acc[w0 + l][i][j][r] = (float)sum;
+                            }
+                    }
+        }
+        run([&](int t) { epi(t, acc[t]); });
+    }
     void atomic_add(int *p, int v) { *p += v; }
     void atomic_add(unsigned *p, unsigned v) { *p += v; }
     void atomic_add(unsigned long long *p, unsigned long long v) { *p += v; }

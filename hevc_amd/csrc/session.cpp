@@ -122,6 +122,16 @@ struct mihevc_session {
     CachedBlock<uint8_t> upscale_tab;
     UpscaleBlock upscale_host;
     int upscale_sw = 0, upscale_sh = 0;
+    // mihevc_set_sr_model, mihevc_send_frame_sr: the network as csrc/sr_net.h packs it.  sr_net is the host copy (launch list and shapes; null: no
+    // model), sr_wdev the packed weights and then the biases in one device block, copied on st_pre from one of two pinned blocks taken in turn as lut_host is, so a
+    // new model follows every launch that reads the old one in stream order; a model of another size waits for st_pre first and takes a new block.  sr_arena:
+    // the activations of the last source size (sr_net_bytes), allocated at the first frame of a size
+    std::unique_ptr<SrNet> sr_net;
+    CachedBlock<uint8_t> sr_wdev, sr_whost[2], sr_arena;
+    Event ev_sr[2];
+    size_t sr_bias_off = 0;
+    int64_t sr_sets = 0;
+    int sr_tw = 0, sr_th = 0;
     // mihevc_set_lut3d, mihevc_send_frame_lut3d: the packed table of lut_n points per axis (0: none) in one device block of the largest size,
     // so a new table of any size overwrites the old one in stream order on st_pre, behind every k_lut3d launch that reads it and in front of the next.  It is
     // copied from one of two pinned blocks, taken in turn; a block is written again only behind the event of the copy that read it, two tables back
@@ -1504,6 +1514,39 @@ static int ingest_lut3d(mihevc_session *s, const mihevc_lut3d_src &f, const void
     return finish_ingest(s, std::move(src), pts, !device_src && !async);
 }
 
+// A smaller R'G'B' source through the network (mihevc_send_frame_sr; the arguments are checked, a model is set): k_sr_input, the launches of the model, then
+// k_ingest_rgb over the three half planes the last layer wrote.  Everything on st_pre.  An arena the device cannot hold: MIHEVC_ENOMEM, nothing launched, the
+// session as it was
+static int ingest_sr(mihevc_session *s, const mihevc_rgb_format &f, int matrix, bool full, int sw, int sh, const void *const *p, int pitch, int64_t pts, bool device_src, bool async)
+{
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    const SrNet &net = *s->sr_net;
+    const int fct = net.scale == 2 ? 2 : 1, tw = sw / fct, th = sh / fct, W = s->cfg.width, H = s->cfg.height;
+    size_t off[SR_BUFS];
+    const size_t bytes = sr_arena_layout(tw, th, off);
+    if (tw != s->sr_tw || th != s->sr_th) {
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still working in the arena of the last size
+        s->sr_tw = s->sr_th = 0;
+        if (s->sr_arena.alloc(s->device, bytes, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
+        s->sr_tw = tw; s->sr_th = th;
+    }
+    mihevc_session::Src src;
+    if (int e = take_src(s, src)) return e;
+    const size_t es = (size_t)rgb_elem_size(f);
+    const int row = rgb_row_elems(f, sw);
+    SrcPlane pl[3] = {{p[0], row, sh, pitch}, {p[1], row, sh, pitch}, {p[2], row, sh, pitch}};
+    if (int e = stage_planes(s, pl, rgb_planes(f), es, device_src)) return e;
+    const void *sp[3] = {pl[0].p, pl[1].p, pl[2].p};
+    uint8_t *arena = s->sr_arena;
+    HIPCK(s, launch_sr_input(s->st_pre, sr_input_args(f, net.scale, sw, sh, sp, pl[0].pitch, (uint16_t *)(arena + off[SR_X])), f.sample, (int)es));
+    HIPCK(s, launch_sr_network(s->st_pre, net, arena, (const uint16_t *)s->sr_wdev.get(), (const float *)(s->sr_wdev.get() + s->sr_bias_off), tw, th));
+    const mihevc_rgb_format planes = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
+    const uint16_t *o = (const uint16_t *)(arena + off[SR_OUT]);
+    const IngestRgbArgs a = ingest_rgb_args(planes, matrix, full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
+    HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
+    return finish_ingest(s, std::move(src), pts, !device_src && !async);
+}
+
 // A source of another size (mihevc_send_frame_scaled; the arguments are checked): k_scale writes the session's own planes, margin included, from the caller's
 // device planes or from their copies in the staging set.  The tables of a new source size are built before the first device call
 static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
@@ -1799,6 +1842,52 @@ int mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src,
                          pitch_y >= src->width && pitch_c >= src->width / 2;
     if (int e = refuse_source(s, args_ok, flags)) return e;
     return ingest_upscaled(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
+}
+int mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const float *weights, size_t count)
+{
+    if (!s || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
+    if (!model) {
+        if (s->failed) return s->fail_code;
+        s->sr_net.reset();
+        return MIHEVC_OK;
+    }
+    if (!sr_model_ok(model) || !weights || count != sr_net_count(model->scale, model->blocks)) return MIHEVC_EINVAL;
+    if (s->failed) return s->fail_code;
+    std::unique_ptr<SrNet> net(new SrNet);
+    if (!sr_net_build(model->scale, model->blocks, weights, count, *net)) return MIHEVC_EINVAL;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    const size_t wbytes = (net->wpk.size() * sizeof(uint16_t) + 255) & ~(size_t)255, total = wbytes + net->bias.size() * sizeof(float);
+    const int k = (int)(s->sr_sets & 1);
+    if (s->sr_wdev.bytes() != total) {
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still reading the block of the last model
+        s->sr_net.reset();
+        if (s->sr_wdev.alloc(s->device, total, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
+    }
+    if (!s->ev_sr[k]) {
+        s->ev_sr[k] = Event(hipEventDisableTiming);
+        if (!s->ev_sr[k]) return fail(s, "mihevc_set_sr_model: no event");
+    } else HIPCK(s, hipEventSynchronize(s->ev_sr[k]));      // the copy of the model before the last one
+    if (s->sr_whost[k].bytes() != total) HIPCK(s, s->sr_whost[k].alloc(s->device, total, true));
+    memcpy(s->sr_whost[k].get(), net->wpk.data(), net->wpk.size() * sizeof(uint16_t));
+    memcpy(s->sr_whost[k].get() + wbytes, net->bias.data(), net->bias.size() * sizeof(float));
+    HIPCK(s, hipMemcpyAsync(s->sr_wdev, s->sr_whost[k], total, hipMemcpyHostToDevice, s->st_pre));
+    HIPCK(s, hipEventRecord(s->ev_sr[k], s->st_pre));
+    net->wpk = std::vector<uint16_t>();      // the launches need the shapes and the list, not the host copy of the weights
+    s->sr_bias_off = wbytes; s->sr_sets++;
+    s->sr_net = std::move(net);
+    return MIHEVC_OK;
+}
+int mihevc_send_frame_sr(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch,
+                         int64_t pts, int flags)
+{
+    const void *p[3] = {p0, p1, p2};
+    const bool fmt_ok = s && rgb_format_ok(fmt);
+    const int matrix = !fmt_ok ? 0 : fmt->matrix ? fmt->matrix : s->cfg.matrix;
+    const bool args_ok = fmt_ok && rgb_matrix_ok(matrix) && s->sr_net && sr_geometry_ok(s->sr_net->scale, src_width, src_height) &&
+                         s->cfg.width == s->sr_net->scale * src_width && s->cfg.height == s->sr_net->scale * src_height && rgb_planes_ok(*fmt, p, pitch, src_width);
+    if (int e = refuse_source(s, args_ok, flags)) return e;
+    const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
+    return ingest_sr(s, *fmt, matrix, full, src_width, src_height, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
 }
 int mihevc_send_frame_deint(mihevc_session *s, const mihevc_deint *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {

@@ -354,6 +354,43 @@ class Encoder:
         self._pts = pts + 1
         self._check(self._lib.mihevc_send_frame_upscaled(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_upscaled")
 
+    def set_sr_model(self, model):
+        """mihevc_set_sr_model: the RRDBNet send_sr runs: an hevc_amd.sr.RrdbNet (load_rrdbnet), or None to drop the model.  The weights are packed
+        and on their way to the device before the call returns; a model may be replaced between frames, and frames already sent keep theirs."""
+        if model is None:
+            self._check(self._lib.mihevc_set_sr_model(self._s, None, None, 0), "set_sr_model")
+            return
+        w = np.ascontiguousarray(model.weights, dtype=np.float32)
+        m = _lib.SrModel(int(model.scale), int(model.blocks))
+        self._check(self._lib.mihevc_set_sr_model(self._s, C.byref(m), w.ctypes.data, w.size), "set_sr_model")
+
+    def send_sr(self, fmt: _lib.RgbFormat, width: int, height: int, *planes, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_sr: a full-range R'G'B' picture of width x height, enlarged by the model of set_sr_model into the session's size (scale x the
+        source's), then converted as send_rgb converts.  The planes, their types, torch tensors on the device and `asynchronous`: as send_rgb, at the SOURCE size."""
+        width, height = int(width), int(height)
+        shapes = fmt.plane_shapes(width, height)
+        planes = list(planes)
+        if fmt.layout and len(planes) == 1 and planes[0] is not None and tuple(planes[0].shape) == (height, width, fmt.layout):
+            if isinstance(planes[0], np.ndarray) or planes[0].is_contiguous():
+                planes[0] = planes[0].reshape(height, width * fmt.layout)
+        if len(planes) != len(shapes) or any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {fmt!r} at {width}x{height}")
+        es = fmt.element_size
+        dt = np.dtype({1: np.float16, 2: np.float32}[fmt.sample]) if fmt.sample else np.dtype(np.uint8 if es == 1 else np.uint16)
+        ptrs, pitches, flags = self._source_planes(fmt, planes, dt, es, bool(fmt.sample), asynchronous, "send_sr")
+        if len(set(pitches)) != 1:
+            raise ValueError("the three planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        ptrs += [None] * (3 - len(ptrs))
+        self._check(self._lib.mihevc_send_frame_sr(self._s, C.byref(fmt), width, height, ptrs[0], ptrs[1], ptrs[2], pitches[0], pts, flags), "send_frame_sr")
+
+    def send_sr_tensor(self, t, pts: Optional[int] = None, asynchronous: bool = False):
+        """send_sr for one tensor in R, G, B order, the shapes and types of send_rgb_tensor; its own size is the source size"""
+        fmt, planes = self._rgb_tensor_planes(t, "send_sr_tensor")
+        h, w = (int(t.shape[1]), int(t.shape[2])) if fmt.layout == 0 else (int(t.shape[0]), int(t.shape[1]))
+        self.send_sr(fmt, w, h, *planes, pts=pts, asynchronous=asynchronous)
+
     def send_rgb(self, fmt: _lib.RgbFormat, *planes, pts: Optional[int] = None, asynchronous: bool = False):
         """mihevc_send_frame_rgb: a full-range R'G'B' picture of the session's display size, matrixed, range-scaled and decimated to 4:2:0 on the device.
         Three (height, width) planes in the order the format's r / g / b fields index, or one packed plane of shape (height, layout * width) or (height, width,
@@ -377,13 +414,12 @@ class Encoder:
         ptrs += [None] * (3 - len(ptrs))
         self._check(self._lib.mihevc_send_frame_rgb(self._s, C.byref(fmt), ptrs[0], ptrs[1], ptrs[2], pitches[0], pts, flags), "send_frame_rgb")
 
-    def send_rgb_tensor(self, t, pts: Optional[int] = None, asynchronous: bool = False):
-        """send_rgb for one tensor in R, G, B order: (3, H, W) of uint8, 16-bit integers (int16 carries the bits of a uint16), float16 or float32 in [0, 1],
-        or (H, W, 3) / (H, W, 4) of uint8 (a fourth element is ignored).  The format is built here; matrix and range follow the session.  A tensor on the session's
-        device is read where it is; a layout the kernel cannot read (column stride other than 1, pixels not side by side) raises ValueError."""
+    @staticmethod
+    def _rgb_tensor_planes(t, who):
+        """the format and planes of a tensor send_rgb_tensor / send_sr_tensor take"""
         kind = str(getattr(t, "dtype", "")).rsplit(".", 1)[-1]      # the tensor is taken by its interface: the package does not import torch
         if not hasattr(t, "data_ptr") or t.dim() != 3:
-            raise ValueError("send_rgb_tensor takes a (3, H, W) or (H, W, 3 | 4) torch tensor")
+            raise ValueError(f"{who} takes a (3, H, W) or (H, W, 3 | 4) torch tensor")
         if t.shape[0] == 3 and kind in ("uint8", "int16", "uint16", "float16", "float32"):
             sample = 1 if kind == "float16" else 2 if kind == "float32" else 0
             fmt = _lib.RgbFormat(0, 0, 1, 2, sample, 0 if sample else 8 if kind == "uint8" else 16)
@@ -400,6 +436,13 @@ class Encoder:
         if not t.is_cuda:
             planes = [p.contiguous().numpy() for p in planes]
             planes = [p.view(np.uint16) if p.dtype == np.int16 else p for p in planes]
+        return fmt, planes
+
+    def send_rgb_tensor(self, t, pts: Optional[int] = None, asynchronous: bool = False):
+        """send_rgb for one tensor in R, G, B order: (3, H, W) of uint8, 16-bit integers (int16 carries the bits of a uint16), float16 or float32 in [0, 1],
+        or (H, W, 3) / (H, W, 4) of uint8 (a fourth element is ignored).  The format is built here; matrix and range follow the session.  A tensor on the session's
+        device is read where it is; a layout the kernel cannot read (column stride other than 1, pixels not side by side) raises ValueError."""
+        fmt, planes = self._rgb_tensor_planes(t, "send_rgb_tensor")
         self.send_rgb(fmt, *planes, pts=pts, asynchronous=asynchronous)
 
     def sync_uploads(self):
@@ -787,7 +830,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
                 tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc',
-                upscale=None, sharpen: int = 8, antiring: int = 8) -> int:
+                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -814,7 +857,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     upscale: (w, h), a target height, or 'auto' for upscale_target's rule: the session, its level and the MP4 track take that size and every picture of the
     source, delivered at its own size, is enlarged on the device (Encoder.send_upscaled) with sharpen (0 .. 64 sixteenths) and antiring (0 .. 8
     eighths).  None: nothing changes.  Planar 4:2:0 sources on one device, per axis between 1:1 and 1:4; not together with size=, native_rgb, deinterlace=,
-    denoise=, lut=, interpolate=, sliced sessions or several devices."""
+    denoise=, lut=, interpolate=, sliced sessions or several devices.
+    sr_model: the path of an RRDBNet .pth file, a state dict, or an hevc_amd.sr.RrdbNet: every picture is enlarged by the network on the device
+    (Encoder.send_sr).  The pipe is asked for R'G'B' as native_rgb=True asks, so the container must probe as one of the RGB pixel formats; the
+    session, its level and the MP4 track open at scale x the source size.  One device; not together with any other source filter, size= or upscale=.  There is
+    no resize after the network and no tiling: a frame the device cannot hold ends the run."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
@@ -860,6 +907,22 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         upscale, size = target, target      # from here on the road of size=: the session takes the target, the clip is opened at the source's own size
     else:
         upscale = None
+    sr = None
+    if sr_model is not None:
+        if (size is not None or deinterlace is not None or denoise is not None or lut is not None or interpolate is not None or (devices and len(devices) > 1)):
+            logger.error("%s: sr_model= takes one device and none of size=, upscale=, deinterlace=, denoise=, lut=, interpolate=", Path(file_path).name)
+            return 1
+        from . import sr as sr_mod
+        try:
+            sr = sr_model if isinstance(sr_model, sr_mod.RrdbNet) else sr_mod.load_rrdbnet(sr_model)
+        except (OSError, ValueError, RuntimeError, KeyError) as e:
+            logger.error("%s: sr_model: %s", Path(file_path).name, e)
+            return 1
+        sw0, sh0 = int(info.width), int(info.height)
+        if min(sw0, sh0) < 4 or (sr.scale == 2 and (sw0 % 2 or sh0 % 2)):
+            logger.error("%s: sr_model: a %dx%d source does not fit a scale %d model", Path(file_path).name, sw0, sh0, sr.scale)
+            return 1
+        native_rgb, size = True, (sr.scale * sw0, sr.scale * sh0)      # the road of size=: the session takes the target, the clip is opened at the source's own size
     clip_info = info        # what the clip is opened with: the source's own description, rate and frame count
     if interpolate is not None:
         if (isinstance(interpolate, bool) or not isinstance(interpolate, int) or interpolate not in (2, 3, 4) or interp_mode not in _lib.INTERP_MODES or denoise is not None
@@ -958,7 +1021,12 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 logger.error("%s: lut= takes a planar 4:2:0 source at 8, 10 or 12 bit, width and height even (%r, %dx%d)", Path(file_path).name, fmt, cfg.width, cfg.height)
                 return 1
             fmt = None
-        if size is not None:
+        if sr is not None:
+            if rgb is None:
+                logger.error("%s: sr_model= takes a source that is read as R'G'B' (%r)", Path(file_path).name, fmt)
+                return 1
+            src_size = (int(clip.width), int(clip.height))
+        elif size is not None:
             fmt420 = fmt is None or (rgb is None and fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned)
             if not fmt420 or (devices and len(devices) > 1):
                 logger.error("%s: %s takes a planar 4:2:0 source on one device (%r)", Path(file_path).name, "size=" if upscale is None else "upscale=", fmt)
@@ -1021,10 +1089,14 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             with Encoder(cfg, device=device or 0) as enc:
                 if lut_table is not None:
                     enc.set_lut3d(lut_table)
+                if sr is not None:
+                    enc.set_sr_model(sr)
                 for i, planes in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    if lut_table is not None:
+                    if sr is not None:
+                        enc.send_sr(fmt, src_size[0], src_size[1], *planes, pts=i)
+                    elif lut_table is not None:
                         enc.send_lut3d(*planes, bit_depth=lut_src_depth, matrix=lut_src_matrix, full_range=lut_src_full, pts=i)
                     elif deint:
                         enc.send_deint(*planes, tff=deint[0], field_rate=deint[1], pts=i * (2 if deint[1] else 1))

@@ -426,6 +426,31 @@ typedef struct mihevc_upscale_src {
  * MIHEVC_ESTATE after flush. */
 int  mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src, const void *y, const void *u, const void *v,
                                 int pitch_y, int pitch_c, int64_t pts, int flags);
+/* ---- added under ABI 6: LEARNED super-resolution (symbols only) ----
+ * An RRDBNet (the architecture of RealESRGAN_x4plus, RealESRGAN_x2plus and RealESRGANv2-anime_6B: num_feat 64, num_grow_ch 32, `blocks` residual-in-residual
+ * dense blocks, scale 4 or 2) evaluated on the device with half activations and weights and fp32 sums on the matrix unit; DESIGN.md 6l is the numerical
+ * definition, hevc_amd/csrc/sr_net.h the flat order of the weights (hevc_amd.sr.load_rrdbnet produces it from a .pth file).  No weights ship with the library.
+ * Not covered: other architectures (SRVGGNetCompact, realesr-general with its denoise blend), scale 1, other channel counts, tiling and frames too large for
+ * device memory, a resize after the network, the other source filters in the same picture, sliced sessions, batching, fp8 / int8 weights, face enhancement. */
+typedef struct mihevc_sr_model {
+    int32_t scale;           /* 4 or 2 */
+    int32_t blocks;          /* RRDBs in the trunk, >= 1 (23 in x4plus / x2plus, 6 in anime_6B) */
+    int32_t reserved[6];     /* 0 */
+} mihevc_sr_model;
+/* The model of the session: weights (count floats, the flat order of sr_net.h) are rounded to half, packed and on their way to the device before the call
+ * returns, so the caller's array is free.  model == NULL drops the model.  A model may be replaced between frames under the rule of mihevc_set_lut3d: frames
+ * already sent keep the model they were sent under.  MIHEVC_EINVAL: a scale other than 4 / 2, blocks outside 1 .. 64, non-zero reserved, NULL weights, a count
+ * other than the model's, slice_count > 1.  MIHEVC_ENOMEM: the device cannot hold the weights; the session has no model then */
+int  mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const float *weights, size_t count);
+/* A full-range R'G'B' picture of src_width x src_height in the layouts of mihevc_send_frame_rgb, enlarged by the model into the session's planes: cfg.width and
+ * cfg.height must equal scale x the source size.  The network's output is clamped to [0, 1] and converted as mihevc_send_frame_rgb converts half planes
+ * (fmt->matrix and fmt->range as there).  Flags, staging, ownership and stream ordering are those of mihevc_send_frame_rgb; pitch: elements per row of the SOURCE.
+ * Device memory for the activations (about 6048 bytes per source pixel at scale 4, a quarter of that at scale 2; sr_net.h states the formula) is allocated at the
+ * first frame of a size; nothing is tiled: MIHEVC_ENOMEM when the device cannot hold it, and the session goes on.  MIHEVC_EINVAL, decided before any device
+ * call and leaving the session usable: everything mihevc_send_frame_rgb refuses, no model set, a size mismatch, odd source dimensions with scale 2, a source
+ * side below 4, slice_count > 1.  MIHEVC_ESTATE after flush.  The entry keeps no ring: it mixes with the other entries that keep none. */
+int  mihevc_send_frame_sr(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2,
+                          int pitch, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -627,6 +652,30 @@ int mihevc_k_mcfi_render(int device, const mihevc_interpolate *d, int j, const v
  * (MIHEVC_EINVAL: what mihevc_send_frame_upscaled refuses, an out_bit_depth other than 8 or 10), then MIHEVC_ENODEV without a device */
 int mihevc_k_upscale_source(int device, const mihevc_upscale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
                             int dst_width, int dst_height, int out_bit_depth, void *out_y, void *out_u, void *out_v);
+/* added under ABI 6.  One launch of k_sr_conv (hevc_amd/csrc/kernels/sr_conv.h), host arrays in and out.  Tensors are IEEE halves, NHWC.  `in`: the source
+ * tensor of in_ch channels, width x height pixels, or with up = 1 ((height + 1) / 2) x ((width + 1) / 2); the launch reads cin channels (a multiple of 32, at
+ * most 192) from in_off on.  weights: fp32 [cout][cin_real][3][3], packed here (input channels cin_real .. cin - 1 meet zero weights); bias: cout.  `out` is read
+ * AND written: it is uploaded as given, the launch writes cout channels (32 or 64) from out_off on of its out_ch, and it comes back whole.  planar = 1: cout is
+ * 3, n_res is 0 and out is three planes of height x width.  act: LeakyReLU with `slope`.  n_res 0 .. 2: v = v a1 + r1, then v = v a2 + r2; r1 / r2 are tensors of the
+ * output's size with r*_ch channels, read from r*_off on.  Channel counts and offsets of buffers are multiples of 8.  MIHEVC_EINVAL first, then MIHEVC_ENODEV */
+typedef struct mihevc_sr_conv_desc {
+    int32_t width, height;                           /* of the output */
+    int32_t up, planar, act, n_res;
+    int32_t in_ch, in_off, cin, cin_real;
+    int32_t out_ch, out_off, cout;
+    int32_t r1_ch, r1_off, r2_ch, r2_off;
+    float slope, a1, a2;
+} mihevc_sr_conv_desc;
+int mihevc_k_sr_conv(int device, const mihevc_sr_conv_desc *d, const uint16_t *in, const float *weights, const float *bias, const uint16_t *r1, const uint16_t *r2,
+                     uint16_t *out);
+/* added under ABI 6.  k_sr_input alone: a source as mihevc_send_frame_rgb takes it (fmt->matrix and fmt->range are not used) -> the network's input tensor of 32
+ * channels: src_width x src_height pixels at scale 4, half of that each way at scale 2 */
+int mihevc_k_sr_input(int device, const mihevc_rgb_format *fmt, int scale, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch,
+                      uint16_t *out);
+/* added under ABI 6.  The whole network as mihevc_send_frame_sr runs it (k_sr_input, then every launch of sr_net.h), from host arrays: weights / count as
+ * mihevc_set_sr_model takes them; out: three planes (R, G, B) of halves, scale x the source size.  MIHEVC_ENOMEM when the device cannot hold the size */
+int mihevc_k_sr_network(int device, const mihevc_sr_model *model, const float *weights, size_t count, const mihevc_rgb_format *fmt, int src_width, int src_height,
+                        const void *p0, const void *p1, const void *p2, int pitch, uint16_t *out);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
