@@ -1131,6 +1131,15 @@ int upload_as_laid_out(DevBuf &d, const void *&p, int row, int rows, int pitch, 
     p = d.as<uint8_t>() + off;
     return MIHEVC_OK;
 }
+// the three planes of a planar 4:2:0 frame `in` of w x h, each as the caller laid it out; d: their device copies
+int upload_yuv420(DevBuf din[3], const void *d[3], const void *const *in, int w, int h, int pitch_y, int pitch_c, size_t es)
+{
+    for (int c = 0; c < 3; c++) {
+        d[c] = in[c];
+        if (int e = upload_as_laid_out(din[c], d[c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, es)) return e;
+    }
+    return MIHEVC_OK;
+}
 // the output of a converter: planes of the coded size (the display size rounded up to 8) and of 16-byte aligned stride
 template <typename TO> struct ConvertOut {
     Planes3<TO> planes;
@@ -1213,9 +1222,8 @@ int stage_lut3d(const mihevc_lut3d_src &f, int n, const uint16_t *table, const v
     DevBuf din[3], dtab;
     ConvertOut<TO> dst;
     if (int e = dst.alloc(w, h)) return e;
-    const void *dsrc[3] = {src[0], src[1], src[2]};
-    for (int c = 0; c < 3; c++)
-        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, es)) return e;
+    const void *dsrc[3];
+    if (int e = upload_yuv420(din, dsrc, src, w, h, pitch_y, pitch_c, es)) return e;
     std::vector<uint16_t> packed(entries * 4);
     lut3d_pack(n, table, packed.data());
     if (int e = to_device(dtab, packed.data(), packed.size())) return e;
@@ -1239,14 +1247,12 @@ int stage_scale(const mihevc_scale_src &f, const void *const *src, int pitch_y, 
     DevBuf din[3], dtab;
     ConvertOut<TO> dst;
     if (int e = dst.alloc(dw, dh)) return e;
-    const void *dsrc[3] = {src[0], src[1], src[2]};
-    for (int c = 0; c < 3; c++)
-        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? f.width / 2 : f.width, c ? f.height / 2 : f.height, c ? pitch_c : pitch_y, es)) return e;
-    CK(dtab.alloc(blk.bytes.size()));
-    CK(hipMemcpy(dtab.p, blk.bytes.data(), blk.bytes.size(), hipMemcpyHostToDevice));
+    const void *dsrc[3];
+    if (int e = upload_yuv420(din, dsrc, src, f.width, f.height, pitch_y, pitch_c, es)) return e;
+    if (int e = to_device(dtab, blk.bytes.data(), blk.bytes.size())) return e;
     const int32_t *first[4];
     const int16_t *coef[4];
-    for (int k = 0; k < 4; k++) { first[k] = (const int32_t *)(dtab.as<uint8_t>() + blk.first[k]); coef[k] = (const int16_t *)(dtab.as<uint8_t>() + blk.coef[k]); }
+    tap_pointers(dtab.as<uint8_t>(), blk.first, first); tap_pointers(dtab.as<uint8_t>(), blk.coef, coef);
     const ScaleArgs a = scale_args(f.bit_depth, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, f.width, f.height, dw, dh, dst.w, dst.h, out_depth, dst.p, dst.stride,
                                    first, coef, blk.taps);
     CK(launch_scale(0, a, es == 2, sizeof(TO) == 2));
@@ -1264,17 +1270,12 @@ int stage_upscale(const mihevc_upscale_src &f, const void *const *src, int pitch
     DevBuf din[3], dtab;
     ConvertOut<TO> dst;
     if (int e = dst.alloc(dw, dh)) return e;
-    const void *dsrc[3] = {src[0], src[1], src[2]};
-    for (int c = 0; c < 3; c++)
-        if (int e = upload_as_laid_out(din[c], dsrc[c], c ? f.width / 2 : f.width, c ? f.height / 2 : f.height, c ? pitch_c : pitch_y, es)) return e;
-    CK(dtab.alloc(blk.bytes.size()));
-    CK(hipMemcpy(dtab.p, blk.bytes.data(), blk.bytes.size(), hipMemcpyHostToDevice));
+    const void *dsrc[3];
+    if (int e = upload_yuv420(din, dsrc, src, f.width, f.height, pitch_y, pitch_c, es)) return e;
+    if (int e = to_device(dtab, blk.bytes.data(), blk.bytes.size())) return e;
     const int32_t *first[4], *near[4];
     const int16_t *coef[4];
-    for (int k = 0; k < 4; k++) {
-        first[k] = (const int32_t *)(dtab.as<uint8_t>() + blk.first[k]); near[k] = (const int32_t *)(dtab.as<uint8_t>() + blk.near[k]);
-        coef[k] = (const int16_t *)(dtab.as<uint8_t>() + blk.coef[k]);
-    }
+    tap_pointers(dtab.as<uint8_t>(), blk.first, first); tap_pointers(dtab.as<uint8_t>(), blk.near, near); tap_pointers(dtab.as<uint8_t>(), blk.coef, coef);
     const UpscaleArgs a = upscale_args(f, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, dw, dh, dst.w, dst.h, out_depth, dst.p, dst.stride, first, near, coef);
     CK(launch_upscale(0, a, es == 2, sizeof(TO) == 2));
     CK(hipDeviceSynchronize());
@@ -1339,11 +1340,9 @@ int stage_deint(const void *const *prev, const void *const *cur, const void *con
     ConvertOut<T> dst;
     if (int e = dst.alloc(w, h)) return e;
     const void *d[3][3];
+    const void *const *in[3] = {prev, cur, next};
     for (int f = 0; f < 3; f++)
-        for (int c = 0; c < 3; c++) {
-            d[f][c] = (f == 0 ? prev : f == 1 ? cur : next)[c];
-            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
-        }
+        if (int e = upload_yuv420(din + 3 * f, d[f], in[f], w, h, pitch_y, pitch_c, sizeof(T))) return e;
     const DeintArgs a = deint_args(depth, d[0], d[1], d[2], pitch_y, pitch_c, w, h, dst.w, dst.h, keep, second, dst.p, dst.stride);
     CK(launch_deint(0, a, sizeof(T) == 2));
     CK(hipDeviceSynchronize());
@@ -1359,11 +1358,9 @@ int stage_denoise(const mihevc_denoise &dn, const void *const *prev, const void 
     ConvertOut<T> dst;
     if (int e = dst.alloc(w, h)) return e;
     const void *d[3][3];
+    const void *const *in[3] = {prev, cur, next};
     for (int f = 0; f < 3; f++)
-        for (int c = 0; c < 3; c++) {
-            d[f][c] = (f == 0 ? prev : f == 1 ? cur : next)[c];
-            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
-        }
+        if (int e = upload_yuv420(din + 3 * f, d[f], in[f], w, h, pitch_y, pitch_c, sizeof(T))) return e;
     const DenoiseArgs a = denoise_args(dn, depth, d[0], d[1], d[2], pitch_y, pitch_c, w, h, dst.w, dst.h, dst.p, dst.stride);
     CK(launch_denoise(0, a, sizeof(T) == 2));
     CK(hipDeviceSynchronize());
@@ -1392,11 +1389,9 @@ template <typename T> int stage_fm_weave(const void *const *cur, const void *con
     ConvertOut<T> dst;
     if (int e = dst.alloc(w, h)) return e;
     const void *d[2][3];
+    const void *const *in[2] = {cur, other};
     for (int f = 0; f < 2; f++)
-        for (int c = 0; c < 3; c++) {
-            d[f][c] = (f ? other : cur)[c];
-            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
-        }
+        if (int e = upload_yuv420(din + 3 * f, d[f], in[f], w, h, pitch_y, pitch_c, sizeof(T))) return e;
     const DeintArgs a = deint_args(depth, d[1], d[0], d[1], pitch_y, pitch_c, w, h, dst.w, dst.h, keep, 0, dst.p, dst.stride);
     CK(launch_fm_weave(0, a, sizeof(T) == 2));
     CK(hipDeviceSynchronize());
@@ -1430,11 +1425,9 @@ int stage_mcfi_render(const mihevc_interpolate &m, int j, const void *const *cur
     ConvertOut<T> dst;
     if (int e = dst.alloc(w, h)) return e;
     const void *d[2][3];
+    const void *const *in[2] = {cur, next};
     for (int f = 0; f < 2; f++)
-        for (int c = 0; c < 3; c++) {
-            d[f][c] = (f ? next : cur)[c];
-            if (int e = upload_as_laid_out(din[3 * f + c], d[f][c], c ? w / 2 : w, c ? h / 2 : h, c ? pitch_c : pitch_y, sizeof(T))) return e;
-        }
+        if (int e = upload_yuv420(din + 3 * f, d[f], in[f], w, h, pitch_y, pitch_c, sizeof(T))) return e;
     if (v)
         if (int e = to_device(dv, v, (size_t)mcfi_blocks(w) * mcfi_blocks(h) * 2)) return e;
     const unsigned long long sum = scene_sum;
@@ -1443,6 +1436,14 @@ int stage_mcfi_render(const mihevc_interpolate &m, int j, const void *const *cur
     CK(launch_mcfi_render(0, a, sizeof(T) == 2));
     CK(hipDeviceSynchronize());
     return dst.planes.download(out);
+}
+
+// every frame of a stage entry's planar sources is there, with its three planes
+bool frames_ok(std::initializer_list<const void *const *> frames)
+{
+    for (const void *const *f : frames)
+        if (!f || !f[0] || !f[1] || !f[2]) return false;
+    return true;
 }
 
 int select_device(int device)
@@ -1672,9 +1673,7 @@ int mihevc_k_scale_source(int device, const mihevc_scale_src *src, const void *y
 int mihevc_k_deinterlace(int device, const void *const prev[3], const void *const cur[3], const void *const next[3], int width, int height, int pitch_y, int pitch_c,
                          int bit_depth, int keep, int second, void *out_y, void *out_u, void *out_v)
 {
-    if (!prev || !cur || !next || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
-    for (int c = 0; c < 3; c++)
-        if (!prev[c] || !cur[c] || !next[c]) return MIHEVC_EINVAL;
+    if (!frames_ok({prev, cur, next}) || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
     if (!deint_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
     if ((keep != 0 && keep != 1) || (second != 0 && second != 1)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
@@ -1685,9 +1684,7 @@ int mihevc_k_deinterlace(int device, const void *const prev[3], const void *cons
 int mihevc_k_denoise(int device, const mihevc_denoise *dn, const void *const prev[3], const void *const cur[3], const void *const next[3], int width, int height,
                      int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v)
 {
-    if (!denoise_strength_ok(dn) || !prev || !cur || !next || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
-    for (int c = 0; c < 3; c++)
-        if (!prev[c] || !cur[c] || !next[c]) return MIHEVC_EINVAL;
+    if (!denoise_strength_ok(dn) || !frames_ok({prev, cur, next}) || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
     if (!denoise_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
     void *out[3] = {out_y, out_u, out_v};
@@ -1706,9 +1703,7 @@ int mihevc_k_fieldmatch_metrics(int device, const void *prev_y, const void *cur_
 int mihevc_k_fieldmatch_weave(int device, const void *const cur[3], const void *const other[3], int width, int height, int pitch_y, int pitch_c, int bit_depth,
                               int keep, void *out_y, void *out_u, void *out_v)
 {
-    if (!cur || !other || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
-    for (int c = 0; c < 3; c++)
-        if (!cur[c] || !other[c]) return MIHEVC_EINVAL;
+    if (!frames_ok({cur, other}) || !out_y || !out_u || !out_v) return MIHEVC_EINVAL;
     if (!deint_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
     if (keep != 0 && keep != 1) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
@@ -1726,9 +1721,7 @@ int mihevc_k_mcfi_vectors(int device, const void *cur_y, const void *next_y, int
 int mihevc_k_mcfi_render(int device, const mihevc_interpolate *d, int j, const void *const cur[3], const void *const next[3], const int16_t *v, uint64_t scene_sum,
                          int width, int height, int pitch_y, int pitch_c, int bit_depth, void *out_y, void *out_u, void *out_v)
 {
-    if (!mcfi_mode_ok(d) || j < 0 || j >= d->factor || !cur || !next || !out_y || !out_u || !out_v || (!v && d->mode == 0)) return MIHEVC_EINVAL;
-    for (int c = 0; c < 3; c++)
-        if (!cur[c] || !next[c]) return MIHEVC_EINVAL;
+    if (!mcfi_mode_ok(d) || j < 0 || j >= d->factor || !frames_ok({cur, next}) || !out_y || !out_u || !out_v || (!v && d->mode == 0)) return MIHEVC_EINVAL;
     if (!mcfi_geometry_ok(width, height) || !convert_geometry_ok(width, height, bit_depth) || pitch_y < width || pitch_c < width / 2) return MIHEVC_EINVAL;
     if (v && !mcfi_vectors_ok(v, (size_t)mcfi_blocks(width) * mcfi_blocks(height))) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;

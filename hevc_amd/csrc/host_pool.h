@@ -171,4 +171,29 @@ private:
     hipEvent_t ev_ = nullptr;
 };
 
+// Two pinned blocks taken in turn: the host side of a device block that is rewritten by copies on one stream.  A block is written again only behind the event
+// of the copy that read it, two sets back
+struct PinnedPair {
+    CachedBlock<uint8_t> host[2];
+    Event ev[2];
+    int64_t sets = 0;
+    // the block of this turn, `bytes` long (one of another size is replaced), once the copy that last read it is through
+    hipError_t acquire(int dev, size_t bytes, uint8_t *&block)
+    {
+        const int k = (int)(sets & 1);
+        if (ev[k]) { if (hipError_t e = hipEventSynchronize(ev[k])) return e; }
+        else if (!(ev[k] = Event(hipEventDisableTiming))) return hipErrorOutOfMemory;
+        if (host[k].bytes() != bytes) if (hipError_t e = host[k].alloc(dev, bytes, true)) return e;
+        block = host[k].get();
+        return hipSuccess;
+    }
+    // the first `bytes` of that block go to dst on `st`, the event behind the copy; the turn passes to the other block
+    hipError_t commit(void *dst, size_t bytes, hipStream_t st)
+    {
+        const int k = (int)(sets++ & 1);
+        if (hipError_t e = hipMemcpyAsync(dst, host[k], bytes, hipMemcpyHostToDevice, st)) return e;
+        return hipEventRecord(ev[k], st);
+    }
+};
+
 }  // namespace mihevc

@@ -106,6 +106,12 @@ inline bool scale_block_build(int sw, int sh, int dw, int dh, int tile_h, int ma
     return true;
 }
 
+// where the four tables of one kind (off: first, coef or near of a block) lie in a copy of the block's bytes at `base`, as T
+template <typename T> inline void tap_pointers(const uint8_t *base, const size_t off[4], const T *out[4])
+{
+    for (int k = 0; k < 4; k++) out[k] = (const T *)(base + off[k]);
+}
+
 // ---- the upscaler (kernels/upscale.h): S <= Dn <= 4 S.  The positions are those above; the kernel is NOT stretched, so the taps of output
 // sample i are the integers k with |pos - k| < 2 (at most 4) weighted CR(pos - k): with A as above, M = 4 Dn and a = |A - M k| the two polynomials above
 // apply over 2 M^3 with this M.  Normalisation and the dropping of end zeros as above (1:1 is the single tap 4096).  near = floor(pos): the anti-ringing clamp

@@ -7,47 +7,41 @@
 // the step's symbols into pinned memory on a second stream, and one CABAC job per picture on the host pool.
 // The device never waits for CABAC except when the 4-deep symbol ring wraps.
 // Replaces, for the selected files, the `ffmpeg -c:v libx265` child of the reference (core/transcoder.py:506).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <functional>
-#include <map>
-#include <mutex>
 #include <numeric>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "bitstream.h"
-#include "device.h"
-#include "fieldmatch_plan.h"
-#include "gop_plan.h"
-#include "host_pool.h"
 #include "md5.h"
-#include "ratectl.h"
-#include "scale_taps.h"
-#include "slice_group.h"
+#include "session.h"
 
-using namespace mihevc;
+constexpr int kSeamRows = 8;      // rows of the pre-deblock reconstruction exchanged either side of a seam (deblocking reads 4 and writes 3; one 8x8 grid row)
+
+// the session's one failure path: every later call returns fail_code, and the other slices of the picture stop waiting for this one
+int fail(mihevc_session *s, std::string msg)
+{
+    { std::lock_guard<std::mutex> l(s->m); s->err = std::move(msg); }
+    s->failed = true;
+    if (s->group) s->group->fail();
+    return MIHEVC_EDEVICE;
+}
+
+// padded 0: a plain picture; 1: a reference picture with its PAD border all round; 2: a work picture with kSeamRows rows above and below (the rows the
+// neighbour slices hand over for deblocking across seams; unused otherwise)
+int alloc_planes(mihevc_session *s, CachedBlock<uint8_t> mem[3], void *p[3], int stride[3], int padded)
+{
+    for (int i = 0; i < 3; i++) {
+        int w = i ? s->w / 2 : s->w, h = i ? s->h / 2 : s->h, pad = padded == 1 ? (i ? PAD_C : PAD_Y) : 0, vm = padded == 2 ? (i ? kSeamRows / 2 : kSeamRows) : pad;
+        stride[i] = (w + 2 * pad + 63) & ~63;
+        HIPCK(s, mem[i].alloc(s->device, (size_t)stride[i] * (h + 2 * vm) * esize(s), false));
+        p[i] = mem[i] + ((size_t)vm * stride[i] + pad) * esize(s);
+    }
+    return 0;
+}
 
 namespace {
-
-constexpr int kRing = 12;     // symbol slots per lane (capacity): slot 0 holds the IDR picture, the rest rotate over the P steps.
-                              // A session uses s->ring of them: 8 up to 1080p-class levels, 12 from level 5 (2160p+), where the CABAC of one
-                              // picture (12 ms at 2160p, 45 ms at 4320p) outlasts five device steps when few GOP lanes are busy
-
-struct Packet {
-    std::vector<uint8_t> data;
-    int64_t pts = 0, dts = 0;
-    bool key = false, ready = false;
-    std::string error;      // the host coder refused the picture's levels (sign data hiding parity): mihevc_receive_packet fails with MIHEVC_EINVAL here
-};
 
 // symbol block of one picture: [cu | coef Y | coef U | coef V | sao | sse[3] | rate estimate | hash[3] | ssim[3]]; the device twin carries the per-CTU squared errors
 // behind it (SaoArgs::sse_ctu: never copied to the host, k_sse_fold turns them into sse[3]).  hash: the CRC / checksum words of cfg.pic_hash 2 / 3 (k_pic_hash_fold);
@@ -75,199 +69,12 @@ struct SymLayout {
     }
 };
 
-// a session's scratch buffer from the process-wide cache (grow()): device memory, optionally with a pinned host twin of the same size
-struct CachedBuf { CachedBlock<uint8_t> d, h; };
-
-constexpr int kGroups = 2;        // lane groups of a chunk's P/B steps: two launch sequences on two streams (encode_chunk)
 // sessions this process has open on a device.  A chunk runs as lane groups only while its session is the device's only one: a second session's launches already
 // fill the first one's launch tails, and with the process's four hardware queues two sessions of five busy streams each had their uploads and copies queue
 // behind kernels (bench.py's two-session leg from pinned host buffers: -5 %).  The stream does not depend on the choice.
 std::atomic<int> &open_sessions(int device) { static std::atomic<int> n[64]; return n[device & 63]; }
-constexpr int kSeamRows = 8;      // rows of the pre-deblock reconstruction exchanged either side of a seam (deblocking reads 4 and writes 3; one 8x8 grid row)
-
-}  // namespace
-
-struct mihevc_session {
-    mihevc_config cfg;
-    int device = 0;
-    int w = 0, h = 0, ctus_w = 0, ctus_h = 0, n_ctu = 0;      // coded size
-    TileGrid tiles;                                            // IDR pictures (PPS 1); 1x1 when cfg.intra_tiles == 0
-    TileGrid ptiles;                                           // P pictures (PPS 0, cfg.p_tiles); 1x1 when off
-    int keyint = 90, lanes = 4, me_range = 16, qp_p = 22, qp_i = 19;
-    bool is16 = false, keep_recon = false, flushed = false, flushing = false;
-    std::atomic<bool> failed{false};     // sticky (fail()); mihevc_abort sets it from another thread
-    int fail_code = MIHEVC_EDEVICE;      // what calls return once `failed` is set: MIHEVC_EINVAL when the host coder refused a picture
-    std::string err;                     // written under `m` (mihevc_abort may run on another thread)
-    CachedStream st_compute, st_copy, st_pre;      // st_pre: the chunk's pre-search, beside the IDR step; then the P/B steps of lane group 1
-    int lane_groups = kGroups;        // launch sequences the P/B steps of a chunk run as (MIHEVC_LANE_GROUPS, read at mihevc_open: 1 = one sequence on the compute stream)
-    // uploads of host frames (mihevc_send_frame / _async) go through st_pre (idle outside a chunk's IDR step; a FOURTH stream per session made two of them share a
-    // hardware queue: the copy stream's SSE pass and symbol copies then queued behind the compute stream's kernels, +10 ms of bubbles per 300-frame clip); the
-    // chunk's first launch waits for ev_up
-    Event ev_up{hipEventDisableTiming};
-    bool up_pending = false;
-    // source pictures of the current chunk (device), in display order
-    struct Src { CachedBlock<uint8_t> mem[3]; void *p[3]; int stride[3]; int64_t pts; bool borrowed; };      // borrowed: the caller's device planes, not copied (mem is empty)
-    std::vector<Src> pending;
-    std::vector<Src> free_src;
-    // mihevc_send_frame_fmt, host planes: the raw planes in the SOURCE layout on their way to k_ingest.  Copy and conversion of a picture are neighbours on st_pre,
-    // so the next picture's copy comes behind this picture's kernel in stream order: one set serves every picture (a set per pending picture would be 12 MB
-    // each for a 1080p 4:4:4 16-bit source).  It grows when a larger format arrives (st_pre is synchronised first) and goes back with the session
-    CachedBlock<uint8_t> stage;
-    // mihevc_send_frame_scaled: the four coefficient tables (csrc/scale_taps.h) of the last source size, built and uploaded once per size; the host copy lives as
-    // long as the device block it is copied from on st_pre
-    CachedBlock<uint8_t> scale_tab;
-    ScaleBlock scale_host;
-    int scale_sw = 0, scale_sh = 0;
-    // mihevc_send_frame_upscaled: its own block of tables (scale_taps.h, upscale_block_build) of the last source size, kept as scale_tab is
-    CachedBlock<uint8_t> upscale_tab;
-    UpscaleBlock upscale_host;
-    int upscale_sw = 0, upscale_sh = 0;
-    // mihevc_set_sr_model, mihevc_send_frame_sr: the network as csrc/sr_net.h packs it.  sr_net is the host copy (launch list and shapes; null: no
-    // model), sr_wdev the packed weights and then the biases in one device block, copied on st_pre from one of two pinned blocks taken in turn as lut_host is, so a
-    // new model follows every launch that reads the old one in stream order; a model of another size waits for st_pre first and takes a new block.  sr_arena:
-    // the activations of the last source size (sr_net_bytes), allocated at the first frame of a size
-    std::unique_ptr<SrNet> sr_net;
-    CachedBlock<uint8_t> sr_wdev, sr_whost[2], sr_arena;
-    Event ev_sr[2];
-    size_t sr_bias_off = 0;
-    int64_t sr_sets = 0;
-    int sr_tw = 0, sr_th = 0;
-    // mihevc_set_lut3d, mihevc_send_frame_lut3d: the packed table of lut_n points per axis (0: none) in one device block of the largest size,
-    // so a new table of any size overwrites the old one in stream order on st_pre, behind every k_lut3d launch that reads it and in front of the next.  It is
-    // copied from one of two pinned blocks, taken in turn; a block is written again only behind the event of the copy that read it, two tables back
-    CachedBlock<uint8_t> lut_dev, lut_host[2];
-    Event ev_lut[2];
-    int lut_n = 0;
-    int64_t lut_sets = 0;
-    // mihevc_send_frame_deint, mihevc_send_frame_denoise, mihevc_send_frame_fieldmatch, mihevc_send_frame_interpolate: a ring of three source-size pictures (display size, rows that begin 16-byte aligned), allocated at the
-    // first call; frame k lies in slot k % 3.  Copies and k_deint / k_denoise launches are neighbours on st_pre, so a slot is overwritten in stream order behind
-    // the last launch that read it.  src_ring_kind: the entry that filled the ring first (a pending frame keeps every other entry out until flush, so it is the only
-    // one); src_ring_n: frames taken; src_ring_pending: the last of them has not produced its picture(s) yet (the next frame or mihevc_flush does that)
-    enum { RING_NONE = 0, RING_DEINT, RING_DENOISE, RING_FIELDMATCH, RING_MCFI };
-    CachedBlock<uint8_t> src_ring[3];
-    void *src_ring_p[3][3] = {};
-    int src_ring_pitch[3] = {};
-    int64_t src_ring_n = 0, src_ring_pts = 0;
-    int src_ring_kind = RING_NONE;
-    bool src_ring_pending = false;
-    int deint_tff = 0, deint_field_rate = 0;
-    mihevc_denoise denoise_pending = {};      // the strengths of the pending frame
-    // mihevc_send_frame_interpolate: mcfi_pending: factor and mode of the session's first interpolated frame, the scene threshold of the pending
-    // one; mcfi_dev: vectors, SAD0(0), the parts of D and D (mcfi_layout), written and read in stream order on st_pre
-    mihevc_interpolate mcfi_pending = {};
-    CachedBlock<uint8_t> mcfi_dev;
-    // mihevc_send_frame_fieldmatch: the frames go through the same ring.  fm_open: from the first fieldmatch frame until flush no other entry
-    // sends a frame.  fm_dev: the partials of k_fm_metrics and the eight folded numbers behind them; fm_host: their pinned copy, valid behind ev_fm.  fm_frames:
-    // what was decided, by frame (decided: mihevc_get_fieldmatch_info may hand it out; under `m`).  fm_held: decimate: the filled pictures of the open cycle with
-    // their frames' numbers; fm_pictures: pictures handed on so far
-    bool fm_open = false;
-    mihevc_fieldmatch fm_mode = {};
-    CachedBlock<uint8_t> fm_dev, fm_host;
-    Event ev_fm;
-    struct FmFrame { mihevc_fm_frame info; bool decided; };
-    std::vector<FmFrame> fm_frames;
-    std::vector<std::pair<Src, int64_t>> fm_held;
-    int64_t fm_pictures = 0, fm_first_pts = 0;
-    // per lane
-    // The vector moves a lane's handles when it grows; the blocks they own stay where they are, so the raw pointers in argument blocks, jobs and BandPub stay valid
-    struct Lane {
-        CachedBlock<uint8_t> rec_mem[3][3]; void *rec_p[3][3] = {}; int rec_stride[3] = {};       // padded final reconstructions: the anchors ping-pong between 0 and 1; 2 = B pictures (cfg.bframes; never a reference)
-        CachedBlock<uint8_t> work_mem[3]; void *work_p[3] = {}; int work_stride[3] = {};           // pre-deblock / deblocked picture (unpadded)
-        CachedBlock<int32_t> me, me1;      // integer-search tables (me1: list 1 of B pictures)
-        CachedBlock<IpInfo> ip;            // per CTU: inter pass -> intra second pass of P pictures
-        CachedBlock<IntraPlan> plan;       // per CTU: k_intra_plan -> k_intra_diag (IDR pictures)
-        CachedBlock<uint8_t> sym_dev[kRing], sym_host[kRing];
-        CachedBlock<uint8_t> md5_host[kRing];      // cfg.pic_hash 1: the final picture (coded size, Y U V without gaps), pinned, per ring slot
-    };
-    std::vector<Lane> lane;
-    CachedBuf args;                   // argument blocks of a whole chunk (device + pinned staging)
-    // by (lane group, ring slot); step 0 (all lanes, one launch) uses group 0's slot 0.  compute: the step's pictures are final; copy: its symbols are on the
-    // host; jobs_open: its CABAC jobs still running (under `m`)
-    struct Slot { Event compute{hipEventDisableTiming}, copy{hipEventDisableTiming}; int jobs_open = 0; } slot[kGroups][kRing];
-    Event ev_join{hipEventDisableTiming};     // behind the last step of lane group 1 (st_pre): the compute stream waits for it at the end of the chunk
-    Event t_begin{hipEventDefault}, t_end{hipEventDefault};      // a chunk's device time (stats.device_ms)
-    std::vector<Event> ev_pool;        // profile_stages: start/stop pairs
-    struct Mark { int stage, pictures; size_t ev; };
-    std::vector<Mark> marks;
-    // host side
-    ThreadPool *pool = nullptr;
-    std::mutex m;
-    std::condition_variable cv;
-    int ring = 8;                 // slots in use (<= kRing)
-    int host_threads = 2;         // CABAC worker threads this session asked the process-wide pool for
-    std::map<int64_t, Packet> packets;     // by output index
-    int64_t next_out = 0, frames_in = 0, frames_done = 0;
-    std::vector<uint8_t> headers, cur_packet;
-    std::map<int64_t, std::vector<uint16_t>> recon;   // keep_recon: final pictures by index (Y,U,V concatenated)
-    mihevc_stats stats{};
-    RateControl rc;                           // rate control (csrc/ratectl.h)
-    CachedBuf probe;                          // cfg.bframes = -1: the probe's argument blocks
-    int64_t pts_step = 1, first_pts = 0;      // pts distance of the first two frames: with B pictures dts = (pts of the frame at the packet's place in decoding order) - pts_step
-    GopState gop;                             // what the GOP planner carries from chunk to chunk (csrc/gop_plan.h)
-    CachedBuf low;                                   // per chunk: 1/4-size SOURCE pictures of every picture, then the search centres of every picture (pre-search)
-    Event ev_pre{hipEventDisableTiming}, ev_args{hipEventDisableTiming};  // the chunk's centres are ready (st_pre) / the IDR step's k_intra_plan is through (compute stream: the argument blocks are on the device too)
-    CachedBuf scene;                                 // per chunk: picture pointers / pitches in, difference sums out (k_scene_diff)
-    std::vector<FrameRec> frames;             // by output index
-    struct Quality { unsigned long long sse[3]; long long ssim[3]; bool known; };
-    std::vector<Quality> quality;             // by output index (display order), written when the picture's symbols have landed (publish_picture)
-    std::atomic<long long> entropy_ns{0};
-    bool events_ok() const      // the events the session is constructed with (an Event that could not be created is empty)
-    {
-        bool ok = ev_up && ev_join && t_begin && t_end && ev_pre && ev_args;
-        for (auto &g : slot) for (auto &sl : g) ok = ok && sl.compute && sl.copy;
-        return ok;
-    }
-    // ---- one slice of a picture whose slices exchange rows (cfg.slice_halo; csrc/slice_group.h)
-    std::shared_ptr<SliceGroup> group;
-    int band = 0, n_bands = 1;
-    int band_h[kMaxBands] = {0};              // coded heights of all bands
-    long long gstep = 0;                      // steps since the session was opened: the same in every band of the group
-    Event ev_x1[2], ev_x2[2];
-    CachedBlock<uint8_t> x1_export[2];
-    size_t x1_part_bytes = 0, x1_lane_bytes = 0;
-    CachedBuf jobs;                           // row-copy job tables of a chunk (device + pinned staging)
-    std::vector<int> peers_enabled;
-    // ---- decoded picture hash (cfg.pic_hash)
-    CachedBlock<uint32_t> hash_part;          // 2 / 3: segment partials of k_pic_hash, MAX_LANES pictures (device)
-    // ---- per-picture SSIM (cfg.ssim)
-    CachedBlock<long long> ssim_part;         // region partials of k_ssim, MAX_LANES pictures (device)
-    long long ssim_total[3] = {0, 0, 0};      // sum of Q over every window of every published picture: an integer, so mihevc_stats.ssim_* does not depend on the
-                                              // order the CABAC jobs finish in (2 M windows of a 4320p picture x 2^32 x 500 000 pictures fit 63 bits)
-};
-
-namespace {
-
-// the session's one failure path: every later call returns fail_code, and the other slices of the picture stop waiting for this one
-int fail(mihevc_session *s, std::string msg)
-{
-    { std::lock_guard<std::mutex> l(s->m); s->err = std::move(msg); }
-    s->failed = true;
-    if (s->group) s->group->fail();
-    return MIHEVC_EDEVICE;
-}
-
-#define HIPCK(s, expr)                                                                    \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail((s), std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-size_t esize(const mihevc_session *s) { return s->is16 ? 2 : 1; }
 long long ssim_window_count(const mihevc_session *s, int c) { return (long long)ssim_windows_x(c ? s->w / 2 : s->w) * ssim_windows_y(c ? s->h / 2 : s->h); }
 size_t md5_pic_bytes(const mihevc_session *s) { return (size_t)s->w * s->h * 3 / 2 * esize(s); }
-
-// padded 0: a plain picture; 1: a reference picture with its PAD border all round; 2: a work picture with kSeamRows rows above and below (the rows the
-// neighbour slices hand over for deblocking across seams; unused otherwise)
-int alloc_planes(mihevc_session *s, CachedBlock<uint8_t> mem[3], void *p[3], int stride[3], int padded)
-{
-    for (int i = 0; i < 3; i++) {
-        int w = i ? s->w / 2 : s->w, h = i ? s->h / 2 : s->h, pad = padded == 1 ? (i ? PAD_C : PAD_Y) : 0, vm = padded == 2 ? (i ? kSeamRows / 2 : kSeamRows) : pad;
-        stride[i] = (w + 2 * pad + 63) & ~63;
-        HIPCK(s, mem[i].alloc(s->device, (size_t)stride[i] * (h + 2 * vm) * esize(s), false));
-        p[i] = mem[i] + ((size_t)vm * stride[i] + pad) * esize(s);
-    }
-    return 0;
-}
 
 // (a failure midway: the local lane gives back what it had taken)
 int ensure_lanes(mihevc_session *s, int n)
@@ -513,7 +320,7 @@ template <typename T> static int probe_bframes(mihevc_session *s, int n, bool &u
         for (int d = 0; d < 2; d++) {
             InterArgs<T> &a = ia[2 * k + (size_t)d];
             memset((void *)&a, 0, sizeof a);
-            const mihevc_session::Src &src = s->pending[(size_t)at[k]];
+            const Src &src = s->pending[(size_t)at[k]];
             for (int i = 0; i < 3; i++) { a.src[i] = mkc<T>(src.p[i], src.stride[i]); a.ref[i] = mkc<T>(L.rec_p[d][i], L.rec_stride[i]); }
             a.w = s->w; a.h = s->h; a.ctus_w = s->ctus_w; a.prm = P; a.me = d ? L.me1 : L.me;
         }
@@ -523,7 +330,7 @@ template <typename T> static int probe_bframes(mihevc_session *s, int n, bool &u
     const size_t es = esize(s), me_bytes = (size_t)s->n_ctu * 63 * sizeof(int32_t);
     for (size_t k = 0; k < at.size(); k++) {
         for (int d = 0; d < 2; d++) {          // the luma of the pictures one and two places back -> the reference buffers (the search reads luma only)
-            const mihevc_session::Src &r = s->pending[(size_t)(at[k] - 1 - d)];
+            const Src &r = s->pending[(size_t)(at[k] - 1 - d)];
             HIPCK(s, hipMemcpy2DAsync(L.rec_p[d][0], L.rec_stride[0] * es, r.p[0], r.stride[0] * es, s->w * es, s->h, hipMemcpyDeviceToDevice, s->st_compute));
         }
         HIPCK(s, launch_pad<T>(s->st_compute, (const SaoArgs<T> *)base, s->w, s->h, 2));
@@ -765,7 +572,7 @@ template <typename T> void build_step_args(mihevc_session *s, const Chunk<T> &c,
     const GopStep gs = c.step(g, t);
     const int fi = c.gl.gstart[(size_t)g] + gs.pos;
     mihevc_session::Lane &L = s->lane[g];
-    mihevc_session::Src &src = s->pending[fi];
+    Src &src = s->pending[fi];
     StepView<T> hv(c.ha, c.lay, t);
     const int a = c.at(t, g);
     struct { IntraArgs<T> &intra; InterArgs<T> &inter; DeblockArgs<T> &dbk_v, &dbk_h; SaoArgs<T> &sao; } A{hv.intra[a], hv.inter[a], hv.dbk_v[a], hv.dbk_h[a], hv.sao[a]};
@@ -1293,6 +1100,18 @@ int run_chunk(mihevc_session *s)
 
 }  // namespace
 
+// a source picture whose planes are filled (or on their way on st_pre): pts bookkeeping, and the chunk once it is complete
+int enqueue_source(mihevc_session *s, Src &&src, int64_t pts)
+{
+    src.pts = pts;
+    if (s->frames_in == 0) s->first_pts = pts; else if (s->frames_in == 1) s->pts_step = std::max<int64_t>(1, pts - s->first_pts);
+    s->pending.push_back(std::move(src));
+    s->frames_in++;
+    s->stats.frames_in = s->frames_in;
+    if ((int)s->pending.size() >= s->lanes * s->keyint) return run_chunk(s);
+    return MIHEVC_OK;
+}
+
 extern "C" {
 
 int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
@@ -1377,580 +1196,6 @@ int mihevc_open(const mihevc_config *cfg, int device, mihevc_session **out)
     return MIHEVC_OK;
 }
 
-// a source picture whose planes are filled (or on their way on st_pre): pts bookkeeping, and the chunk once it is complete
-static int enqueue_source(mihevc_session *s, mihevc_session::Src &&src, int64_t pts)
-{
-    src.pts = pts;
-    if (s->frames_in == 0) s->first_pts = pts; else if (s->frames_in == 1) s->pts_step = std::max<int64_t>(1, pts - s->first_pts);
-    s->pending.push_back(std::move(src));
-    s->frames_in++;
-    s->stats.frames_in = s->frames_in;
-    if ((int)s->pending.size() >= s->lanes * s->keyint) return run_chunk(s);
-    return MIHEVC_OK;
-}
-
-// the planes a source picture is written to: a set the last chunk gave back, or new ones (a failure midway: `src` gives back the planes it had taken)
-static int take_src(mihevc_session *s, mihevc_session::Src &src)
-{
-    if (!s->free_src.empty()) { src = std::move(s->free_src.back()); s->free_src.pop_back(); }
-    else if (int e = alloc_planes(s, src.mem, src.p, src.stride, 0)) return e;
-    src.borrowed = false;
-    return MIHEVC_OK;
-}
-
-// Uploads and conversions run on st_pre; the chunk's first launch waits for the event behind the last one.  wait: the synchronous entry points of host planes
-// wait here (the caller may reuse its buffers on return), the others return with the work in flight
-static int finish_ingest(mihevc_session *s, mihevc_session::Src &&src, int64_t pts, bool wait)
-{
-    if (wait) HIPCK(s, hipStreamSynchronize(s->st_pre));
-    else s->up_pending = true;
-    return enqueue_source(s, std::move(src), pts);
-}
-
-// a plane of a source on its way to a converter: row and pitch in elements
-struct SrcPlane { const void *p; int row, rows, pitch; };
-// Host planes go through the staging set: laid out one behind the other with rows that begin 16-byte aligned (the kernels' widest loads), copied on st_pre;
-// p and pitch of every plane then name its copy.  Device planes stay where they are
-static int stage_planes(mihevc_session *s, SrcPlane *pl, int n, size_t es, bool device_src)
-{
-    if (device_src) return MIHEVC_OK;
-    size_t off[3], total = 0;
-    int spitch[3];
-    for (int c = 0; c < n; c++) {
-        spitch[c] = (pl[c].row + 15) & ~15;
-        off[c] = total;
-        total += ((size_t)spitch[c] * pl[c].rows * es + 255) & ~(size_t)255;
-    }
-    if (total > s->stage.bytes()) {
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // a conversion still reading the smaller set
-        HIPCK(s, s->stage.alloc(s->device, total, false));
-    }
-    for (int c = 0; c < n; c++) {
-        HIPCK(s, hipMemcpy2DAsync(s->stage + off[c], spitch[c] * es, pl[c].p, pl[c].pitch * es, pl[c].row * es, pl[c].rows, hipMemcpyHostToDevice, s->st_pre));
-        pl[c].p = s->stage + off[c]; pl[c].pitch = spitch[c];
-    }
-    return MIHEVC_OK;
-}
-
-// may_borrow: device planes that need no margin may be coded where they are (the rule of mihevc_send_frame_device: valid until the packet is out); false: always copied,
-// so the caller's planes are free once the uploads are through (the rule of mihevc_send_frame_fmt)
-static int ingest(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async, bool may_borrow = true)
-{
-    if (!s || !y || !u || !v) return MIHEVC_EINVAL;
-    if (s->failed) return s->fail_code;
-    if (s->flushed || s->src_ring_pending || s->fm_open) return MIHEVC_ESTATE;      // (a deinterlaced or denoised frame waits for its successor: no other picture may come between; fieldmatch cycles are not interleaved)
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    mihevc_session::Src src;
-    const void *in[3] = {y, u, v};
-    const size_t es = esize(s);
-    // Device planes whose size already is the coded size (no margin to fill) are used where they are: the header's contract keeps them valid and
-    // unmodified until the picture's packet is out.  Saves three 2-D copies per frame (4 % of the device time of a 1080p clip, and most of the
-    // wall time of handing 300 frames over).
-    if (may_borrow && device_src && s->cfg.width == s->w && s->cfg.height == s->h && pitch_y >= s->w && pitch_c >= s->w / 2 &&
-        ((uintptr_t)y & 3) == 0 && ((uintptr_t)u & 3) == 0 && ((uintptr_t)v & 3) == 0 && (pitch_y * es) % 4 == 0 && (pitch_c * es) % 4 == 0) {
-        for (int i = 0; i < 3; i++) { src.p[i] = const_cast<void *>(in[i]); src.stride[i] = i ? pitch_c : pitch_y; }
-        src.borrowed = true;
-        return enqueue_source(s, std::move(src), pts);
-    }
-    if (int e = take_src(s, src)) return e;
-    for (int i = 0; i < 3; i++) {
-        int pw = i ? s->w / 2 : s->w, ph = i ? s->h / 2 : s->h;               // coded plane size
-        int sw = i ? s->cfg.width / 2 : s->cfg.width, sh = i ? s->cfg.height / 2 : s->cfg.height, pitch = i ? pitch_c : pitch_y;
-        if (pitch < sw) return MIHEVC_EINVAL;
-        HIPCK(s, hipMemcpy2DAsync(src.p[i], src.stride[i] * es, in[i], pitch * es, sw * es, sh, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
-        // replicate the last column/row into the coded-size margin (the conformance window crops it again)
-        if (pw > sw || ph > sh) {
-            if (s->is16) HIPCK(s, launch_extend_margin<uint16_t>(s->st_pre, Plane<uint16_t>{(uint16_t *)src.p[i], src.stride[i]}, sw, sh, pw, ph));
-            else HIPCK(s, launch_extend_margin<uint8_t>(s->st_pre, Plane<uint8_t>{(uint8_t *)src.p[i], src.stride[i]}, sw, sh, pw, ph));
-        }
-    }
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// A source in another layout (mihevc_send_frame_fmt; the arguments are checked): k_ingest writes the session's own planes, margin included, from the
-// caller's device planes or from their copies in the staging set
-static int ingest_fmt(mihevc_session *s, const mihevc_src_format &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
-{
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    const size_t es = f.bit_depth > 8 ? 2 : 1;
-    const int W = s->cfg.width, H = s->cfg.height, crow = src_chroma_row(f, W), crows = src_chroma_rows(f, H);
-    SrcPlane pl[3] = {{y, W, H, pitch_y}, {u, crow, crows, pitch_c}, {v, crow, crows, pitch_c}};
-    if (int e = stage_planes(s, pl, f.semi_planar ? 2 : 3, es, device_src)) return e;
-    const IngestArgs a = ingest_args(f, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
-    HIPCK(s, launch_ingest(s->st_pre, a, es == 2, s->is16));
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// An RGB source (mihevc_send_frame_rgb; the arguments are checked, matrix and range resolved): as ingest_fmt, with k_ingest_rgb
-static int ingest_rgb(mihevc_session *s, const mihevc_rgb_format &f, int matrix, bool full, const void *const *p, int pitch, int64_t pts, bool device_src, bool async)
-{
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    const size_t es = (size_t)rgb_elem_size(f);
-    const int W = s->cfg.width, H = s->cfg.height, row = rgb_row_elems(f, W);
-    SrcPlane pl[3] = {{p[0], row, H, pitch}, {p[1], row, H, pitch}, {p[2], row, H, pitch}};
-    if (int e = stage_planes(s, pl, rgb_planes(f), es, device_src)) return e;
-    const IngestRgbArgs a = ingest_rgb_args(f, matrix, full, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
-    HIPCK(s, launch_ingest_rgb(s->st_pre, a, f.sample, (int)es, s->is16));
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// A source through the colour table (mihevc_send_frame_lut3d; the arguments are checked, a table is set): as ingest_fmt, with k_lut3d
-static int ingest_lut3d(mihevc_session *s, const mihevc_lut3d_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
-{
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    const size_t es = f.bit_depth > 8 ? 2 : 1;
-    const int W = s->cfg.width, H = s->cfg.height;
-    SrcPlane pl[3] = {{y, W, H, pitch_y}, {u, W / 2, H / 2, pitch_c}, {v, W / 2, H / 2, pitch_c}};
-    if (int e = stage_planes(s, pl, 3, es, device_src)) return e;
-    const Lut3dArgs a = lut3d_args(f, s->lut_n, s->lut_dev.get(), pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, W, H, s->w, s->h, s->cfg.bit_depth, s->cfg.matrix,
-                                   s->cfg.full_range != 0, src.p, src.stride);
-    HIPCK(s, launch_lut3d(s->st_pre, a, es == 2, s->is16));
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// A smaller R'G'B' source through the network (mihevc_send_frame_sr; the arguments are checked, a model is set): k_sr_input, the launches of the model, then
-// k_ingest_rgb over the three half planes the last layer wrote.  Everything on st_pre.  An arena the device cannot hold: MIHEVC_ENOMEM, nothing launched, the
-// session as it was
-static int ingest_sr(mihevc_session *s, const mihevc_rgb_format &f, int matrix, bool full, int sw, int sh, const void *const *p, int pitch, int64_t pts, bool device_src, bool async)
-{
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    const SrNet &net = *s->sr_net;
-    const int fct = net.scale == 2 ? 2 : 1, tw = sw / fct, th = sh / fct, W = s->cfg.width, H = s->cfg.height;
-    size_t off[SR_BUFS];
-    const size_t bytes = sr_arena_layout(tw, th, off);
-    if (tw != s->sr_tw || th != s->sr_th) {
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still working in the arena of the last size
-        s->sr_tw = s->sr_th = 0;
-        if (s->sr_arena.alloc(s->device, bytes, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
-        s->sr_tw = tw; s->sr_th = th;
-    }
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    const size_t es = (size_t)rgb_elem_size(f);
-    const int row = rgb_row_elems(f, sw);
-    SrcPlane pl[3] = {{p[0], row, sh, pitch}, {p[1], row, sh, pitch}, {p[2], row, sh, pitch}};
-    if (int e = stage_planes(s, pl, rgb_planes(f), es, device_src)) return e;
-    const void *sp[3] = {pl[0].p, pl[1].p, pl[2].p};
-    uint8_t *arena = s->sr_arena;
-    HIPCK(s, launch_sr_input(s->st_pre, sr_input_args(f, net.scale, sw, sh, sp, pl[0].pitch, (uint16_t *)(arena + off[SR_X])), f.sample, (int)es));
-    HIPCK(s, launch_sr_network(s->st_pre, net, arena, (const uint16_t *)s->sr_wdev.get(), (const float *)(s->sr_wdev.get() + s->sr_bias_off), tw, th));
-    const mihevc_rgb_format planes = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
-    const uint16_t *o = (const uint16_t *)(arena + off[SR_OUT]);
-    const IngestRgbArgs a = ingest_rgb_args(planes, matrix, full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride);
-    HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// A source of another size (mihevc_send_frame_scaled; the arguments are checked): k_scale writes the session's own planes, margin included, from the caller's
-// device planes or from their copies in the staging set.  The tables of a new source size are built before the first device call
-static int ingest_scaled(mihevc_session *s, const mihevc_scale_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
-{
-    const int W = s->cfg.width, H = s->cfg.height;
-    const bool fresh = s->scale_sw != f.width || s->scale_sh != f.height;
-    ScaleBlock blk;
-    if (fresh && !scale_block_build(f.width, f.height, W, H, SC_TH, SC_ROWS, blk)) return MIHEVC_EINVAL;
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    if (fresh) {
-        s->scale_sw = s->scale_sh = 0;
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // a launch still reading the tables of the size before
-        HIPCK(s, s->scale_tab.alloc(s->device, blk.bytes.size(), false));
-        s->scale_host = std::move(blk);
-        HIPCK(s, hipMemcpyAsync(s->scale_tab, s->scale_host.bytes.data(), s->scale_host.bytes.size(), hipMemcpyHostToDevice, s->st_pre));
-        s->scale_sw = f.width; s->scale_sh = f.height;
-    }
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    const size_t es = f.bit_depth > 8 ? 2 : 1;
-    SrcPlane pl[3] = {{y, f.width, f.height, pitch_y}, {u, f.width / 2, f.height / 2, pitch_c}, {v, f.width / 2, f.height / 2, pitch_c}};
-    if (int e = stage_planes(s, pl, 3, es, device_src)) return e;
-    const int32_t *first[4];
-    const int16_t *coef[4];
-    for (int k = 0; k < 4; k++) { first[k] = (const int32_t *)(s->scale_tab + s->scale_host.first[k]); coef[k] = (const int16_t *)(s->scale_tab + s->scale_host.coef[k]); }
-    const ScaleArgs a = scale_args(f.bit_depth, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, f.width, f.height, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride,
-                                   first, coef, s->scale_host.taps);
-    HIPCK(s, launch_scale(s->st_pre, a, es == 2, s->is16));
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// A smaller source (mihevc_send_frame_upscaled; the arguments are checked): as ingest_scaled, with k_upscale and the session's own block of its tables
-static int ingest_upscaled(mihevc_session *s, const mihevc_upscale_src &f, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
-{
-    const int W = s->cfg.width, H = s->cfg.height;
-    const bool fresh = s->upscale_sw != f.width || s->upscale_sh != f.height;
-    UpscaleBlock blk;
-    if (fresh && !upscale_block_build(f.width, f.height, W, H, UP_TH, UP_HALO, UP_ROWS, blk)) return MIHEVC_EINVAL;
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    if (fresh) {
-        s->upscale_sw = s->upscale_sh = 0;
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // a launch still reading the tables of the size before
-        HIPCK(s, s->upscale_tab.alloc(s->device, blk.bytes.size(), false));
-        s->upscale_host = std::move(blk);
-        HIPCK(s, hipMemcpyAsync(s->upscale_tab, s->upscale_host.bytes.data(), s->upscale_host.bytes.size(), hipMemcpyHostToDevice, s->st_pre));
-        s->upscale_sw = f.width; s->upscale_sh = f.height;
-    }
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    const size_t es = f.bit_depth > 8 ? 2 : 1;
-    SrcPlane pl[3] = {{y, f.width, f.height, pitch_y}, {u, f.width / 2, f.height / 2, pitch_c}, {v, f.width / 2, f.height / 2, pitch_c}};
-    if (int e = stage_planes(s, pl, 3, es, device_src)) return e;
-    const int32_t *first[4], *near[4];
-    const int16_t *coef[4];
-    for (int k = 0; k < 4; k++) {
-        first[k] = (const int32_t *)(s->upscale_tab + s->upscale_host.first[k]); near[k] = (const int32_t *)(s->upscale_tab + s->upscale_host.near[k]);
-        coef[k] = (const int16_t *)(s->upscale_tab + s->upscale_host.coef[k]);
-    }
-    const UpscaleArgs a = upscale_args(f, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, W, H, s->w, s->h, s->cfg.bit_depth, src.p, src.stride, first, near, coef);
-    HIPCK(s, launch_upscale(s->st_pre, a, es == 2, s->is16));
-    return finish_ingest(s, std::move(src), pts, !device_src && !async);
-}
-
-// The picture(s) of frame k of the ring (mihevc_send_frame_deint, mihevc_send_frame_denoise): P = frame k - 1 (the first frame: itself), C = frame k, N = frame k + 1
-// (has_next; the last frame: itself).  k_deint / k_denoise / k_mcfi_render write the session's own planes, margin included, out of the ring.  Deinterlacing: frame-rate mode
-// keeps the first field's rows, field-rate mode follows with the second field's picture at pts + 1.  Denoising: one picture, with the strengths frame k came with.
-// Interpolation (mihevc_send_frame_interpolate): the vectors of the pair (C, N), then `factor` pictures at pts + j; the last frame: its own picture only
-static int ring_emit(mihevc_session *s, int64_t k, bool has_next, bool wait)
-{
-    s->src_ring_pending = false;
-    void *const *C = s->src_ring_p[k % 3], *const *P = s->src_ring_p[(k > 0 ? k - 1 : k) % 3], *const *N = s->src_ring_p[(has_next ? k + 1 : k) % 3];
-    const bool denoise = s->src_ring_kind == mihevc_session::RING_DENOISE;
-    if (s->src_ring_kind == mihevc_session::RING_MCFI) {      // the pictures between C and N; the last frame: itself (picture 0 of a blend with any N)
-        mihevc_interpolate m = s->mcfi_pending;
-        if (!has_next) m.mode = 1;
-        const int W = s->cfg.width, H = s->cfg.height;
-        const McfiLayout l = mcfi_layout(W, H);
-        uint8_t *const blk = s->mcfi_dev.get();
-        if (m.mode == 0) {
-            const McfiSearchArgs a = mcfi_search_args(s->cfg.bit_depth, C[0], N[0], s->src_ring_pitch[0], W, H, blk);
-            HIPCK(s, launch_mcfi_vectors(s->st_pre, a, mcfi_field_args(a, blk), s->is16));
-        }
-        for (int j = 0; j < (has_next ? m.factor : 1); j++) {
-            mihevc_session::Src src;
-            if (int e = take_src(s, src)) return e;
-            const McfiRenderArgs a = mcfi_render_args(m, j, s->cfg.bit_depth, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], W, H, s->w, s->h, (const int16_t *)(blk + l.v),
-                                                      (const unsigned long long *)(blk + l.dsum), src.p, src.stride);
-            HIPCK(s, launch_mcfi_render(s->st_pre, a, s->is16));
-            if (int e = finish_ingest(s, std::move(src), s->src_ring_pts + j, wait)) return e;
-        }
-        return MIHEVC_OK;
-    }
-    const int first = s->deint_tff ? 0 : 1;
-    for (int f = 0; f <= (denoise ? 0 : s->deint_field_rate); f++) {
-        mihevc_session::Src src;
-        if (int e = take_src(s, src)) return e;
-        if (denoise) {
-            const DenoiseArgs a = denoise_args(s->denoise_pending, s->cfg.bit_depth, P, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], s->cfg.width, s->cfg.height, s->w, s->h,
-                                               src.p, src.stride);
-            HIPCK(s, launch_denoise(s->st_pre, a, s->is16));
-        } else {
-            const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], s->cfg.width, s->cfg.height, s->w, s->h, f ? 1 - first : first, f,
-                                           src.p, src.stride);
-            HIPCK(s, launch_deint(s->st_pre, a, s->is16));
-        }
-        if (int e = finish_ingest(s, std::move(src), s->src_ring_pts + f, wait)) return e;
-    }
-    return MIHEVC_OK;
-}
-
-// decimate: the held pictures go on in order, all but the one at `drop` (-1: a partial cycle comes out whole), whose planes go back to free_src
-static int fm_release(mihevc_session *s, int drop, bool wait)
-{
-    auto held = std::move(s->fm_held);
-    s->fm_held.clear();
-    int e = MIHEVC_OK;
-    for (size_t i = 0; i < held.size(); i++) {
-        const bool dropped = (int)i == drop;
-        {
-            std::lock_guard<std::mutex> l(s->m);
-            auto &f = s->fm_frames[(size_t)held[i].second];
-            f.info.dropped = dropped; f.info.picture = dropped || e ? -1 : s->fm_pictures; f.decided = true;
-        }
-        if (dropped || e) { s->free_src.push_back(std::move(held[i].first)); continue; }
-        e = finish_ingest(s, std::move(held[i].first), s->fm_first_pts + s->fm_pictures++, wait);
-    }
-    return e;
-}
-
-// Frame k of the ring is decided (mihevc_send_frame_fieldmatch): P, C, N as ring_emit.  The metrics of the frame are taken on st_pre and copied to
-// pinned memory behind ev_fm; the host waits for that event only, plans (csrc/fieldmatch_plan.h) and launches the weave, or the deinterlacer, into a Src.
-// Without decimate the picture goes on with its frame's pts; with it the picture is held until its cycle's fifth frame is decided
-static int fm_decide(mihevc_session *s, int64_t k, bool has_next, bool wait)
-{
-    s->src_ring_pending = false;
-    void *const *C = s->src_ring_p[k % 3], *const *P = s->src_ring_p[(k > 0 ? k - 1 : k) % 3], *const *N = s->src_ring_p[(has_next ? k + 1 : k) % 3];
-    const int W = s->cfg.width, H = s->cfg.height, keep = s->fm_mode.tff ? 0 : 1;
-    const size_t nwg = (size_t)fm_workgroups(W, H);
-    unsigned long long *const part = (unsigned long long *)s->fm_dev.get(), *const host = (unsigned long long *)s->fm_host.get();
-    HIPCK(s, launch_fm_metrics(s->st_pre, fm_args(s->cfg.bit_depth, P[0], C[0], N[0], s->src_ring_pitch[0], W, H, keep, part), part + nwg * 8, s->is16));
-    HIPCK(s, hipMemcpyAsync(host, part + nwg * 8, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st_pre));
-    HIPCK(s, hipEventRecord(s->ev_fm, s->st_pre));
-    HIPCK(s, hipEventSynchronize(s->ev_fm));
-    FmMetrics m = fm_metrics_of(host);
-    if (k == 0) fm_first_frame(m);
-    const int match = fm_match(m);
-    const bool fallback = fm_falls_back(m, match, s->fm_mode.deint != 0);
-    mihevc_session::Src src;
-    if (int e = take_src(s, src)) return e;
-    if (fallback) {
-        const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, s->src_ring_pitch[0], s->src_ring_pitch[1], W, H, s->w, s->h, keep, 0, src.p, src.stride);
-        HIPCK(s, launch_deint(s->st_pre, a, s->is16));
-    } else {
-        void *const *X = match == 0 ? C : match == 1 ? P : N;
-        const DeintArgs a = deint_args(s->cfg.bit_depth, X, C, X, s->src_ring_pitch[0], s->src_ring_pitch[1], W, H, s->w, s->h, keep, 0, src.p, src.stride);
-        HIPCK(s, launch_fm_weave(s->st_pre, a, s->is16));
-    }
-    mihevc_fm_frame info = {};
-    for (int i = 0; i < 3; i++) { info.comb_sum[i] = m.comb_sum[i]; info.comb_block[i] = m.comb_block[i]; }
-    info.dup_sum = m.dup_sum; info.dup_block = m.dup_block; info.match = match; info.deinterlaced = fallback; info.dropped = 0;
-    info.picture = s->fm_mode.decimate ? -1 : s->fm_pictures;
-    {
-        std::lock_guard<std::mutex> l(s->m);
-        s->fm_frames[(size_t)k] = {info, !s->fm_mode.decimate};
-    }
-    if (!s->fm_mode.decimate) { s->fm_pictures++; return finish_ingest(s, std::move(src), s->src_ring_pts, wait); }
-    s->fm_held.emplace_back(std::move(src), k);
-    if ((int)s->fm_held.size() < kFmCycle) return MIHEVC_OK;
-    FmMetrics cycle[kFmCycle] = {};
-    for (int i = 0; i < kFmCycle; i++) {
-        const mihevc_fm_frame &f = s->fm_frames[(size_t)s->fm_held[(size_t)i].second].info;
-        cycle[i].dup_sum = f.dup_sum; cycle[i].dup_block = f.dup_block;
-    }
-    return fm_release(s, fm_drop(cycle), wait);
-}
-
-// A frame of kind `kind` (mihevc_send_frame_deint, mihevc_send_frame_denoise; the arguments are checked): into its slot of the ring, then the picture(s) of the frame
-// before it.  Returns with src_ring_pts still that of the frame before: the caller sets what belongs to the new frame
-static int ingest_ring(mihevc_session *s, int kind, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, bool device_src, bool async)
-{
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    const size_t es = esize(s);
-    const int W = s->cfg.width, H = s->cfg.height;
-    if (!s->src_ring[0]) {
-        s->src_ring_pitch[0] = (W + 15) & ~15; s->src_ring_pitch[1] = s->src_ring_pitch[2] = (W / 2 + 15) & ~15;
-        const size_t by = ((size_t)s->src_ring_pitch[0] * H * es + 255) & ~(size_t)255, bc = ((size_t)s->src_ring_pitch[1] * (H / 2) * es + 255) & ~(size_t)255;
-        for (int k = 0; k < 3; k++) {
-            HIPCK(s, s->src_ring[k].alloc(s->device, by + 2 * bc, false));
-            s->src_ring_p[k][0] = s->src_ring[k]; s->src_ring_p[k][1] = s->src_ring[k] + by; s->src_ring_p[k][2] = s->src_ring[k] + by + bc;
-        }
-        s->src_ring_kind = kind;
-    }
-    const int64_t k = s->src_ring_n;
-    const void *in[3] = {y, u, v};
-    for (int c = 0; c < 3; c++)
-        HIPCK(s, hipMemcpy2DAsync(s->src_ring_p[k % 3][c], s->src_ring_pitch[c] * es, in[c], (c ? pitch_c : pitch_y) * es, (c ? W / 2 : W) * es, c ? H / 2 : H,
-                                  device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
-    s->src_ring_n = k + 1;
-    const bool wait = !device_src && !async;
-    int e = MIHEVC_OK;
-    if (k > 0) e = kind == mihevc_session::RING_FIELDMATCH ? fm_decide(s, k - 1, true, wait) : ring_emit(s, k - 1, true, wait);      // (src_ring_pts and denoise_pending are still those of frame k - 1)
-    else if (wait) HIPCK(s, hipStreamSynchronize(s->st_pre));
-    else s->up_pending = true;
-    s->src_ring_pts = pts;
-    s->src_ring_pending = true;
-    return e;
-}
-
-int mihevc_send_frame(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
-{
-    return ingest(s, y, u, v, pitch_y, pitch_c, pts, false, false);
-}
-int mihevc_send_frame_async(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
-{
-    return ingest(s, y, u, v, pitch_y, pitch_c, pts, false, true);
-}
-int mihevc_send_frame_device(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts)
-{
-    return ingest(s, y, u, v, pitch_y, pitch_c, pts, true, false);
-}
-int mihevc_send_frames_device(mihevc_session *s, int n, const void *const *y, const void *const *u, const void *const *v, int pitch_y, int pitch_c, int64_t first_pts)
-{
-    if (!s || n < 0 || (n && (!y || !u || !v))) return MIHEVC_EINVAL;
-    for (int i = 0; i < n; i++)
-        if (int e = ingest(s, y[i], u[i], v[i], pitch_y, pitch_c, first_pts + i, true, false)) return e;
-    return MIHEVC_OK;
-}
-// What the converting entries refuse, in the order in which the errors win.  args_ok: the entry's own checks of its arguments
-static int refuse_source(const mihevc_session *s, bool args_ok, int flags, int kind = mihevc_session::RING_NONE)
-{
-    if (!args_ok || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
-    if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
-    if (s->failed) return s->fail_code;
-    if (s->fm_open && kind != mihevc_session::RING_FIELDMATCH) return MIHEVC_ESTATE;      // (from the first fieldmatch frame until flush)
-    return s->flushed || (s->src_ring_pending && s->src_ring_kind != kind) ? MIHEVC_ESTATE : MIHEVC_OK;
-}
-int mihevc_send_frame_fmt(mihevc_session *s, const mihevc_src_format *fmt, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && src_format_ok(fmt) && y && u && (v || fmt->semi_planar) && pitch_y >= s->cfg.width && pitch_c >= src_chroma_row(*fmt, s->cfg.width);
-    if (int e = refuse_source(s, args_ok, flags)) return e;
-    const bool device_src = (flags & MIHEVC_SRC_DEVICE) != 0, async = (flags & MIHEVC_SRC_ASYNC) != 0;
-    // the session's own layout: the existing route, copy and margin fill.  Device planes are copied too, never borrowed: this entry point lets the caller have
-    // them back after mihevc_sync_uploads, whatever the format
-    if (fmt->chroma == 420 && !fmt->semi_planar && fmt->bit_depth == s->cfg.bit_depth && !fmt->msb_aligned)
-        return ingest(s, y, u, v, pitch_y, pitch_c, pts, device_src, async, false);
-    return ingest_fmt(s, *fmt, y, u, v, pitch_y, pitch_c, pts, device_src, async);
-}
-int mihevc_send_frame_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, const void *p0, const void *p1, const void *p2, int pitch, int64_t pts, int flags)
-{
-    const void *p[3] = {p0, p1, p2};
-    const bool fmt_ok = s && rgb_format_ok(fmt);
-    const int matrix = !fmt_ok ? 0 : fmt->matrix ? fmt->matrix : s->cfg.matrix;
-    if (int e = refuse_source(s, fmt_ok && rgb_matrix_ok(matrix) && rgb_planes_ok(*fmt, p, pitch, s->cfg.width), flags)) return e;
-    const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
-    return ingest_rgb(s, *fmt, matrix, full, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_set_lut3d(mihevc_session *s, int n, const uint16_t *table)
-{
-    if (!s || s->cfg.slice_count > 1 || (table && !lut3d_n_ok(n))) return MIHEVC_EINVAL;
-    if (s->failed) return s->fail_code;
-    if (!table) { s->lut_n = 0; return MIHEVC_OK; }
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    const size_t cap = ((size_t)LUT_MAX_N * LUT_MAX_N * LUT_MAX_N * LUT_ENTRY_BYTES + 255) & ~(size_t)255;
-    const int k = (int)(s->lut_sets & 1);
-    if (!s->lut_dev) HIPCK(s, s->lut_dev.alloc(s->device, cap, false));
-    if (!s->lut_host[k]) {
-        s->ev_lut[k] = Event(hipEventDisableTiming);
-        if (!s->ev_lut[k]) return fail(s, "mihevc_set_lut3d: no event");
-        HIPCK(s, s->lut_host[k].alloc(s->device, cap, true));
-    } else HIPCK(s, hipEventSynchronize(s->ev_lut[k]));      // the copy of the table before the last one
-    lut3d_pack(n, table, (uint16_t *)s->lut_host[k].get());
-    HIPCK(s, hipMemcpyAsync(s->lut_dev, s->lut_host[k], (size_t)n * n * n * LUT_ENTRY_BYTES, hipMemcpyHostToDevice, s->st_pre));
-    HIPCK(s, hipEventRecord(s->ev_lut[k], s->st_pre));
-    s->lut_n = n; s->lut_sets++;
-    return MIHEVC_OK;
-}
-int mihevc_send_frame_lut3d(mihevc_session *s, const mihevc_lut3d_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && lut3d_src_ok(src) && s->lut_n && rgb_matrix_ok(s->cfg.matrix) && lut3d_planes_ok(*src, y, u, v, pitch_y, pitch_c, s->cfg.width);
-    if (int e = refuse_source(s, args_ok, flags)) return e;
-    return ingest_lut3d(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_send_frame_scaled(mihevc_session *s, const mihevc_scale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && scale_src_ok(src) && y && u && v && scale_geometry_ok(src->width, src->height, s->cfg.width, s->cfg.height) &&
-                         pitch_y >= src->width && pitch_c >= src->width / 2;
-    if (int e = refuse_source(s, args_ok, flags)) return e;
-    return ingest_scaled(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && upscale_src_ok(src) && y && u && v && upscale_geometry_ok(src->width, src->height, s->cfg.width, s->cfg.height) &&
-                         pitch_y >= src->width && pitch_c >= src->width / 2;
-    if (int e = refuse_source(s, args_ok, flags)) return e;
-    return ingest_upscaled(s, *src, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const float *weights, size_t count)
-{
-    if (!s || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
-    if (!model) {
-        if (s->failed) return s->fail_code;
-        s->sr_net.reset();
-        return MIHEVC_OK;
-    }
-    if (!sr_model_ok(model) || !weights || count != sr_net_count(model->scale, model->blocks)) return MIHEVC_EINVAL;
-    if (s->failed) return s->fail_code;
-    std::unique_ptr<SrNet> net(new SrNet);
-    if (!sr_net_build(model->scale, model->blocks, weights, count, *net)) return MIHEVC_EINVAL;
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    const size_t wbytes = (net->wpk.size() * sizeof(uint16_t) + 255) & ~(size_t)255, total = wbytes + net->bias.size() * sizeof(float);
-    const int k = (int)(s->sr_sets & 1);
-    if (s->sr_wdev.bytes() != total) {
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still reading the block of the last model
-        s->sr_net.reset();
-        if (s->sr_wdev.alloc(s->device, total, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
-    }
-    if (!s->ev_sr[k]) {
-        s->ev_sr[k] = Event(hipEventDisableTiming);
-        if (!s->ev_sr[k]) return fail(s, "mihevc_set_sr_model: no event");
-    } else HIPCK(s, hipEventSynchronize(s->ev_sr[k]));      // the copy of the model before the last one
-    if (s->sr_whost[k].bytes() != total) HIPCK(s, s->sr_whost[k].alloc(s->device, total, true));
-    memcpy(s->sr_whost[k].get(), net->wpk.data(), net->wpk.size() * sizeof(uint16_t));
-    memcpy(s->sr_whost[k].get() + wbytes, net->bias.data(), net->bias.size() * sizeof(float));
-    HIPCK(s, hipMemcpyAsync(s->sr_wdev, s->sr_whost[k], total, hipMemcpyHostToDevice, s->st_pre));
-    HIPCK(s, hipEventRecord(s->ev_sr[k], s->st_pre));
-    net->wpk = std::vector<uint16_t>();      // the launches need the shapes and the list, not the host copy of the weights
-    s->sr_bias_off = wbytes; s->sr_sets++;
-    s->sr_net = std::move(net);
-    return MIHEVC_OK;
-}
-int mihevc_send_frame_sr(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch,
-                         int64_t pts, int flags)
-{
-    const void *p[3] = {p0, p1, p2};
-    const bool fmt_ok = s && rgb_format_ok(fmt);
-    const int matrix = !fmt_ok ? 0 : fmt->matrix ? fmt->matrix : s->cfg.matrix;
-    const bool args_ok = fmt_ok && rgb_matrix_ok(matrix) && s->sr_net && sr_geometry_ok(s->sr_net->scale, src_width, src_height) &&
-                         s->cfg.width == s->sr_net->scale * src_width && s->cfg.height == s->sr_net->scale * src_height && rgb_planes_ok(*fmt, p, pitch, src_width);
-    if (int e = refuse_source(s, args_ok, flags)) return e;
-    const bool full = fmt->range ? fmt->range == 2 : s->cfg.full_range != 0;
-    return ingest_sr(s, *fmt, matrix, full, src_width, src_height, p, pitch, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_send_frame_deint(mihevc_session *s, const mihevc_deint *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && deint_mode_ok(d) && y && u && v && (s->src_ring_kind != mihevc_session::RING_DEINT || (d->tff == s->deint_tff && d->field_rate == s->deint_field_rate)) &&
-                         deint_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width && pitch_c >= s->cfg.width / 2;
-    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_DEINT)) return e;
-    if (s->src_ring_kind == mihevc_session::RING_NONE) { s->deint_tff = d->tff; s->deint_field_rate = d->field_rate; }
-    return ingest_ring(s, mihevc_session::RING_DEINT, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_send_frame_denoise(mihevc_session *s, const mihevc_denoise *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && denoise_strength_ok(d) && y && u && v && denoise_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width &&
-                         pitch_c >= s->cfg.width / 2;
-    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_DENOISE)) return e;
-    const int e = ingest_ring(s, mihevc_session::RING_DENOISE, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-    s->denoise_pending = *d;      // (the picture of the frame before has been launched with its own)
-    return e;
-}
-int mihevc_send_frame_interpolate(mihevc_session *s, const mihevc_interpolate *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && mcfi_mode_ok(d) && y && u && v &&
-                         (s->src_ring_kind != mihevc_session::RING_MCFI || (d->factor == s->mcfi_pending.factor && d->mode == s->mcfi_pending.mode)) &&
-                         mcfi_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width && pitch_c >= s->cfg.width / 2;
-    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_MCFI)) return e;
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    if (!s->mcfi_dev) {
-        HIPCK(s, s->mcfi_dev.alloc(s->device, (mcfi_layout(s->cfg.width, s->cfg.height).bytes + 255) & ~(size_t)255, false));
-        s->mcfi_pending = *d;
-    }
-    const int e = ingest_ring(s, mihevc_session::RING_MCFI, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-    s->mcfi_pending.scene_threshold = d->scene_threshold;      // (the pictures of the frame before have been launched with its own)
-    return e;
-}
-int mihevc_send_frame_fieldmatch(mihevc_session *s, const mihevc_fieldmatch *d, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
-{
-    const bool args_ok = s && fieldmatch_mode_ok(d) && y && u && v &&
-                         (!s->fm_open || (d->tff == s->fm_mode.tff && d->decimate == s->fm_mode.decimate && d->deint == s->fm_mode.deint)) &&
-                         deint_geometry_ok(s->cfg.width, s->cfg.height) && pitch_y >= s->cfg.width && pitch_c >= s->cfg.width / 2;
-    if (int e = refuse_source(s, args_ok, flags, mihevc_session::RING_FIELDMATCH)) return e;
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    if (!s->fm_open) {
-        const size_t bytes = ((size_t)fm_workgroups(s->cfg.width, s->cfg.height) + 1) * 8 * sizeof(unsigned long long);
-        if (!s->ev_fm) s->ev_fm = Event(hipEventDisableTiming);
-        if (!s->ev_fm) return fail(s, "mihevc_send_frame_fieldmatch: no event");
-        HIPCK(s, s->fm_dev.alloc(s->device, (bytes + 255) & ~(size_t)255, false));
-        HIPCK(s, s->fm_host.alloc(s->device, 256, true));
-        s->fm_mode = *d; s->fm_first_pts = pts; s->fm_open = true;
-    }
-    {
-        std::lock_guard<std::mutex> l(s->m);
-        s->fm_frames.push_back({{}, false});
-    }
-    return ingest_ring(s, mihevc_session::RING_FIELDMATCH, y, u, v, pitch_y, pitch_c, pts, (flags & MIHEVC_SRC_DEVICE) != 0, (flags & MIHEVC_SRC_ASYNC) != 0);
-}
-int mihevc_get_fieldmatch_info(mihevc_session *s, int64_t frame, mihevc_fm_frame *out)
-{
-    if (!s || !out) return MIHEVC_EINVAL;
-    std::lock_guard<std::mutex> l(s->m);
-    if (frame < 0 || (size_t)frame >= s->fm_frames.size()) return MIHEVC_EINVAL;
-    if (!s->fm_frames[(size_t)frame].decided) return MIHEVC_EAGAIN;
-    *out = s->fm_frames[(size_t)frame].info;
-    return MIHEVC_OK;
-}
 int mihevc_sync_uploads(mihevc_session *s)
 {
     if (!s) return MIHEVC_EINVAL;
@@ -1966,13 +1211,7 @@ int mihevc_flush(mihevc_session *s)
     if (!s) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
     if (s->flushed) return MIHEVC_OK;
-    if (s->src_ring_pending) {      // the last frame of the ring: its successor is itself
-        if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-        if (s->src_ring_kind == mihevc_session::RING_FIELDMATCH) {      // and what is left of an open cycle comes out whole
-            if (int e = fm_decide(s, s->src_ring_n - 1, false, false)) return e;
-            if (int e = fm_release(s, -1, false)) return e;
-        } else if (int e = ring_emit(s, s->src_ring_n - 1, false, false)) return e;
-    }
+    if (int e = source_flush(s)) return e;      // the last frame of a ring: its successor is itself
     s->flushing = true;
     int e = run_chunk(s);
     s->flushed = true;
