@@ -192,11 +192,11 @@ class IntraPlanModel:
         return (sse << 4) + ((lambda_q4 * bits) >> 4), sse, bits
 
     # ---------------------------------------------------------------- the plan
-    def plan(self, qp, qp_c, lambda_sad_q4, lambda_q4, chroma_modes=1, detail=None):
+    def plan(self, qp, qp_c, lambda_sad_q4, lambda_q4, chroma_modes=1, detail=None, only=None):
         """-> one PLAN_DTYPE record per CTU in raster order.  detail: a list that receives, per CTU, a dict node -> (luma costs[35], chroma costs[5] or
-        None, J, SSE, bits) of the nodes inside the picture."""
+        None, J, SSE, bits) of the nodes inside the picture.  only: the CTUs to plan (the plan of a CTU depends on no other CTU); the others stay zero."""
         out = np.zeros(self.wc * self.hc, PLAN_DTYPE)
-        for ctu in range(self.wc * self.hc):
+        for ctu in range(self.wc * self.hc) if only is None else sorted(only):
             x0, y0 = ctu % self.wc * CTU, ctu // self.wc * CTU
             valid = [x0 + x + n <= self.w and y0 + y + n <= self.h for x, y, n in NODES]
             mode, cmode, J, info = {}, {}, {}, {}

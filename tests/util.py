@@ -669,6 +669,130 @@ def check_records_carry_the_plan(plan, cu, w, h, nxn):
     assert seen.all(), "a CU record outside every chosen leaf"
 
 
+# ================================================================ cases of the intra code audit: the code stage, the NxN trial and the intra second pass of P pictures
+# (tests/test_intra_code_independent.py on the CPU, tests/test_gpu_intra_code_independent.py on the device; the model is tests/hevc_intra_code.py)
+# An I case is a case of the plan audit (its picture, QP, bit depth, chroma_modes, tile grid and lambdas; the model's own plan is what the model codes) + intra_nxn.
+CodeCase = namedtuple("CodeCase", "id plan nxn sign_hide", defaults=(0,))
+# A P case: content "patched" = a translation by (3, 1) of the reference with four pasted 64x32 patches, two of unrelated content and two of the reference's own content
+# from 60 samples away (where they fit the picture: they are cut at its edges), in CTU rows 0 and 2 and CTU columns 0-1 and 3-4, so that isolated candidates and pairs
+# fill both rounds; "noise" = two patches of white noise, which intra prediction codes no better than the search does; "occluded" = tests/test_bitstream_cpu.py's clip,
+# one connected patch, most of whose CTUs are never tried; "unrelated" = a picture against a black reference: every CTU is a candidate.
+PCodeCase = namedtuple("PCodeCase", "id w h bd qp nxn rdo_zero content seed tiles mc sign_hide", defaults=((1, 1), (0, 0), 0))
+
+
+def _code_cases():
+    out = []
+    for c in PLAN_CASES:
+        if c.lam is not None or c.content.startswith(("line", "drawn")):
+            continue
+        if c.content == "synth" and c.tiles == (1, 1):                         # the matrix: 3 sizes x 2 bit depths x 3 QPs x chroma_modes 0 / 1, x intra_nxn 0 / 1
+            out += [CodeCase(f"{c.id}-nxn{nxn}", c, nxn) for nxn in (0, 1)]
+        else:                                                                  # rails at QP 45 (both depths), the two tile grids, the fan picture
+            out += [CodeCase(f"{c.id}-nxn{nxn}", c, nxn) for nxn in ((0, 1) if c.content == "rails" or c.w == 136 else (1,))]
+    # low QP and lambda_q4 = 0: J is 16 SSE alone and most CUs rebuild their source exactly both ways, so J_nxn == J_2Nx2N occurs and the 2Nx2N coding must stay
+    out.append(CodeCase("jtie-64x64-8bit-qp4-lam0-nxn1", PlanCase("64x64-8bit-qp4-lam0", 64, 64, 8, 4, 1, "synth", (1, 1), (10, 0)), 1))
+    out.append(CodeCase("jtie-72x104-10bit-qp4-lam0-nxn1", PlanCase("72x104-10bit-qp4-lam0", 72, 104, 10, 4, 1, "synth", (1, 1), (40, 0)), 1))
+    assert len({c.id for c in out}) == len(out)
+    return out
+
+
+CODE_CASES = _code_cases()
+# sign data hiding: the oracle has none and the device entries take none, so these run against the stepped kernels only
+CODE_SIGN_HIDE_CASES = [CodeCase("sdh-136x72-8bit-qp22-cm1-nxn1", next(c for c in PLAN_CASES if c.id == "136x72-8bit-qp22-cm1"), 1, 1),
+                        CodeCase("sdh-72x104-10bit-qp32-cm1-nxn1", next(c for c in PLAN_CASES if c.id == "72x104-10bit-qp32-cm1"), 1, 1)]
+# the device file's share: 64x64 and 136x72, both bit depths, QP 22 / 42, chroma modes and NxN on; the tiled cases; the J ties
+GPU_CODE_CASES = [c for c in CODE_CASES if c.nxn and ((c.plan.content == "synth" and c.plan.tiles == (1, 1) and c.plan.lam is None and (c.plan.w, c.plan.h) in ((64, 64), (136, 72)) and
+                                                       c.plan.qp in (22, 42) and c.plan.chroma_modes) or c.plan.tiles != (1, 1) or c.plan.lam is not None)]
+
+
+def _p_code_cases():
+    out, i = [], 0
+    for (w, h) in ((136, 72), (72, 104)):
+        for bd in (8, 10):
+            for nxn in (0, 1):
+                for rz in (0, 1):
+                    content = ("patched", "occluded", "patched", "noise")[i % 4] if (i // 4) % 2 == 0 else ("occluded", "patched", "noise", "patched")[i % 4]
+                    qp = (27, 24, 32, 37)[(i + i // 4) % 4]
+                    out.append(PCodeCase(f"{content}-{w}x{h}-{bd}bit-qp{qp}-nxn{nxn}-rz{rz}", w, h, bd, qp, nxn, rz, content, 1 + i))
+                    i += 1
+    out.append(PCodeCase("patched-136x104-8bit-qp24-nxn1-rz1-tiles2x2", 136, 104, 8, 24, 1, 1, "patched", 30, (2, 2)))
+    out.append(PCodeCase("patched-136x72-10bit-qp27-nxn1-rz1-slice11", 136, 72, 10, 27, 1, 1, "patched", 31, (1, 1), (1, 1)))
+    out.append(PCodeCase("unrelated-136x72-8bit-qp27-nxn1-rz1", 136, 72, 8, 27, 1, 1, "unrelated", 32))
+    assert len({c.id for c in out}) == len(out)
+    return out
+
+
+P_CODE_CASES = _p_code_cases()
+P_CODE_SIGN_HIDE_CASES = [PCodeCase("sdh-patched-136x72-8bit-qp24-nxn1-rz1", 136, 72, 8, 24, 1, 1, "patched", 40, sign_hide=1),
+                          PCodeCase("sdh-patched-72x104-10bit-qp27-nxn1-rz0", 72, 104, 10, 27, 1, 0, "patched", 41, sign_hide=1)]
+GPU_P_CODE_CASES = [c for c in P_CODE_CASES if c.id in ("patched-136x72-8bit-qp27-nxn0-rz0", "patched-136x72-10bit-qp27-nxn1-rz1", "patched-136x104-8bit-qp24-nxn1-rz1-tiles2x2",
+                                                        "noise-136x72-8bit-qp37-nxn1-rz1")]
+assert len(GPU_P_CODE_CASES) == 4
+
+
+@functools.lru_cache(maxsize=None)
+def p_code_case_pictures(c):
+    """(current picture, reference picture)"""
+    if c.content == "occluded":
+        from tests.test_bitstream_cpu import occluded_clip
+        srcs = occluded_clip(c.w, c.h, c.bd)
+        return srcs[1 + c.seed % 2], srcs[0]
+    ref = crop(c.w, c.h, c.bd, 0, 0)
+    if c.content == "unrelated":                                 # against a black reference the inter cost holds the DC term that the activity leaves out: every CTU is a candidate
+        return synth_frame(c.h, c.w, seed=900 + c.seed, bit_depth=c.bd), O.Frame(*[np.zeros_like(p) for p in planes3(ref)])
+    cur = crop(c.w, c.h, c.bd, 3, 1)
+    other, far = synth_frame(c.h, c.w, seed=900 + c.seed, bit_depth=c.bd), crop(c.w, c.h, c.bd, 60, -45)
+    rng = np.random.default_rng(c.seed)
+    noise = O.Frame(*[rng.integers(0, 1 << c.bd, p.shape) for p in planes3(cur)])
+    boxes = ((0, 0, noise), (96, 0, noise)) if c.content == "noise" else ((0, 0, other), (96, 0, far), (0, 64, far), (96, 64, other))
+    for x, y, s in boxes:
+        for p, q, sh in ((cur.y, s.y, 0), (cur.u, s.u, 1), (cur.v, s.v, 1)):
+            p[y >> sh:(y + 32) >> sh, x >> sh:(x + 64) >> sh] = q[y >> sh:(y + 32) >> sh, x >> sh:(x + 64) >> sh]
+    return cur, ref
+
+
+def model_params(cp, sign_hide=0):
+    """the cost parameters as the model takes them: the product's fields + sign_hide (which the stepped entries take as an argument of its own)"""
+    import types
+    return types.SimpleNamespace(sign_hide=sign_hide, **{f: int(getattr(cp, f)) for f, _ in cp._fields_})
+
+
+CODE_COVERAGE = collections.Counter()                            # what the MODEL reached over CODE_CASES and P_CODE_CASES, each counted once (the wants are kept)
+
+
+def code_case_params(c):
+    """(oracle parameters, product parameters) of an I case"""
+    _, prm0, cp0 = plan_case_want(c.plan)
+    prm, cp = type(prm0).from_buffer_copy(prm0), type(cp0).from_buffer_copy(cp0)
+    prm.intra_nxn = cp.intra_nxn = c.nxn
+    return prm, cp
+
+
+@functools.lru_cache(maxsize=None)
+def code_case_want(c, list_from_plan=False):
+    """the model's Result of an I case: computed once.  list_from_plan: the binding test's switch (not counted in CODE_COVERAGE)"""
+    from tests import hevc_intra_code as M
+    plan = plan_case_want(c.plan)[0]
+    _, cp = code_case_params(c)
+    src = plan_case_source(c.plan.content, c.plan.w, c.plan.h, c.plan.bd)
+    counted = c in CODE_CASES and not list_from_plan                 # the sign-hiding cases, their plain twins and the binding test's runs are not counted
+    return M.code_picture(planes3(src), plan, model_params(cp, c.sign_hide), cov=CODE_COVERAGE if counted else None, list_from_plan=list_from_plan)
+
+
+def p_code_case_params(c):
+    return params_pair(c.qp, c.bd, 8, intra_in_p=1, intra_nxn=c.nxn, chroma_modes=1, rdo_zero=c.rdo_zero, tile_cols=c.tiles[0], tile_rows=c.tiles[1], mc_top=c.mc[0], mc_bottom=c.mc[1])
+
+
+@functools.lru_cache(maxsize=None)
+def p_code_case_want(c, list_from_plan=False, activity_with_dc=False):
+    from tests import hevc_intra_code as M
+    _, cp = p_code_case_params(c)
+    cur, ref = p_code_case_pictures(c)
+    counted = c in P_CODE_CASES and not list_from_plan and not activity_with_dc
+    return M.second_pass(planes3(cur), planes3(ref), model_params(cp, c.sign_hide), cov=CODE_COVERAGE if counted else None,
+                         list_from_plan=list_from_plan, activity_with_dc=activity_with_dc)
+
+
 # ================================================================ cases of the inter CTU program's audit (tests/test_inter_cu_independent.py on the CPU, tests/test_gpu_inter_cu_independent.py on the device)
 # content: "crop" = the search audit's pure translation by `shift`; "flat"; "warpG" = every G x G block of the current picture is the reference predicted at a
 # quarter-sample vector of its own through the standard's filter (tests/hevc_recon.py), + noise of +-`noise`; B pictures ("b-..."): the blocks are predicted from
