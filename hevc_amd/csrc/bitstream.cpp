@@ -698,11 +698,10 @@ public:
 
 private:
     const mihevc_cu_rec &cu(int x, int y) const { return pic_.cu[(y >> 3) * w8_ + (x >> 3)]; }
-    static int zorder6(int bx, int by)
+    static int zorder6(int bx, int by)      // bits of bx and by (0..7) interleaved: every availability test asks twice
     {
-        int z = 0;
-        for (int i = 0; i < 3; i++) z |= ((bx >> i) & 1) << (2 * i) | ((by >> i) & 1) << (2 * i + 1);
-        return z;
+        static const uint8_t spread[8] = {0, 1, 4, 5, 16, 17, 20, 21};
+        return spread[bx] | (spread[by] << 1);
     }
     int zaddr(int x, int y) const { return (((y >> kCtuLog2) * wc_ + (x >> kCtuLog2)) << 6) | zorder6((x & 31) >> 2, (y & 31) >> 2); }
     bool avail(int xc, int yc, int xn, int yn) const   // 6.4.1: earlier in decoding order and in the same tile
@@ -1110,52 +1109,48 @@ private:
                 infer_dc = true;
             } else csbf[ys][xs] = 1;
             if (!csbf[ys][xs]) continue;
-            int prev = right + 2 * below;
+            // sig_coeff_flag contexts (9.3.4.2.5): inside a sub-block they depend on the position alone, through one of five patterns (the 4x4 TU's own map, or
+            // the neighbouring sub-blocks' flags), plus an offset that is the same for the whole sub-block; the DC of the TU has context 0
+            static const uint8_t pat[5][16] = {     // [4x4 TU, or prevCsbf + 1][(y << 2) | x]
+                {0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8, 8},
+                {2, 1, 1, 0, 1, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0},
+                {2, 2, 2, 2, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0},
+                {2, 1, 0, 0, 2, 1, 0, 0, 2, 1, 0, 0, 2, 1, 0, 0},
+                {2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2}};
+            const uint8_t *sig_pat = pat[log2n == 2 ? 0 : 1 + right + 2 * below];
+            const int sig_off = kSig + (c_idx ? 27 : 0) +
+                                (log2n == 2 ? 0 : c_idx == 0 ? ((xs || ys) ? 3 : 0) + (log2n == 3 ? (scan == 0 ? 9 : 15) : 21) : (log2n == 3 ? 9 : 12));
             for (int k = (i == last_sb ? last_pos - 1 : 15); k >= 0; k--) {
                 if (k == 0 && infer_dc) break;          // DC of a coded sub-block with no other coefficient: inferred 1
-                int xp = pscan[k][0], yp = pscan[k][1], xc = (xs << 2) + xp, yc = (ys << 2) + yp, sc;
-                if (log2n == 2) { static const uint8_t m[16] = {0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8, 8}; sc = m[(yc << 2) + xc]; }
-                else if (xc + yc == 0) sc = 0;
-                else {
-                    if (prev == 0) sc = (xp + yp == 0) ? 2 : (xp + yp < 3) ? 1 : 0;
-                    else if (prev == 1) sc = yp == 0 ? 2 : yp == 1 ? 1 : 0;
-                    else if (prev == 2) sc = xp == 0 ? 2 : xp == 1 ? 1 : 0;
-                    else sc = 2;
-                    if (c_idx == 0) { if (xs || ys) sc += 3; sc += log2n == 3 ? (scan == 0 ? 9 : 15) : 21; }
-                    else sc += log2n == 3 ? 9 : 12;
-                }
-                cabac_.bin(kSig + (c_idx ? 27 + sc : sc), lev[k] != 0);
+                const int ctx = (k == 0 && i == 0 && log2n != 2) ? kSig + (c_idx ? 27 : 0) : sig_off + sig_pat[(pscan[k][1] << 2) | pscan[k][0]];
+                cabac_.bin(ctx, lev[k] != 0);
                 if (lev[k]) infer_dc = false;
             }
             if (!nsig) continue;   // only possible for i == 0 (coded_sub_block_flag inferred 1, all sig flags 0)
             int ctx_set = (i > 0 && c_idx == 0) ? 2 : 0;
             if (c1_carry == 0) ctx_set++;
-            int c1 = 1, ng1 = 0, g2_pos = -1;
-            for (int k = 15; k >= 0; k--) {
-                if (!lev[k]) continue;
-                if (ng1 == 8) break;
-                int g1 = std::abs(lev[k]) > 1;
+            // the sub-block's levels in coding order (last scan position first), gathered once: the three passes below run over them, not over 16 positions
+            int av[16], ns = 0;
+            uint32_t signs = 0;
+            for (int k = 15; k >= 0; k--) if (lev[k]) { av[ns++] = std::abs(lev[k]); signs = (signs << 1) | (uint32_t)(lev[k] < 0); }
+            int c1 = 1, g2_at = -1;
+            for (int j = 0; j < ns && j < 8; j++) {
+                int g1 = av[j] > 1;
                 cabac_.bin(kG1 + ctx_set * 4 + c1 + (c_idx ? 16 : 0), g1);
-                ng1++;
-                if (g1) { c1 = 0; if (g2_pos < 0) g2_pos = k; }
+                if (g1) { c1 = 0; if (g2_at < 0) g2_at = j; }
                 else if (c1 > 0 && c1 < 3) c1++;
             }
             c1_carry = c1;
-            if (g2_pos >= 0) cabac_.bin(kG2 + ctx_set + (c_idx ? 4 : 0), std::abs(lev[g2_pos]) > 2);
-            uint32_t signs = 0; int ns = 0;
-            for (int k = 15; k >= 0; k--) if (lev[k]) { signs = (signs << 1) | (uint32_t)(lev[k] < 0); ns++; }
-            if (hidden) { signs >>= 1; ns--; }      // the first level's sign is the last one gathered
-            cabac_.bypass_bits(signs, ns);
-            int num = 0, rice = 0;
-            for (int k = 15; k >= 0; k--) {
-                if (!lev[k]) continue;
-                int a = std::abs(lev[k]);
-                int base = num < 8 ? (k == g2_pos ? 3 : 2) : 1;
+            if (g2_at >= 0) cabac_.bin(kG2 + ctx_set + (c_idx ? 4 : 0), av[g2_at] > 2);
+            if (hidden) cabac_.bypass_bits(signs >> 1, ns - 1);      // the first level's sign is the last one gathered
+            else cabac_.bypass_bits(signs, ns);
+            int rice = 0;
+            for (int j = 0; j < ns; j++) {
+                const int a = av[j], base = j < 8 ? (j == g2_at ? 3 : 2) : 1;
                 if (a >= base) {
                     remaining(a - base, rice);
                     if (a > 3 * (1 << rice)) rice = std::min(rice + 1, 4);
                 }
-                num++;
             }
         }
     }

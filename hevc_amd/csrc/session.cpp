@@ -681,15 +681,21 @@ int slice_sums(mihevc_session *s, const std::vector<size_t> &idx, bool with_est)
     return 0;
 }
 
-// the rate estimates the analyses of `lanes` left in ring slot `slot` (device symbol blocks), summed over the slices of the picture
-int lane_estimates(mihevc_session *s, const SymLayout &sl, int slot, const std::vector<int> &lanes, std::vector<unsigned long long> &out)
+// The rate estimates the analyses of `lanes` leave in ring slot `slot` (device symbol blocks), in two halves.  queue_estimates goes right behind the launches
+// that produce them: one 8-byte copy per lane on the compute stream into the session's pinned words.  wait_estimates is the ONE wait of the host for the
+// compute stream (a blocking copy per lane was a round trip per lane, behind a synchronise of its own), then the words, summed over the slices of the picture
+int queue_estimates(mihevc_session *s, const SymLayout &sl, int slot, const std::vector<int> &lanes)
 {
-    std::vector<double> v(lanes.size(), 0.0);
-    for (size_t k = 0; k < lanes.size(); k++) {
-        unsigned long long e = 0;
-        HIPCK(s, hipMemcpy(&e, s->lane[lanes[k]].sym_dev[slot] + sl.est, sizeof e, hipMemcpyDeviceToHost));
-        v[k] = (double)e;
-    }
+    if (!s->est_host) HIPCK(s, s->est_host.alloc(s->device, MAX_LANES * sizeof(unsigned long long), true));
+    for (size_t k = 0; k < lanes.size(); k++)
+        HIPCK(s, hipMemcpyAsync(s->est_host + k, s->lane[lanes[k]].sym_dev[slot] + sl.est, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st_compute));
+    return 0;
+}
+int wait_estimates(mihevc_session *s, size_t n, std::vector<unsigned long long> &out)
+{
+    HIPCK(s, hipStreamSynchronize(s->st_compute));
+    std::vector<double> v(n, 0.0);
+    for (size_t k = 0; k < n; k++) v[k] = (double)s->est_host[k];
     if (int e = group_sum(s, v)) return e;
     out.assign(v.begin(), v.end());
     return 0;
@@ -736,24 +742,34 @@ template <typename T> int rate_feedback(mihevc_session *s, const Chunk<T> &c, co
 // First chunk of a session: rho is only a prior (1/16).  Measure it: analyse every GOP's first P picture once against the UNFILTERED reconstruction of
 // the IDR analysis (copied + padded into the reference buffer the real step 0 overwrites afterwards) at the wanted IDR QP + 3, and read the estimate.
 // Costs one P step per session.  The trial runs in the block behind the chunk's last step.
-template <typename T> int rho_trial(mihevc_session *s, const Chunk<T> &c, const std::vector<int> &want, const std::vector<unsigned long long> &ev, const std::vector<int> &qa)
+// Its first half is everything that does not depend on the wanted QPs: it runs while the device is still busy with the IDR analyses whose estimates decide them
+template <typename T> int rho_trial_prepare(mihevc_session *s, const Chunk<T> &c)
 {
     const int B1 = c.gl.batch[1], tb = c.steps;
     memcpy(c.ha + (size_t)tb * c.lay.total, c.ha + (size_t)1 * c.lay.total, c.lay.total);
-    StepView<T> tv(c.ha, c.lay, tb), dtv(c.da, c.lay, tb), h0(c.ha, c.lay, 0), h1(c.ha, c.lay, 1);
-    std::vector<int> qp_trial((size_t)B1);
+    StepView<T> tv(c.ha, c.lay, tb), h0(c.ha, c.lay, 0), h1(c.ha, c.lay, 1);
     for (int g = 0; g < B1; g++) {
         mihevc_session::Lane &L = s->lane[g];
         const int a = c.at(1, g);      // the trial block is a copy of step 1's: its order
-        qp_trial[(size_t)g] = RateControl::trial_qp(want[(size_t)g]);
         tv.sao[a] = h0.sao[c.at(0, g)];
         tv.sao[a].sao = nullptr; tv.sao[a].sse = nullptr; tv.sao[a].sse_ctu = nullptr; tv.sao[a].cu = nullptr;
         tv.sao[a].halo_top = tv.sao[a].halo_bottom = 0;      // the trial predicts from this band's own unfiltered picture with a replicated border
         tv.inter[a] = h1.inter[a];
         for (int i = 0; i < 3; i++) tv.inter[a].rec[i] = mk<T>(L.rec_p[1][i], L.rec_stride[i]);
-        tv.inter[a].prm = prm_for(s, qp_trial[(size_t)g]);
         tv.inter[a].ip = nullptr;
         HIPCK(s, hipMemsetAsync(L.sym_dev[c.slot_of(1)] + c.sl.sse, 0, 4 * sizeof(unsigned long long), s->st_compute));
+    }
+    return 0;
+}
+// the second half: the trial QPs into the prepared block, the launches, one wait for the estimates
+template <typename T> int rho_trial(mihevc_session *s, const Chunk<T> &c, const std::vector<int> &want, const std::vector<unsigned long long> &ev, const std::vector<int> &qa)
+{
+    const int B1 = c.gl.batch[1], tb = c.steps;
+    StepView<T> tv(c.ha, c.lay, tb), dtv(c.da, c.lay, tb);
+    std::vector<int> qp_trial((size_t)B1);
+    for (int g = 0; g < B1; g++) {
+        qp_trial[(size_t)g] = RateControl::trial_qp(want[(size_t)g]);
+        tv.inter[c.at(1, g)].prm = prm_for(s, qp_trial[(size_t)g]);
     }
     HIPCK(s, hipMemcpyAsync(c.da + (size_t)tb * c.lay.total, c.ha + (size_t)tb * c.lay.total, c.lay.total, hipMemcpyHostToDevice, s->st_compute));
     HIPCK(s, launch_sao<T>(s->st_compute, dtv.sao, s->w, s->h, B1, false));
@@ -761,9 +777,9 @@ template <typename T> int rho_trial(mihevc_session *s, const Chunk<T> &c, const 
     if (s->cfg.pre_search) HIPCK(s, hipStreamWaitEvent(s->st_compute, s->ev_pre, 0));      // the chunk's search centres
     HIPCK(s, launch_me_search<T>(s->st_compute, dtv.inter, s->n_ctu, B1, s->me_range));
     HIPCK(s, launch_inter_ctu<T>(s->st_compute, dtv.inter, s->n_ctu, B1, s->me_range));
-    HIPCK(s, hipStreamSynchronize(s->st_compute));
+    if (int e = queue_estimates(s, c.sl, c.slot_of(1), first_lanes(B1))) return e;
     std::vector<unsigned long long> ep;
-    if (int e = lane_estimates(s, c.sl, c.slot_of(1), first_lanes(B1), ep)) return e;
+    if (int e = wait_estimates(s, (size_t)B1, ep)) return e;
     s->rc.measure_rho(ep, qp_trial, ev, qa);
     return 0;
 }
@@ -777,6 +793,7 @@ template <typename T> int idr_step(mihevc_session *s, const Chunk<T> &c, std::ve
     HIPCK(s, hipMemcpyAsync(c.da, c.ha, c.lay.total, hipMemcpyHostToDevice, s->st_compute));
     for (int g = 0; g < B; g++) HIPCK(s, hipMemsetAsync(s->lane[g].sym_dev[0] + c.sl.sse, 0, 4 * sizeof(unsigned long long), s->st_compute));
     STAGE(s->st_compute, 0, B, launch_intra_picture<T>(s->st_compute, dv.intra, s->ctus_w, s->ctus_h, B, s->tiles.cols, s->tiles.rows, s->cfg.pre_search ? s->ev_args : nullptr));
+    if (s->rc.rc_on) { if (int e = queue_estimates(s, c.sl, 0, first_lanes(B))) return e; }
     // cfg.pre_search: the search centres of EVERY picture of the chunk come from the 1/4-size SOURCE pictures (this picture against the one before it: nothing
     // in it waits for a reconstruction), in two launches on a stream of their own: the work (7 % of a clip's device time when it ran inside every step) sits
     // beside the anti-diagonal chain, which leaves most of the device idle, not beside k_intra_plan (both want the ALUs).  The first P step waits for ev_pre.
@@ -786,13 +803,15 @@ template <typename T> int idr_step(mihevc_session *s, const Chunk<T> &c, std::ve
         HIPCK(s, hipEventRecord(s->ev_pre, s->st_pre));
     }
     if (!s->rc.rc_on) return 0;
-    HIPCK(s, hipStreamSynchronize(s->st_compute));
+    // the host's part of step 0 that needs no estimate runs beside the analyses; the device stands still from the wait below until the next launch
+    const bool trial = !s->rc.rho_measured && c.steps > 1 && c.gl.batch[1] > 0;
+    if (trial) { if (int e = rho_trial_prepare<T>(s, c)) return e; }
     std::vector<unsigned long long> ev, e2;
-    if (int e = lane_estimates(s, c.sl, 0, first_lanes(B), ev)) return e;
+    if (int e = wait_estimates(s, (size_t)B, ev)) return e;
     const std::vector<int> qa(qp_step);                       // QP each lane's current analysis was made at
     std::vector<int> want((size_t)B);
     for (int g = 0; g < B; g++) want[(size_t)g] = s->rc.want_idr(g, ev[(size_t)g], qa[(size_t)g]);
-    if (!s->rc.rho_measured && c.steps > 1 && c.gl.batch[1] > 0) {
+    if (trial) {
         if (int e = rho_trial<T>(s, c, want, ev, qa)) return e;
         for (int g = 0; g < B; g++) want[(size_t)g] = s->rc.want_idr(g, ev[(size_t)g], qa[(size_t)g]);
     }
@@ -811,8 +830,8 @@ template <typename T> int idr_step(mihevc_session *s, const Chunk<T> &c, std::ve
         }
         HIPCK(s, hipMemcpyAsync(c.da, c.ha, c.lay.total, hipMemcpyHostToDevice, s->st_compute));
         STAGE(s->st_compute, 0, (int)redo.size(), launch_intra_picture<T>(s->st_compute, dv.intra + B, s->ctus_w, s->ctus_h, (int)redo.size(), s->tiles.cols, s->tiles.rows, nullptr));
-        HIPCK(s, hipStreamSynchronize(s->st_compute));
-        if (int e = lane_estimates(s, c.sl, 0, redo, e2)) return e;
+        if (int e = queue_estimates(s, c.sl, 0, redo)) return e;
+        if (int e = wait_estimates(s, redo.size(), e2)) return e;
         for (size_t k = 0; k < redo.size(); k++) ev[(size_t)redo[k]] = e2[k];
     }
     s->rc.idr_settled(qp_step);
@@ -1230,6 +1249,7 @@ int mihevc_abort(mihevc_session *s)
 int mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size, int64_t *pts, int64_t *dts, int *keyframe)
 {
     if (!s || !data || !size) return MIHEVC_EINVAL;
+    s->cur_batch.clear();
     std::unique_lock<std::mutex> l(s->m);
     auto it = s->packets.find(s->next_out);
     if (it == s->packets.end() || !it->second.ready) return (s->flushed && s->next_out >= s->frames_in) ? MIHEVC_EOF : MIHEVC_EAGAIN;
@@ -1244,6 +1264,34 @@ int mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
     *data = s->cur_packet.data();
     *size = s->cur_packet.size();
     return MIHEVC_OK;
+}
+
+// mihevc_receive_packet up to `max` times under one lock: the packets move out of the map into cur_batch, which owns them until the next receive call
+int mihevc_receive_packets(mihevc_session *s, int max, const uint8_t **data, size_t *size, int64_t *pts, int64_t *dts, int *keyframe)
+{
+    if (!s || max <= 0 || !data || !size) return MIHEVC_EINVAL;
+    s->cur_batch.clear();
+    std::unique_lock<std::mutex> l(s->m);
+    int n = 0;
+    auto it = s->packets.find(s->next_out);
+    while (n < max && it != s->packets.end() && it->first == s->next_out && it->second.ready) {
+        if (!it->second.error.empty()) {
+            if (n) break;      // the packets in front of it go out first; the next call fails as the one-packet form does
+            std::string err = it->second.error; l.unlock(); s->fail_code = MIHEVC_EINVAL; fail(s, err); return MIHEVC_EINVAL;
+        }
+        s->cur_batch.push_back(std::move(it->second.data));
+        data[n] = s->cur_batch.back().data();
+        size[n] = s->cur_batch.back().size();
+        if (pts) pts[n] = it->second.pts;
+        if (dts) dts[n] = it->second.dts;
+        if (keyframe) keyframe[n] = it->second.key;
+        it = s->packets.erase(it);
+        s->next_out++;
+        n++;
+    }
+    if (!n) return (s->flushed && s->next_out >= s->frames_in) ? MIHEVC_EOF : MIHEVC_EAGAIN;
+    s->stats.frames_out = s->next_out;
+    return n;
 }
 
 int mihevc_get_headers(mihevc_session *s, const uint8_t **data, size_t *size)

@@ -128,6 +128,7 @@ struct mihevc_session {
     };
     std::vector<Lane> lane;
     CachedBuf args;                   // argument blocks of a whole chunk (device + pinned staging)
+    CachedBlock<unsigned long long> est_host;      // step 0 under rate control: the lanes' rate estimates (MAX_LANES pinned words; session.cpp queue_estimates), taken at the first use
     // by (lane group, ring slot); step 0 (all lanes, one launch) uses group 0's slot 0.  compute: the step's pictures are final; copy: its symbols are on the
     // host; jobs_open: its CABAC jobs still running (under `m`)
     struct Slot { Event compute{hipEventDisableTiming}, copy{hipEventDisableTiming}; int jobs_open = 0; } slot[kGroups][kRing];
@@ -145,6 +146,7 @@ struct mihevc_session {
     std::map<int64_t, Packet> packets;     // by output index
     int64_t next_out = 0, frames_in = 0, frames_done = 0;
     std::vector<uint8_t> headers, cur_packet;
+    std::vector<std::vector<uint8_t>> cur_batch;      // what the last mihevc_receive_packets handed out (cur_packet: the last mihevc_receive_packet); either call releases them
     std::map<int64_t, std::vector<uint16_t>> recon;   // keep_recon: final pictures by index (Y,U,V concatenated)
     mihevc_stats stats{};
     RateControl rc;                           // rate control (csrc/ratectl.h)

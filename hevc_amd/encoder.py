@@ -105,6 +105,8 @@ class Encoder:
         if keep_recon:
             self._lib.mihevc_set_keep_recon(self._s, 1)
         self._pts = 0
+        self._arrays = None     # mihevc_receive_packets' output arrays, made at the first drain and kept
+        self._ready = []        # packets received and not yet handed on, last first
 
     # -- lifecycle
     def close(self):
@@ -470,28 +472,34 @@ class Encoder:
         if self._s:
             self._lib.mihevc_abort(self._s)
 
+    _BATCH = 512      # packets per mihevc_receive_packets call: a 300-picture clip drains in one
+
+    def _receive_batch(self) -> bool:
+        """One mihevc_receive_packets call into the arrays the Encoder keeps: the ready packets, copied out as (bytes, pts, keyframe, dts), wait in self._ready
+        (last first) until a generator hands them on, so a caller that stops iterating early finds the rest in its next packets() call.  False: nothing was ready."""
+        if self._arrays is None:
+            n = self._BATCH
+            self._arrays = ((C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_int64 * n)(), (C.c_int64 * n)(), (C.c_int * n)())
+        data, size, pts, dts, key = self._arrays
+        n = self._lib.mihevc_receive_packets(self._s, self._BATCH, data, size, pts, dts, key)
+        if n in (_lib.EAGAIN, _lib.EOF):
+            return False
+        if n < 0:
+            self._check(n, "receive_packets")
+        at = C.string_at
+        self._ready = [(at(d, s), p, k != 0, t) for d, s, p, k, t in zip(data[:n], size[:n], pts[:n], key[:n], dts[:n])][::-1]
+        return True
+
     def packets(self) -> Iterator[Tuple[bytes, int, bool]]:
         """Drain every packet that is ready: (annexb bytes, pts, keyframe)."""
-        data, size = C.POINTER(C.c_uint8)(), C.c_size_t()
-        pts, dts, key = C.c_int64(), C.c_int64(), C.c_int()
-        while True:
-            rc = self._lib.mihevc_receive_packet(self._s, C.byref(data), C.byref(size), C.byref(pts), C.byref(dts), C.byref(key))
-            if rc in (_lib.EAGAIN, _lib.EOF):
-                return
-            self._check(rc, "receive_packet")
-            yield C.string_at(data, size.value), pts.value, bool(key.value)
+        while self._ready or self._receive_batch():
+            yield self._ready.pop()[:3]
 
     def packets_dts(self) -> Iterator[Tuple[bytes, int, bool, int]]:
         """The same with the decoding time stamp: (annexb bytes, pts, keyframe, dts).  Packets always come in DECODING order; dts differs from pts only
         when the session codes B pictures (cfg.bframes)."""
-        data, size = C.POINTER(C.c_uint8)(), C.c_size_t()
-        pts, dts, key = C.c_int64(), C.c_int64(), C.c_int()
-        while True:
-            rc = self._lib.mihevc_receive_packet(self._s, C.byref(data), C.byref(size), C.byref(pts), C.byref(dts), C.byref(key))
-            if rc in (_lib.EAGAIN, _lib.EOF):
-                return
-            self._check(rc, "receive_packet")
-            yield C.string_at(data, size.value), pts.value, bool(key.value), dts.value
+        while self._ready or self._receive_batch():
+            yield self._ready.pop()
 
     def headers(self) -> bytes:
         data, size = C.POINTER(C.c_uint8)(), C.c_size_t()

@@ -454,6 +454,15 @@ int  mihevc_send_frame_sr(mihevc_session *s, const mihevc_rgb_format *fmt, int s
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
+/* ---- added under ABI 6: packets out in ONE call (symbols only) ----
+ * Up to `max` ready access units, in decoding order, as mihevc_receive_packet would hand them out one after the other: data[i], size[i], pts[i], dts[i] and
+ * keyframe[i] of the i-th (pts, dts and keyframe may be NULL), for a caller that drains a whole clip at a time — a host language's call overhead (ctypes: ~3.5 us
+ * per call and more per by-reference argument) is paid once, not per packet.  Returns the number of packets, at least 1; MIHEVC_EAGAIN when nothing is ready and
+ * the session is not flushed, MIHEVC_EOF when it is flushed and drained; MIHEVC_EINVAL: max <= 0, NULL data or size (the session stays usable), or the host coder
+ * refused the next picture (the session has failed, as with the one-packet form; packets in front of that picture are handed out first).  Every packet of the
+ * call stays valid until the next receive call of either kind, or close; the two calls mix in any order. */
+int  mihevc_receive_packets(mihevc_session *s, int max, const uint8_t **data, size_t *size,
+                            int64_t *pts, int64_t *dts, int *keyframe);
 int  mihevc_flush(mihevc_session *s);                /* no more input; drain with receive_packet until MIHEVC_EOF */
 /* Give the session up: it fails every later call, and if it codes one slice of a picture with slice_halo, the sessions of the other slices
  * stop waiting for it (their calls return MIHEVC_EDEVICE).  For a driver whose thread hit an error; mihevc_close is still due. */

@@ -6,6 +6,7 @@
   python tools/prof_summary.py traffic <fetch-dir> <write-dir> <out.json>          -> HBM bytes per launch per kernel
   python tools/prof_summary.py pmcjson <out.json> <dir> [...]                      -> per-kernel VALU issue share (bench.py reads it)
   python tools/prof_summary.py overlap <dir-with-*kernel_trace.csv>                -> kernels per hardware queue, and how long two queues ran kernels at once
+  python tools/prof_summary.py gaps    <dir-with-*kernel_trace.csv>                -> idle time of the compute queue around step 0's host waits, per chunk
 
 Normalisation of the SQ counters (stated because the raw numbers cannot be read without it): every value printed by `pmc` is the MEAN
 PER DISPATCH of what rocprofv3 wrote for that kernel.  On this pool rocprofv3 reports the SQ block of a subset of the shader engines
@@ -65,6 +66,45 @@ def overlap(d):
         live[q] += step
         last = t
     print(f"a kernel was running for {busy / 1e6:.3f} ms; kernels of two or more queues at once for {two / 1e6:.3f} ms ({100.0 * two / max(1, busy):.1f} %)")
+
+
+def gaps(d):
+    """Step 0 under rate control stops the device while the host reads the lanes' estimates (csrc/session.cpp idr_step, rho_trial).  On the hardware queue
+    that runs k_intra_diag, per chunk: (A) the idle time between the last k_intra_diag of the IDR analysis and the next kernel (the rho trial's first, or
+    the loop filter when there is no trial), (B) between the first k_inter_ctu behind it (the trial's) and the kernel after it (k_sao_decide of step 0, or
+    k_intra_plan when lanes are analysed again).  One line per chunk, then the medians."""
+    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
+    per_q = defaultdict(list)
+    for r in csv.DictReader(open(f)):
+        per_q[r.get("Queue_Id", "?")].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]).split("::")[-1].split("<")[0]))
+    rows = []
+    for q, raw in per_q.items():
+        raw.sort()
+        # the runtime's own fill and copy kernels (memsets, small copies) are work of the queue, not idle time: their run time comes off the gap they sit in
+        ks, fill = [], 0
+        for t0, t1, name in raw:
+            if name.startswith("__amd_rocclr"):
+                fill += t1 - t0
+            else:
+                ks.append((t0, t1, name, fill)); fill = 0
+        idle = lambda i: ks[i][0] - ks[i - 1][1] - ks[i][3]      # in front of kernel i
+        state, a = 0, None      # 0: outside; 1: inside a run of k_intra_diag; 2: behind it, waiting for the first k_inter_ctu
+        for i, (t0, t1, name, _) in enumerate(ks):
+            if name == "k_intra_diag":
+                state = 1
+            elif state == 1:
+                a, state = (idle(i), name), 2
+                if name != "k_sao_apply":      # no trial behind this analysis (a later chunk of a session, or the second analysis): one wait, or none
+                    rows.append((q, a, None)); state = 0
+            elif state == 2 and name == "k_inter_ctu" and i + 1 < len(ks):
+                rows.append((q, a, (idle(i + 1), ks[i + 1][2])))
+                state = 0
+    for q, a, b in rows:
+        print(f"queue {q}: k_intra_diag -> {a[1]:14s} {a[0] / 1e3:8.1f} us" + (f"    k_inter_ctu -> {b[1]:14s} {b[0] / 1e3:8.1f} us" if b else ""))
+    med = lambda v: sorted(v)[len(v) // 2] / 1e3 if v else float("nan")
+    trial = [(a, b) for _, a, b in rows if b]
+    print(f"median over {len(trial)} trials: A {med([a[0] for a, _ in trial]):.1f} us, B {med([b[0] for _, b in trial]):.1f} us; "
+          f"behind the {len(rows) - len(trial)} other analyses {med([a[0] for _, a, b in rows if not b]):.1f} us")
 
 
 def pmc_means(d):
@@ -155,6 +195,8 @@ if __name__ == "__main__":
         stats(sys.argv[2])
     elif cmd == "overlap":
         overlap(sys.argv[2])
+    elif cmd == "gaps":
+        gaps(sys.argv[2])
     elif cmd == "pmc":
         pmc(sys.argv[2:])
     elif cmd == "traffic":
