@@ -190,6 +190,14 @@ class SrModel(C.Structure):
         return f"SrModel(scale={self.scale}, blocks={self.blocks})"
 
 
+class SrYuv(C.Structure):
+    """mihevc_sr_yuv: size, depth, matrix and range of the planar 4:2:0 Y'CbCr frames handed to mihevc_send_frame_sr_yuv / mihevc_k_sr_from_yuv"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bit_depth", "matrix", "full_range")] + [("reserved", C.c_int32 * 3)]
+
+    def __repr__(self):
+        return f"SrYuv(width={self.width}, height={self.height}, bit_depth={self.bit_depth}, matrix={self.matrix}, full_range={self.full_range})"
+
+
 class SrConvDesc(C.Structure):
     """mihevc_sr_conv_desc: one launch of k_sr_conv as mihevc_k_sr_conv takes it"""
     _fields_ = ([(n, C.c_int32) for n in ("width", "height", "up", "planar", "act", "n_res", "in_ch", "in_off", "cin", "cin_real", "out_ch", "out_off", "cout",
@@ -258,6 +266,7 @@ EXPORTS = (
     "mihevc_send_frame_interpolate", "mihevc_k_mcfi_vectors", "mihevc_k_mcfi_render",
     "mihevc_send_frame_upscaled", "mihevc_k_upscale_source",
     "mihevc_set_sr_model", "mihevc_send_frame_sr", "mihevc_k_sr_conv", "mihevc_k_sr_input", "mihevc_k_sr_network",
+    "mihevc_send_frame_sr_yuv", "mihevc_send_frame_sr_fit", "mihevc_k_sr_from_yuv",
 )
 
 _lib = None
@@ -351,6 +360,9 @@ def load() -> C.CDLL:
     lib.mihevc_k_sr_conv.argtypes = [i32, C.POINTER(SrConvDesc), vp, vp, vp, vp, vp, vp]
     lib.mihevc_k_sr_input.argtypes = [i32, C.POINTER(RgbFormat), i32, i32, i32, vp, vp, vp, i32, vp]
     lib.mihevc_k_sr_network.argtypes = [i32, C.POINTER(SrModel), vp, C.c_size_t, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, vp]
+    lib.mihevc_send_frame_sr_yuv.argtypes = [vp, C.POINTER(SrYuv), vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_send_frame_sr_fit.argtypes = [vp, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, i64, i32]
+    lib.mihevc_k_sr_from_yuv.argtypes = [i32, C.POINTER(SrYuv), i32, vp, vp, vp, i32, i32, vp]
     _lib = lib
     return lib
 

@@ -18,6 +18,7 @@
 #include "kernels/mcfi.h"
 #include "kernels/pichash.h"
 #include "kernels/scale.h"
+#include "kernels/sr_yuv.h"
 #include "kernels/ssim.h"
 #include "kernels/upscale.h"
 #include "sr_net.h"
@@ -93,6 +94,8 @@ hipError_t launch_sr_conv(hipStream_t st, const SrConvArgs &a, int cin, int cout
 hipError_t launch_sr_input(hipStream_t st, const SrInputArgs &a, int sample, int elem_size);
 // every launch of `net` (sr_net.h) over an arena and packed weights in device memory; the input tensor of tw x th pixels is in the arena's X
 hipError_t launch_sr_network(hipStream_t st, const SrNet &net, uint8_t *arena, const uint16_t *wpk, const float *bias, int tw, int th);
+// a planar 4:2:0 Y'CbCr source -> the input tensor (kernels/sr_yuv.h).  in16: the source's elements are uint16
+hipError_t launch_sr_from_yuv(hipStream_t st, const SrYuvArgs &a, bool in16);
 // deinterlacing source (kernels/deint.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth
 hipError_t launch_deint(hipStream_t st, const DeintArgs &a, bool is16);
 // denoising source (kernels/denoise.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth

@@ -397,6 +397,19 @@ hipError_t launch_sr_network(hipStream_t st, const SrNet &net, uint8_t *arena, c
     });
     return err;
 }
+// a Y'CbCr source in front of the network (kernels/sr_yuv.h): NT blocks of 2 x 2 luma samples per workgroup, one a lane
+template <typename TI> __global__ __launch_bounds__(NT) void k_sr_from_yuv(const SrYuvArgs a)
+{
+    GpuExec ex;
+    sr_from_yuv_program<TI>(ex, a, (int)blockIdx.x);
+}
+hipError_t launch_sr_from_yuv(hipStream_t st, const SrYuvArgs &a, bool in16)
+{
+    const dim3 grid((unsigned)sr_yuv_workgroups(a.sw, a.sh)), block(NT);
+    if (in16) hipLaunchKernelGGL((k_sr_from_yuv<uint16_t>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_sr_from_yuv<uint8_t>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
 
 // RGB source conversion (kernels/ingest_rgb.h): one workgroup per tile of RGB_TW x RGB_TH source pixels, which writes its luma and both chroma tiles
 template <typename TI, bool FLT, typename TO> __global__ __launch_bounds__(NT) void k_ingest_rgb(const IngestRgbArgs a)
@@ -1330,6 +1343,19 @@ int stage_sr(const mihevc_rgb_format &f, int scale, const SrNet *net, int sw, in
     else CK(hipMemcpy(out, arena.as<uint8_t>() + off[SR_X], (size_t)tw * th * SR_CIN0 * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return MIHEVC_OK;
 }
+// the Y'CbCr input kernel alone
+int stage_sr_from_yuv(const mihevc_sr_yuv &f, int scale, const void *const *src, int pitch_y, int pitch_c, uint16_t *out)
+{
+    const size_t es = f.bit_depth > 8 ? 2 : 1, halves = (size_t)f.width * f.height * SR_CIN0 / (scale == 2 ? 4 : 1);
+    DevBuf din[3], dout;
+    const void *dsrc[3];
+    if (int e = upload_yuv420(din, dsrc, src, f.width, f.height, pitch_y, pitch_c, es)) return e;
+    CK(dout.alloc(halves * sizeof(uint16_t)));
+    CK(launch_sr_from_yuv(0, sr_yuv_args(f, scale, dsrc[0], dsrc[1], dsrc[2], pitch_y, pitch_c, dout.as<uint16_t>()), es == 2));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, halves * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
 
 // the deinterlacing kernel alone
 template <typename T>
@@ -1783,6 +1809,14 @@ int mihevc_k_sr_network(int device, const mihevc_sr_model *model, const float *w
     if (!sr_net_build(model->scale, model->blocks, weights, count, net)) return MIHEVC_EINVAL;
     if (int e = select_device(device)) return e;
     return stage_sr(*fmt, model->scale, &net, src_width, src_height, src, pitch, out);
+}
+
+int mihevc_k_sr_from_yuv(int device, const mihevc_sr_yuv *src, int scale, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, uint16_t *out)
+{
+    if (!sr_yuv_src_ok(src) || (scale != 2 && scale != 4) || !out || !sr_yuv_planes_ok(*src, y, u, v, pitch_y, pitch_c)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    const void *p[3] = {y, u, v};
+    return stage_sr_from_yuv(*src, scale, p, pitch_y, pitch_c, out);
 }
 
 #ifdef MIHEVC_PHASE_PROF

@@ -110,8 +110,8 @@ DEV int lut_clip16(int64_t t)
     const int64_t s = (t + 32768) >> 16;
     return s < 0 ? 0 : s > 65535 ? 65535 : (int)s;
 }
-// step 2.  cb8, cr8: with the factor 8 of step 1
-DEV void lut_rgb16(const Lut3dArgs &a, int Y, int cb8, int cr8, int (&v)[3])
+// step 2.  cb8, cr8: with the factor 8 of step 1.  A: what carries the two offsets and the five coefficients under these names (Lut3dArgs; sr_yuv.h's SrYuvArgs)
+template <class A> DEV void lut_rgb16(const A &a, int Y, int cb8, int cr8, int (&v)[3])
 {
     const int64_t y = (int64_t)a.nY * (Y - a.oY);
     const int cb = cb8 - a.oC8, cr = cr8 - a.oC8;

@@ -62,7 +62,13 @@ struct SourceFront {
     // model), wdev the packed weights and then the biases in one device block, copied on st_pre from one of two pinned blocks taken in turn as the LUT's are (PinnedPair, host_pool.h), so a
     // new model follows every launch that reads the old one in stream order; a model of another size waits for st_pre first and takes a new block.  arena:
     // the activations of the last source size (sr_net_bytes), allocated at the first frame of a size
-    struct Sr { std::unique_ptr<SrNet> net; CachedBlock<uint8_t> wdev, arena; PinnedPair whost; size_t bias_off = 0; int tw = 0, th = 0; } sr;
+    // mihevc_send_frame_sr_yuv, mihevc_send_frame_sr_fit into a session smaller than the network's output: mid is the intermediate 4:2:0 picture at 10 bit of
+    // mw x mh = the network's output size (0: none; its planes and strides: sr_mid_layout), taken and let go with the arena; scale: the tables that bring it to
+    // the session's size, an instance of its own so that mihevc_send_frame_scaled keeps its tables
+    struct Sr {
+        std::unique_ptr<SrNet> net; CachedBlock<uint8_t> wdev, arena, mid; PinnedPair whost; size_t bias_off = 0; int tw = 0, th = 0, mw = 0, mh = 0;
+        TapTables<ScaleBlock> scale;
+    } sr;
     // mihevc_set_lut3d, mihevc_send_frame_lut3d: the packed table of n points per axis (0: none) in one device block of the largest size,
     // so a new table of any size overwrites the old one in stream order on st_pre, behind every k_lut3d launch that reads it and in front of the next.  It is
     // copied from one of two pinned blocks, taken in turn; a block is written again only behind the event of the copy that read it, two tables back

@@ -281,6 +281,95 @@ int refuse_source(const mihevc_session *s, bool args_ok, int flags, int kind = S
     return s->flushed || (s->src.ring.pending && s->src.ring.kind != kind) ? MIHEVC_ESTATE : MIHEVC_OK;
 }
 
+// the intermediate picture of the resized route: planar 4:2:0 at 10 bit of the network's output size nw x nh, coded size rounded up to 8 as every coded
+// picture's (scale x an even source at scale 4: its own size), rows 16-byte aligned.  Returns its bytes
+size_t sr_mid_layout(int nw, int nh, size_t (&off)[3], int (&stride)[3], int &pw, int &ph)
+{
+    pw = (nw + 7) & ~7; ph = (nh + 7) & ~7;
+    size_t n = 0;
+    for (int c = 0; c < 3; c++) {
+        stride[c] = ((c ? pw / 2 : pw) + 15) & ~15;
+        off[c] = n;
+        n += ((size_t)stride[c] * (c ? ph / 2 : ph) * sizeof(uint16_t) + 255) & ~(size_t)255;
+    }
+    return n;
+}
+// The session's size against (nw, nh) = scale x the source: 0 the direct route, 1 the resized route, -1 neither (the geometry rule of mihevc_send_frame_sr_yuv)
+int sr_route(const mihevc_session *s, int nw, int nh)
+{
+    if (s->cfg.width == nw && s->cfg.height == nh) return 0;
+    return scale_geometry_ok(nw, nh, s->cfg.width, s->cfg.height) ? 1 : -1;
+}
+// A frame through the network (the arguments are checked, `route` is 0 or 1): the arena of the size, with the resized route the intermediate picture and the
+// tables; then input(pl, tensor) launches the kernel that writes the input tensor from the staged planes, the launches of the model follow, and k_ingest_rgb
+// over the three half planes the last layer wrote: into the session's planes, or into the intermediate picture that k_scale brings to the session's size.
+// Everything on st_pre.  An arena the device cannot hold: MIHEVC_ENOMEM, nothing launched, no planes taken, the session as it was
+template <typename Input>
+int sr_frame(mihevc_session *s, const SrNet *net, int src_width, int src_height, int route, RgbColour col, int flags, int64_t pts, SrcPlane *planes, int n, size_t es,
+             Input &&input)
+{
+    SourceFront::Sr &sr = s->src.sr;
+    const int fct = net->scale == 2 ? 2 : 1, tw = src_width / fct, th = src_height / fct, W = s->cfg.width, H = s->cfg.height;
+    const int nw = net->scale * src_width, nh = net->scale * src_height, mw = route ? nw : 0, mh = route ? nh : 0;
+    size_t off[SR_BUFS], moff[3];
+    int mstride[3], mpw, mph;
+    const size_t bytes = sr_arena_layout(tw, th, off), mbytes = sr_mid_layout(nw, nh, moff, mstride, mpw, mph);
+    if (tw != sr.tw || th != sr.th || mw != sr.mw || mh != sr.mh) {
+        if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still working in the arena of the last size
+        sr.tw = sr.th = sr.mw = sr.mh = 0;
+        sr.mid.reset();
+        if (sr.arena.alloc(s->device, bytes, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
+        if (route && sr.mid.alloc(s->device, mbytes, false) != hipSuccess) { (void)hipGetLastError(); sr.arena.reset(); return MIHEVC_ENOMEM; }
+        sr.tw = tw; sr.th = th; sr.mw = mw; sr.mh = mh;
+    }
+    TapTables<ScaleBlock> &tab = sr.scale;
+    if (route)
+        if (int e = tab.ensure(s, nw, nh, [&](ScaleBlock &b) { return scale_block_build(nw, nh, W, H, SC_TH, SC_ROWS, b); })) return e;
+    return convert_frame(s, SrcFlags::of(flags), pts, planes, n, es, [&](Src &dst, const SrcPlane *pl) -> int {
+        uint8_t *arena = sr.arena;
+        if (int e = input(pl, (uint16_t *)(arena + off[SR_X]))) return e;
+        HIPCK(s, launch_sr_network(s->st_pre, *net, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
+        const mihevc_rgb_format halves = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
+        const uint16_t *o = (const uint16_t *)(arena + off[SR_OUT]);
+        if (!route) {
+            const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, s->w, s->h, s->cfg.bit_depth, dst.p, dst.stride);
+            HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
+            return MIHEVC_OK;
+        }
+        void *mid[3] = {sr.mid + moff[0], sr.mid + moff[1], sr.mid + moff[2]};
+        const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)nw * nh, o + (size_t)2 * nw * nh, nw, nw, nh, mpw, mph, 10, mid, mstride);
+        HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, true));
+        const int32_t *first[4];
+        const int16_t *coef[4];
+        tap_pointers(tab.dev.get(), tab.host.first, first); tap_pointers(tab.dev.get(), tab.host.coef, coef);
+        const ScaleArgs sa = scale_args(10, mid[0], mid[1], mid[2], mstride[0], mstride[1], nw, nh, W, H, s->w, s->h, s->cfg.bit_depth, dst.p, dst.stride, first, coef, tab.host.taps);
+        HIPCK(s, launch_scale(s->st_pre, sa, true, s->is16));
+        return MIHEVC_OK;
+    });
+}
+// an R'G'B' source through the network: mihevc_send_frame_sr (fit false: the session is exactly scale x the source) and mihevc_send_frame_sr_fit
+int send_sr_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch, int64_t pts,
+                int flags, bool fit)
+{
+    const void *p[3] = {p0, p1, p2};
+    const bool fmt_ok = s && rgb_format_ok(fmt);
+    const RgbColour col = rgb_colour(s, fmt, fmt_ok);
+    const SrNet *net = s ? s->src.sr.net.get() : nullptr;      // (null: no model)
+    const bool geo_ok = fmt_ok && net && sr_geometry_ok(net->scale, src_width, src_height);
+    const int route = geo_ok ? sr_route(s, net->scale * src_width, net->scale * src_height) : -1;
+    const bool args_ok = geo_ok && rgb_matrix_ok(col.matrix) && (fit ? route >= 0 : route == 0) && rgb_planes_ok(*fmt, p, pitch, src_width);
+    if (int e = refuse_source(s, args_ok, flags)) return e;
+    const size_t es = (size_t)rgb_elem_size(*fmt);
+    const int row = rgb_row_elems(*fmt, src_width);
+    SrcPlane planes[3] = {{p[0], row, src_height, pitch}, {p[1], row, src_height, pitch}, {p[2], row, src_height, pitch}};
+    return sr_frame(s, net, src_width, src_height, route, col, flags, pts, planes, rgb_planes(*fmt), es, [&](const SrcPlane *pl, uint16_t *x) -> int {
+        const void *sp[3] = {pl[0].p, pl[1].p, pl[2].p};
+        HIPCK(s, launch_sr_input(s->st_pre, sr_input_args(*fmt, net->scale, src_width, src_height, sp, pl[0].pitch, x), fmt->sample, (int)es));
+        return MIHEVC_OK;
+    });
+}
+
 }  // namespace
 
 template <typename Block> template <typename Build> int TapTables<Block>::ensure(mihevc_session *s, int sw_, int sh_, Build build)
@@ -467,42 +556,30 @@ int mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const f
     sr.net = std::move(net);
     return MIHEVC_OK;
 }
-// A smaller R'G'B' source through the network (mihevc_send_frame_sr; a model is set): k_sr_input, the launches of the model, then k_ingest_rgb over the three
-// half planes the last layer wrote.  Everything on st_pre.  An arena the device cannot hold: MIHEVC_ENOMEM, nothing launched, no planes taken, the session as
-// it was
+// A smaller R'G'B' source through the network (mihevc_send_frame_sr; a model is set): k_sr_input in front of sr_frame
 int mihevc_send_frame_sr(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch,
                          int64_t pts, int flags)
 {
-    const void *p[3] = {p0, p1, p2};
-    const bool fmt_ok = s && rgb_format_ok(fmt);
-    const RgbColour col = rgb_colour(s, fmt, fmt_ok);
-    const SrNet *net = s ? s->src.sr.net.get() : nullptr;      // (null: no model)
-    const bool args_ok = fmt_ok && rgb_matrix_ok(col.matrix) && net && sr_geometry_ok(net->scale, src_width, src_height) &&
-                         s->cfg.width == net->scale * src_width && s->cfg.height == net->scale * src_height && rgb_planes_ok(*fmt, p, pitch, src_width);
+    return send_sr_rgb(s, fmt, src_width, src_height, p0, p1, p2, pitch, pts, flags, false);
+}
+int mihevc_send_frame_sr_fit(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2, int pitch,
+                             int64_t pts, int flags)
+{
+    return send_sr_rgb(s, fmt, src_width, src_height, p0, p1, p2, pitch, pts, flags, true);
+}
+// A planar 4:2:0 Y'CbCr source through the network (mihevc_send_frame_sr_yuv): k_sr_from_yuv in front of sr_frame; the output side is the session's matrix and range
+int mihevc_send_frame_sr_yuv(mihevc_session *s, const mihevc_sr_yuv *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    const SrNet *net = s ? s->src.sr.net.get() : nullptr;
+    const bool src_ok = s && net && sr_yuv_src_ok(src);
+    const int route = src_ok ? sr_route(s, net->scale * src->width, net->scale * src->height) : -1;
+    const bool args_ok = src_ok && route >= 0 && rgb_matrix_ok(s->cfg.matrix) && sr_yuv_planes_ok(*src, y, u, v, pitch_y, pitch_c);
     if (int e = refuse_source(s, args_ok, flags)) return e;
-    SourceFront::Sr &sr = s->src.sr;
-    const int fct = net->scale == 2 ? 2 : 1, tw = src_width / fct, th = src_height / fct, W = s->cfg.width, H = s->cfg.height;
-    size_t off[SR_BUFS];
-    const size_t bytes = sr_arena_layout(tw, th, off);
-    if (tw != sr.tw || th != sr.th) {
-        if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still working in the arena of the last size
-        sr.tw = sr.th = 0;
-        if (sr.arena.alloc(s->device, bytes, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
-        sr.tw = tw; sr.th = th;
-    }
-    const size_t es = (size_t)rgb_elem_size(*fmt);
-    const int row = rgb_row_elems(*fmt, src_width);
-    SrcPlane planes[3] = {{p[0], row, src_height, pitch}, {p[1], row, src_height, pitch}, {p[2], row, src_height, pitch}};
-    return convert_frame(s, SrcFlags::of(flags), pts, planes, rgb_planes(*fmt), es, [&](Src &dst, const SrcPlane *pl) -> int {
-        const void *sp[3] = {pl[0].p, pl[1].p, pl[2].p};
-        uint8_t *arena = sr.arena;
-        HIPCK(s, launch_sr_input(s->st_pre, sr_input_args(*fmt, net->scale, src_width, src_height, sp, pl[0].pitch, (uint16_t *)(arena + off[SR_X])), fmt->sample, (int)es));
-        HIPCK(s, launch_sr_network(s->st_pre, *net, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
-        const mihevc_rgb_format halves = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
-        const uint16_t *o = (const uint16_t *)(arena + off[SR_OUT]);
-        const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, s->w, s->h, s->cfg.bit_depth, dst.p, dst.stride);
-        HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
+    const size_t es = src->bit_depth > 8 ? 2 : 1;
+    const int sw = src->width, sh = src->height;
+    SrcPlane planes[3] = {{y, sw, sh, pitch_y}, {u, sw / 2, sh / 2, pitch_c}, {v, sw / 2, sh / 2, pitch_c}};
+    return sr_frame(s, net, sw, sh, route, RgbColour{s->cfg.matrix, s->cfg.full_range != 0}, flags, pts, planes, 3, es, [&](const SrcPlane *pl, uint16_t *x) -> int {
+        HIPCK(s, launch_sr_from_yuv(s->st_pre, sr_yuv_args(*src, net->scale, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, x), es == 2));
         return MIHEVC_OK;
     });
 }

@@ -366,7 +366,7 @@ class Encoder:
         m = _lib.SrModel(int(model.scale), int(model.blocks))
         self._check(self._lib.mihevc_set_sr_model(self._s, C.byref(m), w.ctypes.data, w.size), "set_sr_model")
 
-    def send_sr(self, fmt: _lib.RgbFormat, width: int, height: int, *planes, pts: Optional[int] = None, asynchronous: bool = False):
+    def send_sr(self, fmt: _lib.RgbFormat, width: int, height: int, *planes, pts: Optional[int] = None, asynchronous: bool = False, _entry: str = "send_frame_sr"):
         """mihevc_send_frame_sr: a full-range R'G'B' picture of width x height, enlarged by the model of set_sr_model into the session's size (scale x the
         source's), then converted as send_rgb converts.  The planes, their types, torch tensors on the device and `asynchronous`: as send_rgb, at the SOURCE size."""
         width, height = int(width), int(height)
@@ -385,7 +385,33 @@ class Encoder:
         pts = self._pts if pts is None else pts
         self._pts = pts + 1
         ptrs += [None] * (3 - len(ptrs))
-        self._check(self._lib.mihevc_send_frame_sr(self._s, C.byref(fmt), width, height, ptrs[0], ptrs[1], ptrs[2], pitches[0], pts, flags), "send_frame_sr")
+        self._check(getattr(self._lib, "mihevc_" + _entry)(self._s, C.byref(fmt), width, height, ptrs[0], ptrs[1], ptrs[2], pitches[0], pts, flags), _entry)
+
+    def send_sr_fit(self, fmt: _lib.RgbFormat, width: int, height: int, *planes, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_sr_fit: send_sr into a session that is scale x the source or smaller (per axis down to a quarter of the network's output, every
+        size even and at least 16: sr_target_size states the rule); a smaller session gets the network's picture scaled down on the device by the filter of
+        send_scaled.  Everything else as send_sr."""
+        self.send_sr(fmt, width, height, *planes, pts=pts, asynchronous=asynchronous, _entry="send_frame_sr_fit")
+
+    def send_sr_yuv(self, width: int, height: int, y, u, v, bit_depth: int = 8, matrix: int = 6, full_range: bool = False, pts: Optional[int] = None,
+                    asynchronous: bool = False):
+        """mihevc_send_frame_sr_yuv: a planar 4:2:0 Y'CbCr picture of width x height (both even) at bit_depth 8, 10 or 12 with its own matrix (1, 5, 6 or 9) and
+        range, brought to R'G'B' on the device with the exact integer arithmetic of send_lut3d, enlarged by the model of set_sr_model and coded with the session's
+        matrix, range and depth.  The session's size follows the rule of send_sr_fit.  numpy planes (uint8 at 8 bit, else uint16) are checked for shape and type
+        here; torch tensors on the device are read where they are (MIHEVC_SRC_DEVICE) under the rules of send_fmt.  asynchronous (host planes): the rules of
+        send_async."""
+        src = _lib.SrYuv(int(width), int(height), int(bit_depth), int(matrix), 1 if full_range else 0)
+        planes = [y, u, v]
+        shapes = [(src.height, src.width)] + [(src.height // 2, src.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {src!r}")
+        es = 1 if src.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(src, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_sr_yuv")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_sr_yuv(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_sr_yuv")
 
     def send_sr_tensor(self, t, pts: Optional[int] = None, asynchronous: bool = False):
         """send_sr for one tensor in R, G, B order, the shapes and types of send_rgb_tensor; its own size is the source size"""
@@ -814,6 +840,36 @@ def upscale_target(w: int, h: int, target_height: int = 0) -> Tuple[int, int]:
     return int(w * scale) & ~1, int(target_height)
 
 
+def sr_target_size(sw: int, sh: int, scale: int, target=None) -> Tuple[int, int]:
+    """The session size of a sw x sh source through a model of `scale` (Encoder.send_sr_yuv, Encoder.send_sr_fit).  target None: the network's own output,
+    (scale sw, scale sh).  'auto': upscale_target(sw, sh, 0), the reference's rule (1080 lines for sources below 1080, 2160 below 2160); an int: that height,
+    upscale_target(sw, sh, height); a (w, h) tuple is taken as given.  The result must be the network's output size, or a reduction of it the device scaler
+    takes: all sizes even and at least 16, per axis between a quarter of the network's output and that output.  ValueError names the sizes otherwise; a target
+    LARGER than the network's output (a 240-line source to 1080 through a x4 model) is one of them."""
+    sw, sh, scale = int(sw), int(sh), int(scale)
+    nw, nh = scale * sw, scale * sh
+    if target is None:
+        return nw, nh
+    if isinstance(target, str):
+        if target != 'auto':
+            raise ValueError(f"sr_target={target!r} takes (w, h), a height or 'auto'")
+        w, h = upscale_target(sw, sh, 0)
+    elif isinstance(target, int) and not isinstance(target, bool):
+        if target < 1:
+            raise ValueError(f"sr_target={target!r} takes (w, h), a height or 'auto'")
+        w, h = upscale_target(sw, sh, target)
+    else:
+        try:
+            w, h = (int(x) for x in target)
+        except (TypeError, ValueError):
+            raise ValueError(f"sr_target={target!r} takes (w, h), a height or 'auto'") from None
+    if (w, h) == (nw, nh):
+        return w, h
+    if any(x % 2 or x < 16 for x in (w, h, nw, nh)) or not nw <= 4 * w <= 4 * nw or not nh <= 4 * h <= 4 * nh:
+        raise ValueError(f"a {sw}x{sh} source through a x{scale} model is {nw}x{nh}: {w}x{h} is not that size or an even reduction of it by at most 4 per axis")
+    return w, h
+
+
 def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) -> bool:
     """The native path writes video only; the reference always carries the source's audio as AAC (core/transcoder.py:423-450,480-489).
     When the source has audio (only container inputs can, and those need ffmpeg to be decoded at all) the video track is copied and the
@@ -838,7 +894,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
                 tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc',
-                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None) -> int:
+                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None, sr_target=None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -867,9 +923,13 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     eighths).  None: nothing changes.  Planar 4:2:0 sources on one device, per axis between 1:1 and 1:4; not together with size=, native_rgb, deinterlace=,
     denoise=, lut=, interpolate=, sliced sessions or several devices.
     sr_model: the path of an RRDBNet .pth file, a state dict, or an hevc_amd.sr.RrdbNet: every picture is enlarged by the network on the device
-    (Encoder.send_sr).  The pipe is asked for R'G'B' as native_rgb=True asks, so the container must probe as one of the RGB pixel formats; the
-    session, its level and the MP4 track open at scale x the source size.  One device; not together with any other source filter, size= or upscale=.  There is
-    no resize after the network and no tiling: a frame the device cannot hold ends the run."""
+    (DESIGN.md §6l).  A container that probes as one of the RGB pixel formats is asked for as it is, as native_rgb=True asks (Encoder.send_sr).  A planar 4:2:0
+    Y'CbCr container at 8, 10 or 12 bit is read in its own format and brought to R'G'B' on the device (Encoder.send_sr_yuv): its matrix is the probed one, and
+    when the probe does not know it BT.601 below 720 lines and BT.709 from there on, which is what players and swscale assume; its range is the probed one
+    (yuvj* files read directly are full range; the pipe hands yuvj* over as limited range).  Any other format (4:2:2, 4:4:4, semi-planar) is refused by name.
+    sr_target: None: the session, its level and the MP4 track open at scale x the source size.  'auto', a height or (w, h) (sr_target_size): they open at that
+    size and the network's picture is scaled down to it on the device; 'auto' is what the reference's restoration tool does.  sr_target without sr_model is
+    refused.  One device; not together with any other source filter, size= or upscale=.  There is no tiling: a frame the device cannot hold ends the run."""
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
@@ -930,7 +990,23 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if min(sw0, sh0) < 4 or (sr.scale == 2 and (sw0 % 2 or sh0 % 2)):
             logger.error("%s: sr_model: a %dx%d source does not fit a scale %d model", Path(file_path).name, sw0, sh0, sr.scale)
             return 1
-        native_rgb, size = True, (sr.scale * sw0, sr.scale * sh0)      # the road of size=: the session takes the target, the clip is opened at the source's own size
+        sr_name = (info.pix_fmt or '').lower()
+        sr_yuv = _lib.rgb_format_for(sr_name) is None      # a Y'CbCr container: read in its own format, converted in front of the network
+        if sr_yuv:
+            yf = _lib.src_format_for('yuv' + sr_name[4:] if sr_name.startswith('yuvj') else sr_name)
+            if yf is None or yf.chroma != 420 or yf.semi_planar or yf.msb_aligned or yf.bit_depth not in (8, 10, 12) or sw0 % 2 or sh0 % 2:
+                logger.error("%s: sr_model= takes an R'G'B' source or a planar 4:2:0 Y'CbCr source at 8, 10 or 12 bit with even sides (%r, %dx%d)",
+                             Path(file_path).name, info.pix_fmt, sw0, sh0)
+                return 1
+        try:
+            sr_size = sr_target_size(sw0, sh0, sr.scale, sr_target)
+        except ValueError as e:
+            logger.error("%s: %s", Path(file_path).name, e)
+            return 1
+        native_rgb, size = not sr_yuv, sr_size      # the road of size=: the session takes the target, the clip is opened at the source's own size
+    elif sr_target is not None:
+        logger.error("%s: sr_target= goes with sr_model=", Path(file_path).name)
+        return 1
     clip_info = info        # what the clip is opened with: the source's own description, rate and frame count
     if interpolate is not None:
         if (isinstance(interpolate, bool) or not isinstance(interpolate, int) or interpolate not in (2, 3, 4) or interp_mode not in _lib.INTERP_MODES or denoise is not None
@@ -1030,10 +1106,23 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 return 1
             fmt = None
         if sr is not None:
-            if rgb is None:
+            src_size = (int(clip.width), int(clip.height))
+            if sr_yuv:
+                planar420 = rgb is None and (fmt is None or (fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned))
+                sr_depth = int(fmt.bit_depth) if fmt is not None else int(clip.bit_depth)
+                if not planar420 or sr_depth not in (8, 10, 12) or src_size[0] % 2 or src_size[1] % 2:
+                    logger.error("%s: sr_model= takes a planar 4:2:0 Y'CbCr source at 8, 10 or 12 bit with even sides (%r)", Path(file_path).name, fmt)
+                    return 1
+                sr_matrix = _COLOUR_CODES["matrix"].get(info.color_space, 0)
+                if sr_matrix not in (1, 5, 6, 9):
+                    sr_matrix = 6 if src_size[1] < 720 else 1
+                sr_full = sr_name.startswith('yuvj') and not isinstance(clip, yuvio._PipeClip)      # (the pipe asks swscale for limited range)
+                if cfg.matrix not in (1, 5, 6, 9):
+                    cfg.matrix = sr_matrix
+                fmt = None
+            elif rgb is None:
                 logger.error("%s: sr_model= takes a source that is read as R'G'B' (%r)", Path(file_path).name, fmt)
                 return 1
-            src_size = (int(clip.width), int(clip.height))
         elif size is not None:
             fmt420 = fmt is None or (rgb is None and fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned)
             if not fmt420 or (devices and len(devices) > 1):
@@ -1102,7 +1191,11 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 for i, planes in enumerate(clip.frames()):
                     if stop_event is not None and stop_event.is_set():
                         return 1
-                    if sr is not None:
+                    if sr is not None and sr_yuv:
+                        enc.send_sr_yuv(src_size[0], src_size[1], *planes, bit_depth=sr_depth, matrix=sr_matrix, full_range=sr_full, pts=i)
+                    elif sr is not None and sr_target is not None:
+                        enc.send_sr_fit(fmt, src_size[0], src_size[1], *planes, pts=i)
+                    elif sr is not None:
                         enc.send_sr(fmt, src_size[0], src_size[1], *planes, pts=i)
                     elif lut_table is not None:
                         enc.send_lut3d(*planes, bit_depth=lut_src_depth, matrix=lut_src_matrix, full_range=lut_src_full, pts=i)

@@ -431,7 +431,8 @@ int  mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src
  * dense blocks, scale 4 or 2) evaluated on the device with half activations and weights and fp32 sums on the matrix unit; DESIGN.md 6l is the numerical
  * definition, hevc_amd/csrc/sr_net.h the flat order of the weights (hevc_amd.sr.load_rrdbnet produces it from a .pth file).  No weights ship with the library.
  * Not covered: other architectures (SRVGGNetCompact, realesr-general with its denoise blend), scale 1, other channel counts, tiling and frames too large for
- * device memory, a resize after the network, the other source filters in the same picture, sliced sessions, batching, fp8 / int8 weights, face enhancement. */
+ * device memory, a session larger than the network's output (an enlargement behind the network), 4:2:2 / 4:4:4 / semi-planar / 16-bit Y'CbCr into the
+ * network, HDR transfer handling, the other source filters in the same picture, sliced sessions, batching, fp8 / int8 weights, face enhancement. */
 typedef struct mihevc_sr_model {
     int32_t scale;           /* 4 or 2 */
     int32_t blocks;          /* RRDBs in the trunk, >= 1 (23 in x4plus / x2plus, 6 in anime_6B) */
@@ -451,6 +452,35 @@ int  mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const 
  * side below 4, slice_count > 1.  MIHEVC_ESTATE after flush.  The entry keeps no ring: it mixes with the other entries that keep none. */
 int  mihevc_send_frame_sr(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2,
                           int pitch, int64_t pts, int flags);
+/* ---- added under ABI 6: learned super-resolution for Y'CbCr sources and to a TARGET SIZE (symbols only) ----
+ * The geometry rule of the two entries below, with (nw, nh) = scale x the source size: cfg.width x cfg.height == nw x nh is the direct route of
+ * mihevc_send_frame_sr; a session for which per axis nw / 4 <= cfg size <= nw, all four sizes even and at least 16 (the rule of mihevc_send_frame_scaled
+ * with the network's output as its source) takes the resized route: the network's output is converted (the session's matrix and range) into an intermediate
+ * planar 4:2:0 picture of nw x nh at 10 bit, always, which the scaler of mihevc_send_frame_scaled brings to cfg.width x cfg.height at cfg.bit_depth with its one
+ * rounding.  That picture (3 nw nh bytes) lives and dies with the activations, under the same MIHEVC_ENOMEM rule.  Anything else, a session LARGER than the
+ * network's output included, is MIHEVC_EINVAL. */
+typedef struct mihevc_sr_yuv {
+    int32_t width, height;   /* the source picture: both even, >= 4 */
+    int32_t bit_depth;       /* 8, 10 or 12 */
+    int32_t matrix;          /* of the source: 1, 5, 6 or 9 */
+    int32_t full_range;      /* of the source: 0 limited, 1 full */
+    int32_t reserved[3];     /* 0 */
+} mihevc_sr_yuv;
+/* A planar 4:2:0 Y'CbCr picture of src->width x src->height (uint8 at 8 bit, else little-endian uint16, lsb aligned, values above 2^bit_depth - 1 clamped)
+ * through the session's model into the session's planes; the session's size under the geometry rule above.  One launch (k_sr_from_yuv;
+ * hevc_amd/csrc/kernels/sr_yuv.h states the arithmetic, DESIGN.md 6l repeats it) brings chroma to the luma grid and converts to R'G'B' at 16 bit exactly as
+ * mihevc_send_frame_lut3d does in front of its table, and writes the network's input.  The output side uses cfg.matrix and cfg.full_range.  pitch_y, pitch_c: in
+ * elements.  Flags, staging, ownership, stream ordering, memory and "keeps no ring" are those of mihevc_send_frame_sr.  MIHEVC_EINVAL, decided before any
+ * device call and leaving the session usable, the entry's own arguments first: NULL src or plane, no model set, a depth other than 8 / 10 / 12, a source matrix or
+ * a cfg.matrix other than 1 / 5 / 6 / 9, full_range outside {0, 1}, non-zero reserved, odd source sides or sides below 4, a plane whose address is not a multiple
+ * of the element size, a pitch smaller than the row, the geometry rule; then unknown flag bits; then odd cfg.width / cfg.height and slice_count > 1; then the
+ * code of a failed session; MIHEVC_ESTATE after flush or while a ring entry waits for its next frame. */
+int  mihevc_send_frame_sr_yuv(mihevc_session *s, const mihevc_sr_yuv *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c,
+                              int64_t pts, int flags);
+/* mihevc_send_frame_sr with the geometry rule above in place of "exactly scale x the source"; everything else, the order of the refusals included, as there
+ * and as for mihevc_send_frame_sr_yuv. */
+int  mihevc_send_frame_sr_fit(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2,
+                              int pitch, int64_t pts, int flags);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -685,6 +715,9 @@ int mihevc_k_sr_input(int device, const mihevc_rgb_format *fmt, int scale, int s
  * mihevc_set_sr_model takes them; out: three planes (R, G, B) of halves, scale x the source size.  MIHEVC_ENOMEM when the device cannot hold the size */
 int mihevc_k_sr_network(int device, const mihevc_sr_model *model, const float *weights, size_t count, const mihevc_rgb_format *fmt, int src_width, int src_height,
                         const void *p0, const void *p1, const void *p2, int pitch, uint16_t *out);
+/* added under ABI 6.  k_sr_from_yuv alone (the session's kernel): a source as mihevc_send_frame_sr_yuv takes it, host arrays in -> the network's input tensor of
+ * 32 channels, the shape mihevc_k_sr_input returns: src->width x src->height pixels at scale 4, half of that each way at scale 2 */
+int mihevc_k_sr_from_yuv(int device, const mihevc_sr_yuv *src, int scale, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, uint16_t *out);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
