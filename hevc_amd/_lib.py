@@ -190,6 +190,19 @@ class SrModel(C.Structure):
         return f"SrModel(scale={self.scale}, blocks={self.blocks})"
 
 
+class SrCompact(C.Structure):
+    """mihevc_sr_compact: scale (4 or 2) and number of trunk convolutions of the SRVGGNetCompact whose flat weights go with it (hevc_amd.sr.load_compact)"""
+    _fields_ = [("scale", C.c_int32), ("convs", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+    def __repr__(self):
+        return f"SrCompact(scale={self.scale}, convs={self.convs})"
+
+
+class SrCompactConvDesc(C.Structure):
+    """mihevc_sr_compact_conv_desc: one launch of k_sr_compact as mihevc_k_sr_compact_conv takes it"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "cin", "cin_real", "tail", "scale")] + [("reserved", C.c_int32 * 2)]
+
+
 class SrYuv(C.Structure):
     """mihevc_sr_yuv: size, depth, matrix and range of the planar 4:2:0 Y'CbCr frames handed to mihevc_send_frame_sr_yuv / mihevc_k_sr_from_yuv"""
     _fields_ = [(n, C.c_int32) for n in ("width", "height", "bit_depth", "matrix", "full_range")] + [("reserved", C.c_int32 * 3)]
@@ -267,6 +280,7 @@ EXPORTS = (
     "mihevc_send_frame_upscaled", "mihevc_k_upscale_source",
     "mihevc_set_sr_model", "mihevc_send_frame_sr", "mihevc_k_sr_conv", "mihevc_k_sr_input", "mihevc_k_sr_network",
     "mihevc_send_frame_sr_yuv", "mihevc_send_frame_sr_fit", "mihevc_k_sr_from_yuv",
+    "mihevc_set_sr_compact", "mihevc_k_sr_compact_conv", "mihevc_k_sr_compact_network",
 )
 
 _lib = None
@@ -363,6 +377,9 @@ def load() -> C.CDLL:
     lib.mihevc_send_frame_sr_yuv.argtypes = [vp, C.POINTER(SrYuv), vp, vp, vp, i32, i32, i64, i32]
     lib.mihevc_send_frame_sr_fit.argtypes = [vp, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, i64, i32]
     lib.mihevc_k_sr_from_yuv.argtypes = [i32, C.POINTER(SrYuv), i32, vp, vp, vp, i32, i32, vp]
+    lib.mihevc_set_sr_compact.argtypes = [vp, C.POINTER(SrCompact), vp, C.c_size_t]
+    lib.mihevc_k_sr_compact_conv.argtypes = [i32, C.POINTER(SrCompactConvDesc), vp, vp, vp, vp, vp, vp]
+    lib.mihevc_k_sr_compact_network.argtypes = [i32, C.POINTER(SrCompact), vp, C.c_size_t, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, vp]
     _lib = lib
     return lib
 

@@ -22,6 +22,7 @@
 #include "kernels/ssim.h"
 #include "kernels/upscale.h"
 #include "sr_net.h"
+#include "sr_compact_net.h"
 
 namespace mihevc {
 
@@ -94,6 +95,11 @@ hipError_t launch_sr_conv(hipStream_t st, const SrConvArgs &a, int cin, int cout
 hipError_t launch_sr_input(hipStream_t st, const SrInputArgs &a, int sample, int elem_size);
 // every launch of `net` (sr_net.h) over an arena and packed weights in device memory; the input tensor of tw x th pixels is in the arena's X
 hipError_t launch_sr_network(hipStream_t st, const SrNet &net, uint8_t *arena, const uint16_t *wpk, const float *bias, int tw, int th);
+// compact networks (kernels/sr_compact.h).  One layer: cin 32 or 64 as padded; tail 0 (64 channels, PReLU) or the scale of the shuffling last layer (cin 64); a
+// shape without an instance is hipErrorInvalidValue, never another kernel
+hipError_t launch_sr_compact(hipStream_t st, const SrCompactArgs &a, int cin, int tail);
+// every launch of `net` (sr_compact_net.h) over an arena and packed weights in device memory; the input tensor of sw x sh pixels is in the arena's X
+hipError_t launch_sr_compact_network(hipStream_t st, const SrCompactNet &net, uint8_t *arena, const uint16_t *wpk, const float *par, int sw, int sh);
 // a planar 4:2:0 Y'CbCr source -> the input tensor (kernels/sr_yuv.h).  in16: the source's elements are uint16
 hipError_t launch_sr_from_yuv(hipStream_t st, const SrYuvArgs &a, bool in16);
 // deinterlacing source (kernels/deint.h): one launch writes the three coded-size planes of `a`, margins included, from three frames at the output's own depth

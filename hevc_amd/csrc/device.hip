@@ -397,6 +397,34 @@ hipError_t launch_sr_network(hipStream_t st, const SrNet &net, uint8_t *arena, c
     });
     return err;
 }
+// compact super-resolution networks (kernels/sr_compact.h): at most SRC_MAX_WG workgroups, each with the layer's weights in LDS, walk the tiles of SRC_TW x SRC_TH
+// pixels.  One workgroup per CU: weights and two tile images take 160,256 bytes of LDS at 64 -> 64
+template <int CIN, int NA, int TAIL> __global__ __launch_bounds__(NT, SRC_PER_CU) void k_sr_compact(const SrCompactArgs a)
+{
+    __shared__ __align__(16) SrCompactShared<CIN, NA> s;
+    GpuExec ex;
+    sr_compact_program<CIN, NA, TAIL>(ex, s, a, (int)blockIdx.x, (int)gridDim.x);
+}
+hipError_t launch_sr_compact(hipStream_t st, const SrCompactArgs &a, int cin, int tail)
+{
+    const dim3 grid((unsigned)sr_compact_workgroups(a.w, a.h)), block(NT);
+    if (tail == 4 && cin == 64) hipLaunchKernelGGL((k_sr_compact<64, 3, 4>), grid, block, 0, st, a);
+    else if (tail == 2 && cin == 64) hipLaunchKernelGGL((k_sr_compact<64, 1, 2>), grid, block, 0, st, a);
+    else if (tail) return hipErrorInvalidValue;
+    else if (cin == 32) hipLaunchKernelGGL((k_sr_compact<32, 4, 0>), grid, block, 0, st, a);
+    else if (cin == 64) hipLaunchKernelGGL((k_sr_compact<64, 4, 0>), grid, block, 0, st, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_sr_compact_network(hipStream_t st, const SrCompactNet &net, uint8_t *arena, const uint16_t *wpk, const float *par, int sw, int sh)
+{
+    hipError_t err = hipSuccess;
+    sr_compact_for_each_launch(net, arena, wpk, par, sw, sh, [&](int cin, int tail, const SrCompactArgs &a) {
+        err = launch_sr_compact(st, a, cin, tail);
+        return err != hipSuccess;
+    });
+    return err;
+}
 // a Y'CbCr source in front of the network (kernels/sr_yuv.h): NT blocks of 2 x 2 luma samples per workgroup, one a lane
 template <typename TI> __global__ __launch_bounds__(NT) void k_sr_from_yuv(const SrYuvArgs a)
 {
@@ -1343,6 +1371,49 @@ int stage_sr(const mihevc_rgb_format &f, int scale, const SrNet *net, int sw, in
     else CK(hipMemcpy(out, arena.as<uint8_t>() + off[SR_X], (size_t)tw * th * SR_CIN0 * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return MIHEVC_OK;
 }
+// one launch of k_sr_compact alone
+int stage_sr_compact_conv(const mihevc_sr_compact_conv_desc &d, const uint16_t *in, const float *weights, const float *bias, const float *slopes, const uint16_t *base,
+                          uint16_t *out)
+{
+    const int tail = d.tail ? d.scale : 0, cout = tail ? 3 * tail * tail : 64, cout_pad = (cout + SR_M - 1) / SR_M * SR_M;
+    const size_t px = (size_t)d.width * d.height, out_n = px * (tail ? 3 * tail * tail : 64);
+    std::vector<uint16_t> wpk(sr_packed_halves(cout_pad, d.cin));
+    std::vector<float> par((size_t)cout_pad + 64, 0.0f);
+    sr_pack_layer(weights, cout, d.cin_real, cout_pad, d.cin, wpk.data());
+    for (int c = 0; c < cout; c++) par[(size_t)c] = bias[c];
+    if (!tail) for (int c = 0; c < 64; c++) par[(size_t)cout_pad + c] = slopes[c];
+    DevBuf din, dw, dp, dbase, dout;
+    if (int e = to_device(din, in, px * d.cin)) return e;
+    if (int e = to_device(dw, wpk.data(), wpk.size())) return e;
+    if (int e = to_device(dp, par.data(), par.size())) return e;
+    if (tail) if (int e = to_device(dbase, base, px * SR_CIN0)) return e;
+    if (int e = to_device(dout, out, out_n)) return e;
+    SrCompactArgs a;
+    a.in = din.as<const uint16_t>(); a.out = dout.as<uint16_t>(); a.wpk = dw.as<const uint16_t>(); a.bias = dp.as<const float>(); a.slope = a.bias + cout_pad;
+    a.base = dbase.as<const uint16_t>(); a.w = d.width; a.h = d.height;
+    CK(launch_sr_compact(0, a, d.cin, tail));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, out_n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
+// k_sr_input and every launch of a compact network behind it
+int stage_sr_compact(const mihevc_rgb_format &f, const SrCompactNet &net, int sw, int sh, const void *const *src, int pitch, uint16_t *out)
+{
+    DevBuf din[3], arena, dw, dp;
+    const void *dsrc[3] = {src[0], src[1], src[2]};
+    for (int c = 0; c < rgb_planes(f); c++)
+        if (int e = upload_as_laid_out(din[c], dsrc[c], rgb_row_elems(f, sw), sh, pitch, (size_t)rgb_elem_size(f))) return e;
+    size_t off[SRC_BUFS];
+    const size_t bytes = sr_compact_arena_layout(net.scale, sw, sh, off);
+    if (arena.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
+    CK(launch_sr_input(0, sr_input_args(f, 4, sw, sh, dsrc, pitch, (uint16_t *)(arena.as<uint8_t>() + off[SRC_X])), f.sample, rgb_elem_size(f)));
+    if (int e = to_device(dw, net.wpk.data(), net.wpk.size())) return e;
+    if (int e = to_device(dp, net.par.data(), net.par.size())) return e;
+    CK(launch_sr_compact_network(0, net, arena.as<uint8_t>(), dw.as<const uint16_t>(), dp.as<const float>(), sw, sh));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, arena.as<uint8_t>() + off[SRC_OUT], (size_t)sw * sh * net.scale * net.scale * 3 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MIHEVC_OK;
+}
 // the Y'CbCr input kernel alone
 int stage_sr_from_yuv(const mihevc_sr_yuv &f, int scale, const void *const *src, int pitch_y, int pitch_c, uint16_t *out)
 {
@@ -1817,6 +1888,33 @@ int mihevc_k_sr_from_yuv(int device, const mihevc_sr_yuv *src, int scale, const 
     if (int e = select_device(device)) return e;
     const void *p[3] = {y, u, v};
     return stage_sr_from_yuv(*src, scale, p, pitch_y, pitch_c, out);
+}
+
+// what a single k_sr_compact launch can be
+static bool sr_compact_conv_desc_ok(const mihevc_sr_compact_conv_desc *d)
+{
+    if (!d || d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192 || d->tail & ~1 || d->reserved[0] || d->reserved[1]) return false;
+    if ((d->cin != 32 && d->cin != 64) || d->cin_real < 1 || d->cin_real > d->cin) return false;
+    return !d->tail || (d->cin == 64 && (d->scale == 2 || d->scale == 4));
+}
+int mihevc_k_sr_compact_conv(int device, const mihevc_sr_compact_conv_desc *d, const uint16_t *in, const float *weights, const float *bias, const float *slopes,
+                             const uint16_t *base, uint16_t *out)
+{
+    if (!sr_compact_conv_desc_ok(d) || !in || !weights || !bias || !out || (d->tail ? !base : !slopes)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return stage_sr_compact_conv(*d, in, weights, bias, slopes, base, out);
+}
+
+int mihevc_k_sr_compact_network(int device, const mihevc_sr_compact *model, const float *weights, size_t count, const mihevc_rgb_format *fmt, int src_width,
+                                int src_height, const void *p0, const void *p1, const void *p2, int pitch, uint16_t *out)
+{
+    const void *src[3] = {p0, p1, p2};
+    if (!sr_compact_ok(model) || !weights || count != sr_compact_count(model->scale, model->convs) || !rgb_format_ok(fmt) || !out) return MIHEVC_EINVAL;
+    if (!sr_compact_geometry_ok(src_width, src_height) || !rgb_planes_ok(*fmt, src, pitch, src_width)) return MIHEVC_EINVAL;
+    SrCompactNet net;
+    if (!sr_compact_build(model->scale, model->convs, weights, count, net)) return MIHEVC_EINVAL;
+    if (int e = select_device(device)) return e;
+    return stage_sr_compact(*fmt, net, src_width, src_height, src, pitch, out);
 }
 
 #ifdef MIHEVC_PHASE_PROF

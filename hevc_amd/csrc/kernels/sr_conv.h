@@ -26,8 +26,8 @@
 // What this costs: with Cout = 32 a step is 2 LDS reads and 2 global loads for 4 MFMAs of 16 cycles, and every wave of a workgroup fetches the same weights
 // (from L1 / L2): the kernel is bound by its loads, not by the matrix unit (DESIGN.md §6l has the measurements and what would have to change).
 // The stepped run (tests/emu/sr.cpp, SeqExec::mfma_phase) proves the tiling and the addressing; only the device run proves the lane maps.
-// Out of scope: other architectures (SRVGGNetCompact, realesr-general), scale 1, num_feat / num_grow_ch other than 64 / 32, tiling a frame, batching frames,
-// fp8 / int8 weights.
+// The compact networks (SRVGGNetCompact, realesr-general) have a kernel of their own, sr_compact.h.  Out of scope: other architectures, scale 1,
+// num_feat / num_grow_ch other than 64 / 32, tiling a frame, batching frames, fp8 / int8 weights.
 #pragma once
 #include "ingest_rgb.h"
 

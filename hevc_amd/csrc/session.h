@@ -65,8 +65,10 @@ struct SourceFront {
     // mihevc_send_frame_sr_yuv, mihevc_send_frame_sr_fit into a session smaller than the network's output: mid is the intermediate 4:2:0 picture at 10 bit of
     // mw x mh = the network's output size (0: none; its planes and strides: sr_mid_layout), taken and let go with the arena; scale: the tables that bring it to
     // the session's size, an instance of its own so that mihevc_send_frame_scaled keeps its tables
+    // mihevc_set_sr_compact: cnet is the compact network as csrc/sr_compact_net.h packs it.  At most one of net and cnet is set; both kinds share
+    // wdev (packed weights, then the fp32 parameters at bias_off), whost, arena and mid, so a session that sets no compact model allocates and launches nothing more
     struct Sr {
-        std::unique_ptr<SrNet> net; CachedBlock<uint8_t> wdev, arena, mid; PinnedPair whost; size_t bias_off = 0; int tw = 0, th = 0, mw = 0, mh = 0;
+        std::unique_ptr<SrNet> net; std::unique_ptr<SrCompactNet> cnet; CachedBlock<uint8_t> wdev, arena, mid; PinnedPair whost; size_t bias_off = 0; int tw = 0, th = 0, mw = 0, mh = 0;
         TapTables<ScaleBlock> scale;
     } sr;
     // mihevc_set_lut3d, mihevc_send_frame_lut3d: the packed table of n points per axis (0: none) in one device block of the largest size,

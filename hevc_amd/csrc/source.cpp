@@ -300,21 +300,35 @@ int sr_route(const mihevc_session *s, int nw, int nh)
     if (s->cfg.width == nw && s->cfg.height == nh) return 0;
     return scale_geometry_ok(nw, nh, s->cfg.width, s->cfg.height) ? 1 : -1;
 }
+// The session's model of either kind (mihevc_set_sr_model, mihevc_set_sr_compact; neither: no model) as sr_frame needs it.  A compact network has no
+// pixel-unshuffle: its input tensor is the source at its own size at either scale
+struct SrModelRef {
+    const SrNet *net = nullptr;
+    const SrCompactNet *cnet = nullptr;
+    explicit SrModelRef(const mihevc_session *s) { if (s) { net = s->src.sr.net.get(); cnet = s->src.sr.cnet.get(); } }
+    explicit operator bool() const { return net || cnet; }
+    int scale() const { return cnet ? cnet->scale : net->scale; }
+    int input_scale() const { return cnet ? 4 : net->scale; }      // what k_sr_input / k_sr_from_yuv are told: 2 unshuffles
+    bool geometry_ok(int sw, int sh) const { return cnet ? sr_compact_geometry_ok(sw, sh) : sr_geometry_ok(net->scale, sw, sh); }
+};
 // A frame through the network (the arguments are checked, `route` is 0 or 1): the arena of the size, with the resized route the intermediate picture and the
 // tables; then input(pl, tensor) launches the kernel that writes the input tensor from the staged planes, the launches of the model follow, and k_ingest_rgb
 // over the three half planes the last layer wrote: into the session's planes, or into the intermediate picture that k_scale brings to the session's size.
 // Everything on st_pre.  An arena the device cannot hold: MIHEVC_ENOMEM, nothing launched, no planes taken, the session as it was
 template <typename Input>
-int sr_frame(mihevc_session *s, const SrNet *net, int src_width, int src_height, int route, RgbColour col, int flags, int64_t pts, SrcPlane *planes, int n, size_t es,
+int sr_frame(mihevc_session *s, const SrModelRef model, int src_width, int src_height, int route, RgbColour col, int flags, int64_t pts, SrcPlane *planes, int n, size_t es,
              Input &&input)
 {
     SourceFront::Sr &sr = s->src.sr;
-    const int fct = net->scale == 2 ? 2 : 1, tw = src_width / fct, th = src_height / fct, W = s->cfg.width, H = s->cfg.height;
-    const int nw = net->scale * src_width, nh = net->scale * src_height, mw = route ? nw : 0, mh = route ? nh : 0;
-    size_t off[SR_BUFS], moff[3];
+    const SrNet *const net = model.net;
+    const SrCompactNet *const cnet = model.cnet;
+    const int fct = model.input_scale() == 2 ? 2 : 1, tw = src_width / fct, th = src_height / fct, W = s->cfg.width, H = s->cfg.height;
+    const int nw = model.scale() * src_width, nh = model.scale() * src_height, mw = route ? nw : 0, mh = route ? nh : 0;
+    size_t off[SR_BUFS], coff[SRC_BUFS], moff[3];
     int mstride[3], mpw, mph;
-    const size_t bytes = sr_arena_layout(tw, th, off), mbytes = sr_mid_layout(nw, nh, moff, mstride, mpw, mph);
-    if (tw != sr.tw || th != sr.th || mw != sr.mw || mh != sr.mh) {
+    const size_t bytes = cnet ? sr_compact_arena_layout(cnet->scale, tw, th, coff) : sr_arena_layout(tw, th, off), mbytes = sr_mid_layout(nw, nh, moff, mstride, mpw, mph);
+    const size_t x_off = cnet ? coff[SRC_X] : off[SR_X], out_off = cnet ? coff[SRC_OUT] : off[SR_OUT];
+    if (tw != sr.tw || th != sr.th || mw != sr.mw || mh != sr.mh || sr.arena.bytes() != bytes) {      // (the last: a model of the other kind or scale since)
         if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
         HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still working in the arena of the last size
         sr.tw = sr.th = sr.mw = sr.mh = 0;
@@ -328,10 +342,11 @@ int sr_frame(mihevc_session *s, const SrNet *net, int src_width, int src_height,
         if (int e = tab.ensure(s, nw, nh, [&](ScaleBlock &b) { return scale_block_build(nw, nh, W, H, SC_TH, SC_ROWS, b); })) return e;
     return convert_frame(s, SrcFlags::of(flags), pts, planes, n, es, [&](Src &dst, const SrcPlane *pl) -> int {
         uint8_t *arena = sr.arena;
-        if (int e = input(pl, (uint16_t *)(arena + off[SR_X]))) return e;
-        HIPCK(s, launch_sr_network(s->st_pre, *net, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
+        if (int e = input(pl, (uint16_t *)(arena + x_off))) return e;
+        if (cnet) HIPCK(s, launch_sr_compact_network(s->st_pre, *cnet, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
+        else HIPCK(s, launch_sr_network(s->st_pre, *net, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
         const mihevc_rgb_format halves = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
-        const uint16_t *o = (const uint16_t *)(arena + off[SR_OUT]);
+        const uint16_t *o = (const uint16_t *)(arena + out_off);
         if (!route) {
             const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, s->w, s->h, s->cfg.bit_depth, dst.p, dst.stride);
             HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
@@ -355,17 +370,17 @@ int send_sr_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, 
     const void *p[3] = {p0, p1, p2};
     const bool fmt_ok = s && rgb_format_ok(fmt);
     const RgbColour col = rgb_colour(s, fmt, fmt_ok);
-    const SrNet *net = s ? s->src.sr.net.get() : nullptr;      // (null: no model)
-    const bool geo_ok = fmt_ok && net && sr_geometry_ok(net->scale, src_width, src_height);
-    const int route = geo_ok ? sr_route(s, net->scale * src_width, net->scale * src_height) : -1;
+    const SrModelRef model(s);      // (false: no model)
+    const bool geo_ok = fmt_ok && model && model.geometry_ok(src_width, src_height);
+    const int route = geo_ok ? sr_route(s, model.scale() * src_width, model.scale() * src_height) : -1;
     const bool args_ok = geo_ok && rgb_matrix_ok(col.matrix) && (fit ? route >= 0 : route == 0) && rgb_planes_ok(*fmt, p, pitch, src_width);
     if (int e = refuse_source(s, args_ok, flags)) return e;
     const size_t es = (size_t)rgb_elem_size(*fmt);
     const int row = rgb_row_elems(*fmt, src_width);
     SrcPlane planes[3] = {{p[0], row, src_height, pitch}, {p[1], row, src_height, pitch}, {p[2], row, src_height, pitch}};
-    return sr_frame(s, net, src_width, src_height, route, col, flags, pts, planes, rgb_planes(*fmt), es, [&](const SrcPlane *pl, uint16_t *x) -> int {
+    return sr_frame(s, model, src_width, src_height, route, col, flags, pts, planes, rgb_planes(*fmt), es, [&](const SrcPlane *pl, uint16_t *x) -> int {
         const void *sp[3] = {pl[0].p, pl[1].p, pl[2].p};
-        HIPCK(s, launch_sr_input(s->st_pre, sr_input_args(*fmt, net->scale, src_width, src_height, sp, pl[0].pitch, x), fmt->sample, (int)es));
+        HIPCK(s, launch_sr_input(s->st_pre, sr_input_args(*fmt, model.input_scale(), src_width, src_height, sp, pl[0].pitch, x), fmt->sample, (int)es));
         return MIHEVC_OK;
     });
 }
@@ -526,6 +541,27 @@ int mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src,
         return MIHEVC_OK;
     });
 }
+// The packed weights and the fp32 parameters of a model of either kind on their way to the session's device block: on st_pre, behind every launch that reads the
+// model before.  MIHEVC_ENOMEM leaves the session without a model
+static int sr_upload_model(mihevc_session *s, const std::vector<uint16_t> &wpk, const std::vector<float> &par)
+{
+    SourceFront::Sr &sr = s->src.sr;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    const size_t wbytes = (wpk.size() * sizeof(uint16_t) + 255) & ~(size_t)255, total = wbytes + par.size() * sizeof(float);
+    if (sr.wdev.bytes() != total) {      // a model of another size: new blocks, on the device and (in acquire) on the host
+        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still reading the block of the last model
+        sr.net.reset();
+        sr.cnet.reset();
+        if (sr.wdev.alloc(s->device, total, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
+    }
+    uint8_t *block;
+    HIPCK(s, sr.whost.acquire(s->device, total, block));      // the copy of the model before the last one
+    memcpy(block, wpk.data(), wpk.size() * sizeof(uint16_t));
+    memcpy(block + wbytes, par.data(), par.size() * sizeof(float));
+    HIPCK(s, sr.whost.commit(sr.wdev, total, s->st_pre));
+    sr.bias_off = wbytes;
+    return MIHEVC_OK;
+}
 int mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const float *weights, size_t count)
 {
     if (!s || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
@@ -533,27 +569,31 @@ int mihevc_set_sr_model(mihevc_session *s, const mihevc_sr_model *model, const f
     if (!model) {
         if (s->failed) return s->fail_code;
         sr.net.reset();
+        sr.cnet.reset();
         return MIHEVC_OK;
     }
     if (!sr_model_ok(model) || !weights || count != sr_net_count(model->scale, model->blocks)) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
     std::unique_ptr<SrNet> net(new SrNet);
     if (!sr_net_build(model->scale, model->blocks, weights, count, *net)) return MIHEVC_EINVAL;
-    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    const size_t wbytes = (net->wpk.size() * sizeof(uint16_t) + 255) & ~(size_t)255, total = wbytes + net->bias.size() * sizeof(float);
-    if (sr.wdev.bytes() != total) {      // a model of another size: new blocks, on the device and (in acquire) on the host
-        HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still reading the block of the last model
-        sr.net.reset();
-        if (sr.wdev.alloc(s->device, total, false) != hipSuccess) { (void)hipGetLastError(); return MIHEVC_ENOMEM; }
-    }
-    uint8_t *block;
-    HIPCK(s, sr.whost.acquire(s->device, total, block));      // the copy of the model before the last one
-    memcpy(block, net->wpk.data(), net->wpk.size() * sizeof(uint16_t));
-    memcpy(block + wbytes, net->bias.data(), net->bias.size() * sizeof(float));
-    HIPCK(s, sr.whost.commit(sr.wdev, total, s->st_pre));
+    if (int e = sr_upload_model(s, net->wpk, net->bias)) return e;
     net->wpk = std::vector<uint16_t>();      // the launches need the shapes and the list, not the host copy of the weights
-    sr.bias_off = wbytes;
+    sr.cnet.reset();
     sr.net = std::move(net);
+    return MIHEVC_OK;
+}
+int mihevc_set_sr_compact(mihevc_session *s, const mihevc_sr_compact *model, const float *weights, size_t count)
+{
+    if (!s || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
+    if (!sr_compact_ok(model) || !weights || count != sr_compact_count(model->scale, model->convs)) return MIHEVC_EINVAL;
+    if (s->failed) return s->fail_code;
+    std::unique_ptr<SrCompactNet> net(new SrCompactNet);
+    if (!sr_compact_build(model->scale, model->convs, weights, count, *net)) return MIHEVC_EINVAL;
+    if (int e = sr_upload_model(s, net->wpk, net->par)) return e;
+    net->wpk = std::vector<uint16_t>();
+    net->par = std::vector<float>();
+    s->src.sr.net.reset();
+    s->src.sr.cnet = std::move(net);
     return MIHEVC_OK;
 }
 // A smaller R'G'B' source through the network (mihevc_send_frame_sr; a model is set): k_sr_input in front of sr_frame
@@ -570,16 +610,16 @@ int mihevc_send_frame_sr_fit(mihevc_session *s, const mihevc_rgb_format *fmt, in
 // A planar 4:2:0 Y'CbCr source through the network (mihevc_send_frame_sr_yuv): k_sr_from_yuv in front of sr_frame; the output side is the session's matrix and range
 int mihevc_send_frame_sr_yuv(mihevc_session *s, const mihevc_sr_yuv *src, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
 {
-    const SrNet *net = s ? s->src.sr.net.get() : nullptr;
-    const bool src_ok = s && net && sr_yuv_src_ok(src);
-    const int route = src_ok ? sr_route(s, net->scale * src->width, net->scale * src->height) : -1;
+    const SrModelRef model(s);
+    const bool src_ok = s && model && sr_yuv_src_ok(src);
+    const int route = src_ok ? sr_route(s, model.scale() * src->width, model.scale() * src->height) : -1;
     const bool args_ok = src_ok && route >= 0 && rgb_matrix_ok(s->cfg.matrix) && sr_yuv_planes_ok(*src, y, u, v, pitch_y, pitch_c);
     if (int e = refuse_source(s, args_ok, flags)) return e;
     const size_t es = src->bit_depth > 8 ? 2 : 1;
     const int sw = src->width, sh = src->height;
     SrcPlane planes[3] = {{y, sw, sh, pitch_y}, {u, sw / 2, sh / 2, pitch_c}, {v, sw / 2, sh / 2, pitch_c}};
-    return sr_frame(s, net, sw, sh, route, RgbColour{s->cfg.matrix, s->cfg.full_range != 0}, flags, pts, planes, 3, es, [&](const SrcPlane *pl, uint16_t *x) -> int {
-        HIPCK(s, launch_sr_from_yuv(s->st_pre, sr_yuv_args(*src, net->scale, pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, x), es == 2));
+    return sr_frame(s, model, sw, sh, route, RgbColour{s->cfg.matrix, s->cfg.full_range != 0}, flags, pts, planes, 3, es, [&](const SrcPlane *pl, uint16_t *x) -> int {
+        HIPCK(s, launch_sr_from_yuv(s->st_pre, sr_yuv_args(*src, model.input_scale(), pl[0].p, pl[1].p, pl[2].p, pl[0].pitch, pl[1].pitch, x), es == 2));
         return MIHEVC_OK;
     });
 }

@@ -1,7 +1,7 @@
 // hevc_amd/csrc/sr_net.h — an RRDBNet as kernels/sr_conv.h runs it: the weights packed into MFMA fragments, the list of launches and the
 // device memory a source size needs.  Host arithmetic only, no HIP: the session, the stage entries and the tests (tests/emu/sr.cpp) share it.
-// Network: num_feat 64, num_grow_ch 32, `blocks` >= 1 RRDBs, scale 4 or 2 (scale 2 starts with a pixel-unshuffle: 12 input channels).  Out of scope: other
-// architectures (SRVGGNetCompact, realesr-general with its denoise blend), scale 1, other channel counts, tiling, frames too large for memory, fp8 / int8.
+// Network: num_feat 64, num_grow_ch 32, `blocks` >= 1 RRDBs, scale 4 or 2 (scale 2 starts with a pixel-unshuffle: 12 input channels).  SRVGGNetCompact (realesr-general with its
+// denoise blend) is sr_compact_net.h.  Out of scope: other architectures, scale 1, other channel counts, tiling, frames too large for memory, fp8 / int8.
 //   flat weights   fp32, layer after layer, each layer its weight in torch's order [cout][cin][3][3], then its bias [cout]:
 //                  conv_first (cin 3 or 12), then for block i = 0 .., rdb 1 .. 3, conv 1 .. 5 (cin 64 + 32 (k - 1), cout 32, conv5: 64), then conv_body,
 //                  conv_up1, conv_up2, conv_hr (64 -> 64) and conv_last (64 -> 3)

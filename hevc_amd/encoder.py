@@ -357,12 +357,17 @@ class Encoder:
         self._check(self._lib.mihevc_send_frame_upscaled(self._s, C.byref(src), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_upscaled")
 
     def set_sr_model(self, model):
-        """mihevc_set_sr_model: the RRDBNet send_sr runs: an hevc_amd.sr.RrdbNet (load_rrdbnet), or None to drop the model.  The weights are packed
+        """mihevc_set_sr_model / mihevc_set_sr_compact: the network send_sr runs: an hevc_amd.sr.RrdbNet (load_rrdbnet), an hevc_amd.sr.CompactNet
+        (load_compact, blend; §6m), or None to drop the model.  A session has one model: setting one of either kind replaces the other.  The weights are packed
         and on their way to the device before the call returns; a model may be replaced between frames, and frames already sent keep theirs."""
         if model is None:
             self._check(self._lib.mihevc_set_sr_model(self._s, None, None, 0), "set_sr_model")
             return
         w = np.ascontiguousarray(model.weights, dtype=np.float32)
+        if hasattr(model, "convs"):
+            m = _lib.SrCompact(int(model.scale), int(model.convs))
+            self._check(self._lib.mihevc_set_sr_compact(self._s, C.byref(m), w.ctypes.data, w.size), "set_sr_compact")
+            return
         m = _lib.SrModel(int(model.scale), int(model.blocks))
         self._check(self._lib.mihevc_set_sr_model(self._s, C.byref(m), w.ctypes.data, w.size), "set_sr_model")
 
@@ -894,7 +899,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
                 tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc',
-                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None, sr_target=None) -> int:
+                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None, sr_target=None, sr_denoise=None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -922,8 +927,12 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     source, delivered at its own size, is enlarged on the device (Encoder.send_upscaled) with sharpen (0 .. 64 sixteenths) and antiring (0 .. 8
     eighths).  None: nothing changes.  Planar 4:2:0 sources on one device, per axis between 1:1 and 1:4; not together with size=, native_rgb, deinterlace=,
     denoise=, lut=, interpolate=, sliced sessions or several devices.
-    sr_model: the path of an RRDBNet .pth file, a state dict, or an hevc_amd.sr.RrdbNet: every picture is enlarged by the network on the device
-    (DESIGN.md §6l).  A container that probes as one of the RGB pixel formats is asked for as it is, as native_rgb=True asks (Encoder.send_sr).  A planar 4:2:0
+    sr_model: the path of an RRDBNet or SRVGGNetCompact .pth file, a state dict, or an hevc_amd.sr.RrdbNet / CompactNet (hevc_amd.sr.load_model chooses by
+    the keys): every picture is enlarged by the network on the device.  A pair (model, denoise partner) of compact models with
+    sr_denoise = 0 .. 1 is the compact family's denoise strength (realesr-general-x4v3 with realesr-general-wdn-x4v3): the two are blended on the host
+    (hevc_amd.sr.blend), sr_denoise being the weight of the FIRST model.  The reference's tool has a noise level 0 .. 3 and states no mapping of it onto this
+    strength, so none is made up here: the caller gives the strength.  sr_denoise with a single model or an RRDBNet, or a pair without it, is an error.  A
+    compact model of scale 2 takes odd R'G'B' source sides.  A container that probes as one of the RGB pixel formats is asked for as it is, as native_rgb=True asks (Encoder.send_sr).  A planar 4:2:0
     Y'CbCr container at 8, 10 or 12 bit is read in its own format and brought to R'G'B' on the device (Encoder.send_sr_yuv): its matrix is the probed one, and
     when the probe does not know it BT.601 below 720 lines and BT.709 from there on, which is what players and swscale assume; its range is the probed one
     (yuvj* files read directly are full range; the pipe hands yuvj* over as limited range).  Any other format (4:2:2, 4:4:4, semi-planar) is refused by name.
@@ -982,12 +991,20 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             return 1
         from . import sr as sr_mod
         try:
-            sr = sr_model if isinstance(sr_model, sr_mod.RrdbNet) else sr_mod.load_rrdbnet(sr_model)
-        except (OSError, ValueError, RuntimeError, KeyError) as e:
+            one = lambda m: m if isinstance(m, (sr_mod.RrdbNet, sr_mod.CompactNet)) else sr_mod.load_model(m)
+            if isinstance(sr_model, (tuple, list)):
+                if len(sr_model) != 2 or sr_denoise is None or isinstance(sr_denoise, bool):
+                    raise ValueError("a pair (model, denoise partner) goes with sr_denoise = 0 .. 1")
+                sr = sr_mod.blend(one(sr_model[0]), one(sr_model[1]), sr_denoise)
+            else:
+                sr = one(sr_model)
+                if sr_denoise is not None:
+                    raise ValueError("sr_denoise= goes with a pair (model, denoise partner) of compact models")
+        except (OSError, ValueError, TypeError, RuntimeError, KeyError) as e:
             logger.error("%s: sr_model: %s", Path(file_path).name, e)
             return 1
         sw0, sh0 = int(info.width), int(info.height)
-        if min(sw0, sh0) < 4 or (sr.scale == 2 and (sw0 % 2 or sh0 % 2)):
+        if min(sw0, sh0) < 4 or (sr.scale == 2 and not hasattr(sr, "convs") and (sw0 % 2 or sh0 % 2)):
             logger.error("%s: sr_model: a %dx%d source does not fit a scale %d model", Path(file_path).name, sw0, sh0, sr.scale)
             return 1
         sr_name = (info.pix_fmt or '').lower()
@@ -1006,6 +1023,9 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         native_rgb, size = not sr_yuv, sr_size      # the road of size=: the session takes the target, the clip is opened at the source's own size
     elif sr_target is not None:
         logger.error("%s: sr_target= goes with sr_model=", Path(file_path).name)
+        return 1
+    elif sr_denoise is not None:
+        logger.error("%s: sr_denoise= goes with sr_model=", Path(file_path).name)
         return 1
     clip_info = info        # what the clip is opened with: the source's own description, rate and frame count
     if interpolate is not None:

@@ -430,7 +430,8 @@ int  mihevc_send_frame_upscaled(mihevc_session *s, const mihevc_upscale_src *src
  * An RRDBNet (the architecture of RealESRGAN_x4plus, RealESRGAN_x2plus and RealESRGANv2-anime_6B: num_feat 64, num_grow_ch 32, `blocks` residual-in-residual
  * dense blocks, scale 4 or 2) evaluated on the device with half activations and weights and fp32 sums on the matrix unit; DESIGN.md 6l is the numerical
  * definition, hevc_amd/csrc/sr_net.h the flat order of the weights (hevc_amd.sr.load_rrdbnet produces it from a .pth file).  No weights ship with the library.
- * Not covered: other architectures (SRVGGNetCompact, realesr-general with its denoise blend), scale 1, other channel counts, tiling and frames too large for
+ * The compact networks (SRVGGNetCompact: realesr-animevideov3, realesr-general-x4v3 with its denoise blend) are mihevc_set_sr_compact below.
+ * Not covered: other architectures, scale 3 and 1, other channel counts, tiling and frames too large for
  * device memory, a session larger than the network's output (an enlargement behind the network), 4:2:2 / 4:4:4 / semi-planar / 16-bit Y'CbCr into the
  * network, HDR transfer handling, the other source filters in the same picture, sliced sessions, batching, fp8 / int8 weights, face enhancement. */
 typedef struct mihevc_sr_model {
@@ -481,6 +482,25 @@ int  mihevc_send_frame_sr_yuv(mihevc_session *s, const mihevc_sr_yuv *src, const
  * and as for mihevc_send_frame_sr_yuv. */
 int  mihevc_send_frame_sr_fit(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, int src_height, const void *p0, const void *p1, const void *p2,
                               int pitch, int64_t pts, int flags);
+/* ---- added under ABI 6: COMPACT super-resolution networks (symbols only) ----
+ * An SRVGGNetCompact (the architecture of realesr-animevideov3, 16 trunk convolutions, and of realesr-general-x4v3 / realesr-general-wdn-x4v3, 32: num_feat 64,
+ * a PReLU with one slope per channel behind every convolution but the last, a pixel-shuffle and the sum with the source enlarged by nearest; scale 4 or 2)
+ * evaluated on the device with half activations and weights and fp32 sums on the matrix unit.  DESIGN.md 6m is the numerical definition,
+ * hevc_amd/csrc/sr_compact_net.h the flat order of the weights (hevc_amd.sr.load_compact produces it from a .pth file; hevc_amd.sr.blend is the family's denoise
+ * strength, a blend of two models' weights on the host).  No weights ship with the library.  Not covered: scale 3 and 1, num_feat other than 64. */
+typedef struct mihevc_sr_compact {
+    int32_t scale;           /* 4 or 2 */
+    int32_t convs;           /* trunk convolutions, 1 .. 64 (16 in animevideov3, 32 in general-x4v3) */
+    int32_t reserved[6];     /* 0 */
+} mihevc_sr_compact;
+/* The model of the session, under the rules of mihevc_set_sr_model: packed and on its way to the device before the call returns, frames already sent keep the
+ * model they were sent under.  A session has ONE model of either kind: setting one replaces the other, and mihevc_set_sr_model(s, NULL, ...) drops whichever is
+ * set.  mihevc_send_frame_sr, _sr_fit and _sr_yuv run whichever model is set under their own geometry rules, with one difference: a compact network has no
+ * pixel-unshuffle, so with a compact model of scale 2 the R'G'B' entries take odd source sides (mihevc_send_frame_sr_yuv keeps its own even-sides rule).
+ * Device memory for the activations is 416 bytes per source pixel at scale 4 and 344 at scale 2 (sr_compact_net.h states the formula).  MIHEVC_EINVAL: NULL
+ * model, a scale other than 4 / 2, convs outside 1 .. 64, non-zero reserved, NULL weights, a count other than the model's, slice_count > 1.  MIHEVC_ENOMEM: the
+ * device cannot hold the weights; the session has no model then */
+int  mihevc_set_sr_compact(mihevc_session *s, const mihevc_sr_compact *model, const float *weights, size_t count);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
@@ -718,6 +738,25 @@ int mihevc_k_sr_network(int device, const mihevc_sr_model *model, const float *w
 /* added under ABI 6.  k_sr_from_yuv alone (the session's kernel): a source as mihevc_send_frame_sr_yuv takes it, host arrays in -> the network's input tensor of
  * 32 channels, the shape mihevc_k_sr_input returns: src->width x src->height pixels at scale 4, half of that each way at scale 2 */
 int mihevc_k_sr_from_yuv(int device, const mihevc_sr_yuv *src, int scale, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, uint16_t *out);
+/* added under ABI 6.  One launch of k_sr_compact (hevc_amd/csrc/kernels/sr_compact.h), host arrays in and out.  Tensors are IEEE halves, NHWC.  `in`: width x
+ * height pixels of cin channels (32 or 64; input channels cin_real .. cin - 1 meet zero weights).  tail = 0: weights fp32 [64][cin_real][3][3], bias [64],
+ * slopes [64] (PReLU, one per channel); out: 64 channels.  tail = 1 (cin 64, scale 4 or 2): weights [3 r r][cin_real][3][3], bias [3 r r], slopes not read; base:
+ * the input tensor of the network, width x height pixels of 32 channels, of which channels 0 .. 2 are added; out: three planes of (r height) x (r width).  `out`
+ * is uploaded as given and comes back whole.  MIHEVC_EINVAL first (a NULL array the launch reads, a side below 1 or above 8192, another cin, cin_real outside
+ * 1 .. cin, tail outside {0, 1}, with tail another scale or cin, non-zero reserved), then MIHEVC_ENODEV */
+typedef struct mihevc_sr_compact_conv_desc {
+    int32_t width, height;
+    int32_t cin, cin_real;
+    int32_t tail, scale;     /* scale: read with tail = 1 */
+    int32_t reserved[2];     /* 0 */
+} mihevc_sr_compact_conv_desc;
+int mihevc_k_sr_compact_conv(int device, const mihevc_sr_compact_conv_desc *d, const uint16_t *in, const float *weights, const float *bias, const float *slopes,
+                             const uint16_t *base, uint16_t *out);
+/* added under ABI 6.  The whole compact network as mihevc_send_frame_sr runs it (k_sr_input, then every launch of sr_compact_net.h), from host arrays: weights /
+ * count as mihevc_set_sr_compact takes them; out: three planes (R, G, B) of halves, scale x the source size.  Sides of at least 4, odd ones included.
+ * MIHEVC_ENOMEM when the device cannot hold the size */
+int mihevc_k_sr_compact_network(int device, const mihevc_sr_compact *model, const float *weights, size_t count, const mihevc_rgb_format *fmt, int src_width,
+                                int src_height, const void *p0, const void *p1, const void *p2, int pitch, uint16_t *out);
 
 /* added under ABI 6 (symbols only).  The scene-cut detector of a session alone (mihevc_config.scenecut; the session's kernel and launcher, on zeroed sums): luma[i] is
  * the luma plane of picture i in host memory, pitch[i] x height samples (pitch[i] >= width, in samples; uint8_t at bit_depth 8, uint16_t at 10), width and height
