@@ -211,6 +211,59 @@ class SrYuv(C.Structure):
         return f"SrYuv(width={self.width}, height={self.height}, bit_depth={self.bit_depth}, matrix={self.matrix}, full_range={self.full_range})"
 
 
+CHAIN_FIELD = {None: 0, "deint": 1, "fieldmatch": 2}
+CHAIN_RESIZE = {None: 0, "scale": 1, "upscale": 2, "sr": 3}
+
+
+class Chain(C.Structure):
+    """mihevc_chain: the source filter chain of a session (mihevc_set_source_chain): the source's size and depth, one selector per slot (field:
+    CHAIN_FIELD, denoise_on, resize: CHAIN_RESIZE, interpolate_on) and the parameter structs of the single entries; chain() fills one in"""
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "bit_depth", "field", "denoise_on", "resize", "interpolate_on")] + [("reserved", C.c_int32 * 9)] +
+                [("deint", Deint), ("fieldmatch", Fieldmatch), ("denoise", Denoise), ("upscale", UpscaleSrc), ("sr", SrYuv), ("interpolate", Interpolate)])
+
+    def __repr__(self):
+        return (f"Chain({self.width}x{self.height}@{self.bit_depth}, field={self.field}, denoise={self.denoise_on}, resize={self.resize}, "
+                f"interpolate={self.interpolate_on})")
+
+
+class ChainPlan(C.Structure):
+    """mihevc_chain_plan: what mihevc_chain_plan_for says of a chain: the rate fraction, the slots that are on, the pictures of `frames` frames, and by slot
+    (field, denoise, resize, interpolate) the size and depth the stage runs at (the resize stage: what it writes; 0: off)"""
+    _fields_ = [("rate_num", C.c_int32), ("rate_den", C.c_int32), ("stages", C.c_int32), ("reserved", C.c_int32), ("pictures", C.c_int64), ("width", C.c_int32 * 4),
+                ("height", C.c_int32 * 4), ("bit_depth", C.c_int32 * 4)]
+
+
+def chain(width, height, bit_depth, field=None, tff=True, field_rate=False, decimate=True, fm_deint=True, denoise=None, resize=None, sharpen=8, antiring=8,
+          sr_matrix=6, sr_full_range=False, interpolate=None, interp_mode="mc", scene_threshold=10) -> Chain:
+    """A Chain for a width x height source at bit_depth.  field: None, 'deint' (tff, field_rate) or 'fieldmatch' (tff, decimate, fm_deint); denoise: None, or what
+    denoise_strength takes; resize: None, 'scale', 'upscale' (sharpen, antiring) or 'sr' (sr_matrix, sr_full_range of the source); interpolate: None, or a
+    factor 2 .. 4 (interp_mode, scene_threshold).  The ranges are judged by the library (mihevc_set_source_chain, mihevc_chain_plan_for); names and types here"""
+    if field not in CHAIN_FIELD or resize not in CHAIN_RESIZE:
+        raise ValueError(f"chain: field={field!r} takes None, 'deint' or 'fieldmatch'; resize={resize!r} takes None, 'scale', 'upscale' or 'sr'")
+    c = Chain(int(width), int(height), int(bit_depth), CHAIN_FIELD[field], int(denoise is not None), CHAIN_RESIZE[resize], int(interpolate is not None))
+    if field == "deint":
+        c.deint = Deint(int(bool(tff)), int(bool(field_rate)))
+    elif field == "fieldmatch":
+        c.fieldmatch = Fieldmatch(int(bool(tff)), int(bool(decimate)), int(bool(fm_deint)))
+    if denoise is not None:
+        c.denoise = denoise if isinstance(denoise, Denoise) else denoise_strength(denoise)
+    if resize == "upscale":
+        c.upscale = UpscaleSrc(c.width, c.height, c.bit_depth, int(sharpen), int(antiring))
+    elif resize == "sr":
+        c.sr = SrYuv(c.width, c.height, c.bit_depth, int(sr_matrix), 1 if sr_full_range else 0)
+    if interpolate is not None:
+        c.interpolate = interpolate_mode(interpolate, interp_mode, scene_threshold)
+    return c
+
+
+def chain_plan(c: Chain, width: int, height: int, bit_depth: int, matrix: int = 1, sr_scale: int = 0, frames: int = 0):
+    """mihevc_chain_plan_for: the ChainPlan of chain c in front of a width x height session at bit_depth (matrix: its cfg.matrix; sr_scale: the scale of its
+    network, 0 without one), or None for a descriptor the library refuses"""
+    out = ChainPlan()
+    rc = load().mihevc_chain_plan_for(C.byref(c), int(width), int(height), int(bit_depth), int(matrix), int(sr_scale), int(frames), C.byref(out))
+    return out if rc == 0 else None
+
+
 class SrConvDesc(C.Structure):
     """mihevc_sr_conv_desc: one launch of k_sr_conv as mihevc_k_sr_conv takes it"""
     _fields_ = ([(n, C.c_int32) for n in ("width", "height", "up", "planar", "act", "n_res", "in_ch", "in_off", "cin", "cin_real", "out_ch", "out_off", "cout",
@@ -281,6 +334,7 @@ EXPORTS = (
     "mihevc_set_sr_model", "mihevc_send_frame_sr", "mihevc_k_sr_conv", "mihevc_k_sr_input", "mihevc_k_sr_network",
     "mihevc_send_frame_sr_yuv", "mihevc_send_frame_sr_fit", "mihevc_k_sr_from_yuv",
     "mihevc_set_sr_compact", "mihevc_k_sr_compact_conv", "mihevc_k_sr_compact_network",
+    "mihevc_set_source_chain", "mihevc_send_frame_chain", "mihevc_chain_plan_for",
 )
 
 _lib = None
@@ -380,6 +434,9 @@ def load() -> C.CDLL:
     lib.mihevc_set_sr_compact.argtypes = [vp, C.POINTER(SrCompact), vp, C.c_size_t]
     lib.mihevc_k_sr_compact_conv.argtypes = [i32, C.POINTER(SrCompactConvDesc), vp, vp, vp, vp, vp, vp]
     lib.mihevc_k_sr_compact_network.argtypes = [i32, C.POINTER(SrCompact), vp, C.c_size_t, C.POINTER(RgbFormat), i32, i32, vp, vp, vp, i32, vp]
+    lib.mihevc_set_source_chain.argtypes = [vp, C.POINTER(Chain)]
+    lib.mihevc_send_frame_chain.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32]
+    lib.mihevc_chain_plan_for.argtypes = [C.POINTER(Chain), i32, i32, i32, i32, i32, i64, C.POINTER(ChainPlan)]
     _lib = lib
     return lib
 

@@ -1,8 +1,9 @@
-// hevc_amd/csrc/api_host.cpp — C-ABI entry points that need no device: defaults, cost parameters, bitstream.
+// hevc_amd/csrc/api_host.cpp — C-ABI entry points that need no device: defaults, cost parameters, bitstream, the plan of a source chain.
 #include <cmath>
 #include <cstring>
 
 #include "bitstream.h"
+#include "chain_plan.h"
 
 using namespace mihevc;
 
@@ -135,6 +136,20 @@ int mihevc_encode_picture_host(const mihevc_config *cfg, int slice_type, int poc
     encode_picture(*cfg, p, v, true, &err);
     if (!err.empty()) { g_host_error = err; return MIHEVC_EINVAL; }
     return copy_out(v, buf, cap);
+}
+
+// the rules of a source chain (csrc/chain_plan.h) for a caller without a session: hevc_amd.encoder opens the session with what this says
+int mihevc_chain_plan_for(const mihevc_chain *chain, int width, int height, int bit_depth, int matrix, int sr_scale, int64_t frames, mihevc_chain_plan *out)
+{
+    if (!out || frames < 0 || !chain_check(chain, width, height, bit_depth, matrix, sr_scale)) return MIHEVC_EINVAL;
+    const ChainPlan p = chain_plan(*chain, width, height, bit_depth);
+    *out = {p.rate_num, p.rate_den, p.stages, 0, chain_pictures(*chain, frames), {}, {}, {}};
+    const bool on[4] = {p.field, p.denoise, p.resize, p.interp};
+    for (int i = 0; i < 4; i++) {
+        if (!on[i]) continue;
+        out->width[i] = i < 2 ? p.sw : p.dw; out->height[i] = i < 2 ? p.sh : p.dh; out->bit_depth[i] = i < 2 ? p.sd : p.dd;
+    }
+    return MIHEVC_OK;
 }
 
 }  // extern "C"

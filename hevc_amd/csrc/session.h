@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "bitstream.h"
+#include "chain_plan.h"
 #include "device.h"
 #include "gop_plan.h"
 #include "host_pool.h"
@@ -37,6 +38,9 @@ struct CachedBuf { CachedBlock<uint8_t> d, h; };
 
 // a source picture of the current chunk (device).  borrowed: the caller's device planes, not copied (mem is empty)
 struct Src { CachedBlock<uint8_t> mem[3]; void *p[3]; int stride[3]; int64_t pts; bool borrowed; };
+// where a kernel of the front end writes a picture, as a sink names it (source.cpp): the planes of `src`, or (a chain) of hop picture `hop` or of a
+// ring's slot; pw x ph: the coded size the kernel fills
+struct Out { Src src; int hop = -1; void *p[3] = {}; int stride[3] = {}; int pw = 0, ph = 0; };
 
 // The coefficient tables (csrc/scale_taps.h: Block is ScaleBlock or UpscaleBlock) of the last source size of a resampling entry, built and uploaded once per
 // size; the host copy lives as long as the device block it is copied from on st_pre
@@ -79,9 +83,12 @@ struct SourceFront {
     // first call; frame k lies in slot k % 3.  Copies and k_deint / k_denoise launches are neighbours on st_pre, so a slot is overwritten in stream order behind
     // the last launch that read it.  kind: the entry that filled the ring first (a pending frame keeps every other entry out until flush, so it is the only
     // one); n: frames taken; pending: the last of them has not produced its picture(s) yet (the next frame or mihevc_flush does that)
+    // The ring is a value: w x h at `depth` is what ITS pictures are (the session's ring: the session's display size and depth; a chain's rings: their
+    // stage's), rows the rows of a slot (a slot a kernel writes is rounded up to 8 as a coded picture is: the stores come in runs)
     enum { RING_NONE = 0, RING_DEINT, RING_DENOISE, RING_FIELDMATCH, RING_MCFI };
     struct Ring {
         CachedBlock<uint8_t> mem[3]; void *p[3][3] = {}; int pitch[3] = {};
+        int w = 0, h = 0, depth = 0, rows = 0;
         int64_t n = 0, pts = 0; int kind = RING_NONE; bool pending = false;
         int deint_tff = 0, deint_field_rate = 0;
         mihevc_denoise denoise_pending = {};      // the strengths of the pending frame
@@ -96,9 +103,23 @@ struct SourceFront {
     struct Fm {
         bool open = false; mihevc_fieldmatch mode = {}; CachedBlock<uint8_t> dev, host; Event ev;
         struct Frame { mihevc_fm_frame info; bool decided; };
-        std::vector<Frame> frames; std::vector<std::pair<Src, int64_t>> held;
+        std::vector<Frame> frames; std::vector<std::pair<Out, int64_t>> held;
         int64_t pictures = 0, first_pts = 0;
     } fm;
+    // mihevc_set_source_chain, mihevc_send_frame_chain: d is the descriptor, plan what csrc/chain_plan.h says of it.  ring[F], ring[D], ring[I]:
+    // one ring per temporal stage that is on, at its stage's size and depth; a stage's kernel writes the next ring's slot.  hop: pictures at the source's size and
+    // depth: kFmCycle when a decimating inverse telecine is not the last stage (it holds them where the entry holds Srcs; hop_used: which are held), then one
+    // in front of the resize stage when a kernel writes it (the held pictures are resized where they are).  The inverse telecine and the interpolator keep their state where their entries do (fm, mcfi).  ready: the blocks are allocated
+    // (the first frame); pictures: handed to the session so far, the j-th at first_pts + j; last_pts: of the last frame
+    enum { ST_F = 0, ST_D, ST_R, ST_I, ST_END };
+    struct Hop { CachedBlock<uint8_t> mem; void *p[3] = {}; int pitch[3] = {}; };
+    struct Chain {
+        bool set = false, ready = false; mihevc_chain d = {}; ChainPlan plan = {};
+        Ring ring[ST_END];
+        std::vector<Hop> hop; std::vector<char> hop_used;
+        TapTables<ScaleBlock> scale; TapTables<UpscaleBlock> upscale;
+        int64_t frames = 0, pictures = 0, first_pts = 0, last_pts = 0;
+    } chain;
 };
 
 struct mihevc_session {

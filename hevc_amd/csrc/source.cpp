@@ -5,6 +5,7 @@
 #include <cstring>
 #include <utility>
 
+#include "chain_plan.h"
 #include "fieldmatch_plan.h"
 #include "session.h"
 
@@ -80,7 +81,7 @@ int ingest(mihevc_session *s, const void *y, const void *u, const void *v, int p
 {
     if (!s || !y || !u || !v) return MIHEVC_EINVAL;
     if (s->failed) return s->fail_code;
-    if (s->flushed || s->src.ring.pending || s->src.fm.open) return MIHEVC_ESTATE;      // (a deinterlaced or denoised frame waits for its successor: no other picture may come between; fieldmatch cycles are not interleaved)
+    if (s->flushed || s->src.ring.pending || s->src.fm.open || s->src.chain.set) return MIHEVC_ESTATE;      // (a deinterlaced or denoised frame waits for its successor: no other picture may come between; fieldmatch cycles are not interleaved)
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
     Src src;
     const void *in[3] = {y, u, v};
@@ -116,62 +117,86 @@ RgbColour rgb_colour(const mihevc_session *s, const mihevc_rgb_format *fmt, bool
     return {!fmt_ok ? 0 : fmt->matrix ? fmt->matrix : s->cfg.matrix, fmt_ok && (fmt->range ? fmt->range == 2 : s->cfg.full_range != 0)};
 }
 
+using Ring = SourceFront::Ring;
+
+// What a ring stage writes its pictures to, and what becomes of them.  take: the planes of the next picture and the coded size to fill; put: its
+// kernel is launched (pts: what the stage's own entry would number it); drop: it will not go on (decimation)
+struct Sink {
+    virtual int take(Out &o) = 0;
+    virtual int put(Out &&o, int64_t pts) = 0;
+    virtual void drop(Out &&o) = 0;
+protected:
+    ~Sink() = default;
+};
+// the sink of the single entries: a Src of the session, handed to the encoder with the stage's pts
+struct SrcSink final : Sink {
+    mihevc_session *s; bool wait;
+    SrcSink(mihevc_session *s_, bool wait_) : s(s_), wait(wait_) {}
+    int take(Out &o) override
+    {
+        if (int e = take_src(s, o.src)) return e;
+        for (int c = 0; c < 3; c++) { o.p[c] = o.src.p[c]; o.stride[c] = o.src.stride[c]; }
+        o.pw = s->w; o.ph = s->h;
+        return MIHEVC_OK;
+    }
+    int put(Out &&o, int64_t pts) override { return finish_ingest(s, std::move(o.src), pts, wait); }
+    void drop(Out &&o) override { s->free_src.push_back(std::move(o.src)); }
+};
+
 // Frame k of the ring produces its picture(s): P = frame k - 1 (the first frame: itself), C = frame k, N = frame k + 1 (has_next; the last frame: itself)
 struct RingFrames { void *const *P, *const *C, *const *N; };
-RingFrames ring_take(mihevc_session *s, int64_t k, bool has_next)
+RingFrames ring_take(Ring &r, int64_t k, bool has_next)
 {
-    SourceFront::Ring &r = s->src.ring;
     r.pending = false;
     return {r.p[(k > 0 ? k - 1 : k) % 3], r.p[k % 3], r.p[(has_next ? k + 1 : k) % 3]};
 }
 
-// The picture(s) of frame k of the ring (mihevc_send_frame_deint, mihevc_send_frame_denoise): P, C, N as ring_take.  k_deint / k_denoise / k_mcfi_render write the
-// session's own planes, margin included, out of the ring.  Deinterlacing: frame-rate mode keeps the first field's rows, field-rate mode follows with the second field's
-// picture at pts + 1.  Denoising: one picture, with the strengths frame k came with.  Interpolation (mihevc_send_frame_interpolate): the vectors of the pair (C, N),
-// then `factor` pictures at pts + j; the last frame: its own picture only
-int ring_emit(mihevc_session *s, int64_t k, bool has_next, bool wait)
+// The picture(s) of frame k of ring r (mihevc_send_frame_deint, mihevc_send_frame_denoise, a chain's stages): P, C, N as ring_take.  k_deint / k_denoise /
+// k_mcfi_render write the planes the sink names, margin included, out of the ring, at the ring's size and depth.  Deinterlacing: frame-rate mode keeps the first
+// field's rows, field-rate mode follows with the second field's picture at pts + 1.  Denoising: one picture, with the strengths frame k came with.  Interpolation
+// (mihevc_send_frame_interpolate): the vectors of the pair (C, N), then `factor` pictures at pts + j; the last frame: its own picture only
+int ring_emit(mihevc_session *s, Ring &r, int64_t k, bool has_next, Sink &sink)
 {
-    SourceFront::Ring &r = s->src.ring;
-    const auto [P, C, N] = ring_take(s, k, has_next);
-    const bool denoise = r.kind == SourceFront::RING_DENOISE;
+    const auto [P, C, N] = ring_take(r, k, has_next);
+    const bool denoise = r.kind == SourceFront::RING_DENOISE, is16 = r.depth > 8;
+    const int W = r.w, H = r.h;
     if (r.kind == SourceFront::RING_MCFI) {      // the pictures between C and N; the last frame: itself (picture 0 of a blend with any N)
         mihevc_interpolate m = s->src.mcfi.pending;
         if (!has_next) m.mode = 1;
-        const int W = s->cfg.width, H = s->cfg.height;
         const McfiLayout l = mcfi_layout(W, H);
         uint8_t *const blk = s->src.mcfi.dev.get();
         if (m.mode == 0) {
-            const McfiSearchArgs a = mcfi_search_args(s->cfg.bit_depth, C[0], N[0], r.pitch[0], W, H, blk);
-            HIPCK(s, launch_mcfi_vectors(s->st_pre, a, mcfi_field_args(a, blk), s->is16));
+            const McfiSearchArgs a = mcfi_search_args(r.depth, C[0], N[0], r.pitch[0], W, H, blk);
+            HIPCK(s, launch_mcfi_vectors(s->st_pre, a, mcfi_field_args(a, blk), is16));
         }
         for (int j = 0; j < (has_next ? m.factor : 1); j++) {
-            Src src;
-            if (int e = take_src(s, src)) return e;
-            const McfiRenderArgs a = mcfi_render_args(m, j, s->cfg.bit_depth, C, N, r.pitch[0], r.pitch[1], W, H, s->w, s->h, (const int16_t *)(blk + l.v),
-                                                      (const unsigned long long *)(blk + l.dsum), src.p, src.stride);
-            HIPCK(s, launch_mcfi_render(s->st_pre, a, s->is16));
-            if (int e = finish_ingest(s, std::move(src), r.pts + j, wait)) return e;
+            Out o;
+            if (int e = sink.take(o)) return e;
+            const McfiRenderArgs a = mcfi_render_args(m, j, r.depth, C, N, r.pitch[0], r.pitch[1], W, H, o.pw, o.ph, (const int16_t *)(blk + l.v),
+                                                      (const unsigned long long *)(blk + l.dsum), o.p, o.stride);
+            HIPCK(s, launch_mcfi_render(s->st_pre, a, is16));
+            if (int e = sink.put(std::move(o), r.pts + j)) return e;
         }
         return MIHEVC_OK;
     }
     const int first = r.deint_tff ? 0 : 1;
     for (int f = 0; f <= (denoise ? 0 : r.deint_field_rate); f++) {
-        Src src;
-        if (int e = take_src(s, src)) return e;
+        Out o;
+        if (int e = sink.take(o)) return e;
         if (denoise) {
-            const DenoiseArgs a = denoise_args(r.denoise_pending, s->cfg.bit_depth, P, C, N, r.pitch[0], r.pitch[1], s->cfg.width, s->cfg.height, s->w, s->h, src.p, src.stride);
-            HIPCK(s, launch_denoise(s->st_pre, a, s->is16));
+            const DenoiseArgs a = denoise_args(r.denoise_pending, r.depth, P, C, N, r.pitch[0], r.pitch[1], W, H, o.pw, o.ph, o.p, o.stride);
+            HIPCK(s, launch_denoise(s->st_pre, a, is16));
         } else {
-            const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, r.pitch[0], r.pitch[1], s->cfg.width, s->cfg.height, s->w, s->h, f ? 1 - first : first, f, src.p, src.stride);
-            HIPCK(s, launch_deint(s->st_pre, a, s->is16));
+            const DeintArgs a = deint_args(r.depth, P, C, N, r.pitch[0], r.pitch[1], W, H, o.pw, o.ph, f ? 1 - first : first, f, o.p, o.stride);
+            HIPCK(s, launch_deint(s->st_pre, a, is16));
         }
-        if (int e = finish_ingest(s, std::move(src), r.pts + f, wait)) return e;
+        if (int e = sink.put(std::move(o), r.pts + f)) return e;
     }
     return MIHEVC_OK;
 }
 
-// decimate: the held pictures go on in order, all but the one at `drop` (-1: a partial cycle comes out whole), whose planes go back to free_src
-int fm_release(mihevc_session *s, int drop, bool wait)
+// decimate: the held pictures go on in order, all but the one at `drop` (-1: a partial cycle comes out whole), which goes back to its sink
+int fm_release(mihevc_session *s, int drop, Sink &sink)
 {
     SourceFront::Fm &fm = s->src.fm;
     auto held = std::move(fm.held);
@@ -184,24 +209,25 @@ int fm_release(mihevc_session *s, int drop, bool wait)
             auto &f = fm.frames[(size_t)held[i].second];
             f.info.dropped = dropped; f.info.picture = dropped || e ? -1 : fm.pictures; f.decided = true;
         }
-        if (dropped || e) { s->free_src.push_back(std::move(held[i].first)); continue; }
-        e = finish_ingest(s, std::move(held[i].first), fm.first_pts + fm.pictures++, wait);
+        if (dropped || e) { sink.drop(std::move(held[i].first)); continue; }
+        e = sink.put(std::move(held[i].first), fm.first_pts + fm.pictures++);
     }
     return e;
 }
 
-// Frame k of the ring is decided (mihevc_send_frame_fieldmatch): P, C, N as ring_take.  The metrics of the frame are taken on st_pre and copied to
-// pinned memory behind fm.ev; the host waits for that event only, plans (csrc/fieldmatch_plan.h) and launches the weave, or the deinterlacer, into a Src.
-// Without decimate the picture goes on with its frame's pts; with it the picture is held until its cycle's fifth frame is decided
-int fm_decide(mihevc_session *s, int64_t k, bool has_next, bool wait)
+// Frame k of ring r is decided (mihevc_send_frame_fieldmatch, a chain's field stage): P, C, N as ring_take.  The metrics of the frame are taken on
+// st_pre and copied to pinned memory behind fm.ev; the host waits for that event only, plans (csrc/fieldmatch_plan.h) and launches the weave, or the
+// deinterlacer, into the planes the sink names.  Without decimate the picture goes on with its frame's pts; with it the picture is held until its cycle's fifth
+// frame is decided
+int fm_decide(mihevc_session *s, Ring &r, int64_t k, bool has_next, Sink &sink)
 {
-    SourceFront::Ring &r = s->src.ring;
     SourceFront::Fm &fm = s->src.fm;
-    const auto [P, C, N] = ring_take(s, k, has_next);
-    const int W = s->cfg.width, H = s->cfg.height, keep = fm.mode.tff ? 0 : 1;
+    const auto [P, C, N] = ring_take(r, k, has_next);
+    const int W = r.w, H = r.h, keep = fm.mode.tff ? 0 : 1;
+    const bool is16 = r.depth > 8;
     const size_t nwg = (size_t)fm_workgroups(W, H);
     unsigned long long *const part = (unsigned long long *)fm.dev.get(), *const host = (unsigned long long *)fm.host.get();
-    HIPCK(s, launch_fm_metrics(s->st_pre, fm_args(s->cfg.bit_depth, P[0], C[0], N[0], r.pitch[0], W, H, keep, part), part + nwg * 8, s->is16));
+    HIPCK(s, launch_fm_metrics(s->st_pre, fm_args(r.depth, P[0], C[0], N[0], r.pitch[0], W, H, keep, part), part + nwg * 8, is16));
     HIPCK(s, hipMemcpyAsync(host, part + nwg * 8, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->st_pre));
     HIPCK(s, hipEventRecord(fm.ev, s->st_pre));
     HIPCK(s, hipEventSynchronize(fm.ev));
@@ -209,15 +235,15 @@ int fm_decide(mihevc_session *s, int64_t k, bool has_next, bool wait)
     if (k == 0) fm_first_frame(m);
     const int match = fm_match(m);
     const bool fallback = fm_falls_back(m, match, fm.mode.deint != 0);
-    Src src;
-    if (int e = take_src(s, src)) return e;
+    Out o;
+    if (int e = sink.take(o)) return e;
     if (fallback) {
-        const DeintArgs a = deint_args(s->cfg.bit_depth, P, C, N, r.pitch[0], r.pitch[1], W, H, s->w, s->h, keep, 0, src.p, src.stride);
-        HIPCK(s, launch_deint(s->st_pre, a, s->is16));
+        const DeintArgs a = deint_args(r.depth, P, C, N, r.pitch[0], r.pitch[1], W, H, o.pw, o.ph, keep, 0, o.p, o.stride);
+        HIPCK(s, launch_deint(s->st_pre, a, is16));
     } else {
         void *const *X = match == 0 ? C : match == 1 ? P : N;
-        const DeintArgs a = deint_args(s->cfg.bit_depth, X, C, X, r.pitch[0], r.pitch[1], W, H, s->w, s->h, keep, 0, src.p, src.stride);
-        HIPCK(s, launch_fm_weave(s->st_pre, a, s->is16));
+        const DeintArgs a = deint_args(r.depth, X, C, X, r.pitch[0], r.pitch[1], W, H, o.pw, o.ph, keep, 0, o.p, o.stride);
+        HIPCK(s, launch_fm_weave(s->st_pre, a, is16));
     }
     mihevc_fm_frame info = {};
     for (int i = 0; i < 3; i++) { info.comb_sum[i] = m.comb_sum[i]; info.comb_block[i] = m.comb_block[i]; }
@@ -227,15 +253,34 @@ int fm_decide(mihevc_session *s, int64_t k, bool has_next, bool wait)
         std::lock_guard<std::mutex> l(s->m);
         fm.frames[(size_t)k] = {info, !fm.mode.decimate};
     }
-    if (!fm.mode.decimate) { fm.pictures++; return finish_ingest(s, std::move(src), r.pts, wait); }
-    fm.held.emplace_back(std::move(src), k);
+    if (!fm.mode.decimate) { fm.pictures++; return sink.put(std::move(o), r.pts); }
+    fm.held.emplace_back(std::move(o), k);
     if ((int)fm.held.size() < kFmCycle) return MIHEVC_OK;
     FmMetrics cycle[kFmCycle] = {};
     for (int i = 0; i < kFmCycle; i++) {
         const mihevc_fm_frame &f = fm.frames[(size_t)fm.held[(size_t)i].second].info;
         cycle[i].dup_sum = f.dup_sum; cycle[i].dup_block = f.dup_block;
     }
-    return fm_release(s, fm_drop(cycle), wait);
+    return fm_release(s, fm_drop(cycle), sink);
+}
+
+// A picture of w luma samples a row and `rows` rows at es bytes a sample in one block: rows that begin 16-byte aligned (pitches in samples), planes 256-byte
+// aligned.  A ring's slot, a chain's hop picture
+hipError_t picture_alloc(mihevc_session *s, CachedBlock<uint8_t> &mem, void *(&p)[3], int (&pitch)[3], int w, int rows, size_t es)
+{
+    pitch[0] = (w + 15) & ~15; pitch[1] = pitch[2] = (w / 2 + 15) & ~15;
+    const size_t by = ((size_t)pitch[0] * rows * es + 255) & ~(size_t)255, bc = ((size_t)pitch[1] * (rows / 2) * es + 255) & ~(size_t)255;
+    if (hipError_t e = mem.alloc(s->device, by + 2 * bc, false)) return e;
+    p[0] = mem; p[1] = mem + by; p[2] = mem + by + bc;
+    return hipSuccess;
+}
+// the three slots of a ring of w x h pictures at `depth`, of `rows` rows each
+hipError_t ring_alloc(mihevc_session *s, Ring &r, int kind, int w, int h, int depth, int rows)
+{
+    for (int k = 0; k < 3; k++)
+        if (hipError_t e = picture_alloc(s, r.mem[k], r.p[k], r.pitch, w, rows, depth > 8 ? 2 : 1)) return e;
+    r.w = w; r.h = h; r.depth = depth; r.rows = rows; r.kind = kind;
+    return hipSuccess;
 }
 
 // A frame of kind `kind` (mihevc_send_frame_deint, mihevc_send_frame_denoise; the arguments are checked): into its slot of the ring, then the picture(s) of the frame
@@ -243,18 +288,10 @@ int fm_decide(mihevc_session *s, int64_t k, bool has_next, bool wait)
 int ingest_ring(mihevc_session *s, int kind, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, SrcFlags fl)
 {
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    SourceFront::Ring &r = s->src.ring;
+    Ring &r = s->src.ring;
     const size_t es = esize(s);
     const int W = s->cfg.width, H = s->cfg.height;
-    if (!r.mem[0]) {
-        r.pitch[0] = (W + 15) & ~15; r.pitch[1] = r.pitch[2] = (W / 2 + 15) & ~15;
-        const size_t by = ((size_t)r.pitch[0] * H * es + 255) & ~(size_t)255, bc = ((size_t)r.pitch[1] * (H / 2) * es + 255) & ~(size_t)255;
-        for (int k = 0; k < 3; k++) {
-            HIPCK(s, r.mem[k].alloc(s->device, by + 2 * bc, false));
-            r.p[k][0] = r.mem[k]; r.p[k][1] = r.mem[k] + by; r.p[k][2] = r.mem[k] + by + bc;
-        }
-        r.kind = kind;
-    }
+    if (!r.mem[0]) HIPCK(s, ring_alloc(s, r, kind, W, H, s->cfg.bit_depth, H));
     const int64_t k = r.n;
     const void *in[3] = {y, u, v};
     for (int c = 0; c < 3; c++)
@@ -262,8 +299,9 @@ int ingest_ring(mihevc_session *s, int kind, const void *y, const void *u, const
                                   fl.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
     r.n = k + 1;
     const bool wait = fl.wait();
+    SrcSink sink(s, wait);
     int e = MIHEVC_OK;
-    if (k > 0) e = kind == SourceFront::RING_FIELDMATCH ? fm_decide(s, k - 1, true, wait) : ring_emit(s, k - 1, true, wait);      // (ring.pts and denoise_pending are still those of frame k - 1)
+    if (k > 0) e = kind == SourceFront::RING_FIELDMATCH ? fm_decide(s, r, k - 1, true, sink) : ring_emit(s, r, k - 1, true, sink);      // (ring.pts and denoise_pending are still those of frame k - 1)
     else if (wait) HIPCK(s, hipStreamSynchronize(s->st_pre));
     else s->up_pending = true;
     r.pts = pts;
@@ -278,7 +316,7 @@ int refuse_source(const mihevc_session *s, bool args_ok, int flags, int kind = S
     if ((s->cfg.width & 1) || (s->cfg.height & 1) || s->cfg.slice_count > 1) return MIHEVC_EINVAL;      // (bands of a 4:2:2 picture: out of scope)
     if (s->failed) return s->fail_code;
     if (s->src.fm.open && kind != SourceFront::RING_FIELDMATCH) return MIHEVC_ESTATE;      // (from the first fieldmatch frame until flush)
-    return s->flushed || (s->src.ring.pending && s->src.ring.kind != kind) ? MIHEVC_ESTATE : MIHEVC_OK;
+    return s->flushed || s->src.chain.set || (s->src.ring.pending && s->src.ring.kind != kind) ? MIHEVC_ESTATE : MIHEVC_OK;      // (a chain: its own entry only)
 }
 
 // the intermediate picture of the resized route: planar 4:2:0 at 10 bit of the network's output size nw x nh, coded size rounded up to 8 as every coded
@@ -311,23 +349,21 @@ struct SrModelRef {
     int input_scale() const { return cnet ? 4 : net->scale; }      // what k_sr_input / k_sr_from_yuv are told: 2 unshuffles
     bool geometry_ok(int sw, int sh) const { return cnet ? sr_compact_geometry_ok(sw, sh) : sr_geometry_ok(net->scale, sw, sh); }
 };
-// A frame through the network (the arguments are checked, `route` is 0 or 1): the arena of the size, with the resized route the intermediate picture and the
-// tables; then input(pl, tensor) launches the kernel that writes the input tensor from the staged planes, the launches of the model follow, and k_ingest_rgb
-// over the three half planes the last layer wrote: into the session's planes, or into the intermediate picture that k_scale brings to the session's size.
-// Everything on st_pre.  An arena the device cannot hold: MIHEVC_ENOMEM, nothing launched, no planes taken, the session as it was
-template <typename Input>
-int sr_frame(mihevc_session *s, const SrModelRef model, int src_width, int src_height, int route, RgbColour col, int flags, int64_t pts, SrcPlane *planes, int n, size_t es,
-             Input &&input)
+// What sr_prepare found for a source size: the network's tensor size tw x th, its output nw x nh, where the input tensor and the last layer's output lie in the
+// arena, and the intermediate picture of the resized route
+struct SrPlan { int tw, th, nw, nh, route; size_t x_off, out_off, moff[3]; int mstride[3], mpw, mph; };
+// The arena of a source size, with the resized route (`route` 1) the intermediate picture and the tables.  An arena the device cannot hold: MIHEVC_ENOMEM,
+// nothing launched, no planes taken, the session as it was
+int sr_prepare(mihevc_session *s, const SrModelRef model, int src_width, int src_height, int route, SrPlan &pl)
 {
     SourceFront::Sr &sr = s->src.sr;
-    const SrNet *const net = model.net;
     const SrCompactNet *const cnet = model.cnet;
     const int fct = model.input_scale() == 2 ? 2 : 1, tw = src_width / fct, th = src_height / fct, W = s->cfg.width, H = s->cfg.height;
     const int nw = model.scale() * src_width, nh = model.scale() * src_height, mw = route ? nw : 0, mh = route ? nh : 0;
-    size_t off[SR_BUFS], coff[SRC_BUFS], moff[3];
-    int mstride[3], mpw, mph;
-    const size_t bytes = cnet ? sr_compact_arena_layout(cnet->scale, tw, th, coff) : sr_arena_layout(tw, th, off), mbytes = sr_mid_layout(nw, nh, moff, mstride, mpw, mph);
-    const size_t x_off = cnet ? coff[SRC_X] : off[SR_X], out_off = cnet ? coff[SRC_OUT] : off[SR_OUT];
+    size_t off[SR_BUFS], coff[SRC_BUFS];
+    const size_t bytes = cnet ? sr_compact_arena_layout(cnet->scale, tw, th, coff) : sr_arena_layout(tw, th, off), mbytes = sr_mid_layout(nw, nh, pl.moff, pl.mstride, pl.mpw, pl.mph);
+    pl.tw = tw; pl.th = th; pl.nw = nw; pl.nh = nh; pl.route = route;
+    pl.x_off = cnet ? coff[SRC_X] : off[SR_X]; pl.out_off = cnet ? coff[SRC_OUT] : off[SR_OUT];
     if (tw != sr.tw || th != sr.th || mw != sr.mw || mh != sr.mh || sr.arena.bytes() != bytes) {      // (the last: a model of the other kind or scale since)
         if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
         HIPCK(s, hipStreamSynchronize(s->st_pre));      // launches still working in the arena of the last size
@@ -337,30 +373,48 @@ int sr_frame(mihevc_session *s, const SrModelRef model, int src_width, int src_h
         if (route && sr.mid.alloc(s->device, mbytes, false) != hipSuccess) { (void)hipGetLastError(); sr.arena.reset(); return MIHEVC_ENOMEM; }
         sr.tw = tw; sr.th = th; sr.mw = mw; sr.mh = mh;
     }
-    TapTables<ScaleBlock> &tab = sr.scale;
     if (route)
-        if (int e = tab.ensure(s, nw, nh, [&](ScaleBlock &b) { return scale_block_build(nw, nh, W, H, SC_TH, SC_ROWS, b); })) return e;
-    return convert_frame(s, SrcFlags::of(flags), pts, planes, n, es, [&](Src &dst, const SrcPlane *pl) -> int {
-        uint8_t *arena = sr.arena;
-        if (int e = input(pl, (uint16_t *)(arena + x_off))) return e;
-        if (cnet) HIPCK(s, launch_sr_compact_network(s->st_pre, *cnet, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
-        else HIPCK(s, launch_sr_network(s->st_pre, *net, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), tw, th));
-        const mihevc_rgb_format halves = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
-        const uint16_t *o = (const uint16_t *)(arena + out_off);
-        if (!route) {
-            const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, s->w, s->h, s->cfg.bit_depth, dst.p, dst.stride);
-            HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
-            return MIHEVC_OK;
-        }
-        void *mid[3] = {sr.mid + moff[0], sr.mid + moff[1], sr.mid + moff[2]};
-        const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)nw * nh, o + (size_t)2 * nw * nh, nw, nw, nh, mpw, mph, 10, mid, mstride);
-        HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, true));
-        const int32_t *first[4];
-        const int16_t *coef[4];
-        tap_pointers(tab.dev.get(), tab.host.first, first); tap_pointers(tab.dev.get(), tab.host.coef, coef);
-        const ScaleArgs sa = scale_args(10, mid[0], mid[1], mid[2], mstride[0], mstride[1], nw, nh, W, H, s->w, s->h, s->cfg.bit_depth, dst.p, dst.stride, first, coef, tab.host.taps);
-        HIPCK(s, launch_scale(s->st_pre, sa, true, s->is16));
+        if (int e = sr.scale.ensure(s, nw, nh, [&](ScaleBlock &b) { return scale_block_build(nw, nh, W, H, SC_TH, SC_ROWS, b); })) return e;
+    return MIHEVC_OK;
+}
+// The input tensor is written (or on its way on st_pre): the launches of the model, then k_ingest_rgb over the three half planes the last layer wrote: into the
+// planes dp of coded size pw x ph at the session's depth, or into the intermediate picture that k_scale brings to the session's size
+int sr_launch(mihevc_session *s, const SrModelRef model, const SrPlan &pl, RgbColour col, void *const *dp, const int *dstride, int pw, int ph)
+{
+    SourceFront::Sr &sr = s->src.sr;
+    const int W = s->cfg.width, H = s->cfg.height, nw = pl.nw, nh = pl.nh;
+    uint8_t *arena = sr.arena;
+    if (model.cnet) HIPCK(s, launch_sr_compact_network(s->st_pre, *model.cnet, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), pl.tw, pl.th));
+    else HIPCK(s, launch_sr_network(s->st_pre, *model.net, arena, (const uint16_t *)sr.wdev.get(), (const float *)(sr.wdev.get() + sr.bias_off), pl.tw, pl.th));
+    const mihevc_rgb_format halves = {0, 0, 1, 2, 1, 0, 0, 0, {0, 0, 0, 0}};      // three planes of halves: R, G, B
+    const uint16_t *o = (const uint16_t *)(arena + pl.out_off);
+    if (!pl.route) {
+        const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)W * H, o + (size_t)2 * W * H, W, W, H, pw, ph, s->cfg.bit_depth, dp, dstride);
+        HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, s->is16));
         return MIHEVC_OK;
+    }
+    void *mid[3] = {sr.mid + pl.moff[0], sr.mid + pl.moff[1], sr.mid + pl.moff[2]};
+    const IngestRgbArgs a = ingest_rgb_args(halves, col.matrix, col.full, o, o + (size_t)nw * nh, o + (size_t)2 * nw * nh, nw, nw, nh, pl.mpw, pl.mph, 10, mid, pl.mstride);
+    HIPCK(s, launch_ingest_rgb(s->st_pre, a, 1, 2, true));
+    const TapTables<ScaleBlock> &tab = sr.scale;
+    const int32_t *first[4];
+    const int16_t *coef[4];
+    tap_pointers(tab.dev.get(), tab.host.first, first); tap_pointers(tab.dev.get(), tab.host.coef, coef);
+    const ScaleArgs sa = scale_args(10, mid[0], mid[1], mid[2], pl.mstride[0], pl.mstride[1], nw, nh, W, H, pw, ph, s->cfg.bit_depth, dp, dstride, first, coef, tab.host.taps);
+    HIPCK(s, launch_scale(s->st_pre, sa, true, s->is16));
+    return MIHEVC_OK;
+}
+// A frame through the network (the arguments are checked, `route` is 0 or 1): sr_prepare; then input(pl, tensor) launches the kernel that writes the input
+// tensor from the staged planes, and sr_launch follows, into the session's planes.  Everything on st_pre
+template <typename Input>
+int sr_frame(mihevc_session *s, const SrModelRef model, int src_width, int src_height, int route, RgbColour col, int flags, int64_t pts, SrcPlane *planes, int n, size_t es,
+             Input &&input)
+{
+    SrPlan plan;
+    if (int e = sr_prepare(s, model, src_width, src_height, route, plan)) return e;
+    return convert_frame(s, SrcFlags::of(flags), pts, planes, n, es, [&](Src &dst, const SrcPlane *pl) -> int {
+        if (int e = input(pl, (uint16_t *)(s->src.sr.arena.get() + plan.x_off))) return e;
+        return sr_launch(s, model, plan, col, dst.p, dst.stride, s->w, s->h);
     });
 }
 // an R'G'B' source through the network: mihevc_send_frame_sr (fit false: the session is exactly scale x the source) and mihevc_send_frame_sr_fit
@@ -385,6 +439,200 @@ int send_sr_rgb(mihevc_session *s, const mihevc_rgb_format *fmt, int src_width, 
     });
 }
 
+// ---- a chain of the filters (mihevc_set_source_chain, mihevc_send_frame_chain).  The stages are those of the single entries: ring_emit and fm_decide
+// over the chain's own rings, the resize launches over the chain's own tables, each with the geometry csrc/chain_plan.h gives its stage and a ChainSink that hands
+// the picture to the stage behind
+using Chain = SourceFront::Chain;
+constexpr int ST_F = SourceFront::ST_F, ST_D = SourceFront::ST_D, ST_R = SourceFront::ST_R, ST_I = SourceFront::ST_I, ST_END = SourceFront::ST_END;
+inline int round8(int v) { return (v + 7) & ~7; }
+
+// the first stage behind `from` that is on (from -1: the chain's first); ST_END: none
+int chain_next(const ChainPlan &p, int from)
+{
+    const bool on[ST_END] = {p.field, p.denoise, p.resize, p.interp};
+    for (int i = from + 1; i < ST_END; i++)
+        if (on[i]) return i;
+    return ST_END;
+}
+bool chain_decimates(const Chain &ch) { return ch.d.field == MIHEVC_CHAIN_FIELD_MATCH && ch.d.fieldmatch.decimate != 0; }
+int chain_push(mihevc_session *s, int stage);
+int chain_resize(mihevc_session *s, const void *const *in, const int *pitch);
+
+// The sink of stage `from` of a chain.  The last stage writes a Src, which goes to the encoder as picture j at first_pts + j.  A stage in front of a ring stage
+// writes that ring's next slot, a stage in front of the resize stage the hop picture; a decimating inverse telecine in front of either writes one of its
+// kFmCycle hop pictures, which is copied into the slot, or resized, when its cycle lets it go.  Everything is on st_pre: a slot or hop picture is written again
+// only behind the launches that read it.  Nothing here waits: mihevc_send_frame_chain does, once, at its end
+struct ChainSink final : Sink {
+    mihevc_session *s; Chain &ch; int next; bool hold;
+    ChainSink(mihevc_session *s_, int from) : s(s_), ch(s_->src.chain), next(chain_next(s_->src.chain.plan, from)), hold(from == ST_F && next != ST_END && chain_decimates(s_->src.chain)) {}
+    int take(Out &o) override
+    {
+        if (next == ST_END) return SrcSink(s, false).take(o);
+        if (hold || next == ST_R) {      // the pictures a decimating inverse telecine holds come first, the one in front of the resize stage last
+            const size_t held = chain_decimates(ch) && chain_next(ch.plan, ST_F) != ST_END ? (size_t)kFmCycle : 0;
+            size_t i = hold ? 0 : held;
+            while (hold && i < held && ch.hop_used[i]) i++;
+            if (i >= (hold ? held : ch.hop.size())) return fail(s, "mihevc_send_frame_chain: no hop picture is free");
+            ch.hop_used[i] = hold;
+            o.hop = (int)i;
+            for (int c = 0; c < 3; c++) { o.p[c] = ch.hop[i].p[c]; o.stride[c] = ch.hop[i].pitch[c]; }
+            o.pw = round8(ch.plan.sw); o.ph = round8(ch.plan.sh);
+            return MIHEVC_OK;
+        }
+        const Ring &r = ch.ring[next];
+        for (int c = 0; c < 3; c++) { o.p[c] = r.p[r.n % 3][c]; o.stride[c] = r.pitch[c]; }
+        o.pw = round8(r.w); o.ph = r.rows;
+        return MIHEVC_OK;
+    }
+    int put(Out &&o, int64_t) override
+    {
+        if (next == ST_END) return finish_ingest(s, std::move(o.src), ch.first_pts + ch.pictures++, false);
+        if (o.hop < 0) return chain_push(s, next);
+        const SourceFront::Hop &h = ch.hop[(size_t)o.hop];
+        ch.hop_used[(size_t)o.hop] = 0;
+        if (next == ST_R) return chain_resize(s, h.p, h.pitch);
+        const Ring &r = ch.ring[next];
+        const size_t es = r.depth > 8 ? 2 : 1;
+        for (int c = 0; c < 3; c++)
+            HIPCK(s, hipMemcpy2DAsync(r.p[r.n % 3][c], r.pitch[c] * es, h.p[c], h.pitch[c] * es, (c ? r.w / 2 : r.w) * es, c ? r.h / 2 : r.h, hipMemcpyDeviceToDevice, s->st_pre));
+        return chain_push(s, next);
+    }
+    void drop(Out &&o) override
+    {
+        if (o.hop >= 0) ch.hop_used[(size_t)o.hop] = 0;
+        else s->free_src.push_back(std::move(o.src));
+    }
+};
+
+// Slot n % 3 of the ring of `stage` holds a new frame (or will, in stream order): the picture(s) of the frame before it, as ingest_ring
+int chain_push(mihevc_session *s, int stage)
+{
+    Chain &ch = s->src.chain;
+    Ring &r = ch.ring[stage];
+    const int64_t k = r.n;
+    r.n = k + 1;
+    if (r.kind == SourceFront::RING_FIELDMATCH) {
+        std::lock_guard<std::mutex> l(s->m);
+        s->src.fm.frames.push_back({{}, false});
+    }
+    ChainSink sink(s, stage);
+    int e = MIHEVC_OK;
+    if (k > 0) e = r.kind == SourceFront::RING_FIELDMATCH ? fm_decide(s, r, k - 1, true, sink) : ring_emit(s, r, k - 1, true, sink);
+    r.pending = true;
+    return e;
+}
+
+// The resize stage: a picture of the source's size and depth at `in` (the hop picture, or the staged planes of a chain that begins here) into the planes its sink
+// names, at the session's size and depth, with the launch of mihevc_send_frame_scaled, mihevc_send_frame_upscaled or mihevc_send_frame_sr_yuv
+int chain_resize(mihevc_session *s, const void *const *in, const int *pitch)
+{
+    Chain &ch = s->src.chain;
+    const int W = s->cfg.width, H = s->cfg.height, sw = ch.plan.sw, sh = ch.plan.sh, sd = ch.plan.sd;
+    ChainSink sink(s, ST_R);
+    Out o;
+    if (int e = sink.take(o)) return e;
+    if (ch.d.resize == MIHEVC_CHAIN_RESIZE_SCALE) {
+        const TapTables<ScaleBlock> &tab = ch.scale;
+        const int32_t *first[4];
+        const int16_t *coef[4];
+        tap_pointers(tab.dev.get(), tab.host.first, first); tap_pointers(tab.dev.get(), tab.host.coef, coef);
+        const ScaleArgs a = scale_args(sd, in[0], in[1], in[2], pitch[0], pitch[1], sw, sh, W, H, o.pw, o.ph, s->cfg.bit_depth, o.p, o.stride, first, coef, tab.host.taps);
+        HIPCK(s, launch_scale(s->st_pre, a, sd > 8, s->is16));
+    } else if (ch.d.resize == MIHEVC_CHAIN_RESIZE_UPSCALE) {
+        const TapTables<UpscaleBlock> &tab = ch.upscale;
+        const int32_t *first[4], *near[4];
+        const int16_t *coef[4];
+        tap_pointers(tab.dev.get(), tab.host.first, first); tap_pointers(tab.dev.get(), tab.host.near, near); tap_pointers(tab.dev.get(), tab.host.coef, coef);
+        const UpscaleArgs a = upscale_args(ch.d.upscale, in[0], in[1], in[2], pitch[0], pitch[1], W, H, o.pw, o.ph, s->cfg.bit_depth, o.p, o.stride, first, near, coef);
+        HIPCK(s, launch_upscale(s->st_pre, a, sd > 8, s->is16));
+    } else {
+        const SrModelRef model(s);
+        SrPlan plan;
+        if (int e = sr_prepare(s, model, sw, sh, sr_route(s, model.scale() * sw, model.scale() * sh), plan)) return e;      // (the entry has prepared this size: nothing is allocated here)
+        HIPCK(s, launch_sr_from_yuv(s->st_pre, sr_yuv_args(ch.d.sr, model.input_scale(), in[0], in[1], in[2], pitch[0], pitch[1], (uint16_t *)(s->src.sr.arena.get() + plan.x_off)), sd > 8));
+        if (int e = sr_launch(s, model, plan, RgbColour{s->cfg.matrix, s->cfg.full_range != 0}, o.p, o.stride, o.pw, o.ph)) return e;
+    }
+    return sink.put(std::move(o), 0);
+}
+
+// the session's model serves the chain's sr stage: there is one and the session's size is on one of its two routes
+bool chain_sr_ok(const mihevc_session *s, const ChainPlan &p)
+{
+    const SrModelRef model(s);
+    return model && model.geometry_ok(p.sw, p.sh) && sr_route(s, model.scale() * p.sw, model.scale() * p.sh) >= 0;
+}
+
+// Everything a chain allocates, at its first frame (DESIGN.md §6n states the bytes): the rings of the temporal stages, the hop picture(s), the blocks of the
+// inverse telecine and of the interpolator, the tables of the resize stage or the network's arena.  A device that cannot hold them: MIHEVC_ENOMEM with nothing kept
+int chain_setup(mihevc_session *s)
+{
+    Chain &ch = s->src.chain;
+    const ChainPlan &p = ch.plan;
+    SourceFront::Fm &fm = s->src.fm;
+    const bool match = ch.d.field == MIHEVC_CHAIN_FIELD_MATCH;
+    const int first = chain_next(p, -1);
+    const bool holds = p.field && chain_next(p, ST_F) != ST_END && chain_decimates(ch);      // kFmCycle pictures held; a resize stage right behind reads them where they are
+    const size_t n_hop = (holds ? (size_t)kFmCycle : 0) + (p.resize && (p.denoise || (p.field && !holds)) ? 1 : 0);
+    // what can refuse the frame comes first (ensure keeps nothing of a size it could not build), so that no path leaves with blocks taken and the chain not ready
+    const int W = p.dw, H = p.dh;
+    if (ch.d.resize == MIHEVC_CHAIN_RESIZE_SCALE)
+        if (int e = ch.scale.ensure(s, p.sw, p.sh, [&](ScaleBlock &b) { return scale_block_build(p.sw, p.sh, W, H, SC_TH, SC_ROWS, b); })) return e;
+    if (ch.d.resize == MIHEVC_CHAIN_RESIZE_UPSCALE)
+        if (int e = ch.upscale.ensure(s, p.sw, p.sh, [&](UpscaleBlock &b) { return upscale_block_build(p.sw, p.sh, W, H, UP_TH, UP_HALO, UP_ROWS, b); })) return e;
+    if (match && !fm.ev) {
+        fm.ev = Event(hipEventDisableTiming);
+        if (!fm.ev) return fail(s, "mihevc_send_frame_chain: no event");
+    }
+    bool ok = true;
+    // a ring a kernel writes has the rows of a coded picture; the chain's first ring is filled by copies
+    if (p.field) ok = ok && ring_alloc(s, ch.ring[ST_F], match ? SourceFront::RING_FIELDMATCH : SourceFront::RING_DEINT, p.sw, p.sh, p.sd, p.sh) == hipSuccess;
+    if (p.denoise) ok = ok && ring_alloc(s, ch.ring[ST_D], SourceFront::RING_DENOISE, p.sw, p.sh, p.sd, first == ST_D ? p.sh : round8(p.sh)) == hipSuccess;
+    if (p.interp) ok = ok && ring_alloc(s, ch.ring[ST_I], SourceFront::RING_MCFI, p.dw, p.dh, p.dd, first == ST_I ? p.dh : round8(p.dh)) == hipSuccess;
+    ch.hop.resize(n_hop);
+    ch.hop_used.assign(n_hop, 0);
+    for (auto &h : ch.hop) ok = ok && picture_alloc(s, h.mem, h.p, h.pitch, p.sw, round8(p.sh), p.sd > 8 ? 2 : 1) == hipSuccess;
+    if (match) {
+        const size_t bytes = ((size_t)fm_workgroups(p.sw, p.sh) + 1) * 8 * sizeof(unsigned long long);
+        ok = ok && fm.dev.alloc(s->device, (bytes + 255) & ~(size_t)255, false) == hipSuccess && fm.host.alloc(s->device, 256, true) == hipSuccess;
+    }
+    if (p.interp) ok = ok && s->src.mcfi.dev.alloc(s->device, (mcfi_layout(p.dw, p.dh).bytes + 255) & ~(size_t)255, false) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        for (Ring &r : ch.ring)
+            for (auto &m : r.mem) m.reset();
+        ch.hop.clear();
+        fm.dev.reset(); fm.host.reset(); s->src.mcfi.dev.reset();
+        return MIHEVC_ENOMEM;
+    }
+    if (p.field && !match) { ch.ring[ST_F].deint_tff = ch.d.deint.tff; ch.ring[ST_F].deint_field_rate = ch.d.deint.field_rate; }
+    if (match) { fm.mode = ch.d.fieldmatch; fm.open = true; }
+    if (p.denoise) ch.ring[ST_D].denoise_pending = ch.d.denoise;
+    if (p.interp) s->src.mcfi.pending = ch.d.interpolate;
+    ch.ready = true;
+    return MIHEVC_OK;
+}
+
+// mihevc_flush: the stages front to back.  A stage's last frame (its successor is itself) gives its picture(s) to the stage behind, whose own last frame
+// follows; the interpolator's last frame gives its j = 0 picture
+int chain_flush(mihevc_session *s)
+{
+    Chain &ch = s->src.chain;
+    if (!ch.ready) return MIHEVC_OK;
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    for (int stage : {ST_F, ST_D, ST_I}) {
+        Ring &r = ch.ring[stage];
+        if (!r.pending) continue;
+        ChainSink sink(s, stage);
+        if (r.kind != SourceFront::RING_FIELDMATCH) {
+            if (int e = ring_emit(s, r, r.n - 1, false, sink)) return e;
+            continue;
+        }
+        if (int e = fm_decide(s, r, r.n - 1, false, sink)) return e;      // and what is left of an open cycle comes out whole
+        if (int e = fm_release(s, -1, sink)) return e;
+    }
+    return MIHEVC_OK;
+}
+
 }  // namespace
 
 template <typename Block> template <typename Build> int TapTables<Block>::ensure(mihevc_session *s, int sw_, int sh_, Build build)
@@ -404,12 +652,14 @@ template <typename Block> template <typename Build> int TapTables<Block>::ensure
 
 int source_flush(mihevc_session *s)
 {
-    const SourceFront::Ring &r = s->src.ring;
+    if (s->src.chain.set) return chain_flush(s);
+    Ring &r = s->src.ring;
     if (!r.pending) return MIHEVC_OK;
     if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
-    if (r.kind != SourceFront::RING_FIELDMATCH) return ring_emit(s, r.n - 1, false, false);
-    if (int e = fm_decide(s, r.n - 1, false, false)) return e;      // and what is left of an open cycle comes out whole
-    return fm_release(s, -1, false);
+    SrcSink sink(s, false);
+    if (r.kind != SourceFront::RING_FIELDMATCH) return ring_emit(s, r, r.n - 1, false, sink);
+    if (int e = fm_decide(s, r, r.n - 1, false, sink)) return e;      // and what is left of an open cycle comes out whole
+    return fm_release(s, -1, sink);
 }
 
 extern "C" {
@@ -677,6 +927,67 @@ int mihevc_send_frame_fieldmatch(mihevc_session *s, const mihevc_fieldmatch *d, 
         fm.frames.push_back({{}, false});
     }
     return ingest_ring(s, SourceFront::RING_FIELDMATCH, y, u, v, pitch_y, pitch_c, pts, SrcFlags::of(flags));
+}
+int mihevc_set_source_chain(mihevc_session *s, const mihevc_chain *chain)
+{
+    if (!s || s->cfg.slice_count > 1) return MIHEVC_EINVAL;
+    const SrModelRef model(s);
+    if (!chain_check(chain, s->cfg.width, s->cfg.height, s->cfg.bit_depth, s->cfg.matrix, model ? model.scale() : 0)) return MIHEVC_EINVAL;
+    if (s->failed) return s->fail_code;
+    Chain &ch = s->src.chain;
+    if (ch.set || s->flushed || s->frames_in > 0 || s->src.ring.n > 0 || s->src.fm.open || !s->pending.empty()) return MIHEVC_ESTATE;
+    const ChainPlan plan = chain_plan(*chain, s->cfg.width, s->cfg.height, s->cfg.bit_depth);
+    if (chain->resize == MIHEVC_CHAIN_RESIZE_SR && !chain_sr_ok(s, plan)) return MIHEVC_EINVAL;
+    ch.d = *chain;
+    ch.plan = plan;
+    ch.set = true;
+    return MIHEVC_OK;
+}
+// A frame through the session's chain (mihevc_send_frame_chain): into the first stage's ring, as ingest_ring, or through the staging set into the resize stage;
+// the stages hand their pictures on themselves (ChainSink)
+int mihevc_send_frame_chain(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags)
+{
+    if (!s) return MIHEVC_EINVAL;
+    Chain &ch = s->src.chain;
+    const bool args_ok = y && u && v && (!ch.set || (pitch_y >= ch.plan.sw && pitch_c >= ch.plan.sw / 2 && (ch.frames == 0 || pts > ch.last_pts)));
+    if (!args_ok || (flags & ~(MIHEVC_SRC_DEVICE | MIHEVC_SRC_ASYNC))) return MIHEVC_EINVAL;
+    if (s->failed) return s->fail_code;
+    if (!ch.set || s->flushed) return MIHEVC_ESTATE;
+    if (ch.d.resize == MIHEVC_CHAIN_RESIZE_SR && !chain_sr_ok(s, ch.plan)) return MIHEVC_EINVAL;      // (the model was dropped or replaced since)
+    if (hipSetDevice(s->device) != hipSuccess) return MIHEVC_EDEVICE;
+    if (!ch.ready)
+        if (int e = chain_setup(s)) return e;
+    if (ch.d.resize == MIHEVC_CHAIN_RESIZE_SR) {      // the arena of this size: MIHEVC_ENOMEM before anything is launched
+        const SrModelRef model(s);
+        SrPlan plan;
+        if (int e = sr_prepare(s, model, ch.plan.sw, ch.plan.sh, sr_route(s, model.scale() * ch.plan.sw, model.scale() * ch.plan.sh), plan)) return e;
+    }
+    const SrcFlags fl = SrcFlags::of(flags);
+    const ChainPlan &p = ch.plan;
+    const size_t es = p.sd > 8 ? 2 : 1;
+    const int first = chain_next(p, -1);
+    if (ch.frames == 0) ch.first_pts = pts;
+    ch.frames++;
+    ch.last_pts = pts;
+    int e;
+    if (first == ST_R) {
+        SrcPlane planes[3] = {{y, p.sw, p.sh, pitch_y}, {u, p.sw / 2, p.sh / 2, pitch_c}, {v, p.sw / 2, p.sh / 2, pitch_c}};
+        if (int e2 = stage_planes(s, planes, 3, es, fl.device)) return e2;
+        const void *in[3] = {planes[0].p, planes[1].p, planes[2].p};
+        const int pitch[3] = {planes[0].pitch, planes[1].pitch, planes[2].pitch};
+        e = chain_resize(s, in, pitch);
+    } else {
+        const Ring &r = ch.ring[first];
+        const void *in[3] = {y, u, v};
+        for (int c = 0; c < 3; c++)
+            HIPCK(s, hipMemcpy2DAsync(r.p[r.n % 3][c], r.pitch[c] * es, in[c], (c ? pitch_c : pitch_y) * es, (c ? r.w / 2 : r.w) * es, c ? r.h / 2 : r.h,
+                                      fl.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st_pre));
+        e = chain_push(s, first);
+    }
+    if (e) return e;
+    if (fl.wait()) HIPCK(s, hipStreamSynchronize(s->st_pre));      // once, behind whatever the stages launched: the caller's planes are free
+    else s->up_pending = true;
+    return MIHEVC_OK;
 }
 int mihevc_get_fieldmatch_info(mihevc_session *s, int64_t frame, mihevc_fm_frame *out)
 {

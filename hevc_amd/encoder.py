@@ -307,6 +307,38 @@ class Encoder:
         self._pts = pts + m.factor
         self._check(self._lib.mihevc_send_frame_interpolate(self._s, C.byref(m), ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_interpolate")
 
+    def set_chain(self, width: int, height: int, bit_depth: Optional[int] = None, **stages):
+        """mihevc_set_source_chain: the source filters in series, set once before the first frame; every frame then goes through send_chain and no
+        other send_*.  width, height, bit_depth (None: the session's): the source.  The stages, in their fixed order, are the keywords of _lib.chain: field=None |
+        'deint' (tff, field_rate) | 'fieldmatch' (tff, decimate, fm_deint); denoise=None | a level or four thresholds; resize=None | 'scale' | 'upscale' (sharpen,
+        antiring) | 'sr' (sr_matrix, sr_full_range; the model of set_sr_model, set before this call); interpolate=None | 2 .. 4 (interp_mode, scene_threshold).  A
+        _lib.Chain as the only stage argument `chain=` is taken as it is.  Returns the _lib.Chain."""
+        c = stages.pop("chain") if "chain" in stages else _lib.chain(width, height, self.cfg.bit_depth if bit_depth is None else bit_depth, **stages)
+        self._check(self._lib.mihevc_set_source_chain(self._s, C.byref(c)), "set_source_chain")
+        self._chain = c
+        return c
+
+    def send_chain(self, y, u, v, pts: Optional[int] = None, asynchronous: bool = False):
+        """mihevc_send_frame_chain: a planar 4:2:0 frame of the chain's source size and depth through the chain of set_chain.  The pictures are numbered
+        consecutively from the first frame's pts: the session is opened at the source's rate times the chain's (_lib.chain_plan).  What comes out when is the
+        stages' own: every temporal stage holds its last frame back until the next one arrives, and flush() drains them front to back.  numpy planes are checked
+        for shape and type here; torch tensors on the device are read where they are (MIHEVC_SRC_DEVICE) under the rules of send_fmt.  asynchronous (host planes):
+        the rules of send_async."""
+        c = getattr(self, "_chain", None)
+        if c is None:
+            raise _lib.MihevcError(_lib.ESTATE, "send_chain without set_chain")
+        planes = [y, u, v]
+        shapes = [(c.height, c.width)] + [(c.height // 2, c.width // 2)] * 2
+        if any(p is None or tuple(p.shape) != s for p, s in zip(planes, shapes)):
+            raise ValueError(f"plane shapes {[None if p is None else tuple(p.shape) for p in planes]} do not match {shapes} of {c!r}")
+        es = 1 if c.bit_depth == 8 else 2
+        ptrs, pitches, flags = self._source_planes(c, planes, np.dtype(np.uint8 if es == 1 else np.uint16), es, None, asynchronous, "send_chain")
+        if pitches[1] != pitches[2]:
+            raise ValueError("the two chroma planes must share one pitch")
+        pts = self._pts if pts is None else pts
+        self._pts = pts + 1
+        self._check(self._lib.mihevc_send_frame_chain(self._s, ptrs[0], ptrs[1], ptrs[2], pitches[0], pitches[1], pts, flags), "send_frame_chain")
+
     def set_lut3d(self, table):
         """mihevc_set_lut3d: the 3D colour table send_lut3d interpolates in: an (n, n, n, 3) array indexed [b][g][r][c], the order of a .cube
         file, 2 <= n <= 65; uint16 entries 0 .. 65535, or floats in [0, 1] that go through lut3d.quantise first.  It is copied before the call returns and may be
@@ -895,11 +927,249 @@ def remux_audio(video_mp4: Path, source: Path, out_path: Path, info: VideoInfo) 
         return False
 
 
+def _parse_upscale(upscale, sw: int, sh: int) -> Tuple[int, int]:
+    """upscale= of encode_file: (w, h), a target height, or 'auto' for upscale_target's rule -> the target size.  ValueError / TypeError / IndexError otherwise"""
+    if isinstance(upscale, str):
+        if upscale != 'auto':
+            raise ValueError(upscale)
+        return upscale_target(sw, sh, 0)
+    if isinstance(upscale, int) and not isinstance(upscale, bool):
+        if upscale < 1:
+            raise ValueError(upscale)
+        return upscale_target(sw, sh, upscale)
+    target = (int(upscale[0]), int(upscale[1]))
+    if len(upscale) != 2:
+        raise ValueError(upscale)
+    return target
+
+
+def _load_sr(sr_model, sr_denoise):
+    """sr_model= / sr_denoise= of encode_file -> an hevc_amd.sr.RrdbNet or CompactNet: a model as it is, a path or state dict loaded, a pair blended by
+    sr_denoise.  Raises what the loaders raise, and ValueError for a pair without its strength or a strength without its pair"""
+    from . import sr as sr_mod
+    one = lambda m: m if isinstance(m, (sr_mod.RrdbNet, sr_mod.CompactNet)) else sr_mod.load_model(m)
+    if isinstance(sr_model, (tuple, list)):
+        if len(sr_model) != 2 or sr_denoise is None or isinstance(sr_denoise, bool):
+            raise ValueError("a pair (model, denoise partner) goes with sr_denoise = 0 .. 1")
+        return sr_mod.blend(one(sr_model[0]), one(sr_model[1]), sr_denoise)
+    if sr_denoise is not None:
+        raise ValueError("sr_denoise= goes with a pair (model, denoise partner) of compact models")
+    return one(sr_model)
+
+
+def _field_order(file_path: Path, tff, deinterlace: str):
+    """the field order of deinterlace=: tff when given, else the y4m header's It / Ib tag or ffprobe's field_order; a source that names none is top field first,
+    but for 'auto', which then does nothing (None)"""
+    from . import yuvio
+    order = tff
+    if order is None:
+        suffix = Path(file_path).suffix.lower()
+        if suffix == '.y4m':
+            probe_clip = yuvio.open_clip(Path(file_path))
+            order = {'t': True, 'b': False}.get(probe_clip.interlace)
+            probe_clip.close()
+        elif suffix != '.yuv':
+            from .probe import probe_field_order
+            order = probe_field_order(Path(file_path))
+        if order is None and deinterlace != 'auto':
+            order = True
+    return order
+
+
+def _sr_source_colour(info: VideoInfo, clip, height: int):
+    """(matrix, full range) of a Y'CbCr source on its way into the network: the probed matrix, BT.601 below 720 lines and BT.709 from there on when the probe does
+    not know it; yuvj* files read directly are full range (the pipe hands yuvj* over as limited range)"""
+    from . import yuvio
+    matrix = _COLOUR_CODES["matrix"].get(info.color_space, 0)
+    if matrix not in (1, 5, 6, 9):
+        matrix = 6 if height < 720 else 1
+    return matrix, (info.pix_fmt or '').lower().startswith('yuvj') and not isinstance(clip, yuvio._PipeClip)
+
+
+def _carry_audio(wants_audio: bool, video_path: Path, file_path: Path, out_path: Path, info: VideoInfo) -> bool:
+    """the end of an encode, the video track written: a source with audio gets its audio carried over.  False: the remux failed"""
+    if not wants_audio:
+        return True
+    good = remux_audio(video_path, Path(file_path), Path(out_path), info)
+    try:
+        video_path.unlink()
+    except OSError:
+        pass
+    if not good:
+        logger.warning("%s: audio could not be carried over (ffmpeg remux failed); falling back to the ffmpeg path", Path(file_path).name)
+    return good
+
+
+CHAIN_KEYS = ("deinterlace", "tff", "denoise", "size", "upscale", "sr_model", "sr_target", "sr_denoise", "sharpen", "antiring", "interpolate", "interp_mode")
+
+
+def _encode_file_chain(file_path: Path, out_path: Path, info: VideoInfo, progress_callback, total_frames: int, stop_event, device, chain) -> int:
+    """encode_file(chain=...): the options of the dict become one _lib.Chain, the session opens at what mihevc_chain_plan_for says of it, every frame goes through
+    Encoder.send_chain.  Everything is judged before the session is opened"""
+    import copy
+    from fractions import Fraction
+    from . import mp4, yuvio
+    from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
+    name = Path(file_path).name
+    if not isinstance(chain, dict) or set(chain) - set(CHAIN_KEYS):
+        logger.error("%s: chain= takes a dict with keys out of %s", name, ", ".join(CHAIN_KEYS))
+        return 1
+    opt = {k: chain.get(k) for k in CHAIN_KEYS}
+    sw0, sh0 = int(info.width), int(info.height)
+    kw = {}
+    # field
+    deinterlace = opt["deinterlace"]
+    if deinterlace is not None:
+        if deinterlace not in ('frame', 'field', 'auto', 'ivtc', 'match'):
+            logger.error("%s: chain: deinterlace=%r takes 'frame', 'field', 'auto', 'ivtc' or 'match'", name, deinterlace)
+            return 1
+        order = _field_order(file_path, opt["tff"], deinterlace)
+        if deinterlace in ('ivtc', 'match'):
+            kw.update(field="fieldmatch", tff=bool(order), decimate=deinterlace == 'ivtc', fm_deint=True)
+        elif order is not None:
+            kw.update(field="deint", tff=bool(order), field_rate=deinterlace == 'field')
+    elif opt["tff"] is not None:
+        logger.error("%s: chain: tff= goes with deinterlace=", name)
+        return 1
+    # denoise
+    dn = opt["denoise"]
+    if dn is not None and not (isinstance(dn, int) and not isinstance(dn, bool) and dn == 0):
+        try:
+            kw["denoise"] = _lib.denoise_strength(dn)
+        except (TypeError, ValueError):
+            logger.error("%s: chain: denoise=%r takes a level 0 .. 3 or four thresholds 0 .. 255", name, dn)
+            return 1
+    # resize
+    if sum(opt[k] is not None for k in ("size", "upscale", "sr_model")) > 1:
+        logger.error("%s: chain: one of size=, upscale=, sr_model=", name)
+        return 1
+    target, sr = (sw0, sh0), None
+    sharpen, antiring = (8 if opt[k] is None else opt[k] for k in ("sharpen", "antiring"))
+    if opt["upscale"] is None and (opt["sharpen"] is not None or opt["antiring"] is not None):
+        logger.error("%s: chain: sharpen= and antiring= go with upscale=", name)
+        return 1
+    if opt["sr_model"] is None and (opt["sr_target"] is not None or opt["sr_denoise"] is not None):
+        logger.error("%s: chain: sr_target= and sr_denoise= go with sr_model=", name)
+        return 1
+    try:
+        if opt["size"] is not None:
+            target = (int(opt["size"][0]), int(opt["size"][1]))
+            if len(opt["size"]) != 2:
+                raise ValueError(opt["size"])
+            kw["resize"] = "scale"
+        elif opt["upscale"] is not None:
+            if any(isinstance(x, bool) or not isinstance(x, int) for x in (sharpen, antiring)):
+                raise ValueError("sharpen / antiring")
+            target = _parse_upscale(opt["upscale"], sw0, sh0)
+            kw.update(resize="upscale", sharpen=sharpen, antiring=antiring)
+        elif opt["sr_model"] is not None:
+            sr = _load_sr(opt["sr_model"], opt["sr_denoise"])
+            target = sr_target_size(sw0, sh0, sr.scale, opt["sr_target"])
+            kw["resize"] = "sr"
+    except (OSError, ValueError, TypeError, RuntimeError, KeyError, IndexError) as e:
+        logger.error("%s: chain: the resize stage: %s", name, e)
+        return 1
+    # interpolate
+    if opt["interpolate"] is not None:
+        kw.update(interpolate=opt["interpolate"], interp_mode='mc' if opt["interp_mode"] is None else opt["interp_mode"])
+    elif opt["interp_mode"] is not None:
+        logger.error("%s: chain: interp_mode= goes with interpolate=", name)
+        return 1
+    clip = yuvio.open_any(Path(file_path), info, native_formats=True, rgb_formats=False)
+    mux = None
+    ok = False
+    try:
+        fmt = getattr(clip, 'src_format', None)
+        planar420 = getattr(clip, 'rgb_format', None) is None and (fmt is None or (fmt.chroma == 420 and not fmt.semi_planar and not fmt.msb_aligned))
+        src_depth = int(fmt.bit_depth) if fmt is not None else int(clip.bit_depth)
+        if not planar420 or src_depth not in (8, 10):
+            logger.error("%s: chain= takes a planar 4:2:0 source at 8 or 10 bit (%r)", name, fmt)
+            return 1
+        sw, sh = int(clip.width), int(clip.height)
+        out_info = copy.copy(info)
+        out_info.width, out_info.height = int(target[0]), int(target[1])
+        if src_depth > 8 and bit_depth_of(out_info) == 8:      # the file's own header outranks the probe, as in encode_file
+            out_info.pix_fmt = 'yuv420p10le'
+        depth = bit_depth_of(out_info)
+        if sr is not None:
+            sr_matrix, sr_full = _sr_source_colour(info, clip, sh)
+            kw.update(sr_matrix=sr_matrix, sr_full_range=sr_full)
+        try:
+            c = _lib.chain(sw, sh, src_depth, **kw)
+        except (TypeError, ValueError) as e:
+            logger.error("%s: chain: %s", name, e)
+            return 1
+        n_src = clip.n_frames or total_frames
+        matrix = _COLOUR_CODES["matrix"].get(out_info.color_space, 0)
+        if sr is not None and matrix not in (1, 5, 6, 9):
+            matrix = sr_matrix
+        plan = _lib.chain_plan(c, out_info.width, out_info.height, depth, matrix if sr is not None else 1, sr.scale if sr is not None else 0, int(n_src or 0))
+        if plan is None:
+            logger.error("%s: chain: %r in front of a %dx%d session at %d bit is not a chain the device takes (no stage on, a size, ratio or strength out of range)",
+                         name, c, out_info.width, out_info.height, depth)
+            return 1
+        rate = Fraction(plan.rate_num, plan.rate_den)
+        exact = Fraction(str(info.fps or 30.0)).limit_denominator(1001) * rate
+        out_info.fps = float(info.fps or 30.0) * float(rate) if rate.denominator == 1 else float(exact)
+        nb = int(getattr(info, 'nb_frames', 0) or 0)
+        out_info.nb_frames = int(_lib.chain_plan(c, out_info.width, out_info.height, depth, matrix if sr is not None else 1, sr.scale if sr is not None else 0, nb).pictures)
+        crf, _cq, maxrate, bufsize, gop = calculate_dynamic_values(out_info)
+        level, tier = calculate_apple_hevc_level(out_info)
+        cfg = config_for(out_info, crf, maxrate, bufsize, gop, level, tier)
+        if rate.denominator != 1:
+            cfg.fps_num, cfg.fps_den = exact.numerator, exact.denominator
+        if sr is not None and cfg.matrix not in (1, 5, 6, 9):
+            cfg.matrix = sr_matrix
+        total = int(plan.pictures)
+        wants_audio = bool(info.audio_channels and info.audio_channels > 0) and Path(file_path).suffix.lower() not in ('.y4m', '.yuv')
+        video_path = Path(out_path).with_suffix('.video.mp4') if wants_audio else Path(out_path)
+        mux = mp4.Mp4Writer(video_path, cfg)
+        n_out = 0
+
+        def progress():
+            if progress_callback:
+                try:
+                    progress_callback(name, n_out, total)
+                except Exception:
+                    logger.debug("progress_callback raised", exc_info=True)
+
+        with Encoder(cfg, device=device or 0) as enc:
+            if sr is not None:
+                enc.set_sr_model(sr)
+            enc.set_chain(sw, sh, src_depth, chain=c)
+            for i, planes in enumerate(clip.frames()):
+                if stop_event is not None and stop_event.is_set():
+                    return 1
+                enc.send_chain(*planes, pts=i)
+                for data, pts, key, dts in enc.packets_dts():
+                    mux.add_sample(data, pts, key, dts)
+                    n_out += 1
+                progress()
+            enc.flush()
+            for data, pts, key, dts in enc.packets_dts():
+                mux.add_sample(data, pts, key, dts)
+                n_out += 1
+            progress()
+            headers = enc.headers()
+        if n_out == 0:
+            return 1
+        mux.finish(headers)
+        mux = None
+        if not _carry_audio(wants_audio, video_path, file_path, out_path, out_info):
+            return 1
+        ok = True
+        return 0
+    finally:
+        if mux is not None and not ok:
+            mux.abort()
+        clip.close()
+
+
 def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callback: Optional[Callable[[str, int, int], None]] = None,
                 total_frames: int = 1, stop_event: Optional[threading.Event] = None, device: Optional[int] = None, debug: bool = False,
                 devices=None, row_split: bool = False, native_rgb: bool = False, size=None, deinterlace: Optional[str] = None,
                 tff: Optional[bool] = None, denoise=None, lut=None, lut_bit_depth: int = 8, interpolate: Optional[int] = None, interp_mode: str = 'mc',
-                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None, sr_target=None, sr_denoise=None) -> int:
+                upscale=None, sharpen: int = 8, antiring: int = 8, sr_model=None, sr_target=None, sr_denoise=None, chain: Optional[dict] = None) -> int:
     """Encode `file_path` to `out_path` (MP4/hvc1) on an MI355X.  Returns 0 on success, 1 on failure/cancel —
     the same (returncode) shape `run_ffmpeg` gives `convert_video` (core/transcoder.py:497-535).  native_rgb: a container probed as one of the RGB pixel
     formats of _lib.rgb_format_for is decoded to that format and converted on the device (Encoder.send_rgb) instead of by swscale; the session signals the
@@ -938,7 +1208,19 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
     (yuvj* files read directly are full range; the pipe hands yuvj* over as limited range).  Any other format (4:2:2, 4:4:4, semi-planar) is refused by name.
     sr_target: None: the session, its level and the MP4 track open at scale x the source size.  'auto', a height or (w, h) (sr_target_size): they open at that
     size and the network's picture is scaled down to it on the device; 'auto' is what the reference's restoration tool does.  sr_target without sr_model is
-    refused.  One device; not together with any other source filter, size= or upscale=.  There is no tiling: a frame the device cannot hold ends the run."""
+    refused.  One device; not together with any other source filter, size= or upscale=.  There is no tiling: a frame the device cannot hold ends the run.
+    chain: a dict of the options above that go TOGETHER (Encoder.set_chain / send_chain): deinterlace= and tff=, denoise=, one of size= | upscale=
+    (sharpen=, antiring=) | sr_model= (sr_target=, sr_denoise=), interpolate= and interp_mode=, each meaning what the option of that name means; the filters run
+    in that fixed order on the device, field and denoise at the source's size, interpolation at the session's.  The session's size, level, rate figures, the
+    progress total and the MP4 track follow the chain's size and rate (hevc_amd/csrc/chain_plan.h); 'ivtc' sets the rate as an exact fraction.  Planar 4:2:0
+    sources at 8 or 10 bit on one device; chain= together with any of those options outside the dict, with native_rgb, lut= or several devices is refused.
+    chain=dict(denoise=n, sr_model=p, sr_target='auto', interpolate=k) is the whole process_video of the reference's restoration tool on the device."""
+    if chain is not None:
+        if (size is not None or deinterlace is not None or tff is not None or denoise is not None or lut is not None or interpolate is not None or upscale is not None
+                or sr_model is not None or sr_target is not None or sr_denoise is not None or native_rgb or row_split or (devices and len(devices) > 1)):
+            logger.error("%s: chain= takes its filters inside the dict, one device, and none of native_rgb, lut=", Path(file_path).name)
+            return 1
+        return _encode_file_chain(file_path, out_path, info, progress_callback, total_frames, stop_event, device, chain)
     import copy
     from . import mp4, yuvio
     from .transcoder import calculate_apple_hevc_level, calculate_dynamic_values
@@ -963,18 +1245,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                          "denoise=, lut=, interpolate=", Path(file_path).name, upscale)
             return 1
         try:
-            if isinstance(upscale, str):
-                if upscale != 'auto':
-                    raise ValueError(upscale)
-                target = upscale_target(sw0, sh0, 0)
-            elif isinstance(upscale, int) and not isinstance(upscale, bool):
-                if upscale < 1:
-                    raise ValueError(upscale)
-                target = upscale_target(sw0, sh0, upscale)
-            else:
-                target = (int(upscale[0]), int(upscale[1]))
-                if len(upscale) != 2:
-                    raise ValueError(upscale)
+            target = _parse_upscale(upscale, sw0, sh0)
         except (TypeError, ValueError, IndexError):
             logger.error("%s: upscale=%r takes (w, h), a height or 'auto'", Path(file_path).name, upscale)
             return 1
@@ -989,17 +1260,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if (size is not None or deinterlace is not None or denoise is not None or lut is not None or interpolate is not None or (devices and len(devices) > 1)):
             logger.error("%s: sr_model= takes one device and none of size=, upscale=, deinterlace=, denoise=, lut=, interpolate=", Path(file_path).name)
             return 1
-        from . import sr as sr_mod
         try:
-            one = lambda m: m if isinstance(m, (sr_mod.RrdbNet, sr_mod.CompactNet)) else sr_mod.load_model(m)
-            if isinstance(sr_model, (tuple, list)):
-                if len(sr_model) != 2 or sr_denoise is None or isinstance(sr_denoise, bool):
-                    raise ValueError("a pair (model, denoise partner) goes with sr_denoise = 0 .. 1")
-                sr = sr_mod.blend(one(sr_model[0]), one(sr_model[1]), sr_denoise)
-            else:
-                sr = one(sr_model)
-                if sr_denoise is not None:
-                    raise ValueError("sr_denoise= goes with a pair (model, denoise partner) of compact models")
+            sr = _load_sr(sr_model, sr_denoise)
         except (OSError, ValueError, TypeError, RuntimeError, KeyError) as e:
             logger.error("%s: sr_model: %s", Path(file_path).name, e)
             return 1
@@ -1070,18 +1332,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
         if deinterlace not in ('frame', 'field', 'auto', 'ivtc', 'match') or size is not None or native_rgb or (devices and len(devices) > 1):
             logger.error("%s: deinterlace=%r takes 'frame', 'field', 'auto', 'ivtc' or 'match', one device, and neither size= nor native_rgb", Path(file_path).name, deinterlace)
             return 1
-        order = tff
-        if order is None:
-            suffix = Path(file_path).suffix.lower()
-            if suffix == '.y4m':
-                probe_clip = yuvio.open_clip(Path(file_path))
-                order = {'t': True, 'b': False}.get(probe_clip.interlace)
-                probe_clip.close()
-            elif suffix != '.yuv':
-                from .probe import probe_field_order
-                order = probe_field_order(Path(file_path))
-            if order is None and deinterlace != 'auto':
-                order = True
+        order = _field_order(file_path, tff, deinterlace)
         if deinterlace in ('ivtc', 'match'):
             ivtc = (bool(order), deinterlace == 'ivtc')
             if ivtc[1]:
@@ -1133,10 +1384,7 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
                 if not planar420 or sr_depth not in (8, 10, 12) or src_size[0] % 2 or src_size[1] % 2:
                     logger.error("%s: sr_model= takes a planar 4:2:0 Y'CbCr source at 8, 10 or 12 bit with even sides (%r)", Path(file_path).name, fmt)
                     return 1
-                sr_matrix = _COLOUR_CODES["matrix"].get(info.color_space, 0)
-                if sr_matrix not in (1, 5, 6, 9):
-                    sr_matrix = 6 if src_size[1] < 720 else 1
-                sr_full = sr_name.startswith('yuvj') and not isinstance(clip, yuvio._PipeClip)      # (the pipe asks swscale for limited range)
+                sr_matrix, sr_full = _sr_source_colour(info, clip, src_size[1])
                 if cfg.matrix not in (1, 5, 6, 9):
                     cfg.matrix = sr_matrix
                 fmt = None
@@ -1251,15 +1499,8 @@ def encode_file(file_path: Path, out_path: Path, info: VideoInfo, progress_callb
             return 1
         mux.finish(headers)
         mux = None
-        if wants_audio:
-            good = remux_audio(video_path, Path(file_path), Path(out_path), info)
-            try:
-                video_path.unlink()
-            except OSError:
-                pass
-            if not good:
-                logger.warning("%s: audio could not be carried over (ffmpeg remux failed); falling back to the ffmpeg path", Path(file_path).name)
-                return 1
+        if not _carry_audio(wants_audio, video_path, file_path, out_path, info):
+            return 1
         ok = True
         return 0
     finally:

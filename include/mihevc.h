@@ -501,6 +501,70 @@ typedef struct mihevc_sr_compact {
  * model, a scale other than 4 / 2, convs outside 1 .. 64, non-zero reserved, NULL weights, a count other than the model's, slice_count > 1.  MIHEVC_ENOMEM: the
  * device cannot hold the weights; the session has no model then */
 int  mihevc_set_sr_compact(mihevc_session *s, const mihevc_sr_compact *model, const float *weights, size_t count);
+/* ---- added under ABI 6: a CHAIN of the source filters (symbols only) ----
+ * The filters above in series, in one fixed order, every frame of the session through all of them (hevc_amd/csrc/chain_plan.h states the rules):
+ *   field        none, the deinterlacer (mihevc_send_frame_deint) or inverse telecine (mihevc_send_frame_fieldmatch)    at the source's size and depth
+ *   denoise      off, or the four thresholds of mihevc_send_frame_denoise                                             at the source's size and depth
+ *   resize       none, mihevc_send_frame_scaled, mihevc_send_frame_upscaled, or the session's network on the route of   the source's size and depth to the
+ *                mihevc_send_frame_sr_yuv (the model of mihevc_set_sr_model / mihevc_set_sr_compact)                    session's
+ *   interpolate  off, or mihevc_send_frame_interpolate                                                                at the session's size and depth
+ * Every slot is optional and at least one is on.  A stage's picture is the next stage's frame, on the device, with the arithmetic of the single entries: a
+ * chain's stream is that of a session fed, through mihevc_send_frame, the pictures the filters' definitions give one after the other.  The source is planar
+ * 4:2:0 at 8 or 10 bit with even sides of at least 16, its height a multiple of 4 when the field slot is on; without a resize stage its size and depth are the
+ * session's.  Not covered: any other order or a graph of filters, the colour table, format or RGB conversion inside a chain, a resize in front of the field or
+ * denoise stage, a chain that changes from frame to frame, sliced sessions and several devices, two stages in one kernel. */
+#define MIHEVC_CHAIN_FIELD_NONE  0
+#define MIHEVC_CHAIN_FIELD_DEINT 1
+#define MIHEVC_CHAIN_FIELD_MATCH 2
+#define MIHEVC_CHAIN_RESIZE_NONE    0
+#define MIHEVC_CHAIN_RESIZE_SCALE   1
+#define MIHEVC_CHAIN_RESIZE_UPSCALE 2
+#define MIHEVC_CHAIN_RESIZE_SR      3
+typedef struct mihevc_chain {
+    int32_t width, height;        /* the source picture: both even, >= 16 */
+    int32_t bit_depth;            /* of the source: 8 or 10 */
+    int32_t field;                /* MIHEVC_CHAIN_FIELD_* */
+    int32_t denoise_on;           /* 0, 1 */
+    int32_t resize;               /* MIHEVC_CHAIN_RESIZE_* */
+    int32_t interpolate_on;       /* 0, 1 */
+    int32_t reserved[9];          /* 0 */
+    mihevc_deint deint;                /* field == MIHEVC_CHAIN_FIELD_DEINT */
+    mihevc_fieldmatch fieldmatch;      /* field == MIHEVC_CHAIN_FIELD_MATCH */
+    mihevc_denoise denoise;            /* denoise_on */
+    mihevc_upscale_src upscale;        /* resize == MIHEVC_CHAIN_RESIZE_UPSCALE: sharpen, antiring; width, height and bit_depth repeat the chain's */
+    mihevc_sr_yuv sr;                  /* resize == MIHEVC_CHAIN_RESIZE_SR: matrix, full_range of the source; width, height and bit_depth repeat the chain's */
+    mihevc_interpolate interpolate;    /* interpolate_on */
+} mihevc_chain;
+/* The chain of the session, set once, before the first frame: the descriptor is copied.  Everything is judged before any device call.  MIHEVC_EINVAL, leaving
+ * the session usable: NULL, non-zero reserved, a selector out of range, no slot on, a source side odd, below 16 or above 8192, a depth other than 8 / 10 (the
+ * session's included), a height that is no multiple of 4 with a field stage, whatever the entry of a stage that is on refuses in its struct, a size or depth other
+ * than the session's without a resize stage, a ratio the resize stage's entry refuses, MIHEVC_CHAIN_RESIZE_SR without a model or with a cfg.matrix other than
+ * 1 / 5 / 6 / 9, width / height / bit_depth of the embedded upscale or sr struct other than the chain's, odd cfg.width / cfg.height, slice_count > 1.  The
+ * embedded structs of slots that are off are not looked at.  MIHEVC_ESTATE: a frame has been sent by any entry, a chain is already set, after flush. */
+int  mihevc_set_source_chain(mihevc_session *s, const mihevc_chain *chain);
+/* A frame of the chain's source size and depth through the chain.  pitch_y, pitch_c: in elements.  Flags, ownership and staging are those of
+ * mihevc_send_frame_deint: the frame is copied into the first stage's ring (a chain that begins with its resize stage: into the staging set) on the upload
+ * stream, host planes may be reused on return unless MIHEVC_SRC_ASYNC is set, device planes (MIHEVC_SRC_DEVICE) after mihevc_sync_uploads or mihevc_flush.
+ * Pictures are numbered consecutively from the first frame's pts, as decimating inverse telecine numbers them: the caller opens the session at the source's
+ * rate times the chain's (field rate x2, decimate x4/5, interpolate x factor).  The pts of later frames must increase and are otherwise ignored.
+ * mihevc_stats.frames_in counts pictures; mihevc_get_fieldmatch_info works for a chain with an inverse telecine stage.  Rings, hop pictures and the network's
+ * arena are allocated at the first frame, nothing per frame; MIHEVC_ENOMEM when the device cannot hold them, before any picture is taken, and the session goes
+ * on.  mihevc_flush drains the stages front to back: the field stage's last frame goes into denoise, denoise's last into resize and interpolate, and the
+ * interpolator's last frame gives its j = 0 picture.  MIHEVC_EINVAL, decided before any device call: NULL planes, a pitch smaller than the plane, unknown flag
+ * bits, a pts that does not increase.  MIHEVC_ESTATE: no chain set, after flush.  While a chain is set every OTHER entry that sends a frame returns
+ * MIHEVC_ESTATE. */
+int  mihevc_send_frame_chain(mihevc_session *s, const void *y, const void *u, const void *v, int pitch_y, int pitch_c, int64_t pts, int flags);
+/* What chain_plan.h says of a descriptor, without a session or a device: width, height, bit_depth and matrix are the session's cfg fields, sr_scale the scale of
+ * the network (0: none).  MIHEVC_EINVAL for a descriptor mihevc_set_source_chain refuses with it; else rate_num / rate_den, the reduced fraction the chain
+ * multiplies the source's rate by, stages, the slots that are on, pictures, what `frames` frames give once flushed, and the size and depth of every stage. */
+typedef struct mihevc_chain_plan {
+    int32_t rate_num, rate_den;
+    int32_t stages;
+    int32_t reserved;
+    int64_t pictures;
+    int32_t width[4], height[4], bit_depth[4];   /* by slot (field, denoise, resize, interpolate): what the stage runs at, the resize stage: what it writes; 0: off */
+} mihevc_chain_plan;
+int  mihevc_chain_plan_for(const mihevc_chain *chain, int width, int height, int bit_depth, int matrix, int sr_scale, int64_t frames, mihevc_chain_plan *out);
 /* One access unit (Annex-B NAL units) in session-owned memory, valid until the next receive/close. */
 int  mihevc_receive_packet(mihevc_session *s, const uint8_t **data, size_t *size,
                            int64_t *pts, int64_t *dts, int *keyframe);
