@@ -177,24 +177,6 @@ def test_config3_2160p_main10_hdr10_session(lib):
     replay(lib, cfg, frames, infos, recs, 2)
 
 
-def hrd_arrival_schedule(sizes_bits, keys, bit_rate, init_delays_90k, fps):
-    """H.265 C.2.2 (cbr_flag = 0) + C.2.3 for a stream without reordering: picture n is removed at n / fps (the picture timing SEI counts
-    clock ticks since the last buffering period), its first bit may enter the CPB no earlier than its removal time minus the initial delay
-    announced by the LAST buffering period, and never before the previous picture has fully arrived.  Returns the smallest slack
-    (removal time - final arrival time) in seconds: negative = the CPB underflows."""
-    t_af, slack, delay = 0.0, 1e9, init_delays_90k[0] / 90000.0
-    k = 0
-    for n, (bits, key) in enumerate(zip(sizes_bits, keys)):
-        if key:
-            delay = init_delays_90k[min(k, len(init_delays_90k) - 1)] / 90000.0
-            k += 1
-        t_r = init_delays_90k[0] / 90000.0 + n / fps
-        t_ai = max(t_af, t_r - delay)
-        t_af = t_ai + bits / bit_rate
-        slack = min(slack, t_r - t_af)
-    return slack
-
-
 @pytest.mark.parametrize("w,h,bd,keyint,n,maxrate,bufsize", [(640, 352, 8, 30, 150, 600, 720), (416, 240, 10, 20, 130, 400, 480)])
 def test_cpb_schedule_of_the_produced_sizes_never_underflows(lib, w, h, bd, keyint, n, maxrate, bufsize):
     """nal-hrd=vbr:vbv-maxrate:vbv-bufsize (reference core/transcoder.py:399-400): the sizes the session produces, fed through the
@@ -226,7 +208,7 @@ def test_cpb_schedule_of_the_produced_sizes_never_underflows(lib, w, h, bd, keyi
     assert abs(rate - maxrate * 1000) <= 64 and abs(cpb - bufsize * 1000) <= 16
     d0 = info["sei.bp.initial_delay"]
     assert abs(d0 - 90000 * 0.9 * cpb / rate) <= 2
-    slack = hrd_arrival_schedule(sizes, keys, rate, [d0], 30.0)
+    slack = util.hrd_arrival_schedule(sizes, keys, rate, [d0], 30.0)
     assert slack >= 0.0, f"CPB underflow: a picture finishes arriving {-slack * 1e3:.1f} ms after its removal time"
     assert sum(sizes) / (n / 30.0) <= maxrate * 1000, (sum(sizes) / (n / 30.0), maxrate * 1000)
     assert max(sizes) <= 0.9 * cpb
@@ -283,7 +265,7 @@ def test_stress_clip_zoom_fades_flash_and_cut(lib):
     dec, info = O.decode(stream)
     assert len(dec) == n and all(d.same(r) for d, r in zip(dec, recs))
     rate = (info["hrd.bit_rate_value_minus1"] + 1) << (6 + info["hrd.bit_rate_scale"])
-    assert hrd_arrival_schedule(sizes, keys, rate, [info["sei.bp.initial_delay"]], 30.0) >= 0.0
+    assert util.hrd_arrival_schedule(sizes, keys, rate, [info["sei.bp.initial_delay"]], 30.0) >= 0.0
     # four seconds with two forced IDR pictures on top of the periodic ones: the CPB (checked above) is the hard limit, it starts 0.9 full and lends its
     # content once; the mean rate of so short a clip may sit a little above vbv-maxrate (here 301 of 294 kb/s)
     assert sum(sizes) / (n / 30.0) <= 1.05 * maxrate * 1000, (sum(sizes) / (n / 30.0), maxrate * 1000)

@@ -30,12 +30,13 @@ INDEPENDENT = {"hevc_syntax.py": set(), "hevc_recon.py": {"tests.hevc_syntax", "
                "hevc_intra_plan.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref"},    # the intra plan (tests/test_intra_plan_independent.py)
                "hevc_inter_cu.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref", "tests.sdh_ref"},      # the inter CTU program (tests/test_inter_cu_independent.py)
                # the intra code stage, the NxN trial and the intra second pass (tests/test_intra_code_independent.py)
-               "hevc_intra_code.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref", "tests.sdh_ref", "tests.hevc_intra_plan", "tests.hevc_inter_cu"}}
+               "hevc_intra_code.py": {"tests.hevc_recon", "tests.hevc_analysis", "tests.transform_ref", "tests.sdh_ref", "tests.hevc_intra_plan", "tests.hevc_inter_cu"},
+               "ratectl_ref.py": set()}                                        # the rate controller (tests/test_ratectl_cpu.py, tests/test_gpu_ratectl_independent.py)
 
 
 def test_the_reader_imports_only_the_standard_library_and_numpy():
     """tests/hevc_syntax.py, tests/hevc_recon.py (with the stdlib-and-numpy tests/pichash_ref.py it uses), tests/hevc_analysis.py, tests/hevc_intra_plan.py and
-    tests/hevc_inter_cu.py (with tests/transform_ref.py and tests/sdh_ref.py), tests/hevc_intra_code.py (on top of them) and tests/scene_ref.py load nothing of hevc_amd/ or oracle/"""
+    tests/hevc_inter_cu.py (with tests/transform_ref.py and tests/sdh_ref.py), tests/hevc_intra_code.py (on top of them), tests/scene_ref.py and tests/ratectl_ref.py load nothing of hevc_amd/ or oracle/"""
     for module, allowed in INDEPENDENT.items():
         tree = ast.parse((HERE / module).read_text())
         names = set()

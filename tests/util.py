@@ -160,10 +160,10 @@ def psnr(a, b, peak=255.0):
 
 def stepped_library():
     """tests/emu/libkernel_emu.so: the kernel sources stepped on the CPU (a test harness: hevc_amd/ never loads it).  Rebuilt when a harness
-    source or header, a kernel header, the stage argument builders, the GOP planner or the ABI header is newer than the library"""
+    source or header, a kernel header, the stage argument builders, the GOP planner, the rate controller or the ABI header is newer than the library"""
     so = EMU_DIR / "libkernel_emu.so"
     sources = sorted(EMU_DIR.glob("*.cpp"))
-    deps = sources + list(EMU_DIR.glob("*.h")) + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "hevc_amd" / "csrc" / "gop_plan.h", ROOT / "include" / "mihevc.h"]
+    deps = sources + list(EMU_DIR.glob("*.h")) + list((ROOT / "hevc_amd" / "csrc" / "kernels").glob("*.h")) + [ROOT / "hevc_amd" / "csrc" / "stage_args.h", ROOT / "hevc_amd" / "csrc" / "gop_plan.h", ROOT / "hevc_amd" / "csrc" / "ratectl.h", ROOT / "include" / "mihevc.h"]
     if not so.exists() or any(d.stat().st_mtime > so.stat().st_mtime for d in deps):
         tmp = so.with_name(f"libkernel_emu.{os.getpid()}.so")                  # renamed into place: a process that has the old one loaded keeps it
         try:
@@ -330,6 +330,24 @@ def idr_positions(n, keyint, lanes=4, balance=True):
             at += (m // g + (j < m % g)) if balance else keyint
         pos += m
     return out
+
+
+def hrd_arrival_schedule(sizes_bits, keys, bit_rate, init_delays_90k, fps):
+    """H.265 C.2.2 (cbr_flag = 0) + C.2.3 for a stream without reordering: picture n is removed at n / fps (the picture timing SEI counts
+    clock ticks since the last buffering period), its first bit may enter the CPB no earlier than its removal time minus the initial delay
+    announced by the LAST buffering period, and never before the previous picture has fully arrived.  Returns the smallest slack
+    (removal time - final arrival time) in seconds: negative = the CPB underflows."""
+    t_af, slack, delay = 0.0, 1e9, init_delays_90k[0] / 90000.0
+    k = 0
+    for n, (bits, key) in enumerate(zip(sizes_bits, keys)):
+        if key:
+            delay = init_delays_90k[min(k, len(init_delays_90k) - 1)] / 90000.0
+            k += 1
+        t_r = init_delays_90k[0] / 90000.0 + n / fps
+        t_ai = max(t_af, t_r - delay)
+        t_af = t_ai + bits / bit_rate
+        slack = min(slack, t_r - t_af)
+    return slack
 
 
 # ================================================================ cases of the decision audit (tests/test_analysis_independent.py on the CPU, tests/test_gpu_analysis_independent.py on the device)
